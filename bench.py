@@ -19,6 +19,9 @@ Multi-GPU on one GPU: `--force-dist` initialises the RCCL process group even at 
 `--emulate-rank r --emulate-world W` runs rank r's shard of the W-GPU job (e.g. configs[4]: hil_music,
 2048 clips over 8 GPUs) in a single process — a shard check, not a scaling measurement.
 
+`--dump-outputs DIR` writes what the last timed step returned (RVQ indices, decoded waveform) as float32 .npy files; the inputs
+and weights are seeded, so two builds run with the same arguments can be compared output for output.
+
 Prints ONE JSON line (rank 0) with
   roofline     — dominant kernel = the fp32-MFMA GEMM core (pointwise convs and everything fused
                  onto them), every launch timed with HIP events on the launch stream INSIDE the timed
@@ -75,9 +78,14 @@ def parse():
     ap.add_argument("--force-dist", action="store_true", help="initialise the RCCL process group even at world size 1")
     ap.add_argument("--emulate-rank", type=int, default=None, help="with --emulate-world W: run rank r's shard of the W-GPU job in this one process")
     ap.add_argument("--emulate-world", type=int, default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step returned "
+                    "(RVQ indices and decoded waveform) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed seeded sample of "
+                    "clips / streams beyond that); ranks > 0 add _rank<r> to the names")
     a = ap.parse_args()
     a.is_default = (a.model is None and a.mode == "offline" and a.batch is None and a.samples == 24000 and a.gpus == 1
                     and a.emulate_world is None and not a.exec_opt)
+    if (a.steps is not None and a.steps < 1) or (a.warmup is not None and a.warmup < 0):
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if (a.emulate_rank is None) != (a.emulate_world is None):
         ap.error("--emulate-rank and --emulate-world go together")
     if a.emulate_world is not None and not 0 <= a.emulate_rank < a.emulate_world:
@@ -354,6 +362,31 @@ def timed_region(step, steps: int, warmup: int, D, launch_timing: bool):
     return dt, idx, wav, timer
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict, suffix: str = "", limit: int = DUMP_LIMIT_BYTES, seed: int = 0) -> dict:
+    """Writes `arrays` ({name: (tensor, batch axis)}, all with the same batch) as out_dir/<name><suffix>.npy in float32 (indices are
+    < 2^24, exact).  Beyond `limit` bytes in all, the same fixed, seeded sample of batch rows is kept of every array."""
+    import numpy as np
+    host = {k: (t.detach().to("cpu", torch.float32).numpy(), ax) for k, (t, ax) in arrays.items() if t is not None}
+    batch = {a.shape[ax] for a, ax in host.values()}
+    assert len(batch) == 1, batch
+    batch = batch.pop()
+    total = sum(a.nbytes for a, _ in host.values())
+    rows = None
+    if total > limit:
+        keep = max(1, batch * limit // total)
+        rows = np.sort(np.random.default_rng(seed).choice(batch, keep, replace=False))
+        host = {k: (np.take(a, rows, axis=ax), ax) for k, (a, ax) in host.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, (a, _) in host.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "arrays": {k + suffix: list(a.shape) for k, (a, _) in host.items()}, "dtype": "float32",
+            "bytes": sum(a.nbytes for a, _ in host.values()),
+            "rows": "all" if rows is None else f"{len(rows)} of {batch}, numpy default_rng({seed}).choice, sorted"}
+
+
 def other_config_lines(dev, D, clips: int = 256, streams: int = 1024, census_clips: int = 0):
     """Short, separately reported runs of BASELINE configs[2] and configs[3] (never part of `value`): the driver sees them in
     the one JSON line of the default invocation."""
@@ -437,6 +470,12 @@ def main():
             ctx["hopper"] = ctx["make_hopper"]()                 # captured with the defaults: capture again
 
     dt, idx, wav, timer = timed_region(step, args.steps, args.warmup, D, not args.no_launch_timing)
+    dumped = None
+    if args.dump_outputs:
+        # at once: a graph replay returns its static buffers, which the steps after the timed region overwrite
+        torch.cuda.synchronize()
+        dumped = dump_outputs(args.dump_outputs, {"indices": (idx, 0 if args.mode == "offline" else 1), "wav": (wav, 0)},
+                              "" if rank == 0 else f"_rank{rank}")
 
     per_rank = D.gather_counters({"clips": float((hi - lo) * args.steps), "audio_s": audio_per_step * args.steps,
                                   "wall_s": dt, "index_checksum": float(idx.sum().item())}, dev)   # the data path has NO collective: this gathers the counters (a second gather below carries each rank's clock / power)
@@ -482,6 +521,8 @@ def main():
                       "wall_skew_s": max(r["wall_s"] for r in per_rank) - min(r["wall_s"] for r in per_rank)},
             "build": {"csrc_sha16": _lib.source_hash(), "abi": _lib.ABI_VERSION},
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         whole_tflops = value * FLOP_PER_AUDIO_SECOND[name] / 1e12 / world
         roof = {"bound": "mfma", "achieved": None, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": None,
                 "traffic": None, "whole_path_tflops_per_gpu": whole_tflops,

@@ -276,6 +276,8 @@ def main():
     shard_golden(ref)
     for fname, scale in WS_GOLDENS:
         ws_golden(ref, fname, scale)
+    vs_reference_golden(ref)
+    onnx_files_golden()
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("golden bytes:", tot)
 
@@ -448,6 +450,159 @@ def trained_codebook_golden(ref):
     print("trained dequantizer KAT:", q.shape, float(q.abs().mean()))
 
 
+def sha(t) -> str:
+    """sha256 of a tensor's bytes: a bit-exact fingerprint of the tensors too large to store (codebooks, caches)."""
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(t2n(t)).tobytes()).hexdigest()
+
+
+def vs_reference_golden(ref):
+    """The reference's side of tests/test_oracle_vs_reference.py (its seeds and shapes, not those of the other goldens) and
+    the reference's constructor signatures for tests/test_api_cpu.py.  Small outputs are stored whole, codebooks and
+    streaming caches as sha256 fingerprints."""
+    import inspect
+    import json
+    import yaml
+    out = {}
+    meta = {"state_dict_shapes": {}, "n_params": {}, "yaml_model_kwargs": {}}
+    for name, f in (("hil_speech", "hilcodec_speech.yaml"), ("hil_music", "hilcodec_music.yaml")):
+        mk = synth.model_kwargs(name)
+        model = ref.OfflineHILCodec(sample_rate=24000, channels_audio=1, **copy.deepcopy(mk))
+        meta["state_dict_shapes"][name] = [[k, list(v.shape)] for k, v in model.state_dict().items() if hasattr(v, "shape")]
+        meta["n_params"][name] = sum(p.numel() for p in model.parameters())
+        with open(os.path.join(R.REFERENCE_ROOT, "configs", f)) as fh:
+            meta["yaml_model_kwargs"][name] = yaml.safe_load(fh)["model_kwargs"]
+    # tests/test_api_cpu.py::test_legacy_rvq_matches_reference_constructor_and_state_dict
+    sig = {}
+    for cls in ("EuclideanCodebook", "VectorQuantize", "ResidualVQ"):
+        ps = inspect.signature(getattr(ref.vq_old, cls).__init__).parameters
+        sig[cls] = [[k, v.default is not inspect.Parameter.empty, None if v.default is inspect.Parameter.empty else v.default]
+                    for k, v in ps.items()]
+    sig["VectorQuantize.forward"] = list(inspect.signature(ref.vq_old.VectorQuantize.forward).parameters)
+    meta["legacy_vq_signatures"] = sig
+    kw = dict(num_quantizers=3, dropout=True, dropout_index=[1, 3], dim=16, codebook_size=32, kmeans_init=False,
+              kmeans_iters=20, decay=0.9, eps=1e-7, ema_num_threshold=0.5, ema_num_initial=2.0, commitment=0.25,
+              channel_last=False)
+    meta["legacy_vq_state_dict_shapes"] = [[k, list(v.shape)] for k, v in ref.vq_old.ResidualVQ(**kw).state_dict().items()]
+
+    for name, seed, T in (("hil_speech", 3, 6400), ("hil_music", 5, 3333)):
+        mk = synth.model_kwargs(name)
+        model = R.build_offline(ref, mk, synth.synth_state_dict(name, seed=seed))
+        x = synth.synth_clips(2, T, seed=seed * 11)
+        with torch.no_grad():
+            z = model.encoder(x.clone())
+            q, nr, loss, idx = model.quantizer(z, None, return_indices=True)
+            wav = model.decoder(q)
+        p = f"offline_{name}_"
+        out.update({p + "z": t2n(z), p + "indices": t2n(idx).astype(np.int16), p + "wav": t2n(wav), p + "loss": t2n(loss),
+                    p + "num_replaces": np.asarray(nr)})
+
+    mk = synth.model_kwargs("hil_speech")
+    model = R.build_offline(ref, mk, synth.synth_state_dict("hil_speech", seed=13))
+    sm = R.build_streaming(ref, mk, model)
+    x = synth.synth_clips(2, 1600, seed=77)
+    ce, cd = sm.initialize_cache(x)
+    meta["stream_cache_shapes"] = {"enc": [list(c.shape) for c in ce], "dec": [list(c.shape) for c in cd]}
+    meta["stream_cache_sha"] = []
+    zs, idxs, wavs = [], [], []
+    with torch.no_grad():
+        for h in range(0, 1600, 320):
+            zr, ce = sm.encoder(x[:, :, h:h + 320], *ce)
+            ir = sm.quantizer(zr, 8)
+            wr, cd = sm.decoder(sm.dequantizer(ir, 8), *cd)
+            zs.append(t2n(zr))
+            idxs.append(t2n(ir).astype(np.int16))
+            wavs.append(t2n(wr))
+            meta["stream_cache_sha"].append({"enc": [sha(c) for c in ce], "dec": [sha(c) for c in cd]})
+    out.update(stream_z=np.stack(zs), stream_indices=np.stack(idxs), stream_wav=np.stack(wavs))
+
+    D, K, nq = 128, 1024, 4
+    old = ref.vq_old.ResidualVQ(num_quantizers=nq, dropout=False, dim=D, codebook_size=K, kmeans_init=False).eval()
+    for i in range(nq):
+        old.layers[i]._codebook.embed.copy_(torch.from_numpy(synth.normalish(500 + i, K * D) * np.float32(0.3)).view(K, D))
+    z = torch.from_numpy(synth.normalish(9, 3 * D * 20)).view(3, D, 20)
+    with torch.no_grad():
+        q, nr, loss = old(z, 3)
+    out.update(legacy_q=t2n(q), legacy_num_replaces=np.asarray(nr), legacy_loss=t2n(loss))
+
+    def train_trace(key, rvq, codebook, seed0, with_indices):
+        """three train-mode steps: outputs per step, ema_num whole, embed / ema_embed as fingerprints"""
+        meta[key + "_sha"] = []
+        qs, losses, idxs, ema_nums = [], [], [], []
+        for step in range(3):
+            z = torch.from_numpy(synth.normalish(seed0 + step, 2 * D * 40)).view(2, D, 40)
+            if with_indices:
+                q, _, loss, idx = rvq(z, 2, return_indices=True)
+                idxs.append(t2n(idx).astype(np.int16))
+            else:
+                q, _, loss = rvq(z, 2)
+            qs.append(t2n(q))
+            losses.append(t2n(loss))
+            cbs = [codebook(rvq, i) for i in range(3)]
+            ema_nums.append(np.stack([t2n(c.ema_num) for c in cbs]))
+            meta[key + "_sha"].append({"embed": [sha(c.embed) for c in cbs], "ema_embed": [sha(c.ema_embed) for c in cbs]})
+        out.update({key + "_q": np.stack(qs), key + "_loss": np.stack(losses), key + "_ema_num": np.stack(ema_nums)})
+        if with_indices:
+            out[key + "_indices"] = np.stack(idxs)
+
+    decay, init = 0.9, 0.5
+    rvq = ref.vq_new.ResidualVQ(num_quantizers=3, dropout=False, channel_last=False, dim=D, codebook_size=K,
+                                kmeans_init=False, decay=decay, ema_num_threshold=0.0, ema_num_initial=init).train()
+    for i in range(3):
+        e = torch.from_numpy(synth.normalish(800 + i, K * D) * np.float32(0.3)).view(K, D)
+        rvq.layers[i].embed.copy_(e)
+        rvq.layers[i].ema_embed.copy_(e * init)
+    train_trace("train", rvq, lambda m, i: m.layers[i], 70, True)
+    rvq = ref.vq_old.ResidualVQ(num_quantizers=3, dropout=False, dim=D, codebook_size=K, kmeans_init=False,
+                                decay=decay, ema_num_threshold=0.0, ema_num_initial=init).train()
+    for i in range(3):
+        e = torch.from_numpy(synth.normalish(820 + i, K * D) * np.float32(0.3)).view(K, D)
+        rvq.layers[i]._codebook.embed.copy_(e)
+        rvq.layers[i]._codebook.ema_embed.copy_(e * init)
+    train_trace("legacy_train", rvq, lambda m, i: m.layers[i]._codebook, 75, False)
+
+    out["meta_json"] = np.array(json.dumps(meta))
+    np.savez_compressed(os.path.join(OUT, "vs_reference.npz"), **out)
+    print("vs_reference:", {k: v.shape for k, v in out.items()})
+
+
+def onnx_files_golden():
+    """The reference's shipped streaming-driver files (`onnx/`), rebuildable byte for byte from a few KB: every ONNX
+    codebook file is a small frame around its `embed` table (and, in the `vq` graphs, the same table transposed).  The
+    frame is stored with the offsets of the tables taken out; hil_speech's tables are realistic.npz's `codebooks`,
+    hil_music's first and last are stored here.  sha256 of every original file is kept to prove the rebuild exact."""
+    import hashlib
+    from hilcodec_amd import wire
+    onnx_dir = os.path.join(R.REFERENCE_ROOT, "onnx")
+    out = {}
+    for f in ("hil_speech_cache_enc.npz", "hil_speech_cache_dec.npz", "hil_speech_quantized.npy"):
+        with open(os.path.join(onnx_dir, f), "rb") as fh:
+            out["file:" + f] = np.frombuffer(fh.read(), dtype=np.uint8)
+    for name, n in (("hil_speech", 8), ("hil_music", 12)):
+        for i in (0, n - 1):
+            for kind in ("deq", "vq"):
+                fname = f"{name}_{kind}{i}.onnx"
+                with open(os.path.join(onnx_dir, fname), "rb") as fh:
+                    raw = fh.read()
+                e = wire.read_onnx_codebook(os.path.join(onnx_dir, fname)).numpy()
+                frame, spans, pos = b"", [], 0
+                for table, code in ((e, 0), (np.ascontiguousarray(e.T), 1)):
+                    at = raw.find(table.tobytes(), pos)
+                    if at < 0:
+                        continue
+                    frame += raw[pos:at]
+                    spans.append((len(frame), code))
+                    pos = at + table.nbytes
+                frame += raw[pos:]
+                out["frame:" + fname] = np.frombuffer(frame, dtype=np.uint8)
+                out["spans:" + fname] = np.array(spans, dtype=np.int64)
+                out["sha256:" + fname] = np.array(hashlib.sha256(raw).hexdigest())
+                if name == "hil_music" and kind == "deq":
+                    out[f"codebook:{name}:{i}"] = e
+    np.savez_compressed(os.path.join(OUT, "reference_files.npz"), **out)
+    print("reference_files:", sorted(out))
+
+
 if __name__ == "__main__":
     if "--trained" in sys.argv:
         os.makedirs(OUT, exist_ok=True)
@@ -466,5 +621,11 @@ if __name__ == "__main__":
     elif "--rvq-train" in sys.argv:
         os.makedirs(OUT, exist_ok=True)
         rvq_train_golden(R.load_reference())
+    elif "--vs-reference" in sys.argv:
+        os.makedirs(OUT, exist_ok=True)
+        vs_reference_golden(R.load_reference())
+    elif "--reference-files" in sys.argv:
+        os.makedirs(OUT, exist_ok=True)
+        onnx_files_golden()
     else:
         main()

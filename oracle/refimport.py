@@ -1,8 +1,8 @@
 """Import shim for the real reference (aask1357/hilcodec at /root/reference) — BUILD CONTAINER ONLY.
 
-Test infrastructure: used by `oracle/make_golden.py` and `tests/test_oracle_vs_reference.py` to run
-the reference's own PyTorch modules on CPU.  `/root/reference` does not exist on the GPU box, so
-everything that calls `load_reference()` is skipped there; nothing in the product imports this.
+Golden-vector infrastructure: used by `oracle/make_golden.py` to run the reference's own PyTorch modules
+on CPU; the tests read only what it stored under `tests/golden/`.  Nothing in the product or the test
+suite imports this.
 
 The reference's package `__init__` files pull in trainer-only third-party modules that are not
 installed here (librosa, torchaudio, tensorboard, pesq, pystoi, soundfile); they are stubbed in

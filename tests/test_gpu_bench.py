@@ -127,3 +127,22 @@ def test_emulated_rank_line_and_shard_checksums():
         assert torch.equal(idx, idx_all[lo:hi])                     # a shard computes exactly its clips of the global batch
         sums.append(int(idx.sum()))
     assert sum(sums) == int(idx_all.sum()) and sums[7] == d["index_checksum"]
+
+
+@pytest.mark.parametrize("extra", [(), ("--mode", "streaming", "--graph", "--pipeline")])
+def test_dump_outputs_are_the_last_timed_step(tmp_path, extra):
+    """--dump-outputs: the indices and waveform of the last timed step as float32 .npy (graph replays return static buffers that
+    later steps overwrite: the dump's indices must still sum to the line's index_checksum), identical inputs run to run."""
+    import numpy as np
+    args = ("--batch", "8", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-clock-probe", "--no-launch-timing") + extra
+    runs = []
+    for k in range(2):
+        d = run_bench(*args, "--dump-outputs", str(tmp_path / str(k)))
+        assert d["steps"] == 3 and d["dump_outputs"]["rows"] == "all"
+        out = {n: np.load(tmp_path / str(k) / f"{n}.npy") for n in ("indices", "wav")}
+        assert all(a.dtype == np.float32 and list(a.shape) == d["dump_outputs"]["arrays"][n] for n, a in out.items())
+        assert int(out["indices"].astype(np.float64).sum()) == d["index_checksum"]
+        assert np.isfinite(out["wav"]).all() and out["wav"].shape[0] == 8
+        runs.append(out)
+    assert np.array_equal(runs[0]["indices"], runs[1]["indices"])
+    assert np.abs(runs[0]["wav"] - runs[1]["wav"]).max() < 1e-6

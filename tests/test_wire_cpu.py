@@ -8,8 +8,6 @@ import torch
 
 from hilcodec_amd import synth, wire
 
-REF_ONNX = "/root/reference/onnx"
-
 
 def test_index_npy_roundtrip(tmp_path):
     idx = torch.randint(0, 1024, (8, 3, 17), generator=torch.Generator().manual_seed(11))
@@ -52,20 +50,46 @@ def test_cache_npz_roundtrip(tmp_path):
         wire.load_cache_npz(p, "d_in")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_ONNX), reason="reference checkout not present")
-def test_against_reference_shipped_files():
+def _reference_files(golden, out_dir):
+    """The reference's shipped `onnx/` files this test reads, rebuilt byte for byte from tests/golden/reference_files.npz
+    (`python oracle/make_golden.py --reference-files`): each ONNX file is its stored frame with the codebook (span code 0)
+    and its transpose (span code 1) put back; hil_speech's codebooks are realistic.npz's.  Checked against the sha256 of
+    the shipped file."""
+    import hashlib
+    g = golden("reference_files")
+    speech = golden("realistic")["codebooks"]
+    for key, blob in g.items():
+        if key.startswith("file:"):
+            (out_dir / key[5:]).write_bytes(blob.tobytes())
+        elif key.startswith("frame:"):
+            fname = key[6:]
+            name, kind_i = fname[:-5].rsplit("_", 1)
+            i = int(kind_i.lstrip("deqv"))
+            e = speech[i] if name == "hil_speech" else g[f"codebook:{name}:{i}"]
+            frame, raw, pos = blob.tobytes(), b"", 0
+            for at, code in g["spans:" + fname]:
+                raw += frame[pos:at] + (e if code == 0 else np.ascontiguousarray(e.T)).tobytes()
+                pos = at
+            raw += frame[pos:]
+            assert hashlib.sha256(raw).hexdigest() == str(g["sha256:" + fname]), fname
+            (out_dir / fname).write_bytes(raw)
+    return str(out_dir)
+
+
+def test_against_reference_shipped_files(golden, tmp_path):
     from oracle import hilcodec_oracle as O
+    ref_onnx = _reference_files(golden, tmp_path)
     enc_shapes, dec_shapes = O.stream_cache_shapes(synth.model_kwargs("hil_speech"))
-    e = wire.load_cache_npz(os.path.join(REF_ONNX, "hil_speech_cache_enc.npz"), "e_in")
-    d = wire.load_cache_npz(os.path.join(REF_ONNX, "hil_speech_cache_dec.npz"), "d_in")
+    e = wire.load_cache_npz(os.path.join(ref_onnx, "hil_speech_cache_enc.npz"), "e_in")
+    d = wire.load_cache_npz(os.path.join(ref_onnx, "hil_speech_cache_dec.npz"), "d_in")
     assert [tuple(c.shape) for c in e] == [(1, c, l) for c, l in enc_shapes] and not any(c.any() for c in e)
     assert [tuple(c.shape) for c in d] == [(1, c, l) for c, l in dec_shapes]
-    q = wire.load_indices_npy(os.path.join(REF_ONNX, "hil_speech_quantized.npy"))
+    q = wire.load_indices_npy(os.path.join(ref_onnx, "hil_speech_quantized.npy"))
     assert q.shape == (8, 1, 2296) and int(q.min()) >= 0 and int(q.max()) <= 1023
     for name, n in (("hil_speech", 8), ("hil_music", 12)):
         for i in (0, n - 1):
-            cb = wire.read_onnx_codebook(os.path.join(REF_ONNX, f"{name}_deq{i}.onnx"))
-            vq = wire.read_onnx_codebook(os.path.join(REF_ONNX, f"{name}_vq{i}.onnx"))
+            cb = wire.read_onnx_codebook(os.path.join(ref_onnx, f"{name}_deq{i}.onnx"))
+            vq = wire.read_onnx_codebook(os.path.join(ref_onnx, f"{name}_vq{i}.onnx"))
             assert cb.shape == (1024, 128) and torch.isfinite(cb).all() and torch.equal(cb, vq)
 
 
