@@ -67,9 +67,11 @@ SIGNATURES = {
     "hilc_rvq_ema_stats": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "hilc_rvq_ema_update": [_p, _p, _p, _p, _d, _i, _i, _i, _p],
     "hilc_rvq_decode_mixed": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "hilc_state_slots_apply": [_p, _p, _p, _i, _i, _p, _p, _i, _p],
+    "hilc_state_slots_gather": [_p, _p, _p, _i, _i, _p, _i, _p, _p],
 }
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 def source_hash() -> str:

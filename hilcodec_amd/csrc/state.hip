@@ -1,0 +1,221 @@
+// Per-stream sessions of a graphed streaming hop: zero one stream's caches, load them from a staged record, or gather
+// them into a record, inside the state block (hilcodec_amd/graph_step.py StateBlock: slice k of stream b at
+// block + slice_off[k] + b * slice_len[k]).  A record is one stream's slices concatenated in slice order.
+//
+// hilc_state_slots_apply runs at the head of every hop and almost always has nothing to do, so the idle case decides
+// its form: a fixed grid of APPLY_WGS workgroups, each of which reads the whole `action` array (1024 streams = 4 loads
+// per thread, L2-resident) and leaves after one barrier when no entry is active.  When some are, every workgroup
+// builds the same list of active streams in LDS (ballot order, deterministic) and the (stream, piece) work items of
+// that list are spread over the whole grid: one stream's 306 KB are copied by up to 19 workgroups side by side
+// instead of one workgroup's latency-bound loop; each item finds its slices in an LDS copy of the slice table.  (One workgroup per stream that exits on action[b] == 0 would issue
+// 1024 workgroups per idle hop and still copy a resumed stream through a single workgroup.)
+#include "common.h"
+
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int PASS = 4 * THREADS;   // streams scanned per pass: the LDS list holds the active streams of one pass
+constexpr int PIECE = 4096;         // floats of a record per work item: 16 per thread, one round of loads (19 items per stream)
+constexpr int APPLY_WGS = 256;      // one per CU
+constexpr int GATHER_WGS = 256;
+
+constexpr int MAX_SLICES = 128;     // the slice table lives in LDS (52 slices for the shipped models)
+
+struct Layout {
+  const int64_t* off;
+  const int* len;
+  int nslices;
+};
+
+// the slice table in LDS, with the record offset of every slice (pre[k] = sum of len[0..k)): a work item finds its slices with
+// a binary search over LDS instead of a walk of dependent scalar loads (one L2 round trip per slice: 26 us for a resumed stream)
+struct Table {
+  int64_t off[MAX_SLICES];
+  int64_t pre[MAX_SLICES + 1];
+  int len[MAX_SLICES];
+};
+
+__device__ __forceinline__ void load_table(Table& tb, const Layout& L) {
+  const int t = threadIdx.x;
+  for (int k = t; k < L.nslices; k += THREADS) {
+    tb.off[k] = L.off[k];
+    tb.len[k] = L.len[k];
+  }
+  if (t < 64) {                            // wave 0: pre[] by an inclusive wave scan, 64 slices per step
+    const int lane = t;
+    long carry = 0;
+    for (int base = 0; base < L.nslices; base += 64) {
+      const int k = base + lane;
+      long v = k < L.nslices ? (long)L.len[k] : 0;
+      for (int d = 1; d < 64; d <<= 1) {
+        const long u = __shfl_up(v, d);
+        if (lane >= d) v += u;
+      }
+      if (k < L.nslices) tb.pre[k + 1] = carry + v;
+      carry += __shfl(v, 63);
+    }
+    if (lane == 0) tb.pre[0] = 0;
+  }
+  __syncthreads();
+}
+
+// dst[0..n) = src[0..n), or zeros when src == nullptr; n <= PIECE; every thread of the workgroup takes part.
+// 16-byte vectors only where both addresses are 16-B aligned and n is a multiple of 4 (the per-stream slices of the
+// [1, 1023] waveform history, and every slice of a record behind it, are not): dwords otherwise.
+__device__ __forceinline__ void move(float* __restrict__ dst, const float* __restrict__ src, int n) {
+  const int t = threadIdx.x;
+  if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15) == 0 && (n & 3) == 0) {
+    const int n4 = n >> 2;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    f32x4 v[PIECE / 4 / THREADS];
+#pragma unroll
+    for (int i = 0; i < PIECE / 4 / THREADS; ++i) {
+      const int j = t + i * THREADS;
+      v[i] = src != nullptr && j < n4 ? reinterpret_cast<const f32x4*>(src)[j] : z;
+    }
+#pragma unroll
+    for (int i = 0; i < PIECE / 4 / THREADS; ++i) {
+      const int j = t + i * THREADS;
+      if (j < n4) reinterpret_cast<f32x4*>(dst)[j] = v[i];
+    }
+  } else {
+    float v[PIECE / THREADS];
+#pragma unroll
+    for (int i = 0; i < PIECE / THREADS; ++i) {
+      const int j = t + i * THREADS;
+      v[i] = src != nullptr && j < n ? src[j] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < PIECE / THREADS; ++i) {
+      const int j = t + i * THREADS;
+      if (j < n) dst[j] = v[i];
+    }
+  }
+}
+
+// record floats [p0, p1) of stream b: TO_BLOCK = record -> block (rec == nullptr: zeros), else block -> record
+template <bool TO_BLOCK>
+__device__ void move_piece(float* block, const Table& tb, int nslices, long b, float* rec, long p0, long p1) {
+  int lo = 0, hi = nslices - 1;            // the last slice with pre[k] <= p0
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tb.pre[mid] <= p0) lo = mid; else hi = mid - 1;
+  }
+  for (int k = lo; k < nslices && tb.pre[k] < p1; ++k) {
+    const long pre = tb.pre[k], len = tb.len[k];
+    const long a = p0 > pre ? p0 : pre;
+    const long e = p1 < pre + len ? p1 : pre + len;
+    if (e > a) {
+      float* slot = block + tb.off[k] + b * len + (a - pre);
+      if (TO_BLOCK)
+        move(slot, rec != nullptr ? rec + a : nullptr, (int)(e - a));
+      else
+        move(rec + a, slot, (int)(e - a));
+    }
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void state_apply_kernel(float* block, Layout L, int streams, const int* action,
+                                                              const float* records, int nrecords) {
+  __shared__ int list_b[PASS], list_a[PASS];
+  __shared__ int cnt[4][THREADS / 64];
+  __shared__ Table tb;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  long reclen = -1, npieces = 0;
+  for (int base = 0; base < streams; base += PASS) {
+    int act[4];
+    bool ok[4], any = false;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int b = base + i * THREADS + t;
+      act[i] = b < streams ? action[b] : 0;
+      ok[i] = act[i] == -1 || (act[i] >= 1 && act[i] <= nrecords);    // anything else: keep
+      any |= ok[i];
+    }
+    if (!__syncthreads_or(any)) continue;                              // the idle hop ends here
+    uint64_t m[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      m[i] = __ballot(ok[i]);
+      if (lane == 0) cnt[i][wave] = __popcll(m[i]);
+    }
+    __syncthreads();
+    int run = 0, pos[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      for (int w = 0; w < THREADS / 64; ++w) {
+        if (w == wave) pos[i] = run;
+        run += cnt[i][w];
+      }
+    const uint64_t lt = __lanemask_lt();
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (ok[i]) {
+        const int p = pos[i] + __popcll(m[i] & lt);
+        list_b[p] = base + i * THREADS + t;
+        list_a[p] = act[i];
+      }
+    __syncthreads();
+    if (reclen < 0) {
+      load_table(tb, L);
+      reclen = tb.pre[L.nslices];
+      npieces = (reclen + PIECE - 1) / PIECE;
+    }
+    const long items = (long)run * npieces;
+    for (long it = blockIdx.x; it < items; it += gridDim.x) {
+      const int j = (int)(it / npieces);
+      const long p0 = (it % npieces) * PIECE;
+      const long p1 = p0 + PIECE < reclen ? p0 + PIECE : reclen;
+      const int b = __builtin_amdgcn_readfirstlane(list_b[j]);
+      const int a = __builtin_amdgcn_readfirstlane(list_a[j]);
+      float* rec = a > 0 ? const_cast<float*>(records) + (long)(a - 1) * reclen : nullptr;
+      move_piece<true>(block, tb, L.nslices, b, rec, p0, p1);
+    }
+    __syncthreads();                                                   // the next pass rewrites the list
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void state_gather_kernel(const float* block, Layout L, int streams, const int* slots,
+                                                               int nslots, float* records) {
+  __shared__ Table tb;
+  load_table(tb, L);
+  const long reclen = tb.pre[L.nslices];
+  const long npieces = (reclen + PIECE - 1) / PIECE;
+  const long items = (long)nslots * npieces;
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const int j = (int)(it / npieces);
+    const long p0 = (it % npieces) * PIECE;
+    const long p1 = p0 + PIECE < reclen ? p0 + PIECE : reclen;
+    const int b = __builtin_amdgcn_readfirstlane(slots[j]);
+    if (b < 0 || b >= streams) continue;                               // record i left as it was
+    move_piece<false>(const_cast<float*>(block), tb, L.nslices, b, records + (long)j * reclen, p0, p1);
+  }
+}
+
+}  // namespace
+
+extern "C" int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices,
+                                      int streams, const int* action, const float* records, int nrecords, void* stream) {
+  if (!block || !slice_off || !slice_len || !action || (!records && nrecords > 0)) return HILC_ERR_NULL;
+  if (nslices <= 0 || streams <= 0 || nrecords < 0) return HILC_ERR_SHAPE;
+  if (nslices > MAX_SLICES) return HILC_ERR_UNSUPPORTED;
+  const Layout L = {slice_off, slice_len, nslices};
+  HILC_CLEAR_ERROR();
+  hipLaunchKernelGGL(state_apply_kernel, dim3(APPLY_WGS), dim3(THREADS), 0, (hipStream_t)stream, block, L, streams, action,
+                     records, nrecords);
+  HILC_CHECK_LAUNCH();
+  return HILC_OK;
+}
+
+extern "C" int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices,
+                                       int streams, const int* slots, int nslots, float* records, void* stream) {
+  if (!block || !slice_off || !slice_len || !slots || !records) return HILC_ERR_NULL;
+  if (nslices <= 0 || streams <= 0 || nslots <= 0) return HILC_ERR_SHAPE;
+  if (nslices > MAX_SLICES) return HILC_ERR_UNSUPPORTED;
+  const Layout L = {slice_off, slice_len, nslices};
+  HILC_CLEAR_ERROR();
+  hipLaunchKernelGGL(state_gather_kernel, dim3(GATHER_WGS), dim3(THREADS), 0, (hipStream_t)stream, block, L, streams, slots,
+                     nslots, records);
+  HILC_CHECK_LAUNCH();
+  return HILC_OK;
+}

@@ -31,29 +31,74 @@ def _spectra_on(encoder, stream: Optional[torch.cuda.Stream]):
     return engine.spectra_side_stream(stream)
 
 
+def state_layout(model, batch: int) -> ops.StateLayout:
+    """the layout of a state block of `batch` streams of `model` (host-only: the cache shapes come from a CPU probe)"""
+    ce, cd = model.initialize_cache(torch.zeros(1, 1, 1))
+    return ops.StateLayout([(batch,) + tuple(c.shape[1:]) for c in list(ce) + list(cd)], len(ce))
+
+
+class SessionQueue:
+    """Host side of GraphedHop's per-stream sessions: what the next hop does to which slot, checked here before anything is
+    launched (no device).  `starts[slot]` = None (fresh zeros) or the slot's record; `n[slot]` = its new number of quantiser
+    stages.  A later call for the same slot replaces an earlier one of the same hop; `start` without `n` resets the slot to
+    `n_max`, the graph's default."""
+
+    def __init__(self, batch: int, n_max: int, max_loads: int, layout: ops.StateLayout):
+        self.batch, self.n_max, self.max_loads, self.layout = int(batch), int(n_max), int(max_loads), layout
+        self.starts = {}
+        self.n = {}
+
+    def slot(self, slot) -> int:
+        s = int(slot)
+        if not 0 <= s < self.batch:
+            raise IndexError(f"slot {slot} outside [0, {self.batch})")
+        return s
+
+    def check_n(self, n) -> int:
+        v = int(n)
+        if not 1 <= v <= self.n_max:
+            raise ValueError(f"n = {n} outside [1, {self.n_max}] (the graph's n is the maximum)")
+        return v
+
+    @property
+    def loads(self) -> int:
+        return sum(r is not None for r in self.starts.values())
+
+    @property
+    def pending(self) -> bool:
+        return bool(self.starts or self.n)
+
+    def start(self, slot, cache_enc=None, cache_dec=None, n=None) -> None:
+        s = self.slot(slot)
+        v = self.n_max if n is None else self.check_n(n)
+        rec = None
+        if cache_enc is not None or cache_dec is not None:
+            if cache_enc is None or cache_dec is None:
+                raise ValueError("start: give both cache lists (encoder and decoder) or neither")
+            rec = self.layout.record(cache_enc, cache_dec)
+            if self.starts.get(s) is None and self.loads >= self.max_loads:
+                raise RuntimeError(f"start: more than {self.max_loads} loads queued for one hop (max_loads_per_hop)")
+        self.starts[s] = rec
+        self.n[s] = v
+
+    def set_bitrate(self, slot, n) -> None:
+        s = self.slot(slot)
+        self.n[s] = self.check_n(n)
+
+    def clear(self) -> None:
+        self.starts.clear()
+        self.n.clear()
+
+
 class StateBlock:
     """The 22 + 30 caches of `batch` streams as views into ONE contiguous fp32 buffer (16-B aligned slices)."""
 
     def __init__(self, model, batch: int, device: torch.device):
-        probe = torch.zeros(batch, 1, 1, device=device)
-        ce, cd = model.initialize_cache(probe)
-        shapes = [tuple(c.shape) for c in list(ce) + list(cd)]
-        offs, total = [], 0
-        for s in shapes:
-            offs.append(total)
-            n = 1
-            for d in s:
-                n *= d
-            total += (n + 3) // 4 * 4
-        self.buffer = torch.zeros(total, device=device, dtype=torch.float32)
-        views = []
-        for s, o in zip(shapes, offs):
-            n = 1
-            for d in s:
-                n *= d
-            views.append(self.buffer[o:o + n].view(s))
-        self.enc: List[Tensor] = views[:len(ce)]
-        self.dec: List[Tensor] = views[len(ce):]
+        self.layout = state_layout(model, batch)
+        self.buffer = torch.zeros(self.layout.total, device=device, dtype=torch.float32)
+        views = [self.buffer[o:o + s[0] * n].view(s) for s, o, n in zip(self.layout.shapes, self.layout.off, self.layout.lens)]
+        self.enc: List[Tensor] = views[:self.layout.n_enc]
+        self.dec: List[Tensor] = views[self.layout.n_enc:]
 
     def zero_(self) -> None:
         self.buffer.zero_()
@@ -77,9 +122,18 @@ class GraphedHop:
     runs the groups' chains (encoder -> RVQ -> dequantiser -> decoder) side by side on separate HIP streams.  Streams are
     independent, so this is the same arithmetic on the same data — outputs bit-identical to `groups=1`, NO added latency
     (unlike PipelinedHop) — but every launch of a hop covers the chip only 1.3-4 times at 1024 streams, and two or more
-    independent chains fill each other's partly-filled last rounds."""
+    independent chains fill each other's partly-filled last rounds.
 
-    def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, groups: int = 1):
+    `sessions=True`: every slot is an independent stream session.  `start(slot, ...)` begins a fresh stream (zero caches)
+    or resumes one from its 22 + 30 caches, `set_bitrate(slot, n)` changes its number of quantiser stages (`n` of the
+    constructor is the maximum and the default), `export(slot)` returns its current caches; each takes effect at the next
+    `step()`.  The graph then starts each group's chain with one hilc_state_slots_apply on the block the hop reads, and the
+    quantiser and dequantiser take their per-stream n from a device buffer (rows >= a stream's n of the indices hold -1).
+    Pending actions travel from pinned host buffers on the replay stream, only when something changed.
+    `sessions=False` captures exactly the graph of earlier rounds."""
+
+    def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, groups: int = 1,
+                 sessions: bool = False, max_loads_per_hop: int = 4):
         self.model, self.n = model, n
         self.device = device
         groups = max(1, min(int(groups), batch))
@@ -88,6 +142,9 @@ class GraphedHop:
         # per group: a ping-pong pair of state blocks (a cache tensor is [streams, C, pad]: a group's slice must be contiguous)
         self.gstate = [(StateBlock(model, hi - lo, device), StateBlock(model, hi - lo, device)) for lo, hi in self.bounds]
         self.parity = 0                       # the block holding the CURRENT caches (input of the next hop)
+        self.sessions = bool(sessions)
+        if self.sessions:
+            self._init_sessions(batch, int(max_loads_per_hop))
         # the STFT side branch (engine._early_spectra) only for a single chain: with several chains the launches of the other
         # groups already fill the idle CUs, and a fork of a forked stream inside one capture crashes hipStreamEndCapture (ROCm 7.2)
         self.spec_side = [torch.cuda.Stream(device) if groups == 1 else None for _ in self.bounds]
@@ -128,11 +185,18 @@ class GraphedHop:
         lo, hi = self.bounds[g]
         src, dst = self.gstate[g][p], self.gstate[g][p ^ 1]
         x = self.x[lo:hi]
+        if self.sessions:
+            # before the encoder: it forks the STFT side branch, which reads this block's waveform histories
+            ops.state_slots_apply(src.buffer, src.layout, self.action[lo:hi], self.records)
         with ops.sched_workspace(self.sched[g]):
             with _spectra_on(m.encoder, self.spec_side[g]):
                 z, _ = m.encoder(x, *src.enc, cache_out=dst.enc)
-            idx = m.quantizer(z, self.n)
-            q = m.dequantizer(idx, self.n)
+            if self.sessions:
+                idx = m.quantizer(z, self.n, n_clip=self.n_slot[lo:hi])
+                q = m.dequantizer(idx, self.n, n_clip=self.n_slot[lo:hi])
+            else:
+                idx = m.quantizer(z, self.n)
+                q = m.dequantizer(idx, self.n)
             wav, _ = m.decoder(q, *src.dec, cache_out=dst.dec)
         return idx, wav
 
@@ -167,19 +231,118 @@ class GraphedHop:
         return self._current("dec")
 
     def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
-        """zero history, or resume from caches saved earlier (`wire.save_cache` / `e_in*`, `d_in*`)"""
+        """zero history, or resume from caches saved earlier (`wire.save_cache` / `e_in*`, `d_in*`); with sessions also drops
+        every queued action and puts every slot back to the default n"""
         with torch.no_grad():
             self.parity = 0
             for (lo, hi), (a, _b) in zip(self.bounds, self.gstate):
                 a.load_(None if cache_enc is None else [c[lo:hi] for c in cache_enc],
                         None if cache_dec is None else [c[lo:hi] for c in cache_dec])
+            if self.sessions:
+                self.queue.clear()
+                self._uploaded.synchronize()
+                self._h_ctl[0].zero_()
+                self._h_ctl[1].fill_(self.n)
+                self._stage[:self._h_ctl.numel()].copy_(self._h_stage[:self._h_ctl.numel()], non_blocking=True)
+                self._uploaded.record()
+                self._action_live = False
 
     def step(self, x: Tensor) -> Tuple[Tensor, Tensor]:
         self.x.copy_(x)
+        if self.sessions:
+            self._upload()
         self.graphs[self.parity].replay()
         out = self.outs[self.parity]
         self.parity ^= 1
         return out
+
+    # ---------------------------------------------------------------- sessions
+    def _init_sessions(self, batch: int, max_loads: int) -> None:
+        if max_loads < 1:
+            raise ValueError("max_loads_per_hop must be >= 1")
+        layout = self.gstate[0][0].layout
+        self.queue = SessionQueue(batch, self.n, max_loads, layout)
+        # device side, captured by address, ONE buffer so that a hop's upload is one copy: ctl[0] = action per slot (0 keep,
+        # -1 zero, r >= 1 load record r-1), ctl[1] = n per slot, then the staged records
+        n_ctl = 2 * batch
+        self._stage = torch.zeros(n_ctl + max_loads * layout.record_len, device=self.device)
+        self._h_stage = torch.zeros(self._stage.numel()).pin_memory()    # its pinned host mirror
+        self.ctl = self._stage[:n_ctl].view(torch.int32).view(2, batch)
+        self.records = self._stage[n_ctl:].view(max_loads, layout.record_len)
+        self._h_ctl = self._h_stage[:n_ctl].view(torch.int32).view(2, batch)
+        self._h_rec = self._h_stage[n_ctl:].view(max_loads, layout.record_len)
+        self.ctl[1].fill_(self.n)
+        self._h_ctl[1].fill_(self.n)
+        self.action, self.n_slot = self.ctl[0], self.ctl[1]
+        self._uploaded = torch.cuda.Event()
+        self._action_live = False             # the device action row holds the previous hop's actions
+        for a, b in self.gstate:              # the kernels' layout tables, built before the capture
+            a.layout.tables(self.device)
+            b.layout.tables(self.device)
+
+    def _upload(self) -> None:
+        """queued actions and bitrates -> the graph's device buffers, on the replay stream (an action applies to exactly one
+        hop: the upload after a hop with actions clears them)"""
+        q = self.queue
+        if not q.pending and not self._action_live:
+            return
+        self._uploaded.synchronize()          # the previous upload's copy has left the pinned buffer
+        h = self._h_ctl
+        h[0].zero_()
+        stream = torch.cuda.current_stream(self.device)
+        host = [(s, r) for s, r in q.starts.items() if r is not None and not r.is_cuda]      # host records first: one copy
+        dev = [(s, r) for s, r in q.starts.items() if r is not None and r.is_cuda]
+        for slot, rec in q.starts.items():
+            if rec is None:
+                h[0, slot] = -1
+        for r, (slot, rec) in enumerate(host + dev):
+            h[0, slot] = r + 1
+            if r < len(host):
+                self._h_rec[r].copy_(rec)
+        for slot, n in q.n.items():
+            h[1, slot] = n
+        used = h.numel() + len(host) * self.records.shape[1]
+        self._stage[:used].copy_(self._h_stage[:used], non_blocking=True)
+        for r, (_slot, rec) in enumerate(dev, start=len(host)):
+            rec.record_stream(stream)
+            self.records[r].copy_(rec, non_blocking=True)
+        self._uploaded.record(stream)
+        self._action_live = bool(q.starts)
+        q.clear()
+
+    def _need_sessions(self, what: str) -> None:
+        if not self.sessions:
+            raise RuntimeError(f"GraphedHop.{what}: construct with sessions=True")
+
+    def _where(self, slot: int) -> Tuple[int, int]:
+        for g, (lo, hi) in enumerate(self.bounds):
+            if lo <= slot < hi:
+                return g, slot - lo
+        raise IndexError(slot)
+
+    def start(self, slot: int, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None,
+              n: Optional[int] = None) -> None:
+        """At the next step, slot `slot` begins a fresh stream (zero caches) or, given one stream's 22 + 30 caches (B = 1
+        tensors, as `export` / `wire.load_cache_npz(..., batch=1)` give them, on the host or the device), resumes that stream.
+        `n`: its number of quantiser stages (default: the graph's n).  At most `max_loads_per_hop` resumes per hop."""
+        self._need_sessions("start")
+        self.queue.start(slot, cache_enc, cache_dec, n)
+
+    def set_bitrate(self, slot: int, n: int) -> None:
+        """from the next step on, slot `slot` uses the first `n` quantiser stages (1 <= n <= the graph's n)"""
+        self._need_sessions("set_bitrate")
+        self.queue.set_bitrate(slot, n)
+
+    def export(self, slot: int) -> Tuple[List[Tensor], List[Tensor]]:
+        """the current 22 + 30 caches of slot `slot` as B = 1 device tensors (one gather launch) — the state after the last
+        step, without actions queued since"""
+        self._need_sessions("export")
+        g, local = self._where(self.queue.slot(slot))
+        blk = self.gstate[g][self.parity]
+        slots = torch.tensor([local], dtype=torch.int32, device=self.device)
+        with torch.no_grad():
+            rec = ops.state_slots_gather(blk.buffer, blk.layout, slots)
+        return blk.layout.split(rec[0])
 
 
 class PipelinedHop:
@@ -198,9 +361,14 @@ class PipelinedHop:
     State blocks as in GraphedHop; the encoder and decoder halves of a block flip on opposite parities (the decoder is
     one hop behind), the indices travel through two fixed `[n,B,T]` buffers."""
 
-    def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, groups: int = 1):
+    def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, groups: int = 1,
+                 sessions: bool = False):
         """`groups` > 1: additionally split the streams into contiguous groups, each with its own encoder and decoder chain
-        (2 * groups HIP streams inside the graph), as in GraphedHop."""
+        (2 * groups HIP streams inside the graph), as in GraphedHop.  `sessions` (GraphedHop's per-stream sessions) is not
+        available on this schedule."""
+        if sessions:
+            raise NotImplementedError("PipelinedHop(sessions=True): per-stream sessions exist on GraphedHop only (the encoder and "
+                                      "decoder halves of a block flip on opposite parities here)")
         self.model, self.n, self.device = model, n, device
         groups = max(1, min(int(groups), batch))
         self.bounds = [(batch * g // groups, batch * (g + 1) // groups) for g in range(groups)]

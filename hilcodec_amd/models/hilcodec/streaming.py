@@ -73,8 +73,13 @@ class ResidualVQ(_CodebookStack):
         self.layers = nn.ModuleList([EuclideanCodebook(**kwargs) for _ in range(num_quantizers)])
         self.rvq_valu_only = False      # launch option, see models/hilcodec/vector_quantize.py
 
-    def forward(self, x: Tensor, n: int) -> Tensor:
+    def forward(self, x: Tensor, n: int, n_clip: Optional[Tensor] = None) -> Tensor:
+        """`n_clip`: per-stream n as an int32 device tensor `[B]` (entries in [1, n], validated by the caller), `n` the rows"""
         sp = self._tables(x.device)
+        if n_clip is not None:
+            n = min(int(n), len(self.layers))
+            return ops.rvq_encode(x.contiguous().float(), sp.codebooks, sp.codebooks_t, sp.norms, n, channel_last=True,
+                                  stage_major=True, want_q=False, valu_only=self.rvq_valu_only, n_clip=n_clip)[0]
         if ops.is_scalar_n(n):
             n = min(int(n), len(self.layers))           # reference: `self.layers[:n]`
             if n < 1:
@@ -108,13 +113,14 @@ class Dequantizer(_CodebookStack):
         super().__init__()
         self.layers = nn.ModuleList([EuclideanCodebookDeq(**kwargs) for _ in range(num_quantizers)])
 
-    def forward(self, indices: Tensor, n: int) -> Tensor:
+    def forward(self, indices: Tensor, n: int, n_clip: Optional[Tensor] = None) -> Tensor:
+        """`n_clip`: per-stream n as an int32 device tensor `[B]` (see ResidualVQ.forward)"""
         sp = self._tables(indices.device)
         if indices.dtype != torch.int64:
             indices = indices.long()                   # test_onnx.py stores int16 (:96-100)
-        if ops.is_scalar_n(n):
+        if ops.is_scalar_n(n) or n_clip is not None:
             n = int(n)
-        return ops.rvq_decode(indices.contiguous(), sp.codebooks, n, channel_last=True, stage_major=True)
+        return ops.rvq_decode(indices.contiguous(), sp.codebooks, n, channel_last=True, stage_major=True, n_clip=n_clip)
 
 
 class DWSBlock(nn.Module):

@@ -743,6 +743,89 @@ def _rvq_ema_update(embed, ema_num, ema_embed, bucket, decay):
 _register("rvq_ema_update", "(Tensor(a!) embed, Tensor(b!) ema_num, Tensor(c!) ema_embed, Tensor bucket, float decay)"
           " -> ()", _rvq_ema_update, lambda embed, ema_num, ema_embed, bucket, decay: None)
 
+# ======================================================================================================
+# per-stream session state (graph_step.GraphedHop(sessions=True))
+# ======================================================================================================
+class StateLayout:
+    """Where every stream's part of every cache lies in one state block (graph_step.StateBlock; the layout of
+    hilc_state_slots_apply / _gather): cache k, a `[streams, C, L]` tensor, starts at float `off[k]` (16-B aligned) and stream
+    b's part of it is the `lens[k]` = C*L floats at `off[k] + b * lens[k]`.  A record is one stream's parts concatenated in
+    order (`record_len` floats).  Host-only (no device needed); `tables(device)` gives the kernels' device arrays."""
+
+    def __init__(self, shapes: Sequence[Sequence[int]], n_enc: int):
+        """shapes: the `[streams, C, L]` shape of every cache in the reference's order, the first `n_enc` the encoder's"""
+        self.shapes = [tuple(int(d) for d in s) for s in shapes]
+        self.n_enc = int(n_enc)
+        self.streams = self.shapes[0][0]
+        if any(len(s) != 3 or s[0] != self.streams for s in self.shapes):
+            raise ValueError("StateLayout: every cache must be [streams, C, L] with the same streams")
+        self.off: List[int] = []
+        self.lens: List[int] = []
+        total = 0
+        for s in self.shapes:
+            self.off.append(total)
+            self.lens.append(s[1] * s[2])
+            total += (s[0] * s[1] * s[2] + 3) // 4 * 4
+        self.total = total                       # floats of the block
+        self.record_len = sum(self.lens)
+        self._tables = {}
+
+    def tables(self, device) -> Tuple[Tensor, Tensor]:
+        """(slice_off int64, slice_len int32) on `device`, built once (before a graph capture: the first hop warms them)"""
+        key = str(torch.device(device))
+        if key not in self._tables:
+            self._tables[key] = (torch.tensor(self.off, dtype=torch.int64, device=device),
+                                 torch.tensor(self.lens, dtype=torch.int32, device=device))
+        return self._tables[key]
+
+    def record(self, cache_enc: Sequence[Tensor], cache_dec: Sequence[Tensor]) -> Tensor:
+        """one stream's caches (B = 1 tensors, the format of `wire.load_cache_npz(..., batch=1)`) -> its flat fp32 record, on
+        the first cache's device; ValueError if a count or a shape does not match"""
+        caches = list(cache_enc) + list(cache_dec)
+        if len(cache_enc) != self.n_enc or len(caches) != len(self.shapes):
+            raise ValueError(f"expected {self.n_enc} + {len(self.shapes) - self.n_enc} caches, got {len(cache_enc)} + {len(cache_dec)}")
+        for k, (c, s) in enumerate(zip(caches, self.shapes)):
+            if tuple(c.shape) != (1,) + s[1:]:
+                raise ValueError(f"cache {k}: expected shape {(1,) + s[1:]}, got {tuple(c.shape)}")
+        dev = caches[0].device
+        return torch.cat([c.detach().reshape(-1).to(dev, torch.float32) for c in caches])
+
+    def split(self, record: Tensor) -> Tuple[List[Tensor], List[Tensor]]:
+        """a flat record -> (encoder caches, decoder caches) as B = 1 views of it"""
+        out, o = [], 0
+        for s, n in zip(self.shapes, self.lens):
+            out.append(record[o:o + n].view(1, s[1], s[2]))
+            o += n
+        return out[:self.n_enc], out[self.n_enc:]
+
+
+def _state_slots_apply(block, slice_off, slice_len, action, records):
+    if slice_len.numel() != slice_off.numel():
+        raise RuntimeError("state_slots_apply: slice_off and slice_len differ in length")
+    nrec = 0 if records is None else records.shape[0]
+    check(lib.hilc_state_slots_apply(_ptr(block), _ptr(slice_off, torch.int64), _ptr(slice_len, torch.int32), slice_off.numel(),
+                                     action.numel(), _ptr(action, torch.int32), _ptr(records), nrec, _stream()),
+          "hilc_state_slots_apply")
+
+
+_register("state_slots_apply", "(Tensor(a!) block, Tensor slice_off, Tensor slice_len, Tensor action, Tensor? records) -> ()",
+          _state_slots_apply, lambda block, slice_off, slice_len, action, records: None)
+
+
+def _state_slots_gather(block, slice_off, slice_len, slots, streams, record_len):
+    if slice_len.numel() != slice_off.numel():
+        raise RuntimeError("state_slots_gather: slice_off and slice_len differ in length")
+    rec = _new(block, slots.numel(), record_len)
+    check(lib.hilc_state_slots_gather(_ptr(block), _ptr(slice_off, torch.int64), _ptr(slice_len, torch.int32), slice_off.numel(),
+                                      streams, _ptr(slots, torch.int32), slots.numel(), _ptr(rec), _stream()),
+          "hilc_state_slots_gather")
+    return rec
+
+
+_register("state_slots_gather", "(Tensor block, Tensor slice_off, Tensor slice_len, Tensor slots, int streams, int record_len)"
+          " -> Tensor", _state_slots_gather,
+          lambda block, slice_off, slice_len, slots, streams, record_len: block.new_empty(slots.shape[0], record_len))
+
 _OPS = torch.ops.hilcodec
 
 
@@ -1181,23 +1264,34 @@ def per_clip_n(n, B: int, Nq: int, device):
     return hi, host.to(torch.int32).to(device)
 
 
+def _device_n(n, n_clip: Tensor, B: int):
+    """the device-resident per-clip form: `n` = rows of the indices, `n_clip` int32 `[B]` on the GPU, entries in [1, n] (the
+    kernels clamp to that range).  Neither copied to the host nor range-checked per call: the caller validates (a graphed hop
+    uploads the entries it has checked)."""
+    if n_clip.numel() != B:
+        raise RuntimeError(f"n_clip needs {B} entries, got {n_clip.numel()}")
+    return int(n), n_clip
+
+
 def rvq_encode(z: Tensor, codebooks: Tensor, codebooks_t: Tensor, norms: Tensor, n,
                channel_last: bool = False, stage_major: bool = False, want_q: bool = True,
-               want_loss: bool = False, valu_only: bool = False):
+               want_loss: bool = False, valu_only: bool = False, n_clip: Optional[Tensor] = None):
     """Returns (indices int64, q or None, loss 0-d or None).  `n`: int, or one int per clip (rows of `indices`
     beyond a clip's own n hold -1).  `valu_only` (HILC_RVQ_VALU_ONLY of the C ABI): keep batches of 8 192 frames and more on the
-    VALU form instead of the matrix pipe — same fmaf chains, same bits; the quantiser modules pass their `rvq_valu_only` attribute."""
+    VALU form instead of the matrix pipe — same fmaf chains, same bits; the quantiser modules pass their `rvq_valu_only` attribute.
+    `n_clip`: the per-clip n as an int32 device tensor `[B]` with `n` (int) the rows — see `_device_n`."""
     B = z.shape[0]
-    n, n_clip = per_clip_n(n, B, codebooks.shape[0], z.device)
+    n, n_clip = per_clip_n(n, B, codebooks.shape[0], z.device) if n_clip is None else _device_n(n, n_clip, B)
     idx, q, loss = _OPS.rvq_encode(z, codebooks, codebooks_t, norms, n_clip, n, bool(channel_last), bool(stage_major),
                                    bool(want_q), bool(want_loss), RVQ_VALU_ONLY if valu_only else 0)
     return idx, (q if want_q else None), (loss if want_loss else None)
 
 
 def rvq_decode(indices: Tensor, codebooks: Tensor, n, channel_last: bool = True,
-               stage_major: bool = True) -> Tensor:
+               stage_major: bool = True, n_clip: Optional[Tensor] = None) -> Tensor:
+    """`n`: int or one int per clip; or `n_clip` = int32 device tensor `[B]` with `n` the rows (`_device_n`)"""
     B = indices.shape[1] if stage_major else indices.shape[0]
-    n, n_clip = per_clip_n(n, B, codebooks.shape[0], indices.device)
+    n, n_clip = per_clip_n(n, B, codebooks.shape[0], indices.device) if n_clip is None else _device_n(n, n_clip, B)
     return _OPS.rvq_decode(indices, codebooks, n_clip, n, bool(channel_last), bool(stage_major))
 
 
@@ -1211,3 +1305,22 @@ def rvq_ema_stats(z: Tensor, codebooks: Tensor, indices: Tensor, n: int, channel
 def rvq_ema_update(embed: Tensor, ema_num: Tensor, ema_embed: Tensor, bucket: Tensor, decay: float) -> None:
     """In place on stacked `[n,K,C]` / `[n,K]` tensors: EMA of counts and sums, embed = ema_embed / ema_num."""
     _OPS.rvq_ema_update(embed, ema_num, ema_embed, bucket, float(decay))
+
+
+def state_slots_apply(block: Tensor, layout: StateLayout, action: Tensor, records: Optional[Tensor] = None) -> None:
+    """In place on a state block (`layout`): stream b zeroed where action[b] == -1, loaded from row r-1 of `records`
+    `[R, layout.record_len]` where action[b] == r >= 1, kept otherwise; `action` int32 `[layout.streams]` on the device."""
+    if block.numel() < layout.total or action.numel() != layout.streams:
+        raise RuntimeError("state_slots_apply: block or action does not match the layout")
+    if records is not None and (records.dim() != 2 or records.shape[1] != layout.record_len):
+        raise RuntimeError(f"state_slots_apply: records must be [R, {layout.record_len}]")
+    off, lens = layout.tables(block.device)
+    _OPS.state_slots_apply(block, off, lens, action, records)
+
+
+def state_slots_gather(block: Tensor, layout: StateLayout, slots: Tensor) -> Tensor:
+    """records `[len(slots), layout.record_len]` of the streams `slots` (int32, device) of a state block"""
+    if block.numel() < layout.total:
+        raise RuntimeError("state_slots_gather: block does not match the layout")
+    off, lens = layout.tables(block.device)
+    return _OPS.state_slots_gather(block, off, lens, slots, layout.streams, layout.record_len)

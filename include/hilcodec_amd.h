@@ -37,7 +37,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 15   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -398,6 +398,26 @@ int hilc_rvq_ema_stats(const float* z, const float* codebooks, const int64_t* in
                        int T, int K, int n, int index_rows, int channel_last, int stage_major, void* stream);
 int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const float* bucket, double decay, int K,
                         int C, int n, void* stream);
+
+
+/* ---- per-stream session state of a streaming hop (ABI 16) ------------------------------------------------------------------
+ * Layout: the caches of `streams` streams live in ONE fp32 block (hilcodec_amd/graph_step.py StateBlock): slice k (one
+ * `[streams][C][L]` cache tensor, k < nslices, in the reference's order: 22 encoder then 30 decoder caches) starts at
+ * block + slice_off[k], and stream b's part of it is the slice_len[k] = C*L floats at block + slice_off[k] + b * slice_len[k].
+ * slice_off (int64) and slice_len (int32) are DEVICE arrays of nslices entries, built once per block.  A "record" is one
+ * stream's nslices parts concatenated in order: sum(slice_len) floats (76 479 for both shipped models), records packed back to
+ * back.  The reference's caches start at zero (`causal_layers.py:56-58,131-133,156-158`) and the codec keeps no other per-stream
+ * state, so zeroing a stream's parts starts a fresh stream there and loading a record resumes one.
+ * hilc_state_slots_apply: action[b] (int32, device, `streams` entries) = 0 keep, -1 zero stream b, r >= 1 copy record r-1 of
+ * `records` (nrecords records; may be NULL when nrecords == 0) into stream b; any other value: keep.  Meant to run at the head
+ * of every hop (captured in its graph): a fixed grid that leaves after one barrier when no action is set.
+ * hilc_state_slots_gather: record i of `records` = the current state of stream slots[i] (int32, device, i < nslots); a slot
+ * outside [0, streams) leaves its record untouched.  Both: every slice must lie inside `block` (not checked: device tables);
+ * nslices <= 128 (the table is staged in LDS), else HILC_ERR_UNSUPPORTED. */
+int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams,
+                           const int* action, const float* records, int nrecords, void* stream);
+int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams,
+                            const int* slots, int nslots, float* records, void* stream);
 
 #ifdef __cplusplus
 }

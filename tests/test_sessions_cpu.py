@@ -1,0 +1,160 @@
+"""CPU: the per-stream session layer of the graphed hop — ABI 16 entry points, their argument checks, the state-block layout
+the kernels address, the fake kernels of the two new ops, and the host-side session checks.  (No kernel is launched here.)"""
+import ctypes
+import os
+import re
+
+import pytest
+import torch
+
+from hilcodec_amd import synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("hilc_state_slots_apply", "hilc_state_slots_gather")
+
+
+def _model(name="hil_speech"):
+    from hilcodec_amd.models.hilcodec.streaming import HILCodec
+    mk = dict(synth.model_kwargs(name))
+    for k in ("spec_learnable", "causal", "pad_mode"):
+        mk.pop(k)
+    return HILCodec(24000, **mk).eval()
+
+
+def test_abi16_symbols_exported_and_declared():
+    from hilcodec_amd import _lib
+    assert _lib.ABI_VERSION == 16 and _lib.lib.hilc_abi_version() == 16
+    header = open(os.path.join(ROOT, "include", "hilcodec_amd.h")).read()
+    assert re.search(r"#define HILC_ABI_VERSION 16\b", header)
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in NEW:
+        assert re.search(r"\bint " + name + r"\(", header), name
+        assert hasattr(lib, name) and name in _lib.SIGNATURES
+
+
+def test_state_slots_argument_checks():
+    from hilcodec_amd._lib import lib
+    p = ctypes.c_void_p(16)
+    # apply(block, slice_off, slice_len, nslices, streams, action, records, nrecords, stream)
+    assert lib.hilc_state_slots_apply(None, p, p, 52, 4, p, p, 1, None) == -2
+    assert lib.hilc_state_slots_apply(p, None, p, 52, 4, p, p, 1, None) == -2
+    assert lib.hilc_state_slots_apply(p, p, None, 52, 4, p, p, 1, None) == -2
+    assert lib.hilc_state_slots_apply(p, p, p, 52, 4, None, p, 1, None) == -2
+    assert lib.hilc_state_slots_apply(p, p, p, 52, 4, p, None, 1, None) == -2      # records promised, none given
+    assert lib.hilc_state_slots_apply(p, p, p, 0, 4, p, p, 1, None) == -1
+    assert lib.hilc_state_slots_apply(p, p, p, 52, 0, p, p, 1, None) == -1
+    assert lib.hilc_state_slots_apply(p, p, p, 52, 4, p, p, -1, None) == -1
+    assert lib.hilc_state_slots_apply(p, p, p, 129, 4, p, p, 1, None) == -4      # the slice table is staged in LDS
+    assert lib.hilc_state_slots_gather(p, p, p, 129, 4, p, 1, p, None) == -4
+    # gather(block, slice_off, slice_len, nslices, streams, slots, nslots, records, stream)
+    assert lib.hilc_state_slots_gather(None, p, p, 52, 4, p, 1, p, None) == -2
+    assert lib.hilc_state_slots_gather(p, p, p, 52, 4, None, 1, p, None) == -2
+    assert lib.hilc_state_slots_gather(p, p, p, 52, 4, p, 1, None, None) == -2
+    assert lib.hilc_state_slots_gather(p, p, p, 0, 4, p, 1, p, None) == -1
+    assert lib.hilc_state_slots_gather(p, p, p, 52, -3, p, 1, p, None) == -1
+    assert lib.hilc_state_slots_gather(p, p, p, 52, 4, p, 0, p, None) == -1
+
+
+@pytest.mark.parametrize("name", ["hil_speech", "hil_music"])
+def test_layout_matches_state_block_views(name):
+    """the table the kernels address (graph_step.state_layout, host-only) is the StateBlock's views: slice k of stream b at
+    buffer + off[k] + b * lens[k], 16-B aligned slice bases, one record = 76 479 floats"""
+    from hilcodec_amd import graph_step as G
+    model = _model(name)
+    B = 3
+    layout = G.state_layout(model, B)
+    assert layout.record_len == 76479 and len(layout.shapes) == 52 and layout.n_enc == 22 and layout.streams == B
+    blk = G.StateBlock(model, B, torch.device("cpu"))
+    assert blk.layout.off == layout.off and blk.layout.lens == layout.lens and blk.buffer.numel() == layout.total
+    base = blk.buffer.data_ptr()
+    ce, cd = model.initialize_cache(torch.zeros(B, 1, 1))
+    for v, ref, o, n in zip(blk.enc + blk.dec, ce + cd, layout.off, layout.lens):
+        assert v.shape == ref.shape and n == ref.shape[1] * ref.shape[2] and o % 4 == 0
+        for b in range(B):
+            assert v[b].data_ptr() == base + 4 * (o + b * n)
+    assert layout.lens[0] == 1023                          # the waveform history: stream slices after the first misaligned
+    # record <-> caches: concatenation in slice order, split back into B = 1 views
+    blk.buffer.copy_(torch.arange(blk.buffer.numel(), dtype=torch.float32))
+    enc, dec = [c[1:2] for c in blk.enc], [c[1:2] for c in blk.dec]
+    rec = layout.record(enc, dec)
+    assert rec.shape == (76479,)
+    e2, d2 = layout.split(rec)
+    assert len(e2) == 22 and len(d2) == 30
+    assert all(torch.equal(a, b) for a, b in zip(e2 + d2, enc + dec))
+    assert layout.tables(torch.device("cpu"))[0].dtype == torch.int64
+
+
+def test_session_ops_registered_with_fake_kernels():
+    from torch._subclasses.fake_tensor import FakeTensorMode
+    from hilcodec_amd import graph_step as G, ops
+    layout = G.state_layout(_model(), 5)
+    for name in ("state_slots_apply", "state_slots_gather"):
+        assert hasattr(torch.ops.hilcodec, name)
+    schema = str(torch.ops.hilcodec.state_slots_apply.default._schema)
+    assert "Tensor(a!) block" in schema
+    with FakeTensorMode():
+        block = torch.empty(layout.total)
+        off = torch.empty(52, dtype=torch.int64)
+        lens = torch.empty(52, dtype=torch.int32)
+        out = torch.ops.hilcodec.state_slots_gather(block, off, lens, torch.empty(3, dtype=torch.int32), 5, layout.record_len)
+        assert out.shape == (3, 76479) and out.dtype == torch.float32
+        assert torch.ops.hilcodec.state_slots_apply(block, off, lens, torch.empty(5, dtype=torch.int32),
+                                                    torch.empty(4, 76479)) is None
+        # the device-resident per-clip n of the quantiser ops: indices keep `n` rows
+        z = torch.empty(5, 1, 128)
+        cb = torch.empty(8, 1024, 128)
+        idx, _, _ = ops.rvq_encode(z, cb, cb.transpose(1, 2).contiguous(), torch.empty(8, 1024), 8, channel_last=True,
+                                   stage_major=True, want_q=False, n_clip=torch.empty(5, dtype=torch.int32))
+        assert idx.shape == (8, 5, 1) and idx.dtype == torch.int64
+        q = ops.rvq_decode(idx, cb, 8, n_clip=torch.empty(5, dtype=torch.int32))
+        assert q.shape == (5, 1, 128)
+    with pytest.raises(RuntimeError):                     # no CPU fallback
+        torch.ops.hilcodec.state_slots_gather(torch.zeros(layout.total), torch.zeros(52, dtype=torch.int64),
+                                              torch.zeros(52, dtype=torch.int32), torch.zeros(1, dtype=torch.int32), 5, 76479)
+
+
+def test_session_queue_checks():
+    """everything a GraphedHop(sessions=True) refuses is refused by the host-side queue before any launch"""
+    from hilcodec_amd import graph_step as G
+    model = _model()
+    layout = G.state_layout(model, 6)
+    q = G.SessionQueue(6, 8, 2, layout)
+    for bad in (-1, 6, 100):
+        with pytest.raises(IndexError):
+            q.start(bad)
+        with pytest.raises(IndexError):
+            q.set_bitrate(bad, 4)
+    for bad in (0, 9, -2):
+        with pytest.raises(ValueError):
+            q.set_bitrate(1, bad)
+        with pytest.raises(ValueError):
+            q.start(1, n=bad)
+    assert not q.pending
+    ce, cd = model.initialize_cache(torch.zeros(1, 1, 1))
+    q.start(0, ce, cd, n=4)
+    q.start(0, ce, cd)                                    # the same slot again: replaces, not a second load
+    q.start(1, ce, cd)
+    assert q.loads == 2 and q.n == {0: 8, 1: 8}
+    with pytest.raises(RuntimeError):
+        q.start(2, ce, cd)                                # a third load in one hop
+    q.start(2)                                            # fresh starts are not loads
+    q.set_bitrate(2, 1)
+    assert q.starts[2] is None and q.n[2] == 1 and q.loads == 2
+    with pytest.raises(ValueError):
+        q.start(3, ce, None)                              # one list without the other
+    with pytest.raises(ValueError):
+        q.start(3, ce[:-1], cd)                           # a cache missing
+    bad = list(cd)
+    bad[4] = torch.zeros(1, bad[4].shape[1], bad[4].shape[2] + 1)
+    with pytest.raises(ValueError):
+        q.start(3, ce, bad)                               # a shape that does not match
+    with pytest.raises(ValueError):
+        q.start(3, [c.expand(2, -1, -1) for c in ce], cd)  # B = 2 caches: one stream only
+    q.clear()
+    assert not q.pending and q.loads == 0
+
+
+def test_pipelined_hop_refuses_sessions():
+    from hilcodec_amd.graph_step import PipelinedHop
+    with pytest.raises(NotImplementedError):
+        PipelinedHop(None, 4, 320, 8, torch.device("cpu"), sessions=True)
