@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from . import engine, ops
+from . import engine, ops, wire
 
 
 def _spectra_on(encoder, stream: Optional[torch.cuda.Stream]):
@@ -31,10 +31,37 @@ def _spectra_on(encoder, stream: Optional[torch.cuda.Stream]):
     return engine.spectra_side_stream(stream)
 
 
-def state_layout(model, batch: int) -> ops.StateLayout:
-    """the layout of a state block of `batch` streams of `model` (host-only: the cache shapes come from a CPU probe)"""
+def state_layout(model, batch: int, side: str = "both") -> ops.StateLayout:
+    """the layout of a state block of `batch` streams of `model` (host-only: the cache shapes come from a CPU probe); `side`
+    "enc" / "dec": a one-sided block of the 22 encoder or the 30 decoder caches only (its records hold that side only)"""
+    if side not in ("both", "enc", "dec"):
+        raise ValueError(f"side must be 'both', 'enc' or 'dec', got {side!r}")
     ce, cd = model.initialize_cache(torch.zeros(1, 1, 1))
+    ce, cd = (ce if side != "dec" else []), (cd if side != "enc" else [])
     return ops.StateLayout([(batch,) + tuple(c.shape[1:]) for c in list(ce) + list(cd)], len(ce))
+
+
+def _capture_pair(hop, zero, device: torch.device, warmup: int):
+    """warm `hop(0)` / `hop(1)` up on a side stream (builds every lazily cached table: folded weights, codebooks), zero the
+    state, then capture one graph per parity; returns (graphs, their static outputs)"""
+    side = torch.cuda.Stream(device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side), torch.no_grad():
+        for _ in range(warmup):
+            hop(0)
+            hop(1)
+        zero()
+    torch.cuda.current_stream(device).wait_stream(side)
+    torch.cuda.synchronize(device)
+    graphs, outs = [], []
+    for p in (0, 1):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g), torch.no_grad():
+            out = hop(p)
+        graphs.append(g)
+        outs.append(out)
+    zero()
+    return graphs, outs
 
 
 class SessionQueue:
@@ -43,8 +70,11 @@ class SessionQueue:
     stages.  A later call for the same slot replaces an earlier one of the same hop; `start` without `n` resets the slot to
     `n_max`, the graph's default."""
 
-    def __init__(self, batch: int, n_max: int, max_loads: int, layout: ops.StateLayout):
+    def __init__(self, batch: int, n_max: int, max_loads: int, layout: ops.StateLayout, one_sided: bool = False):
+        """`one_sided`: the layout holds one side's caches (state_layout(side="enc" / "dec")) and a record is that side's list
+        alone; otherwise both lists or neither"""
         self.batch, self.n_max, self.max_loads, self.layout = int(batch), int(n_max), int(max_loads), layout
+        self.one_sided = bool(one_sided)
         self.starts = {}
         self.n = {}
 
@@ -73,9 +103,9 @@ class SessionQueue:
         v = self.n_max if n is None else self.check_n(n)
         rec = None
         if cache_enc is not None or cache_dec is not None:
-            if cache_enc is None or cache_dec is None:
+            if not self.one_sided and (cache_enc is None or cache_dec is None):
                 raise ValueError("start: give both cache lists (encoder and decoder) or neither")
-            rec = self.layout.record(cache_enc, cache_dec)
+            rec = self.layout.record([] if cache_enc is None else cache_enc, [] if cache_dec is None else cache_dec)
             if self.starts.get(s) is None and self.loads >= self.max_loads:
                 raise RuntimeError(f"start: more than {self.max_loads} loads queued for one hop (max_loads_per_hop)")
         self.starts[s] = rec
@@ -91,10 +121,11 @@ class SessionQueue:
 
 
 class StateBlock:
-    """The 22 + 30 caches of `batch` streams as views into ONE contiguous fp32 buffer (16-B aligned slices)."""
+    """The 22 + 30 caches of `batch` streams as views into ONE contiguous fp32 buffer (16-B aligned slices); `side` "enc" /
+    "dec": one side's caches only (the other list is empty)."""
 
-    def __init__(self, model, batch: int, device: torch.device):
-        self.layout = state_layout(model, batch)
+    def __init__(self, model, batch: int, device: torch.device, side: str = "both"):
+        self.layout = state_layout(model, batch, side)
         self.buffer = torch.zeros(self.layout.total, device=device, dtype=torch.float32)
         views = [self.buffer[o:o + s[0] * n].view(s) for s, o, n in zip(self.layout.shapes, self.layout.off, self.layout.lens)]
         self.enc: List[Tensor] = views[:self.layout.n_enc]
@@ -132,6 +163,8 @@ class GraphedHop:
     Pending actions travel from pinned host buffers on the replay stream, only when something changed.
     `sessions=False` captures exactly the graph of earlier rounds."""
 
+    side = "both"                             # the caches a state block holds (GraphedEncodeHop: the encoder's only)
+
     def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, groups: int = 1,
                  sessions: bool = False, max_loads_per_hop: int = 4):
         self.model, self.n = model, n
@@ -150,23 +183,7 @@ class GraphedHop:
         self.spec_side = [torch.cuda.Stream(device) if groups == 1 else None for _ in self.bounds]
         self.chain = [None] + [torch.cuda.Stream(device) for _ in self.bounds[1:]]      # group 0 runs on the capture stream
         self.sched = [ops.SchedWorkspace(device) for _ in self.bounds]    # ticket words: one workspace per concurrent chain
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(warmup):          # builds every lazily cached table (folded weights, codebooks)
-                self._hop(0)
-                self._hop(1)
-            self._zero()
-        torch.cuda.current_stream(device).wait_stream(side)
-        torch.cuda.synchronize(device)
-        self.graphs, self.outs = [], []
-        for p in (0, 1):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g), torch.no_grad():
-                out = self._hop(p)
-            self.graphs.append(g)
-            self.outs.append(out)
-        self._zero()
+        self.graphs, self.outs = _capture_pair(self._hop, self._zero, device, warmup)
 
     @property
     def state(self):
@@ -261,7 +278,7 @@ class GraphedHop:
         if max_loads < 1:
             raise ValueError("max_loads_per_hop must be >= 1")
         layout = self.gstate[0][0].layout
-        self.queue = SessionQueue(batch, self.n, max_loads, layout)
+        self.queue = SessionQueue(batch, self.n, max_loads, layout, one_sided=self.side != "both")
         # device side, captured by address, ONE buffer so that a hop's upload is one copy: ctl[0] = action per slot (0 keep,
         # -1 zero, r >= 1 load record r-1), ctl[1] = n per slot, then the staged records
         n_ctl = 2 * batch
@@ -518,3 +535,200 @@ class PipelinedHop:
             wav = torch.cat([self._decode(g, self.parity) for g in range(len(self.bounds))], dim=0)
         self.pending = False
         return wav
+
+
+class GraphedEncodeHop(GraphedHop):
+    """The sender: one graph replay per hop turns `[B,1,hop]` samples into per-stream 10-bit packets (`wire.packet_bytes`).
+    A hop is GraphedHop's chain cut after the quantiser — (hilc_state_slots_apply if `sessions`) -> streaming encoder with its
+    STFT side branch -> RVQ (per-stream n if `sessions`) -> hilc_pack_codes_10bit — on a ping-pong pair of ENCODER-ONLY state
+    blocks (the 22 encoder caches; `state_bytes`).  `step(x)` returns (packets uint8 `[B, packet_bytes(n, T)]`, nbytes int32
+    `[B]`), `.indices` the same hop's `[n,B,T]`: static views that the next-but-one `step` overwrites.
+    Sessions as in GraphedHop, on the encoder side: `start(slot, cache_enc=None, n=None)`, `set_bitrate(slot, n)`,
+    `export(slot) -> cache_enc`."""
+
+    side = "enc"
+
+    def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
+                 max_loads_per_hop: int = 4):
+        self.model, self.n, self.device = model, n, device
+        self.bounds = [(0, batch)]
+        self.x = torch.zeros(batch, 1, hop, device=device)
+        self.gstate = [(StateBlock(model, batch, device, "enc"), StateBlock(model, batch, device, "enc"))]
+        self.parity = 0
+        self.sessions = bool(sessions)
+        if self.sessions:
+            self._init_sessions(batch, int(max_loads_per_hop))
+        self.spec_side = [torch.cuda.Stream(device)]
+        self.chain = [None]
+        self.sched = [ops.SchedWorkspace(device)]
+        self.graphs, self.outs = _capture_pair(self._hop, self._zero, device, warmup)
+        self.indices = self.outs[0][0]
+
+    @property
+    def state_bytes(self) -> int:
+        """bytes of the two encoder-only state blocks"""
+        return sum(b.nbytes for b in self.gstate[0])
+
+    def _chain(self, g: int, p: int) -> Tuple[Tensor, Tensor, Tensor]:
+        m = self.model
+        src, dst = self.gstate[0][p], self.gstate[0][p ^ 1]
+        n_clip = self.n_slot if self.sessions else None
+        if self.sessions:
+            ops.state_slots_apply(src.buffer, src.layout, self.action, self.records)
+        with ops.sched_workspace(self.sched[0]):
+            with _spectra_on(m.encoder, self.spec_side[0]):
+                z, _ = m.encoder(self.x, *src.enc, cache_out=dst.enc)
+            idx = m.quantizer(z, self.n, n_clip=n_clip)
+        packets, nbytes = ops.pack_codes_10bit(idx, n_clip)
+        return idx, packets, nbytes
+
+    def step(self, x: Tensor) -> Tuple[Tensor, Tensor]:
+        self.indices, packets, nbytes = super().step(x)
+        return packets, nbytes
+
+    def start(self, slot: int, cache_enc: Optional[Sequence[Tensor]] = None, n: Optional[int] = None) -> None:
+        """At the next step, slot `slot` begins a fresh stream or resumes one from its 22 encoder caches (B = 1 tensors, host or
+        device); `n`: its number of quantiser stages (default: the graph's n)"""
+        self._need_sessions("start")
+        self.queue.start(slot, cache_enc, None, n)
+
+    def export(self, slot: int) -> List[Tensor]:
+        """the current 22 encoder caches of slot `slot` as B = 1 device tensors"""
+        return super().export(slot)[0]
+
+
+class GraphedDecodeHop:
+    """The receiver: one graph replay per hop turns per-stream 10-bit packets (`wire.packet_bytes(n, frames)` bytes per row)
+    into `[B,1,320 frames]` samples.  `step(packets, n_per_stream)`: `packets` uint8 `[B, packet_bytes(n, frames)]` on the host
+    or the device, `n_per_stream` B host ints in [1, n] (checked here: ValueError).  Both go into one static device buffer (one
+    copy from the host; packets already on the device take a device copy), then the graph runs (hilc_state_slots_apply if
+    `sessions`) -> hilc_rvq_decode_packed -> streaming decoder on a ping-pong pair of DECODER-ONLY state blocks (the 30 decoder
+    caches).  The returned waveform is a static view that the next-but-one `step` overwrites.
+    `frames` may differ from the sender's T (the reference's `num_frames`): packets of consecutive sender hops are re-framed by
+    the caller (`wire.unpack_stream_packet` / `pack_stream_packet`).  The per-stream n arrives with every hop, so there is no
+    `set_bitrate`; sessions: `start(slot, cache_dec=None)`, `export(slot) -> cache_dec`."""
+
+    def __init__(self, model, batch: int, frames: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
+                 max_loads_per_hop: int = 4):
+        self.model, self.batch, self.frames, self.n, self.device = model, int(batch), int(frames), int(n), device
+        if not 1 <= self.n <= len(model.dequantizer.layers):
+            raise ValueError(f"n = {n} outside [1, {len(model.dequantizer.layers)}]")
+        self.sessions = bool(sessions)
+        if self.sessions and max_loads_per_hop < 1:
+            raise ValueError("max_loads_per_hop must be >= 1")
+        self.stride = wire.packet_bytes(self.n, self.frames)
+        self.state = (StateBlock(model, batch, device, "dec"), StateBlock(model, batch, device, "dec"))
+        self.parity = 0
+        layout = self.state[0].layout
+        loads = int(max_loads_per_hop) if self.sessions else 0
+        B = self.batch
+        # ONE device buffer, captured by address: ctl[0] = action per slot, ctl[1] = n per slot, the packets, the staged records
+        self._rec_off = 2 * B + (B * self.stride + 3) // 4
+        self._stage = torch.zeros(self._rec_off + loads * layout.record_len, device=device)
+        self._h_stage = torch.zeros(self._stage.numel()).pin_memory()
+        ctl = self._stage[:2 * B].view(torch.int32).view(2, B)
+        self.action, self.n_slot = ctl[0], ctl[1]
+        self.packets = self._stage[2 * B:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
+        self.records = self._stage[self._rec_off:].view(loads, layout.record_len)
+        self._h_ctl = self._h_stage[:2 * B].view(torch.int32).view(2, B)
+        self._h_packets = self._h_stage[2 * B:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
+        self._h_rec = self._h_stage[self._rec_off:].view(loads, layout.record_len)
+        self.n_slot.fill_(self.n)
+        if self.sessions:
+            self.queue = SessionQueue(B, self.n, loads, layout, one_sided=True)
+            for blk in self.state:
+                blk.layout.tables(device)
+        self._uploaded = torch.cuda.Event()
+        self.sched = ops.SchedWorkspace(device)
+        self.graphs, self.outs = _capture_pair(self._hop, self._zero, device, warmup)
+
+    @property
+    def state_bytes(self) -> int:
+        """bytes of the two decoder-only state blocks"""
+        return sum(b.nbytes for b in self.state)
+
+    @property
+    def cache_dec(self) -> List[Tensor]:
+        """the CURRENT 30 decoder caches of all streams (views of the state block)"""
+        return self.state[self.parity].dec
+
+    def _zero(self) -> None:
+        for blk in self.state:
+            blk.zero_()
+
+    def _hop(self, p: int) -> Tensor:
+        m = self.model
+        src, dst = self.state[p], self.state[p ^ 1]
+        if self.sessions:
+            ops.state_slots_apply(src.buffer, src.layout, self.action, self.records)
+        with ops.sched_workspace(self.sched):
+            q = m.dequantizer.decode_packed(self.packets, self.n_slot, self.n, self.frames)
+            wav, _ = m.decoder(q, *src.dec, cache_out=dst.dec)
+        return wav
+
+    def _check(self, packets: Tensor, n_per_stream) -> Tensor:
+        if isinstance(n_per_stream, Tensor) and n_per_stream.is_cuda:
+            raise ValueError("n_per_stream: host ints, not a device tensor")
+        n = torch.as_tensor(n_per_stream).reshape(-1)
+        if n.is_floating_point() or n.numel() != self.batch:
+            raise ValueError(f"n_per_stream: {self.batch} ints expected")
+        if int(n.min()) < 1 or int(n.max()) > self.n:
+            raise ValueError(f"n_per_stream: every entry must lie in [1, {self.n}]")
+        if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or tuple(packets.shape) != (self.batch, self.stride):
+            raise ValueError(f"packets: uint8 [{self.batch}, {self.stride}] expected")
+        return n
+
+    def step(self, packets: Tensor, n_per_stream) -> Tensor:
+        n = self._check(packets, n_per_stream)
+        self._uploaded.synchronize()          # the previous upload's copy has left the pinned buffer
+        B, h = self.batch, self._h_ctl
+        h[0].zero_()
+        h[1].copy_(n)
+        host, dev = [], []
+        if self.sessions:
+            q = self.queue
+            host = [(s, r) for s, r in q.starts.items() if r is not None and not r.is_cuda]
+            dev = [(s, r) for s, r in q.starts.items() if r is not None and r.is_cuda]
+            for slot, rec in q.starts.items():
+                if rec is None:
+                    h[0, slot] = -1
+            for r, (slot, rec) in enumerate(host + dev):
+                h[0, slot] = r + 1
+                if r < len(host):
+                    self._h_rec[r].copy_(rec)
+            q.clear()
+        stream = torch.cuda.current_stream(self.device)
+        if packets.is_cuda:
+            self._stage[:2 * B].copy_(self._h_stage[:2 * B], non_blocking=True)
+            self.packets.copy_(packets)
+        else:
+            self._h_packets.copy_(packets)
+            self._stage[:self._rec_off].copy_(self._h_stage[:self._rec_off], non_blocking=True)
+        if host:
+            end = self._rec_off + len(host) * self.records.shape[1]
+            self._stage[self._rec_off:end].copy_(self._h_stage[self._rec_off:end], non_blocking=True)
+        for r, (_slot, rec) in enumerate(dev, start=len(host)):
+            rec.record_stream(stream)
+            self.records[r].copy_(rec, non_blocking=True)
+        self._uploaded.record(stream)
+        self.graphs[self.parity].replay()
+        out = self.outs[self.parity]
+        self.parity ^= 1
+        return out
+
+    def start(self, slot: int, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
+        """At the next step, slot `slot` begins a fresh stream (zero caches) or resumes one from its 30 decoder caches (B = 1
+        tensors, host or device); at most `max_loads_per_hop` resumes per hop"""
+        if not self.sessions:
+            raise RuntimeError("GraphedDecodeHop.start: construct with sessions=True")
+        self.queue.start(slot, None, cache_dec)
+
+    def export(self, slot: int) -> List[Tensor]:
+        """the current 30 decoder caches of slot `slot` as B = 1 device tensors (one gather launch)"""
+        if not self.sessions:
+            raise RuntimeError("GraphedDecodeHop.export: construct with sessions=True")
+        blk = self.state[self.parity]
+        slots = torch.tensor([self.queue.slot(slot)], dtype=torch.int32, device=self.device)
+        with torch.no_grad():
+            rec = ops.state_slots_gather(blk.buffer, blk.layout, slots)
+        return blk.layout.split(rec[0])[1]

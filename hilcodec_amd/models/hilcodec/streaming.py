@@ -122,6 +122,12 @@ class Dequantizer(_CodebookStack):
             n = int(n)
         return ops.rvq_decode(indices.contiguous(), sp.codebooks, n, channel_last=True, stage_major=True, n_clip=n_clip)
 
+    def decode_packed(self, packets: Tensor, n_per_stream: Optional[Tensor], n: int, frames: int) -> Tensor:
+        """the receiver's dequantiser: per-stream 10-bit packets `[B, wire.packet_bytes(n, frames)]` uint8 (device) with
+        `n_per_stream` int32 `[B]` (device; None = n) -> `[B, frames, C]`, the result of `forward` on the unpacked indices"""
+        sp = self._tables(packets.device)
+        return ops.rvq_decode_packed(packets, sp.codebooks, n, frames, n_clip=n_per_stream)
+
 
 class DWSBlock(nn.Module):
     """`streaming.py:160-192`: [ELU, pointwise 1x1 (no bias)] -> depthwise causal conv with cache."""

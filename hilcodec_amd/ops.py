@@ -826,6 +826,45 @@ _register("state_slots_gather", "(Tensor block, Tensor slice_off, Tensor slice_l
           " -> Tensor", _state_slots_gather,
           lambda block, slice_off, slice_len, slots, streams, record_len: block.new_empty(slots.shape[0], record_len))
 
+
+# ======================================================================================================
+# per-stream 10-bit packets (graph_step.GraphedEncodeHop / GraphedDecodeHop; format: wire.packet_bytes)
+# ======================================================================================================
+def _packet_stride(n: int, T: int) -> int:
+    return (10 * n * T + 7) // 8                      # wire.packet_bytes
+
+
+def _pack_codes_10bit(indices, n_clip):
+    n, B, T = indices.shape
+    packets = _new(indices, B, _packet_stride(n, T), dtype=torch.uint8)
+    nbytes = _new(indices, B, dtype=torch.int32)
+    check(lib.hilc_pack_codes_10bit(_ptr(indices, torch.int64), _ptr(n_clip, torch.int32), _ptr(packets, torch.uint8),
+                                    _ptr(nbytes, torch.int32), B, T, n, _stream()), "hilc_pack_codes_10bit")
+    return packets, nbytes
+
+
+def _pack_codes_10bit_fake(indices, n_clip):
+    n, B, T = indices.shape
+    return indices.new_empty(B, _packet_stride(n, T), dtype=torch.uint8), indices.new_empty(B, dtype=torch.int32)
+
+
+_register("pack_codes_10bit", "(Tensor indices, Tensor? n_clip) -> (Tensor, Tensor)", _pack_codes_10bit, _pack_codes_10bit_fake)
+
+
+def _rvq_decode_packed(packets, n_clip, codebooks, n, frames):
+    B = packets.shape[0]
+    Nq, K, Cc = codebooks.shape
+    if packets.dim() != 2 or packets.shape[1] != _packet_stride(n, frames):
+        raise RuntimeError(f"rvq_decode_packed: packets must be [B, {_packet_stride(n, frames)}] for n = {n}, {frames} frames")
+    q = _new(codebooks, B, frames, Cc)
+    check(lib.hilc_rvq_decode_packed(_ptr(packets, torch.uint8), _ptr(n_clip, torch.int32), _ptr(codebooks), _ptr(q), B, Cc, frames, K,
+                                     Nq, n, _stream()), "hilc_rvq_decode_packed")
+    return q
+
+
+_register("rvq_decode_packed", "(Tensor packets, Tensor? n_clip, Tensor codebooks, int n, int frames) -> Tensor", _rvq_decode_packed,
+          lambda packets, n_clip, codebooks, n, frames: codebooks.new_empty(packets.shape[0], frames, codebooks.shape[2]))
+
 _OPS = torch.ops.hilcodec
 
 
@@ -1324,3 +1363,22 @@ def state_slots_gather(block: Tensor, layout: StateLayout, slots: Tensor) -> Ten
         raise RuntimeError("state_slots_gather: block does not match the layout")
     off, lens = layout.tables(block.device)
     return _OPS.state_slots_gather(block, off, lens, slots, layout.streams, layout.record_len)
+
+
+def pack_codes_10bit(indices: Tensor, n_clip: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """stage-major indices `[n, B, T]` -> (packets uint8 `[B, wire.packet_bytes(n, T)]`, nbytes int32 `[B]`): stream b's first
+    n_b stages (`n_clip` int32 device `[B]`, clamped to [1, n]; None = n) in the wire format of `wire.pack_stream_packet`, the row
+    zero past its length.  Codes outside [0, 1024) are clamped into it."""
+    if indices.dim() != 3:
+        raise RuntimeError("pack_codes_10bit: indices must be [n, B, T]")
+    if n_clip is not None and n_clip.numel() != indices.shape[1]:
+        raise RuntimeError(f"n_clip needs {indices.shape[1]} entries, got {n_clip.numel()}")
+    return _OPS.pack_codes_10bit(indices, n_clip)
+
+
+def rvq_decode_packed(packets: Tensor, codebooks: Tensor, n: int, frames: int, n_clip: Optional[Tensor] = None) -> Tensor:
+    """packets `[B, wire.packet_bytes(n, frames)]` -> q `[B, frames, C]` (channel-last), bit-identical to `rvq_decode` of the
+    unpacked indices with the same per-stream n (`n_clip` int32 device `[B]`, clamped to [1, n]; None = n)"""
+    if n_clip is not None and n_clip.numel() != packets.shape[0]:
+        raise RuntimeError(f"n_clip needs {packets.shape[0]} entries, got {n_clip.numel()}")
+    return _OPS.rvq_decode_packed(packets, n_clip, codebooks, int(n), int(frames))

@@ -51,6 +51,36 @@ def unpack_indices_10bit(blob: bytes) -> Tensor:
     return torch.from_numpy(vals.reshape(n, B, T))
 
 
+# ---------------------------------------------------------------- per-stream packets (graph_step.GraphedEncodeHop / GraphedDecodeHop)
+# One stream's packet for one hop of T frames: its first n stages x T codes, stage-major, 10 bits each, MSB first, the last byte
+# zero-padded — exactly the body of pack_indices_10bit(indices[:n, b:b+1, :]) without its header.  A batch of packets is a
+# uint8 [B, packet_bytes(n_max, T)] tensor (row b zero past packet_bytes(n_b, T)) with an int32 [B] byte count.
+def packet_bytes(n: int, T: int) -> int:
+    return (10 * int(n) * int(T) + 7) // 8
+
+
+def packet_n(nbytes: int, T: int) -> int:
+    """the n of a packet of `nbytes` bytes (unique: consecutive n differ by >= 1.25 bytes); ValueError when none matches"""
+    n = (8 * int(nbytes)) // (10 * int(T))             # ceil(10 n T / 8) = nbytes  <=>  n = floor(8 nbytes / 10 T), if any
+    if n >= 1 and packet_bytes(n, T) == nbytes:
+        return n
+    raise ValueError(f"no stage count gives a {nbytes}-byte packet of {T} frames")
+
+
+def pack_stream_packet(codes: Tensor) -> bytes:
+    """one stream's codes `[n, T]` in [0, 1024) -> its packet"""
+    if codes.dim() != 2:
+        raise ValueError("codes must be [n, T]")
+    return pack_indices_10bit(codes.unsqueeze(1))[12:]
+
+
+def unpack_stream_packet(blob: bytes, n: int, T: int) -> Tensor:
+    """a packet of `n` stages x `T` frames -> its codes `[n, T]` int64 (bytes past packet_bytes(n, T) are ignored)"""
+    if len(blob) < packet_bytes(n, T):
+        raise ValueError(f"a packet of {n} x {T} codes needs {packet_bytes(n, T)} bytes, got {len(blob)}")
+    return unpack_indices_10bit(struct.pack("<III", n, 1, T) + bytes(blob[:packet_bytes(n, T)]))[:, 0, :]
+
+
 # ---------------------------------------------------------------- caches
 def save_cache_npz(path: str, caches: Sequence[Tensor], prefix: str) -> None:
     """prefix 'e_in' (encoder, 22 tensors) or 'd_in' (decoder, 30)."""

@@ -419,6 +419,26 @@ int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* sl
 int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams,
                             const int* slots, int nslots, float* records, void* stream);
 
+/* ---- per-stream 10-bit packets of a streaming hop (additive under ABI 16) ------------------------------------------------------
+ * Two entry points added WITHOUT a version bump: they change no existing signature or struct, so a binding of ABI 16 that does
+ * not use them is unaffected; binders find them by symbol (dlsym), not by version.
+ * Packet of stream b for one hop of T frames: its first n_b stages x T codes, stage-major (stage 0's T frames first), 10 bits per
+ * code, MSB first, the last byte zero-padded — ceil(10 n_b T / 8) bytes, the body of hilcodec_amd/wire.py pack_indices_10bit(
+ * indices[:n_b, b:b+1, :]) without its header.  A batch is `packets` uint8 [B][stride], stride = ceil(10 n_max T / 8), with row b's
+ * bytes past its own length set to zero.  n_per_stream: optional int32 [B] (device; NULL = n_max for every stream), each entry
+ * clamped to [1, n_max] as hilc_rvq_decode_mixed clamps n_per_clip.
+ * hilc_pack_codes_10bit: indices int64 [n_max][B][T] (stage-major, as hilc_rvq_encode_mixed writes them; rows >= n_b are not read)
+ * -> packets [B][stride] and nbytes int32 [B] (stream b's packet length).  A code outside [0, 1024) in a row < n_b is clamped into
+ * it, as hilc_rvq_decode clamps its indices.  n_max < 1: HILC_ERR_RANGE.
+ * hilc_rvq_decode_packed: the dequantiser read straight from packets -> q [B][T][C] (channel-last: what the streaming Dequantizer
+ * hands the decoder), bit-identical to hilc_rvq_decode_mixed(channel_last = 1, stage_major = 1) on the unpacked indices (same
+ * per-element sum in stage order).  codebooks [Nq][K][C]; n_max outside 1..Nq: HILC_ERR_RANGE; K != 1024 or n_max > 32:
+ * HILC_ERR_UNSUPPORTED. */
+int hilc_pack_codes_10bit(const int64_t* indices, const int* n_per_stream, uint8_t* packets, int* nbytes, int B, int T, int n_max,
+                          void* stream);
+int hilc_rvq_decode_packed(const uint8_t* packets, const int* n_per_stream, const float* codebooks, float* q, int B, int C, int T,
+                           int K, int Nq, int n_max, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
