@@ -69,6 +69,7 @@ SIGNATURES = {
     "hilc_rvq_decode_mixed": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "hilc_state_slots_apply": [_p, _p, _p, _i, _i, _p, _p, _i, _p],
     "hilc_state_slots_gather": [_p, _p, _p, _i, _i, _p, _i, _p, _p],
+    "hilc_state_slots_hold": [_p, _p, _p, _p, _i, _i, _p, _p, _i, _p, _i, _i, _p, _i, _p, _p],
     "hilc_pack_codes_10bit": [_p, _p, _p, _p, _i, _i, _i, _p],
     "hilc_rvq_decode_packed": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
 }

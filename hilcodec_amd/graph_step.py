@@ -64,11 +64,19 @@ def _capture_pair(hop, zero, device: torch.device, warmup: int):
     return graphs, outs
 
 
+def _mark(row: Tensor, slots) -> None:
+    """a pinned int32 control row: 1 at `slots`, 0 elsewhere"""
+    row.zero_()
+    if slots:
+        row[torch.tensor(sorted(slots), dtype=torch.long)] = 1
+
+
 class SessionQueue:
     """Host side of GraphedHop's per-stream sessions: what the next hop does to which slot, checked here before anything is
     launched (no device).  `starts[slot]` = None (fresh zeros) or the slot's record; `n[slot]` = its new number of quantiser
     stages.  A later call for the same slot replaces an earlier one of the same hop; `start` without `n` resets the slot to
-    `n_max`, the graph's default."""
+    `n_max`, the graph's default.  `holds` = the slots held on the next hop only, `stops` = the slots held on every hop until
+    their next `start`; `held` = both (a held slot does not advance: GraphedHop.step(hold=...))."""
 
     def __init__(self, batch: int, n_max: int, max_loads: int, layout: ops.StateLayout, one_sided: bool = False):
         """`one_sided`: the layout holds one side's caches (state_layout(side="enc" / "dec")) and a record is that side's list
@@ -77,6 +85,8 @@ class SessionQueue:
         self.one_sided = bool(one_sided)
         self.starts = {}
         self.n = {}
+        self.holds = set()
+        self.stops = set()
 
     def slot(self, slot) -> int:
         s = int(slot)
@@ -98,6 +108,33 @@ class SessionQueue:
     def pending(self) -> bool:
         return bool(self.starts or self.n)
 
+    @property
+    def held(self) -> frozenset:
+        return frozenset(self.holds | self.stops)
+
+    @property
+    def stopped(self) -> Tuple[int, ...]:
+        return tuple(sorted(self.stops))
+
+    @staticmethod
+    def host_slots(hold) -> List[int]:
+        """`hold` (None or an iterable of host ints) -> a list; ValueError for a device tensor (no hidden device sync)"""
+        if hold is None:
+            return []
+        if isinstance(hold, Tensor):
+            if hold.device.type != "cpu":
+                raise ValueError("hold: host ints, not a device tensor")
+            hold = hold.reshape(-1).tolist()
+        return [int(s) for s in hold]
+
+    def hold(self, slots) -> None:
+        """the slots `slots` (host ints) do not advance on the next hop; every slot is checked before any is taken"""
+        held = [self.slot(s) for s in self.host_slots(slots)]
+        self.holds.update(held)
+
+    def stop(self, slot) -> None:
+        self.stops.add(self.slot(slot))
+
     def start(self, slot, cache_enc=None, cache_dec=None, n=None) -> None:
         s = self.slot(slot)
         v = self.n_max if n is None else self.check_n(n)
@@ -110,14 +147,21 @@ class SessionQueue:
                 raise RuntimeError(f"start: more than {self.max_loads} loads queued for one hop (max_loads_per_hop)")
         self.starts[s] = rec
         self.n[s] = v
+        self.stops.discard(s)
 
     def set_bitrate(self, slot, n) -> None:
         s = self.slot(slot)
         self.n[s] = self.check_n(n)
 
     def clear(self) -> None:
+        """after a hop's upload: drops that hop's starts, bitrates and holds (stops stay)"""
         self.starts.clear()
         self.n.clear()
+        self.holds.clear()
+
+    def reset(self) -> None:
+        self.clear()
+        self.stops.clear()
 
 
 class StateBlock:
@@ -161,6 +205,10 @@ class GraphedHop:
     `step()`.  The graph then starts each group's chain with one hilc_state_slots_apply on the block the hop reads, and the
     quantiser and dequantiser take their per-stream n from a device buffer (rows >= a stream's n of the indices hold -1).
     Pending actions travel from pinned host buffers on the replay stream, only when something changed.
+    Held streams: `step(x, hold=slots)` leaves the slots `slots` (host ints) exactly as they are for that hop (caches
+    bit-identical afterwards, a `start` queued for the hop included; their `x` rows are not read for anything that matters; their
+    wav rows are 0 and indices -1); `stop(slot)` holds a slot on every step until its next `start`, `stopped` lists those slots.
+    Each group's chain ends with one hilc_state_slots_hold, which copies held streams back from the block the hop read.
     `sessions=False` captures exactly the graph of earlier rounds."""
 
     side = "both"                             # the caches a state block holds (GraphedEncodeHop: the encoder's only)
@@ -215,6 +263,9 @@ class GraphedHop:
                 idx = m.quantizer(z, self.n)
                 q = m.dequantizer(idx, self.n)
             wav, _ = m.decoder(q, *src.dec, cache_out=dst.dec)
+        if self.sessions:
+            # after the last write to dst and to this group's outputs
+            ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self.hold[lo:hi], wav=wav, indices=idx)
         return idx, wav
 
     def _hop(self, p: int) -> Tuple[Tensor, Tensor]:
@@ -249,24 +300,29 @@ class GraphedHop:
 
     def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
         """zero history, or resume from caches saved earlier (`wire.save_cache` / `e_in*`, `d_in*`); with sessions also drops
-        every queued action and puts every slot back to the default n"""
+        every queued action, clears every stop and puts every slot back to the default n"""
         with torch.no_grad():
             self.parity = 0
             for (lo, hi), (a, _b) in zip(self.bounds, self.gstate):
                 a.load_(None if cache_enc is None else [c[lo:hi] for c in cache_enc],
                         None if cache_dec is None else [c[lo:hi] for c in cache_dec])
             if self.sessions:
-                self.queue.clear()
+                self.queue.reset()
                 self._uploaded.synchronize()
                 self._h_ctl[0].zero_()
                 self._h_ctl[1].fill_(self.n)
+                self._h_ctl[2].zero_()
                 self._stage[:self._h_ctl.numel()].copy_(self._h_stage[:self._h_ctl.numel()], non_blocking=True)
                 self._uploaded.record()
                 self._action_live = False
+                self._held_live = frozenset()
 
-    def step(self, x: Tensor) -> Tuple[Tensor, Tensor]:
+    def step(self, x: Tensor, hold=None) -> Tuple[Tensor, Tensor]:
+        """`hold`: slots (host ints) that do not advance on this hop (sessions=True only; None or empty: every slot advances)"""
+        held = self._hold_slots(hold)
         self.x.copy_(x)
         if self.sessions:
+            self.queue.hold(held)
             self._upload()
         self.graphs[self.parity].replay()
         out = self.outs[self.parity]
@@ -280,28 +336,30 @@ class GraphedHop:
         layout = self.gstate[0][0].layout
         self.queue = SessionQueue(batch, self.n, max_loads, layout, one_sided=self.side != "both")
         # device side, captured by address, ONE buffer so that a hop's upload is one copy: ctl[0] = action per slot (0 keep,
-        # -1 zero, r >= 1 load record r-1), ctl[1] = n per slot, then the staged records
-        n_ctl = 2 * batch
+        # -1 zero, r >= 1 load record r-1), ctl[1] = n per slot, ctl[2] = 1 where the slot is held, then the staged records
+        n_ctl = 3 * batch
         self._stage = torch.zeros(n_ctl + max_loads * layout.record_len, device=self.device)
         self._h_stage = torch.zeros(self._stage.numel()).pin_memory()    # its pinned host mirror
-        self.ctl = self._stage[:n_ctl].view(torch.int32).view(2, batch)
+        self.ctl = self._stage[:n_ctl].view(torch.int32).view(3, batch)
         self.records = self._stage[n_ctl:].view(max_loads, layout.record_len)
-        self._h_ctl = self._h_stage[:n_ctl].view(torch.int32).view(2, batch)
+        self._h_ctl = self._h_stage[:n_ctl].view(torch.int32).view(3, batch)
         self._h_rec = self._h_stage[n_ctl:].view(max_loads, layout.record_len)
         self.ctl[1].fill_(self.n)
         self._h_ctl[1].fill_(self.n)
-        self.action, self.n_slot = self.ctl[0], self.ctl[1]
+        self.action, self.n_slot, self.hold = self.ctl[0], self.ctl[1], self.ctl[2]
         self._uploaded = torch.cuda.Event()
         self._action_live = False             # the device action row holds the previous hop's actions
+        self._held_live = frozenset()         # the slots the device hold row marks
         for a, b in self.gstate:              # the kernels' layout tables, built before the capture
             a.layout.tables(self.device)
             b.layout.tables(self.device)
 
     def _upload(self) -> None:
-        """queued actions and bitrates -> the graph's device buffers, on the replay stream (an action applies to exactly one
-        hop: the upload after a hop with actions clears them)"""
+        """queued actions, bitrates and holds -> the graph's device buffers, on the replay stream (an action applies to exactly
+        one hop: the upload after a hop with actions clears them; the hold row goes up when it changes)"""
         q = self.queue
-        if not q.pending and not self._action_live:
+        held = q.held
+        if not q.pending and not self._action_live and held == self._held_live:
             return
         self._uploaded.synchronize()          # the previous upload's copy has left the pinned buffer
         h = self._h_ctl
@@ -318,6 +376,7 @@ class GraphedHop:
                 self._h_rec[r].copy_(rec)
         for slot, n in q.n.items():
             h[1, slot] = n
+        _mark(h[2], held)
         used = h.numel() + len(host) * self.records.shape[1]
         self._stage[:used].copy_(self._h_stage[:used], non_blocking=True)
         for r, (_slot, rec) in enumerate(dev, start=len(host)):
@@ -325,11 +384,20 @@ class GraphedHop:
             self.records[r].copy_(rec, non_blocking=True)
         self._uploaded.record(stream)
         self._action_live = bool(q.starts)
+        self._held_live = held
         q.clear()
 
     def _need_sessions(self, what: str) -> None:
         if not self.sessions:
             raise RuntimeError(f"GraphedHop.{what}: construct with sessions=True")
+
+    def _hold_slots(self, hold) -> List[int]:
+        """step's `hold` checked before anything is launched"""
+        slots = SessionQueue.host_slots(hold)
+        if slots:
+            self._need_sessions("step(hold=...)")
+            slots = [self.queue.slot(s) for s in slots]
+        return slots
 
     def _where(self, slot: int) -> Tuple[int, int]:
         for g, (lo, hi) in enumerate(self.bounds):
@@ -350,9 +418,19 @@ class GraphedHop:
         self._need_sessions("set_bitrate")
         self.queue.set_bitrate(slot, n)
 
+    def stop(self, slot: int) -> None:
+        """from the next step on, slot `slot` is held (does not advance) on every step until the next `start(slot, ...)`"""
+        self._need_sessions("stop")
+        self.queue.stop(slot)
+
+    @property
+    def stopped(self) -> Tuple[int, ...]:
+        """the stopped slots, sorted"""
+        return self.queue.stopped if self.sessions else ()
+
     def export(self, slot: int) -> Tuple[List[Tensor], List[Tensor]]:
         """the current 22 + 30 caches of slot `slot` as B = 1 device tensors (one gather launch) — the state after the last
-        step, without actions queued since"""
+        step, without actions queued since (a stopped slot: its caches when it stopped)"""
         self._need_sessions("export")
         g, local = self._where(self.queue.slot(slot))
         blk = self.gstate[g][self.parity]
@@ -544,7 +622,8 @@ class GraphedEncodeHop(GraphedHop):
     blocks (the 22 encoder caches; `state_bytes`).  `step(x)` returns (packets uint8 `[B, packet_bytes(n, T)]`, nbytes int32
     `[B]`), `.indices` the same hop's `[n,B,T]`: static views that the next-but-one `step` overwrites.
     Sessions as in GraphedHop, on the encoder side: `start(slot, cache_enc=None, n=None)`, `set_bitrate(slot, n)`,
-    `export(slot) -> cache_enc`."""
+    `export(slot) -> cache_enc`, `step(x, hold=slots)`, `stop(slot)`; a held row's packet is all zero with nbytes 0 and its
+    `.indices` are -1."""
 
     side = "enc"
 
@@ -580,10 +659,12 @@ class GraphedEncodeHop(GraphedHop):
                 z, _ = m.encoder(self.x, *src.enc, cache_out=dst.enc)
             idx = m.quantizer(z, self.n, n_clip=n_clip)
         packets, nbytes = ops.pack_codes_10bit(idx, n_clip)
+        if self.sessions:
+            ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self.hold, indices=idx, packets=packets, nbytes=nbytes)
         return idx, packets, nbytes
 
-    def step(self, x: Tensor) -> Tuple[Tensor, Tensor]:
-        self.indices, packets, nbytes = super().step(x)
+    def step(self, x: Tensor, hold=None) -> Tuple[Tensor, Tensor]:
+        self.indices, packets, nbytes = super().step(x, hold)
         return packets, nbytes
 
     def start(self, slot: int, cache_enc: Optional[Sequence[Tensor]] = None, n: Optional[int] = None) -> None:
@@ -606,7 +687,9 @@ class GraphedDecodeHop:
     caches).  The returned waveform is a static view that the next-but-one `step` overwrites.
     `frames` may differ from the sender's T (the reference's `num_frames`): packets of consecutive sender hops are re-framed by
     the caller (`wire.unpack_stream_packet` / `pack_stream_packet`).  The per-stream n arrives with every hop, so there is no
-    `set_bitrate`; sessions: `start(slot, cache_dec=None)`, `export(slot) -> cache_dec`."""
+    `set_bitrate`; sessions: `start(slot, cache_dec=None)`, `export(slot) -> cache_dec`, and held streams as in GraphedHop:
+    `step(packets, n_per_stream, hold=slots)` (a late or lost packet: the slot does not advance, its packet row and its
+    n_per_stream entry are not read or checked, its wav row is 0) and `stop(slot)`."""
 
     def __init__(self, model, batch: int, frames: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4):
@@ -622,16 +705,18 @@ class GraphedDecodeHop:
         layout = self.state[0].layout
         loads = int(max_loads_per_hop) if self.sessions else 0
         B = self.batch
-        # ONE device buffer, captured by address: ctl[0] = action per slot, ctl[1] = n per slot, the packets, the staged records
-        self._rec_off = 2 * B + (B * self.stride + 3) // 4
+        # ONE device buffer, captured by address: ctl[0] = action per slot, ctl[1] = n per slot, ctl[2] = 1 where the slot is
+        # held, the packets, the staged records
+        self._n_ctl = 3 * B
+        self._rec_off = self._n_ctl + (B * self.stride + 3) // 4
         self._stage = torch.zeros(self._rec_off + loads * layout.record_len, device=device)
         self._h_stage = torch.zeros(self._stage.numel()).pin_memory()
-        ctl = self._stage[:2 * B].view(torch.int32).view(2, B)
-        self.action, self.n_slot = ctl[0], ctl[1]
-        self.packets = self._stage[2 * B:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
+        ctl = self._stage[:self._n_ctl].view(torch.int32).view(3, B)
+        self.action, self.n_slot, self.hold = ctl[0], ctl[1], ctl[2]
+        self.packets = self._stage[self._n_ctl:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
         self.records = self._stage[self._rec_off:].view(loads, layout.record_len)
-        self._h_ctl = self._h_stage[:2 * B].view(torch.int32).view(2, B)
-        self._h_packets = self._h_stage[2 * B:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
+        self._h_ctl = self._h_stage[:self._n_ctl].view(torch.int32).view(3, B)
+        self._h_packets = self._h_stage[self._n_ctl:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
         self._h_rec = self._h_stage[self._rec_off:].view(loads, layout.record_len)
         self.n_slot.fill_(self.n)
         if self.sessions:
@@ -664,26 +749,41 @@ class GraphedDecodeHop:
         with ops.sched_workspace(self.sched):
             q = m.dequantizer.decode_packed(self.packets, self.n_slot, self.n, self.frames)
             wav, _ = m.decoder(q, *src.dec, cache_out=dst.dec)
+        if self.sessions:
+            ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self.hold, wav=wav)
         return wav
 
-    def _check(self, packets: Tensor, n_per_stream) -> Tensor:
+    def _check(self, packets: Tensor, n_per_stream, held=()) -> Tensor:
+        """n_per_stream as a tensor; the entries of `held` slots are not range-checked and become the graph's n"""
         if isinstance(n_per_stream, Tensor) and n_per_stream.is_cuda:
             raise ValueError("n_per_stream: host ints, not a device tensor")
         n = torch.as_tensor(n_per_stream).reshape(-1)
         if n.is_floating_point() or n.numel() != self.batch:
             raise ValueError(f"n_per_stream: {self.batch} ints expected")
+        if held:
+            n = n.clone()
+            n[torch.tensor(sorted(held), dtype=torch.long)] = self.n
         if int(n.min()) < 1 or int(n.max()) > self.n:
             raise ValueError(f"n_per_stream: every entry must lie in [1, {self.n}]")
         if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or tuple(packets.shape) != (self.batch, self.stride):
             raise ValueError(f"packets: uint8 [{self.batch}, {self.stride}] expected")
         return n
 
-    def step(self, packets: Tensor, n_per_stream) -> Tensor:
-        n = self._check(packets, n_per_stream)
+    def step(self, packets: Tensor, n_per_stream, hold=None) -> Tensor:
+        """`hold`: slots (host ints) that do not advance on this hop (sessions=True only; None or empty: every slot advances)"""
+        held = SessionQueue.host_slots(hold)
+        if held:
+            if not self.sessions:
+                raise RuntimeError("GraphedDecodeHop.step(hold=...): construct with sessions=True")
+            held = [self.queue.slot(s) for s in held]
+        if self.sessions:
+            held = set(held) | self.queue.stops
+        n = self._check(packets, n_per_stream, held)
         self._uploaded.synchronize()          # the previous upload's copy has left the pinned buffer
         B, h = self.batch, self._h_ctl
         h[0].zero_()
         h[1].copy_(n)
+        _mark(h[2], held)
         host, dev = [], []
         if self.sessions:
             q = self.queue
@@ -699,7 +799,7 @@ class GraphedDecodeHop:
             q.clear()
         stream = torch.cuda.current_stream(self.device)
         if packets.is_cuda:
-            self._stage[:2 * B].copy_(self._h_stage[:2 * B], non_blocking=True)
+            self._stage[:self._n_ctl].copy_(self._h_stage[:self._n_ctl], non_blocking=True)
             self.packets.copy_(packets)
         else:
             self._h_packets.copy_(packets)
@@ -723,8 +823,20 @@ class GraphedDecodeHop:
             raise RuntimeError("GraphedDecodeHop.start: construct with sessions=True")
         self.queue.start(slot, None, cache_dec)
 
+    def stop(self, slot: int) -> None:
+        """from the next step on, slot `slot` is held (does not advance) on every step until the next `start(slot, ...)`"""
+        if not self.sessions:
+            raise RuntimeError("GraphedDecodeHop.stop: construct with sessions=True")
+        self.queue.stop(slot)
+
+    @property
+    def stopped(self) -> Tuple[int, ...]:
+        """the stopped slots, sorted"""
+        return self.queue.stopped if self.sessions else ()
+
     def export(self, slot: int) -> List[Tensor]:
-        """the current 30 decoder caches of slot `slot` as B = 1 device tensors (one gather launch)"""
+        """the current 30 decoder caches of slot `slot` as B = 1 device tensors (one gather launch; a stopped slot: its caches
+        when it stopped)"""
         if not self.sessions:
             raise RuntimeError("GraphedDecodeHop.export: construct with sessions=True")
         blk = self.state[self.parity]

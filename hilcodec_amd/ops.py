@@ -827,6 +827,23 @@ _register("state_slots_gather", "(Tensor block, Tensor slice_off, Tensor slice_l
           lambda block, slice_off, slice_len, slots, streams, record_len: block.new_empty(slots.shape[0], record_len))
 
 
+def _state_slots_hold(src, dst, slice_off, slice_len, hold, wav, indices, packets, nbytes):
+    if slice_len.numel() != slice_off.numel():
+        raise RuntimeError("state_slots_hold: slice_off and slice_len differ in length")
+    B = hold.numel()
+    n_max, frames = (0, 0) if indices is None else (indices.shape[0], indices.shape[2])
+    check(lib.hilc_state_slots_hold(_ptr(src), _ptr(dst), _ptr(slice_off, torch.int64), _ptr(slice_len, torch.int32),
+                                    slice_off.numel(), B, _ptr(hold, torch.int32), _ptr(wav), 0 if wav is None else wav.numel() // B,
+                                    _ptr(indices, torch.int64), n_max, frames, _ptr(packets, torch.uint8),
+                                    0 if packets is None else packets.shape[1], _ptr(nbytes, torch.int32), _stream()),
+          "hilc_state_slots_hold")
+
+
+_register("state_slots_hold", "(Tensor src, Tensor(a!) dst, Tensor slice_off, Tensor slice_len, Tensor hold, Tensor(b!)? wav, "
+          "Tensor(c!)? indices, Tensor(d!)? packets, Tensor(e!)? nbytes) -> ()", _state_slots_hold,
+          lambda src, dst, slice_off, slice_len, hold, wav, indices, packets, nbytes: None)
+
+
 # ======================================================================================================
 # per-stream 10-bit packets (graph_step.GraphedEncodeHop / GraphedDecodeHop; format: wire.packet_bytes)
 # ======================================================================================================
@@ -1363,6 +1380,27 @@ def state_slots_gather(block: Tensor, layout: StateLayout, slots: Tensor) -> Ten
         raise RuntimeError("state_slots_gather: block does not match the layout")
     off, lens = layout.tables(block.device)
     return _OPS.state_slots_gather(block, off, lens, slots, layout.streams, layout.record_len)
+
+
+def state_slots_hold(src: Tensor, dst: Tensor, layout: StateLayout, hold: Tensor, wav: Optional[Tensor] = None,
+                     indices: Optional[Tensor] = None, packets: Optional[Tensor] = None, nbytes: Optional[Tensor] = None) -> None:
+    """Streams b with hold[b] != 0 (int32 `[layout.streams]` on the device) do not advance: their parts of `dst` (the block a hop
+    wrote) are copied back from `src` (the block it read), their `wav` rows (`[streams, ...]` fp32) are set to 0, their `indices`
+    (`[n, streams, T]` int64) to -1, their `packets` rows (`[streams, stride]` uint8) and `nbytes` (`[streams]` int32) to 0.
+    Every output is optional; in place."""
+    B = layout.streams
+    if src.numel() < layout.total or dst.numel() < layout.total or hold.numel() != B:
+        raise RuntimeError("state_slots_hold: src, dst or hold does not match the layout")
+    if wav is not None and (wav.shape[0] != B or wav.numel() == 0):
+        raise RuntimeError(f"state_slots_hold: wav must be [{B}, ...]")
+    if indices is not None and (indices.dim() != 3 or indices.shape[1] != B):
+        raise RuntimeError(f"state_slots_hold: indices must be [n, {B}, T]")
+    if packets is not None and (packets.dim() != 2 or packets.shape[0] != B):
+        raise RuntimeError(f"state_slots_hold: packets must be [{B}, stride]")
+    if nbytes is not None and nbytes.numel() != B:
+        raise RuntimeError(f"state_slots_hold: nbytes must have {B} entries")
+    off, lens = layout.tables(src.device)
+    _OPS.state_slots_hold(src, dst, off, lens, hold, wav, indices, packets, nbytes)
 
 
 def pack_codes_10bit(indices: Tensor, n_clip: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:

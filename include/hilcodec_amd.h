@@ -419,6 +419,19 @@ int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* sl
 int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams,
                             const int* slots, int nslots, float* records, void* stream);
 
+/* ---- held streams of a streaming hop (additive under ABI 16) -------------------------------------------------------------------
+ * One entry point added WITHOUT a version bump, as the packet entry points below: it changes no existing signature or struct.
+ * hilc_state_slots_hold: for every stream b with hold[b] != 0 (int32, device, `streams` entries): its slices are copied from `src`
+ * (the block the hop read) to `dst` (the block it wrote), in the layout of hilc_state_slots_apply, so the stream leaves the hop
+ * exactly as it entered it; and its output rows are set: wav[b][0..wav_len) = 0 (fp32 [streams][wav_len]), indices[s][b][t] = -1
+ * for s < n_max, t < frames (int64 [n_max][streams][frames]), packets[b][0..stride) = 0 (uint8 [streams][stride]), nbytes[b] = 0
+ * (int32 [streams]).  Each output pointer may be NULL (that output is not touched); a non-NULL one with its length <= 0:
+ * HILC_ERR_SHAPE.  Meant to run at the tail of every hop (captured in its graph, after the last write to `dst` and to the
+ * outputs): a fixed grid that leaves after one barrier when no entry of `hold` is set.  nslices <= 128, else HILC_ERR_UNSUPPORTED. */
+int hilc_state_slots_hold(const float* src, float* dst, const int64_t* slice_off, const int* slice_len, int nslices, int streams,
+                          const int* hold, float* wav, int wav_len, int64_t* indices, int n_max, int frames, uint8_t* packets,
+                          int stride, int* nbytes, void* stream);
+
 /* ---- per-stream 10-bit packets of a streaming hop (additive under ABI 16) ------------------------------------------------------
  * Two entry points added WITHOUT a version bump: they change no existing signature or struct, so a binding of ABI 16 that does
  * not use them is unaffected; binders find them by symbol (dlsym), not by version.
