@@ -72,6 +72,8 @@ SIGNATURES = {
     "hilc_state_slots_hold": [_p, _p, _p, _p, _i, _i, _p, _p, _i, _p, _i, _i, _p, _i, _p, _p],
     "hilc_pack_codes_10bit": [_p, _p, _p, _p, _i, _i, _i, _p],
     "hilc_rvq_decode_packed": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
+    "hilc_conceal_prepare": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "hilc_conceal_gain": [_p, _p, _p, _p, _i, _i, _i, _p],
 }
 
 ABI_VERSION = 16

@@ -1,0 +1,138 @@
+// Loss concealment of the graphed receiver (graph_step.GraphedDecodeHop(conceal=True)): a slot whose packet did not arrive
+// is decoded from the codes of the last frame it received, repeated over the hop, and its wav row is faded towards silence over
+// F hops; a received packet after a loss fades back in.  Two launches per hop, both captured in the receiver's graph:
+//
+//   hilc_conceal_prepare  after hilc_state_slots_apply, before hilc_rvq_decode_packed.  Works on the receiver's per-hop control
+//                         buffer (re-uploaded in full by the host every hop, so the graph may write into it for this hop): per slot
+//                         it updates the concealment state, writes a substitute packet and n for a concealed slot, marks a
+//                         device-decided hold, and records the slot's gain ramp.
+//   hilc_conceal_gain     after the decoder, before hilc_state_slots_hold: multiplies the wav rows that have a ramp.
+//
+// State row of slot b (int32, n_max + 3 words): [0] run k (hops lost in a row, 0..F), [1] has-codes, [2] stored n, [3 + s] code of
+// stage s of the last frame of the last packet received (0 for s >= stored n).  Ramp word of slot b: 0 none; r in 1..F: a lost hop,
+// gains G[r - 1] -> G[r]; r in -F..-1: a received hop after -r lost ones, gains G[-r] -> G[0].
+//
+// Both kernels: one wave per slot (4 per workgroup), wave-uniform branches only.  The common case (every packet received) costs
+// one round of loads and one of stores per slot in prepare, and one load per slot in gain.
+#include "common.h"
+
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int WAVES = THREADS / 64;
+constexpr int MAX_N = 32;          // stages per stored frame: as hilc_rvq_decode_packed
+constexpr int ST_RUN = 0, ST_HAS = 1, ST_N = 2, ST_CODES = 3;
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ int code_at(const uint8_t* p, int bit) {
+  const uint8_t* q = p + (bit >> 3);
+  const uint32_t v = ((uint32_t)q[0] << 8) | (uint32_t)q[1];
+  return (int)((v >> (6 - (bit & 7))) & 1023u);
+}
+
+__global__ __launch_bounds__(THREADS) void conceal_prepare_kernel(int* __restrict__ state, const int* __restrict__ action,
+                                                                  int* __restrict__ hold, const int* __restrict__ lost,
+                                                                  int* __restrict__ n_slot, uint8_t* __restrict__ packets,
+                                                                  int* __restrict__ ramp, int B, int T, int n_max, int stride, int F) {
+  const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + ((int)threadIdx.x >> 6));
+  if (b >= B) return;
+  const int lane = threadIdx.x & 63;
+  const int words = n_max + 3;
+  int* st = state + (long)b * words;
+  uint8_t* pk = packets + (long)b * stride;
+  // every load of the slot in one round: the last frame's code of stage `lane` is read whether or not the packet arrived
+  const int act = action[b], held = hold[b], gone = lost[b], n_in = n_slot[b];
+  const int old = lane < words ? st[lane] : 0;
+  const int fresh = lane < n_max ? code_at(pk, 10 * (lane * T + T - 1)) : 0;
+  const int run0 = __builtin_amdgcn_readfirstlane(__shfl(old, ST_RUN));
+  const int has0 = __builtin_amdgcn_readfirstlane(__shfl(old, ST_HAS));
+  const int n0 = __builtin_amdgcn_readfirstlane(__shfl(old, ST_N));
+  const bool reset = act != 0;                         // a start or a resume on this hop: no stored codes, run 0
+  const int k = reset ? 0 : clampi(run0, 0, F);
+  const bool has = !reset && has0 != 0;
+  int word = reset ? 0 : old;                          // this lane's word of the state row after the hop
+  int r = 0;
+  if (held != 0) {
+    // host-held or stopped: the state is left as it is (a start on the same hop is applied first)
+  } else if (gone == 0) {
+    const int nb = clampi(n_in, 1, n_max);
+    const int s = lane - ST_CODES;
+    const int c = __shfl(fresh, s < 0 ? 0 : s);        // lane s read stage s's code of the packet's last frame
+    word = lane == ST_RUN ? 0 : (lane == ST_HAS ? 1 : (lane == ST_N ? nb : (s < nb ? c : 0)));
+    r = k > 0 ? -k : 0;
+  } else if (has && k < F) {
+    const int nb = clampi(n0, 1, n_max);
+    const int count = nb * T;
+    const int len = (10 * count + 7) >> 3;
+    // the substitute packet: stage s of every frame = stored code s, in the layout of hilc_pack_codes_10bit
+    for (int j0 = 0; j0 < stride; j0 += 64) {
+      const int j = j0 + lane;
+      const int i0 = (8 * j) / 10;
+      const int off = 8 * j - 10 * i0;
+      const int s0 = min(i0 / T, MAX_N - 1), s1 = min((i0 + 1) / T, MAX_N - 1);
+      const uint32_t c0 = (uint32_t)__shfl(old, ST_CODES + s0) & 1023u;
+      const uint32_t c1 = (uint32_t)__shfl(old, ST_CODES + s1) & 1023u;
+      if (j < stride) {
+        uint32_t out = 0;
+        if (j < len) {
+          const uint32_t w = (c0 << 10) | (i0 + 1 < count ? c1 : 0u);
+          out = (w >> (12 - off)) & 0xFFu;
+        }
+        pk[j] = (uint8_t)out;
+      }
+    }
+    if (lane == 0) n_slot[b] = nb;
+    if (lane == ST_RUN) word = k + 1;
+    r = k + 1;
+  } else {
+    // nothing received since the start, or faded out: a device-decided hold
+    if (lane == 0) hold[b] = 1;
+  }
+  if (lane < words) st[lane] = word;
+  if (lane == 0) ramp[b] = r;
+}
+
+__global__ __launch_bounds__(THREADS) void conceal_gain_kernel(float* __restrict__ wav, const int* __restrict__ ramp,
+                                                               const float* __restrict__ gains, const float* __restrict__ weights,
+                                                               int B, int S, int F) {
+  const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + ((int)threadIdx.x >> 6));
+  if (b >= B) return;
+  const int r = ramp[b];
+  if (r == 0 || r > F || r < -F) return;               // no ramp: the row is not touched
+  const int a = r > 0 ? r - 1 : -r;
+  const int c = r > 0 ? r : 0;
+  const float ga = gains[a];
+  const float d = __fsub_rn(gains[c], ga);
+  float* row = wav + (long)b * S;
+  for (int s = threadIdx.x & 63; s < S; s += 64) row[s] = __fmul_rn(row[s], __fadd_rn(ga, __fmul_rn(d, weights[s])));
+}
+
+}  // namespace
+
+extern "C" int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets,
+                                    int* ramp, int B, int T, int n_max, int fade_hops, void* stream) {
+  if (!state || !action || !hold || !lost || !n_per_stream || !packets || !ramp) return HILC_ERR_NULL;
+  if (B <= 0 || T <= 0) return HILC_ERR_SHAPE;
+  if (n_max < 1 || fade_hops < 1) return HILC_ERR_RANGE;
+  if (n_max > MAX_N) return HILC_ERR_UNSUPPORTED;
+  const long stride = (10L * n_max * T + 7) / 8;
+  if (stride > (1L << 30)) return HILC_ERR_SHAPE;
+  HILC_CLEAR_ERROR();
+  hipLaunchKernelGGL(conceal_prepare_kernel, dim3((unsigned)((B + WAVES - 1) / WAVES)), dim3(THREADS), 0, (hipStream_t)stream, state,
+                     action, hold, lost, n_per_stream, packets, ramp, B, T, n_max, (int)stride, fade_hops);
+  HILC_CHECK_LAUNCH();
+  return HILC_OK;
+}
+
+extern "C" int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples,
+                                 int fade_hops, void* stream) {
+  if (!wav || !ramp || !gains || !weights) return HILC_ERR_NULL;
+  if (B <= 0 || samples <= 0) return HILC_ERR_SHAPE;
+  if (fade_hops < 1) return HILC_ERR_RANGE;
+  HILC_CLEAR_ERROR();
+  hipLaunchKernelGGL(conceal_gain_kernel, dim3((unsigned)((B + WAVES - 1) / WAVES)), dim3(THREADS), 0, (hipStream_t)stream, wav, ramp,
+                     gains, weights, B, samples, fade_hops);
+  HILC_CHECK_LAUNCH();
+  return HILC_OK;
+}

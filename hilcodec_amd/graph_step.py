@@ -135,6 +135,19 @@ class SessionQueue:
     def stop(self, slot) -> None:
         self.stops.add(self.slot(slot))
 
+    def lost_slots(self, lost, hold=()) -> List[int]:
+        """the receiver's `lost` (host ints) checked before anything is launched: every slot in range (IndexError), none also in
+        `hold` (this hop's checked holds) and none stopped (ValueError: a held slot's packet is not read at all, a stopped slot has
+        no stream to conceal)"""
+        slots = sorted({self.slot(s) for s in self.host_slots(lost)})
+        both = set(slots) & {int(s) for s in hold}
+        if both:
+            raise ValueError(f"lost: slots {sorted(both)} are also held on this hop")
+        stopped = set(slots) & self.stops
+        if stopped:
+            raise ValueError(f"lost: slots {sorted(stopped)} are stopped (start them first)")
+        return slots
+
     def start(self, slot, cache_enc=None, cache_dec=None, n=None) -> None:
         s = self.slot(slot)
         v = self.n_max if n is None else self.check_n(n)
@@ -689,16 +702,30 @@ class GraphedDecodeHop:
     the caller (`wire.unpack_stream_packet` / `pack_stream_packet`).  The per-stream n arrives with every hop, so there is no
     `set_bitrate`; sessions: `start(slot, cache_dec=None)`, `export(slot) -> cache_dec`, and held streams as in GraphedHop:
     `step(packets, n_per_stream, hold=slots)` (a late or lost packet: the slot does not advance, its packet row and its
-    n_per_stream entry are not read or checked, its wav row is 0) and `stop(slot)`."""
+    n_per_stream entry are not read or checked, its wav row is 0) and `stop(slot)`.
+    `conceal=True` (needs `sessions`): `step(..., lost=slots)` conceals the slots whose packet did not arrive instead of holding
+    them.  Each slot keeps the codes of the last frame of the last packet it received; a lost hop is decoded from those codes
+    repeated over the hop (with that packet's n) and faded from G[k] to G[k+1] over the hop (k = hops lost in a row before it,
+    G[k] = (F - k) / F, F = `fade_hops`); the first received hop after k >= 1 lost ones fades from G[k] back to 1.  A lost slot
+    with nothing received since its start, or with k = F, is held by the graph itself (wav 0, caches unchanged).  Ramps and
+    tables: `wire.conceal_tables`; substitute packets: `wire.conceal_packet`.  `concealed` is each slot's k after the last step.
+    Graph: hilc_conceal_prepare after hilc_state_slots_apply (rewrites this hop's packet, n and hold rows of concealed slots),
+    hilc_conceal_gain after the decoder.  `conceal=False` captures exactly the graph of earlier rounds."""
 
     def __init__(self, model, batch: int, frames: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
-                 max_loads_per_hop: int = 4):
+                 max_loads_per_hop: int = 4, conceal: bool = False, fade_hops: int = 4):
         self.model, self.batch, self.frames, self.n, self.device = model, int(batch), int(frames), int(n), device
         if not 1 <= self.n <= len(model.dequantizer.layers):
             raise ValueError(f"n = {n} outside [1, {len(model.dequantizer.layers)}]")
         self.sessions = bool(sessions)
         if self.sessions and max_loads_per_hop < 1:
             raise ValueError("max_loads_per_hop must be >= 1")
+        self.conceal = bool(conceal)
+        if self.conceal and not self.sessions:
+            raise ValueError("GraphedDecodeHop(conceal=True) needs sessions=True")
+        if isinstance(fade_hops, bool) or int(fade_hops) != fade_hops or fade_hops < 1:
+            raise ValueError(f"fade_hops must be an int >= 1, got {fade_hops!r}")
+        self.fade_hops = int(fade_hops)
         self.stride = wire.packet_bytes(self.n, self.frames)
         self.state = (StateBlock(model, batch, device, "dec"), StateBlock(model, batch, device, "dec"))
         self.parity = 0
@@ -706,16 +733,18 @@ class GraphedDecodeHop:
         loads = int(max_loads_per_hop) if self.sessions else 0
         B = self.batch
         # ONE device buffer, captured by address: ctl[0] = action per slot, ctl[1] = n per slot, ctl[2] = 1 where the slot is
-        # held, the packets, the staged records
-        self._n_ctl = 3 * B
+        # held, (conceal) ctl[3] = 1 where its packet was lost, the packets, the staged records
+        rows = 4 if self.conceal else 3
+        self._n_ctl = rows * B
         self._rec_off = self._n_ctl + (B * self.stride + 3) // 4
         self._stage = torch.zeros(self._rec_off + loads * layout.record_len, device=device)
         self._h_stage = torch.zeros(self._stage.numel()).pin_memory()
-        ctl = self._stage[:self._n_ctl].view(torch.int32).view(3, B)
+        ctl = self._stage[:self._n_ctl].view(torch.int32).view(rows, B)
         self.action, self.n_slot, self.hold = ctl[0], ctl[1], ctl[2]
+        self.lost = ctl[3] if self.conceal else None
         self.packets = self._stage[self._n_ctl:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
         self.records = self._stage[self._rec_off:].view(loads, layout.record_len)
-        self._h_ctl = self._h_stage[:self._n_ctl].view(torch.int32).view(3, B)
+        self._h_ctl = self._h_stage[:self._n_ctl].view(torch.int32).view(rows, B)
         self._h_packets = self._h_stage[self._n_ctl:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
         self._h_rec = self._h_stage[self._rec_off:].view(loads, layout.record_len)
         self.n_slot.fill_(self.n)
@@ -723,6 +752,11 @@ class GraphedDecodeHop:
             self.queue = SessionQueue(B, self.n, loads, layout, one_sided=True)
             for blk in self.state:
                 blk.layout.tables(device)
+        if self.conceal:
+            # per slot: run k, has-codes, stored n, the stored frame's n codes (updated in place by hilc_conceal_prepare once per hop)
+            self._conceal = torch.zeros(B, self.n + 3, dtype=torch.int32, device=device)
+            gains, weights = wire.conceal_tables(self.fade_hops, 320 * self.frames)
+            self._gains, self._weights = gains.to(device), weights.to(device)
         self._uploaded = torch.cuda.Event()
         self.sched = ops.SchedWorkspace(device)
         self.graphs, self.outs = _capture_pair(self._hop, self._zero, device, warmup)
@@ -737,18 +771,33 @@ class GraphedDecodeHop:
         """the CURRENT 30 decoder caches of all streams (views of the state block)"""
         return self.state[self.parity].dec
 
+    @property
+    def concealed(self) -> Tensor:
+        """int32 `[B]` device view: each slot's run of lost hops after the last step (0: decoded from a received packet, or no
+        run; k >= 1: k hops lost in a row, at most `fade_hops`).  Read-only: written by the graph."""
+        if not self.conceal:
+            raise RuntimeError("GraphedDecodeHop.concealed: construct with conceal=True")
+        return self._conceal[:, 0]
+
     def _zero(self) -> None:
         for blk in self.state:
             blk.zero_()
+        if self.conceal:
+            self._conceal.zero_()
 
     def _hop(self, p: int) -> Tensor:
         m = self.model
         src, dst = self.state[p], self.state[p ^ 1]
         if self.sessions:
             ops.state_slots_apply(src.buffer, src.layout, self.action, self.records)
+        if self.conceal:
+            ramp = ops.conceal_prepare(self._conceal, self.action, self.hold, self.lost, self.n_slot, self.packets, self.frames,
+                                       self.fade_hops)
         with ops.sched_workspace(self.sched):
             q = m.dequantizer.decode_packed(self.packets, self.n_slot, self.n, self.frames)
             wav, _ = m.decoder(q, *src.dec, cache_out=dst.dec)
+        if self.conceal:
+            ops.conceal_gain(wav, ramp, self._gains, self._weights)
         if self.sessions:
             ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self.hold, wav=wav)
         return wav
@@ -769,21 +818,30 @@ class GraphedDecodeHop:
             raise ValueError(f"packets: uint8 [{self.batch}, {self.stride}] expected")
         return n
 
-    def step(self, packets: Tensor, n_per_stream, hold=None) -> Tensor:
-        """`hold`: slots (host ints) that do not advance on this hop (sessions=True only; None or empty: every slot advances)"""
+    def step(self, packets: Tensor, n_per_stream, hold=None, lost=None) -> Tensor:
+        """`hold`: slots (host ints) that do not advance on this hop (sessions=True only; None or empty: every slot advances).
+        `lost`: slots (host ints) whose packet for this hop did not arrive (conceal=True only): concealed; their packet rows and
+        n_per_stream entries are not read or checked"""
         held = SessionQueue.host_slots(hold)
         if held:
             if not self.sessions:
                 raise RuntimeError("GraphedDecodeHop.step(hold=...): construct with sessions=True")
             held = [self.queue.slot(s) for s in held]
+        gone = SessionQueue.host_slots(lost)
+        if gone and not self.conceal:
+            raise RuntimeError("GraphedDecodeHop.step(lost=...): construct with conceal=True")
+        if self.conceal:
+            gone = self.queue.lost_slots(gone, held)
         if self.sessions:
             held = set(held) | self.queue.stops
-        n = self._check(packets, n_per_stream, held)
+        n = self._check(packets, n_per_stream, set(held) | set(gone))
         self._uploaded.synchronize()          # the previous upload's copy has left the pinned buffer
         B, h = self.batch, self._h_ctl
         h[0].zero_()
         h[1].copy_(n)
         _mark(h[2], held)
+        if self.conceal:
+            _mark(h[3], gone)
         host, dev = [], []
         if self.sessions:
             q = self.queue

@@ -882,6 +882,40 @@ def _rvq_decode_packed(packets, n_clip, codebooks, n, frames):
 _register("rvq_decode_packed", "(Tensor packets, Tensor? n_clip, Tensor codebooks, int n, int frames) -> Tensor", _rvq_decode_packed,
           lambda packets, n_clip, codebooks, n, frames: codebooks.new_empty(packets.shape[0], frames, codebooks.shape[2]))
 
+
+# ======================================================================================================
+# loss concealment of the receiver (graph_step.GraphedDecodeHop(conceal=True); semantics: include/hilcodec_amd.h)
+# ======================================================================================================
+def _conceal_prepare(state, action, hold, lost, n_slot, packets, frames, fade_hops):
+    B = action.numel()
+    if state.dim() != 2 or state.shape[0] != B or hold.numel() != B or lost.numel() != B or n_slot.numel() != B:
+        raise RuntimeError(f"conceal_prepare: state must be [{B}, n_max + 3] and hold, lost, n_slot [{B}]")
+    n_max = state.shape[1] - 3
+    if packets.dim() != 2 or packets.shape[0] != B or packets.shape[1] != _packet_stride(max(n_max, 0), frames):
+        raise RuntimeError(f"conceal_prepare: packets must be [{B}, {_packet_stride(max(n_max, 0), frames)}]")
+    ramp = _new(state, B, dtype=torch.int32)
+    check(lib.hilc_conceal_prepare(_ptr(state, torch.int32), _ptr(action, torch.int32), _ptr(hold, torch.int32), _ptr(lost, torch.int32),
+                                   _ptr(n_slot, torch.int32), _ptr(packets, torch.uint8), _ptr(ramp, torch.int32), B, frames, n_max,
+                                   fade_hops, _stream()), "hilc_conceal_prepare")
+    return ramp
+
+
+_register("conceal_prepare", "(Tensor(a!) state, Tensor action, Tensor(b!) hold, Tensor lost, Tensor(c!) n_slot, Tensor(d!) packets, "
+          "int frames, int fade_hops) -> Tensor", _conceal_prepare,
+          lambda state, action, hold, lost, n_slot, packets, frames, fade_hops: state.new_empty(action.shape[0], dtype=torch.int32))
+
+
+def _conceal_gain(wav, ramp, gains, weights):
+    B = ramp.numel()
+    if wav.shape[0] != B or wav.numel() == 0 or weights.numel() * B != wav.numel() or gains.numel() < 2:
+        raise RuntimeError(f"conceal_gain: wav must be [{B}, ...] with weights.numel() samples per row, gains [fade_hops + 1]")
+    check(lib.hilc_conceal_gain(_ptr(wav), _ptr(ramp, torch.int32), _ptr(gains), _ptr(weights), B, weights.numel(), gains.numel() - 1,
+                                _stream()), "hilc_conceal_gain")
+
+
+_register("conceal_gain", "(Tensor(a!) wav, Tensor ramp, Tensor gains, Tensor weights) -> ()", _conceal_gain,
+          lambda wav, ramp, gains, weights: None)
+
 _OPS = torch.ops.hilcodec
 
 
@@ -1420,3 +1454,19 @@ def rvq_decode_packed(packets: Tensor, codebooks: Tensor, n: int, frames: int, n
     if n_clip is not None and n_clip.numel() != packets.shape[0]:
         raise RuntimeError(f"n_clip needs {packets.shape[0]} entries, got {n_clip.numel()}")
     return _OPS.rvq_decode_packed(packets, n_clip, codebooks, int(n), int(frames))
+
+
+def conceal_prepare(state: Tensor, action: Tensor, hold: Tensor, lost: Tensor, n_slot: Tensor, packets: Tensor, frames: int,
+                    fade_hops: int) -> Tensor:
+    """The receiver's concealment step before its packed dequantiser, in place on its per-hop control rows (int32 `[B]` device
+    rows `action`, `hold`, `lost`, `n_slot`; `packets` uint8 `[B, wire.packet_bytes(n_max, frames)]`) and the concealment state
+    (int32 `[B, n_max + 3]`): received slots store their last frame, concealed slots get the substitute packet and n, slots with
+    nothing to repeat are held.  Returns the per-slot ramp word (int32 `[B]`) that `conceal_gain` reads."""
+    return _OPS.conceal_prepare(state, action, hold, lost, n_slot, packets, int(frames), int(fade_hops))
+
+
+def conceal_gain(wav: Tensor, ramp: Tensor, gains: Tensor, weights: Tensor) -> None:
+    """wav `[B, ...]` (fp32, `weights.numel()` samples per row) times the fade ramp of each row with a ramp word (`conceal_prepare`):
+    gain = G[a] + (G[c] - G[a]) * W[s], each operation rounded on its own in fp32; `gains` = G `[F + 1]`, `weights` = W
+    (`wire.conceal_tables`).  Rows without a ramp are not touched; in place."""
+    _OPS.conceal_gain(wav, ramp, gains, weights)

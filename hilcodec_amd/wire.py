@@ -81,6 +81,26 @@ def unpack_stream_packet(blob: bytes, n: int, T: int) -> Tensor:
     return unpack_indices_10bit(struct.pack("<III", n, 1, T) + bytes(blob[:packet_bytes(n, T)]))[:, 0, :]
 
 
+
+# Loss concealment of the receiver (graph_step.GraphedDecodeHop(conceal=True)): a lost hop is decoded from the codes of the last
+# frame received, repeated over the hop, and faded.  These are the definitions the receiver's kernels follow.
+def conceal_packet(packet: bytes, n: int, T: int) -> bytes:
+    """the substitute packet for a stream whose last received packet is `packet` (`n` stages x `T` frames): that packet's last
+    frame's n codes repeated over T frames, in the packet format"""
+    codes = unpack_stream_packet(packet, n, T)
+    return pack_stream_packet(codes[:, -1:].expand(int(n), int(T)).contiguous())
+
+
+def conceal_tables(fade_hops: int, samples: int) -> Tuple[Tensor, Tensor]:
+    """(G, W) fp32: G[k] = (F - k) / F for k = 0..F, the gain after k lost hops in a row, and W[s] = (s + 1) / S for s < S =
+    `samples`, the weight of sample s on a hop's ramp; each computed in float64 and rounded once to fp32"""
+    F, S = int(fade_hops), int(samples)
+    if F < 1 or S < 1:
+        raise ValueError("fade_hops and samples must be >= 1")
+    G = ((F - torch.arange(F + 1, dtype=torch.float64)) / F).float()
+    W = ((torch.arange(S, dtype=torch.float64) + 1) / S).float()
+    return G, W
+
 # ---------------------------------------------------------------- caches
 def save_cache_npz(path: str, caches: Sequence[Tensor], prefix: str) -> None:
     """prefix 'e_in' (encoder, 22 tensors) or 'd_in' (decoder, 30)."""

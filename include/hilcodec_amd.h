@@ -37,7 +37,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -451,6 +451,32 @@ int hilc_pack_codes_10bit(const int64_t* indices, const int* n_per_stream, uint8
                           void* stream);
 int hilc_rvq_decode_packed(const uint8_t* packets, const int* n_per_stream, const float* codebooks, float* q, int B, int C, int T,
                            int K, int Nq, int n_max, void* stream);
+
+/* ---- loss concealment of the packet receiver (additive under ABI 16) ------------------------------------------------------------
+ * Two entry points added WITHOUT a version bump, as the packet entry points above.  A receiving hop of B streams, T frames and
+ * packets of at most n_max stages (layout of hilc_rvq_decode_packed) keeps per stream b one int32 state row of n_max + 3 words at
+ * state + b (n_max + 3): [0] run k = hops lost in a row (0..F), [1] has-codes (0/1), [2] stored n, [3 + s] for s < n_max the code of
+ * stage s of the LAST frame of the last packet received (0 for s >= stored n).  All zero = a fresh stream.  F = fade_hops >= 1.
+ * hilc_conceal_prepare, at the head of the hop (after hilc_state_slots_apply, before hilc_rvq_decode_packed), per stream b, every
+ * array int32 [B] on the device unless named otherwise:
+ *   action[b] != 0 (a start or a resume on this hop, the action row of hilc_state_slots_apply): the state row is zeroed first;
+ *   hold[b] != 0: nothing else (ramp[b] = 0);
+ *   else lost[b] == 0 (received): the row stores the packet's last frame (stage s < n_b, n_b = n_per_stream[b] clamped to
+ *     [1, n_max]) and n_b, has-codes 1, run 0; ramp[b] = -k if the run k was >= 1, else 0;
+ *   else (lost) with has-codes and k < F: packets[b][0..stride) (uint8 [B][stride], stride = ceil(10 n_max T / 8)) is rewritten
+ *     as the stored codes repeated over T frames in the 10-bit packet layout, n_per_stream[b] = stored n, run k + 1,
+ *     ramp[b] = k + 1;
+ *   else (lost, nothing received since the start, or k = F): hold[b] = 1 (hilc_state_slots_hold keeps the stream), ramp[b] = 0.
+ * A stored run > F counts as F, a stored n is clamped to [1, n_max] and codes to 10 bits.  n_max or fade_hops < 1:
+ * HILC_ERR_RANGE; n_max > 32: HILC_ERR_UNSUPPORTED.
+ * hilc_conceal_gain, after the decoder (before hilc_state_slots_hold): for each stream with ramp[b] in 1..F (a = ramp - 1,
+ * c = ramp) or in -F..-1 (a = -ramp, c = 0), wav[b][s] (fp32 [B][samples]) *= gains[a] + (gains[c] - gains[a]) * weights[s], every
+ * operation rounded on its own in fp32 (no contraction); gains fp32 [F + 1], weights fp32 [samples].  Any other ramp value: the row
+ * is not touched.  Both: one wave per stream; fade_hops < 1: HILC_ERR_RANGE. */
+int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp,
+                         int B, int T, int n_max, int fade_hops, void* stream);
+int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops,
+                      void* stream);
 
 #ifdef __cplusplus
 }
