@@ -11,8 +11,12 @@ is an all_gather of per-rank counters over RCCL after the timed region.
 
 Other workloads: `--model hil_music` (configs[2]), `--mode streaming` (configs[3]: 1024 concurrent
 streams per GPU, one 320-sample hop per step, the 52 cache tensors of every stream resident in HBM).
-The DEFAULT invocation also times short runs of configs[2] and configs[3] after the headline region and
-reports them under `other_configs` of the same JSON line (they are never part of `value`).
+
+A plain run does only what the headline line needs: set-up, W warm-up steps, the K timed steps, the dump
+of `--dump-outputs` and the JSON line.  Everything else is measured with `--full` alone, after the timed
+region: the CPU baseline and the parity census riding on it, the sustained clock / power probe, and (for
+the default invocation, or `--other-configs`) short runs of configs[2] and configs[3] reported under
+`other_configs` of the same JSON line (they are never part of `value`).
 
 Multi-GPU on one GPU: `--force-dist` initialises the RCCL process group even at world size 1 (so that
 `init_process_group("nccl", device_id=...)`, the barriers and the counters all_gather really execute);
@@ -26,7 +30,7 @@ Prints ONE JSON line (rank 0) with
   roofline     — dominant kernel = the fp32-MFMA GEMM core (pointwise convs and everything fused
                  onto them), every launch timed with HIP events on the launch stream INSIDE the timed
                  region; achieved = algorithmic FLOPs / summed launch time; peak 157.3 TFLOP/s.
-  cpu_baseline — the CPU oracle (restatement of the reference in plain torch fp32 ops, bit-identical
+  cpu_baseline — (--full) the CPU oracle (restatement of the reference in plain torch fp32 ops, bit-identical
                  to the reference, tests/test_oracle_vs_reference.py) timed on this box's host cores
                  over a bounded sample of the same workload (1 warm-up + 3 timed passes per thread
                  setting, median)."""
@@ -59,12 +63,15 @@ def parse():
     ap.add_argument("--mode", default="offline", choices=["offline", "streaming"])
     ap.add_argument("--batch", type=int, default=None, help="clips (offline) / streams (streaming) per GPU")
     ap.add_argument("--samples", type=int, default=24000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-clock-probe", action="store_true", help="skip the 2.5 s sustained clock / power sample")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure what the headline figure does not need: "
+                    "the CPU baseline and its parity census, the sustained clock / power probe and, for the default invocation, the "
+                    "short configs[2] / configs[3] lines (the --no-* switches below leave parts out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity census")
+    ap.add_argument("--no-clock-probe", action="store_true", help="with --full: skip the 2.5 s sustained clock / power sample")
     ap.add_argument("--no-launch-timing", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="default run only: skip the short configs[2] / configs[3] lines")
-    ap.add_argument("--other-configs", action="store_true", help="add the short configs[2] / configs[3] lines to a non-default offline "
-                    "invocation too (sizes follow --batch: that many clips, four times as many streams)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full, default run only: skip the short configs[2] / configs[3] lines")
+    ap.add_argument("--other-configs", action="store_true", help="with --full: add the short configs[2] / configs[3] lines to a non-default "
+                    "offline invocation too (sizes follow --batch: that many clips, four times as many streams)")
     ap.add_argument("--pipeline", action="store_true", help="with --graph: two-stage software pipeline over hops "
                     "(decoder of hop i-1 beside the encoder of hop i on a second HIP stream; +1 hop output latency)")
     ap.add_argument("--graph", action="store_true", help="streaming mode: replay each hop as one HIP graph "
@@ -90,6 +97,11 @@ def parse():
         ap.error("--emulate-rank and --emulate-world go together")
     if a.emulate_world is not None and not 0 <= a.emulate_rank < a.emulate_world:
         ap.error("--emulate-rank must be in [0, --emulate-world)")
+    if a.other_configs and not a.full:
+        ap.error("--other-configs adds to a --full run")
+    if not a.full:
+        # a plain run: the headline line and nothing after the timed region but the dump (launch timing stays: it rides inside the timed steps)
+        a.no_cpu_baseline = a.no_clock_probe = a.no_other_configs = True
     if a.model is None:
         a.model = "hil_music" if ((a.gpus == 8 or a.emulate_world == 8) and a.mode == "offline") else "hil_speech"
     if a.mode == "offline":

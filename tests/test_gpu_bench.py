@@ -1,7 +1,7 @@
 """GPU: the bench.py contract on a small workload — one JSON line per invocation with the fields the driver and the judge
 read (metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype /
-data / config.workload / roofline / cpu_baseline), for the headline mode, the streaming schedules, the launch-structure
-A/B switch and the multi-GPU plumbing at world size 1."""
+data / config.workload / roofline, and with --full cpu_baseline / other_configs), for the headline mode, the streaming schedules,
+the launch-structure A/B switch and the multi-GPU plumbing at world size 1."""
 import json
 import os
 import subprocess
@@ -34,7 +34,7 @@ def check_common(d, steps, warmup):
 
 
 def test_headline_line_small():
-    d = run_bench("--batch", "8", "--steps", "2", "--warmup", "1", "--cpu-clips", "2", "--no-clock-probe", "--other-configs")
+    d = run_bench("--full", "--batch", "8", "--steps", "2", "--warmup", "1", "--cpu-clips", "2", "--no-clock-probe", "--other-configs")
     check_common(d, 2, 1)
     assert d["ranks"]["process_group_initialized"] is False and d["ranks"]["backend"].startswith("none")
     # the short configs[2] / configs[3] lines ride in the same JSON line (the default invocation runs them at full size)
@@ -58,6 +58,15 @@ def test_headline_line_small():
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and "sample" in c
     p = d["parity_census"]
     assert p["index_mismatch_frames"] == 0 and p["genuine_mismatches"] == 0 and p["dwav_max_end_to_end"] < 1e-4
+
+
+def test_plain_line_is_the_headline_only():
+    """Without --full nothing runs after the timed region: no CPU baseline, parity census, clock probe or other_configs; the
+    launch-timed roofline rides inside the timed steps and stays"""
+    d = run_bench("--batch", "8", "--steps", "2", "--warmup", "1")
+    check_common(d, 2, 1)
+    assert not {"cpu_baseline", "parity_census", "other_configs"} & set(d)
+    assert "sustained" not in d["roofline"] and d["roofline"]["achieved"] > 0
 
 
 @pytest.mark.parametrize("extra", [(), ("--graph",), ("--graph", "--pipeline")])

@@ -9,13 +9,13 @@ TAG=${1:-profile}
 R=$(pwd)
 O=$R/gpurun_out/$TAG
 mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
-python bench.py --model hil_music --no-cpu-baseline > $O/bench_hil_music.json 2>> $O/bench.err
-python bench.py --mode streaming --no-cpu-baseline > $O/bench_streaming.json 2>> $O/bench.err
-python bench.py --mode streaming --graph --no-cpu-baseline > $O/bench_streaming_graph.json 2>> $O/bench.err
-python bench.py --mode streaming --graph --groups 2 --no-cpu-baseline > $O/bench_streaming_graph_groups2.json 2>> $O/bench.err
-python bench.py --mode streaming --graph --pipeline --no-cpu-baseline > $O/bench_streaming_pipelined.json 2>> $O/bench.err
-python bench.py --mode streaming --graph --pipeline --groups 2 --no-cpu-baseline > $O/bench_streaming_pipelined_groups2.json 2>> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
+python bench.py --full --model hil_music --no-cpu-baseline > $O/bench_hil_music.json 2>> $O/bench.err
+python bench.py --full --mode streaming --no-cpu-baseline > $O/bench_streaming.json 2>> $O/bench.err
+python bench.py --full --mode streaming --graph --no-cpu-baseline > $O/bench_streaming_graph.json 2>> $O/bench.err
+python bench.py --full --mode streaming --graph --groups 2 --no-cpu-baseline > $O/bench_streaming_graph_groups2.json 2>> $O/bench.err
+python bench.py --full --mode streaming --graph --pipeline --no-cpu-baseline > $O/bench_streaming_pipelined.json 2>> $O/bench.err
+python bench.py --full --mode streaming --graph --pipeline --groups 2 --no-cpu-baseline > $O/bench_streaming_pipelined_groups2.json 2>> $O/bench.err
 python tools/layer_profile.py > $O/layer_table.txt 2>> $O/bench.err
 python tools/layer_profile.py --mode streaming --batch 1024 > $O/layer_table_streaming.txt 2>> $O/bench.err
 cd /tmp && export TMPDIR=/tmp

@@ -17,10 +17,10 @@ for LEG in ${LEGS:-offline streaming}; do
   for N in 1 2 4 8; do
     [ "$N" -gt "$NGPU" ] && break
     if [ "$LEG" = offline ]; then
-      ARGS="--gpus $N --steps 10 --warmup 3 --no-cpu-baseline --no-other-configs"
+      ARGS="--full --gpus $N --steps 10 --warmup 3 --no-cpu-baseline --no-other-configs"
       [ -n "${MODEL:-}" ] && ARGS="$ARGS --model $MODEL"
     else
-      ARGS="--gpus $N --mode streaming --graph --steps 150 --warmup 10 --no-cpu-baseline"
+      ARGS="--full --gpus $N --mode streaming --graph --steps 150 --warmup 10 --no-cpu-baseline"
       [ -n "${PIPELINE:-}" ] && ARGS="$ARGS --pipeline"
     fi
     if [ "$N" -eq 1 ]; then
