@@ -4,5 +4,7 @@ Importing the package loads `lib/libhilcodec_amd.so` (hand-written HIP kernels b
 `include/hilcodec_amd.h`) and fails loudly if it is missing: there is no CPU or PyTorch fallback."""
 from . import _lib  # noqa: F401  (raises if the HIP library is not built)
 from .models.hilcodec.models import HILCodec  # noqa: F401
+# the offline converter; the module's other names are imported from it by name (`from hilcodec_amd.resample import design`)
+from .resample import Resampler, resample  # noqa: F401
 
-__all__ = ["HILCodec"]
+__all__ = ["HILCodec", "Resampler", "resample"]

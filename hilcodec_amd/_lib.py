@@ -74,6 +74,7 @@ SIGNATURES = {
     "hilc_rvq_decode_packed": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     "hilc_conceal_prepare": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "hilc_conceal_gain": [_p, _p, _p, _p, _i, _i, _i, _p],
+    "hilc_resample_poly": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
 }
 
 ABI_VERSION = 16

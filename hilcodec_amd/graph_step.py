@@ -22,6 +22,7 @@ import torch
 from torch import Tensor
 
 from . import engine, ops, wire
+from .resample import BASE_RATE, design, device_taps, hop_samples
 
 
 def _spectra_on(encoder, stream: Optional[torch.cuda.Stream]):
@@ -31,14 +32,21 @@ def _spectra_on(encoder, stream: Optional[torch.cuda.Stream]):
     return engine.spectra_side_stream(stream)
 
 
-def state_layout(model, batch: int, side: str = "both") -> ops.StateLayout:
+def state_layout(model, batch: int, side: str = "both", history: int = 0) -> ops.StateLayout:
     """the layout of a state block of `batch` streams of `model` (host-only: the cache shapes come from a CPU probe); `side`
-    "enc" / "dec": a one-sided block of the 22 encoder or the 30 decoder caches only (its records hold that side only)"""
+    "enc" / "dec": a one-sided block of the 22 encoder or the 30 decoder caches only (its records hold that side only).
+    `history` > 0 (one-sided only): one more cache `[batch, 1, history]` after that side's last, the resampler's input history
+    (GraphedEncodeHop(input_rate=), GraphedDecodeHop(output_rate=))"""
     if side not in ("both", "enc", "dec"):
         raise ValueError(f"side must be 'both', 'enc' or 'dec', got {side!r}")
+    if history and side == "both":
+        raise ValueError("state_layout: a resampler history belongs to a one-sided block")
     ce, cd = model.initialize_cache(torch.zeros(1, 1, 1))
-    ce, cd = (ce if side != "dec" else []), (cd if side != "enc" else [])
-    return ops.StateLayout([(batch,) + tuple(c.shape[1:]) for c in list(ce) + list(cd)], len(ce))
+    shapes = [tuple(c.shape[1:]) for c in (ce if side != "dec" else [])]
+    shapes_dec = [tuple(c.shape[1:]) for c in (cd if side != "enc" else [])]
+    if history:
+        (shapes if side == "enc" else shapes_dec).append((1, int(history)))
+    return ops.StateLayout([(batch,) + sh for sh in shapes + shapes_dec], len(shapes))
 
 
 def _capture_pair(hop, zero, device: torch.device, warmup: int):
@@ -179,14 +187,23 @@ class SessionQueue:
 
 class StateBlock:
     """The 22 + 30 caches of `batch` streams as views into ONE contiguous fp32 buffer (16-B aligned slices); `side` "enc" /
-    "dec": one side's caches only (the other list is empty)."""
+    "dec": one side's caches only (the other list is empty).  `history` > 0: that side's list ends with the resampler's history
+    `[batch, 1, history]` (`hist`); `codec_enc` / `codec_dec` are the model's caches alone."""
 
-    def __init__(self, model, batch: int, device: torch.device, side: str = "both"):
-        self.layout = state_layout(model, batch, side)
+    def __init__(self, model, batch: int, device: torch.device, side: str = "both", history: int = 0):
+        self.layout = state_layout(model, batch, side, history)
         self.buffer = torch.zeros(self.layout.total, device=device, dtype=torch.float32)
         views = [self.buffer[o:o + s[0] * n].view(s) for s, o, n in zip(self.layout.shapes, self.layout.off, self.layout.lens)]
         self.enc: List[Tensor] = views[:self.layout.n_enc]
         self.dec: List[Tensor] = views[self.layout.n_enc:]
+        self.hist: Optional[Tensor] = None
+        self.codec_enc, self.codec_dec = self.enc, self.dec
+        if history:
+            self.hist = views[-1] if side == "dec" else self.enc[-1]
+            if side == "dec":
+                self.codec_dec = self.dec[:-1]
+            else:
+                self.codec_enc = self.enc[:-1]
 
     def zero_(self) -> None:
         self.buffer.zero_()
@@ -636,16 +653,29 @@ class GraphedEncodeHop(GraphedHop):
     `[B]`), `.indices` the same hop's `[n,B,T]`: static views that the next-but-one `step` overwrites.
     Sessions as in GraphedHop, on the encoder side: `start(slot, cache_enc=None, n=None)`, `set_bitrate(slot, n)`,
     `export(slot) -> cache_enc`, `step(x, hold=slots)`, `stop(slot)`; a held row's packet is all zero with nbytes 0 and its
-    `.indices` are -1."""
+    `.indices` are -1.
+    `input_rate` (resample.RATES; default 24 000 = no resampler): `step(x)` takes `[B,1,resample.hop_samples(hop // 320,
+    input_rate)]` samples at that rate, and the graph converts them to the encoder's 24 kHz hop with one hilc_resample_poly launch
+    after hilc_state_slots_apply.  Its per-stream input history is one more cache, the LAST of the encoder list: `export`,
+    `start` and `cache_enc` then hold 23 caches, `start(slot)` zeroes it and a held or stopped slot keeps it."""
 
     side = "enc"
 
     def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
-                 max_loads_per_hop: int = 4):
+                 max_loads_per_hop: int = 4, input_rate: int = BASE_RATE):
         self.model, self.n, self.device = model, n, device
+        self.input_rate = int(input_rate)
+        self.rs, history, hop_in = None, 0, hop
+        if self.input_rate != BASE_RATE:
+            if hop % 320:
+                raise ValueError(f"GraphedEncodeHop(input_rate={input_rate}): hop must be a multiple of 320, got {hop}")
+            hop_in = hop_samples(hop // 320, self.input_rate)
+            self.rs = design(self.input_rate, BASE_RATE)
+            self.rs_taps = device_taps(self.rs, device)
+            history = self.rs.history
         self.bounds = [(0, batch)]
-        self.x = torch.zeros(batch, 1, hop, device=device)
-        self.gstate = [(StateBlock(model, batch, device, "enc"), StateBlock(model, batch, device, "enc"))]
+        self.x = torch.zeros(batch, 1, hop_in, device=device)
+        self.gstate = [(StateBlock(model, batch, device, "enc", history), StateBlock(model, batch, device, "enc", history))]
         self.parity = 0
         self.sessions = bool(sessions)
         if self.sessions:
@@ -667,9 +697,12 @@ class GraphedEncodeHop(GraphedHop):
         n_clip = self.n_slot if self.sessions else None
         if self.sessions:
             ops.state_slots_apply(src.buffer, src.layout, self.action, self.records)
+        x = self.x
+        if self.rs is not None:
+            x = ops.resample_poly(x, self.rs_taps, self.rs.L, self.rs.M, hist=src.hist, hist_out=dst.hist)
         with ops.sched_workspace(self.sched[0]):
             with _spectra_on(m.encoder, self.spec_side[0]):
-                z, _ = m.encoder(self.x, *src.enc, cache_out=dst.enc)
+                z, _ = m.encoder(x, *src.codec_enc, cache_out=dst.codec_enc)
             idx = m.quantizer(z, self.n, n_clip=n_clip)
         packets, nbytes = ops.pack_codes_10bit(idx, n_clip)
         if self.sessions:
@@ -682,12 +715,12 @@ class GraphedEncodeHop(GraphedHop):
 
     def start(self, slot: int, cache_enc: Optional[Sequence[Tensor]] = None, n: Optional[int] = None) -> None:
         """At the next step, slot `slot` begins a fresh stream or resumes one from its 22 encoder caches (B = 1 tensors, host or
-        device); `n`: its number of quantiser stages (default: the graph's n)"""
+        device; 23 with `input_rate`, the resampler's history last); `n`: its number of quantiser stages (default: the graph's n)"""
         self._need_sessions("start")
         self.queue.start(slot, cache_enc, None, n)
 
     def export(self, slot: int) -> List[Tensor]:
-        """the current 22 encoder caches of slot `slot` as B = 1 device tensors"""
+        """the current 22 encoder caches of slot `slot` as B = 1 device tensors (23 with `input_rate`: the resampler's history last)"""
         return super().export(slot)[0]
 
 
@@ -710,11 +743,22 @@ class GraphedDecodeHop:
     with nothing received since its start, or with k = F, is held by the graph itself (wav 0, caches unchanged).  Ramps and
     tables: `wire.conceal_tables`; substitute packets: `wire.conceal_packet`.  `concealed` is each slot's k after the last step.
     Graph: hilc_conceal_prepare after hilc_state_slots_apply (rewrites this hop's packet, n and hold rows of concealed slots),
-    hilc_conceal_gain after the decoder.  `conceal=False` captures exactly the graph of earlier rounds."""
+    hilc_conceal_gain after the decoder.  `conceal=False` captures exactly the graph of earlier rounds.
+    `output_rate` (resample.RATES; default 24 000 = no resampler): the graph converts the decoded (and, with `conceal`, faded) hop
+    with one hilc_resample_poly launch before hilc_state_slots_hold, and `step` returns `[B,1,resample.hop_samples(frames,
+    output_rate)]` samples at that rate (held rows 0).  Its per-stream history is one more cache, the LAST of the decoder list:
+    `export`, `start` and `cache_dec` then hold 31 caches, `start(slot)` zeroes it and a held, stopped or faded-out slot keeps it."""
 
     def __init__(self, model, batch: int, frames: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
-                 max_loads_per_hop: int = 4, conceal: bool = False, fade_hops: int = 4):
+                 max_loads_per_hop: int = 4, conceal: bool = False, fade_hops: int = 4, output_rate: int = BASE_RATE):
         self.model, self.batch, self.frames, self.n, self.device = model, int(batch), int(frames), int(n), device
+        self.output_rate = int(output_rate)
+        self.rs, history = None, 0
+        if self.output_rate != BASE_RATE:
+            hop_samples(self.frames, self.output_rate)                  # ValueError: frames do not make whole samples at that rate
+            self.rs = design(BASE_RATE, self.output_rate)
+            self.rs_taps = device_taps(self.rs, device)
+            history = self.rs.history
         if not 1 <= self.n <= len(model.dequantizer.layers):
             raise ValueError(f"n = {n} outside [1, {len(model.dequantizer.layers)}]")
         self.sessions = bool(sessions)
@@ -727,7 +771,7 @@ class GraphedDecodeHop:
             raise ValueError(f"fade_hops must be an int >= 1, got {fade_hops!r}")
         self.fade_hops = int(fade_hops)
         self.stride = wire.packet_bytes(self.n, self.frames)
-        self.state = (StateBlock(model, batch, device, "dec"), StateBlock(model, batch, device, "dec"))
+        self.state = (StateBlock(model, batch, device, "dec", history), StateBlock(model, batch, device, "dec", history))
         self.parity = 0
         layout = self.state[0].layout
         loads = int(max_loads_per_hop) if self.sessions else 0
@@ -768,7 +812,7 @@ class GraphedDecodeHop:
 
     @property
     def cache_dec(self) -> List[Tensor]:
-        """the CURRENT 30 decoder caches of all streams (views of the state block)"""
+        """the CURRENT 30 decoder caches of all streams (views of the state block; 31 with `output_rate`, the history last)"""
         return self.state[self.parity].dec
 
     @property
@@ -795,9 +839,11 @@ class GraphedDecodeHop:
                                        self.fade_hops)
         with ops.sched_workspace(self.sched):
             q = m.dequantizer.decode_packed(self.packets, self.n_slot, self.n, self.frames)
-            wav, _ = m.decoder(q, *src.dec, cache_out=dst.dec)
+            wav, _ = m.decoder(q, *src.codec_dec, cache_out=dst.codec_dec)
         if self.conceal:
             ops.conceal_gain(wav, ramp, self._gains, self._weights)
+        if self.rs is not None:
+            wav = ops.resample_poly(wav.contiguous(), self.rs_taps, self.rs.L, self.rs.M, hist=src.hist, hist_out=dst.hist)
         if self.sessions:
             ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self.hold, wav=wav)
         return wav
@@ -876,7 +922,7 @@ class GraphedDecodeHop:
 
     def start(self, slot: int, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
         """At the next step, slot `slot` begins a fresh stream (zero caches) or resumes one from its 30 decoder caches (B = 1
-        tensors, host or device); at most `max_loads_per_hop` resumes per hop"""
+        tensors, host or device; 31 with `output_rate`, the resampler's history last); at most `max_loads_per_hop` resumes per hop"""
         if not self.sessions:
             raise RuntimeError("GraphedDecodeHop.start: construct with sessions=True")
         self.queue.start(slot, None, cache_dec)
@@ -894,7 +940,7 @@ class GraphedDecodeHop:
 
     def export(self, slot: int) -> List[Tensor]:
         """the current 30 decoder caches of slot `slot` as B = 1 device tensors (one gather launch; a stopped slot: its caches
-        when it stopped)"""
+        when it stopped; 31 with `output_rate`, the resampler's history last)"""
         if not self.sessions:
             raise RuntimeError("GraphedDecodeHop.export: construct with sessions=True")
         blk = self.state[self.parity]

@@ -916,6 +916,30 @@ def _conceal_gain(wav, ramp, gains, weights):
 _register("conceal_gain", "(Tensor(a!) wav, Tensor ramp, Tensor gains, Tensor weights) -> ()", _conceal_gain,
           lambda wav, ramp, gains, weights: None)
 
+# ======================================================================================================
+# sample-rate conversion at the codec's input and output (hilcodec_amd/resample.py; semantics: include/hilcodec_amd.h)
+# ======================================================================================================
+def _resample_len(T, L, M):
+    return (T * L + M - 1) // M
+
+
+def _resample_poly(x, hist_in, hist_out, taps, L, M):
+    if x.dim() != 3 or x.shape[1] != 1 or x.shape[2] < 1 or taps.dim() != 2 or taps.shape[0] != L:
+        raise RuntimeError(f"resample_poly: x must be [B, 1, T >= 1] and taps [L = {L}, Q]")
+    B, _, T = x.shape
+    Q = taps.shape[1]
+    for name, h in (("hist_in", hist_in), ("hist_out", hist_out)):
+        if h is not None and h.numel() != B * (Q - 1):
+            raise RuntimeError(f"resample_poly: {name} must be [{B}, 1, {Q - 1}]")
+    y = _new(x, B, 1, _resample_len(T, L, M))
+    check(lib.hilc_resample_poly(_ptr(x), _ptr(hist_in), _ptr(hist_out), _ptr(y), _ptr(taps), B, T, L, M, Q, _stream()),
+          "hilc_resample_poly")
+    return y
+
+
+_register("resample_poly", "(Tensor x, Tensor? hist_in, Tensor(a!)? hist_out, Tensor taps, int L, int M) -> Tensor", _resample_poly,
+          lambda x, hist_in, hist_out, taps, L, M: x.new_empty(x.shape[0], 1, _resample_len(x.shape[2], L, M)))
+
 _OPS = torch.ops.hilcodec
 
 
@@ -1470,3 +1494,12 @@ def conceal_gain(wav: Tensor, ramp: Tensor, gains: Tensor, weights: Tensor) -> N
     gain = G[a] + (G[c] - G[a]) * W[s], each operation rounded on its own in fp32; `gains` = G `[F + 1]`, `weights` = W
     (`wire.conceal_tables`).  Rows without a ramp are not touched; in place."""
     _OPS.conceal_gain(wav, ramp, gains, weights)
+
+
+def resample_poly(x: Tensor, taps: Tensor, L: int, M: int, hist: Optional[Tensor] = None, hist_out: Optional[Tensor] = None) -> Tensor:
+    """x fp32 `[B, 1, T]` -> y `[B, 1, ceil(T L / M)]`: the polyphase conversion of hilcodec_amd/resample.py with the phase-major tap
+    table `taps` `[L, Q]` (resample.device_taps).  `hist` `[B, 1, Q - 1]`: the input samples before x (None: zeros); `hist_out`
+    (distinct from `hist`): receives the last Q - 1 samples of hist || x, in place, in the style of `cache_out=`."""
+    if hist is not None and hist is hist_out:
+        raise RuntimeError("resample_poly: hist and hist_out must be distinct buffers (the kernel refuses one shared pointer too)")
+    return _OPS.resample_poly(x, hist, hist_out, taps, int(L), int(M))

@@ -9,7 +9,9 @@ MI355X kernels instead of ONNXRuntime sessions:
 
     python -m hilcodec_amd.stream_driver -n hil_speech -q 8 -f 1 --enc --dec --input in.wav --outdir out/
 
-`--input` is a 16-bit PCM mono WAV (read with the stdlib `wave` module) or a float32 `.npy`; weights come
+`--input` is a 16-bit PCM mono WAV (read with the stdlib `wave` module) or a float32 `.npy` (taken to be at `--sr`).  A WAV at
+another supported rate (8 / 16 / 22.05 / 32 / 44.1 / 48 kHz) is resampled to 24 kHz on the device first (`hilcodec_amd.resample`,
+the reference's `librosa.load(PATH, sr=sr)` step); `--out_sr` writes the decoded output at such a rate.  Weights come
 from `--checkpoint` (the reference's `NNNNN.pth`, key 'model') or, without it, from the deterministic synthetic
 generator used by the tests (there are no trained encoder/decoder weights in the reference tree)."""
 from __future__ import annotations
@@ -95,6 +97,18 @@ def read_wav(path: str, sr: int) -> np.ndarray:
     return (pcm.astype(np.float32) / 32768.0)
 
 
+def read_wav_rate(path: str, default_rate: int = 24_000) -> Tuple[np.ndarray, int]:
+    """16-bit PCM mono WAV -> (float32 samples in [-1, 1), the file's own sample rate); a `.npy` has no rate: `default_rate`"""
+    if path.endswith(".npy"):
+        return np.load(path).astype(np.float32).reshape(-1), int(default_rate)
+    with wave.open(path, "rb") as w:
+        if w.getnchannels() != 1 or w.getsampwidth() != 2:
+            raise ValueError("expected 16-bit mono PCM")
+        rate = w.getframerate()
+        pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2")
+    return (pcm.astype(np.float32) / 32768.0), rate
+
+
 def write_wav(path: str, wav: np.ndarray, sr: int) -> None:
     pcm = np.clip(np.round(wav * 32767.0), -32768, 32767).astype("<i2")
     with wave.open(path, "wb") as w:
@@ -173,20 +187,28 @@ def main(argv=None):
     ap.add_argument("--input", default=None)
     ap.add_argument("--outdir", default=".")
     ap.add_argument("--checkpoint", default=None)
+    ap.add_argument("--out_sr", type=int, default=None, help="sample rate of the decoded output (default: --sr)")
     a = ap.parse_args(argv)
+    from .resample import check_rates, resample
+    out_sr = a.sr if a.out_sr is None else a.out_sr
+    check_rates(a.sr, out_sr)
     dev = torch.device("cuda:0")
     model = build_streaming_model(a.name, a.checkpoint, dev)
     timer = StageClock(a.sr)
     qpath = os.path.join(a.outdir, f"{a.name}_quantized.npy")
     if a.enc:
-        wav = read_wav(a.input, a.sr) if a.input else synth.sweep_clip(a.sr * 2, a.sr).numpy().reshape(-1)
+        wav, rate = read_wav_rate(a.input, a.sr) if a.input else (synth.sweep_clip(a.sr * 2, a.sr).numpy().reshape(-1), a.sr)
         x = torch.from_numpy(np.clip(wav, -1, 1)).view(1, 1, -1).to(dev)
+        if rate != a.sr:
+            x = resample(x, rate, a.sr)
         idx, _ = encode_stream(model, x, a.num_quantizers, a.num_frames, a.hop_size, timer=timer)
         wire.save_indices_npy(qpath, idx)
     if a.dec:
         idx = wire.load_indices_npy(qpath)
         wav, _ = decode_stream(model, idx, a.num_quantizers, a.num_frames, timer=timer)
-        write_wav(os.path.join(a.outdir, f"{a.name}_output.wav"), wav[0, 0].cpu().numpy(), a.sr)
+        if out_sr != a.sr:
+            wav = resample(wav.contiguous(), a.sr, out_sr)
+        write_wav(os.path.join(a.outdir, f"{a.name}_output.wav"), wav[0, 0].cpu().numpy(), out_sr)
     print(timer.summary())
     return timer.report()
 

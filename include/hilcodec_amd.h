@@ -37,7 +37,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -477,6 +477,20 @@ int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lo
                          int B, int T, int n_max, int fade_hops, void* stream);
 int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops,
                       void* stream);
+
+/* ---- sample-rate conversion at the codec's input and output (additive under ABI 16) --------------------------------------------
+ * One entry point added WITHOUT a version bump, as the packet and concealment entry points above.  It replaces the reference's
+ * `librosa.load(PATH, sr=sr)` (test_onnx.py:52, scripts/inference.ipynb), which resamples an input file to the model's rate, with the
+ * project's own polyphase converter (hilcodec_amd/resample.py designs the filter and states the definition).
+ * hilc_resample_poly: x fp32 [B][T_in] at the input rate -> y fp32 [B][T_out], T_out = ceil(T_in L / M), the rate ratio L / M in
+ * lowest terms; taps fp32 [L][Q] phase-major (taps[p Q + j] = h[p + j L]).  For output m, ph = (m M) mod L, base = (m M - ph) / L:
+ *   y[m] = sum_{j = 0 .. Q-1} taps[ph][j] * x[base - j], summed in order of j from 0.0f, each product and sum rounded on its own;
+ * x[i < 0] = hist_in[b][Q - 1 + i] (fp32 [B][Q - 1]; NULL = zeros).  hist_out (fp32 [B][Q - 1]; NULL = not written) receives the
+ * last Q - 1 samples of hist_in || x; it must not be hist_in (a hop reads one block and writes the other).  NULL x, y or taps:
+ * HILC_ERR_NULL; B, T_in, L or M <= 0, Q < 2 or hist_out == hist_in: HILC_ERR_SHAPE; a filter too long for the kernel's LDS tiles
+ * (more than 64 KiB for TILE = 64 outputs of 16 streams: every rate pair of resample.py fits with room to spare): HILC_ERR_UNSUPPORTED. */
+int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M,
+                       int Q, void* stream);
 
 #ifdef __cplusplus
 }
