@@ -75,6 +75,8 @@ SIGNATURES = {
     "hilc_conceal_prepare": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "hilc_conceal_gain": [_p, _p, _p, _p, _i, _i, _i, _p],
     "hilc_resample_poly": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "hilc_pack_codes_10bit_fec": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "hilc_fec_select": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
 }
 
 ABI_VERSION = 16

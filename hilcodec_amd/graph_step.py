@@ -72,6 +72,19 @@ def _capture_pair(hop, zero, device: torch.device, warmup: int):
     return graphs, outs
 
 
+def _fec_stages(fec_stages, n: int) -> int:
+    """the `fec_stages` argument of the sender and the receiver checked: 0 (no FEC) or an int m in [1, n] with n + m <= 32 (the
+    most stages one packet holds, as hilc_rvq_decode_packed)"""
+    if isinstance(fec_stages, bool) or int(fec_stages) != fec_stages:
+        raise ValueError(f"fec_stages must be an int, got {fec_stages!r}")
+    m = int(fec_stages)
+    if m != 0 and not 1 <= m <= int(n):
+        raise ValueError(f"fec_stages = {m} outside [1, n = {n}] (0: no FEC)")
+    if int(n) + m > 32:
+        raise ValueError(f"fec_stages = {m}: a packet holds at most 32 stages, n + m = {int(n) + m}")
+    return m
+
+
 def _mark(row: Tensor, slots) -> None:
     """a pinned int32 control row: 1 at `slots`, 0 elsewhere"""
     row.zero_()
@@ -91,6 +104,7 @@ class SessionQueue:
         alone; otherwise both lists or neither"""
         self.batch, self.n_max, self.max_loads, self.layout = int(batch), int(n_max), int(max_loads), layout
         self.one_sided = bool(one_sided)
+        self.n_min = 1                        # the least n a start or a bitrate may ask for (GraphedEncodeHop(fec_stages=m): m)
         self.starts = {}
         self.n = {}
         self.holds = set()
@@ -104,8 +118,8 @@ class SessionQueue:
 
     def check_n(self, n) -> int:
         v = int(n)
-        if not 1 <= v <= self.n_max:
-            raise ValueError(f"n = {n} outside [1, {self.n_max}] (the graph's n is the maximum)")
+        if not self.n_min <= v <= self.n_max:
+            raise ValueError(f"n = {n} outside [{self.n_min}, {self.n_max}] (the graph's n is the maximum)")
         return v
 
     @property
@@ -154,6 +168,22 @@ class SessionQueue:
         stopped = set(slots) & self.stops
         if stopped:
             raise ValueError(f"lost: slots {sorted(stopped)} are stopped (start them first)")
+        return slots
+
+    def fec_slots(self, fec, hold=(), lost=()) -> List[int]:
+        """the receiver's `fec` (host ints) checked before anything is launched: every slot in range (IndexError), none also in
+        `hold` or `lost` (this hop's checked holds and losses) and none stopped (ValueError: a FEC slot is decoded from the next
+        packet's redundant section, so it is neither held nor concealed, and a stopped slot has no stream)"""
+        slots = sorted({self.slot(s) for s in self.host_slots(fec)})
+        both = set(slots) & {int(s) for s in hold}
+        if both:
+            raise ValueError(f"fec: slots {sorted(both)} are also held on this hop")
+        both = set(slots) & {int(s) for s in lost}
+        if both:
+            raise ValueError(f"fec: slots {sorted(both)} are also lost on this hop")
+        stopped = set(slots) & self.stops
+        if stopped:
+            raise ValueError(f"fec: slots {sorted(stopped)} are stopped (start them first)")
         return slots
 
     def start(self, slot, cache_enc=None, cache_dec=None, n=None) -> None:
@@ -657,13 +687,23 @@ class GraphedEncodeHop(GraphedHop):
     `input_rate` (resample.RATES; default 24 000 = no resampler): `step(x)` takes `[B,1,resample.hop_samples(hop // 320,
     input_rate)]` samples at that rate, and the graph converts them to the encoder's 24 kHz hop with one hilc_resample_poly launch
     after hilc_state_slots_apply.  Its per-stream input history is one more cache, the LAST of the encoder list: `export`,
-    `start` and `cache_enc` then hold 23 caches, `start(slot)` zeroes it and a held or stopped slot keeps it."""
+    `start` and `cache_enc` then hold 23 caches, `start(slot)` zeroes it and a held or stopped slot keeps it.
+    `fec_stages` = m >= 1 (in-band FEC, at most n; `hop` a multiple of 320): each packet also carries the first m stages of the
+    stream's previous encoded hop, `wire.pack_fec_packet(idx[:n_b], prev)`, so packets are uint8 `[B, wire.fec_packet_bytes(n, m,
+    T)]`; `.indices` are unchanged.  A stream without a previous encoded hop (the first hop after construction, `reset`, a `start`
+    or a resume) sends the plain n_b-stage packet; a held or stopped slot keeps its previous codes; `export` and a resume carry no
+    FEC state.  Per-stream n (`start(n=)`, `set_bitrate`) must be >= m.  The graph runs hilc_pack_codes_10bit_fec in place of
+    hilc_pack_codes_10bit on a ping-pong pair of int32 rows `[B, 1 + m T]` (valid, codes) indexed by parity, like the state blocks.
+    `fec_stages=0` captures exactly the graph without FEC."""
 
     side = "enc"
 
     def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
-                 max_loads_per_hop: int = 4, input_rate: int = BASE_RATE):
+                 max_loads_per_hop: int = 4, input_rate: int = BASE_RATE, fec_stages: int = 0):
         self.model, self.n, self.device = model, n, device
+        self.fec_stages = _fec_stages(fec_stages, n)
+        if self.fec_stages and hop % 320:
+            raise ValueError(f"GraphedEncodeHop(fec_stages={fec_stages}): hop must be a multiple of 320, got {hop}")
         self.input_rate = int(input_rate)
         self.rs, history, hop_in = None, 0, hop
         if self.input_rate != BASE_RATE:
@@ -680,6 +720,12 @@ class GraphedEncodeHop(GraphedHop):
         self.sessions = bool(sessions)
         if self.sessions:
             self._init_sessions(batch, int(max_loads_per_hop))
+            self.queue.n_min = max(1, self.fec_stages)
+        self._prev = None
+        if self.fec_stages:
+            # per parity, per slot: valid, then the first m stages x T frames of its last encoded hop (the hop of parity p reads
+            # row p and writes row p ^ 1)
+            self._prev = torch.zeros(2, batch, 1 + self.fec_stages * (hop // 320), dtype=torch.int32, device=device)
         self.spec_side = [torch.cuda.Stream(device)]
         self.chain = [None]
         self.sched = [ops.SchedWorkspace(device)]
@@ -704,10 +750,26 @@ class GraphedEncodeHop(GraphedHop):
             with _spectra_on(m.encoder, self.spec_side[0]):
                 z, _ = m.encoder(x, *src.codec_enc, cache_out=dst.codec_enc)
             idx = m.quantizer(z, self.n, n_clip=n_clip)
-        packets, nbytes = ops.pack_codes_10bit(idx, n_clip)
+        if self.fec_stages:
+            packets, nbytes = ops.pack_codes_10bit_fec(idx, self._prev[p], self._prev[p ^ 1], self.fec_stages, n_clip,
+                                                       self.action if self.sessions else None, self.hold if self.sessions else None)
+        else:
+            packets, nbytes = ops.pack_codes_10bit(idx, n_clip)
         if self.sessions:
             ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self.hold, indices=idx, packets=packets, nbytes=nbytes)
         return idx, packets, nbytes
+
+    def _zero(self) -> None:
+        super()._zero()
+        if self._prev is not None:
+            self._prev.zero_()
+
+    def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
+        """as GraphedHop.reset; with FEC, no stream has a previous hop afterwards"""
+        super().reset(cache_enc, cache_dec)
+        if self._prev is not None:
+            with torch.no_grad():
+                self._prev.zero_()
 
     def step(self, x: Tensor, hold=None) -> Tuple[Tensor, Tensor]:
         self.indices, packets, nbytes = super().step(x, hold)
@@ -747,10 +809,19 @@ class GraphedDecodeHop:
     `output_rate` (resample.RATES; default 24 000 = no resampler): the graph converts the decoded (and, with `conceal`, faded) hop
     with one hilc_resample_poly launch before hilc_state_slots_hold, and `step` returns `[B,1,resample.hop_samples(frames,
     output_rate)]` samples at that rate (held rows 0).  Its per-stream history is one more cache, the LAST of the decoder list:
-    `export`, `start` and `cache_dec` then hold 31 caches, `start(slot)` zeroes it and a held, stopped or faded-out slot keeps it."""
+    `export`, `start` and `cache_dec` then hold 31 caches, `start(slot)` zeroes it and a held, stopped or faded-out slot keeps it.
+    `fec_stages` = m >= 1 (in-band FEC, at most n; the sender's m, and `frames` must equal the sender's T: FEC packets are not
+    re-framed): `packets` rows are `wire.fec_packet_bytes(n, m, frames)` wide, with or without a redundant section.
+    `step(..., fec=slots)` names the slots whose packet for this hop was lost but whose NEXT packet has arrived: their rows hold
+    that next packet and their n_per_stream entries its primary n_b, in [m, n].  Such a slot is decoded from the next packet's
+    redundant section at n = m, bit for bit as if `wire.fec_redundant(next, n_b, m, frames)` had arrived with n = m (wav, caches
+    and, with `conceal`, the concealment state: run 0, the fade-in after a loss, the stored frame).  Other slots are decoded from
+    their primary section (`wire.fec_primary`).  Graph: one hilc_fec_select after hilc_state_slots_apply compacts the wide rows
+    into the rows the unchanged concealment and dequantiser kernels read.  `fec_stages=0` captures exactly the graph without FEC."""
 
     def __init__(self, model, batch: int, frames: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
-                 max_loads_per_hop: int = 4, conceal: bool = False, fade_hops: int = 4, output_rate: int = BASE_RATE):
+                 max_loads_per_hop: int = 4, conceal: bool = False, fade_hops: int = 4, output_rate: int = BASE_RATE,
+                 fec_stages: int = 0):
         self.model, self.batch, self.frames, self.n, self.device = model, int(batch), int(frames), int(n), device
         self.output_rate = int(output_rate)
         self.rs, history = None, 0
@@ -770,15 +841,17 @@ class GraphedDecodeHop:
         if isinstance(fade_hops, bool) or int(fade_hops) != fade_hops or fade_hops < 1:
             raise ValueError(f"fade_hops must be an int >= 1, got {fade_hops!r}")
         self.fade_hops = int(fade_hops)
-        self.stride = wire.packet_bytes(self.n, self.frames)
+        self.fec_stages = _fec_stages(fec_stages, self.n)
+        self.stride = wire.packet_bytes(self.n + self.fec_stages, self.frames)
         self.state = (StateBlock(model, batch, device, "dec", history), StateBlock(model, batch, device, "dec", history))
         self.parity = 0
         layout = self.state[0].layout
         loads = int(max_loads_per_hop) if self.sessions else 0
         B = self.batch
         # ONE device buffer, captured by address: ctl[0] = action per slot, ctl[1] = n per slot, ctl[2] = 1 where the slot is
-        # held, (conceal) ctl[3] = 1 where its packet was lost, the packets, the staged records
-        rows = 4 if self.conceal else 3
+        # held, (conceal) ctl[3] = 1 where its packet was lost, (fec) the next row = 1 where it is decoded from the next packet's
+        # redundant section, the packets, the staged records
+        rows = 3 + self.conceal + (self.fec_stages > 0)
         self._n_ctl = rows * B
         self._rec_off = self._n_ctl + (B * self.stride + 3) // 4
         self._stage = torch.zeros(self._rec_off + loads * layout.record_len, device=device)
@@ -786,6 +859,7 @@ class GraphedDecodeHop:
         ctl = self._stage[:self._n_ctl].view(torch.int32).view(rows, B)
         self.action, self.n_slot, self.hold = ctl[0], ctl[1], ctl[2]
         self.lost = ctl[3] if self.conceal else None
+        self.fec = ctl[rows - 1] if self.fec_stages else None
         self.packets = self._stage[self._n_ctl:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
         self.records = self._stage[self._rec_off:].view(loads, layout.record_len)
         self._h_ctl = self._h_stage[:self._n_ctl].view(torch.int32).view(rows, B)
@@ -796,6 +870,8 @@ class GraphedDecodeHop:
             self.queue = SessionQueue(B, self.n, loads, layout, one_sided=True)
             for blk in self.state:
                 blk.layout.tables(device)
+        # the host checks of step(fec=...): the session queue, or (sessions=False: no holds, losses or stops) a queue of its own
+        self._slots = self.queue if self.sessions else SessionQueue(B, self.n, 0, layout, one_sided=True)
         if self.conceal:
             # per slot: run k, has-codes, stored n, the stored frame's n codes (updated in place by hilc_conceal_prepare once per hop)
             self._conceal = torch.zeros(B, self.n + 3, dtype=torch.int32, device=device)
@@ -834,11 +910,14 @@ class GraphedDecodeHop:
         src, dst = self.state[p], self.state[p ^ 1]
         if self.sessions:
             ops.state_slots_apply(src.buffer, src.layout, self.action, self.records)
+        packets = self.packets
+        if self.fec_stages:
+            packets = ops.fec_select(self.packets, self.fec, self.n_slot, self.n, self.fec_stages, self.frames)
         if self.conceal:
-            ramp = ops.conceal_prepare(self._conceal, self.action, self.hold, self.lost, self.n_slot, self.packets, self.frames,
+            ramp = ops.conceal_prepare(self._conceal, self.action, self.hold, self.lost, self.n_slot, packets, self.frames,
                                        self.fade_hops)
         with ops.sched_workspace(self.sched):
-            q = m.dequantizer.decode_packed(self.packets, self.n_slot, self.n, self.frames)
+            q = m.dequantizer.decode_packed(packets, self.n_slot, self.n, self.frames)
             wav, _ = m.decoder(q, *src.codec_dec, cache_out=dst.codec_dec)
         if self.conceal:
             ops.conceal_gain(wav, ramp, self._gains, self._weights)
@@ -848,8 +927,9 @@ class GraphedDecodeHop:
             ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self.hold, wav=wav)
         return wav
 
-    def _check(self, packets: Tensor, n_per_stream, held=()) -> Tensor:
-        """n_per_stream as a tensor; the entries of `held` slots are not range-checked and become the graph's n"""
+    def _check(self, packets: Tensor, n_per_stream, held=(), fec=()) -> Tensor:
+        """n_per_stream as a tensor; the entries of `held` slots are not range-checked and become the graph's n, those of `fec`
+        slots must lie in [fec_stages, n]"""
         if isinstance(n_per_stream, Tensor) and n_per_stream.is_cuda:
             raise ValueError("n_per_stream: host ints, not a device tensor")
         n = torch.as_tensor(n_per_stream).reshape(-1)
@@ -860,14 +940,17 @@ class GraphedDecodeHop:
             n[torch.tensor(sorted(held), dtype=torch.long)] = self.n
         if int(n.min()) < 1 or int(n.max()) > self.n:
             raise ValueError(f"n_per_stream: every entry must lie in [1, {self.n}]")
+        if fec and int(n[torch.tensor(sorted(fec), dtype=torch.long)].min()) < self.fec_stages:
+            raise ValueError(f"n_per_stream: the entries of fec slots (the next packet's n) must lie in [{self.fec_stages}, {self.n}]")
         if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or tuple(packets.shape) != (self.batch, self.stride):
             raise ValueError(f"packets: uint8 [{self.batch}, {self.stride}] expected")
         return n
 
-    def step(self, packets: Tensor, n_per_stream, hold=None, lost=None) -> Tensor:
+    def step(self, packets: Tensor, n_per_stream, hold=None, lost=None, fec=None) -> Tensor:
         """`hold`: slots (host ints) that do not advance on this hop (sessions=True only; None or empty: every slot advances).
         `lost`: slots (host ints) whose packet for this hop did not arrive (conceal=True only): concealed; their packet rows and
-        n_per_stream entries are not read or checked"""
+        n_per_stream entries are not read or checked.  `fec`: slots (host ints) whose packet for this hop was lost but whose next
+        packet is in their row (fec_stages >= 1 only): decoded from its redundant section"""
         held = SessionQueue.host_slots(hold)
         if held:
             if not self.sessions:
@@ -878,9 +961,14 @@ class GraphedDecodeHop:
             raise RuntimeError("GraphedDecodeHop.step(lost=...): construct with conceal=True")
         if self.conceal:
             gone = self.queue.lost_slots(gone, held)
+        red = SessionQueue.host_slots(fec)
+        if red and not self.fec_stages:
+            raise RuntimeError("GraphedDecodeHop.step(fec=...): construct with fec_stages >= 1")
+        if self.fec_stages:
+            red = self._slots.fec_slots(red, held, gone)
         if self.sessions:
             held = set(held) | self.queue.stops
-        n = self._check(packets, n_per_stream, set(held) | set(gone))
+        n = self._check(packets, n_per_stream, set(held) | set(gone), red)
         self._uploaded.synchronize()          # the previous upload's copy has left the pinned buffer
         B, h = self.batch, self._h_ctl
         h[0].zero_()
@@ -888,6 +976,8 @@ class GraphedDecodeHop:
         _mark(h[2], held)
         if self.conceal:
             _mark(h[3], gone)
+        if self.fec_stages:
+            _mark(h[-1], red)
         host, dev = [], []
         if self.sessions:
             q = self.queue

@@ -940,6 +940,49 @@ def _resample_poly(x, hist_in, hist_out, taps, L, M):
 _register("resample_poly", "(Tensor x, Tensor? hist_in, Tensor(a!)? hist_out, Tensor taps, int L, int M) -> Tensor", _resample_poly,
           lambda x, hist_in, hist_out, taps, L, M: x.new_empty(x.shape[0], 1, _resample_len(x.shape[2], L, M)))
 
+# ======================================================================================================
+# in-band forward error correction of the sender / receiver (graph_step.GraphedEncodeHop / GraphedDecodeHop(fec_stages=m);
+# format: wire.fec_packet_bytes; semantics: include/hilcodec_amd.h)
+# ======================================================================================================
+def _pack_codes_10bit_fec(indices, n_clip, prev_in, prev_out, action, hold, m):
+    n, B, T = indices.shape
+    W = 1 + m * T
+    if prev_in.shape != (B, W) or prev_out.shape != (B, W) or prev_in.dtype != torch.int32 or prev_out.dtype != torch.int32:
+        raise RuntimeError(f"pack_codes_10bit_fec: prev_in and prev_out must be int32 [{B}, {W}]")
+    for name, row in (("n_clip", n_clip), ("action", action), ("hold", hold)):
+        if row is not None and row.numel() != B:
+            raise RuntimeError(f"pack_codes_10bit_fec: {name} needs {B} entries")
+    packets = _new(indices, B, _packet_stride(n + m, T), dtype=torch.uint8)
+    nbytes = _new(indices, B, dtype=torch.int32)
+    check(lib.hilc_pack_codes_10bit_fec(_ptr(indices, torch.int64), _ptr(n_clip, torch.int32), _ptr(prev_in, torch.int32),
+                                        _ptr(prev_out, torch.int32), _ptr(action, torch.int32), _ptr(hold, torch.int32),
+                                        _ptr(packets, torch.uint8), _ptr(nbytes, torch.int32), B, T, n, m, _stream()),
+          "hilc_pack_codes_10bit_fec")
+    return packets, nbytes
+
+
+def _pack_codes_10bit_fec_fake(indices, n_clip, prev_in, prev_out, action, hold, m):
+    n, B, T = indices.shape
+    return indices.new_empty(B, _packet_stride(n + m, T), dtype=torch.uint8), indices.new_empty(B, dtype=torch.int32)
+
+
+_register("pack_codes_10bit_fec", "(Tensor indices, Tensor? n_clip, Tensor prev_in, Tensor(a!) prev_out, Tensor? action, "
+          "Tensor? hold, int m) -> (Tensor, Tensor)", _pack_codes_10bit_fec, _pack_codes_10bit_fec_fake)
+
+
+def _fec_select(packets, fec, n_slot, n, m, frames):
+    B = packets.shape[0]
+    if packets.dim() != 2 or packets.shape[1] != _packet_stride(n + m, frames) or fec.numel() != B or n_slot.numel() != B:
+        raise RuntimeError(f"fec_select: packets must be [B, {_packet_stride(n + m, frames)}] and fec, n_slot [B]")
+    out = _new(packets, B, _packet_stride(n, frames), dtype=torch.uint8)
+    check(lib.hilc_fec_select(_ptr(packets, torch.uint8), _ptr(fec, torch.int32), _ptr(n_slot, torch.int32), _ptr(out, torch.uint8),
+                              B, frames, n, m, _stream()), "hilc_fec_select")
+    return out
+
+
+_register("fec_select", "(Tensor packets, Tensor fec, Tensor(a!) n_slot, int n, int m, int frames) -> Tensor", _fec_select,
+          lambda packets, fec, n_slot, n, m, frames: packets.new_empty(packets.shape[0], _packet_stride(n, frames)))
+
 _OPS = torch.ops.hilcodec
 
 
@@ -1494,6 +1537,27 @@ def conceal_gain(wav: Tensor, ramp: Tensor, gains: Tensor, weights: Tensor) -> N
     gain = G[a] + (G[c] - G[a]) * W[s], each operation rounded on its own in fp32; `gains` = G `[F + 1]`, `weights` = W
     (`wire.conceal_tables`).  Rows without a ramp are not touched; in place."""
     _OPS.conceal_gain(wav, ramp, gains, weights)
+
+
+def pack_codes_10bit_fec(indices: Tensor, prev_in: Tensor, prev_out: Tensor, m: int, n_clip: Optional[Tensor] = None,
+                         action: Optional[Tensor] = None, hold: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """The FEC sender's packets: stage-major indices `[n, B, T]` -> (packets uint8 `[B, wire.packet_bytes(n + m, T)]`, nbytes int32
+    `[B]`).  Stream b's packet is `wire.pack_fec_packet` of its first n_b stages (`n_clip`, clamped to [m, n]; None = n) and, when
+    its previous-codes row in `prev_in` (int32 `[B, 1 + m T]`: valid, then the m x T codes) is valid, those codes.  `prev_out`
+    (distinct from `prev_in`) receives this hop's first m stages, in place.  `action` / `hold` (int32 `[B]`, optional): a slot
+    with an action has no previous hop; a held slot keeps its row and sends nothing (row 0, nbytes 0)."""
+    if indices.dim() != 3:
+        raise RuntimeError("pack_codes_10bit_fec: indices must be [n, B, T]")
+    if prev_in is prev_out:
+        raise RuntimeError("pack_codes_10bit_fec: prev_in and prev_out must be distinct buffers")
+    return _OPS.pack_codes_10bit_fec(indices, n_clip, prev_in, prev_out, action, hold, int(m))
+
+
+def fec_select(packets: Tensor, fec: Tensor, n_slot: Tensor, n: int, m: int, frames: int) -> Tensor:
+    """The FEC receiver's compaction: wide rows uint8 `[B, wire.packet_bytes(n + m, frames)]` -> rows `[B, wire.packet_bytes(n,
+    frames)]`: `wire.fec_primary` of each row, or `wire.fec_redundant` where `fec` (int32 `[B]`) is set, whose `n_slot` entry
+    (int32 `[B]`, in place: the row's primary n on entry) becomes m."""
+    return _OPS.fec_select(packets, fec, n_slot, int(n), int(m), int(frames))
 
 
 def resample_poly(x: Tensor, taps: Tensor, L: int, M: int, hist: Optional[Tensor] = None, hist_out: Optional[Tensor] = None) -> Tensor:

@@ -101,6 +101,49 @@ def conceal_tables(fade_hops: int, samples: int) -> Tuple[Tensor, Tensor]:
     W = ((torch.arange(S, dtype=torch.float64) + 1) / S).float()
     return G, W
 
+
+# In-band forward error correction (graph_step.GraphedEncodeHop / GraphedDecodeHop(fec_stages=m)): the packet of hop k of a
+# stream with n_b stages is the packet of the [n_b + m, T] codes cat(idx_k[:n_b], idx_{k-1}[:m]) — the primary codes first,
+# unchanged, then the first m stages of the stream's previous encoded hop, its redundant section.  A stream without a previous
+# encoded hop (the first hop after a start, a resume, construction or reset) sends the plain packet_bytes(n_b, T) bytes.  The
+# first m stages of a residual VQ encoding are themselves a valid m-stage encoding of that hop, so a receiver that lost packet k
+# decodes hop k from the redundant section of packet k + 1 at n = m.  These are the definitions the kernels follow.
+def fec_packet_bytes(n: int, m: int, T: int) -> int:
+    """the length of an n-stage packet of T frames with an m-stage redundant section"""
+    return packet_bytes(int(n) + int(m), T)
+
+
+def pack_fec_packet(codes: Tensor, prev_codes=None) -> bytes:
+    """one stream's codes `[n, T]` and its previous hop's first m stages `[m, T]` (None: no previous hop) -> its FEC packet"""
+    if prev_codes is None:
+        return pack_stream_packet(codes)
+    if codes.dim() != 2 or prev_codes.dim() != 2 or prev_codes.shape[1] != codes.shape[1]:
+        raise ValueError("codes must be [n, T] and prev_codes [m, T]")
+    return pack_stream_packet(torch.cat([codes, prev_codes.to(codes.dtype)]))
+
+
+def fec_primary(packet: bytes, n: int, T: int) -> bytes:
+    """the primary section of an FEC packet with `n` primary stages: packet_bytes(n, T) bytes, the bits of the last byte that
+    belong to the redundant section zeroed — byte for byte the packet of a sender without FEC"""
+    return pack_stream_packet(unpack_stream_packet(packet, n, T))
+
+
+def fec_redundant(packet: bytes, n: int, m: int, T: int) -> bytes:
+    """the redundant section of an FEC packet (`n` primary stages, `m` redundant ones) re-packed as an m-stage packet"""
+    return pack_stream_packet(unpack_stream_packet(packet, int(n) + int(m), T)[int(n):])
+
+
+def fec_present(nbytes: int, n: int, m: int, T: int) -> bool:
+    """whether a packet of `nbytes` bytes with `n` primary stages carries an m-stage redundant section; ValueError for a length
+    that is neither packet_bytes(n, T) nor fec_packet_bytes(n, m, T)"""
+    if int(m) < 1:
+        raise ValueError(f"fec_present: m must be >= 1, got {m}")
+    if int(nbytes) == fec_packet_bytes(n, m, T):
+        return True
+    if int(nbytes) == packet_bytes(n, T):
+        return False
+    raise ValueError(f"a {nbytes}-byte packet fits neither {n} nor {n} + {m} stages of {T} frames")
+
 # ---------------------------------------------------------------- caches
 def save_cache_npz(path: str, caches: Sequence[Tensor], prefix: str) -> None:
     """prefix 'e_in' (encoder, 22 tensors) or 'd_in' (decoder, 30)."""

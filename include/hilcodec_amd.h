@@ -37,7 +37,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -491,6 +491,33 @@ int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const flo
  * (more than 64 KiB for TILE = 64 outputs of 16 streams: every rate pair of resample.py fits with room to spare): HILC_ERR_UNSUPPORTED. */
 int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M,
                        int Q, void* stream);
+
+/* ---- in-band forward error correction of the packet sender and receiver (additive under ABI 16) --------------------------------
+ * Two entry points added WITHOUT a version bump, as the packet, concealment and resampling entry points above.  With m redundant
+ * stages (1 <= m <= n_max, n_max + m <= 32, else HILC_ERR_RANGE / HILC_ERR_UNSUPPORTED), the packet of stream b for hop k is the
+ * 10-bit packet (layout of hilc_pack_codes_10bit) of the n_b + m stages cat(idx_k[:n_b, b], idx_{k-1}[:m, b]) — the primary codes
+ * first, unchanged, then the first m stages of the stream's previous encoded hop — ceil(10 (n_b + m) T / 8) bytes; a stream without
+ * a previous encoded hop sends the plain packet of its n_b stages.  A batch is uint8 [B][stride], stride = ceil(10 (n_max + m) T / 8),
+ * row b zero past its length.
+ * hilc_pack_codes_10bit_fec: indices int64 [n_max][B][T] as hilc_pack_codes_10bit (codes clamped into [0, 1024)); n_per_stream
+ * optional int32 [B] (NULL = n_max), each entry clamped to [m, n_max]; prev_in and prev_out distinct int32 [B][1 + m T] rows of the
+ * previous codes, [0] valid (0/1), [1 + s T + t] the code of stage s, frame t (the hop reads one, writes the other); action and hold
+ * optional int32 [B] (NULL = 0): the action row of hilc_state_slots_apply and the hold row of hilc_state_slots_hold.  Per stream b:
+ *   the input row counts as all zero if action[b] != 0 (a start or a resume: no previous hop);
+ *   hold[b] != 0: prev_out[b] = that input row, packets[b] = 0, nbytes[b] = 0;
+ *   else packets[b] = the packet above with the redundant section iff the input row is valid, nbytes[b] = its length, and
+ *   prev_out[b] = {1, idx[s][b][t] clamped, s < m}.
+ * hilc_fec_select: the receiver's compaction before hilc_conceal_prepare / hilc_rvq_decode_packed.  packets uint8 [B][stride] as
+ * above, fec int32 [B], n_per_stream int32 [B] (in place) -> out uint8 [B][ceil(10 n_max T / 8)].  Per stream b: fec[b] == 0: out[b]
+ * = the primary section of n_b = n_per_stream[b] clamped to [1, n_max] stages (the bits of its last byte past 10 n_b T zeroed);
+ * fec[b] != 0 (the row holds the NEXT hop's packet, n_b its primary stage count, clamped to [m, n_max]): out[b] = the redundant
+ * section re-packed at bit 0, an m-stage packet, and n_per_stream[b] = m.  Bytes of out[b] past the section are zero.  NULL
+ * pointers: HILC_ERR_NULL; B or T <= 0, or prev_in == prev_out: HILC_ERR_SHAPE.  The sender: one thread per output byte; the
+ * receiver: one wave per stream. */
+int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action,
+                              const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream);
+int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m,
+                    void* stream);
 
 #ifdef __cplusplus
 }
