@@ -77,6 +77,8 @@ SIGNATURES = {
     "hilc_resample_poly": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "hilc_pack_codes_10bit_fec": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "hilc_fec_select": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "hilc_dtx_encode": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _d, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "hilc_cng_synth": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
 }
 
 ABI_VERSION = 16

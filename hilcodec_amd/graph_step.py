@@ -21,6 +21,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
+from . import dtx as dtx_def
 from . import engine, ops, wire
 from .resample import BASE_RATE, design, device_taps, hop_samples
 
@@ -185,6 +186,25 @@ class SessionQueue:
         if stopped:
             raise ValueError(f"fec: slots {sorted(stopped)} are stopped (start them first)")
         return slots
+
+    def cn_slots(self, sid, silent, hold=(), lost=(), fec=()) -> Tuple[List[int], List[int]]:
+        """the receiver's `sid` and `silent` (host ints) checked before anything is launched: every slot in range (IndexError), the two
+        disjoint, neither also in `hold`, `lost` or `fec` (this hop's checked holds, losses and FEC slots) and none stopped (ValueError: a
+        comfort-noise slot is neither decoded nor held by the caller, and a stopped slot has no stream)"""
+        a = sorted({self.slot(s) for s in self.host_slots(sid)})
+        b = sorted({self.slot(s) for s in self.host_slots(silent)})
+        both = set(a) & set(b)
+        if both:
+            raise ValueError(f"sid / silent: slots {sorted(both)} are in both")
+        for name, slots in (("sid", a), ("silent", b)):
+            for what, other in (("held", hold), ("lost", lost), ("decoded by FEC", fec)):
+                both = set(slots) & {int(s) for s in other}
+                if both:
+                    raise ValueError(f"{name}: slots {sorted(both)} are also {what} on this hop")
+            stopped = set(slots) & self.stops
+            if stopped:
+                raise ValueError(f"{name}: slots {sorted(stopped)} are stopped (start them first)")
+        return a, b
 
     def start(self, slot, cache_enc=None, cache_dec=None, n=None) -> None:
         s = self.slot(slot)
@@ -694,14 +714,29 @@ class GraphedEncodeHop(GraphedHop):
     or a resume) sends the plain n_b-stage packet; a held or stopped slot keeps its previous codes; `export` and a resume carry no
     FEC state.  Per-stream n (`start(n=)`, `set_bitrate`) must be >= m.  The graph runs hilc_pack_codes_10bit_fec in place of
     hilc_pack_codes_10bit on a ping-pong pair of int32 rows `[B, 1 + m T]` (valid, codes) indexed by parity, like the state blocks.
-    `fec_stages=0` captures exactly the graph without FEC."""
+    `fec_stages=0` captures exactly the graph without FEC.
+    `dtx` = dtx.DtxConfig(threshold_db, hangover, sid_interval, order) (`hop` a multiple of 320; a SID of 1 + order bytes must fit
+    `wire.packet_bytes(n, T)`): discontinuous transmission.  After the packer, one hilc_dtx_encode analyses each stream's 24 kHz hop
+    (after the input resampler) and advances its run counter; `.kind` (int32 `[B]` device view, like `.indices`) is each stream's
+    dtx.HELD / SPEECH / SID / SILENT.  SPEECH rows are what the sender without DTX sends; a SID row holds `dtx.pack_sid(L, q)` then
+    zeros with nbytes 1 + order, a SILENT row is zero with nbytes 0, and both have `.indices` -1 (with FEC, the next speech hop is a
+    plain packet).  A held slot keeps its run; `start` clears it; `export` and a resume carry no DTX state.  `dtx=None` captures
+    exactly the graph without DTX."""
 
     side = "enc"
 
     def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
-                 max_loads_per_hop: int = 4, input_rate: int = BASE_RATE, fec_stages: int = 0):
+                 max_loads_per_hop: int = 4, input_rate: int = BASE_RATE, fec_stages: int = 0,
+                 dtx: Optional[dtx_def.DtxConfig] = None):
         self.model, self.n, self.device = model, n, device
         self.fec_stages = _fec_stages(fec_stages, n)
+        if dtx is not None and not isinstance(dtx, dtx_def.DtxConfig):
+            raise ValueError(f"dtx must be a dtx.DtxConfig or None, got {dtx!r}")
+        self.dtx = dtx
+        if dtx is not None:
+            if hop % 320:
+                raise ValueError(f"GraphedEncodeHop(dtx=...): hop must be a multiple of 320, got {hop}")
+            dtx_def.check_order(dtx.order, wire.packet_bytes(n, hop // 320), "GraphedEncodeHop(dtx=...)")
         if self.fec_stages and hop % 320:
             raise ValueError(f"GraphedEncodeHop(fec_stages={fec_stages}): hop must be a multiple of 320, got {hop}")
         self.input_rate = int(input_rate)
@@ -726,11 +761,17 @@ class GraphedEncodeHop(GraphedHop):
             # per parity, per slot: valid, then the first m stages x T frames of its last encoded hop (the hop of parity p reads
             # row p and writes row p ^ 1)
             self._prev = torch.zeros(2, batch, 1 + self.fec_stages * (hop // 320), dtype=torch.int32, device=device)
+        self._run = None
+        if dtx is not None:
+            # per slot: the DTX run counter (updated in place by hilc_dtx_encode once per hop)
+            self._run = torch.zeros(batch, dtype=torch.int32, device=device)
+            self._level_thr = torch.from_numpy(dtx_def.level_table()).to(device)
         self.spec_side = [torch.cuda.Stream(device)]
         self.chain = [None]
         self.sched = [ops.SchedWorkspace(device)]
         self.graphs, self.outs = _capture_pair(self._hop, self._zero, device, warmup)
         self.indices = self.outs[0][0]
+        self.kind = self.outs[0][3] if dtx is not None else None
 
     @property
     def state_bytes(self) -> int:
@@ -755,24 +796,37 @@ class GraphedEncodeHop(GraphedHop):
                                                        self.action if self.sessions else None, self.hold if self.sessions else None)
         else:
             packets, nbytes = ops.pack_codes_10bit(idx, n_clip)
+        kind = None
+        if self.dtx is not None:
+            d = self.dtx
+            kind = ops.dtx_encode(x, self._run, packets, nbytes, idx, self._level_thr, d.thr_vad, d.order, d.hangover, d.sid_interval,
+                                  self.action if self.sessions else None, self.hold if self.sessions else None,
+                                  self._prev[p ^ 1] if self.fec_stages else None)
         if self.sessions:
             ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self.hold, indices=idx, packets=packets, nbytes=nbytes)
-        return idx, packets, nbytes
+        return (idx, packets, nbytes) if kind is None else (idx, packets, nbytes, kind)
 
     def _zero(self) -> None:
         super()._zero()
         if self._prev is not None:
             self._prev.zero_()
+        if self._run is not None:
+            self._run.zero_()
 
     def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
-        """as GraphedHop.reset; with FEC, no stream has a previous hop afterwards"""
+        """as GraphedHop.reset; with FEC, no stream has a previous hop afterwards; with DTX, every run counter is 0"""
         super().reset(cache_enc, cache_dec)
-        if self._prev is not None:
-            with torch.no_grad():
+        with torch.no_grad():
+            if self._prev is not None:
                 self._prev.zero_()
+            if self._run is not None:
+                self._run.zero_()
 
     def step(self, x: Tensor, hold=None) -> Tuple[Tensor, Tensor]:
-        self.indices, packets, nbytes = super().step(x, hold)
+        out = super().step(x, hold)
+        self.indices, packets, nbytes = out[:3]
+        if self.dtx is not None:
+            self.kind = out[3]
         return packets, nbytes
 
     def start(self, slot: int, cache_enc: Optional[Sequence[Tensor]] = None, n: Optional[int] = None) -> None:
@@ -817,11 +871,22 @@ class GraphedDecodeHop:
     redundant section at n = m, bit for bit as if `wire.fec_redundant(next, n_b, m, frames)` had arrived with n = m (wav, caches
     and, with `conceal`, the concealment state: run 0, the fade-in after a loss, the stored frame).  Other slots are decoded from
     their primary section (`wire.fec_primary`).  Graph: one hilc_fec_select after hilc_state_slots_apply compacts the wide rows
-    into the rows the unchanged concealment and dequantiser kernels read.  `fec_stages=0` captures exactly the graph without FEC."""
+    into the rows the unchanged concealment and dequantiser kernels read.  `fec_stages=0` captures exactly the graph without FEC.
+    `cng_order` = K (needs `sessions`; a SID of 1 + K bytes must fit `wire.packet_bytes(n, frames)`): comfort noise for senders in DTX
+    (dtx.py).  `step(..., sid=slots, silent=slots)`: a `sid` slot's row holds a SID packet (its n_per_stream entry is not read or
+    checked), a `silent` slot received nothing because its stream is in DTX.  A `sid` slot stores the SID's level and coefficients and
+    produces this hop's noise (filter memory from zero after a decoded hop, else carried over); a `silent` slot produces noise from
+    the stored SID, or is held (wav 0) when it has none.  A slot producing noise leaves its decoder caches and, with `conceal`, its
+    concealment state as they were; with `output_rate` the noise goes through the resampler, whose history advances.  Any decoded
+    slot (received, concealed or FEC) forgets its SID; a held slot keeps it; `start` clears it; `export` and a resume carry none.
+    Graph: the host marks `sid` / `silent` slots 2 / 3 in the hold row (so every existing kernel treats them as held); one
+    hilc_cng_synth writes the noise — after the final hilc_state_slots_hold without `output_rate`; with it, before the resampler,
+    followed by one hilc_state_slots_hold over the decoder caches (not the resampler history) of the slots that produced noise.
+    `cng_order=None` captures exactly the graph without comfort noise."""
 
     def __init__(self, model, batch: int, frames: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, conceal: bool = False, fade_hops: int = 4, output_rate: int = BASE_RATE,
-                 fec_stages: int = 0):
+                 fec_stages: int = 0, cng_order: Optional[int] = None):
         self.model, self.batch, self.frames, self.n, self.device = model, int(batch), int(frames), int(n), device
         self.output_rate = int(output_rate)
         self.rs, history = None, 0
@@ -842,6 +907,14 @@ class GraphedDecodeHop:
             raise ValueError(f"fade_hops must be an int >= 1, got {fade_hops!r}")
         self.fade_hops = int(fade_hops)
         self.fec_stages = _fec_stages(fec_stages, self.n)
+        self.cng_order = None
+        if cng_order is not None:
+            if isinstance(cng_order, bool) or int(cng_order) != cng_order or not 0 <= int(cng_order) <= dtx_def.MAX_ORDER:
+                raise ValueError(f"cng_order must be None or an int in [0, {dtx_def.MAX_ORDER}], got {cng_order!r}")
+            if not self.sessions:
+                raise ValueError("GraphedDecodeHop(cng_order=...) needs sessions=True")
+            self.cng_order = int(cng_order)
+            dtx_def.check_order(self.cng_order, wire.packet_bytes(self.n, self.frames), "GraphedDecodeHop(cng_order=...)")
         self.stride = wire.packet_bytes(self.n + self.fec_stages, self.frames)
         self.state = (StateBlock(model, batch, device, "dec", history), StateBlock(model, batch, device, "dec", history))
         self.parity = 0
@@ -877,6 +950,12 @@ class GraphedDecodeHop:
             self._conceal = torch.zeros(B, self.n + 3, dtype=torch.int32, device=device)
             gains, weights = wire.conceal_tables(self.fade_hops, 320 * self.frames)
             self._gains, self._weights = gains.to(device), weights.to(device)
+        if self.cng_order is not None:
+            # per slot: the CN state row (dtx.state_words, updated in place by hilc_cng_synth once per hop); device-only: the slots
+            # that produced noise this hop (their decoder caches are copied back)
+            self._cn = torch.zeros(B, dtx_def.state_words(self.cng_order), dtype=torch.int32, device=device)
+            self._cn_gains = torch.from_numpy(dtx_def.gain_table()).to(device)
+            self._restore = torch.zeros(B, dtype=torch.int32, device=device)
         self._uploaded = torch.cuda.Event()
         self.sched = ops.SchedWorkspace(device)
         self.graphs, self.outs = _capture_pair(self._hop, self._zero, device, warmup)
@@ -899,11 +978,22 @@ class GraphedDecodeHop:
             raise RuntimeError("GraphedDecodeHop.concealed: construct with conceal=True")
         return self._conceal[:, 0]
 
+    @property
+    def cng_state(self) -> Tensor:
+        """int32 `[B, dtx.state_words(cng_order)]` device view: each slot's CN state (has-SID, L, c, q, filter memory) after the last
+        step.  Read-only: written by the graph."""
+        if self.cng_order is None:
+            raise RuntimeError("GraphedDecodeHop.cng_state: construct with cng_order=K")
+        return self._cn
+
     def _zero(self) -> None:
         for blk in self.state:
             blk.zero_()
         if self.conceal:
             self._conceal.zero_()
+        if self.cng_order is not None:
+            self._cn.zero_()
+            self._restore.zero_()
 
     def _hop(self, p: int) -> Tensor:
         m = self.model
@@ -921,10 +1011,20 @@ class GraphedDecodeHop:
             wav, _ = m.decoder(q, *src.codec_dec, cache_out=dst.codec_dec)
         if self.conceal:
             ops.conceal_gain(wav, ramp, self._gains, self._weights)
+        cng = self.cng_order is not None
+        if cng and self.rs is not None:
+            # the noise goes through the resampler: written before it, and the decoder caches (not the history) of the slots that
+            # produced it are copied back from the block the hop read
+            wav = wav.contiguous()
+            ops.cng_synth(self.packets, self.hold, self._cn, wav, self._cn_gains, self.cng_order, self.action, self._restore)
+            ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self._restore, slices=len(src.layout.shapes) - 1)
         if self.rs is not None:
             wav = ops.resample_poly(wav.contiguous(), self.rs_taps, self.rs.L, self.rs.M, hist=src.hist, hist_out=dst.hist)
         if self.sessions:
             ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self.hold, wav=wav)
+        if cng and self.rs is None:
+            # the final hold treated the CN slots (hold 2 / 3) as held: their caches are as they were, the noise overwrites the zeros
+            ops.cng_synth(self.packets, self.hold, self._cn, wav, self._cn_gains, self.cng_order, self.action)
         return wav
 
     def _check(self, packets: Tensor, n_per_stream, held=(), fec=()) -> Tensor:
@@ -946,11 +1046,12 @@ class GraphedDecodeHop:
             raise ValueError(f"packets: uint8 [{self.batch}, {self.stride}] expected")
         return n
 
-    def step(self, packets: Tensor, n_per_stream, hold=None, lost=None, fec=None) -> Tensor:
+    def step(self, packets: Tensor, n_per_stream, hold=None, lost=None, fec=None, sid=None, silent=None) -> Tensor:
         """`hold`: slots (host ints) that do not advance on this hop (sessions=True only; None or empty: every slot advances).
         `lost`: slots (host ints) whose packet for this hop did not arrive (conceal=True only): concealed; their packet rows and
         n_per_stream entries are not read or checked.  `fec`: slots (host ints) whose packet for this hop was lost but whose next
-        packet is in their row (fec_stages >= 1 only): decoded from its redundant section"""
+        packet is in their row (fec_stages >= 1 only): decoded from its redundant section.  `sid` / `silent`: slots (host ints) whose
+        row holds a SID / that received nothing because their stream is in DTX (cng_order only): comfort noise"""
         held = SessionQueue.host_slots(hold)
         if held:
             if not self.sessions:
@@ -966,14 +1067,23 @@ class GraphedDecodeHop:
             raise RuntimeError("GraphedDecodeHop.step(fec=...): construct with fec_stages >= 1")
         if self.fec_stages:
             red = self._slots.fec_slots(red, held, gone)
+        sids, quiet = SessionQueue.host_slots(sid), SessionQueue.host_slots(silent)
+        if (sids or quiet) and self.cng_order is None:
+            raise RuntimeError("GraphedDecodeHop.step(sid=..., silent=...): construct with cng_order=K")
+        if self.cng_order is not None:
+            sids, quiet = self.queue.cn_slots(sids, quiet, held, gone, red)
         if self.sessions:
             held = set(held) | self.queue.stops
-        n = self._check(packets, n_per_stream, set(held) | set(gone), red)
+        n = self._check(packets, n_per_stream, set(held) | set(gone) | set(sids) | set(quiet), red)
         self._uploaded.synchronize()          # the previous upload's copy has left the pinned buffer
         B, h = self.batch, self._h_ctl
         h[0].zero_()
         h[1].copy_(n)
         _mark(h[2], held)
+        if sids:
+            h[2, torch.tensor(sids, dtype=torch.long)] = 2
+        if quiet:
+            h[2, torch.tensor(quiet, dtype=torch.long)] = 3
         if self.conceal:
             _mark(h[3], gone)
         if self.fec_stages:

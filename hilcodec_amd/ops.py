@@ -983,6 +983,56 @@ def _fec_select(packets, fec, n_slot, n, m, frames):
 _register("fec_select", "(Tensor packets, Tensor fec, Tensor(a!) n_slot, int n, int m, int frames) -> Tensor", _fec_select,
           lambda packets, fec, n_slot, n, m, frames: packets.new_empty(packets.shape[0], _packet_stride(n, frames)))
 
+# ======================================================================================================
+# discontinuous transmission and comfort noise of the sender / receiver (graph_step.GraphedEncodeHop(dtx=),
+# GraphedDecodeHop(cng_order=); definition: hilcodec_amd/dtx.py; semantics: include/hilcodec_amd.h)
+# ======================================================================================================
+def _dtx_encode(x, action, hold, run, packets, nbytes, indices, prev, level_thr, thr_vad, order, hangover, sid_interval):
+    B = run.numel()
+    if x.dim() != 3 or x.shape[0] != B or x.shape[1] != 1 or x.shape[2] % 320 or x.shape[2] == 0:
+        raise RuntimeError(f"dtx_encode: x must be [{B}, 1, 320 T]")
+    T = x.shape[2] // 320
+    if indices.dim() != 3 or indices.shape[1] != B or indices.shape[2] != T:
+        raise RuntimeError(f"dtx_encode: indices must be [n, {B}, {T}]")
+    if packets.dim() != 2 or packets.shape[0] != B or nbytes.numel() != B or level_thr.numel() != 127:
+        raise RuntimeError(f"dtx_encode: packets must be [{B}, stride], nbytes [{B}], level_thr [127]")
+    for name, row in (("action", action), ("hold", hold)):
+        if row is not None and row.numel() != B:
+            raise RuntimeError(f"dtx_encode: {name} needs {B} entries")
+    if prev is not None and (prev.dim() != 2 or prev.shape[0] != B):
+        raise RuntimeError(f"dtx_encode: prev must be [{B}, words]")
+    kind = _new(run, B, dtype=torch.int32)
+    check(lib.hilc_dtx_encode(_ptr(x.contiguous()), _ptr(action, torch.int32), _ptr(hold, torch.int32), _ptr(run, torch.int32),
+                              _ptr(kind, torch.int32), _ptr(packets, torch.uint8), _ptr(nbytes, torch.int32), _ptr(indices, torch.int64),
+                              _ptr(prev, torch.int32), _ptr(level_thr, torch.float64), float(thr_vad), B, T, order, hangover,
+                              sid_interval, indices.shape[0], packets.shape[1], 0 if prev is None else prev.shape[1], _stream()),
+          "hilc_dtx_encode")
+    return kind
+
+
+_register("dtx_encode", "(Tensor x, Tensor? action, Tensor? hold, Tensor(a!) run, Tensor(b!) packets, Tensor(c!) nbytes, "
+          "Tensor(d!) indices, Tensor(e!)? prev, Tensor level_thr, float thr_vad, int order, int hangover, int sid_interval) -> Tensor",
+          _dtx_encode, lambda x, action, hold, run, packets, nbytes, indices, prev, level_thr, thr_vad, order, hangover, sid_interval:
+          run.new_empty(run.shape[0], dtype=torch.int32))
+
+
+def _cng_synth(packets, action, hold, state, wav, restore, gains, order):
+    B = hold.numel()
+    if wav.dim() != 3 or wav.shape[0] != B or wav.shape[1] != 1 or wav.shape[2] % 320 or wav.shape[2] == 0 or not wav.is_contiguous():
+        raise RuntimeError(f"cng_synth: wav must be a contiguous [{B}, 1, 320 T]")
+    if packets.dim() != 2 or packets.shape[0] != B or state.shape != (B, 3 + 2 * order) or gains.numel() != 128:
+        raise RuntimeError(f"cng_synth: packets must be [{B}, stride], state [{B}, {3 + 2 * order}], gains [128]")
+    for name, row in (("action", action), ("restore", restore)):
+        if row is not None and row.numel() != B:
+            raise RuntimeError(f"cng_synth: {name} needs {B} entries")
+    check(lib.hilc_cng_synth(_ptr(packets, torch.uint8), _ptr(action, torch.int32), _ptr(hold, torch.int32), _ptr(state, torch.int32),
+                             _ptr(wav), _ptr(restore, torch.int32), _ptr(gains), B, wav.shape[2] // 320, order, packets.shape[1],
+                             _stream()), "hilc_cng_synth")
+
+
+_register("cng_synth", "(Tensor packets, Tensor? action, Tensor(a!) hold, Tensor(b!) state, Tensor(c!) wav, Tensor(d!)? restore, "
+          "Tensor gains, int order) -> ()", _cng_synth, lambda packets, action, hold, state, wav, restore, gains, order: None)
+
 _OPS = torch.ops.hilcodec
 
 
@@ -1484,11 +1534,12 @@ def state_slots_gather(block: Tensor, layout: StateLayout, slots: Tensor) -> Ten
 
 
 def state_slots_hold(src: Tensor, dst: Tensor, layout: StateLayout, hold: Tensor, wav: Optional[Tensor] = None,
-                     indices: Optional[Tensor] = None, packets: Optional[Tensor] = None, nbytes: Optional[Tensor] = None) -> None:
+                     indices: Optional[Tensor] = None, packets: Optional[Tensor] = None, nbytes: Optional[Tensor] = None,
+                     slices: Optional[int] = None) -> None:
     """Streams b with hold[b] != 0 (int32 `[layout.streams]` on the device) do not advance: their parts of `dst` (the block a hop
     wrote) are copied back from `src` (the block it read), their `wav` rows (`[streams, ...]` fp32) are set to 0, their `indices`
     (`[n, streams, T]` int64) to -1, their `packets` rows (`[streams, stride]` uint8) and `nbytes` (`[streams]` int32) to 0.
-    Every output is optional; in place."""
+    Every output is optional; in place.  `slices`: only the layout's first `slices` slices (None: all of them)."""
     B = layout.streams
     if src.numel() < layout.total or dst.numel() < layout.total or hold.numel() != B:
         raise RuntimeError("state_slots_hold: src, dst or hold does not match the layout")
@@ -1501,6 +1552,8 @@ def state_slots_hold(src: Tensor, dst: Tensor, layout: StateLayout, hold: Tensor
     if nbytes is not None and nbytes.numel() != B:
         raise RuntimeError(f"state_slots_hold: nbytes must have {B} entries")
     off, lens = layout.tables(src.device)
+    if slices is not None:
+        off, lens = off[:slices], lens[:slices]
     _OPS.state_slots_hold(src, dst, off, lens, hold, wav, indices, packets, nbytes)
 
 
@@ -1558,6 +1611,27 @@ def fec_select(packets: Tensor, fec: Tensor, n_slot: Tensor, n: int, m: int, fra
     frames)]`: `wire.fec_primary` of each row, or `wire.fec_redundant` where `fec` (int32 `[B]`) is set, whose `n_slot` entry
     (int32 `[B]`, in place: the row's primary n on entry) becomes m."""
     return _OPS.fec_select(packets, fec, n_slot, int(n), int(m), int(frames))
+
+
+def dtx_encode(x: Tensor, run: Tensor, packets: Tensor, nbytes: Tensor, indices: Tensor, level_thr: Tensor, thr_vad: float, order: int,
+               hangover: int, sid_interval: int, action: Optional[Tensor] = None, hold: Optional[Tensor] = None,
+               prev: Optional[Tensor] = None) -> Tensor:
+    """The DTX sender's step after its packer (dtx.encode_model): the 24 kHz hop `x` fp32 `[B, 1, 320 T]` is analysed per stream,
+    `run` (int32 `[B]`) advances in place, SID and SILENT hops rewrite their `packets` row (uint8 `[B, stride >= 1 + order]`),
+    `nbytes` (int32 `[B]`) and `indices` (int64 `[n, B, T]`) in place, and clear word 0 of their `prev` row (the FEC packer's
+    int32 `[B, 1 + m T]` output, optional).  `level_thr`: float64 `[127]` (dtx.level_table) on the device.  `action` / `hold`
+    (int32 `[B]`, optional): the session rows.  Returns each stream's kind (int32 `[B]`: dtx.HELD / SPEECH / SID / SILENT)."""
+    return _OPS.dtx_encode(x, action, hold, run, packets, nbytes, indices, prev, level_thr, float(thr_vad), int(order), int(hangover),
+                           int(sid_interval))
+
+
+def cng_synth(packets: Tensor, hold: Tensor, state: Tensor, wav: Tensor, gains: Tensor, order: int, action: Optional[Tensor] = None,
+              restore: Optional[Tensor] = None) -> None:
+    """The CN receiver's step after its decoder (dtx.cng_model), in place: per slot, `hold` (int32 `[B]`) 2 = a SID is in its
+    `packets` row (uint8 `[B, stride >= 1 + order]`), 3 = silent, 0 = decoded this hop, else held.  Slots that produce noise get
+    their `wav` row (fp32 contiguous `[B, 1, 320 T]`) overwritten, hold 0 and `restore` 1; a silent slot without a SID gets hold 1.
+    `state`: int32 `[B, 3 + 2 order]` (dtx.state_words); `gains`: fp32 `[128]` (dtx.gain_table) on the device."""
+    _OPS.cng_synth(packets, action, hold, state, wav, restore, gains, int(order))
 
 
 def resample_poly(x: Tensor, taps: Tensor, L: int, M: int, hist: Optional[Tensor] = None, hist_out: Optional[Tensor] = None) -> Tensor:

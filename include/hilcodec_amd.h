@@ -37,7 +37,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -518,6 +518,38 @@ int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, c
                               const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream);
 int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m,
                     void* stream);
+
+/* ---- discontinuous transmission (DTX) and comfort noise (CN) of the packet sender and receiver (additive under ABI 16) ----------
+ * Two entry points added WITHOUT a version bump, as the packet, concealment, resampling and FEC entry points above.  The definition,
+ * bit for bit, is hilcodec_amd/dtx.py; K = order in 0..16 (else HILC_ERR_RANGE), S = 320 T samples per hop, and a SID (byte 0 the
+ * level L in 0..127, bytes 1..K the int8 reflection coefficients q_i) must fit a packet row: stride >= 1 + K (else HILC_ERR_SHAPE).
+ * hilc_dtx_encode: the sender's last launch before hilc_state_slots_hold, after the packer.  x fp32 [B][S] (the encoder's 24 kHz
+ * hop); action and hold optional int32 [B] (NULL = 0): the rows of hilc_state_slots_apply / hilc_state_slots_hold; run int32 [B]
+ * (in place); kind int32 [B] (out: 0 held, 1 speech, 2 SID, 3 silent); packets uint8 [B][stride] and nbytes int32 [B] as the packer
+ * wrote them; indices int64 [n_max][B][T]; prev optional int32 [B][prev_words] (the FEC packer's output row, word 0 its valid flag);
+ * level_thr float64 [127] (dtx.level_table); thr_vad the activity threshold on R[0] / S; hangover H >= 0, sid_interval I >= 1.
+ * Per stream b: action[b] != 0 resets run[b] to 0 first; hold[b] != 0: kind 0, nothing else.  Otherwise: R[k], k <= K, in float64
+ * (lane l of 64 sums x[s] x[s - k] over s = l mod 64, s >= k, in increasing s, then the 64 partials in lane order); active iff
+ * R[0] / S >= thr_vad; Levinson-Durbin on R'[0] = R[0] (1 + 2^-13) -> k_i, E_K; L = #{j : E_K / S < level_thr[j]};
+ * q_i = clamp(rint(128 k_i), -127, 127); run = active ? 0 : run <= H ? run + 1 : H + 1 + (run - H) mod I; kind = speech if active or
+ * run <= H, SID if run == H + 1, else silent.  SID: packets[b] = L, q_1..q_K, then zeros, nbytes[b] = 1 + K; silent: packets[b] = 0,
+ * nbytes[b] = 0; both: indices of b = -1 and prev[b][0] = 0.  Speech rows are not touched.
+ * hilc_cng_synth: the receiver's launch after the decoder.  packets uint8 [B][stride] (a SID slot's row: the SID); action optional;
+ * hold int32 [B] (in place): 2 = a SID arrived, 3 = silent (the stream is in DTX), 0 = decoded, anything else = held; state int32
+ * [B][3 + 2 K] (in place): has-SID, L, c (noise hops since the start, mod 2^32), q_1..q_K, then K fp32 words of filter memory
+ * y[-K..-1]; wav fp32 [B][S]; restore optional int32 [B] (out: 1 where the slot produced noise, else 0); gains fp32 [128]
+ * (dtx.gain_table).  Per slot: action != 0 clears the state row first.  hold 2: L = min(byte 0, 127), q_i = clamp(int8 byte i,
+ * -127, 127) are stored, has = 1, the filter memory starts from zero if has was 0; the slot produces noise.  hold 3: with has, noise
+ * from the stored parameters; without, hold[b] = 1.  hold 0: has = 0.  Noise: wav[b][s] = y[s] = g u[s] - a_K y[s - K] - ... -
+ * a_1 y[s - 1] in fp32 (each product and difference rounded, left to right), g = gains[L], a = step-up of q_i / 128 in float64
+ * rounded to fp32, u[s] = fp32(h >> 8) 2^-23 - 1, h = lowbias32(((c S + s) mod 2^32) ^ ((b + 1) 0x9E3779B9 mod 2^32)); if some |y[s]| >= 16
+ * or is not finite the row and the memory become 0; then c += 1, the memory = the last K outputs, hold[b] = 0.  Rows of slots without noise are not touched.  NULL pointers: HILC_ERR_NULL; B or
+ * T <= 0: HILC_ERR_SHAPE.  Both: one wave per stream. */
+int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes,
+                    int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover,
+                    int sid_interval, int n_max, int stride, int prev_words, void* stream);
+int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains,
+                   int B, int T, int order, int stride, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,410 @@
+"""GPU: discontinuous transmission and comfort noise of the graphed sender / receiver (GraphedEncodeHop(dtx=DtxConfig(...)),
+GraphedDecodeHop(cng_order=K), `step(..., sid=slots, silent=slots)`).  The two kernels against hilcodec_amd/dtx.py, the sender
+against a sender without DTX, the receiver against a receiver without comfort noise that holds the CN slots — every comparison bit
+for bit (torch.equal)."""
+import numpy as np
+import pytest
+import torch
+
+from hilcodec_amd import dtx, synth, wire
+from hilcodec_amd.resample import design, hop_samples, reference
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda:0")
+HOP = 320
+
+
+def build_streaming(seed=7, name="hil_speech"):
+    from hilcodec_amd.models.hilcodec.streaming import HILCodec
+    mk = dict(synth.model_kwargs(name))
+    sd = synth.synth_state_dict(name, seed=seed)
+    for k in ("spec_learnable", "causal", "pad_mode"):
+        mk.pop(k)
+    model = HILCodec(24000, **mk).eval()
+    model.load_offline_state_dict(sd)
+    model.remove_weight_reparameterizations()
+    return model
+
+
+@pytest.fixture(scope="module")
+def speech():
+    return build_streaming()
+
+
+def ar2(gen, B, S, a1=-1.2, a2=0.5):
+    e = torch.randn(B, S + 64, generator=gen, dtype=torch.float64)
+    y = torch.zeros_like(e)
+    for s in range(2, S + 64):
+        y[:, s] = e[:, s] - a1 * y[:, s - 1] - a2 * y[:, s - 2]
+    y = y[:, 64:]
+    return (y / y.pow(2).mean(dim=1, keepdim=True).sqrt()).float()
+
+
+def make_signals(gen, B, S, cfg):
+    """white noise at random levels, AR(2) noise, digital silence, full scale, and constants whose E sits a few ulps around thr_vad
+    and around level thresholds"""
+    x = torch.randn(B, S, generator=gen) * (10.0 ** (-torch.rand(B, 1, generator=gen) * 6.0))
+    kinds = torch.arange(B) % 6
+    x[kinds == 1] = ar2(gen, int((kinds == 1).sum()), S) * 10.0 ** -2.5
+    x[kinds == 2] = 0.0
+    x[kinds == 3] = torch.where(torch.rand(int((kinds == 3).sum()), S, generator=gen) < 0.5, -1.0, 1.0)
+    near = np.float32(np.sqrt(cfg.thr_vad))
+    thr = dtx.level_table()
+    for i in torch.nonzero(kinds >= 4).flatten().tolist():
+        base = near if kinds[i] == 4 else np.float32(np.sqrt(thr[i % 127]) * 128.0)   # E_K ~ E / 2^13 for a constant
+        v = base
+        for _ in range(int(i % 7) - 3):
+            v = np.nextafter(v, np.float32(1.0))
+        for _ in range(3 - int(i % 7)):
+            v = np.nextafter(v, np.float32(0.0))
+        x[i] = float(v)
+    return x
+
+
+# ---------------------------------------------------------------- the kernels against dtx.py
+@pytest.mark.parametrize("B", [1, 7, 1024])
+@pytest.mark.parametrize("T", [1, 3])
+@pytest.mark.parametrize("K", [0, 1, 10, 16])
+def test_dtx_encode_kernel(B, T, K):
+    from hilcodec_amd import ops
+    n = 8 if T == 3 else 14                                  # rows of 30 / 18 bytes: a SID of 1 + K fits
+    stride = wire.packet_bytes(n, T)
+    S = 320 * T
+    gen = torch.Generator().manual_seed(B + 10 * T + 100 * K)
+    cfg = dtx.DtxConfig(threshold_db=-40.0, hangover=2, sid_interval=3, order=K)
+    run = torch.zeros(B, dtype=torch.int32)
+    d_run = run.to(DEV)
+    thr = torch.from_numpy(dtx.level_table()).to(DEV)
+    for hop in range(8):
+        x = make_signals(gen, B, S, cfg)
+        if hop % 2:
+            x[torch.rand(B, generator=gen) < 0.5] *= 1e-4             # switch activity
+        action = ((torch.rand(B, generator=gen) < 0.1) * torch.randint(-1, 3, (B,), generator=gen)).to(torch.int32)
+        hold = (torch.rand(B, generator=gen) < 0.15).to(torch.int32) * torch.randint(1, 4, (B,), generator=gen, dtype=torch.int32)
+        packets = torch.randint(0, 256, (B, stride), generator=gen, dtype=torch.uint8)
+        nbytes = torch.randint(0, stride + 1, (B,), generator=gen, dtype=torch.int32)
+        indices = torch.randint(-1, 1024, (n, B, T), generator=gen)
+        prev = torch.randint(0, 1024, (B, 1 + 2 * T), generator=gen, dtype=torch.int32)
+        with_rows = hop % 3 != 2                                  # also without the optional rows
+        a_, h_, p_ = (action, hold, prev) if with_rows else (None, None, None)
+        exp = dtx.encode_model(x, run, a_, h_, packets, nbytes, indices, p_, cfg)
+        d = [t.to(DEV) for t in (packets, nbytes, indices, prev)]
+        kind = ops.dtx_encode(x.view(B, 1, S).to(DEV), d_run, d[0], d[1], d[2], thr, cfg.thr_vad, K, cfg.hangover, cfg.sid_interval,
+                              a_.to(DEV) if with_rows else None, h_.to(DEV) if with_rows else None, d[3] if with_rows else None)
+        torch.cuda.synchronize()
+        got = (d_run.cpu(), kind.cpu(), d[0].cpu(), d[1].cpu(), d[2].cpu(), d[3].cpu() if with_rows else None)
+        for name, g, e in zip(("run", "kind", "packets", "nbytes", "indices", "prev"), got, exp):
+            if e is not None:
+                assert torch.equal(g, e), f"hop {hop}: {name}"
+        run = exp[0]
+    assert int((exp[1] == dtx.SID).sum()) + int((exp[1] == dtx.SILENT).sum()) >= 0
+
+
+@pytest.mark.parametrize("K", [0, 1, 10, 16])
+@pytest.mark.parametrize("T", [1, 2])
+def test_cng_synth_kernel(K, T):
+    from hilcodec_amd import ops
+    B = 67
+    S = 320 * T
+    stride = max(wire.packet_bytes(8, T), 1 + K)
+    gen = torch.Generator().manual_seed(K + 31 * T)
+    state = torch.zeros(B, dtx.state_words(K), dtype=torch.int32)
+    d_state = state.to(DEV)
+    gains = torch.from_numpy(dtx.gain_table()).to(DEV)
+    for hop in range(7):
+        hold = torch.randint(0, 4, (B,), generator=gen, dtype=torch.int32)
+        if hop == 0:
+            hold[:] = 2                                          # every slot starts with a SID
+        hold[:4] = torch.tensor([2, 3, 3, 3], dtype=torch.int32) if hop != 3 else torch.tensor([2, 2, 0, 3], dtype=torch.int32)  # SID mid-run
+        packets = torch.randint(0, 256, (B, stride), generator=gen, dtype=torch.uint8)  # L > 127, q = -128: clamped
+        packets[::3, 0] = torch.randint(0, 128, (packets[::3].shape[0],), generator=gen, dtype=torch.uint8)
+        if K:
+            packets[4:7, 0] = 0                                  # slots 4..6: a SID the fp32 filter cannot follow -> silence
+            packets[4:7, 1:1 + K] = torch.tensor(-127, dtype=torch.int8).view(torch.uint8)
+        action = ((torch.rand(B, generator=gen) < 0.1) * torch.randint(-1, 3, (B,), generator=gen)).to(torch.int32)
+        action[:4] = 0
+        with_action = hop % 2 == 0
+        exp_state, exp_hold, exp_restore, noise = dtx.cng_model(state, packets, hold, action if with_action else None, K, T)
+        wav = torch.full((B, 1, S), 7.0, device=DEV)
+        d_hold, restore = hold.to(DEV), torch.full((B,), 5, dtype=torch.int32, device=DEV)
+        ops.cng_synth(packets.to(DEV), d_hold, d_state, wav, gains, K, action.to(DEV) if with_action else None, restore)
+        torch.cuda.synchronize()
+        exp_wav = torch.where(exp_restore.bool()[:, None], noise, torch.full((B, S), 7.0))
+        assert torch.equal(d_state.cpu(), exp_state), f"hop {hop}: state"
+        assert torch.equal(d_hold.cpu(), exp_hold), f"hop {hop}: hold"
+        assert torch.equal(restore.cpu(), exp_restore), f"hop {hop}: restore"
+        assert torch.equal(wav.cpu().view(B, S), exp_wav), f"hop {hop}: wav"
+        assert bool(exp_restore.any())
+        state = exp_state
+    # slot 0 received a SID every hop: its noise continues the filter memory of the previous hop
+    assert int(state[0, dtx.ST_COUNT]) == 7 and int(state[0, dtx.ST_HAS]) == 1
+
+
+# ---------------------------------------------------------------- the sender
+def signal(B, S_in, hops, seed):
+    """half the streams switch between speech-like bursts and low-level noise every few hops, the others stay active"""
+    x = synth.synth_clips(B, S_in * hops, seed=seed)
+    gain = torch.ones(B, hops)
+    rng = np.random.default_rng(seed)
+    for b in range(0, B, 2):
+        period = int(rng.integers(3, 7))
+        phase = int(rng.integers(0, period))
+        gain[b] = torch.tensor([1.0 if ((h + phase) // period) % 2 == 0 else 3e-5 for h in range(hops)])
+    return (x.view(B, 1, hops, S_in) * gain.view(B, 1, hops, 1)).view(B, 1, hops * S_in)
+
+
+def check_sender(model, B, hops, seed, cfg, n=8, input_rate=24000, fec=0, plan=True, frames=1):
+    from hilcodec_amd.graph_step import GraphedEncodeHop
+    S_in = hop_samples(frames, input_rate)
+    x = signal(B, S_in, hops, seed).to(DEV)
+    kw = dict(sessions=True, input_rate=input_rate, fec_stages=fec)
+    d = GraphedEncodeHop(model, B, HOP * frames, n, DEV, dtx=cfg, **kw)
+    p = GraphedEncodeHop(model, B, HOP * frames, n, DEV, **kw)
+    rs = design(input_rate, 24000) if input_rate != 24000 else None
+    hist = torch.zeros(B, 1, rs.history) if rs is not None else None
+    run = torch.zeros(B, dtype=torch.int32)
+    quiet = [False] * B                                       # the slot's last (not held) hop was SID / SILENT
+    seen = {dtx.SPEECH: 0, dtx.SID: 0, dtx.SILENT: 0, dtx.HELD: 0}
+    for h in range(hops):
+        hold, action = set(), torch.zeros(B, dtype=torch.int32)
+        if plan and h == 3:
+            for s in (d, p):
+                s.start(1)
+                s.start(3)
+            hold.add(3)                                       # started and held on the same hop
+            action[1] = action[3] = -1
+        if plan and h == 5:
+            for s in (d, p):
+                s.stop(2)
+        if plan and h == 9:
+            for s in (d, p):
+                s.start(2)
+            action[2] = -1
+        if plan and h >= 2:
+            hold.add(4 + h % 3)
+        chunk = x[:, :, S_in * h:S_in * (h + 1)].contiguous()
+        pk, nb = d.step(chunk, hold=sorted(hold))
+        pk0, nb0 = p.step(chunk, hold=sorted(hold))
+        held = hold | set(d.stopped)
+        hrow = torch.zeros(B, dtype=torch.int32)
+        if held:
+            hrow[sorted(held)] = 1
+        x24 = chunk.cpu()
+        if rs is not None:
+            x24, hist_new = reference(chunk, rs, hist)
+            keep = torch.zeros(B, dtype=torch.bool)
+            if held:
+                keep[sorted(held)] = True
+            hist = torch.where(keep.view(B, 1, 1), hist, hist_new)
+        exp_run, exp_kind, exp_pk, exp_nb, exp_idx, _ = dtx.encode_model(x24.view(B, -1), run, action, hrow, pk0, nb0, p.indices,
+                                                                          None, cfg)
+        if fec:
+            # the first speech hop after DTX carries no redundant section: the plain part of the FEC sender's packet
+            for b in range(B):
+                if int(exp_kind[b]) == dtx.SPEECH and quiet[b]:
+                    plain = wire.packet_bytes(n, frames)
+                    exp_pk[b, plain:] = 0
+                    exp_nb[b] = plain
+        assert torch.equal(d.kind.cpu(), exp_kind), f"hop {h}: kind"
+        assert torch.equal(pk.cpu(), exp_pk), f"hop {h}: packets"
+        assert torch.equal(nb.cpu(), exp_nb), f"hop {h}: nbytes"
+        assert torch.equal(d.indices.cpu(), exp_idx), f"hop {h}: indices"
+        for b in range(B):
+            k = int(exp_kind[b])
+            seen[k] += 1
+            if k != dtx.HELD:
+                quiet[b] = k in (dtx.SID, dtx.SILENT)
+            elif int(action[b]):
+                quiet[b] = False
+        run = exp_run
+    assert seen[dtx.SID] > 0 and seen[dtx.SILENT] > 0 and seen[dtx.SPEECH] > 0
+    return d
+
+
+def test_sender_dtx(speech):
+    check_sender(speech, 12, 16, seed=3, cfg=dtx.DtxConfig(threshold_db=-50.0, hangover=2, sid_interval=3, order=8))
+
+
+def test_sender_dtx_input_rate(speech):
+    check_sender(speech, 10, 14, seed=5, cfg=dtx.DtxConfig(threshold_db=-50.0, hangover=1, sid_interval=2, order=9),
+                 input_rate=16000, plan=False, frames=3)
+
+
+def test_sender_dtx_fec(speech):
+    check_sender(speech, 12, 16, seed=9, cfg=dtx.DtxConfig(threshold_db=-50.0, hangover=0, sid_interval=3, order=8), fec=2)
+
+
+# ---------------------------------------------------------------- the receiver
+def check_receiver(model, B, hops, seed, K, n=8, conceal=False, fec=0, output_rate=24000):
+    """slot roles per hop: received, SID, silent (with or without a stored SID), held, lost, FEC; the CN receiver against a receiver
+    without comfort noise that holds the CN slots, the noise against dtx.cng_model.  With `output_rate` the plain receiver runs at
+    24 kHz and every row of the CN receiver is checked against resample.reference of its 24 kHz hop (decoded or noise) with a
+    history kept on the host (the history of a slot that produced noise has advanced through it, unlike a held slot's)"""
+    from hilcodec_amd.graph_step import GraphedDecodeHop
+    kw = dict(sessions=True, conceal=conceal, fec_stages=fec, output_rate=output_rate)
+    c = GraphedDecodeHop(model, B, 1, n, DEV, cng_order=K, **kw)
+    p = GraphedDecodeHop(model, B, 1, n, DEV, **dict(kw, output_rate=24000))
+    rs = design(24000, output_rate) if output_rate != 24000 else None
+    hist = torch.zeros(B, 1, rs.history) if rs is not None else None
+    stride = c.stride
+    rng = np.random.default_rng(seed)
+    gen = torch.Generator().manual_seed(seed)
+    st = torch.zeros(B, dtx.state_words(K), dtype=torch.int32)
+    cn_total = 0
+    for h in range(hops):
+        roles = rng.choice(6 if (conceal and fec) else (5 if conceal or fec else 4), size=B)
+        roles[0] = 1 if h % 4 == 0 else 2                     # slot 0: a SID, then silent hops
+        roles[1] = 2 if h < 2 else roles[1]                   # slot 1: silent before any SID: held
+        sid = [b for b in range(B) if roles[b] == 1]
+        silent = [b for b in range(B) if roles[b] == 2]
+        hold = [b for b in range(B) if roles[b] == 3]
+        extra = [b for b in range(B) if roles[b] >= 4]
+        lost = extra[::2] if conceal and fec else (extra if conceal else [])
+        fec_slots = [b for b in extra if b not in lost] if fec else []
+        action = torch.zeros(B, dtype=torch.int32)
+        if h == 5:
+            for r in (c, p):
+                r.start(0)                                    # a start clears the CN state
+            action[0] = -1
+        codes = torch.randint(0, 1024, (n + max(fec, 0), B, 1), generator=gen)
+        packets = torch.zeros(B, stride, dtype=torch.uint8)
+        n_per = [n] * B
+        for b in range(B):
+            row = wire.pack_stream_packet(codes[:n + fec, b])
+            packets[b, :len(row)] = torch.frombuffer(bytearray(row), dtype=torch.uint8)
+        for b in sid:
+            L = int(rng.integers(0, 128))
+            q = rng.integers(-127, 128, size=K)
+            blob = dtx.pack_sid(L, q)
+            packets[b] = 0
+            packets[b, :len(blob)] = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
+            n_per[b] = 0                                      # not read or checked
+        y = c.step(packets, n_per, hold=hold, lost=lost or None, fec=fec_slots or None, sid=sid, silent=silent)
+        n_plain = list(n_per)
+        for b in sid:
+            n_plain[b] = n
+        y0 = p.step(packets, n_plain, hold=sorted(hold + sid + silent), lost=lost or None, fec=fec_slots or None)
+        torch.cuda.synchronize()
+        hrow = torch.zeros(B, dtype=torch.int32)
+        for slots, v in ((hold, 1), (sid, 2), (silent, 3)):
+            if slots:
+                hrow[slots] = v
+        for b in lost:
+            # a lost slot with nothing to repeat is held by the graph (wav 0): its hold row is 1 when the synth runs
+            if not bool(y0.cpu().view(B, -1)[b].any()):
+                hrow[b] = 1
+        st, hrow_out, restore, noise = dtx.cng_model(st, packets, hrow, action, K, 1)
+        cn = restore.bool()
+        cn_total += int(cn.sum())
+        ya, y0a = y.cpu().view(B, -1), y0.cpu().view(B, -1)
+        if rs is None:
+            assert torch.equal(ya[~cn], y0a[~cn]), f"hop {h}: non-CN wav"
+            assert torch.equal(ya[cn], noise[cn]), f"hop {h}: CN wav"
+        else:
+            held = hrow_out != 0                              # held by the caller or by the graph: wav 0, history kept
+            hist[action != 0] = 0                             # a start zeroes the history
+            src24 = torch.where(cn[:, None], noise, y0a).view(B, 1, 320)
+            out, hist_new = reference(src24, rs, hist)
+            exp = torch.where(held[:, None], torch.zeros(()), out.view(B, -1))
+            hist = torch.where(held.view(B, 1, 1), hist, hist_new)
+            assert torch.equal(ya, exp), f"hop {h}: wav at {output_rate} Hz"
+            assert torch.equal(c.cache_dec[-1].cpu(), hist), f"hop {h}: resampler history"
+        cd, cd0 = c.cache_dec, p.cache_dec
+        for i in range(len(cd0)):
+            assert torch.equal(cd[i], cd0[i]), f"hop {h}: decoder cache {i}"
+        if conceal:
+            assert torch.equal(c.concealed, p.concealed) and torch.equal(c._conceal, p._conceal), f"hop {h}: conceal state"
+        assert torch.equal(c.cng_state.cpu(), st), f"hop {h}: CN state"
+        assert 1 not in set(torch.nonzero(cn).flatten().tolist()) or h >= 2
+    assert cn_total > 0
+
+
+def test_receiver_cng(speech):
+    check_receiver(speech, 10, 10, seed=1, K=8)
+
+
+def test_receiver_cng_output_rate(speech):
+    check_receiver(speech, 10, 10, seed=2, K=9, output_rate=48000)
+
+
+def test_receiver_cng_conceal_fec(speech):
+    check_receiver(speech, 12, 10, seed=4, K=8, conceal=True, fec=2)
+
+
+def test_receiver_cng_conceal_fec_output_rate(speech):
+    check_receiver(speech, 12, 8, seed=6, K=4, conceal=True, fec=2, output_rate=48000)
+
+
+def test_silent_without_sid_is_held(speech):
+    from hilcodec_amd.graph_step import GraphedDecodeHop
+    B, n = 4, 8
+    c = GraphedDecodeHop(speech, B, 1, n, DEV, sessions=True, cng_order=8)
+    pk = torch.randint(0, 256, (B, c.stride), dtype=torch.uint8)
+    c.step(pk, [n] * B)
+    before = [t.clone() for t in c.cache_dec]
+    y = c.step(pk, [n] * B, silent=[2])
+    assert torch.equal(y[2].cpu(), torch.zeros_like(y[2].cpu()))
+    assert all(torch.equal(a[2], b[2]) for a, b in zip(c.cache_dec, before))
+    assert int(c.cng_state[2, dtx.ST_HAS]) == 0 and int(c.cng_state[2, dtx.ST_COUNT]) == 0
+
+
+# ---------------------------------------------------------------- production shape
+def test_production_shape(speech):
+    """sender -> host transport (kind -> packet / sid / silent) -> receiver at 1 024 streams, n = 8, one frame per hop"""
+    from hilcodec_amd.graph_step import GraphedDecodeHop, GraphedEncodeHop
+    B, n, hops = 1024, 8, 14
+    cfg = dtx.DtxConfig(threshold_db=-50.0, hangover=2, sid_interval=3, order=8)
+    x = signal(B, HOP, hops, seed=11).to(DEV)
+    s = GraphedEncodeHop(speech, B, HOP, n, DEV, sessions=True, dtx=cfg)
+    s0 = GraphedEncodeHop(speech, B, HOP, n, DEV, sessions=True)
+    c = GraphedDecodeHop(speech, B, 1, n, DEV, sessions=True, cng_order=cfg.order)
+    c0 = GraphedDecodeHop(speech, B, 1, n, DEV, sessions=True)
+    run = torch.zeros(B, dtype=torch.int32)
+    st = torch.zeros(B, dtx.state_words(cfg.order), dtype=torch.int32)
+    counts = {dtx.SPEECH: 0, dtx.SID: 0, dtx.SILENT: 0}
+    for h in range(hops):
+        chunk = x[:, :, HOP * h:HOP * (h + 1)].contiguous()
+        pk, nb = s.step(chunk)
+        pk0, nb0 = s0.step(chunk)
+        z = torch.zeros(B, dtype=torch.int32)
+        exp = dtx.encode_model(chunk.cpu().view(B, -1), run, z, z, pk0, nb0, s0.indices, None, cfg)
+        kind = s.kind.cpu()
+        assert torch.equal(kind, exp[1]) and torch.equal(pk.cpu(), exp[2]) and torch.equal(nb.cpu(), exp[3]), f"hop {h}: sender"
+        run = exp[0]
+        for k in counts:
+            counts[k] += int((kind == k).sum())
+        # transport: speech packets with their n, SIDs, nothing for SILENT
+        rows = pk.cpu()
+        n_per = [n] * B
+        sid = torch.nonzero(kind == dtx.SID).flatten().tolist()
+        silent = torch.nonzero(kind == dtx.SILENT).flatten().tolist()
+        y = c.step(rows, n_per, sid=sid, silent=silent)
+        y0 = c0.step(rows, n_per, hold=sid + silent)
+        hrow = kind.clone()
+        hrow[kind == dtx.SPEECH] = 0
+        st, _, restore, noise = dtx.cng_model(st, rows, hrow, None, cfg.order, 1)
+        cn = restore.bool()
+        ya, y0a = y.cpu().view(B, -1), y0.cpu().view(B, -1)
+        assert torch.equal(ya[~cn], y0a[~cn]) and torch.equal(ya[cn], noise[cn]), f"hop {h}: receiver wav"
+        assert all(torch.equal(a, b) for a, b in zip(c.cache_dec, c0.cache_dec)), f"hop {h}: receiver caches"
+        assert torch.equal(c.cng_state.cpu(), st)
+    assert counts[dtx.SID] > 0 and counts[dtx.SILENT] > 0 and counts[dtx.SPEECH] > 0
+
+
+def test_dtx_checks(speech):
+    from hilcodec_amd.graph_step import GraphedDecodeHop, GraphedEncodeHop
+    with pytest.raises(ValueError, match="order must be <= 9"):
+        GraphedEncodeHop(speech, 2, HOP, 8, DEV, dtx=dtx.DtxConfig(order=10))
+    with pytest.raises(ValueError, match="multiple of 320"):
+        GraphedEncodeHop(speech, 2, 160, 8, DEV, dtx=dtx.DtxConfig(order=2))
+    with pytest.raises(ValueError, match="order must be <= 9"):
+        GraphedDecodeHop(speech, 2, 1, 8, DEV, sessions=True, cng_order=10)
+    with pytest.raises(ValueError, match="sessions"):
+        GraphedDecodeHop(speech, 2, 1, 8, DEV, cng_order=8)
+    plain = GraphedDecodeHop(speech, 2, 1, 8, DEV, sessions=True)
+    pk = torch.zeros(2, plain.stride, dtype=torch.uint8)
+    with pytest.raises(RuntimeError, match="cng_order"):
+        plain.step(pk, [8, 8], sid=[0])
+    with pytest.raises(RuntimeError, match="cng_order"):
+        plain.step(pk, [8, 8], silent=[1])
