@@ -79,6 +79,8 @@ SIGNATURES = {
     "hilc_fec_select": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     "hilc_dtx_encode": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _d, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "hilc_cng_synth": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "hilc_packet_header": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "hilc_jitter_step": [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
 }
 
 ABI_VERSION = 16

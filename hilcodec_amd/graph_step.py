@@ -18,11 +18,13 @@ from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 from torch import Tensor
 
 from . import dtx as dtx_def
 from . import engine, ops, wire
+from .jitter import JitterConfig
 from .resample import BASE_RATE, design, device_taps, hop_samples
 
 
@@ -721,15 +723,26 @@ class GraphedEncodeHop(GraphedHop):
     dtx.HELD / SPEECH / SID / SILENT.  SPEECH rows are what the sender without DTX sends; a SID row holds `dtx.pack_sid(L, q)` then
     zeros with nbytes 1 + order, a SILENT row is zero with nbytes 0, and both have `.indices` -1 (with FEC, the next speech hop is a
     plain packet).  A held slot keeps its run; `start` clears it; `export` and a resume carry no DTX state.  `dtx=None` captures
-    exactly the graph without DTX."""
+    exactly the graph without DTX.
+    `header=True` (`hop` a multiple of 320): every packet carries the 3-byte transport header of `wire.pack_transport` — the slot's hop
+    index (the hops its encoder advanced since its last start, mod 2^16), the SID and FEC flags and n — so rows are uint8 `[B,
+    wire.transport_bytes(n, m, T)]` and byte counts include the header (0: nothing to send).  One hilc_packet_header runs last, on a
+    ping-pong pair of int32 counter rows indexed by parity.  A start or a resume restarts a slot's counter at 0 (that hop's packet
+    carries h = 0); a held or stopped slot sends nothing and keeps it; a DTX SILENT hop sends nothing but advances it.  `.hop_index`
+    (int32 `[B]` device view) is each slot's counter for the next hop; `export` and a resume carry none.  `header=False` captures
+    exactly the graph without the header."""
 
     side = "enc"
 
     def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, input_rate: int = BASE_RATE, fec_stages: int = 0,
-                 dtx: Optional[dtx_def.DtxConfig] = None):
+                 dtx: Optional[dtx_def.DtxConfig] = None, header: bool = False):
         self.model, self.n, self.device = model, n, device
         self.fec_stages = _fec_stages(fec_stages, n)
+        self.header = bool(header)
+        if self.header and hop % 320:
+            raise ValueError(f"GraphedEncodeHop(header=True): hop must be a multiple of 320, got {hop}")
+        self.frames = hop // 320
         if dtx is not None and not isinstance(dtx, dtx_def.DtxConfig):
             raise ValueError(f"dtx must be a dtx.DtxConfig or None, got {dtx!r}")
         self.dtx = dtx
@@ -766,6 +779,10 @@ class GraphedEncodeHop(GraphedHop):
             # per slot: the DTX run counter (updated in place by hilc_dtx_encode once per hop)
             self._run = torch.zeros(batch, dtype=torch.int32, device=device)
             self._level_thr = torch.from_numpy(dtx_def.level_table()).to(device)
+        self._ctr = None
+        if self.header:
+            # per parity, per slot: the hop counter (the hop of parity p reads row p and writes row p ^ 1)
+            self._ctr = torch.zeros(2, batch, dtype=torch.int32, device=device)
         self.spec_side = [torch.cuda.Stream(device)]
         self.chain = [None]
         self.sched = [ops.SchedWorkspace(device)]
@@ -804,6 +821,10 @@ class GraphedEncodeHop(GraphedHop):
                                   self._prev[p ^ 1] if self.fec_stages else None)
         if self.sessions:
             ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self.hold, indices=idx, packets=packets, nbytes=nbytes)
+        if self.header:
+            packets, nbytes = ops.packet_header(packets, nbytes, self._ctr[p], self._ctr[p ^ 1], self.n, self.fec_stages, self.frames,
+                                                n_clip, kind, self.action if self.sessions else None,
+                                                self.hold if self.sessions else None)
         return (idx, packets, nbytes) if kind is None else (idx, packets, nbytes, kind)
 
     def _zero(self) -> None:
@@ -812,15 +833,28 @@ class GraphedEncodeHop(GraphedHop):
             self._prev.zero_()
         if self._run is not None:
             self._run.zero_()
+        if self._ctr is not None:
+            self._ctr.zero_()
 
     def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
-        """as GraphedHop.reset; with FEC, no stream has a previous hop afterwards; with DTX, every run counter is 0"""
+        """as GraphedHop.reset; with FEC, no stream has a previous hop afterwards; with DTX, every run counter is 0; with the header,
+        every hop counter is 0"""
         super().reset(cache_enc, cache_dec)
         with torch.no_grad():
             if self._prev is not None:
                 self._prev.zero_()
             if self._run is not None:
                 self._run.zero_()
+            if self._ctr is not None:
+                self._ctr.zero_()
+
+    @property
+    def hop_index(self) -> Tensor:
+        """int32 `[B]` device view: each slot's hop counter, the h its next sent packet carries unless a start intervenes (header=True
+        only).  Read-only: written by the graph."""
+        if self._ctr is None:
+            raise RuntimeError("GraphedEncodeHop.hop_index: construct with header=True")
+        return self._ctr[self.parity]
 
     def step(self, x: Tensor, hold=None) -> Tuple[Tensor, Tensor]:
         out = super().step(x, hold)
@@ -882,11 +916,22 @@ class GraphedDecodeHop:
     Graph: the host marks `sid` / `silent` slots 2 / 3 in the hold row (so every existing kernel treats them as held); one
     hilc_cng_synth writes the noise — after the final hilc_state_slots_hold without `output_rate`; with it, before the resampler,
     followed by one hilc_state_slots_hold over the decoder caches (not the resampler history) of the slots that produced noise.
-    `cng_order=None` captures exactly the graph without comfort noise."""
+    `cng_order=None` captures exactly the graph without comfort noise.
+    `jitter` = jitter.JitterConfig(depth=D, capacity=C) (needs `sessions`; `frames` must equal the sender's T): a device-side jitter
+    buffer for packets with the transport header of GraphedEncodeHop(header=True).  `play(slots, packets, nbytes, hold=None)` takes
+    this hop's arrivals in push order — `slots` and `nbytes` A host ints, `packets` uint8 `[A, wire.transport_bytes(n, m, frames)]` on
+    the host or the device, 0 <= A <= `max_arrivals` (default 2 B) — and the graph's first launch, hilc_jitter_step, keeps them in a
+    per-slot ring of C entries and decides what each slot plays (jitter.py): its packet D hops after the first one arrived, a SID or
+    DTX silence as comfort noise, a gap from the next packet's redundant section, concealed (`conceal`) or held.  It writes the n,
+    lost and fec rows and the packet matrix that `step` uploads, so the rest of the graph is unchanged and the output is a pure
+    function of the arrival trace.  Host holds and stops pause a slot's playout (its arrivals are still buffered); `start` clears
+    its jitter state; `export` and a resume carry none; `jitter_state` is the int32 `[B, jitter.ST_WORDS]` state rows.  With `jitter`,
+    `step` raises RuntimeError; without it, `play` does.  `jitter=None` captures exactly the graph without the jitter buffer."""
 
     def __init__(self, model, batch: int, frames: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, conceal: bool = False, fade_hops: int = 4, output_rate: int = BASE_RATE,
-                 fec_stages: int = 0, cng_order: Optional[int] = None):
+                 fec_stages: int = 0, cng_order: Optional[int] = None, jitter: Optional[JitterConfig] = None,
+                 max_arrivals: Optional[int] = None):
         self.model, self.batch, self.frames, self.n, self.device = model, int(batch), int(frames), int(n), device
         self.output_rate = int(output_rate)
         self.rs, history = None, 0
@@ -915,29 +960,39 @@ class GraphedDecodeHop:
                 raise ValueError("GraphedDecodeHop(cng_order=...) needs sessions=True")
             self.cng_order = int(cng_order)
             dtx_def.check_order(self.cng_order, wire.packet_bytes(self.n, self.frames), "GraphedDecodeHop(cng_order=...)")
+        if jitter is not None and not isinstance(jitter, JitterConfig):
+            raise ValueError(f"jitter must be a jitter.JitterConfig or None, got {jitter!r}")
+        if jitter is not None and not self.sessions:
+            raise ValueError("GraphedDecodeHop(jitter=...) needs sessions=True")
+        self.jitter = jitter
         self.stride = wire.packet_bytes(self.n + self.fec_stages, self.frames)
         self.state = (StateBlock(model, batch, device, "dec", history), StateBlock(model, batch, device, "dec", history))
         self.parity = 0
         layout = self.state[0].layout
         loads = int(max_loads_per_hop) if self.sessions else 0
         B = self.batch
+        if jitter is not None:
+            self._init_jitter(jitter, 2 * B if max_arrivals is None else max_arrivals, loads, layout)
+        elif max_arrivals is not None:
+            raise ValueError("GraphedDecodeHop(max_arrivals=...) needs jitter=JitterConfig(...)")
         # ONE device buffer, captured by address: ctl[0] = action per slot, ctl[1] = n per slot, ctl[2] = 1 where the slot is
         # held, (conceal) ctl[3] = 1 where its packet was lost, (fec) the next row = 1 where it is decoded from the next packet's
         # redundant section, the packets, the staged records
-        rows = 3 + self.conceal + (self.fec_stages > 0)
-        self._n_ctl = rows * B
-        self._rec_off = self._n_ctl + (B * self.stride + 3) // 4
-        self._stage = torch.zeros(self._rec_off + loads * layout.record_len, device=device)
-        self._h_stage = torch.zeros(self._stage.numel()).pin_memory()
-        ctl = self._stage[:self._n_ctl].view(torch.int32).view(rows, B)
-        self.action, self.n_slot, self.hold = ctl[0], ctl[1], ctl[2]
-        self.lost = ctl[3] if self.conceal else None
-        self.fec = ctl[rows - 1] if self.fec_stages else None
-        self.packets = self._stage[self._n_ctl:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
-        self.records = self._stage[self._rec_off:].view(loads, layout.record_len)
-        self._h_ctl = self._h_stage[:self._n_ctl].view(torch.int32).view(rows, B)
-        self._h_packets = self._h_stage[self._n_ctl:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
-        self._h_rec = self._h_stage[self._rec_off:].view(loads, layout.record_len)
+        if jitter is None:
+            rows = 3 + self.conceal + (self.fec_stages > 0)
+            self._n_ctl = rows * B
+            self._rec_off = self._n_ctl + (B * self.stride + 3) // 4
+            self._stage = torch.zeros(self._rec_off + loads * layout.record_len, device=device)
+            self._h_stage = torch.zeros(self._stage.numel()).pin_memory()
+            ctl = self._stage[:self._n_ctl].view(torch.int32).view(rows, B)
+            self.action, self.n_slot, self.hold = ctl[0], ctl[1], ctl[2]
+            self.lost = ctl[3] if self.conceal else None
+            self.fec = ctl[rows - 1] if self.fec_stages else None
+            self.packets = self._stage[self._n_ctl:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
+            self.records = self._stage[self._rec_off:].view(loads, layout.record_len)
+            self._h_ctl = self._h_stage[:self._n_ctl].view(torch.int32).view(rows, B)
+            self._h_packets = self._h_stage[self._n_ctl:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
+            self._h_rec = self._h_stage[self._rec_off:].view(loads, layout.record_len)
         self.n_slot.fill_(self.n)
         if self.sessions:
             self.queue = SessionQueue(B, self.n, loads, layout, one_sided=True)
@@ -994,10 +1049,17 @@ class GraphedDecodeHop:
         if self.cng_order is not None:
             self._cn.zero_()
             self._restore.zero_()
+        if self.jitter is not None:
+            self._jstate.zero_()
+            self._jmeta.zero_()
+            self._jring.zero_()
 
     def _hop(self, p: int) -> Tensor:
         m = self.model
         src, dst = self.state[p], self.state[p ^ 1]
+        if self.jitter is not None:
+            ops.jitter_step(self.arrivals, self.offsets, self.hold, self.n_slot, self.packets, self._jstate, self._jmeta, self._jring,
+                            self.n, self.fec_stages, self.frames, self.cng_order, self.jitter.depth, self.action, self.lost, self.fec)
         if self.sessions:
             ops.state_slots_apply(src.buffer, src.layout, self.action, self.records)
         packets = self.packets
@@ -1052,6 +1114,8 @@ class GraphedDecodeHop:
         n_per_stream entries are not read or checked.  `fec`: slots (host ints) whose packet for this hop was lost but whose next
         packet is in their row (fec_stages >= 1 only): decoded from its redundant section.  `sid` / `silent`: slots (host ints) whose
         row holds a SID / that received nothing because their stream is in DTX (cng_order only): comfort noise"""
+        if self.jitter is not None:
+            raise RuntimeError("GraphedDecodeHop.step: a receiver with jitter=... takes play(slots, packets, nbytes)")
         held = SessionQueue.host_slots(hold)
         if held:
             if not self.sessions:
@@ -1120,9 +1184,115 @@ class GraphedDecodeHop:
         self.parity ^= 1
         return out
 
+    # ---------------------------------------------------------------- jitter buffer
+    def _init_jitter(self, cfg: JitterConfig, max_arrivals, loads: int, layout: ops.StateLayout) -> None:
+        if isinstance(max_arrivals, bool) or int(max_arrivals) != max_arrivals or max_arrivals < 1:
+            raise ValueError(f"max_arrivals must be an int >= 1, got {max_arrivals!r}")
+        B, dev = self.batch, self.device
+        self.max_arrivals = int(max_arrivals)
+        self.tstride = wire.transport_bytes(self.n, self.fec_stages, self.frames)
+        aw = 1 + (self.tstride + 3) // 4                   # an arrival record: byte count, then the headed packet
+        # ONE device buffer, captured by address, uploaded up to the last arrival used: ctl[0] = action per slot, ctl[1] = the host's
+        # holds (hilc_jitter_step adds its own), the CSR offsets of the arrivals [B + 1], the arrival records grouped by slot, the staged
+        # records.  The n, lost and fec rows and the packet matrix are written by hilc_jitter_step and are never uploaded.
+        self._n_ctl = 3 * B + 1
+        self._rec_off = self._n_ctl + self.max_arrivals * aw
+        self._stage = torch.zeros(self._rec_off + loads * layout.record_len, device=dev)
+        self._h_stage = torch.zeros(self._stage.numel()).pin_memory()
+        ctl = self._stage[:2 * B].view(torch.int32).view(2, B)
+        self.action, self.hold = ctl[0], ctl[1]
+        self.offsets = self._stage[2 * B:self._n_ctl].view(torch.int32)
+        self.arrivals = self._stage[self._n_ctl:self._rec_off].view(torch.int32).view(self.max_arrivals, aw)
+        self.records = self._stage[self._rec_off:].view(loads, layout.record_len)
+        self._h_ctl = self._h_stage[:2 * B].view(torch.int32).view(2, B)
+        self._h_offsets = self._h_stage[2 * B:self._n_ctl].view(torch.int32)
+        self._h_arrivals = self._h_stage[self._n_ctl:self._rec_off].view(torch.int32).view(self.max_arrivals, aw)
+        self._h_rec = self._h_stage[self._rec_off:].view(loads, layout.record_len)
+        rows = torch.zeros(3, B, dtype=torch.int32, device=dev)
+        self.n_slot = rows[0]
+        self.lost = rows[1] if self.conceal else None
+        self.fec = rows[2] if self.fec_stages else None
+        self.packets = torch.zeros(B, self.stride, dtype=torch.uint8, device=dev)
+        # per slot: the state row (jitter.ST_*, updated in place once per hop), the ring's meta words and bodies
+        self._jstate = torch.zeros(B, 14, dtype=torch.int32, device=dev)
+        self._jmeta = torch.zeros(B, cfg.capacity, dtype=torch.int32, device=dev)
+        self._jring = torch.zeros(B, cfg.capacity, (self.stride + 3) // 4, dtype=torch.int32, device=dev)
+
+    @property
+    def jitter_state(self) -> Tensor:
+        """int32 `[B, jitter.ST_WORDS]` device view: each slot's jitter state row after the last play (jitter.ST_* / STAT_*).
+        Read-only: written by the graph."""
+        if self.jitter is None:
+            raise RuntimeError("GraphedDecodeHop.jitter_state: construct with jitter=JitterConfig(...)")
+        return self._jstate
+
+    def play(self, slots, packets: Tensor, nbytes, hold=None) -> Tensor:
+        """one hop of a jitter receiver: this hop's arrivals, in push order — `slots` and `nbytes` (A host ints), `packets` uint8
+        `[A, wire.transport_bytes(n, m, frames)]` (host or device) — and `hold`: slots (host ints) held on this hop (playout
+        pauses).  Returns the hop's waveform, a static view that the next-but-one call overwrites."""
+        if self.jitter is None:
+            raise RuntimeError("GraphedDecodeHop.play: construct with jitter=JitterConfig(...)")
+        held = {self.queue.slot(s) for s in SessionQueue.host_slots(hold)} | self.queue.stops
+        for name, v in (("slots", slots), ("nbytes", nbytes)):
+            if isinstance(v, Tensor) and v.is_cuda:
+                raise ValueError(f"play: {name} must be host ints, not a device tensor")
+        sl = np.asarray(slots.tolist() if isinstance(slots, Tensor) else slots, dtype=np.int64).reshape(-1)
+        nb = np.asarray(nbytes.tolist() if isinstance(nbytes, Tensor) else nbytes, dtype=np.int64).reshape(-1)
+        A, B = len(sl), self.batch
+        if A > self.max_arrivals:
+            raise ValueError(f"play: {A} arrivals, at most max_arrivals = {self.max_arrivals}")
+        if len(nb) != A:
+            raise ValueError(f"play: {A} slots but {len(nb)} byte counts")
+        if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or tuple(packets.shape) != (A, self.tstride):
+            raise ValueError(f"play: packets must be uint8 [{A}, {self.tstride}]")
+        if A and (sl.min() < 0 or sl.max() >= B):
+            raise IndexError(f"play: a slot outside [0, {B})")
+        order = np.argsort(sl, kind="stable")
+        self._uploaded.synchronize()          # the previous upload's copy has left the pinned buffer
+        h = self._h_ctl
+        h[0].zero_()
+        _mark(h[1], held)
+        offs = self._h_offsets.numpy()
+        offs[0] = 0
+        offs[1:] = np.cumsum(np.bincount(sl, minlength=B))
+        if A:
+            self._h_arrivals[:A, 0].copy_(torch.from_numpy(np.clip(nb[order], -1, 1 << 20).astype(np.int32)))
+        q = self.queue
+        host = [(s, r) for s, r in q.starts.items() if r is not None and not r.is_cuda]
+        dev = [(s, r) for s, r in q.starts.items() if r is not None and r.is_cuda]
+        for slot, rec in q.starts.items():
+            if rec is None:
+                h[0, slot] = -1
+        for r, (slot, rec) in enumerate(host + dev):
+            h[0, slot] = r + 1
+            if r < len(host):
+                self._h_rec[r].copy_(rec)
+        q.clear()
+        stream = torch.cuda.current_stream(self.device)
+        bytes_of = lambda t: t.view(torch.uint8)[:, 4:4 + self.tstride]
+        used = self._n_ctl + A * self.arrivals.shape[1]
+        if A and not packets.is_cuda:
+            bytes_of(self._h_arrivals[:A]).copy_(packets[torch.from_numpy(order)])
+        self._stage[:used].copy_(self._h_stage[:used], non_blocking=True)
+        if A and packets.is_cuda:
+            rows = packets if np.array_equal(order, np.arange(A)) else packets[torch.from_numpy(order).to(self.device)]
+            bytes_of(self.arrivals[:A]).copy_(rows)
+        if host:
+            end = self._rec_off + len(host) * self.records.shape[1]
+            self._stage[self._rec_off:end].copy_(self._h_stage[self._rec_off:end], non_blocking=True)
+        for r, (_slot, rec) in enumerate(dev, start=len(host)):
+            rec.record_stream(stream)
+            self.records[r].copy_(rec, non_blocking=True)
+        self._uploaded.record(stream)
+        self.graphs[self.parity].replay()
+        out = self.outs[self.parity]
+        self.parity ^= 1
+        return out
+
     def start(self, slot: int, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
         """At the next step, slot `slot` begins a fresh stream (zero caches) or resumes one from its 30 decoder caches (B = 1
-        tensors, host or device; 31 with `output_rate`, the resampler's history last); at most `max_loads_per_hop` resumes per hop"""
+        tensors, host or device; 31 with `output_rate`, the resampler's history last); at most `max_loads_per_hop` resumes per hop.
+        With `jitter`, its jitter state is cleared on that hop"""
         if not self.sessions:
             raise RuntimeError("GraphedDecodeHop.start: construct with sessions=True")
         self.queue.start(slot, None, cache_dec)

@@ -1033,6 +1033,58 @@ def _cng_synth(packets, action, hold, state, wav, restore, gains, order):
 _register("cng_synth", "(Tensor packets, Tensor? action, Tensor(a!) hold, Tensor(b!) state, Tensor(c!) wav, Tensor(d!)? restore, "
           "Tensor gains, int order) -> ()", _cng_synth, lambda packets, action, hold, state, wav, restore, gains, order: None)
 
+# ======================================================================================================
+# transport header of the sender and jitter buffer of the receiver (graph_step.GraphedEncodeHop(header=True),
+# GraphedDecodeHop(jitter=); format: wire.pack_transport; definition: hilcodec_amd/jitter.py; semantics: include/hilcodec_amd.h)
+# ======================================================================================================
+def _packet_header(packets, nbytes, n_clip, kind, action, hold, ctr_in, ctr_out, n, m, frames):
+    B = packets.shape[0]
+    if packets.dim() != 2 or packets.shape[1] != _packet_stride(n + m, frames) or nbytes.numel() != B:
+        raise RuntimeError(f"packet_header: packets must be [B, {_packet_stride(n + m, frames)}] and nbytes [B]")
+    if ctr_in.numel() != B or ctr_out.numel() != B:
+        raise RuntimeError(f"packet_header: the counter rows need {B} entries")
+    for name, row in (("n_clip", n_clip), ("kind", kind), ("action", action), ("hold", hold)):
+        if row is not None and row.numel() != B:
+            raise RuntimeError(f"packet_header: {name} needs {B} entries")
+    out = _new(packets, B, 3 + packets.shape[1], dtype=torch.uint8)
+    out_nbytes = _new(packets, B, dtype=torch.int32)
+    check(lib.hilc_packet_header(_ptr(packets, torch.uint8), _ptr(nbytes, torch.int32), _ptr(n_clip, torch.int32), _ptr(kind, torch.int32),
+                                 _ptr(action, torch.int32), _ptr(hold, torch.int32), _ptr(ctr_in, torch.int32), _ptr(ctr_out, torch.int32),
+                                 _ptr(out, torch.uint8), _ptr(out_nbytes, torch.int32), B, frames, n, m, _stream()), "hilc_packet_header")
+    return out, out_nbytes
+
+
+_register("packet_header", "(Tensor packets, Tensor nbytes, Tensor? n_clip, Tensor? kind, Tensor? action, Tensor? hold, Tensor ctr_in, "
+          "Tensor(a!) ctr_out, int n, int m, int frames) -> (Tensor, Tensor)", _packet_header,
+          lambda packets, nbytes, n_clip, kind, action, hold, ctr_in, ctr_out, n, m, frames:
+          (packets.new_empty(packets.shape[0], 3 + packets.shape[1]), packets.new_empty(packets.shape[0], dtype=torch.int32)))
+
+
+def _jitter_step(arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, n, m, frames, order, depth):
+    B = hold.numel()
+    stride = _packet_stride(n + m, frames)
+    aw = (3 + stride + 3) // 4
+    if arrivals.dim() != 2 or arrivals.shape[1] != 1 + aw or offsets.numel() != B + 1:
+        raise RuntimeError(f"jitter_step: arrivals must be [A, {1 + aw}] and offsets [{B + 1}]")
+    if packets.shape != (B, stride) or state.shape != (B, 14) or meta.dim() != 2 or meta.shape[0] != B:
+        raise RuntimeError(f"jitter_step: packets must be [{B}, {stride}], state [{B}, 14], meta [{B}, C]")
+    C = meta.shape[1]
+    if ring.shape != (B, C, (stride + 3) // 4):
+        raise RuntimeError(f"jitter_step: ring must be [{B}, {C}, {(stride + 3) // 4}]")
+    for name, row in (("action", action), ("n_slot", n_slot), ("lost", lost), ("fec", fec)):
+        if row is not None and row.numel() != B:
+            raise RuntimeError(f"jitter_step: {name} needs {B} entries")
+    check(lib.hilc_jitter_step(_ptr(arrivals, torch.int32), _ptr(offsets, torch.int32), arrivals.shape[0], _ptr(action, torch.int32),
+                               _ptr(hold, torch.int32), _ptr(n_slot, torch.int32), _ptr(lost, torch.int32), _ptr(fec, torch.int32),
+                               _ptr(packets, torch.uint8), _ptr(state, torch.int32), _ptr(meta, torch.int32), _ptr(ring, torch.int32), B,
+                               frames, n, m, order, int(lost is not None), depth, C, _stream()), "hilc_jitter_step")
+
+
+_register("jitter_step", "(Tensor arrivals, Tensor offsets, Tensor? action, Tensor(a!) hold, Tensor(b!) n_slot, Tensor(c!)? lost, "
+          "Tensor(d!)? fec, Tensor(e!) packets, Tensor(f!) state, Tensor(g!) meta, Tensor(h!) ring, int n, int m, int frames, int order, "
+          "int depth) -> ()", _jitter_step,
+          lambda arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, n, m, frames, order, depth: None)
+
 _OPS = torch.ops.hilcodec
 
 
@@ -1632,6 +1684,30 @@ def cng_synth(packets: Tensor, hold: Tensor, state: Tensor, wav: Tensor, gains: 
     their `wav` row (fp32 contiguous `[B, 1, 320 T]`) overwritten, hold 0 and `restore` 1; a silent slot without a SID gets hold 1.
     `state`: int32 `[B, 3 + 2 order]` (dtx.state_words); `gains`: fp32 `[128]` (dtx.gain_table) on the device."""
     _OPS.cng_synth(packets, action, hold, state, wav, restore, gains, int(order))
+
+
+def packet_header(packets: Tensor, nbytes: Tensor, ctr_in: Tensor, ctr_out: Tensor, n: int, m: int, frames: int,
+                  n_clip: Optional[Tensor] = None, kind: Optional[Tensor] = None, action: Optional[Tensor] = None,
+                  hold: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """The headed sender's last step: packets uint8 `[B, wire.packet_bytes(n + m, frames)]` and nbytes int32 `[B]` -> (rows uint8
+    `[B, wire.transport_bytes(n, m, frames)]`, byte counts int32 `[B]`, 0 = nothing to send): each sent row is
+    `wire.pack_transport(c_b, packet, n_b, sid, fec)` with c_b the slot's hop counter from `ctr_in` (int32 `[B]`); `ctr_out` (distinct)
+    receives the next counters, in place.  `n_clip`, `kind` (dtx kinds), `action`, `hold`: optional int32 `[B]` session rows."""
+    if ctr_in is ctr_out:
+        raise RuntimeError("packet_header: ctr_in and ctr_out must be distinct buffers")
+    return _OPS.packet_header(packets, nbytes, n_clip, kind, action, hold, ctr_in, ctr_out, int(n), int(m), int(frames))
+
+
+def jitter_step(arrivals: Tensor, offsets: Tensor, hold: Tensor, n_slot: Tensor, packets: Tensor, state: Tensor, meta: Tensor,
+                ring: Tensor, n: int, m: int, frames: int, order: Optional[int], depth: int, action: Optional[Tensor] = None,
+                lost: Optional[Tensor] = None, fec: Optional[Tensor] = None) -> None:
+    """The jitter receiver's first step (jitter.JitterModel), in place: this hop's arrivals (int32 `[A, 1 + ceil((3 + stride) / 4)]`:
+    byte count, then the headed packet; grouped by slot, `offsets` int32 `[B + 1]`) go into each slot's ring (`meta` int32 `[B, C]`,
+    `ring` int32 `[B, C, ceil(stride / 4)]`) and state row (`state` int32 `[B, 14]`), and the slot's play decision is written to the
+    `hold` (in: the host's holds), `n_slot`, `lost` (conceal only), `fec` (m >= 1 only) rows and `packets` (uint8 `[B, stride]`),
+    stride = wire.packet_bytes(n + m, frames).  `order`: the comfort-noise order (None: a SID is malformed)."""
+    _OPS.jitter_step(arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, int(n), int(m), int(frames),
+                     -1 if order is None else int(order), int(depth))
 
 
 def resample_poly(x: Tensor, taps: Tensor, L: int, M: int, hist: Optional[Tensor] = None, hist_out: Optional[Tensor] = None) -> Tensor:

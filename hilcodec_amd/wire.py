@@ -144,6 +144,71 @@ def fec_present(nbytes: int, n: int, m: int, T: int) -> bool:
         return False
     raise ValueError(f"a {nbytes}-byte packet fits neither {n} nor {n} + {m} stages of {T} frames")
 
+
+# Transport header of the graphed sender / receiver (graph_step.GraphedEncodeHop(header=True), GraphedDecodeHop(jitter=...)): a sent
+# packet is 3 header bytes then its body.  Bytes 0-1: the hop index h mod 2^16, big-endian (the hops the sending slot's encoder
+# advanced since its last start, before this hop); byte 2: bit 7 SID, bit 6 a redundant (FEC) section is present, bit 5 zero, bits
+# 4..0 n (codes: 1..31; SID: 0).  The body is the packet_bytes(n, T) codes, the fec_packet_bytes(n, m, T) codes with bit 6, or a SID
+# of dtx.sid_bytes(K) bytes.  Headed packets are not re-framed: the receiver's frames are the sender's T.
+TRANSPORT_HEADER = 3
+_SID_BIT, _FEC_BIT, _RSV_BIT = 0x80, 0x40, 0x20
+
+
+def transport_bytes(n: int, m: int, T: int) -> int:
+    """the widest headed packet of a sender with n stages, m redundant ones and T frames (a SID always fits)"""
+    return TRANSPORT_HEADER + packet_bytes(int(n) + int(m), T)
+
+
+def pack_transport(hop: int, body: bytes, n: int, sid: bool = False, fec: bool = False) -> bytes:
+    """header (hop mod 2^16, SID / FEC flags, n) + body; ValueError for an n outside 1..31 (codes), a SID with n != 0 or with the
+    FEC flag"""
+    n = int(n)
+    if sid and (n != 0 or fec):
+        raise ValueError("pack_transport: a SID has n = 0 and no redundant section")
+    if not sid and not 1 <= n <= 31:
+        raise ValueError(f"pack_transport: n = {n} outside [1, 31]")
+    flags = (_SID_BIT if sid else 0) | (_FEC_BIT if fec else 0) | n
+    h = int(hop) & 0xFFFF
+    return bytes([h >> 8, h & 0xFF, flags]) + bytes(body)
+
+
+def parse_transport(packet, nbytes: int, T: int, n_max: int, m: int, K) -> Tuple[int, bool, bool, int, bytes]:
+    """(hop, sid, fec, n, body) of the first `nbytes` bytes of `packet`, for a receiver of n_max stages, m redundant ones (0: no
+    FEC) and comfort noise of order K (None: none).  ValueError for a malformed packet: shorter than the header, bit 5 set, a codes
+    packet with n = 0 or n > n_max, a SID without K or with n != 0, the FEC flag without m or with n < m, or a length that does not
+    match the header"""
+    from .dtx import sid_bytes
+    nbytes = int(nbytes)
+    data = bytes(packet[:max(nbytes, 0)])
+    if nbytes < TRANSPORT_HEADER or len(data) < nbytes:
+        raise ValueError(f"a {nbytes}-byte packet is shorter than its {TRANSPORT_HEADER}-byte header")
+    hop, flags = (data[0] << 8) | data[1], data[2]
+    sid, fec, n = bool(flags & _SID_BIT), bool(flags & _FEC_BIT), flags & 0x1F
+    if flags & _RSV_BIT:
+        raise ValueError("header bit 5 is set")
+    if fec and (int(m) < 1 or n < int(m)):
+        raise ValueError(f"a redundant section with n = {n}, m = {m}")
+    body = nbytes - TRANSPORT_HEADER
+    if sid:
+        if K is None:
+            raise ValueError("a SID without comfort noise")
+        if n != 0:
+            raise ValueError(f"a SID with n = {n}")
+        if body != sid_bytes(K):
+            raise ValueError(f"a {body}-byte SID body, order {K} needs {sid_bytes(K)}")
+    else:
+        if not 1 <= n <= int(n_max):
+            raise ValueError(f"n = {n} outside [1, {n_max}]")
+        if int(m) >= 1:
+            present = fec_present(body, n, m, T)           # ValueError: neither length
+        elif body == packet_bytes(n, T):
+            present = False
+        else:
+            raise ValueError(f"a {body}-byte body is not {n} stages of {T} frames")
+        if present != fec:
+            raise ValueError(f"a {body}-byte body disagrees with its header's FEC flag")
+    return hop, sid, fec, n, data[TRANSPORT_HEADER:nbytes]
+
 # ---------------------------------------------------------------- caches
 def save_cache_npz(path: str, caches: Sequence[Tensor], prefix: str) -> None:
     """prefix 'e_in' (encoder, 22 tensors) or 'd_in' (decoder, 30)."""

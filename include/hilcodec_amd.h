@@ -37,7 +37,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -550,6 +550,33 @@ int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run
                     int sid_interval, int n_max, int stride, int prev_words, void* stream);
 int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains,
                    int B, int T, int order, int stride, void* stream);
+
+/* ---- transport header and jitter buffer of the packet sender and receiver (additive under ABI 16) -------------------------------
+ * Two entry points added WITHOUT a version bump, as the packet, concealment, resampling, FEC and DTX entry points above.  Header
+ * (hilcodec_amd/wire.py, pack_transport): byte 0-1 the hop index h mod 2^16 big-endian, byte 2 = SID << 7 | FEC << 6 | n (bit 5 zero,
+ * n 1..31 for codes, 0 for a SID), then the body; stride = ceil(10 (n_max + m) T / 8), a headed row is 3 + stride bytes.  m in
+ * [0, n_max] (else HILC_ERR_RANGE), n_max <= 31 and n_max + m <= 32 (else HILC_ERR_UNSUPPORTED).
+ * hilc_packet_header: the sender's last launch.  packets uint8 [B][stride] and nbytes int32 [B] as the packer (and hilc_dtx_encode)
+ * left them; n_per_stream, kind (hilc_dtx_encode's), action, hold optional int32 [B] (NULL = n_max, speech, 0, 0); counter_in and
+ * counter_out distinct int32 [B] (the hop of parity p reads one, writes the other) -> out uint8 [B][3 + stride], out_nbytes int32 [B].
+ * Per stream b: c = action[b] != 0 ? 0 : counter_in[b] mod 2^16; hold[b] != 0: out[b] = 0, out_nbytes[b] = 0, counter_out[b] = c;
+ * else counter_out[b] = (c + 1) mod 2^16 and, when nbytes[b] > 0, out[b] = header(c, SID iff kind[b] == 2, FEC iff m >= 1 and
+ * nbytes[b] = ceil(10 (n_b + m) T / 8) with n_b = n_per_stream[b] clamped to [max(m, 1), n_max], n = 0 for a SID else n_b) then the
+ * nbytes[b] packet bytes, out_nbytes[b] = 3 + nbytes[b]; nbytes[b] == 0: out[b] = 0, out_nbytes[b] = 0.  One thread per output byte.
+ * hilc_jitter_step: the receiver's first launch; the rules, bit for bit, are hilcodec_amd/jitter.py (JitterModel).  arrivals int32
+ * [max_arrivals][1 + ceil((3 + stride) / 4)] (word 0 the byte count, then the headed packet), grouped by slot: slot b's arrivals are
+ * records offsets[b] .. offsets[b + 1] - 1 (int32 [B + 1], clamped to [0, max_arrivals]) in push order; action optional int32 [B];
+ * hold int32 [B] (in: the host's holds and stops; out: 0, or 1 held, 2 SID, 3 silent); n_per_stream, lost (conceal != 0 only), fec
+ * (m >= 1 only) int32 [B] and packets uint8 [B][stride] (out); state int32 [B][14], meta int32 [B][capacity] and ring int32
+ * [B][capacity][ceil(stride / 4)] (in place).  order = the receiver's comfort-noise order K, -1 for none (a SID needs 1 + K <=
+ * stride, else HILC_ERR_SHAPE; K > 16: HILC_ERR_RANGE); capacity a power of two in [2, 32], 0 <= depth <= capacity - 2 (else
+ * HILC_ERR_RANGE).  NULL pointers: HILC_ERR_NULL; B or T <= 0 or max_arrivals < 0: HILC_ERR_SHAPE.  One wave per slot. */
+int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action,
+                       const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max,
+                       int m, void* stream);
+int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream,
+                     int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order,
+                     int conceal, int depth, int capacity, void* stream);
 
 #ifdef __cplusplus
 }
