@@ -26,13 +26,7 @@ from . import dtx as dtx_def
 from . import engine, ops, wire
 from .jitter import JitterConfig
 from .resample import BASE_RATE, design, device_taps, hop_samples
-
-
-def _spectra_on(encoder, stream: Optional[torch.cuda.Stream]):
-    """while a hop is warmed up / captured on this thread: the STFT front halves of the un-fused SpecBlocks go to `stream`
-    (engine._early_spectra), a branch of the graph beside the first encoder stages.  Context-local (engine._SIDE_STREAM),
-    nothing is written into the model."""
-    return engine.spectra_side_stream(stream)
+from .sessions import SessionQueue, stage_layout, stage_starts
 
 
 def state_layout(model, batch: int, side: str = "both", history: int = 0) -> ops.StateLayout:
@@ -52,37 +46,24 @@ def state_layout(model, batch: int, side: str = "both", history: int = 0) -> ops
     return ops.StateLayout([(batch,) + sh for sh in shapes + shapes_dec], len(shapes))
 
 
-def _capture_pair(hop, zero, device: torch.device, warmup: int):
-    """warm `hop(0)` / `hop(1)` up on a side stream (builds every lazily cached table: folded weights, codebooks), zero the
-    state, then capture one graph per parity; returns (graphs, their static outputs)"""
-    side = torch.cuda.Stream(device)
-    side.wait_stream(torch.cuda.current_stream(device))
-    with torch.cuda.stream(side), torch.no_grad():
-        for _ in range(warmup):
-            hop(0)
-            hop(1)
-        zero()
-    torch.cuda.current_stream(device).wait_stream(side)
-    torch.cuda.synchronize(device)
-    graphs, outs = [], []
-    for p in (0, 1):
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g), torch.no_grad():
-            out = hop(p)
-        graphs.append(g)
-        outs.append(out)
-    zero()
-    return graphs, outs
+def _int_arg(name: str, value, lo: int, hi: Optional[int] = None) -> int:
+    """an argument that must be an int (not a bool) in [lo, hi], or >= lo without `hi`: ValueError otherwise"""
+    if isinstance(value, bool) or int(value) != value or value < lo or (hi is not None and value > hi):
+        raise ValueError(f"{name} must be an int {f'>= {lo}' if hi is None else f'in [{lo}, {hi}]'}, got {value!r}")
+    return int(value)
+
+
+def _whole_frames(who: str, hop: int) -> int:
+    """the frames of a hop of `hop` samples at 24 kHz, for an option `who` that works on whole 320-sample frames"""
+    if hop % 320:
+        raise ValueError(f"{who}: hop must be a multiple of 320, got {hop}")
+    return hop // 320
 
 
 def _fec_stages(fec_stages, n: int) -> int:
     """the `fec_stages` argument of the sender and the receiver checked: 0 (no FEC) or an int m in [1, n] with n + m <= 32 (the
     most stages one packet holds, as hilc_rvq_decode_packed)"""
-    if isinstance(fec_stages, bool) or int(fec_stages) != fec_stages:
-        raise ValueError(f"fec_stages must be an int, got {fec_stages!r}")
-    m = int(fec_stages)
-    if m != 0 and not 1 <= m <= int(n):
-        raise ValueError(f"fec_stages = {m} outside [1, n = {n}] (0: no FEC)")
+    m = _int_arg("fec_stages", fec_stages, 0, int(n))
     if int(n) + m > 32:
         raise ValueError(f"fec_stages = {m}: a packet holds at most 32 stages, n + m = {int(n) + m}")
     return m
@@ -93,148 +74,6 @@ def _mark(row: Tensor, slots) -> None:
     row.zero_()
     if slots:
         row[torch.tensor(sorted(slots), dtype=torch.long)] = 1
-
-
-class SessionQueue:
-    """Host side of GraphedHop's per-stream sessions: what the next hop does to which slot, checked here before anything is
-    launched (no device).  `starts[slot]` = None (fresh zeros) or the slot's record; `n[slot]` = its new number of quantiser
-    stages.  A later call for the same slot replaces an earlier one of the same hop; `start` without `n` resets the slot to
-    `n_max`, the graph's default.  `holds` = the slots held on the next hop only, `stops` = the slots held on every hop until
-    their next `start`; `held` = both (a held slot does not advance: GraphedHop.step(hold=...))."""
-
-    def __init__(self, batch: int, n_max: int, max_loads: int, layout: ops.StateLayout, one_sided: bool = False):
-        """`one_sided`: the layout holds one side's caches (state_layout(side="enc" / "dec")) and a record is that side's list
-        alone; otherwise both lists or neither"""
-        self.batch, self.n_max, self.max_loads, self.layout = int(batch), int(n_max), int(max_loads), layout
-        self.one_sided = bool(one_sided)
-        self.n_min = 1                        # the least n a start or a bitrate may ask for (GraphedEncodeHop(fec_stages=m): m)
-        self.starts = {}
-        self.n = {}
-        self.holds = set()
-        self.stops = set()
-
-    def slot(self, slot) -> int:
-        s = int(slot)
-        if not 0 <= s < self.batch:
-            raise IndexError(f"slot {slot} outside [0, {self.batch})")
-        return s
-
-    def check_n(self, n) -> int:
-        v = int(n)
-        if not self.n_min <= v <= self.n_max:
-            raise ValueError(f"n = {n} outside [{self.n_min}, {self.n_max}] (the graph's n is the maximum)")
-        return v
-
-    @property
-    def loads(self) -> int:
-        return sum(r is not None for r in self.starts.values())
-
-    @property
-    def pending(self) -> bool:
-        return bool(self.starts or self.n)
-
-    @property
-    def held(self) -> frozenset:
-        return frozenset(self.holds | self.stops)
-
-    @property
-    def stopped(self) -> Tuple[int, ...]:
-        return tuple(sorted(self.stops))
-
-    @staticmethod
-    def host_slots(hold) -> List[int]:
-        """`hold` (None or an iterable of host ints) -> a list; ValueError for a device tensor (no hidden device sync)"""
-        if hold is None:
-            return []
-        if isinstance(hold, Tensor):
-            if hold.device.type != "cpu":
-                raise ValueError("hold: host ints, not a device tensor")
-            hold = hold.reshape(-1).tolist()
-        return [int(s) for s in hold]
-
-    def hold(self, slots) -> None:
-        """the slots `slots` (host ints) do not advance on the next hop; every slot is checked before any is taken"""
-        held = [self.slot(s) for s in self.host_slots(slots)]
-        self.holds.update(held)
-
-    def stop(self, slot) -> None:
-        self.stops.add(self.slot(slot))
-
-    def lost_slots(self, lost, hold=()) -> List[int]:
-        """the receiver's `lost` (host ints) checked before anything is launched: every slot in range (IndexError), none also in
-        `hold` (this hop's checked holds) and none stopped (ValueError: a held slot's packet is not read at all, a stopped slot has
-        no stream to conceal)"""
-        slots = sorted({self.slot(s) for s in self.host_slots(lost)})
-        both = set(slots) & {int(s) for s in hold}
-        if both:
-            raise ValueError(f"lost: slots {sorted(both)} are also held on this hop")
-        stopped = set(slots) & self.stops
-        if stopped:
-            raise ValueError(f"lost: slots {sorted(stopped)} are stopped (start them first)")
-        return slots
-
-    def fec_slots(self, fec, hold=(), lost=()) -> List[int]:
-        """the receiver's `fec` (host ints) checked before anything is launched: every slot in range (IndexError), none also in
-        `hold` or `lost` (this hop's checked holds and losses) and none stopped (ValueError: a FEC slot is decoded from the next
-        packet's redundant section, so it is neither held nor concealed, and a stopped slot has no stream)"""
-        slots = sorted({self.slot(s) for s in self.host_slots(fec)})
-        both = set(slots) & {int(s) for s in hold}
-        if both:
-            raise ValueError(f"fec: slots {sorted(both)} are also held on this hop")
-        both = set(slots) & {int(s) for s in lost}
-        if both:
-            raise ValueError(f"fec: slots {sorted(both)} are also lost on this hop")
-        stopped = set(slots) & self.stops
-        if stopped:
-            raise ValueError(f"fec: slots {sorted(stopped)} are stopped (start them first)")
-        return slots
-
-    def cn_slots(self, sid, silent, hold=(), lost=(), fec=()) -> Tuple[List[int], List[int]]:
-        """the receiver's `sid` and `silent` (host ints) checked before anything is launched: every slot in range (IndexError), the two
-        disjoint, neither also in `hold`, `lost` or `fec` (this hop's checked holds, losses and FEC slots) and none stopped (ValueError: a
-        comfort-noise slot is neither decoded nor held by the caller, and a stopped slot has no stream)"""
-        a = sorted({self.slot(s) for s in self.host_slots(sid)})
-        b = sorted({self.slot(s) for s in self.host_slots(silent)})
-        both = set(a) & set(b)
-        if both:
-            raise ValueError(f"sid / silent: slots {sorted(both)} are in both")
-        for name, slots in (("sid", a), ("silent", b)):
-            for what, other in (("held", hold), ("lost", lost), ("decoded by FEC", fec)):
-                both = set(slots) & {int(s) for s in other}
-                if both:
-                    raise ValueError(f"{name}: slots {sorted(both)} are also {what} on this hop")
-            stopped = set(slots) & self.stops
-            if stopped:
-                raise ValueError(f"{name}: slots {sorted(stopped)} are stopped (start them first)")
-        return a, b
-
-    def start(self, slot, cache_enc=None, cache_dec=None, n=None) -> None:
-        s = self.slot(slot)
-        v = self.n_max if n is None else self.check_n(n)
-        rec = None
-        if cache_enc is not None or cache_dec is not None:
-            if not self.one_sided and (cache_enc is None or cache_dec is None):
-                raise ValueError("start: give both cache lists (encoder and decoder) or neither")
-            rec = self.layout.record([] if cache_enc is None else cache_enc, [] if cache_dec is None else cache_dec)
-            if self.starts.get(s) is None and self.loads >= self.max_loads:
-                raise RuntimeError(f"start: more than {self.max_loads} loads queued for one hop (max_loads_per_hop)")
-        self.starts[s] = rec
-        self.n[s] = v
-        self.stops.discard(s)
-
-    def set_bitrate(self, slot, n) -> None:
-        s = self.slot(slot)
-        self.n[s] = self.check_n(n)
-
-    def clear(self) -> None:
-        """after a hop's upload: drops that hop's starts, bitrates and holds (stops stay)"""
-        self.starts.clear()
-        self.n.clear()
-        self.holds.clear()
-
-    def reset(self) -> None:
-        self.clear()
-        self.stops.clear()
 
 
 class StateBlock:
@@ -270,99 +109,146 @@ class StateBlock:
         return self.buffer.numel() * 4
 
 
-class GraphedHop:
-    """model: `hilcodec_amd.models.hilcodec.streaming.HILCodec` (eval, reparameterisations removed).
-    `step(x)` consumes `[B,1,hop]` samples (copied into the static input) and returns (indices `[n,B,T]`, wav `[B,1,hop]`)
-    as views of static buffers that a later `step` overwrites (each parity has its own pair).
+class ControlStage:
+    """A hop's control data: ONE device buffer, captured by address, and its pinned host mirror, laid out as int32 rows per slot |
+    payload | staged records (sessions.stage_layout), so that what a hop needs goes up in one copy.  `row[name]` / `h_row[name]` are
+    the `[B]` int32 rows on the device / in the mirror, `payload` / `h_payload` and `records` / `h_records` the two regions.
+    A hop's upload is: `wait()`, write the mirror (`put_starts` for the queued starts), `send(words)`, `finish(...)`.
+    `sent_words` / `sent_record_words`: the words of the last upload's pinned copy / of its host records' own copy."""
 
-    `groups` > 1: the streams are split into that many contiguous groups, each with its own state blocks, and the graph
-    runs the groups' chains (encoder -> RVQ -> dequantiser -> decoder) side by side on separate HIP streams.  Streams are
-    independent, so this is the same arithmetic on the same data — outputs bit-identical to `groups=1`, NO added latency
-    (unlike PipelinedHop) — but every launch of a hop covers the chip only 1.3-4 times at 1024 streams, and two or more
-    independent chains fill each other's partly-filled last rounds.
-
-    `sessions=True`: every slot is an independent stream session.  `start(slot, ...)` begins a fresh stream (zero caches)
-    or resumes one from its 22 + 30 caches, `set_bitrate(slot, n)` changes its number of quantiser stages (`n` of the
-    constructor is the maximum and the default), `export(slot)` returns its current caches; each takes effect at the next
-    `step()`.  The graph then starts each group's chain with one hilc_state_slots_apply on the block the hop reads, and the
-    quantiser and dequantiser take their per-stream n from a device buffer (rows >= a stream's n of the indices hold -1).
-    Pending actions travel from pinned host buffers on the replay stream, only when something changed.
-    Held streams: `step(x, hold=slots)` leaves the slots `slots` (host ints) exactly as they are for that hop (caches
-    bit-identical afterwards, a `start` queued for the hop included; their `x` rows are not read for anything that matters; their
-    wav rows are 0 and indices -1); `stop(slot)` holds a slot on every step until its next `start`, `stopped` lists those slots.
-    Each group's chain ends with one hilc_state_slots_hold, which copies held streams back from the block the hop read.
-    `sessions=False` captures exactly the graph of earlier rounds."""
-
-    side = "both"                             # the caches a state block holds (GraphedEncodeHop: the encoder's only)
-
-    def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, groups: int = 1,
-                 sessions: bool = False, max_loads_per_hop: int = 4):
-        self.model, self.n = model, n
+    def __init__(self, batch: int, rows: Sequence[str], payload_words: int, loads: int, record_len: int, device: torch.device):
+        self.row_off, self.payload_off, self.rec_off, total = stage_layout(batch, rows, payload_words, loads, record_len)
         self.device = device
+        self.dev = torch.zeros(total, device=device)
+        self.host = torch.zeros(total).pin_memory()
+        self.row = {k: self.dev[o:o + batch].view(torch.int32) for k, o in self.row_off.items()}
+        self.h_row = {k: self.host[o:o + batch].view(torch.int32) for k, o in self.row_off.items()}
+        self.payload, self.h_payload = self.dev[self.payload_off:self.rec_off], self.host[self.payload_off:self.rec_off]
+        self.records, self.h_records = self.dev[self.rec_off:].view(loads, record_len), self.host[self.rec_off:].view(loads, record_len)
+        self.uploaded = torch.cuda.Event()
+        self.sent_words = self.sent_record_words = 0
+        self._n_host, self._dev_records = 0, []
+
+    def wait(self) -> None:
+        """before the mirror is written: the previous upload's copy has left the pinned buffer"""
+        self.uploaded.synchronize()
+
+    def put_starts(self, starts) -> int:
+        """the queued starts -> the mirror's action row and records (sessions.stage_starts); returns the number of host records"""
+        self.h_row["action"].zero_()
+        self._n_host, self._dev_records = stage_starts(starts, self.h_row["action"], self.h_records)
+        return self._n_host
+
+    def send(self, words: int) -> None:
+        """the first `words` words of the mirror -> the device, on the current stream"""
+        self.dev[:words].copy_(self.host[:words], non_blocking=True)
+        self.sent_words = words
+
+    def finish(self, host_records_apart: bool = False) -> None:
+        """after `send`: the host records in a copy of their own (`host_records_apart`: `send` stopped short of them), the device
+        records one by one behind them, and the event that `wait` waits for"""
+        stream = torch.cuda.current_stream(self.device)
+        n_host, rec_len = self._n_host, self.records.shape[1]
+        self.sent_record_words = n_host * rec_len if host_records_apart else 0
+        if self.sent_record_words:
+            end = self.rec_off + self.sent_record_words
+            self.dev[self.rec_off:end].copy_(self.host[self.rec_off:end], non_blocking=True)
+        for r, rec in enumerate(self._dev_records, start=n_host):
+            rec.record_stream(stream)
+            self.records[r].copy_(rec, non_blocking=True)
+        self._n_host, self._dev_records = 0, []
+        self.uploaded.record(stream)
+
+
+class _Hop:
+    """What the graphed hops share: the groups' bounds and ping-pong state blocks, `parity`, warm-up and capture, replay-and-flip,
+    the per-group concatenation of the caches, and the session front end (the queue is host-only and always exists; `sessions`
+    gates the public methods and the graph's session kernels)."""
+
+    _scratch: Sequence[Tensor] = ()           # per-slot device buffers beside the state blocks: cleared with them (_zero, _load)
+
+    def __init__(self, model, batch: int, n: int, device: torch.device, groups: int = 1, sessions: bool = False,
+                 max_loads_per_hop: int = 4):
+        self.model, self.n, self.device = model, n, device
         groups = max(1, min(int(groups), batch))
         self.bounds = [(batch * g // groups, batch * (g + 1) // groups) for g in range(groups)]
-        self.x = torch.zeros(batch, 1, hop, device=device)
         # per group: a ping-pong pair of state blocks (a cache tensor is [streams, C, pad]: a group's slice must be contiguous)
-        self.gstate = [(StateBlock(model, hi - lo, device), StateBlock(model, hi - lo, device)) for lo, hi in self.bounds]
+        self.gstate = [(self._block(hi - lo), self._block(hi - lo)) for lo, hi in self.bounds]
         self.parity = 0                       # the block holding the CURRENT caches (input of the next hop)
         self.sessions = bool(sessions)
+        if self.sessions and max_loads_per_hop < 1:
+            raise ValueError("max_loads_per_hop must be >= 1")
+        layout = self.gstate[0][0].layout
+        self.queue = SessionQueue(batch, n, int(max_loads_per_hop) if self.sessions else 0, layout,
+                                  one_sided=layout.n_enc in (0, len(layout.shapes)))
         if self.sessions:
-            self._init_sessions(batch, int(max_loads_per_hop))
-        # the STFT side branch (engine._early_spectra) only for a single chain: with several chains the launches of the other
-        # groups already fill the idle CUs, and a fork of a forked stream inside one capture crashes hipStreamEndCapture (ROCm 7.2)
-        self.spec_side = [torch.cuda.Stream(device) if groups == 1 else None for _ in self.bounds]
-        self.chain = [None] + [torch.cuda.Stream(device) for _ in self.bounds[1:]]      # group 0 runs on the capture stream
-        self.sched = [ops.SchedWorkspace(device) for _ in self.bounds]    # ticket words: one workspace per concurrent chain
-        self.graphs, self.outs = _capture_pair(self._hop, self._zero, device, warmup)
+            for a, b in self.gstate:          # the kernels' layout tables, built before the capture
+                a.layout.tables(device)
+                b.layout.tables(device)
+
+    def _block(self, streams: int) -> StateBlock:
+        """a state block of `streams` streams (the sender and the receiver: one side's caches only)"""
+        return StateBlock(self.model, streams, self.device)
+
+    def _new_stage(self, rows: Sequence[str], payload_words: int = 0) -> ControlStage:
+        """the control stage of a hop with these rows and payload, and the device views every session graph reads"""
+        q = self.queue
+        stage = ControlStage(q.batch, rows, payload_words, q.max_loads, q.layout.record_len, self.device)
+        self.action, self.hold, self.records = stage.row["action"], stage.row["hold"], stage.records
+        return stage
 
     @property
     def state(self):
         """(block A, block B) of a single-group schedule (the form tests and callers of earlier rounds use)"""
         if len(self.gstate) != 1:
-            raise RuntimeError("GraphedHop.state: the streams are split into groups — use .gstate[g]")
+            raise RuntimeError(f"{type(self).__name__}.state: the streams are split into groups — use .gstate[g]")
         return self.gstate[0]
 
     def _zero(self) -> None:
         for a, b in self.gstate:
             a.zero_()
             b.zero_()
+        for t in self._scratch:
+            t.zero_()
 
-    def _chain(self, g: int, p: int) -> Tuple[Tensor, Tensor]:
-        m = self.model
-        lo, hi = self.bounds[g]
-        src, dst = self.gstate[g][p], self.gstate[g][p ^ 1]
-        x = self.x[lo:hi]
-        if self.sessions:
-            # before the encoder: it forks the STFT side branch, which reads this block's waveform histories
-            ops.state_slots_apply(src.buffer, src.layout, self.action[lo:hi], self.records)
-        with ops.sched_workspace(self.sched[g]):
-            with _spectra_on(m.encoder, self.spec_side[g]):
-                z, _ = m.encoder(x, *src.enc, cache_out=dst.enc)
-            if self.sessions:
-                idx = m.quantizer(z, self.n, n_clip=self.n_slot[lo:hi])
-                q = m.dequantizer(idx, self.n, n_clip=self.n_slot[lo:hi])
-            else:
-                idx = m.quantizer(z, self.n)
-                q = m.dequantizer(idx, self.n)
-            wav, _ = m.decoder(q, *src.dec, cache_out=dst.dec)
-        if self.sessions:
-            # after the last write to dst and to this group's outputs
-            ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self.hold[lo:hi], wav=wav, indices=idx)
-        return idx, wav
+    def _load(self, cache_enc: Optional[Sequence[Tensor]], cache_dec: Optional[Sequence[Tensor]]) -> None:
+        """reset's state part: parity 0, block A zero or the given caches, the scratch buffers zero"""
+        self.parity = 0
+        for (lo, hi), (a, _b) in zip(self.bounds, self.gstate):
+            a.load_(None if cache_enc is None else [c[lo:hi] for c in cache_enc],
+                    None if cache_dec is None else [c[lo:hi] for c in cache_dec])
+        for t in self._scratch:
+            t.zero_()
 
-    def _hop(self, p: int) -> Tuple[Tensor, Tensor]:
-        if len(self.bounds) == 1:
-            return self._chain(0, p)
-        main = torch.cuda.current_stream(self.device)
-        outs = [None] * len(self.bounds)
-        for g in range(1, len(self.bounds)):              # fork
-            self.chain[g].wait_stream(main)
-            with torch.cuda.stream(self.chain[g]):
-                outs[g] = self._chain(g, p)
-        outs[0] = self._chain(0, p)
-        for g in range(1, len(self.bounds)):              # join
-            main.wait_stream(self.chain[g])
-        return torch.cat([o[0] for o in outs], dim=1), torch.cat([o[1] for o in outs], dim=0)
+    def _capture_pair(self, hop, warmup: int):
+        """warm `hop(0)` / `hop(1)` up on a side stream (builds every lazily cached table: folded weights, codebooks), zero the
+        state, then capture one graph per parity; returns (graphs, their static outputs)"""
+        device = self.device
+        side = torch.cuda.Stream(device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side), torch.no_grad():
+            for _ in range(warmup):
+                hop(0)
+                hop(1)
+            self._zero()
+        torch.cuda.current_stream(device).wait_stream(side)
+        torch.cuda.synchronize(device)
+        graphs, outs = [], []
+        for p in (0, 1):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g), torch.no_grad():
+                out = hop(p)
+            graphs.append(g)
+            outs.append(out)
+        self._zero()
+        return graphs, outs
+
+    def _replay(self):
+        """replay the current parity's graph and flip; returns that graph's static outputs"""
+        p = self.parity
+        self.graphs[p].replay()
+        self.parity ^= 1
+        return self.outs[p]
 
     def _current(self, which: str) -> List[Tensor]:
         per_group = [getattr(blocks[self.parity], which) for blocks in self.gstate]
@@ -370,108 +256,10 @@ class GraphedHop:
             return per_group[0]                                        # views of the state block itself
         return [torch.cat(cs, dim=0) for cs in zip(*per_group)]      # groups are contiguous stream ranges: copies, full batch
 
-    @property
-    def cache_enc(self) -> List[Tensor]:
-        """the CURRENT encoder caches of all streams, in the reference's order (`streaming.py:458-470`) — what
-        `wire.save_cache` / `reset(...)` take; with groups > 1 concatenated over the groups (copies)"""
-        return self._current("enc")
-
-    @property
-    def cache_dec(self) -> List[Tensor]:
-        return self._current("dec")
-
-    def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
-        """zero history, or resume from caches saved earlier (`wire.save_cache` / `e_in*`, `d_in*`); with sessions also drops
-        every queued action, clears every stop and puts every slot back to the default n"""
-        with torch.no_grad():
-            self.parity = 0
-            for (lo, hi), (a, _b) in zip(self.bounds, self.gstate):
-                a.load_(None if cache_enc is None else [c[lo:hi] for c in cache_enc],
-                        None if cache_dec is None else [c[lo:hi] for c in cache_dec])
-            if self.sessions:
-                self.queue.reset()
-                self._uploaded.synchronize()
-                self._h_ctl[0].zero_()
-                self._h_ctl[1].fill_(self.n)
-                self._h_ctl[2].zero_()
-                self._stage[:self._h_ctl.numel()].copy_(self._h_stage[:self._h_ctl.numel()], non_blocking=True)
-                self._uploaded.record()
-                self._action_live = False
-                self._held_live = frozenset()
-
-    def step(self, x: Tensor, hold=None) -> Tuple[Tensor, Tensor]:
-        """`hold`: slots (host ints) that do not advance on this hop (sessions=True only; None or empty: every slot advances)"""
-        held = self._hold_slots(hold)
-        self.x.copy_(x)
-        if self.sessions:
-            self.queue.hold(held)
-            self._upload()
-        self.graphs[self.parity].replay()
-        out = self.outs[self.parity]
-        self.parity ^= 1
-        return out
-
     # ---------------------------------------------------------------- sessions
-    def _init_sessions(self, batch: int, max_loads: int) -> None:
-        if max_loads < 1:
-            raise ValueError("max_loads_per_hop must be >= 1")
-        layout = self.gstate[0][0].layout
-        self.queue = SessionQueue(batch, self.n, max_loads, layout, one_sided=self.side != "both")
-        # device side, captured by address, ONE buffer so that a hop's upload is one copy: ctl[0] = action per slot (0 keep,
-        # -1 zero, r >= 1 load record r-1), ctl[1] = n per slot, ctl[2] = 1 where the slot is held, then the staged records
-        n_ctl = 3 * batch
-        self._stage = torch.zeros(n_ctl + max_loads * layout.record_len, device=self.device)
-        self._h_stage = torch.zeros(self._stage.numel()).pin_memory()    # its pinned host mirror
-        self.ctl = self._stage[:n_ctl].view(torch.int32).view(3, batch)
-        self.records = self._stage[n_ctl:].view(max_loads, layout.record_len)
-        self._h_ctl = self._h_stage[:n_ctl].view(torch.int32).view(3, batch)
-        self._h_rec = self._h_stage[n_ctl:].view(max_loads, layout.record_len)
-        self.ctl[1].fill_(self.n)
-        self._h_ctl[1].fill_(self.n)
-        self.action, self.n_slot, self.hold = self.ctl[0], self.ctl[1], self.ctl[2]
-        self._uploaded = torch.cuda.Event()
-        self._action_live = False             # the device action row holds the previous hop's actions
-        self._held_live = frozenset()         # the slots the device hold row marks
-        for a, b in self.gstate:              # the kernels' layout tables, built before the capture
-            a.layout.tables(self.device)
-            b.layout.tables(self.device)
-
-    def _upload(self) -> None:
-        """queued actions, bitrates and holds -> the graph's device buffers, on the replay stream (an action applies to exactly
-        one hop: the upload after a hop with actions clears them; the hold row goes up when it changes)"""
-        q = self.queue
-        held = q.held
-        if not q.pending and not self._action_live and held == self._held_live:
-            return
-        self._uploaded.synchronize()          # the previous upload's copy has left the pinned buffer
-        h = self._h_ctl
-        h[0].zero_()
-        stream = torch.cuda.current_stream(self.device)
-        host = [(s, r) for s, r in q.starts.items() if r is not None and not r.is_cuda]      # host records first: one copy
-        dev = [(s, r) for s, r in q.starts.items() if r is not None and r.is_cuda]
-        for slot, rec in q.starts.items():
-            if rec is None:
-                h[0, slot] = -1
-        for r, (slot, rec) in enumerate(host + dev):
-            h[0, slot] = r + 1
-            if r < len(host):
-                self._h_rec[r].copy_(rec)
-        for slot, n in q.n.items():
-            h[1, slot] = n
-        _mark(h[2], held)
-        used = h.numel() + len(host) * self.records.shape[1]
-        self._stage[:used].copy_(self._h_stage[:used], non_blocking=True)
-        for r, (_slot, rec) in enumerate(dev, start=len(host)):
-            rec.record_stream(stream)
-            self.records[r].copy_(rec, non_blocking=True)
-        self._uploaded.record(stream)
-        self._action_live = bool(q.starts)
-        self._held_live = held
-        q.clear()
-
     def _need_sessions(self, what: str) -> None:
         if not self.sessions:
-            raise RuntimeError(f"GraphedHop.{what}: construct with sessions=True")
+            raise RuntimeError(f"{type(self).__name__}.{what}: construct with sessions=True")
 
     def _hold_slots(self, hold) -> List[int]:
         """step's `hold` checked before anything is launched"""
@@ -495,11 +283,6 @@ class GraphedHop:
         self._need_sessions("start")
         self.queue.start(slot, cache_enc, cache_dec, n)
 
-    def set_bitrate(self, slot: int, n: int) -> None:
-        """from the next step on, slot `slot` uses the first `n` quantiser stages (1 <= n <= the graph's n)"""
-        self._need_sessions("set_bitrate")
-        self.queue.set_bitrate(slot, n)
-
     def stop(self, slot: int) -> None:
         """from the next step on, slot `slot` is held (does not advance) on every step until the next `start(slot, ...)`"""
         self._need_sessions("stop")
@@ -508,7 +291,7 @@ class GraphedHop:
     @property
     def stopped(self) -> Tuple[int, ...]:
         """the stopped slots, sorted"""
-        return self.queue.stopped if self.sessions else ()
+        return self.queue.stopped
 
     def export(self, slot: int) -> Tuple[List[Tensor], List[Tensor]]:
         """the current 22 + 30 caches of slot `slot` as B = 1 device tensors (one gather launch) — the state after the last
@@ -522,7 +305,147 @@ class GraphedHop:
         return blk.layout.split(rec[0])
 
 
-class PipelinedHop:
+class GraphedHop(_Hop):
+    """model: `hilcodec_amd.models.hilcodec.streaming.HILCodec` (eval, reparameterisations removed).
+    `step(x)` consumes `[B,1,hop]` samples (copied into the static input) and returns (indices `[n,B,T]`, wav `[B,1,hop]`)
+    as views of static buffers that a later `step` overwrites (each parity has its own pair).
+
+    `groups` > 1: the streams are split into that many contiguous groups, each with its own state blocks, and the graph
+    runs the groups' chains (encoder -> RVQ -> dequantiser -> decoder) side by side on separate HIP streams.  Streams are
+    independent, so this is the same arithmetic on the same data — outputs bit-identical to `groups=1`, NO added latency
+    (unlike PipelinedHop) — but every launch of a hop covers the chip only 1.3-4 times at 1024 streams, and two or more
+    independent chains fill each other's partly-filled last rounds.
+
+    `sessions=True`: every slot is an independent stream session.  `start(slot, ...)` begins a fresh stream (zero caches)
+    or resumes one from its 22 + 30 caches, `set_bitrate(slot, n)` changes its number of quantiser stages (`n` of the
+    constructor is the maximum and the default), `export(slot)` returns its current caches; each takes effect at the next
+    `step()`.  The graph then starts each group's chain with one hilc_state_slots_apply on the block the hop reads, and the
+    quantiser and dequantiser take their per-stream n from a device buffer (rows >= a stream's n of the indices hold -1).
+    Pending actions travel from pinned host buffers on the replay stream, only when something changed.
+    Held streams: `step(x, hold=slots)` leaves the slots `slots` (host ints) exactly as they are for that hop (caches
+    bit-identical afterwards, a `start` queued for the hop included; their `x` rows are not read for anything that matters; their
+    wav rows are 0 and indices -1); `stop(slot)` holds a slot on every step until its next `start`, `stopped` lists those slots.
+    Each group's chain ends with one hilc_state_slots_hold, which copies held streams back from the block the hop read.
+    `sessions=False` captures exactly the graph of earlier rounds."""
+
+    def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, groups: int = 1,
+                 sessions: bool = False, max_loads_per_hop: int = 4):
+        super().__init__(model, batch, n, device, groups, sessions, max_loads_per_hop)
+        self.x = torch.zeros(batch, 1, hop, device=device)
+        if self.sessions:
+            # ONE buffer so that a hop's upload is one copy: action per slot (0 keep, -1 zero, r >= 1 load record r-1), n per
+            # slot, 1 where the slot is held, then the staged records
+            self.stage = self._new_stage(("action", "n_slot", "hold"))
+            self.n_slot = self.stage.row["n_slot"]
+            self.n_slot.fill_(self.n)
+            self.stage.h_row["n_slot"].fill_(self.n)
+            self._action_live = False         # the device action row holds the previous hop's actions
+            self._held_live = frozenset()     # the slots the device hold row marks
+        # the STFT side branch (engine._early_spectra) only for a single chain: with several chains the launches of the other
+        # groups already fill the idle CUs, and a fork of a forked stream inside one capture crashes hipStreamEndCapture (ROCm 7.2)
+        self.spec_side = [torch.cuda.Stream(device) if len(self.bounds) == 1 else None for _ in self.bounds]
+        self.chain = [None] + [torch.cuda.Stream(device) for _ in self.bounds[1:]]      # group 0 runs on the capture stream
+        self.sched = [ops.SchedWorkspace(device) for _ in self.bounds]    # ticket words: one workspace per concurrent chain
+        self.graphs, self.outs = self._capture_pair(self._hop, warmup)
+
+    def _chain(self, g: int, p: int) -> Tuple[Tensor, Tensor]:
+        m = self.model
+        lo, hi = self.bounds[g]
+        src, dst = self.gstate[g][p], self.gstate[g][p ^ 1]
+        x = self.x[lo:hi]
+        n_clip = self.n_slot[lo:hi] if self.sessions else None
+        if self.sessions:
+            # before the encoder: it forks the STFT side branch, which reads this block's waveform histories
+            ops.state_slots_apply(src.buffer, src.layout, self.action[lo:hi], self.records)
+        with ops.sched_workspace(self.sched[g]):
+            # while this thread warms up or captures: the STFT front halves of the un-fused SpecBlocks go to the side stream
+            # (context-local, nothing is written into the model)
+            with engine.spectra_side_stream(self.spec_side[g]):
+                z, _ = m.encoder(x, *src.enc, cache_out=dst.enc)
+            idx = m.quantizer(z, self.n, n_clip=n_clip)
+            q = m.dequantizer(idx, self.n, n_clip=n_clip)
+            wav, _ = m.decoder(q, *src.dec, cache_out=dst.dec)
+        if self.sessions:
+            # after the last write to dst and to this group's outputs
+            ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self.hold[lo:hi], wav=wav, indices=idx)
+        return idx, wav
+
+    def _hop(self, p: int) -> Tuple[Tensor, Tensor]:
+        if len(self.bounds) == 1:
+            return self._chain(0, p)
+        main = torch.cuda.current_stream(self.device)
+        outs = [None] * len(self.bounds)
+        for g in range(1, len(self.bounds)):              # fork
+            self.chain[g].wait_stream(main)
+            with torch.cuda.stream(self.chain[g]):
+                outs[g] = self._chain(g, p)
+        outs[0] = self._chain(0, p)
+        for g in range(1, len(self.bounds)):              # join
+            main.wait_stream(self.chain[g])
+        return torch.cat([o[0] for o in outs], dim=1), torch.cat([o[1] for o in outs], dim=0)
+
+    @property
+    def cache_enc(self) -> List[Tensor]:
+        """the CURRENT encoder caches of all streams, in the reference's order (`streaming.py:458-470`) — what
+        `wire.save_cache` / `reset(...)` take; with groups > 1 concatenated over the groups (copies)"""
+        return self._current("enc")
+
+    @property
+    def cache_dec(self) -> List[Tensor]:
+        return self._current("dec")
+
+    def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
+        """zero history, or resume from caches saved earlier (`wire.save_cache` / `e_in*`, `d_in*`); with sessions also drops
+        every queued action, clears every stop and puts every slot back to the default n.  (GraphedEncodeHop: with FEC, no stream
+        has a previous hop afterwards; with DTX, every run counter is 0; with the header, every hop counter is 0)"""
+        with torch.no_grad():
+            self._load(cache_enc, cache_dec)
+            if self.sessions:
+                self.queue.reset()
+                st = self.stage
+                st.wait()
+                st.put_starts({})
+                st.h_row["n_slot"].fill_(self.n)
+                st.h_row["hold"].zero_()
+                st.send(st.rec_off)
+                st.finish()
+                self._action_live = False
+                self._held_live = frozenset()
+
+    def step(self, x: Tensor, hold=None) -> Tuple[Tensor, Tensor]:
+        """`hold`: slots (host ints) that do not advance on this hop (sessions=True only; None or empty: every slot advances)"""
+        held = self._hold_slots(hold)
+        self.x.copy_(x)
+        if self.sessions:
+            self.queue.hold(held)
+            self._upload()
+        return self._replay()
+
+    def _upload(self) -> None:
+        """queued actions, bitrates and holds -> the graph's device buffers, on the replay stream (an action applies to exactly
+        one hop: the upload after a hop with actions clears them; the hold row goes up when it changes)"""
+        q, st = self.queue, self.stage
+        held = q.held
+        if not q.pending and not self._action_live and held == self._held_live:
+            return
+        st.wait()
+        n_host = st.put_starts(q.starts)      # host records first: they go up in the one copy
+        for slot, n in q.n.items():
+            st.h_row["n_slot"][slot] = n
+        _mark(st.h_row["hold"], held)
+        st.send(st.rec_off + n_host * st.records.shape[1])
+        st.finish()
+        self._action_live = bool(q.starts)
+        self._held_live = held
+        q.clear()
+
+    def set_bitrate(self, slot: int, n: int) -> None:
+        """from the next step on, slot `slot` uses the first `n` quantiser stages (1 <= n <= the graph's n)"""
+        self._need_sessions("set_bitrate")
+        self.queue.set_bitrate(slot, n)
+
+
+class PipelinedHop(_Hop):
     """Throughput schedule for a node that runs BOTH halves of the codec on the same streams (transcoding, evaluation,
     the benchmark): a two-stage software pipeline over hops.  One graph replay runs, side by side on two HIP streams,
     the encoder + RVQ of hop i and the dequantiser + decoder of hop i-1 — two independent chains (the only edge between
@@ -546,57 +469,28 @@ class PipelinedHop:
         if sessions:
             raise NotImplementedError("PipelinedHop(sessions=True): per-stream sessions exist on GraphedHop only (the encoder and "
                                       "decoder halves of a block flip on opposite parities here)")
-        self.model, self.n, self.device = model, n, device
-        groups = max(1, min(int(groups), batch))
-        self.bounds = [(batch * g // groups, batch * (g + 1) // groups) for g in range(groups)]
+        super().__init__(model, batch, n, device, groups)
         self.x = torch.zeros(batch, 1, hop, device=device)
-        self.gstate = [(StateBlock(model, hi - lo, device), StateBlock(model, hi - lo, device)) for lo, hi in self.bounds]
-        self.parity = 0                       # encoder parity: the block holding the encoder caches of the next hop
+        # `parity` is the encoder's: the block holding the encoder caches of the next hop
         self.pending = False                  # a hop is encoded but not decoded yet
         # chains: encoder of group 0 on the capture stream, every other chain on its own stream (all forked from the capture
         # stream; a fork of a fork crashes hipStreamEndCapture on ROCm 7.2, so the STFT side branch exists for groups == 1 only)
         self.enc_stream = [None] + [torch.cuda.Stream(device) for _ in self.bounds[1:]]
         self.dec_stream = [torch.cuda.Stream(device) for _ in self.bounds]
-        self.spec_side = torch.cuda.Stream(device) if groups == 1 else None
+        self.spec_side = torch.cuda.Stream(device) if len(self.bounds) == 1 else None
         # concurrent chains never share ticket words
         self.sched_enc = [ops.SchedWorkspace(device) for _ in self.bounds]
         self.sched_dec = [ops.SchedWorkspace(device) for _ in self.bounds]
-        warm = torch.cuda.Stream(device)
-        warm.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(warm), torch.no_grad():
-            idx = torch.cat([self._encode(g, 0) for g in range(groups)], dim=1)
-            self.idx = (torch.zeros_like(idx), torch.zeros_like(idx))
-            for _ in range(warmup):
-                for p in (0, 1):
-                    self._both(p)
-            self._zero()
-        torch.cuda.current_stream(device).wait_stream(warm)
-        torch.cuda.synchronize(device)
-        self.graphs, self.wavs = [], []
-        for p in (0, 1):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g), torch.no_grad():
-                wav = self._both(p)
-            self.graphs.append(g)
-            self.wavs.append(wav)
-        self._zero()
-
-    @property
-    def state(self):
-        if len(self.gstate) != 1:
-            raise RuntimeError("PipelinedHop.state: the streams are split into groups — use .gstate[g]")
-        return self.gstate[0]
-
-    def _zero(self) -> None:
-        for a, b in self.gstate:
-            a.zero_()
-            b.zero_()
+        with torch.no_grad():                 # one eager encode gives the shape of the two index buffers
+            idx = torch.cat([self._encode(g, 0) for g in range(len(self.bounds))], dim=1)
+        self.idx = (torch.zeros_like(idx), torch.zeros_like(idx))
+        self.graphs, self.outs = self._capture_pair(self._both, warmup)        # outs: the wav of each parity
 
     def _encode(self, g: int, p: int) -> Tensor:
         m = self.model
         lo, hi = self.bounds[g]
         st = self.gstate[g]
-        with ops.sched_workspace(self.sched_enc[g]), _spectra_on(m.encoder, self.spec_side):
+        with ops.sched_workspace(self.sched_enc[g]), engine.spectra_side_stream(self.spec_side):
             z, _ = m.encoder(self.x[lo:hi], *st[p].enc, cache_out=st[p ^ 1].enc)
         return m.quantizer(z, self.n)
 
@@ -605,10 +499,7 @@ class PipelinedHop:
         m = self.model
         lo, hi = self.bounds[g]
         st = self.gstate[g]
-        # (rounds 4-5 captured this chain with `engine.exec_overrides(decoder_stage_narrow=False)`: beside the encoder's chain the narrow decoder
-        # stages were faster as up-sampling launch + chain.  Round 6, with EVERY stage of a hop one launch and the closing conv inside the last:
-        # 4.64 ms with that override, 4.49 without (tools/ab_pipelined_overrides.py) — the model's own options stand.  The plain replay
-        # (`GraphedHop`, no added latency) is at 4.46 ms: the two-chain schedule no longer buys anything at 1 024 streams.)
+        # captured with the model's own ExecOptions: an override for this chain alone measured slower (tools/ab_pipelined_overrides.py)
         with ops.sched_workspace(self.sched_dec[g]):
             wav, _ = m.decoder(m.dequantizer(self.idx[p ^ 1][:, lo:hi].contiguous(), self.n), *st[p ^ 1].dec,
                                cache_out=st[p].dec)
@@ -640,23 +531,20 @@ class PipelinedHop:
         decoder is one hop behind the encoder, and a (cache_enc, cache_dec) pair taken then would resume with the decoder out of
         step — refused instead of silently wrong."""
         self._no_pending("cache_enc")
-        per_group = [blocks[self.parity].enc for blocks in self.gstate]
-        return per_group[0] if len(per_group) == 1 else [torch.cat(cs, dim=0) for cs in zip(*per_group)]
+        return self.cache_enc_unsynced
 
     @property
     def cache_enc_unsynced(self) -> List[Tensor]:
         """The encoder caches as of the LAST ENCODED hop, also while a hop is pending (then the decoder's caches are one hop older: this
         list alone is a valid encoder snapshot, a (cache_enc_unsynced, cache_dec) pair is not a resumable state — `flush()` first for
         that).  For callers that checkpoint the encoder side only; rounds 2-4's `cache_enc` behaved like this."""
-        per_group = [blocks[self.parity].enc for blocks in self.gstate]
-        return per_group[0] if len(per_group) == 1 else [torch.cat(cs, dim=0) for cs in zip(*per_group)]
+        return self._current("enc")
 
     @property
     def cache_dec(self) -> List[Tensor]:
         """CURRENT decoder caches (only after `flush()`, see `cache_enc`: then both cache lists describe the same instant)"""
         self._no_pending("cache_dec")
-        per_group = [blocks[self.parity].dec for blocks in self.gstate]
-        return per_group[0] if len(per_group) == 1 else [torch.cat(cs, dim=0) for cs in zip(*per_group)]
+        return self._current("dec")
 
     def _no_pending(self, what: str) -> None:
         if self.pending:
@@ -666,10 +554,8 @@ class PipelinedHop:
     def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
         """zero history, or resume from caches exported earlier (`cache_enc` / `cache_dec`, which can only be read after a `flush()`)"""
         with torch.no_grad():
-            self.parity, self.pending = 0, False
-            for (lo, hi), (a, _b) in zip(self.bounds, self.gstate):
-                a.load_(None if cache_enc is None else [c[lo:hi] for c in cache_enc],
-                        None if cache_dec is None else [c[lo:hi] for c in cache_dec])
+            self.pending = False
+            self._load(cache_enc, cache_dec)
 
     def step(self, x: Tensor) -> Tuple[Tensor, Optional[Tensor]]:
         """x `[B,1,hop]` -> (indices of THIS hop `[n,B,T]`, wav `[B,1,hop]` of the PREVIOUS hop or None on the first
@@ -677,14 +563,13 @@ class PipelinedHop:
         p = self.parity
         self.x.copy_(x)
         if self.pending:
-            self.graphs[p].replay()
-            wav = self.wavs[p]
+            wav = self._replay()
         else:                                              # first hop: nothing to decode yet
             with torch.no_grad():
                 self.idx[p].copy_(torch.cat([self._encode(g, p) for g in range(len(self.bounds))], dim=1))
             wav = None
+            self.parity ^= 1
         self.pending = True
-        self.parity ^= 1
         return self.idx[p], wav
 
     def flush(self) -> Optional[Tensor]:
@@ -732,63 +617,50 @@ class GraphedEncodeHop(GraphedHop):
     (int32 `[B]` device view) is each slot's counter for the next hop; `export` and a resume carry none.  `header=False` captures
     exactly the graph without the header."""
 
-    side = "enc"
-
     def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, input_rate: int = BASE_RATE, fec_stages: int = 0,
                  dtx: Optional[dtx_def.DtxConfig] = None, header: bool = False):
-        self.model, self.n, self.device = model, n, device
+        # what the captured chain reads is set up first: GraphedHop's constructor captures it
         self.fec_stages = _fec_stages(fec_stages, n)
         self.header = bool(header)
-        if self.header and hop % 320:
-            raise ValueError(f"GraphedEncodeHop(header=True): hop must be a multiple of 320, got {hop}")
+        if self.header:
+            _whole_frames("GraphedEncodeHop(header=True)", hop)
         self.frames = hop // 320
         if dtx is not None and not isinstance(dtx, dtx_def.DtxConfig):
             raise ValueError(f"dtx must be a dtx.DtxConfig or None, got {dtx!r}")
         self.dtx = dtx
         if dtx is not None:
-            if hop % 320:
-                raise ValueError(f"GraphedEncodeHop(dtx=...): hop must be a multiple of 320, got {hop}")
-            dtx_def.check_order(dtx.order, wire.packet_bytes(n, hop // 320), "GraphedEncodeHop(dtx=...)")
-        if self.fec_stages and hop % 320:
-            raise ValueError(f"GraphedEncodeHop(fec_stages={fec_stages}): hop must be a multiple of 320, got {hop}")
+            dtx_def.check_order(dtx.order, wire.packet_bytes(n, _whole_frames("GraphedEncodeHop(dtx=...)", hop)),
+                                "GraphedEncodeHop(dtx=...)")
+        if self.fec_stages:
+            _whole_frames(f"GraphedEncodeHop(fec_stages={fec_stages})", hop)
         self.input_rate = int(input_rate)
-        self.rs, history, hop_in = None, 0, hop
+        self.rs, self._history, hop_in = None, 0, hop
         if self.input_rate != BASE_RATE:
-            if hop % 320:
-                raise ValueError(f"GraphedEncodeHop(input_rate={input_rate}): hop must be a multiple of 320, got {hop}")
-            hop_in = hop_samples(hop // 320, self.input_rate)
+            hop_in = hop_samples(_whole_frames(f"GraphedEncodeHop(input_rate={input_rate})", hop), self.input_rate)
             self.rs = design(self.input_rate, BASE_RATE)
             self.rs_taps = device_taps(self.rs, device)
-            history = self.rs.history
-        self.bounds = [(0, batch)]
-        self.x = torch.zeros(batch, 1, hop_in, device=device)
-        self.gstate = [(StateBlock(model, batch, device, "enc", history), StateBlock(model, batch, device, "enc", history))]
-        self.parity = 0
-        self.sessions = bool(sessions)
-        if self.sessions:
-            self._init_sessions(batch, int(max_loads_per_hop))
-            self.queue.n_min = max(1, self.fec_stages)
-        self._prev = None
+            self._history = self.rs.history
+        self._prev = self._run = self._ctr = None
         if self.fec_stages:
             # per parity, per slot: valid, then the first m stages x T frames of its last encoded hop (the hop of parity p reads
             # row p and writes row p ^ 1)
-            self._prev = torch.zeros(2, batch, 1 + self.fec_stages * (hop // 320), dtype=torch.int32, device=device)
-        self._run = None
+            self._prev = torch.zeros(2, batch, 1 + self.fec_stages * self.frames, dtype=torch.int32, device=device)
         if dtx is not None:
             # per slot: the DTX run counter (updated in place by hilc_dtx_encode once per hop)
             self._run = torch.zeros(batch, dtype=torch.int32, device=device)
             self._level_thr = torch.from_numpy(dtx_def.level_table()).to(device)
-        self._ctr = None
         if self.header:
             # per parity, per slot: the hop counter (the hop of parity p reads row p and writes row p ^ 1)
             self._ctr = torch.zeros(2, batch, dtype=torch.int32, device=device)
-        self.spec_side = [torch.cuda.Stream(device)]
-        self.chain = [None]
-        self.sched = [ops.SchedWorkspace(device)]
-        self.graphs, self.outs = _capture_pair(self._hop, self._zero, device, warmup)
+        self._scratch = [t for t in (self._prev, self._run, self._ctr) if t is not None]
+        super().__init__(model, batch, hop_in, n, device, warmup, 1, sessions, max_loads_per_hop)
+        self.queue.n_min = max(1, self.fec_stages)
         self.indices = self.outs[0][0]
         self.kind = self.outs[0][3] if dtx is not None else None
+
+    def _block(self, streams: int) -> StateBlock:
+        return StateBlock(self.model, streams, self.device, "enc", self._history)
 
     @property
     def state_bytes(self) -> int:
@@ -798,55 +670,31 @@ class GraphedEncodeHop(GraphedHop):
     def _chain(self, g: int, p: int) -> Tuple[Tensor, Tensor, Tensor]:
         m = self.model
         src, dst = self.gstate[0][p], self.gstate[0][p ^ 1]
-        n_clip = self.n_slot if self.sessions else None
+        action, hold, n_clip = (self.action, self.hold, self.n_slot) if self.sessions else (None, None, None)
         if self.sessions:
-            ops.state_slots_apply(src.buffer, src.layout, self.action, self.records)
+            ops.state_slots_apply(src.buffer, src.layout, action, self.records)
         x = self.x
         if self.rs is not None:
             x = ops.resample_poly(x, self.rs_taps, self.rs.L, self.rs.M, hist=src.hist, hist_out=dst.hist)
         with ops.sched_workspace(self.sched[0]):
-            with _spectra_on(m.encoder, self.spec_side[0]):
+            with engine.spectra_side_stream(self.spec_side[0]):
                 z, _ = m.encoder(x, *src.codec_enc, cache_out=dst.codec_enc)
             idx = m.quantizer(z, self.n, n_clip=n_clip)
         if self.fec_stages:
-            packets, nbytes = ops.pack_codes_10bit_fec(idx, self._prev[p], self._prev[p ^ 1], self.fec_stages, n_clip,
-                                                       self.action if self.sessions else None, self.hold if self.sessions else None)
+            packets, nbytes = ops.pack_codes_10bit_fec(idx, self._prev[p], self._prev[p ^ 1], self.fec_stages, n_clip, action, hold)
         else:
             packets, nbytes = ops.pack_codes_10bit(idx, n_clip)
         kind = None
         if self.dtx is not None:
             d = self.dtx
             kind = ops.dtx_encode(x, self._run, packets, nbytes, idx, self._level_thr, d.thr_vad, d.order, d.hangover, d.sid_interval,
-                                  self.action if self.sessions else None, self.hold if self.sessions else None,
-                                  self._prev[p ^ 1] if self.fec_stages else None)
+                                  action, hold, self._prev[p ^ 1] if self.fec_stages else None)
         if self.sessions:
-            ops.state_slots_hold(src.buffer, dst.buffer, src.layout, self.hold, indices=idx, packets=packets, nbytes=nbytes)
+            ops.state_slots_hold(src.buffer, dst.buffer, src.layout, hold, indices=idx, packets=packets, nbytes=nbytes)
         if self.header:
             packets, nbytes = ops.packet_header(packets, nbytes, self._ctr[p], self._ctr[p ^ 1], self.n, self.fec_stages, self.frames,
-                                                n_clip, kind, self.action if self.sessions else None,
-                                                self.hold if self.sessions else None)
+                                                n_clip, kind, action, hold)
         return (idx, packets, nbytes) if kind is None else (idx, packets, nbytes, kind)
-
-    def _zero(self) -> None:
-        super()._zero()
-        if self._prev is not None:
-            self._prev.zero_()
-        if self._run is not None:
-            self._run.zero_()
-        if self._ctr is not None:
-            self._ctr.zero_()
-
-    def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
-        """as GraphedHop.reset; with FEC, no stream has a previous hop afterwards; with DTX, every run counter is 0; with the header,
-        every hop counter is 0"""
-        super().reset(cache_enc, cache_dec)
-        with torch.no_grad():
-            if self._prev is not None:
-                self._prev.zero_()
-            if self._run is not None:
-                self._run.zero_()
-            if self._ctr is not None:
-                self._ctr.zero_()
 
     @property
     def hop_index(self) -> Tensor:
@@ -866,15 +714,14 @@ class GraphedEncodeHop(GraphedHop):
     def start(self, slot: int, cache_enc: Optional[Sequence[Tensor]] = None, n: Optional[int] = None) -> None:
         """At the next step, slot `slot` begins a fresh stream or resumes one from its 22 encoder caches (B = 1 tensors, host or
         device; 23 with `input_rate`, the resampler's history last); `n`: its number of quantiser stages (default: the graph's n)"""
-        self._need_sessions("start")
-        self.queue.start(slot, cache_enc, None, n)
+        super().start(slot, cache_enc, None, n)
 
     def export(self, slot: int) -> List[Tensor]:
         """the current 22 encoder caches of slot `slot` as B = 1 device tensors (23 with `input_rate`: the resampler's history last)"""
         return super().export(slot)[0]
 
 
-class GraphedDecodeHop:
+class GraphedDecodeHop(_Hop):
     """The receiver: one graph replay per hop turns per-stream 10-bit packets (`wire.packet_bytes(n, frames)` bytes per row)
     into `[B,1,320 frames]` samples.  `step(packets, n_per_stream)`: `packets` uint8 `[B, packet_bytes(n, frames)]` on the host
     or the device, `n_per_stream` B host ints in [1, n] (checked here: ValueError).  Both go into one static device buffer (one
@@ -932,88 +779,69 @@ class GraphedDecodeHop:
                  max_loads_per_hop: int = 4, conceal: bool = False, fade_hops: int = 4, output_rate: int = BASE_RATE,
                  fec_stages: int = 0, cng_order: Optional[int] = None, jitter: Optional[JitterConfig] = None,
                  max_arrivals: Optional[int] = None):
-        self.model, self.batch, self.frames, self.n, self.device = model, int(batch), int(frames), int(n), device
+        self.batch, self.frames = int(batch), int(frames)
         self.output_rate = int(output_rate)
-        self.rs, history = None, 0
+        self.rs, self._history = None, 0
         if self.output_rate != BASE_RATE:
             hop_samples(self.frames, self.output_rate)                  # ValueError: frames do not make whole samples at that rate
             self.rs = design(BASE_RATE, self.output_rate)
             self.rs_taps = device_taps(self.rs, device)
-            history = self.rs.history
-        if not 1 <= self.n <= len(model.dequantizer.layers):
+            self._history = self.rs.history
+        if not 1 <= int(n) <= len(model.dequantizer.layers):
             raise ValueError(f"n = {n} outside [1, {len(model.dequantizer.layers)}]")
-        self.sessions = bool(sessions)
-        if self.sessions and max_loads_per_hop < 1:
-            raise ValueError("max_loads_per_hop must be >= 1")
         self.conceal = bool(conceal)
-        if self.conceal and not self.sessions:
+        if self.conceal and not sessions:
             raise ValueError("GraphedDecodeHop(conceal=True) needs sessions=True")
-        if isinstance(fade_hops, bool) or int(fade_hops) != fade_hops or fade_hops < 1:
-            raise ValueError(f"fade_hops must be an int >= 1, got {fade_hops!r}")
-        self.fade_hops = int(fade_hops)
-        self.fec_stages = _fec_stages(fec_stages, self.n)
+        self.fade_hops = _int_arg("fade_hops", fade_hops, 1)
+        self.fec_stages = _fec_stages(fec_stages, int(n))
         self.cng_order = None
         if cng_order is not None:
-            if isinstance(cng_order, bool) or int(cng_order) != cng_order or not 0 <= int(cng_order) <= dtx_def.MAX_ORDER:
-                raise ValueError(f"cng_order must be None or an int in [0, {dtx_def.MAX_ORDER}], got {cng_order!r}")
-            if not self.sessions:
+            self.cng_order = _int_arg("cng_order", cng_order, 0, dtx_def.MAX_ORDER)
+            if not sessions:
                 raise ValueError("GraphedDecodeHop(cng_order=...) needs sessions=True")
-            self.cng_order = int(cng_order)
-            dtx_def.check_order(self.cng_order, wire.packet_bytes(self.n, self.frames), "GraphedDecodeHop(cng_order=...)")
+            dtx_def.check_order(self.cng_order, wire.packet_bytes(int(n), self.frames), "GraphedDecodeHop(cng_order=...)")
         if jitter is not None and not isinstance(jitter, JitterConfig):
             raise ValueError(f"jitter must be a jitter.JitterConfig or None, got {jitter!r}")
-        if jitter is not None and not self.sessions:
+        if jitter is not None and not sessions:
             raise ValueError("GraphedDecodeHop(jitter=...) needs sessions=True")
         self.jitter = jitter
+        if jitter is None and max_arrivals is not None:
+            raise ValueError("GraphedDecodeHop(max_arrivals=...) needs jitter=JitterConfig(...)")
+        super().__init__(model, self.batch, int(n), device, 1, sessions, max_loads_per_hop)
         self.stride = wire.packet_bytes(self.n + self.fec_stages, self.frames)
-        self.state = (StateBlock(model, batch, device, "dec", history), StateBlock(model, batch, device, "dec", history))
-        self.parity = 0
-        layout = self.state[0].layout
-        loads = int(max_loads_per_hop) if self.sessions else 0
         B = self.batch
         if jitter is not None:
-            self._init_jitter(jitter, 2 * B if max_arrivals is None else max_arrivals, loads, layout)
-        elif max_arrivals is not None:
-            raise ValueError("GraphedDecodeHop(max_arrivals=...) needs jitter=JitterConfig(...)")
-        # ONE device buffer, captured by address: ctl[0] = action per slot, ctl[1] = n per slot, ctl[2] = 1 where the slot is
-        # held, (conceal) ctl[3] = 1 where its packet was lost, (fec) the next row = 1 where it is decoded from the next packet's
-        # redundant section, the packets, the staged records
-        if jitter is None:
-            rows = 3 + self.conceal + (self.fec_stages > 0)
-            self._n_ctl = rows * B
-            self._rec_off = self._n_ctl + (B * self.stride + 3) // 4
-            self._stage = torch.zeros(self._rec_off + loads * layout.record_len, device=device)
-            self._h_stage = torch.zeros(self._stage.numel()).pin_memory()
-            ctl = self._stage[:self._n_ctl].view(torch.int32).view(rows, B)
-            self.action, self.n_slot, self.hold = ctl[0], ctl[1], ctl[2]
-            self.lost = ctl[3] if self.conceal else None
-            self.fec = ctl[rows - 1] if self.fec_stages else None
-            self.packets = self._stage[self._n_ctl:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
-            self.records = self._stage[self._rec_off:].view(loads, layout.record_len)
-            self._h_ctl = self._h_stage[:self._n_ctl].view(torch.int32).view(rows, B)
-            self._h_packets = self._h_stage[self._n_ctl:self._rec_off].view(torch.uint8)[:B * self.stride].view(B, self.stride)
-            self._h_rec = self._h_stage[self._rec_off:].view(loads, layout.record_len)
+            self._init_jitter(jitter, 2 * B if max_arrivals is None else max_arrivals)
+        else:
+            # ONE device buffer, captured by address: action per slot, n per slot, 1 where the slot is held, (conceal) 1 where its
+            # packet was lost, (fec) 1 where it is decoded from the next packet's redundant section, the packets, the staged records
+            rows = ["action", "n_slot", "hold"] + ["lost"] * self.conceal + ["fec"] * (self.fec_stages > 0)
+            st = self.stage = self._new_stage(rows, (B * self.stride + 3) // 4)
+            self.n_slot, self.lost, self.fec = st.row["n_slot"], st.row.get("lost"), st.row.get("fec")
+            self.packets = st.payload.view(torch.uint8)[:B * self.stride].view(B, self.stride)
+            self._h_packets = st.h_payload.view(torch.uint8)[:B * self.stride].view(B, self.stride)
         self.n_slot.fill_(self.n)
-        if self.sessions:
-            self.queue = SessionQueue(B, self.n, loads, layout, one_sided=True)
-            for blk in self.state:
-                blk.layout.tables(device)
-        # the host checks of step(fec=...): the session queue, or (sessions=False: no holds, losses or stops) a queue of its own
-        self._slots = self.queue if self.sessions else SessionQueue(B, self.n, 0, layout, one_sided=True)
+        self._scratch = []
         if self.conceal:
             # per slot: run k, has-codes, stored n, the stored frame's n codes (updated in place by hilc_conceal_prepare once per hop)
             self._conceal = torch.zeros(B, self.n + 3, dtype=torch.int32, device=device)
             gains, weights = wire.conceal_tables(self.fade_hops, 320 * self.frames)
             self._gains, self._weights = gains.to(device), weights.to(device)
+            self._scratch += [self._conceal]
         if self.cng_order is not None:
             # per slot: the CN state row (dtx.state_words, updated in place by hilc_cng_synth once per hop); device-only: the slots
             # that produced noise this hop (their decoder caches are copied back)
             self._cn = torch.zeros(B, dtx_def.state_words(self.cng_order), dtype=torch.int32, device=device)
             self._cn_gains = torch.from_numpy(dtx_def.gain_table()).to(device)
             self._restore = torch.zeros(B, dtype=torch.int32, device=device)
-        self._uploaded = torch.cuda.Event()
+            self._scratch += [self._cn, self._restore]
+        if jitter is not None:
+            self._scratch += [self._jstate, self._jmeta, self._jring]
         self.sched = ops.SchedWorkspace(device)
-        self.graphs, self.outs = _capture_pair(self._hop, self._zero, device, warmup)
+        self.graphs, self.outs = self._capture_pair(self._hop, warmup)
+
+    def _block(self, streams: int) -> StateBlock:
+        return StateBlock(self.model, streams, self.device, "dec", self._history)
 
     @property
     def state_bytes(self) -> int:
@@ -1023,7 +851,7 @@ class GraphedDecodeHop:
     @property
     def cache_dec(self) -> List[Tensor]:
         """the CURRENT 30 decoder caches of all streams (views of the state block; 31 with `output_rate`, the history last)"""
-        return self.state[self.parity].dec
+        return self._current("dec")
 
     @property
     def concealed(self) -> Tensor:
@@ -1040,19 +868,6 @@ class GraphedDecodeHop:
         if self.cng_order is None:
             raise RuntimeError("GraphedDecodeHop.cng_state: construct with cng_order=K")
         return self._cn
-
-    def _zero(self) -> None:
-        for blk in self.state:
-            blk.zero_()
-        if self.conceal:
-            self._conceal.zero_()
-        if self.cng_order is not None:
-            self._cn.zero_()
-            self._restore.zero_()
-        if self.jitter is not None:
-            self._jstate.zero_()
-            self._jmeta.zero_()
-            self._jring.zero_()
 
     def _hop(self, p: int) -> Tensor:
         m = self.model
@@ -1116,11 +931,7 @@ class GraphedDecodeHop:
         row holds a SID / that received nothing because their stream is in DTX (cng_order only): comfort noise"""
         if self.jitter is not None:
             raise RuntimeError("GraphedDecodeHop.step: a receiver with jitter=... takes play(slots, packets, nbytes)")
-        held = SessionQueue.host_slots(hold)
-        if held:
-            if not self.sessions:
-                raise RuntimeError("GraphedDecodeHop.step(hold=...): construct with sessions=True")
-            held = [self.queue.slot(s) for s in held]
+        held = self._hold_slots(hold)
         gone = SessionQueue.host_slots(lost)
         if gone and not self.conceal:
             raise RuntimeError("GraphedDecodeHop.step(lost=...): construct with conceal=True")
@@ -1130,84 +941,52 @@ class GraphedDecodeHop:
         if red and not self.fec_stages:
             raise RuntimeError("GraphedDecodeHop.step(fec=...): construct with fec_stages >= 1")
         if self.fec_stages:
-            red = self._slots.fec_slots(red, held, gone)
+            red = self.queue.fec_slots(red, held, gone)
         sids, quiet = SessionQueue.host_slots(sid), SessionQueue.host_slots(silent)
         if (sids or quiet) and self.cng_order is None:
             raise RuntimeError("GraphedDecodeHop.step(sid=..., silent=...): construct with cng_order=K")
         if self.cng_order is not None:
             sids, quiet = self.queue.cn_slots(sids, quiet, held, gone, red)
-        if self.sessions:
-            held = set(held) | self.queue.stops
-        n = self._check(packets, n_per_stream, set(held) | set(gone) | set(sids) | set(quiet), red)
-        self._uploaded.synchronize()          # the previous upload's copy has left the pinned buffer
-        B, h = self.batch, self._h_ctl
-        h[0].zero_()
-        h[1].copy_(n)
-        _mark(h[2], held)
+        held = set(held) | self.queue.stops
+        n = self._check(packets, n_per_stream, held | set(gone) | set(sids) | set(quiet), red)
+        st, q = self.stage, self.queue
+        st.wait()
+        h = st.h_row
+        h["n_slot"].copy_(n)
+        _mark(h["hold"], held)
         if sids:
-            h[2, torch.tensor(sids, dtype=torch.long)] = 2
+            h["hold"][torch.tensor(sids, dtype=torch.long)] = 2
         if quiet:
-            h[2, torch.tensor(quiet, dtype=torch.long)] = 3
+            h["hold"][torch.tensor(quiet, dtype=torch.long)] = 3
         if self.conceal:
-            _mark(h[3], gone)
+            _mark(h["lost"], gone)
         if self.fec_stages:
-            _mark(h[-1], red)
-        host, dev = [], []
-        if self.sessions:
-            q = self.queue
-            host = [(s, r) for s, r in q.starts.items() if r is not None and not r.is_cuda]
-            dev = [(s, r) for s, r in q.starts.items() if r is not None and r.is_cuda]
-            for slot, rec in q.starts.items():
-                if rec is None:
-                    h[0, slot] = -1
-            for r, (slot, rec) in enumerate(host + dev):
-                h[0, slot] = r + 1
-                if r < len(host):
-                    self._h_rec[r].copy_(rec)
-            q.clear()
-        stream = torch.cuda.current_stream(self.device)
+            _mark(h["fec"], red)
+        st.put_starts(q.starts)
+        q.clear()
         if packets.is_cuda:
-            self._stage[:self._n_ctl].copy_(self._h_stage[:self._n_ctl], non_blocking=True)
+            st.send(st.payload_off)
             self.packets.copy_(packets)
         else:
             self._h_packets.copy_(packets)
-            self._stage[:self._rec_off].copy_(self._h_stage[:self._rec_off], non_blocking=True)
-        if host:
-            end = self._rec_off + len(host) * self.records.shape[1]
-            self._stage[self._rec_off:end].copy_(self._h_stage[self._rec_off:end], non_blocking=True)
-        for r, (_slot, rec) in enumerate(dev, start=len(host)):
-            rec.record_stream(stream)
-            self.records[r].copy_(rec, non_blocking=True)
-        self._uploaded.record(stream)
-        self.graphs[self.parity].replay()
-        out = self.outs[self.parity]
-        self.parity ^= 1
-        return out
+            st.send(st.rec_off)
+        st.finish(host_records_apart=True)
+        return self._replay()
 
     # ---------------------------------------------------------------- jitter buffer
-    def _init_jitter(self, cfg: JitterConfig, max_arrivals, loads: int, layout: ops.StateLayout) -> None:
-        if isinstance(max_arrivals, bool) or int(max_arrivals) != max_arrivals or max_arrivals < 1:
-            raise ValueError(f"max_arrivals must be an int >= 1, got {max_arrivals!r}")
+    def _init_jitter(self, cfg: JitterConfig, max_arrivals) -> None:
         B, dev = self.batch, self.device
-        self.max_arrivals = int(max_arrivals)
+        self.max_arrivals = _int_arg("max_arrivals", max_arrivals, 1)
         self.tstride = wire.transport_bytes(self.n, self.fec_stages, self.frames)
         aw = 1 + (self.tstride + 3) // 4                   # an arrival record: byte count, then the headed packet
-        # ONE device buffer, captured by address, uploaded up to the last arrival used: ctl[0] = action per slot, ctl[1] = the host's
-        # holds (hilc_jitter_step adds its own), the CSR offsets of the arrivals [B + 1], the arrival records grouped by slot, the staged
+        # ONE device buffer, captured by address, uploaded up to the last arrival used: action per slot, the host's holds
+        # (hilc_jitter_step adds its own), the CSR offsets of the arrivals [B + 1], the arrival records grouped by slot, the staged
         # records.  The n, lost and fec rows and the packet matrix are written by hilc_jitter_step and are never uploaded.
-        self._n_ctl = 3 * B + 1
-        self._rec_off = self._n_ctl + self.max_arrivals * aw
-        self._stage = torch.zeros(self._rec_off + loads * layout.record_len, device=dev)
-        self._h_stage = torch.zeros(self._stage.numel()).pin_memory()
-        ctl = self._stage[:2 * B].view(torch.int32).view(2, B)
-        self.action, self.hold = ctl[0], ctl[1]
-        self.offsets = self._stage[2 * B:self._n_ctl].view(torch.int32)
-        self.arrivals = self._stage[self._n_ctl:self._rec_off].view(torch.int32).view(self.max_arrivals, aw)
-        self.records = self._stage[self._rec_off:].view(loads, layout.record_len)
-        self._h_ctl = self._h_stage[:2 * B].view(torch.int32).view(2, B)
-        self._h_offsets = self._h_stage[2 * B:self._n_ctl].view(torch.int32)
-        self._h_arrivals = self._h_stage[self._n_ctl:self._rec_off].view(torch.int32).view(self.max_arrivals, aw)
-        self._h_rec = self._h_stage[self._rec_off:].view(loads, layout.record_len)
+        st = self.stage = self._new_stage(("action", "hold"), B + 1 + self.max_arrivals * aw)
+        self._arr_off = st.payload_off + B + 1              # the words in front of the arrival records
+        self.offsets, self._h_offsets = st.payload[:B + 1].view(torch.int32), st.h_payload[:B + 1].view(torch.int32)
+        self.arrivals = st.payload[B + 1:].view(torch.int32).view(self.max_arrivals, aw)
+        self._h_arrivals = st.h_payload[B + 1:].view(torch.int32).view(self.max_arrivals, aw)
         rows = torch.zeros(3, B, dtype=torch.int32, device=dev)
         self.n_slot = rows[0]
         self.lost = rows[1] if self.conceal else None
@@ -1232,7 +1011,7 @@ class GraphedDecodeHop:
         pauses).  Returns the hop's waveform, a static view that the next-but-one call overwrites."""
         if self.jitter is None:
             raise RuntimeError("GraphedDecodeHop.play: construct with jitter=JitterConfig(...)")
-        held = {self.queue.slot(s) for s in SessionQueue.host_slots(hold)} | self.queue.stops
+        held = set(self._hold_slots(hold)) | self.queue.stops
         for name, v in (("slots", slots), ("nbytes", nbytes)):
             if isinstance(v, Tensor) and v.is_cuda:
                 raise ValueError(f"play: {name} must be host ints, not a device tensor")
@@ -1248,73 +1027,33 @@ class GraphedDecodeHop:
         if A and (sl.min() < 0 or sl.max() >= B):
             raise IndexError(f"play: a slot outside [0, {B})")
         order = np.argsort(sl, kind="stable")
-        self._uploaded.synchronize()          # the previous upload's copy has left the pinned buffer
-        h = self._h_ctl
-        h[0].zero_()
-        _mark(h[1], held)
+        st, q = self.stage, self.queue
+        st.wait()
+        _mark(st.h_row["hold"], held)
         offs = self._h_offsets.numpy()
         offs[0] = 0
         offs[1:] = np.cumsum(np.bincount(sl, minlength=B))
         if A:
             self._h_arrivals[:A, 0].copy_(torch.from_numpy(np.clip(nb[order], -1, 1 << 20).astype(np.int32)))
-        q = self.queue
-        host = [(s, r) for s, r in q.starts.items() if r is not None and not r.is_cuda]
-        dev = [(s, r) for s, r in q.starts.items() if r is not None and r.is_cuda]
-        for slot, rec in q.starts.items():
-            if rec is None:
-                h[0, slot] = -1
-        for r, (slot, rec) in enumerate(host + dev):
-            h[0, slot] = r + 1
-            if r < len(host):
-                self._h_rec[r].copy_(rec)
+        st.put_starts(q.starts)
         q.clear()
-        stream = torch.cuda.current_stream(self.device)
         bytes_of = lambda t: t.view(torch.uint8)[:, 4:4 + self.tstride]
-        used = self._n_ctl + A * self.arrivals.shape[1]
         if A and not packets.is_cuda:
             bytes_of(self._h_arrivals[:A]).copy_(packets[torch.from_numpy(order)])
-        self._stage[:used].copy_(self._h_stage[:used], non_blocking=True)
+        st.send(self._arr_off + A * self.arrivals.shape[1])
         if A and packets.is_cuda:
             rows = packets if np.array_equal(order, np.arange(A)) else packets[torch.from_numpy(order).to(self.device)]
             bytes_of(self.arrivals[:A]).copy_(rows)
-        if host:
-            end = self._rec_off + len(host) * self.records.shape[1]
-            self._stage[self._rec_off:end].copy_(self._h_stage[self._rec_off:end], non_blocking=True)
-        for r, (_slot, rec) in enumerate(dev, start=len(host)):
-            rec.record_stream(stream)
-            self.records[r].copy_(rec, non_blocking=True)
-        self._uploaded.record(stream)
-        self.graphs[self.parity].replay()
-        out = self.outs[self.parity]
-        self.parity ^= 1
-        return out
+        st.finish(host_records_apart=True)
+        return self._replay()
 
     def start(self, slot: int, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
         """At the next step, slot `slot` begins a fresh stream (zero caches) or resumes one from its 30 decoder caches (B = 1
         tensors, host or device; 31 with `output_rate`, the resampler's history last); at most `max_loads_per_hop` resumes per hop.
         With `jitter`, its jitter state is cleared on that hop"""
-        if not self.sessions:
-            raise RuntimeError("GraphedDecodeHop.start: construct with sessions=True")
-        self.queue.start(slot, None, cache_dec)
-
-    def stop(self, slot: int) -> None:
-        """from the next step on, slot `slot` is held (does not advance) on every step until the next `start(slot, ...)`"""
-        if not self.sessions:
-            raise RuntimeError("GraphedDecodeHop.stop: construct with sessions=True")
-        self.queue.stop(slot)
-
-    @property
-    def stopped(self) -> Tuple[int, ...]:
-        """the stopped slots, sorted"""
-        return self.queue.stopped if self.sessions else ()
+        super().start(slot, None, cache_dec)
 
     def export(self, slot: int) -> List[Tensor]:
         """the current 30 decoder caches of slot `slot` as B = 1 device tensors (one gather launch; a stopped slot: its caches
         when it stopped; 31 with `output_rate`, the resampler's history last)"""
-        if not self.sessions:
-            raise RuntimeError("GraphedDecodeHop.export: construct with sessions=True")
-        blk = self.state[self.parity]
-        slots = torch.tensor([self.queue.slot(slot)], dtype=torch.int32, device=self.device)
-        with torch.no_grad():
-            rec = ops.state_slots_gather(blk.buffer, blk.layout, slots)
-        return blk.layout.split(rec[0])[1]
+        return super().export(slot)[1]

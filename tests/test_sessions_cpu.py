@@ -158,3 +158,62 @@ def test_pipelined_hop_refuses_sessions():
     from hilcodec_amd.graph_step import PipelinedHop
     with pytest.raises(NotImplementedError):
         PipelinedHop(None, 4, 320, 8, torch.device("cpu"), sessions=True)
+
+
+@pytest.mark.parametrize("B", [1, 5, 1024])
+def test_stage_layout_matches_the_three_layouts(B):
+    """sessions.stage_layout gives the word offsets the three hops used to compute by hand (written out here as literals)"""
+    from hilcodec_amd.sessions import stage_layout
+    for loads, L in ((0, 37), (3, 37)):
+        # GraphedHop / GraphedEncodeHop: action, n, hold, then the records
+        rows, pay, rec, total = stage_layout(B, ("action", "n_slot", "hold"), 0, loads, L)
+        assert rows == {"action": 0, "n_slot": B, "hold": 2 * B}
+        assert pay == rec == 3 * B and total == 3 * B + loads * L
+        # GraphedDecodeHop.step: (3 + conceal + (m > 0)) rows, the packet matrix rounded up to words, the records
+        for conceal in (False, True):
+            for m in (0, 2):
+                for stride in (1, 7, 10, 13, 255):
+                    names = ["action", "n_slot", "hold"] + ["lost"] * conceal + ["fec"] * (m > 0)
+                    rows, pay, rec, total = stage_layout(B, names, (B * stride + 3) // 4, loads, L)
+                    n_ctl = (3 + conceal + (m > 0)) * B
+                    assert (rows["action"], rows["n_slot"], rows["hold"]) == (0, B, 2 * B)
+                    assert rows.get("lost") == (3 * B if conceal else None)
+                    assert rows.get("fec") == (n_ctl - B if m else None)          # the last row
+                    assert pay == n_ctl and rec == n_ctl + (B * stride + 3) // 4 and total == rec + loads * L
+        # GraphedDecodeHop.play: action, hold, the CSR offsets [B + 1], max_arrivals records of 1 + ceil(tstride / 4) words
+        for max_arrivals in (1, 2 * B, 2 * B + 1):
+            for tstride in (3, 13, 16, 257):
+                aw = 1 + (tstride + 3) // 4
+                rows, pay, rec, total = stage_layout(B, ("action", "hold"), B + 1 + max_arrivals * aw, loads, L)
+                assert rows == {"action": 0, "hold": B} and pay == 2 * B
+                assert pay + B + 1 == 3 * B + 1                                    # where the arrival records begin
+                assert rec == 3 * B + 1 + max_arrivals * aw and total == rec + loads * L
+
+
+def test_stage_starts_rule():
+    """queued starts -> action row and records: a fresh start writes -1, host records come first, the record at index r writes
+    r + 1, a later start for the same slot replaces the earlier one"""
+    from types import SimpleNamespace
+    from hilcodec_amd import ops
+    from hilcodec_amd.sessions import SessionQueue, stage_starts
+    B = 6
+    layout = ops.StateLayout([(B, 1, 2), (B, 1, 3)], 1)
+    q = SessionQueue(B, 8, 4, layout)
+    rec = lambda v: ([torch.full((1, 1, 2), float(v))], [torch.full((1, 1, 3), float(v))])
+    q.start(4)
+    q.start(1, *rec(1.0))
+    q.start(5, *rec(5.0))
+    q.start(1)                                            # replaces the resume of slot 1 by a fresh start
+    q.start(4, *rec(4.0))                                 # replaces the fresh start of slot 4 by a resume
+    q.start(0, *rec(7.0))
+    on_device = SimpleNamespace(is_cuda=True)             # stands for a record that lives on the device: handed back, not copied
+    q.starts[2] = on_device
+    q.starts[3] = None
+    action = torch.zeros(B, dtype=torch.int32)
+    h_records = torch.zeros(4, layout.record_len)
+    n_host, dev = stage_starts(q.starts, action, h_records)
+    assert n_host == 3 and dev == [on_device]
+    # host records in queue order: slot 4, slot 5, slot 0; then the device record of slot 2
+    assert action.tolist() == [3, -1, 4, -1, 1, 2]
+    assert h_records[:, 0].tolist() == [4.0, 5.0, 7.0, 0.0] and bool((h_records[:3] == h_records[:3, :1]).all())
+    assert stage_starts({}, action.zero_(), h_records) == (0, []) and not action.any()

@@ -111,6 +111,7 @@ def make(leg):
 
 hoppers = {leg: make(leg) for leg in args.legs}
 host_s = {leg: [] for leg in args.legs}
+sent = {leg: [] for leg in args.legs}      # bytes of each call's pinned copy (ControlStage.sent_words)
 
 
 def one(leg, i):
@@ -126,6 +127,7 @@ def one(leg, i):
     else:
         h.step(rows, n_list, **kw)
     host_s[leg].append(time.perf_counter() - c0)
+    sent[leg].append(4 * h.stage.sent_words)
 
 
 def run(leg, hops):
@@ -145,6 +147,7 @@ def run(leg, hops):
 for leg in args.legs:                    # warm
     run(leg, min(5, args.hops))
     host_s[leg].clear()
+    sent[leg].clear()
 res = {leg: [] for leg in args.legs}
 print(f"# jitter_hop_ab: {B} streams, hil_speech, frames 1, n {n}, m {m}, K {K}, {cfg}, host packets, {args.hops} hops per leg x "
       f"{args.alternations} alternations; {torch.cuda.get_device_name(dev)}", flush=True)
@@ -168,11 +171,6 @@ for leg in args.legs:
     kind, mix, name = LEGS[leg]
     if kind == "enc":
         continue
-    h = hoppers[leg]
-    if kind == "play":
-        aw = h.arrivals.shape[1]
-        sizes = [4 * (h._n_ctl + len(tr[0]) * aw) for tr in traces[mix]]
-    else:
-        sizes = [4 * h._rec_off] * len(traces[mix])
+    sizes = sent[leg]
     print(f"{name:40s} upload median {int(statistics.median(sizes))} B (min {min(sizes)}, max {max(sizes)}), host "
           f"{1e6 * statistics.median(host_s[leg]):.1f} us/call", flush=True)
