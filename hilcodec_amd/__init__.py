@@ -6,5 +6,8 @@ from . import _lib  # noqa: F401  (raises if the HIP library is not built)
 from .models.hilcodec.models import HILCodec  # noqa: F401
 # the offline converter; the module's other names are imported from it by name (`from hilcodec_amd.resample import design`)
 from .resample import Resampler, resample  # noqa: F401
+# the room mixer's eager one-call form and its configuration (the graphed form: graph_step.GraphedDecodeHop(mix=MixConfig(...)))
+from .mixer import MixConfig  # noqa: F401
+from .ops import room_mix as mix_rooms  # noqa: F401
 
-__all__ = ["HILCodec", "Resampler", "resample"]
+__all__ = ["HILCodec", "Resampler", "resample", "MixConfig", "mix_rooms"]

@@ -25,6 +25,7 @@ from torch import Tensor
 from . import dtx as dtx_def
 from . import engine, ops, wire
 from .jitter import JitterConfig
+from .mixer import MixConfig
 from .resample import BASE_RATE, design, device_taps, hop_samples
 from .sessions import SessionQueue, stage_layout, stage_starts
 
@@ -773,12 +774,23 @@ class GraphedDecodeHop(_Hop):
     lost and fec rows and the packet matrix that `step` uploads, so the rest of the graph is unchanged and the output is a pure
     function of the arrival trace.  Host holds and stops pause a slot's playout (its arrivals are still buffered); `start` clears
     its jitter state; `export` and a resume carry none; `jitter_state` is the int32 `[B, jitter.ST_WORDS]` state rows.  With `jitter`,
-    `step` raises RuntimeError; without it, `play` does.  `jitter=None` captures exactly the graph without the jitter buffer."""
+    `step` raises RuntimeError; without it, `play` does.  `jitter=None` captures exactly the graph without the jitter buffer.
+    `mix` = mixer.MixConfig(top_k) (needs `sessions`): a conference bridge's room mixer at the tail of the graph (mixer.py).  `join(slot,
+    room)` / `leave(slot)` put a slot into a room (an id in [0, B)) or into none, `rooms` is the host's membership tuple (-1: none;
+    initially every slot; `stop` does not leave a room).  Membership is a pinned int32 row; when it has changed since the last hop, the
+    whole row goes to a device row captured by address, on the replay stream before the replay (not through the control stage).
+    `step` and `play` return what they return without `mix`; after them `mixed` (fp32 `[B,1,L]`, L the returned waveform's length, so at
+    `output_rate`) holds every slot's mix of its room's `top_k` highest-scoring other members — a static view that the next-but-one call
+    overwrites, like the waveform, and that a GraphedEncodeHop on the same device takes as its `step(x)`: a bridge is two replays per
+    hop and no host copy.  `speakers` (int32 `[B]`) marks the slots among their room's top_k, `levels` (float64 `[B]`) is the peak-hold
+    score of every slot; a `start` clears a slot's score inside the graph.  Graph: hilc_mix_levels and hilc_mix_rooms are the last two
+    launches, after the final hilc_state_slots_hold and the hilc_cng_synth behind it: comfort noise is mixed as noise, a held slot as
+    zeros, and a held listener still gets its mix.  `mix=None` captures exactly the graph without the mixer."""
 
     def __init__(self, model, batch: int, frames: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, conceal: bool = False, fade_hops: int = 4, output_rate: int = BASE_RATE,
                  fec_stages: int = 0, cng_order: Optional[int] = None, jitter: Optional[JitterConfig] = None,
-                 max_arrivals: Optional[int] = None):
+                 max_arrivals: Optional[int] = None, mix: Optional[MixConfig] = None):
         self.batch, self.frames = int(batch), int(frames)
         self.output_rate = int(output_rate)
         self.rs, self._history = None, 0
@@ -807,6 +819,11 @@ class GraphedDecodeHop(_Hop):
         self.jitter = jitter
         if jitter is None and max_arrivals is not None:
             raise ValueError("GraphedDecodeHop(max_arrivals=...) needs jitter=JitterConfig(...)")
+        if mix is not None and not isinstance(mix, MixConfig):
+            raise ValueError(f"mix must be a mixer.MixConfig or None, got {mix!r}")
+        if mix is not None and not sessions:
+            raise ValueError("GraphedDecodeHop(mix=...) needs sessions=True")
+        self.mix = mix
         super().__init__(model, self.batch, int(n), device, 1, sessions, max_loads_per_hop)
         self.stride = wire.packet_bytes(self.n + self.fec_stages, self.frames)
         B = self.batch
@@ -837,6 +854,17 @@ class GraphedDecodeHop(_Hop):
             self._scratch += [self._cn, self._restore]
         if jitter is not None:
             self._scratch += [self._jstate, self._jmeta, self._jring]
+        if mix is not None:
+            # per slot: the peak-hold score (updated in place by hilc_mix_levels once per hop); per parity: the mixes; the speaker
+            # marks; the room row (device, captured by address) and its pinned host mirror
+            L = hop_samples(self.frames, self.output_rate) if self.rs is not None else 320 * self.frames
+            self._score = torch.zeros(B, dtype=torch.float64, device=device)
+            self._mixed = torch.zeros(2, B, 1, L, device=device)
+            self._speakers = torch.zeros(B, dtype=torch.int32, device=device)
+            self._room = torch.full((B,), -1, dtype=torch.int32, device=device)
+            self._h_room = torch.full((B,), -1, dtype=torch.int32).pin_memory()
+            self._room_dirty, self._room_sent = False, torch.cuda.Event()
+            self._scratch += [self._score]
         self.sched = ops.SchedWorkspace(device)
         self.graphs, self.outs = self._capture_pair(self._hop, warmup)
 
@@ -902,7 +930,65 @@ class GraphedDecodeHop(_Hop):
         if cng and self.rs is None:
             # the final hold treated the CN slots (hold 2 / 3) as held: their caches are as they were, the noise overwrites the zeros
             ops.cng_synth(self.packets, self.hold, self._cn, wav, self._cn_gains, self.cng_order, self.action)
+        if self.mix is not None:
+            # the graph's last two launches: the rows are final (noise written, held rows zero)
+            ops.mix_levels(wav, self._score, self.action)
+            ops.mix_rooms(wav, self._room, self._score, self.mix.top_k, self._mixed[p], self._speakers)
         return wav
+
+    # ---------------------------------------------------------------- room mixing
+    def _need_mix(self, what: str) -> None:
+        if self.mix is None:
+            raise RuntimeError(f"GraphedDecodeHop.{what}: construct with mix=MixConfig(...)")
+
+    def join(self, slot: int, room: int) -> None:
+        """from the next hop on, slot `slot` is a member of room `room` (an int in [0, B): ValueError), and of no other"""
+        self._need_mix("join")
+        s = self.queue.slot(slot)
+        self._set_room(s, _int_arg("room", room, 0, self.batch - 1))
+
+    def leave(self, slot: int) -> None:
+        """from the next hop on, slot `slot` is in no room (its mix is zero and nobody hears it)"""
+        self._need_mix("leave")
+        self._set_room(self.queue.slot(slot), -1)
+
+    def _set_room(self, slot: int, room: int) -> None:
+        if int(self._h_room[slot]) != room:
+            self._room_sent.synchronize()     # the previous upload's copy has left the pinned row
+            self._h_room[slot] = room
+            self._room_dirty = True
+
+    def _send_rooms(self) -> None:
+        """before a replay, on its stream: the membership row, when it has changed since the last hop"""
+        if self.mix is not None and self._room_dirty:
+            self._room.copy_(self._h_room, non_blocking=True)
+            self._room_sent.record(torch.cuda.current_stream(self.device))
+            self._room_dirty = False
+
+    @property
+    def rooms(self) -> Tuple[int, ...]:
+        """each slot's room as the host has it (-1: none)"""
+        self._need_mix("rooms")
+        return tuple(self._h_room.tolist())
+
+    @property
+    def mixed(self) -> Tensor:
+        """fp32 `[B,1,L]` device view: every slot's mix after the last hop (zeros before the first); overwritten by the next-but-one
+        call.  Read-only: written by the graph."""
+        self._need_mix("mixed")
+        return self._mixed[self.parity ^ 1]
+
+    @property
+    def speakers(self) -> Tensor:
+        """int32 `[B]` device view: 1 for the slots among their room's top_k after the last hop.  Read-only: written by the graph."""
+        self._need_mix("speakers")
+        return self._speakers
+
+    @property
+    def levels(self) -> Tensor:
+        """float64 `[B]` device view: every slot's peak-hold score after the last hop.  Read-only: written by the graph."""
+        self._need_mix("levels")
+        return self._score
 
     def _check(self, packets: Tensor, n_per_stream, held=(), fec=()) -> Tensor:
         """n_per_stream as a tensor; the entries of `held` slots are not range-checked and become the graph's n, those of `fec`
@@ -971,6 +1057,7 @@ class GraphedDecodeHop(_Hop):
             self._h_packets.copy_(packets)
             st.send(st.rec_off)
         st.finish(host_records_apart=True)
+        self._send_rooms()
         return self._replay()
 
     # ---------------------------------------------------------------- jitter buffer
@@ -1045,6 +1132,7 @@ class GraphedDecodeHop(_Hop):
             rows = packets if np.array_equal(order, np.arange(A)) else packets[torch.from_numpy(order).to(self.device)]
             bytes_of(self.arrivals[:A]).copy_(rows)
         st.finish(host_records_apart=True)
+        self._send_rooms()
         return self._replay()
 
     def start(self, slot: int, cache_dec: Optional[Sequence[Tensor]] = None) -> None:

@@ -1085,6 +1085,39 @@ _register("jitter_step", "(Tensor arrivals, Tensor offsets, Tensor? action, Tens
           "int depth) -> ()", _jitter_step,
           lambda arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, n, m, frames, order, depth: None)
 
+# ======================================================================================================
+# per-room mixing of the receiver's output (graph_step.GraphedDecodeHop(mix=); definition: hilcodec_amd/mixer.py; semantics:
+# include/hilcodec_amd.h)
+# ======================================================================================================
+def _mix_rows(name, wav):
+    if wav.dim() != 3 or wav.shape[1] != 1 or wav.shape[0] < 1 or wav.shape[2] < 1 or not wav.is_contiguous():
+        raise RuntimeError(f"{name}: wav must be a contiguous [B, 1, L >= 1]")
+    return wav.shape[0], wav.shape[2]
+
+
+def _mix_levels(wav, score, action):
+    B, L = _mix_rows("mix_levels", wav)
+    if score.shape != (B,) or (action is not None and action.numel() != B):
+        raise RuntimeError(f"mix_levels: score must be float64 [{B}] and action int32 [{B}]")
+    check(lib.hilc_mix_levels(_ptr(wav), _ptr(score, torch.float64), _ptr(action, torch.int32), B, L, _stream()), "hilc_mix_levels")
+
+
+_register("mix_levels", "(Tensor wav, Tensor(a!) score, Tensor? action) -> ()", _mix_levels, lambda wav, score, action: None)
+
+
+def _mix_rooms(wav, room, score, top_k, mixed, speakers):
+    B, L = _mix_rows("mix_rooms", wav)
+    if room.shape != (B,) or score.shape != (B,) or speakers.shape != (B,):
+        raise RuntimeError(f"mix_rooms: room, score and speakers must be [{B}]")
+    if mixed.shape != wav.shape or mixed.data_ptr() == wav.data_ptr():
+        raise RuntimeError(f"mix_rooms: mixed must be [{B}, 1, {L}] and a buffer other than wav")
+    check(lib.hilc_mix_rooms(_ptr(wav), _ptr(room, torch.int32), _ptr(score, torch.float64), top_k, _ptr(mixed),
+                             _ptr(speakers, torch.int32), B, L, _stream()), "hilc_mix_rooms")
+
+
+_register("mix_rooms", "(Tensor wav, Tensor room, Tensor score, int top_k, Tensor(a!) mixed, Tensor(b!) speakers) -> ()", _mix_rooms,
+          lambda wav, room, score, top_k, mixed, speakers: None)
+
 _OPS = torch.ops.hilcodec
 
 
@@ -1717,3 +1750,33 @@ def resample_poly(x: Tensor, taps: Tensor, L: int, M: int, hist: Optional[Tensor
     if hist is not None and hist is hist_out:
         raise RuntimeError("resample_poly: hist and hist_out must be distinct buffers (the kernel refuses one shared pointer too)")
     return _OPS.resample_poly(x, hist, hist_out, taps, int(L), int(M))
+
+
+def mix_levels(wav: Tensor, score: Tensor, action: Optional[Tensor] = None) -> None:
+    """The mixer's first step (mixer.py), in place: `score` (float64 `[B]`) becomes max(E, score / 2) with E the float64 energy of the
+    slot's `wav` row (fp32 contiguous `[B, 1, L]`); a slot with an `action` (int32 `[B]`, optional) starts from score 0."""
+    _OPS.mix_levels(wav, score, action)
+
+
+def mix_rooms(wav: Tensor, room: Tensor, score: Tensor, top_k: int, mixed: Tensor, speakers: Tensor) -> None:
+    """The mixer's second step (mixer.py), in place: per slot of `room` (int32 `[B]`, -1 = none) the clamped fp32 sum of the rows of
+    its room's `top_k` highest-scoring other members -> `mixed` (fp32 `[B, 1, L]`, not `wav`), and `speakers` (int32 `[B]`): 1 for the
+    slots that are among their room's top_k.  `score`: float64 `[B]` as `mix_levels` left it."""
+    _OPS.mix_rooms(wav, room, score, int(top_k), mixed, speakers)
+
+
+def room_mix(wav: Tensor, room: Tensor, score: Optional[Tensor] = None, top_k: int = 3) -> Tuple[Tensor, Tensor, Tensor]:
+    """`hilcodec_amd.mix_rooms`: one hop of the room mixer for callers without a graph (two launches; mixer.MixModel bit for bit).
+    wav fp32 `[B, 1, L]` and room int32 `[B]` on the GPU; `score` float64 `[B]`: the state returned by the previous call (updated in
+    place; None: a fresh one).  Returns (mixed fp32 `[B, 1, L]`, speakers int32 `[B]`, score)."""
+    from .mixer import MixConfig
+    top_k = int(MixConfig(top_k).top_k)
+    wav = wav.contiguous()
+    B = wav.shape[0]
+    if score is None:
+        score = torch.zeros(B, dtype=torch.float64, device=wav.device)
+    mixed = torch.empty_like(wav)
+    speakers = torch.empty(B, dtype=torch.int32, device=wav.device)
+    mix_levels(wav, score)
+    mix_rooms(wav, room, score, top_k, mixed, speakers)
+    return mixed, speakers, score
