@@ -114,6 +114,11 @@ class ResBlockSpec:
     pw1_chain: Optional[Tensor] = None    # the same for a chain launch (streaming plans; another row split below C = 192, else the tensors above)
     pw2_chain: Optional[Tensor] = None
 
+    @property
+    def chain_args(self) -> tuple:
+        """this block as `ops.resblock_chain` and the stage ops take it"""
+        return (self.pw1_chain, self.dw1_w, self.dw1_b, self.pw2_chain, self.dw2_w, self.dw2_b, self.pre_scale, self.out_scale)
+
 
 @dataclass
 class SpecBlockSpec:
@@ -266,6 +271,35 @@ def _fusable(rb: ResBlockSpec, x: Tensor, streaming: bool = False, wide: Optiona
             and ops.resblock_supported(x.shape[1], x.shape[2], x.shape[0], streaming))
 
 
+def _chainable(blocks: Sequence[ResBlockSpec]) -> bool:
+    """what every chain / stage kernel assumes of its blocks: weights packed for it, 5-tap depthwise convs with a bias"""
+    return all(rb.pw1_chain is not None and rb.dw1_w.shape[1] == 5 and rb.dw2_w.shape[1] == 5 and rb.dw1_b is not None
+               and rb.dw2_b is not None for rb in blocks)
+
+
+def _pairs(seq: Optional[Sequence[Tensor]], start: int, n: int) -> Optional[List[Sequence[Tensor]]]:
+    """the two depthwise caches of each of n consecutive blocks, the first block's at seq[start]; None where there is no list"""
+    return None if seq is None else [seq[start + 2 * i: start + 2 * i + 2] for i in range(n)]
+
+
+# the argument tuples of the stage ops (`ops.encoder_stage0`, `ops.encoder_stage`, `ops.decoder_stage`, `ops.decoder_stage_post`)
+def _spec0_args(es: "EncoderSpec") -> tuple:
+    sb = es.stages[0].spec
+    return (sb.fused[0], sb.fused[1], sb.fused[2], sb.bias, es.pre_w, es.pre_b, es.pre_in_scale, sb.mean, sb.std, sb.normalize, sb.out_scale)
+
+
+def _down_args(st: "EncStageSpec") -> tuple:
+    return (st.down_lo, st.down_hi, st.down_dw_w, st.down_dw_b, st.down_in_scale, st.ratio)
+
+
+def _up_args(st: "DecStageSpec") -> tuple:
+    return (st.tr_w if st.taps is None else st.taps, st.up_lo, st.up_hi, st.pw_b, st.in_scale, st.ratio)
+
+
+def _post_args(ds: "DecoderSpec") -> tuple:
+    return (ds.post_w, ds.post_b, ds.post_in_scale, ds.post_out_scale, ds.tanh)
+
+
 def _resblock(rb: ResBlockSpec, x: Tensor, caches: Optional[Sequence[Tensor]], new_caches: Optional[list],
               outs: Optional[Sequence[Tensor]] = None, opts: ExecOptions = _DEFAULT_OPTIONS) -> Tensor:
     """One residual block; streaming: `caches` = its two depthwise caches, `outs` = where the next hop's caches go
@@ -315,25 +349,19 @@ def _stage_blocks(blocks: Sequence[ResBlockSpec], x: Tensor, caches: Optional[Se
     activations between them stay in registers: `ops.resblock_chain`); otherwise block by block."""
     n = len(blocks)
     streaming = caches is not None
-    if (streaming and FUSE_RESBLOCK and FUSE_STREAM and opts.stage_launches and n >= 2 and x.shape[2] >= 4
-            and all(rb.pw1_chain is not None and rb.dw1_w.shape[1] == 5 and rb.dw2_w.shape[1] == 5 and rb.dw1_b is not None
-                    and rb.dw2_b is not None for rb in blocks)
+    hist, hist_out = _pairs(caches, ci, n), _pairs(caches_out, ci, n)
+    if (streaming and FUSE_RESBLOCK and FUSE_STREAM and opts.stage_launches and n >= 2 and x.shape[2] >= 4 and _chainable(blocks)
             and (x.shape[1] <= FUSE_RESBLOCK_MAX_C or opts.wide_blocks)
             and ops.resblock_chain_supported(x.shape[1], x.shape[2], n, x.shape[0])):
-        y, cs = ops.resblock_chain(
-            x, [(rb.pw1_chain, rb.dw1_w, rb.dw1_b, rb.pw2_chain, rb.dw2_w, rb.dw2_b, rb.pre_scale, rb.out_scale) for rb in blocks],
-            [caches[ci + 2 * i: ci + 2 * i + 2] for i in range(n)],
-            [caches_out[ci + 2 * i: ci + 2 * i + 2] for i in range(n)] if caches_out is not None else None)
+        y, cs = ops.resblock_chain(x, [rb.chain_args for rb in blocks], hist, hist_out)
         new_caches.extend(cs)
         return y
     if (not streaming and FUSE_RESBLOCK and opts.stage_launches and n >= 2
             and all(rb.pw1_chain is not None and _fusable(rb, x, False, opts.wide_blocks) for rb in blocks)
             and ops.resblock_chain_supported(x.shape[1], x.shape[2], n, x.shape[0], streaming=False)):
-        return ops.resblock_chain(
-            x, [(rb.pw1_chain, rb.dw1_w, rb.dw1_b, rb.pw2_chain, rb.dw2_w, rb.dw2_b, rb.pre_scale, rb.out_scale) for rb in blocks])
+        return ops.resblock_chain(x, [rb.chain_args for rb in blocks])
     for i, rb in enumerate(blocks):
-        x = _resblock(rb, x, caches[ci + 2 * i: ci + 2 * i + 2] if streaming else None, new_caches,
-                      caches_out[ci + 2 * i: ci + 2 * i + 2] if caches_out is not None else None, opts=opts)
+        x = _resblock(rb, x, hist[i] if streaming else None, new_caches, hist_out[i] if hist_out is not None else None, opts=opts)
     return x
 
 
@@ -342,14 +370,40 @@ def _stage_fusable_blocks(st: "DecStageSpec", x: Tensor, streaming: bool, partia
     first one (where LDS holds the carry slots / the halo form of one block only), or 0 = no stage launch for this shape."""
     if st.up_lo is None or st.pw_b is None or not st.blocks:
         return 0
-    if not all(rb.pw1_chain is not None and rb.dw1_w.shape[1] == 5 and rb.dw2_w.shape[1] == 5 and rb.dw1_b is not None
-               and rb.dw2_b is not None for rb in st.blocks):
+    if not _chainable(st.blocks):
         return 0
     c, t = st.pw_wt.shape[1], x.shape[2] * st.ratio
     for nb in ((len(st.blocks), 1) if partial else (len(st.blocks),)):
         if ops.decoder_stage_supported(c, t, nb, st.ratio, x.shape[0], streaming=streaming):
             return nb
     return 0
+
+
+def _pre_fusable(es: "EncoderSpec", wav: Tensor, wav_hist: Optional[Tensor]) -> bool:
+    """the first conv and the stage-0 SpecBlock in one launch (`ops.spec_block_conv_pre`, or as the opening phase of `ops.encoder_stage0`)"""
+    sb0 = es.stages[0].spec
+    return bool(FUSE_SPECBLOCK and sb0.fused is not None and sb0.n_fft == 64 and sb0.hop == 1
+                and es.pre_w.shape == (64, 5) and ops.spec_block_supported(64, 1, 64, wav.shape[2])
+                and (wav_hist is None or wav_hist.shape[-1] >= 63))
+
+
+def _stage_launchable(st: "EncStageSpec", t: int, streaming: bool, opts: ExecOptions) -> bool:
+    """what both one-launch forms of an encoder stage ask of the schedule and of the spec, at t samples per clip / stream"""
+    return (FUSE_RESBLOCK and opts.stage_launches and (not streaming or FUSE_STREAM) and st.down_lo is not None and st.down_dw_b is not None
+            and st.down_dw_w.shape[1] == 2 * st.ratio and t % st.ratio == 0 and _chainable(st.blocks))
+
+
+def _stage0_fusable(es: "EncoderSpec", wav: Tensor, streaming: bool, opts: ExecOptions) -> bool:
+    """(where `_pre_fusable`) the whole first stage behind the first conv and its SpecBlock: `ops.encoder_stage0`"""
+    st0 = es.stages[0]
+    return bool((not streaming or STREAM_STAGE0) and _stage_launchable(st0, wav.shape[2], streaming, opts)
+                and ops.encoder_stage0_supported(wav.shape[2], len(st0.blocks), st0.ratio, 64, 1, es.pre_w.shape[1], wav.shape[0], streaming))
+
+
+def _enc_stage_fusable(st: "EncStageSpec", x: Tensor, streaming: bool, opts: ExecOptions) -> bool:
+    """an encoder stage, residual blocks and down-sampling layer, as one launch: `ops.encoder_stage`"""
+    return bool(_stage_launchable(st, x.shape[2], streaming, opts) and (x.shape[1] <= FUSE_RESBLOCK_MAX_C or opts.wide_blocks)
+                and ops.encoder_stage_supported(x.shape[1], x.shape[2], len(st.blocks), st.ratio, x.shape[0], streaming))
 
 
 def _spec_fused(sb: SpecBlockSpec, wav: Tensor, wav_hist: Optional[Tensor]) -> bool:
@@ -465,25 +519,10 @@ def run_encoder(es: EncoderSpec, wav: Tensor, caches: Optional[Sequence[Tensor]]
         new_caches.append(ops.tail(wav, wav_hist, es.wav_cache_len, out=out(0)))
         ci = 1
     sb0 = es.stages[0].spec
-    fuse_pre = (FUSE_SPECBLOCK and sb0.fused is not None and sb0.n_fft == 64 and sb0.hop == 1
-                and es.pre_w.shape == (64, 5) and ops.spec_block_supported(64, 1, 64, wav.shape[2])
-                and (wav_hist is None or wav_hist.shape[-1] >= 63))
-    st0 = es.stages[0]
-    fuse_stage0 = (fuse_pre and (not streaming or (FUSE_STREAM and STREAM_STAGE0)) and FUSE_RESBLOCK and opts.stage_launches and st0.down_lo is not None and st0.down_dw_b is not None
-                   and st0.down_dw_w.shape[1] == 2 * st0.ratio and wav.shape[2] % st0.ratio == 0
-                   and all(rb.pw1_chain is not None and rb.dw1_w.shape[1] == 5 and rb.dw2_w.shape[1] == 5 and rb.dw1_b is not None
-                           and rb.dw2_b is not None for rb in st0.blocks)
-                   and ops.encoder_stage0_supported(wav.shape[2], len(st0.blocks), st0.ratio, 64, 1, es.pre_w.shape[1], wav.shape[0], streaming))
-    blocks0 = [(rb.pw1_chain, rb.dw1_w, rb.dw1_b, rb.pw2_chain, rb.dw2_w, rb.dw2_b, rb.pre_scale, rb.out_scale) for rb in st0.blocks] if fuse_stage0 else None
-    if fuse_stage0 and not streaming:
-        # first conv + first SpecBlock + the whole first stage in one launch: neither the [64 x T] tensor in front of the stage nor the one
-        # behind its blocks ever exists
-        x = ops.encoder_stage0(
-            wav, (sb0.fused[0], sb0.fused[1], sb0.fused[2], sb0.bias, es.pre_w, es.pre_b, es.pre_in_scale, sb0.mean, sb0.std, sb0.normalize,
-                  sb0.out_scale),
-            blocks0, (st0.down_lo, st0.down_hi, st0.down_dw_w, st0.down_dw_b, st0.down_in_scale, st0.ratio))
-    elif fuse_stage0:
-        x = None      # launched below, once the side branch that computes stage 1's SpecBlock has been forked
+    fuse_pre = _pre_fusable(es, wav, wav_hist)
+    fuse_stage0 = fuse_pre and _stage0_fusable(es, wav, streaming, opts)
+    if fuse_stage0:
+        x = None      # first conv + first SpecBlock + the whole first stage in one launch: the first turn of the stage loop below
     elif fuse_pre:
         # first conv + first SpecBlock in one launch: the [64 x T] tensor between them never exists
         x = ops.spec_block_conv_pre(wav, sb0.fused[0], sb0.fused[1], sb0.fused[2], sb0.bias, es.pre_w, es.pre_b,
@@ -510,45 +549,29 @@ def run_encoder(es: EncoderSpec, wav: Tensor, caches: Optional[Sequence[Tensor]]
         return _spec_branch(sb, wav, wav_hist)
 
     for si, st in enumerate(es.stages):
-        if fuse_stage0 and si == 0:
-            if streaming:
-                # a hop's first conv + first SpecBlock + first stage (streaming.py:490-511) in one launch, with the waveform cache in front
-                # of every stream's t = 0, the blocks' caches and the down-sampling layer's
-                nb0 = len(st.blocks)
-                x, cs_, c = ops.encoder_stage0(
-                    wav, (sb0.fused[0], sb0.fused[1], sb0.fused[2], sb0.bias, es.pre_w, es.pre_b, es.pre_in_scale, sb0.mean, sb0.std,
-                          sb0.normalize, sb0.out_scale),
-                    blocks0, (st.down_lo, st.down_hi, st.down_dw_w, st.down_dw_b, st.down_in_scale, st.ratio),
-                    res=branch_of(later[0]) if defer else None,
-                    hist=[caches[ci + 2 * i: ci + 2 * i + 2] for i in range(nb0)],
-                    hist_out=[caches_out[ci + 2 * i: ci + 2 * i + 2] for i in range(nb0)] if caches_out is not None else None,
-                    down_hist=caches[ci + 2 * nb0], down_hist_out=out(ci + 2 * nb0), wav_hist=wav_hist)
-                new_caches.extend(cs_)
-                new_caches.append(c)
-            ci += 2 * len(st.blocks) + 1
-            continue
+        stage0 = fuse_stage0 and si == 0
         if not (fuse_pre and si == 0) and not (defer and si > 0):
             x = _spec_block(st.spec, x, wav, wav_hist)
         nxt = later[si] if defer else None
         nb = len(st.blocks)
-        if (FUSE_RESBLOCK and opts.stage_launches and st.down_lo is not None and st.down_dw_b is not None
-                and st.down_dw_w.shape[1] == 2 * st.ratio and x.shape[2] % st.ratio == 0 and (not streaming or FUSE_STREAM)
-                and all(rb.pw1_chain is not None and rb.dw1_w.shape[1] == 5 and rb.dw2_w.shape[1] == 5 and rb.dw1_b is not None
-                        and rb.dw2_b is not None for rb in st.blocks)
-                and (x.shape[1] <= FUSE_RESBLOCK_MAX_C or opts.wide_blocks)
-                and ops.encoder_stage_supported(x.shape[1], x.shape[2], nb, st.ratio, x.shape[0], streaming)):
-            # the whole stage — its residual blocks and its down-sampling layer — is one launch; the stage's output never reaches HBM
-            blocks = [(rb.pw1_chain, rb.dw1_w, rb.dw1_b, rb.pw2_chain, rb.dw2_w, rb.dw2_b, rb.pre_scale, rb.out_scale) for rb in st.blocks]
-            down = (st.down_lo, st.down_hi, st.down_dw_w, st.down_dw_b, st.down_in_scale, st.ratio)
+        if stage0 or _enc_stage_fusable(st, x, streaming, opts):
+            # the whole stage — its residual blocks and its down-sampling layer — is one launch; the stage's output never reaches HBM.
+            # Stage 0 with the first conv and its SpecBlock in front (offline: seanet.py:368-378; a hop: streaming.py:490-511, with the
+            # waveform cache in front of every stream's t = 0): neither the [64 x T] tensor in front of the stage nor the one behind its
+            # blocks ever exists.  A hop launches it here, not above, so that the side branches have been forked by now.
+            blocks, down = [rb.chain_args for rb in st.blocks], _down_args(st)
+            state = dict(res=branch_of(nxt) if defer else None, hist=_pairs(caches, ci, nb), hist_out=_pairs(caches_out, ci, nb),
+                         down_hist=caches[ci + 2 * nb] if streaming else None, down_hist_out=out(ci + 2 * nb))
+            if stage0:
+                r = ops.encoder_stage0(wav, _spec0_args(es), blocks, down, wav_hist=wav_hist, **state)
+            else:
+                r = ops.encoder_stage(x, blocks, down, **state)
             if streaming:
-                x, cs_, c = ops.encoder_stage(
-                    x, blocks, down, hist=[caches[ci + 2 * i: ci + 2 * i + 2] for i in range(nb)],
-                    hist_out=[caches_out[ci + 2 * i: ci + 2 * i + 2] for i in range(nb)] if caches_out is not None else None,
-                    down_hist=caches[ci + 2 * nb], down_hist_out=out(ci + 2 * nb), res=branch_of(nxt) if defer else None)
+                x, cs_, c = r
                 new_caches.extend(cs_)
                 new_caches.append(c)
             else:
-                x = ops.encoder_stage(x, blocks, down)
+                x = r
             ci += 2 * nb + 1
             continue
         x = _stage_blocks(st.blocks, x, caches, ci, new_caches, caches_out, opts)
@@ -618,71 +641,55 @@ def run_decoder(ds: DecoderSpec, q: Tensor, caches: Optional[Sequence[Tensor]] =
         x = ops.dw_conv(h, ds.pre_dw_w, ds.pre_dw_b)
     ci = 1
     for st in ds.stages:
-        fused_up = FUSE_UPSAMPLE and (x.shape[2] * st.ratio) % 4 == 0
-        if (streaming and FUSE_STREAM and FUSE_RESBLOCK and opts.stage_launches
-                and (opts.decoder_stage_narrow if st.pw_wt.shape[1] <= FUSE_RESBLOCK_MAX_C else opts.wide_blocks)
-                and _stage_fusable_blocks(st, x, True, opts.decoder_stage_narrow) > 0):
-            # the whole stage — up-sampling layer and residual blocks — is one launch; the tensor between them never exists
-            # (C = 384: the up-sampling layer and the FIRST block; the other two follow as launches of their own)
-            nb = _stage_fusable_blocks(st, x, True, opts.decoder_stage_narrow)
-            up_w = st.tr_w if st.taps is None else st.taps
-            if (st is ds.stages[-1] and nb == len(st.blocks) and ds.post_w.dim() == 2 and ds.post_w.shape[0] == st.pw_wt.shape[1]
-                    and ops.decoder_stage_post_supported(st.pw_wt.shape[1], x.shape[2] * st.ratio, nb, st.ratio, ds.post_w.shape[1])):
-                # the LAST stage and the closing conv (streaming.py:639-648) in one launch: the stage's output — the hop's largest tensor —
-                # is neither written nor read; the conv's cache is read at a stream's t = 0 and written by its last column group
+        width, t = st.pw_wt.shape[1], x.shape[2] * st.ratio
+        nb = 0
+        if ((FUSE_STREAM if streaming else FUSE_UPSAMPLE) and FUSE_RESBLOCK and opts.stage_launches
+                and (opts.decoder_stage_narrow if width <= FUSE_RESBLOCK_MAX_C else opts.wide_blocks)):
+            nb = _stage_fusable_blocks(st, x, streaming, opts.decoder_stage_narrow)
+        if nb > 0:
+            # the stage — up-sampling layer and residual blocks — is one launch; the tensor between them never exists.  Where LDS holds
+            # one block only behind the up-sampling phase (a hop's C = 384, the offline model's C = 768) the other blocks follow as
+            # launches of their own.
+            up, blocks = _up_args(st), [rb.chain_args for rb in st.blocks[:nb]]
+            hist, hist_out = _pairs(caches, ci + 1, nb), _pairs(caches_out, ci + 1, nb)
+            up_hist = caches[ci] if streaming else None
+            if (st is ds.stages[-1] and nb == len(st.blocks) and ds.post_w.dim() == 2 and ds.post_w.shape[0] == width
+                    and ops.decoder_stage_post_supported(width, t, nb, st.ratio, ds.post_w.shape[1])):
+                # the LAST stage and the closing conv (seanet.py:453-476, streaming.py:639-648) in one launch: the stage's [B, C, T] output
+                # — the step's largest tensor — is neither written nor read; a hop reads the conv's cache at a stream's t = 0 and
+                # writes it from its last column group
                 cp = ci + 1 + 2 * nb
-                wav, cs_, c, cpost = ops.decoder_stage_post(
-                    x, (up_w, st.up_lo, st.up_hi, st.pw_b, st.in_scale, st.ratio),
-                    [(rb.pw1_chain, rb.dw1_w, rb.dw1_b, rb.pw2_chain, rb.dw2_w, rb.dw2_b, rb.pre_scale, rb.out_scale) for rb in st.blocks],
-                    (ds.post_w, ds.post_b, ds.post_in_scale, ds.post_out_scale, ds.tanh),
-                    [caches[ci + 1 + 2 * i: ci + 3 + 2 * i] for i in range(nb)], caches[ci], caches[cp],
-                    [caches_out[ci + 1 + 2 * i: ci + 3 + 2 * i] for i in range(nb)] if caches_out is not None else None, out(ci), out(cp))
-                new_caches.append(c)
+                r = ops.decoder_stage_post(x, up, blocks, _post_args(ds), hist, up_hist, caches[cp] if streaming else None,
+                                           hist_out, out(ci), out(cp))
+                if not streaming:
+                    return r
+                wav, cs_, cu, cpost = r
+                new_caches.append(cu)
                 new_caches.extend(cs_)
                 new_caches.append(cpost)
                 return wav, new_caches
-            x, cs_, c = ops.decoder_stage(
-                x, (up_w, st.up_lo, st.up_hi, st.pw_b, st.in_scale, st.ratio),
-                [(rb.pw1_chain, rb.dw1_w, rb.dw1_b, rb.pw2_chain, rb.dw2_w, rb.dw2_b, rb.pre_scale, rb.out_scale) for rb in st.blocks[:nb]],
-                [caches[ci + 1 + 2 * i: ci + 3 + 2 * i] for i in range(nb)], caches[ci],
-                [caches_out[ci + 1 + 2 * i: ci + 3 + 2 * i] for i in range(nb)] if caches_out is not None else None, out(ci))
-            new_caches.append(c)
-            new_caches.extend(cs_)
+            r = ops.decoder_stage(x, up, blocks, hist, up_hist, hist_out, out(ci))
+            if streaming:
+                x, cs_, cu = r
+                new_caches.append(cu)
+                new_caches.extend(cs_)
+            else:
+                x = r
             ci += 1 + 2 * nb
             if nb < len(st.blocks):
                 x = _stage_blocks(st.blocks[nb:], x, caches, ci, new_caches, caches_out, opts)
                 ci += 2 * (len(st.blocks) - nb)
             continue
-        elif streaming and FUSE_STREAM and (x.shape[2] * st.ratio) % 4 == 0:
-            x, c = ops.up_conv(x, st.tr_w, st.pw_wt, st.pw_b, st.ratio, in_scale=st.in_scale, in_elu=True,
-                               hist=caches[ci], want_hist=True, taps=st.taps, hist_out=out(ci))
-            new_caches.append(c)
+        if streaming and FUSE_STREAM and t % 4 == 0:
+            x, cu = ops.up_conv(x, st.tr_w, st.pw_wt, st.pw_b, st.ratio, in_scale=st.in_scale, in_elu=True,
+                                hist=caches[ci], want_hist=True, taps=st.taps, hist_out=out(ci))
+            new_caches.append(cu)
         elif streaming:
-            u, c = ops.dw_convtr(x, st.tr_w, st.ratio, hist=caches[ci], want_hist=True,
-                                 in_scale=st.in_scale, in_elu=True, hist_out=out(ci))
-            new_caches.append(c)
+            u, cu = ops.dw_convtr(x, st.tr_w, st.ratio, hist=caches[ci], want_hist=True,
+                                  in_scale=st.in_scale, in_elu=True, hist_out=out(ci))
+            new_caches.append(cu)
             x = ops.pw_conv(u, st.pw_wt, st.pw_b)
-        elif (not streaming and FUSE_RESBLOCK and FUSE_UPSAMPLE and opts.stage_launches
-              and (opts.decoder_stage_narrow if st.pw_wt.shape[1] <= FUSE_RESBLOCK_MAX_C else opts.wide_blocks)
-              and _stage_fusable_blocks(st, x, False, opts.decoder_stage_narrow) > 0):
-            # (the widest stage, C = 768: its carry slots leave LDS room for ONE block behind the up-sampling phase; the other blocks follow)
-            nb = _stage_fusable_blocks(st, x, False, opts.decoder_stage_narrow)
-            blocks_ = [(rb.pw1_chain, rb.dw1_w, rb.dw1_b, rb.pw2_chain, rb.dw2_w, rb.dw2_b, rb.pre_scale, rb.out_scale) for rb in st.blocks[:nb]]
-            if (st is ds.stages[-1] and nb == len(st.blocks) and ds.post_w.dim() == 2 and ds.post_w.shape[0] == st.pw_wt.shape[1]
-                    and ops.decoder_stage_post_supported(st.pw_wt.shape[1], x.shape[2] * st.ratio, nb, st.ratio, ds.post_w.shape[1])):
-                # the LAST stage and the closing conv (seanet.py:453-476) in one launch: the stage's [B, C, T] output — the step's largest
-                # tensor — is neither written nor read
-                return ops.decoder_stage_post(
-                    x, (st.tr_w if st.taps is None else st.taps, st.up_lo, st.up_hi, st.pw_b, st.in_scale, st.ratio), blocks_,
-                    (ds.post_w, ds.post_b, ds.post_in_scale, ds.post_out_scale, ds.tanh))
-            x = ops.decoder_stage(
-                x, (st.tr_w if st.taps is None else st.taps, st.up_lo, st.up_hi, st.pw_b, st.in_scale, st.ratio),
-                [(rb.pw1_chain, rb.dw1_w, rb.dw1_b, rb.pw2_chain, rb.dw2_w, rb.dw2_b, rb.pre_scale, rb.out_scale) for rb in st.blocks[:nb]])
-            if nb < len(st.blocks):
-                x = _stage_blocks(st.blocks[nb:], x, None, 0, None, None, opts)
-            ci += 1 + 2 * len(st.blocks)
-            continue
-        elif fused_up:
+        elif FUSE_UPSAMPLE and t % 4 == 0:
             # the up-sampled tensor only exists inside the GEMM's loader
             x = ops.up_conv(x, st.tr_w, st.pw_wt, st.pw_b, st.ratio, in_scale=st.in_scale, in_elu=True, taps=st.taps)
         else:

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import contextlib
 import contextvars
+import ctypes
 import numbers
 from typing import List, Optional, Sequence, Tuple
 
@@ -22,7 +23,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from ._lib import check, lib
+from ._lib import DownParams, PostParams, ResblockParams, Spec0Params, UpParams, check, lib
 
 _LIB = torch.library.Library("hilcodec", "DEF")
 
@@ -288,28 +289,55 @@ _register("resblock", "(Tensor x, Tensor w1p, Tensor dw1_w, Tensor dw1_b, Tensor
           torch.empty_like(x))
 
 
-def _resblock_chain(x, params, hist_in, hist_out, pre_scales, out_scales):
-    from ._lib import ResblockParams
-    B, Cc, T = x.shape
+def _void(obj):
+    """a ctypes struct, or an array of them, as a `const void *` argument of the C ABI"""
+    return ctypes.cast(ctypes.pointer(obj), ctypes.c_void_p)
+
+
+def _block_params(op, B, Cc, streaming, params, hist_in, hist_out, pre_scales, out_scales):
+    """The `hilc_resblock_params` array of a stage launch from the flat lists of the op schemas: 6 parameter tensors per block and
+    (streaming) 2 caches in + 2 caches out per block, each `[B, C, 4]`; offline no cache at all.  The lists are checked as a whole
+    before the first pointer is taken: a kernel indexes them by block and trusts the shapes."""
     n = len(pre_scales)
-    streaming = len(hist_in) > 0                   # no caches: the offline causal model (zero padding in front of every clip)
-    if len(params) != 6 * n or len(out_scales) != n or (streaming and (len(hist_in) != 2 * n or len(hist_out) != 2 * n)) or \
-            (not streaming and len(hist_out) != 0):
-        raise RuntimeError("resblock_chain: 6 parameter tensors per block, and (streaming) 2 caches in and 2 caches out per block")
+    if len(params) != 6 * n or len(out_scales) != n or len(hist_in) != (2 * n if streaming else 0) or len(hist_out) != len(hist_in):
+        raise RuntimeError(f"{op}: 6 parameter tensors per block, and (streaming) 2 caches in and 2 caches out per block")
     for h in list(hist_in) + list(hist_out):
         if tuple(h.shape) != (B, Cc, 4):
-            raise RuntimeError(f"resblock caches must be [{B},{Cc},4], got {tuple(h.shape)}")
+            raise RuntimeError(f"{op}: resblock caches must be [{B},{Cc},4], got {tuple(h.shape)}")
     blocks = (ResblockParams * n)()
     for i in range(n):
-        w1p, d1w, d1b, w2p, d2w, d2b = params[6 * i:6 * i + 6]
-        h = [_ptr(t) for t in (hist_in[2 * i], hist_in[2 * i + 1], hist_out[2 * i], hist_out[2 * i + 1])] if streaming else [None] * 4
-        blocks[i] = ResblockParams(_ptr(w1p), _ptr(d1w), _ptr(d1b), _ptr(w2p), _ptr(d2w), _ptr(d2b), h[0], h[1], h[2], h[3],
-                                   float(pre_scales[i]), float(out_scales[i]))
+        caches = list(hist_in[2 * i:2 * i + 2]) + list(hist_out[2 * i:2 * i + 2]) if streaming else [None] * 4
+        blocks[i] = ResblockParams(*[_ptr(t) for t in list(params[6 * i:6 * i + 6]) + caches], float(pre_scales[i]), float(out_scales[i]))
+    return blocks
+
+
+def _down_params(op, y, w_lo, w_hi, ddw_w, ddw_b, dhist, dhist_out, dres, in_scale, stride):
+    """`hilc_down_params`: the down-sampling layer behind the blocks of an encoder stage launch, writing y `[B, 2C, T / stride]`"""
+    B, C2, To = y.shape
+    for t, shape in ((dhist, (B, C2, stride)), (dhist_out, (B, C2, stride)), (dres, (B, C2, To))):
+        if t is not None and tuple(t.shape) != shape:
+            raise RuntimeError(f"{op}: expected {shape}, got {tuple(t.shape)}")
+    return DownParams(_ptr(w_lo), _ptr(w_hi), _ptr(ddw_w), _ptr(ddw_b), _ptr(dhist), _ptr(dhist_out), _ptr(dres), _ptr(y),
+                      float(in_scale), int(stride))
+
+
+def _up_params(op, xin, tr_w, w_lo, w_hi, bias, uhist, uhist_out, in_scale, stride):
+    """`hilc_up_params`: the up-sampling layer in front of the blocks of a decoder stage launch, reading xin `[B, 2C, T / stride]`"""
+    B, K2, _ = xin.shape
+    for h in (uhist, uhist_out):
+        if h is not None and h.numel() != B * K2:
+            raise RuntimeError(f"{op}: the up-sampling cache must be [{B},{K2},1], got {tuple(h.shape)}")
+    return UpParams(_ptr(xin), _ptr(tr_w), _ptr(w_lo), _ptr(w_hi), _ptr(bias), _ptr(uhist), _ptr(uhist_out), float(in_scale), int(stride))
+
+
+def _resblock_chain(x, params, hist_in, hist_out, pre_scales, out_scales):
+    B, Cc, T = x.shape
+    streaming = len(hist_in) > 0                   # no caches: the offline causal model (zero padding in front of every clip)
+    blocks = _block_params("resblock_chain", B, Cc, streaming, params, hist_in, hist_out, pre_scales, out_scales)
+    n = len(blocks)
     y = torch.empty_like(x)
-    import ctypes
     with _timed("resblock", 4.0 * n * B * T * Cc * Cc, f"C{Cc} T{T}" + (" stream" if streaming else "") + f" chain x{n}"):
-        check(lib.hilc_resblock_chain(_ptr(x), _ptr(y), ctypes.cast(blocks, ctypes.c_void_p), n, int(streaming), B, Cc, T, _stream()),
-              "hilc_resblock_chain")
+        check(lib.hilc_resblock_chain(_ptr(x), _ptr(y), _void(blocks), n, int(streaming), B, Cc, T, _stream()), "hilc_resblock_chain")
     return y
 
 
@@ -320,32 +348,17 @@ _register("resblock_chain", "(Tensor x, Tensor[] params, Tensor[] hist_in, Tenso
 
 def _encoder_stage(x, params, hist_in, hist_out, pre_scales, out_scales, w_lo, w_hi, ddw_w, ddw_b, dhist, dhist_out, dres, in_scale,
                    stride):
-    import ctypes
-    from ._lib import DownParams, ResblockParams
     B, Cc, T = x.shape
-    n = len(pre_scales)
     streaming = dhist_out is not None
-    if len(params) != 6 * n or len(out_scales) != n or len(hist_in) != (2 * n if streaming else 0) or len(hist_out) != len(hist_in):
-        raise RuntimeError("encoder_stage: 6 parameter tensors per block, and (streaming) 2 caches in and 2 caches out per block")
     if T % stride != 0:
         raise RuntimeError("encoder_stage: T must be a multiple of the stride")
-    blocks = (ResblockParams * n)()
-    for i in range(n):
-        w1p, d1w, d1b, w2p, d2w, d2b = params[6 * i:6 * i + 6]
-        h = [_ptr(t) for t in (hist_in[2 * i], hist_in[2 * i + 1], hist_out[2 * i], hist_out[2 * i + 1])] if streaming else [None] * 4
-        blocks[i] = ResblockParams(_ptr(w1p), _ptr(d1w), _ptr(d1b), _ptr(w2p), _ptr(d2w), _ptr(d2b), h[0], h[1], h[2], h[3],
-                                   float(pre_scales[i]), float(out_scales[i]))
-    To = T // stride
-    for t, shape in ((dhist, (B, 2 * Cc, stride)), (dhist_out, (B, 2 * Cc, stride)), (dres, (B, 2 * Cc, To))):
-        if t is not None and tuple(t.shape) != shape:
-            raise RuntimeError(f"encoder_stage: expected {shape}, got {tuple(t.shape)}")
-    y = torch.empty(B, 2 * Cc, To, device=x.device, dtype=torch.float32)
-    down = DownParams(_ptr(w_lo), _ptr(w_hi), _ptr(ddw_w), _ptr(ddw_b), _ptr(dhist), _ptr(dhist_out), _ptr(dres), _ptr(y),
-                      float(in_scale), int(stride))
+    blocks = _block_params("encoder_stage", B, Cc, streaming, params, hist_in, hist_out, pre_scales, out_scales)
+    n = len(blocks)
+    y = torch.empty(B, 2 * Cc, T // stride, device=x.device, dtype=torch.float32)
+    down = _down_params("encoder_stage", y, w_lo, w_hi, ddw_w, ddw_b, dhist, dhist_out, dres, in_scale, stride)
     tag = f"C{Cc} T{T}" + (" stream" if streaming else "")
     with _timed("resblock", 4.0 * n * B * T * Cc * Cc + 4.0 * B * T * Cc * Cc, tag + f" stage x{n} + down s{stride}"):
-        check(lib.hilc_encoder_stage(_ptr(x), ctypes.cast(blocks, ctypes.c_void_p), n, ctypes.cast(ctypes.pointer(down), ctypes.c_void_p),
-                                     int(streaming), B, Cc, T, _stream()), "hilc_encoder_stage")
+        check(lib.hilc_encoder_stage(_ptr(x), _void(blocks), n, _void(down), int(streaming), B, Cc, T, _stream()), "hilc_encoder_stage")
     return y
 
 
@@ -357,28 +370,15 @@ _register("encoder_stage", "(Tensor x, Tensor[] params, Tensor[] hist_in, Tensor
 
 
 def _decoder_stage(xin, tr_w, w_lo, w_hi, bias, uhist, uhist_out, in_scale, stride, params, hist_in, hist_out, pre_scales, out_scales):
-    import ctypes
-    from ._lib import ResblockParams, UpParams
     B, K2, Tin = xin.shape
     Cc, T = K2 // 2, Tin * stride
-    n = len(pre_scales)
     streaming = len(hist_in) > 0 or uhist_out is not None        # no caches at all: the offline causal model
-    if len(params) != 6 * n or len(out_scales) != n or len(hist_in) != (2 * n if streaming else 0) or len(hist_out) != len(hist_in):
-        raise RuntimeError("decoder_stage: 6 parameter tensors per block, and (streaming) 2 caches in and 2 caches out per block")
-    for h in (uhist, uhist_out):
-        if h is not None and h.numel() != B * K2:
-            raise RuntimeError(f"decoder_stage: the up-sampling cache must be [{B},{K2},1], got {tuple(h.shape)}")
-    blocks = (ResblockParams * n)()
-    for i in range(n):
-        w1p, d1w, d1b, w2p, d2w, d2b = params[6 * i:6 * i + 6]
-        h = [_ptr(t) for t in (hist_in[2 * i], hist_in[2 * i + 1], hist_out[2 * i], hist_out[2 * i + 1])] if streaming else [None] * 4
-        blocks[i] = ResblockParams(_ptr(w1p), _ptr(d1w), _ptr(d1b), _ptr(w2p), _ptr(d2w), _ptr(d2b), h[0], h[1], h[2], h[3],
-                                   float(pre_scales[i]), float(out_scales[i]))
-    up = UpParams(_ptr(xin), _ptr(tr_w), _ptr(w_lo), _ptr(w_hi), _ptr(bias), _ptr(uhist), _ptr(uhist_out), float(in_scale), int(stride))
+    blocks = _block_params("decoder_stage", B, Cc, streaming, params, hist_in, hist_out, pre_scales, out_scales)
+    n = len(blocks)
+    up = _up_params("decoder_stage", xin, tr_w, w_lo, w_hi, bias, uhist, uhist_out, in_scale, stride)
     y = torch.empty(B, Cc, T, device=xin.device, dtype=torch.float32)
     with _timed("resblock", 4.0 * n * B * T * Cc * Cc + 4.0 * B * T * Cc * Cc, f"C{Cc} T{T}" + (" stream" if streaming else "") + f" up r{stride} + stage x{n}"):
-        check(lib.hilc_decoder_stage(ctypes.cast(ctypes.pointer(up), ctypes.c_void_p), ctypes.cast(blocks, ctypes.c_void_p), n, _ptr(y),
-                                     int(streaming), B, Cc, T, _stream()), "hilc_decoder_stage")
+        check(lib.hilc_decoder_stage(_void(up), _void(blocks), n, _ptr(y), int(streaming), B, Cc, T, _stream()), "hilc_decoder_stage")
     return y
 
 
@@ -391,38 +391,24 @@ _register("decoder_stage", "(Tensor xin, Tensor tr_w, Tensor w_lo, Tensor w_hi, 
 
 def _encoder_stage0(wav, wav_hist, dft_packed, nyq_sin, pw_packed, bias, pre_w, pre_b, pre_in_scale, mean, std, normalize, out_scale, params, hist_in,
                     hist_out, pre_scales, out_scales, w_lo, w_hi, ddw_w, ddw_b, dhist, dhist_out, dres, in_scale, stride):
-    import ctypes
-    from ._lib import DownParams, ResblockParams, Spec0Params
     B, one, T = wav.shape
     Cc, k = pre_w.shape
-    n = len(pre_scales)
     streaming = dhist_out is not None
-    if one != 1 or Cc != 64 or len(params) != 6 * n or len(out_scales) != n or T % stride != 0:
-        raise RuntimeError("encoder_stage0: wav [B,1,T], a 64-channel first conv, 6 parameter tensors per block, T a multiple of the stride")
-    if len(hist_in) != (2 * n if streaming else 0) or len(hist_out) != len(hist_in):
-        raise RuntimeError("encoder_stage0: (streaming) 2 caches in and 2 caches out per block")
+    if one != 1 or Cc != 64 or T % stride != 0:
+        raise RuntimeError("encoder_stage0: wav [B,1,T], a 64-channel first conv, T a multiple of the stride")
     if wav_hist is not None and (wav_hist.shape[0] != B or wav_hist.numel() // B < 63):
         raise RuntimeError(f"encoder_stage0: the waveform history must be [{B},1,>=63], got {tuple(wav_hist.shape)}")
-    blocks = (ResblockParams * n)()
-    for i in range(n):
-        w1p, d1w, d1b, w2p, d2w, d2b = params[6 * i:6 * i + 6]
-        h = [_ptr(t) for t in (hist_in[2 * i], hist_in[2 * i + 1], hist_out[2 * i], hist_out[2 * i + 1])] if streaming else [None] * 4
-        blocks[i] = ResblockParams(_ptr(w1p), _ptr(d1w), _ptr(d1b), _ptr(w2p), _ptr(d2w), _ptr(d2b), h[0], h[1], h[2], h[3],
-                                   float(pre_scales[i]), float(out_scales[i]))
-    To = T // stride
-    for t, shape in ((dhist, (B, 2 * Cc, stride)), (dhist_out, (B, 2 * Cc, stride)), (dres, (B, 2 * Cc, To))):
-        if t is not None and tuple(t.shape) != shape:
-            raise RuntimeError(f"encoder_stage0: expected {shape}, got {tuple(t.shape)}")
-    y = torch.empty(B, 2 * Cc, To, device=wav.device, dtype=torch.float32)
+    blocks = _block_params("encoder_stage0", B, Cc, streaming, params, hist_in, hist_out, pre_scales, out_scales)
+    n = len(blocks)
+    y = torch.empty(B, 2 * Cc, T // stride, device=wav.device, dtype=torch.float32)
+    down = _down_params("encoder_stage0", y, w_lo, w_hi, ddw_w, ddw_b, dhist, dhist_out, dres, in_scale, stride)
     wh = wav_hist.reshape(B, -1) if wav_hist is not None else None
     spec = Spec0Params(_ptr(wav), _ptr(dft_packed), _ptr(nyq_sin), _ptr(pw_packed), _ptr(bias), _ptr(pre_w), _ptr(pre_b),
                        _ptr(wh), int(wh.shape[1]) if wh is not None else 0, float(pre_in_scale),
                        float(mean), float(std), float(out_scale), int(normalize), 64, 1, int(pre_w.shape[1]))
-    down = DownParams(_ptr(w_lo), _ptr(w_hi), _ptr(ddw_w), _ptr(ddw_b), _ptr(dhist), _ptr(dhist_out), _ptr(dres), _ptr(y), float(in_scale), int(stride))
     work = 2.0 * B * T * 64 * (64 + 1 + 32 + 1) + 2.0 * B * T * Cc * k + 4.0 * n * B * T * Cc * Cc + 4.0 * B * T * Cc * Cc
     with _timed("resblock", work, f"C{Cc} T{T}" + (" stream" if streaming else "") + f" conv_pre + spec N64 + stage x{n} + down s{stride}"):
-        check(lib.hilc_encoder_stage0(ctypes.cast(ctypes.pointer(spec), ctypes.c_void_p), ctypes.cast(blocks, ctypes.c_void_p), n,
-                                      ctypes.cast(ctypes.pointer(down), ctypes.c_void_p), int(streaming), B, T, _stream()), "hilc_encoder_stage0")
+        check(lib.hilc_encoder_stage0(_void(spec), _void(blocks), n, _void(down), int(streaming), B, T, _stream()), "hilc_encoder_stage0")
     return y
 
 
@@ -437,35 +423,22 @@ _register("encoder_stage0", "(Tensor wav, Tensor? wav_hist, Tensor dft_packed, T
 
 def _decoder_stage_post(xin, tr_w, w_lo, w_hi, bias, uhist, uhist_out, in_scale, stride, params, hist_in, hist_out, pre_scales, out_scales,
                         post_w, post_b, post_hist, post_hist_out, post_in_scale, post_out_scale, do_tanh):
-    import ctypes
-    from ._lib import PostParams, ResblockParams, UpParams
     B, K2, Tin = xin.shape
     Cc, T = K2 // 2, Tin * stride
-    n = len(pre_scales)
     streaming = len(hist_in) > 0 or uhist_out is not None or post_hist_out is not None      # no caches at all: the offline causal model
-    if len(params) != 6 * n or len(out_scales) != n or len(hist_in) != (2 * n if streaming else 0) or len(hist_out) != len(hist_in):
-        raise RuntimeError("decoder_stage_post: 6 parameter tensors per block, and (streaming) 2 caches in and 2 caches out per block")
     if post_w.dim() != 2 or post_w.shape[0] != Cc:
         raise RuntimeError(f"decoder_stage_post: the closing conv's taps must be [{Cc}, k], got {tuple(post_w.shape)}")
-    for h in (uhist, uhist_out):
-        if h is not None and h.numel() != B * K2:
-            raise RuntimeError(f"decoder_stage_post: the up-sampling cache must be [{B},{K2},1], got {tuple(h.shape)}")
     for h in (post_hist, post_hist_out):
         if h is not None and tuple(h.shape) != (B, Cc, post_w.shape[1] - 1):
             raise RuntimeError(f"decoder_stage_post: the closing conv's cache must be [{B},{Cc},{post_w.shape[1] - 1}], got {tuple(h.shape)}")
-    blocks = (ResblockParams * n)()
-    for i in range(n):
-        w1p, d1w, d1b, w2p, d2w, d2b = params[6 * i:6 * i + 6]
-        h = [_ptr(t) for t in (hist_in[2 * i], hist_in[2 * i + 1], hist_out[2 * i], hist_out[2 * i + 1])] if streaming else [None] * 4
-        blocks[i] = ResblockParams(_ptr(w1p), _ptr(d1w), _ptr(d1b), _ptr(w2p), _ptr(d2w), _ptr(d2b), h[0], h[1], h[2], h[3],
-                                   float(pre_scales[i]), float(out_scales[i]))
-    up = UpParams(_ptr(xin), _ptr(tr_w), _ptr(w_lo), _ptr(w_hi), _ptr(bias), _ptr(uhist), _ptr(uhist_out), float(in_scale), int(stride))
+    blocks = _block_params("decoder_stage_post", B, Cc, streaming, params, hist_in, hist_out, pre_scales, out_scales)
+    n = len(blocks)
+    up = _up_params("decoder_stage_post", xin, tr_w, w_lo, w_hi, bias, uhist, uhist_out, in_scale, stride)
     wav = torch.empty(B, 1, T, device=xin.device, dtype=torch.float32)
     post = PostParams(_ptr(post_w), _ptr(post_b), _ptr(wav), _ptr(post_hist), _ptr(post_hist_out), float(post_in_scale), float(post_out_scale),
                       int(do_tanh), int(post_w.shape[1]))
     with _timed("resblock", 4.0 * n * B * T * Cc * Cc + 4.0 * B * T * Cc * Cc, f"C{Cc} T{T}" + (" stream" if streaming else "") + f" up r{stride} + stage x{n} + conv_post"):
-        check(lib.hilc_decoder_stage_post(ctypes.cast(ctypes.pointer(up), ctypes.c_void_p), ctypes.cast(blocks, ctypes.c_void_p), n,
-                                          ctypes.cast(ctypes.pointer(post), ctypes.c_void_p), int(streaming), B, Cc, T, _stream()), "hilc_decoder_stage_post")
+        check(lib.hilc_decoder_stage_post(_void(up), _void(blocks), n, _void(post), int(streaming), B, Cc, T, _stream()), "hilc_decoder_stage_post")
     return wav
 
 
@@ -1238,29 +1211,35 @@ def resblock_chain_pack(wt: Tensor, streaming: bool = True) -> Tensor:
     return _OPS.resblock_pack_rc(wt, resblock_chain_row_classes(wt.shape[0], streaming))
 
 
+def _flatten_blocks(x: Tensor, Cc: int, blocks: Sequence[Sequence], hist, hist_out):
+    """The per-block arguments of a stage op -> the flat lists of its schema (params, hist_in, hist_out, pre_scales, out_scales):
+    `blocks[i]` = (w1p, dw1_w, dw1_b, w2p, dw2_w, dw2_b, pre_scale, out_scale), `hist[i]` = that block's two caches, `hist_out[i]` =
+    where its new caches `[B, C, 4]` go (None: fresh tensors).  hist None, the offline model, leaves both cache lists empty."""
+    B = x.shape[0]
+    params, hin, hout, pre, out = [], [], [], [], []
+    for i, blk in enumerate(blocks):
+        if len(blk) != 8:
+            raise RuntimeError("a block is (w1p, dw1_w, dw1_b, w2p, dw2_w, dw2_b, pre_scale, out_scale)")
+        params.extend(blk[:6])
+        pre.append(float(blk[6]))
+        out.append(float(blk[7]))
+        if hist is not None:
+            hin.extend(hist[i])
+            given = hist_out[i] if hist_out is not None and hist_out[i] is not None else (None, None)
+            hout.extend([_state_out(given[0], x, B, Cc, 4), _state_out(given[1], x, B, Cc, 4)])
+    return params, hin, hout, pre, out
+
+
 def resblock_chain(x: Tensor, blocks: Sequence[Sequence], hist: Optional[Sequence[Sequence[Tensor]]] = None,
                    hist_out: Optional[Sequence[Optional[Sequence[Tensor]]]] = None):
     """The residual blocks of ONE stage of a streaming hop in one launch (hilc_resblock_chain): `blocks[i]` =
     (w1p, dw1_w, dw1_b, w2p, dw2_w, dw2_b, pre_scale, out_scale) with w1p / w2p packed by `resblock_chain_pack`, `hist[i]` =
     that block's two caches, `hist_out[i]` = where its new caches go (None: fresh tensors).  Returns (y, [new caches of block 0,
-    of block 1, ...]) — equal, bit for bit, to the blocks launched one by one."""
-    B, Cc, _ = x.shape
-    params, hin, hout, pre, post = [], [], [], [], []
-    if hist is None:            # offline: (w1p, ...) packed with resblock_chain_pack(w, streaming=False); returns y only
-        for blk in blocks:
-            params.extend(blk[:6])
-            pre.append(float(blk[6]))
-            post.append(float(blk[7]))
-        return _OPS.resblock_chain(x, params, [], [], pre, post)
-    for i, blk in enumerate(blocks):
-        params.extend(blk[:6])
-        pre.append(float(blk[6]))
-        post.append(float(blk[7]))
-        hin.extend(hist[i])
-        given = hist_out[i] if hist_out is not None and hist_out[i] is not None else (None, None)
-        hout.extend([_state_out(given[0], x, B, Cc, 4), _state_out(given[1], x, B, Cc, 4)])
+    of block 1, ...]) — equal, bit for bit, to the blocks launched one by one.  hist None: the offline model (w1p / w2p packed with
+    `resblock_chain_pack(w, streaming=False)`) -> y only."""
+    params, hin, hout, pre, post = _flatten_blocks(x, x.shape[1], blocks, hist, hist_out)
     y = _OPS.resblock_chain(x, params, hin, hout, pre, post)
-    return y, hout
+    return y if hist is None else (y, hout)
 
 
 def decoder_stage_supported(C: int, T: int, nblk: int, stride: int, B: int = 1, streaming: bool = True) -> bool:
@@ -1283,25 +1262,13 @@ def decoder_stage(xin: Tensor, up: Sequence, blocks: Sequence[Sequence], hist: O
     `resblock_chain_pack` — and its residual blocks (`blocks[i]`, `hist[i]`, `hist_out[i]` as in `resblock_chain`).
     xin `[B,2C,T/r]`, up_hist `[B,2C,1]` -> (y `[B,C,T]`, [block caches...], up-sampling cache); hist None: the offline model -> y."""
     B, K2, _ = xin.shape
-    Cc = K2 // 2
     tr_w, w_lo, w_hi, bias, in_scale, stride = up
-    params, hin, hout, pre, post = [], [], [], [], []
-    if hist is None:                 # offline: y only
-        for blk in blocks:
-            params.extend(blk[:6])
-            pre.append(float(blk[6]))
-            post.append(float(blk[7]))
-        return _OPS.decoder_stage(xin, tr_w, w_lo, w_hi, bias, None, None, float(in_scale), int(stride), params, [], [], pre, post)
-    for i, blk in enumerate(blocks):
-        params.extend(blk[:6])
-        pre.append(float(blk[6]))
-        post.append(float(blk[7]))
-        hin.extend(hist[i])
-        given = hist_out[i] if hist_out is not None and hist_out[i] is not None else (None, None)
-        hout.extend([_state_out(given[0], xin, B, Cc, 4), _state_out(given[1], xin, B, Cc, 4)])
-    uout = _state_out(up_hist_out, xin, B, K2, 1)
-    y = _OPS.decoder_stage(xin, tr_w, w_lo, w_hi, bias, up_hist, uout, float(in_scale), int(stride), params, hin, hout, pre, post)
-    return y, hout, uout
+    streaming = hist is not None
+    params, hin, hout, pre, post = _flatten_blocks(xin, K2 // 2, blocks, hist, hist_out)
+    uout = _state_out(up_hist_out, xin, B, K2, 1) if streaming else None
+    y = _OPS.decoder_stage(xin, tr_w, w_lo, w_hi, bias, up_hist if streaming else None, uout, float(in_scale), int(stride),
+                           params, hin, hout, pre, post)
+    return (y, hout, uout) if streaming else y
 
 
 def encoder_stage0_supported(T: int, nblk: int, stride: int, n_fft: int, hop: int, pre_ksize: int, B: int = 1, streaming: bool = False) -> bool:
@@ -1323,22 +1290,13 @@ def encoder_stage0(wav: Tensor, spec: Sequence, blocks: Sequence[Sequence], down
     dft, nyq, pw, bias, pre_w, pre_b, pre_in, mean, std, normalize, out_scale = spec
     w_lo, w_hi, ddw_w, ddw_b, in_scale, stride = down
     B, Cc = wav.shape[0], pre_w.shape[0]
-    params, hin, hout, pre, post = [], [], [], [], []
-    for i, blk in enumerate(blocks):
-        params.extend(blk[:6])
-        pre.append(float(blk[6]))
-        post.append(float(blk[7]))
-        if hist is not None:
-            hin.extend(hist[i])
-            given = hist_out[i] if hist_out is not None and hist_out[i] is not None else (None, None)
-            hout.extend([_state_out(given[0], wav, B, Cc, 4), _state_out(given[1], wav, B, Cc, 4)])
-    if hist is None:
-        return _OPS.encoder_stage0(wav, None, dft, nyq, pw, bias, pre_w, pre_b, float(pre_in), float(mean), float(std), int(normalize), float(out_scale),
-                                   params, [], [], pre, post, w_lo, w_hi, ddw_w, ddw_b, None, None, res, float(in_scale), int(stride))
-    dout = _state_out(down_hist_out, wav, B, 2 * Cc, int(stride))
-    y = _OPS.encoder_stage0(wav, wav_hist, dft, nyq, pw, bias, pre_w, pre_b, float(pre_in), float(mean), float(std), int(normalize), float(out_scale),
-                            params, hin, hout, pre, post, w_lo, w_hi, ddw_w, ddw_b, down_hist, dout, res, float(in_scale), int(stride))
-    return y, hout, dout
+    streaming = hist is not None
+    params, hin, hout, pre, post = _flatten_blocks(wav, Cc, blocks, hist, hist_out)
+    dout = _state_out(down_hist_out, wav, B, 2 * Cc, int(stride)) if streaming else None
+    y = _OPS.encoder_stage0(wav, wav_hist if streaming else None, dft, nyq, pw, bias, pre_w, pre_b, float(pre_in), float(mean), float(std),
+                            int(normalize), float(out_scale), params, hin, hout, pre, post, w_lo, w_hi, ddw_w, ddw_b,
+                            down_hist if streaming else None, dout, res, float(in_scale), int(stride))
+    return (y, hout, dout) if streaming else y
 
 
 def decoder_stage_post_supported(C: int, T: int, nblk: int, stride: int, ksize: int) -> bool:
@@ -1356,26 +1314,17 @@ def decoder_stage_post(xin: Tensor, up: Sequence, blocks: Sequence[Sequence], po
     `hist_out` / `up_hist_out` as in `decoder_stage`, `post_hist` `[B,C,4]` = the closing conv's cache ->
     (wav, [block caches...], up-sampling cache, closing conv's cache), equal bit for bit to `decoder_stage` + `conv_post` with the same caches."""
     tr_w, w_lo, w_hi, bias, in_scale, stride = up
+    pw, pb, p_in, p_out, p_tanh = post
     B, K2, _ = xin.shape
     Cc = K2 // 2
-    params, hin, hout, pre, post_s = [], [], [], [], []
-    for i, blk in enumerate(blocks):
-        params.extend(blk[:6])
-        pre.append(float(blk[6]))
-        post_s.append(float(blk[7]))
-        if hist is not None:
-            hin.extend(hist[i])
-            given = hist_out[i] if hist_out is not None and hist_out[i] is not None else (None, None)
-            hout.extend([_state_out(given[0], xin, B, Cc, 4), _state_out(given[1], xin, B, Cc, 4)])
-    pw, pb, p_in, p_out, p_tanh = post
-    if hist is None:
-        return _OPS.decoder_stage_post(xin, tr_w, w_lo, w_hi, bias, None, None, float(in_scale), int(stride), params, [], [], pre, post_s, pw, pb,
-                                       None, None, float(p_in), float(p_out), bool(p_tanh))
-    uout = _state_out(up_hist_out, xin, B, K2, 1)
-    pout = _state_out(post_hist_out, xin, B, Cc, pw.shape[1] - 1)
-    wav = _OPS.decoder_stage_post(xin, tr_w, w_lo, w_hi, bias, up_hist, uout, float(in_scale), int(stride), params, hin, hout, pre, post_s, pw, pb,
-                                  post_hist, pout, float(p_in), float(p_out), bool(p_tanh))
-    return wav, hout, uout, pout
+    streaming = hist is not None
+    params, hin, hout, pre, post_s = _flatten_blocks(xin, Cc, blocks, hist, hist_out)
+    uout = _state_out(up_hist_out, xin, B, K2, 1) if streaming else None
+    pout = _state_out(post_hist_out, xin, B, Cc, pw.shape[1] - 1) if streaming else None
+    wav = _OPS.decoder_stage_post(xin, tr_w, w_lo, w_hi, bias, up_hist if streaming else None, uout, float(in_scale), int(stride),
+                                  params, hin, hout, pre, post_s, pw, pb, post_hist if streaming else None, pout,
+                                  float(p_in), float(p_out), bool(p_tanh))
+    return (wav, hout, uout, pout) if streaming else wav
 
 
 def encoder_stage_supported(C: int, T: int, nblk: int, stride: int, B: int = 1, streaming: bool = True) -> bool:
@@ -1399,20 +1348,12 @@ def encoder_stage(x: Tensor, blocks: Sequence[Sequence], down: Sequence, hist: O
     `res` `[B,2C,T/r]` is added to the output (the next stage's SpecBlock branch)."""
     B, Cc, _ = x.shape
     w_lo, w_hi, ddw_w, ddw_b, in_scale, stride = down
-    params, hin, hout, pre, post = [], [], [], [], []
-    for i, blk in enumerate(blocks):
-        params.extend(blk[:6])
-        pre.append(float(blk[6]))
-        post.append(float(blk[7]))
-        if hist is not None:
-            hin.extend(hist[i])
-            given = hist_out[i] if hist_out is not None and hist_out[i] is not None else (None, None)
-            hout.extend([_state_out(given[0], x, B, Cc, 4), _state_out(given[1], x, B, Cc, 4)])
-    if hist is None:
-        return _OPS.encoder_stage(x, params, [], [], pre, post, w_lo, w_hi, ddw_w, ddw_b, None, None, res, float(in_scale), int(stride))
-    dout = _state_out(down_hist_out, x, B, 2 * Cc, int(stride))
-    y = _OPS.encoder_stage(x, params, hin, hout, pre, post, w_lo, w_hi, ddw_w, ddw_b, down_hist, dout, res, float(in_scale), int(stride))
-    return y, hout, dout
+    streaming = hist is not None
+    params, hin, hout, pre, post = _flatten_blocks(x, Cc, blocks, hist, hist_out)
+    dout = _state_out(down_hist_out, x, B, 2 * Cc, int(stride)) if streaming else None
+    y = _OPS.encoder_stage(x, params, hin, hout, pre, post, w_lo, w_hi, ddw_w, ddw_b, down_hist if streaming else None, dout, res,
+                           float(in_scale), int(stride))
+    return (y, hout, dout) if streaming else y
 
 
 def resblock_pack(wt: Tensor) -> Tensor:

@@ -910,6 +910,79 @@ def test_encoder_stage0_streaming_equals_conv_pre_spec_then_stage(env, T, B, n):
             assert torch.equal(ca[j][0], cb[j][0]) and torch.equal(ca[j][1], cb[j][1]), (h, j)
 
 
+@pytest.mark.parametrize("op", ["resblock_chain", "encoder_stage", "encoder_stage0", "decoder_stage", "decoder_stage_post"])
+def test_stage_ops_refuse_inconsistent_block_lists_before_launching(env, op):
+    """The five stage ops index their flat parameter / cache lists by block and hand the kernel `[B, C, 4]` caches unchecked: a
+    list that is one cache short, a block cache of another length and a block tuple that is one parameter tensor short each raise
+    RuntimeError BEFORE anything is launched — the caller's state-block destinations still hold their sentinel.  The smallest
+    shape each op takes in a hop."""
+    ops, fold, O, dev = env
+    B = 2
+    encoder = op in ("encoder_stage", "encoder_stage0")
+    C, r, n = (64, 2, 2) if encoder or op == "resblock_chain" else (96, 2, 3)
+    T = {"resblock_chain": 8, "encoder_stage": 128, "encoder_stage0": 128}.get(op, 64 * r)
+    blocks = _stage_params(ops, dev, C, r, n, True)[0]
+    hist = [[torch.zeros(B, C, 4, device=dev), torch.zeros(B, C, 4, device=dev)] for _ in range(n)]
+    outs = [[torch.full((B, C, 4), 9.0, device=dev), torch.full((B, C, 4), 9.0, device=dev)] for _ in range(n)]
+    layer_outs = []                  # the down- / up-sampling layer's and the closing conv's destinations
+
+    def sentinel(*shape):
+        layer_outs.append(torch.full(shape, 9.0, device=dev))
+        return layer_outs[-1]
+
+    if op == "resblock_chain":
+        assert ops.resblock_chain_supported(C, T, n, B)
+        x = rnd(1, B, C, T).to(dev)
+
+        def call(blocks, hist):
+            return ops.resblock_chain(x, blocks, hist, outs)
+    elif encoder:
+        down = _stage_params(ops, dev, C, r, n, True)[5]
+        dh, dho = torch.zeros(B, 2 * C, r, device=dev), sentinel(B, 2 * C, r)
+        if op == "encoder_stage":
+            assert ops.encoder_stage_supported(C, T, n, r, B)
+            x = rnd(1, B, C, T).to(dev)
+
+            def call(blocks, hist):
+                return ops.encoder_stage(x, blocks, down, hist=hist, hist_out=outs, down_hist=dh, down_hist_out=dho)
+        else:
+            assert ops.encoder_stage0_supported(T, n, r, 64, 1, 5, B, True) and not ops.encoder_stage0_supported(T - 4, n, r, 64, 1, 5, B, True)
+            wt = fold.pointwise_layout(rnd(65, C, 33, 1) / 33 ** 0.5).to(dev)
+            spec = tuple(ops.spec_block_tables(fold.stft_basis_layout(synth.stft_basis(64)).to(dev), wt, 64)) + (
+                None, (rnd(71, 64, 5) * 0.5).to(dev), None, 1.0, -4.0, 2.8, True, 0.37)
+            wav = synth.synth_clips(B, T, seed=3).to(dev)
+
+            def call(blocks, hist):
+                return ops.encoder_stage0(wav, spec, blocks, down, hist=hist, hist_out=outs, down_hist=dh, down_hist_out=dho)
+    else:
+        assert ops.decoder_stage_supported(C, T, n, r, B) and ops.decoder_stage_post_supported(C, T, n, r, 5)
+        wu = (rnd(81, 2 * C, C) / (2 * C) ** 0.5).to(dev)
+        up = ((rnd(80, 2 * C, 2 * r) * 0.3).to(dev), ops.resblock_chain_pack(wu[:C].contiguous()), ops.resblock_chain_pack(wu[C:].contiguous()),
+              (rnd(82, C) * 0.1).to(dev), 0.7071, r)
+        xin = rnd(1, B, 2 * C, T // r).to(dev)
+        uh, uho = torch.zeros(B, 2 * C, 1, device=dev), sentinel(B, 2 * C, 1)
+        if op == "decoder_stage":
+            def call(blocks, hist):
+                return ops.decoder_stage(xin, up, blocks, hist, uh, outs, uho)
+        else:
+            post = ((rnd(83, C, 5) * 0.2).to(dev), None, 0.5, 0.1122, True)
+            ph, pho = torch.zeros(B, C, 4, device=dev), sentinel(B, C, 4)
+
+            def call(blocks, hist):
+                return ops.decoder_stage_post(xin, up, blocks, post, hist, uh, ph, outs, uho, pho)
+
+    one_short = hist[:-1] + [hist[-1][:1]]
+    wrong_len = hist[:-1] + [[hist[-1][0], torch.zeros(B, C, 3, device=dev)]]
+    short_block = blocks[:-1] + [blocks[-1][:4] + blocks[-1][5:]]
+    for bad_blocks, bad_hist, what in ((blocks, one_short, "2 caches in and 2 caches out per block"), (blocks, wrong_len, "caches must be"),
+                                       (short_block, hist, "a block is")):
+        with pytest.raises(RuntimeError, match=what):
+            call(bad_blocks, bad_hist)
+    torch.cuda.synchronize()
+    for t in [t for pair in outs for t in pair] + layer_outs:
+        assert torch.equal(t, torch.full_like(t, 9.0))
+
+
 def test_resblock_chain_shapes_it_does_not_take(env):
     ops, fold, O, dev = env
     from hilcodec_amd._lib import lib

@@ -1,0 +1,199 @@
+"""CPU: the PLAN — which `torch.ops.hilcodec.*` ops `engine.run_encoder` / `engine.run_decoder` dispatch, in which order and with
+which argument in which position — pinned against `tests/golden/plan_trace.json`.  The specs live on the meta device, so no kernel
+is launched and the real batch sizes are free (B = 640 takes the clip chunks, B = 1024 the 32-bit-offset predicates).
+
+Every tensor argument is recorded by WHERE IT CAME FROM (a field of the spec, the waveform, cache i in / out, output j of op k), so a
+cache mix-up — two caches of a block swapped, an offset off by one — changes the trace although every shape stays right.  The
+scenarios are those of `tools/launch_table.py`; each streaming one is walked with fresh caches and with a state block
+(`caches_out`), and two more use a 960-sample hop.
+
+  python tests/test_plan_cpu.py --dump DIR      one JSON file of full rows per scenario (diff two trees when a hash differs)
+  python tests/test_plan_cpu.py --write         rewrite the fixture from THIS tree (only for a change that is meant to move the plan)"""
+import dataclasses
+import functools
+import hashlib
+import importlib.util
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if __name__ == "__main__":
+    sys.path.insert(0, ROOT)
+
+import pytest
+import torch
+from torch.utils._python_dispatch import TorchDispatchMode
+from torch.utils._pytree import tree_leaves
+
+import hilcodec_amd
+from hilcodec_amd import engine, synth
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "plan_trace.json")
+
+
+def _launch_table_scenarios():
+    spec = importlib.util.spec_from_file_location("_launch_table", os.path.join(ROOT, "tools", "launch_table.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return dict(mod.SCENARIOS)
+
+
+SCENARIOS = _launch_table_scenarios()       # name: (model, mode, batch, samples per clip / hop, exec options)
+SCENARIOS["streaming hop 960 (3 frames), 1024 streams"] = ("hil_speech", "streaming", 1024, 960, {})
+SCENARIOS["streaming hop 960 (3 frames), 37 streams"] = ("hil_speech", "streaming", 37, 960, {})
+
+# (scenario, state block) — a streaming scenario is walked twice
+CASES = [(name, block) for name, sc in SCENARIOS.items() for block in ((False, True) if sc[1] == "streaming" else (False,))]
+
+
+def _key(name, block):
+    return name + (" [caches_out]" if block else "")
+
+
+@functools.lru_cache(maxsize=None)
+def _specs(model_name, streaming):
+    mk = dict(synth.model_kwargs(model_name))
+    sd = synth.synth_state_dict(model_name, seed=7)
+    if streaming:
+        from hilcodec_amd.models.hilcodec.streaming import HILCodec
+        for k in ("spec_learnable", "causal", "pad_mode"):
+            mk.pop(k)
+        m = HILCodec(24000, **mk).eval()
+        m.load_offline_state_dict(sd)
+        m.remove_weight_reparameterizations()
+    else:
+        m = hilcodec_amd.HILCodec(24000, 1, **mk).eval()
+        m.load_state_dict(sd, strict=False)
+    return tuple(engine.finalize_spec(engine.spec_to(half.build_spec("cpu"), "meta"), streaming=streaming) for half in (m.encoder, m.decoder))
+
+
+class _Recorder(TorchDispatchMode):
+    """rows = [op name, [arguments], {keyword arguments}] of every op that reaches the dispatcher, ATen ones included; a tensor is
+    written as its name, and the outputs of op k are named `#k.j`"""
+
+    def __init__(self):
+        super().__init__()
+        self.names = {}         # id(tensor) -> name
+        self.keep = []          # ... and the tensors themselves: an id must not be handed out twice
+        self.rows = []
+
+    def name(self, t, name):
+        if id(t) not in self.names:
+            self.names[id(t)] = name
+            self.keep.append(t)
+
+    def name_tree(self, obj, path):
+        if isinstance(obj, torch.Tensor):
+            self.name(obj, path)
+        elif isinstance(obj, (list, tuple)):
+            for i, v in enumerate(obj):
+                self.name_tree(v, f"{path}[{i}]")
+        elif dataclasses.is_dataclass(obj):
+            for f in dataclasses.fields(obj):
+                self.name_tree(getattr(obj, f.name), f"{path}.{f.name}")
+
+    def _enc(self, a, where):
+        if isinstance(a, torch.Tensor):
+            assert id(a) in self.names, f"{where}: a tensor {tuple(a.shape)} that is neither a spec field, an input, a cache nor an op's output"
+            return self.names[id(a)]
+        if isinstance(a, (list, tuple)):
+            return [self._enc(v, where) for v in a]
+        return repr(a)
+
+    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        k = len(self.rows)
+        op = func._schema.name.replace("::", ".") + ("." + func._overloadname if func._overloadname else "")
+        where = f"op {k} {op}"
+        self.rows.append([op, [self._enc(a, where) for a in args], {n: self._enc(v, where) for n, v in sorted(kwargs.items())}])
+        out = func(*args, **kwargs)
+        for j, t in enumerate(tree_leaves(out)):
+            if isinstance(t, torch.Tensor):
+                self.name(t, f"#{k}.{j}")
+        return out
+
+
+def trace(name, block):
+    """the rows of one scenario: run_encoder, then run_decoder on what it returned"""
+    model_name, mode, B, T, opts = SCENARIOS[name]
+    streaming = mode == "streaming"
+    es, ds = _specs(model_name, streaming)
+    opts = engine.ExecOptions(**opts)
+    rec = _Recorder()
+    rec.name_tree(es, "es")
+    rec.name_tree(ds, "ds")
+    wav = torch.empty(B, 1, T, device="meta")
+    rec.name(wav, "wav")
+    if not streaming:
+        with rec:
+            z = engine.run_encoder(es, wav, opts=opts)
+            out = engine.run_decoder(ds, z, opts=opts)
+        assert out.shape == (B, 1, -(-T // 320) * 320)          # ceil semantics of the strided layers
+        return rec.rows
+    ce = [torch.empty(B, c, l, device="meta") for c, l in engine.encoder_cache_shapes(es)]
+    cd = [torch.empty(B, c, l, device="meta") for c, l in engine.decoder_cache_shapes(ds)]
+    oe = [torch.empty_like(t) for t in ce] if block else None
+    od = [torch.empty_like(t) for t in cd] if block else None
+    for label, seq in (("ce", ce), ("cd", cd), ("oe", oe), ("od", od)):
+        rec.name_tree(seq, label)
+    with rec:
+        z, ne = engine.run_encoder(es, wav, ce, channel_last_out=True, caches_out=oe, opts=opts)
+        out, nd = engine.run_decoder(ds, z.transpose(1, 2), cd, caches_out=od, opts=opts)
+    assert out.shape == (B, 1, T) and [t.shape for t in ne] == [t.shape for t in ce] and [t.shape for t in nd] == [t.shape for t in cd]
+    if block:        # the contract that caches_out[i] IS the returned cache i
+        assert all(a is b for a, b in zip(ne, oe)) and all(a is b for a, b in zip(nd, od))
+    else:
+        assert all(a is not b for a, b in zip(ne + nd, ce + cd))
+    return rec.rows
+
+
+def _launches(rows):
+    return [r[0][len("hilcodec."):] for r in rows if r[0].startswith("hilcodec.")]
+
+
+def _digest(rows):
+    return hashlib.sha256(json.dumps(rows, sort_keys=True, separators=(",", ":")).encode()).hexdigest()
+
+
+def summary(rows):
+    return {"ops": _launches(rows), "sha256": _digest(rows)}
+
+
+@functools.lru_cache(maxsize=None)
+def _golden():
+    with open(GOLDEN) as f:
+        return json.load(f)
+
+
+def test_fixture_lists_every_case():
+    assert sorted(_golden()) == sorted(_key(n, b) for n, b in CASES)
+
+
+@pytest.mark.parametrize("name,block", CASES, ids=[_key(n, b) for n, b in CASES])
+def test_plan_matches_the_recorded_trace(name, block):
+    rows = trace(name, block)
+    want = _golden()[_key(name, block)]
+    assert _launches(rows) == want["ops"]
+    assert _digest(rows) == want["sha256"], "same ops, another argument: `python tests/test_plan_cpu.py --dump DIR` in both trees and diff"
+
+
+@pytest.mark.parametrize("name,block,count", [
+    ("offline hil_speech B256 T24000", False, 20), ("offline hil_music B256 T24000", False, 20),
+    ("streaming hop 320, 1024 streams", False, 19), ("streaming hop 320, 1024 streams", True, 19)])
+def test_launch_counts_of_the_default_plans(name, block, count):
+    """a whole stage per launch: 20 launches for an offline encoder + decoder pass, 19 for a 320-sample hop"""
+    assert len(_launches(trace(name, block))) == count
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "--dump":
+        os.makedirs(sys.argv[2], exist_ok=True)
+        for i, (n, b) in enumerate(CASES):
+            with open(os.path.join(sys.argv[2], f"{i:02d}.json"), "w") as f:
+                json.dump({"scenario": _key(n, b), "rows": trace(n, b)}, f, indent=0)
+    elif sys.argv[1:] == ["--write"]:
+        with open(GOLDEN, "w") as f:       # one scenario per line
+            f.write("{\n" + ",\n".join(f"{json.dumps(_key(n, b))}: {json.dumps(summary(trace(n, b)), sort_keys=True)}" for n, b in CASES) + "\n}\n")
+    else:
+        sys.exit(__doc__)
