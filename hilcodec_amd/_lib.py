@@ -83,6 +83,7 @@ SIGNATURES = {
     "hilc_jitter_step": [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "hilc_mix_levels": [_p, _p, _p, _i, _i, _p],
     "hilc_mix_rooms": [_p, _p, _p, _i, _p, _p, _i, _i, _p],
+    "hilc_vbr_select": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _p],
 }
 
 ABI_VERSION = 16

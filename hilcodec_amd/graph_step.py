@@ -24,6 +24,7 @@ from torch import Tensor
 
 from . import dtx as dtx_def
 from . import engine, ops, wire
+from . import vbr as vbr_def
 from .jitter import JitterConfig
 from .mixer import MixConfig
 from .resample import BASE_RATE, design, device_taps, hop_samples
@@ -167,6 +168,7 @@ class _Hop:
     gates the public methods and the graph's session kernels)."""
 
     _scratch: Sequence[Tensor] = ()           # per-slot device buffers beside the state blocks: cleared with them (_zero, _load)
+    _scratch_fill: Sequence[Tuple[Tensor, int]] = ()      # those of them whose cleared value is not 0, with that value
 
     def __init__(self, model, batch: int, n: int, device: torch.device, groups: int = 1, sessions: bool = False,
                  max_loads_per_hop: int = 4):
@@ -209,8 +211,13 @@ class _Hop:
         for a, b in self.gstate:
             a.zero_()
             b.zero_()
+        self._clear_scratch()
+
+    def _clear_scratch(self) -> None:
         for t in self._scratch:
             t.zero_()
+        for t, v in self._scratch_fill:
+            t.fill_(v)
 
     def _load(self, cache_enc: Optional[Sequence[Tensor]], cache_dec: Optional[Sequence[Tensor]]) -> None:
         """reset's state part: parity 0, block A zero or the given caches, the scratch buffers zero"""
@@ -218,8 +225,7 @@ class _Hop:
         for (lo, hi), (a, _b) in zip(self.bounds, self.gstate):
             a.load_(None if cache_enc is None else [c[lo:hi] for c in cache_enc],
                     None if cache_dec is None else [c[lo:hi] for c in cache_dec])
-        for t in self._scratch:
-            t.zero_()
+        self._clear_scratch()
 
     def _capture_pair(self, hop, warmup: int):
         """warm `hop(0)` / `hop(1)` up on a side stream (builds every lazily cached table: folded weights, codebooks), zero the
@@ -398,7 +404,8 @@ class GraphedHop(_Hop):
     def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
         """zero history, or resume from caches saved earlier (`wire.save_cache` / `e_in*`, `d_in*`); with sessions also drops
         every queued action, clears every stop and puts every slot back to the default n.  (GraphedEncodeHop: with FEC, no stream
-        has a previous hop afterwards; with DTX, every run counter is 0; with the header, every hop counter is 0)"""
+        has a previous hop afterwards; with DTX, every run counter is 0; with the header, every hop counter is 0; with a VBR
+        cap, every bucket is full)"""
         with torch.no_grad():
             self._load(cache_enc, cache_dec)
             if self.sessions:
@@ -616,11 +623,22 @@ class GraphedEncodeHop(GraphedHop):
     ping-pong pair of int32 counter rows indexed by parity.  A start or a resume restarts a slot's counter at 0 (that hop's packet
     carries h = 0); a held or stopped slot sends nothing and keeps it; a DTX SILENT hop sends nothing but advances it.  `.hop_index`
     (int32 `[B]` device view) is each slot's counter for the next hop; `export` and a resume carry none.  `header=False` captures
-    exactly the graph without the header."""
+    exactly the graph without the header.
+    `vbr` = vbr.VbrConfig(target_db, n_min, cap_kbps, burst_hops) (`hop` a multiple of 320; with `fec_stages` it needs `header=True`:
+    without the header a receiver cannot tell an n-stage packet with a redundant section from a longer plain one): quality-targeted
+    variable bitrate (vbr.py).  Right after the quantiser one hilc_vbr_select measures, per slot, the float64 quantisation error after
+    every stage, picks the fewest stages n_eff in [max(n_min, fec_stages, 1), n_b] whose error is target_db below the energy of the
+    quantiser's input (n_b: the graph's n, or the slot's `start(n=)` / `set_bitrate` ceiling), caps it by the slot's token bucket when
+    `cap_kbps` is given, and sets the rows >= n_eff of `.indices` to -1; the packer, the FEC packer and the header take n_eff in place
+    of the per-stream n, so `nbytes` follows.  `.n_eff` (int32 `[B]`), `.distortion` (float64 `[B, n + 1]`) and, with a cap, `.credit`
+    (int32 `[B]`, bits) are device views like `.indices`.  A `start` or a resume refills a slot's bucket; a held or stopped slot keeps
+    it, reports n_eff = n_b and a zero distortion row; `reset` refills every bucket; `export` and a resume carry no VBR state.  DTX runs
+    after the packer, unchanged: a SID or SILENT hop is still charged what VBR chose.  A receiver gets n from the header (`play()`), or
+    from `wire.packet_n(nbytes, T)` for headerless packets without FEC.  `vbr=None` captures exactly the graph without VBR."""
 
     def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, input_rate: int = BASE_RATE, fec_stages: int = 0,
-                 dtx: Optional[dtx_def.DtxConfig] = None, header: bool = False):
+                 dtx: Optional[dtx_def.DtxConfig] = None, header: bool = False, vbr: Optional[vbr_def.VbrConfig] = None):
         # what the captured chain reads is set up first: GraphedHop's constructor captures it
         self.fec_stages = _fec_stages(fec_stages, n)
         self.header = bool(header)
@@ -642,7 +660,16 @@ class GraphedEncodeHop(GraphedHop):
             self.rs = design(self.input_rate, BASE_RATE)
             self.rs_taps = device_taps(self.rs, device)
             self._history = self.rs.history
-        self._prev = self._run = self._ctr = None
+        if vbr is not None and not isinstance(vbr, vbr_def.VbrConfig):
+            raise ValueError(f"vbr must be a vbr.VbrConfig or None, got {vbr!r}")
+        self.vbr = vbr
+        if vbr is not None:
+            if self.fec_stages and not self.header:
+                raise ValueError("GraphedEncodeHop(vbr=..., fec_stages=m) needs header=True: without the header a receiver cannot tell "
+                                 "an n-stage packet with a redundant section from a longer plain one")
+            self._vbr_lo = min(int(n), vbr_def.floor_stages(vbr, self.fec_stages))
+            self._vbr_bits = vbr_def.bucket_bits(vbr, _whole_frames("GraphedEncodeHop(vbr=...)", hop), self.fec_stages)
+        self._prev = self._run = self._ctr = self._credit = None
         if self.fec_stages:
             # per parity, per slot: valid, then the first m stages x T frames of its last encoded hop (the hop of parity p reads
             # row p and writes row p ^ 1)
@@ -654,11 +681,16 @@ class GraphedEncodeHop(GraphedHop):
         if self.header:
             # per parity, per slot: the hop counter (the hop of parity p reads row p and writes row p ^ 1)
             self._ctr = torch.zeros(2, batch, dtype=torch.int32, device=device)
-        self._scratch = [t for t in (self._prev, self._run, self._ctr) if t is not None]
+        if vbr is not None and vbr.cap_kbps is not None:
+            # per slot: the token bucket's credit in bits (updated in place by hilc_vbr_select once per hop); cleared = full
+            self._credit = torch.full((batch,), self._vbr_bits[2], dtype=torch.int32, device=device)
+            self._scratch_fill = [(self._credit, self._vbr_bits[2])]
+        self._scratch = [t for t in (self._prev, self._run, self._ctr, self._credit) if t is not None]
         super().__init__(model, batch, hop_in, n, device, warmup, 1, sessions, max_loads_per_hop)
         self.queue.n_min = max(1, self.fec_stages)
         self.indices = self.outs[0][0]
         self.kind = self.outs[0][3] if dtx is not None else None
+        self.n_eff, self.distortion = self.outs[0][-2:] if vbr is not None else (None, None)
 
     def _block(self, streams: int) -> StateBlock:
         return StateBlock(self.model, streams, self.device, "enc", self._history)
@@ -681,6 +713,12 @@ class GraphedEncodeHop(GraphedHop):
             with engine.spectra_side_stream(self.spec_side[0]):
                 z, _ = m.encoder(x, *src.codec_enc, cache_out=dst.codec_enc)
             idx = m.quantizer(z, self.n, n_clip=n_clip)
+        n_eff = distortion = None
+        if self.vbr is not None:
+            stage_bits, rate_bits, burst_bits = self._vbr_bits
+            n_eff, distortion = ops.vbr_select(z.contiguous(), idx, m.quantizer._tables(z.device).codebooks, self._vbr_lo, self.vbr.rho,
+                                               stage_bits, rate_bits, burst_bits, n_clip, action, hold, self._credit)
+            n_clip = n_eff
         if self.fec_stages:
             packets, nbytes = ops.pack_codes_10bit_fec(idx, self._prev[p], self._prev[p ^ 1], self.fec_stages, n_clip, action, hold)
         else:
@@ -695,7 +733,16 @@ class GraphedEncodeHop(GraphedHop):
         if self.header:
             packets, nbytes = ops.packet_header(packets, nbytes, self._ctr[p], self._ctr[p ^ 1], self.n, self.fec_stages, self.frames,
                                                 n_clip, kind, action, hold)
-        return (idx, packets, nbytes) if kind is None else (idx, packets, nbytes, kind)
+        out = (idx, packets, nbytes) if kind is None else (idx, packets, nbytes, kind)
+        return out if n_eff is None else out + (n_eff, distortion)
+
+    @property
+    def credit(self) -> Tensor:
+        """int32 `[B]` device view: each slot's token-bucket credit in bits after the last hop (vbr with a cap only).  Read-only:
+        written by the graph."""
+        if self._credit is None:
+            raise RuntimeError("GraphedEncodeHop.credit: construct with vbr=VbrConfig(..., cap_kbps=...)")
+        return self._credit
 
     @property
     def hop_index(self) -> Tensor:
@@ -710,6 +757,8 @@ class GraphedEncodeHop(GraphedHop):
         self.indices, packets, nbytes = out[:3]
         if self.dtx is not None:
             self.kind = out[3]
+        if self.vbr is not None:
+            self.n_eff, self.distortion = out[-2:]
         return packets, nbytes
 
     def start(self, slot: int, cache_enc: Optional[Sequence[Tensor]] = None, n: Optional[int] = None) -> None:

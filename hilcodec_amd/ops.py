@@ -1091,6 +1091,33 @@ def _mix_rooms(wav, room, score, top_k, mixed, speakers):
 _register("mix_rooms", "(Tensor wav, Tensor room, Tensor score, int top_k, Tensor(a!) mixed, Tensor(b!) speakers) -> ()", _mix_rooms,
           lambda wav, room, score, top_k, mixed, speakers: None)
 
+# ======================================================================================================
+# quality-targeted variable bitrate of the sender (graph_step.GraphedEncodeHop(vbr=); definition: hilcodec_amd/vbr.py; semantics:
+# include/hilcodec_amd.h)
+# ======================================================================================================
+def _vbr_select(z, indices, codebooks, n_clip, action, hold, credit, n_lo, rho, stage_bits, rate_bits, burst_bits):
+    if z.dim() != 3 or indices.dim() != 3 or codebooks.dim() != 3 or indices.shape[1:] != z.shape[:2] or codebooks.shape[2] != z.shape[2]:
+        raise RuntimeError("vbr_select: z must be [B, T, C], indices [n, B, T] and codebooks [Nq, K, C]")
+    B, T, Cc = z.shape
+    n = indices.shape[0]
+    Nq, K, _ = codebooks.shape
+    for name, row in (("n_clip", n_clip), ("action", action), ("hold", hold), ("credit", credit)):
+        if row is not None and row.numel() != B:
+            raise RuntimeError(f"vbr_select: {name} needs {B} entries")
+    n_eff = _new(z, B, dtype=torch.int32)
+    distortion = _new(z, B, n + 1, dtype=torch.float64)
+    check(lib.hilc_vbr_select(_ptr(z), _ptr(indices, torch.int64), _ptr(codebooks), _ptr(n_clip, torch.int32), _ptr(action, torch.int32),
+                              _ptr(hold, torch.int32), _ptr(credit, torch.int32), _ptr(n_eff, torch.int32),
+                              _ptr(distortion, torch.float64), B, T, Cc, K, Nq, n, n_lo, rho, stage_bits, rate_bits, burst_bits,
+                              _stream()), "hilc_vbr_select")
+    return n_eff, distortion
+
+
+_register("vbr_select", "(Tensor z, Tensor(a!) indices, Tensor codebooks, Tensor? n_clip, Tensor? action, Tensor? hold, "
+          "Tensor(b!)? credit, int n_lo, float rho, int stage_bits, int rate_bits, int burst_bits) -> (Tensor, Tensor)", _vbr_select,
+          lambda z, indices, codebooks, n_clip, action, hold, credit, n_lo, rho, stage_bits, rate_bits, burst_bits:
+          (z.new_empty(z.shape[0], dtype=torch.int32), z.new_empty(z.shape[0], indices.shape[0] + 1, dtype=torch.float64)))
+
 _OPS = torch.ops.hilcodec
 
 
@@ -1721,3 +1748,15 @@ def room_mix(wav: Tensor, room: Tensor, score: Optional[Tensor] = None, top_k: i
     mix_levels(wav, score)
     mix_rooms(wav, room, score, top_k, mixed, speakers)
     return mixed, speakers, score
+
+
+def vbr_select(z: Tensor, indices: Tensor, codebooks: Tensor, n_lo: int, rho: float, stage_bits: int = 0, rate_bits: int = 0,
+               burst_bits: int = 0, n_clip: Optional[Tensor] = None, action: Optional[Tensor] = None, hold: Optional[Tensor] = None,
+               credit: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """The VBR sender's step between its quantiser and its packer (vbr.VbrModel): `z` fp32 `[B, T, C]` (the quantiser's input),
+    `indices` int64 `[n, B, T]` (in place: rows >= a slot's n_eff become -1), `codebooks` fp32 `[Nq, K, C]` -> (n_eff int32 `[B]`,
+    distortion float64 `[B, n + 1]`).  `n_clip` (int32 `[B]`, optional): each slot's ceiling; `action` / `hold` (int32 `[B]`, optional):
+    the session rows; `credit` (int32 `[B]`, in place, optional): the token bucket of a capped sender, with vbr.bucket_bits' three
+    numbers (without it `rate_bits` must be 0)."""
+    return _OPS.vbr_select(z, indices, codebooks, n_clip, action, hold, credit, int(n_lo), float(rho), int(stage_bits), int(rate_bits),
+                           int(burst_bits))

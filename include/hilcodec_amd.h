@@ -37,7 +37,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -594,6 +594,29 @@ int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, 
 int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream);
 int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L,
                    void* stream);
+
+/* ---- quality-targeted variable bitrate of the packet sender (additive under ABI 16) ----------------------------------------------
+ * One entry point added WITHOUT a version bump, as the entry points above.  The definition, bit for bit, is hilcodec_amd/vbr.py.
+ * hilc_vbr_select: the sender's launch between the quantiser and the packer.  z fp32 [B][T][C] (the quantiser's input, channel-last);
+ * indices int64 [n][B][T] (stage-major, in place); codebooks fp32 [Nq][K][C]; n_per_stream, action, hold optional int32 [B] (NULL = n,
+ * 0, 0): the slot's ceiling n_b (clamped to [1, n]) and the rows of hilc_state_slots_apply / hilc_state_slots_hold; credit optional
+ * int32 [B] (in place; NULL = no cap, then rate_bits must be 0) -> n_eff int32 [B], distortion float64 [B][n + 1].  Per slot b:
+ *   per frame t ascending, r = z[b][t][:]; for s = 0 .. n_b: e(t, s) = |r|^2, then (s < n_b) r[c] = r[c] - codebooks[s][k][c] with k =
+ *   indices[s][b][t] clamped to [0, K), one fp32 subtraction per channel (rvq_encode_kernel's chain).  |r|^2 in float64: lane l of 64
+ *   sums (double)r[c] (double)r[c] over c = l, l + 64, ... ascending, each product and each sum rounded on its own, then the 64
+ *   partials are added in lane order.  D[s] = sum over t ascending of e(t, s); D[s > n_b] = D[n_b].
+ *   n_q = the smallest s in [lo, n_b] with D[s] <= rho D[0] (one rounded float64 product), else n_b; lo = min(n_b, n_lo).
+ *   With credit: c = burst_bits if action[b] != 0, else credit[b]; then c = min(c + rate_bits, burst_bits), n_eff = min(n_q,
+ *   clamp(c / stage_bits, lo, n_b)), credit[b] = c - n_eff stage_bits.  Without: n_eff = n_q.
+ *   hold[b] != 0: n_eff[b] = n_b, distortion[b] = 0, credit[b] = c before the refill (so an action on the same hop still fills it).
+ *   Finally indices[s][b][:] = -1 for s >= n_eff[b].
+ * C a multiple of 64 and <= 512, n <= 32 (else HILC_ERR_UNSUPPORTED); 1 <= n <= Nq, 1 <= n_lo <= n, 0 < rho <= 1, and with credit
+ * stage_bits >= 1, rate_bits >= stage_bits n_lo, rate_bits <= burst_bits <= 2^30 (else HILC_ERR_RANGE); NULL pointers (the optional
+ * rows excepted; credit NULL with rate_bits != 0): HILC_ERR_NULL; B, T, C, K or Nq <= 0: HILC_ERR_SHAPE.  One wave per slot, no
+ * atomics; every element of n_eff and distortion is written. */
+int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action,
+                    const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo,
+                    double rho, int stage_bits, int rate_bits, int burst_bits, void* stream);
 
 #ifdef __cplusplus
 }
