@@ -81,6 +81,7 @@ SIGNATURES = {
     "hilc_cng_synth": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "hilc_packet_header": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "hilc_jitter_step": [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "hilc_jitter_adapt_step": [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p],
     "hilc_mix_levels": [_p, _p, _p, _i, _i, _p],
     "hilc_mix_rooms": [_p, _p, _p, _i, _p, _p, _i, _i, _p],
     "hilc_vbr_select": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _p],

@@ -8,32 +8,14 @@
 //   hilc_jitter_step    the receiver's first launch: takes this hop's arrivals of each slot into its ring, plays the entry the slot's
 //                       clock points at and writes the hold, n, lost and fec rows and the packet matrix the explicit step() uploads.
 //
-// Arrival record a (int32, 1 + aw words, aw = ceil((3 + stride) / 4)): [0] byte count, then the headed packet's bytes (little-endian
-// words).  Ring of slot b: meta int32 [C] (jitter.meta_word, 0 when free) and body int32 [C][rw], rw = ceil(stride / 4), the packet
-// body zero past its length.  Lane j of the slot's wave owns body word j (and j + 64, ...) in every pass, so a body stored by an
-// arrival and read back when played is read by the lane that wrote it; the meta words live in lanes 0..C-1 and move by shuffles.
-#include "common.h"
+// The layout of the arrival records and the ring, and what the adaptive kernel (jitter_adapt.hip) shares: jitter_ring.h.
+#include "jitter_ring.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
-constexpr int HDR = 3;              // wire.TRANSPORT_HEADER
-constexpr int MAX_N = 32;           // primary + redundant stages: as hilc_rvq_decode_packed
+using namespace jring;
+
 constexpr int KIND_SID = 2;         // dtx.SID
-constexpr int MAX_ORDER = 16;       // dtx.MAX_ORDER
-
-// jitter.py: ST_* / STAT_* / META_*
-constexpr int ST_ANCHORED = 0, ST_WAIT = 1, ST_NEXT = 2, ST_IN_DTX = 3, ST_MASK = 4;
-constexpr int STAT_ACCEPTED = 5, STAT_DUPLICATE = 6, STAT_LATE = 7, STAT_EARLY = 8, STAT_MALFORMED = 9;
-constexpr int STAT_DECODED = 10, STAT_FEC = 11, STAT_LOST = 12, STAT_NOISE = 13;
-constexpr int ST_WORDS = 14;
-constexpr uint32_t META_SID = 1u << 16, META_FEC = 1u << 17;
-constexpr int META_N_SHIFT = 18;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ int pbytes(int n, int T) { return (10 * n * T + 7) >> 3; }   // wire.packet_bytes
 
 // one thread per output byte, the shape of pack_codes_kernel; thread 0 of a row writes its byte count and next counter
 __global__ __launch_bounds__(THREADS) void packet_header_kernel(const uint8_t* __restrict__ packets, const int* __restrict__ nbytes,
@@ -97,38 +79,18 @@ __global__ __launch_bounds__(THREADS) void jitter_step_kernel(const int* __restr
   const int a1 = clampi(off[b + 1], a0, max_a);
   for (int a = a0; a < a1; ++a) {
     const int* rec = arr + (long)a * (1 + aw);
-    const int nb = rec[0];
-    const int body = nb - HDR;
-    bool ok = nb >= HDR && nb <= tb;
-    uint32_t hop = 0, flags = 0;
-    if (ok) {
-      const uint32_t w = (uint32_t)rec[1];                  // packet bytes 0..3
-      hop = ((w & 0xFFu) << 8) | ((w >> 8) & 0xFFu);
-      flags = (w >> 16) & 0xFFu;
-    }
-    const bool sid = (flags & 0x80u) != 0, fb = (flags & 0x40u) != 0;
-    const int n = (int)(flags & 0x1Fu);
-    if (ok) {
-      if (flags & 0x20u)
-        ok = false;
-      else if (fb && (m < 1 || n < m))
-        ok = false;
-      else if (sid)
-        ok = order >= 0 && n == 0 && body == 1 + order;
-      else
-        ok = n >= 1 && n <= n_max && body == (fb ? pbytes(n + m, T) : pbytes(n, T));
-    }
-    if (!ok) {
+    const Arrival p = parse_arrival(rec, tb, T, n_max, m, order);
+    if (!p.ok) {
       ++s[STAT_MALFORMED];
       continue;
     }
-    const int i = (int)hop & (C - 1);
+    const int i = (int)p.hop & (C - 1);
     if (!s[ST_ANCHORED]) {
       s[ST_ANCHORED] = 1;
-      s[ST_NEXT] = (int)hop;
+      s[ST_NEXT] = (int)p.hop;
       s[ST_WAIT] = depth;
     } else {
-      const int d = (((int)hop - s[ST_NEXT] + 0x8000) & 0xFFFF) - 0x8000;
+      const int d = int16_of((int)p.hop - s[ST_NEXT]);
       if (d < 0) {
         ++s[STAT_LATE];
         continue;
@@ -142,15 +104,8 @@ __global__ __launch_bounds__(THREADS) void jitter_step_kernel(const int* __restr
         continue;
       }
     }
-    if (lane == i) my_meta = hop | (sid ? META_SID : 0u) | (fb ? META_FEC : 0u) | ((uint32_t)n << META_N_SHIFT);
-    for (int j = lane; j < rw; j += 64) {
-      const uint32_t lo = (uint32_t)rec[1 + j];             // body byte 4 j = packet byte 4 j + 3
-      const uint32_t hi = (2 + j <= aw) ? (uint32_t)rec[2 + j] : 0u;
-      uint32_t w = (lo >> 24) | (hi << 8);
-      const int keep = body - 4 * j;                        // body bytes in this word
-      if (keep < 4) w = keep <= 0 ? 0u : (w & ((1u << (8 * keep)) - 1u));
-      rrow[(long)i * rw + j] = (int)w;
-    }
+    if (lane == i) my_meta = p.meta();
+    store_body(rec, rrow + (long)i * rw, p.body, aw, rw, lane);
     s[ST_MASK] = (int)((uint32_t)s[ST_MASK] | (1u << i));
     ++s[STAT_ACCEPTED];
   }
@@ -165,50 +120,10 @@ __global__ __launch_bounds__(THREADS) void jitter_step_kernel(const int* __restr
       --s[ST_WAIT];
       ho = 1;
     } else {
-      const int h = s[ST_NEXT];
-      const int i = h & (C - 1), j = (h + 1) & (C - 1);
-      uint32_t mask = (uint32_t)s[ST_MASK];
-      const uint32_t mi = (uint32_t)__shfl((int)my_meta, i);
-      const uint32_t mj = (uint32_t)__shfl((int)my_meta, j);
-      if ((mask >> i) & 1u) {
-        src = i;
-        if (mi & META_SID) {
-          ho = 2;
-          s[ST_IN_DTX] = 1;
-          ++s[STAT_NOISE];
-        } else {
-          no = (int)(mi >> META_N_SHIFT);
-          s[ST_IN_DTX] = 0;
-          ++s[STAT_DECODED];
-        }
-        mask &= ~(1u << i);
-        if (lane == i) my_meta = 0u;
-      } else if (s[ST_IN_DTX]) {
-        ho = 3;
-        ++s[STAT_NOISE];
-      } else if (m >= 1 && ((mask >> j) & 1u) && !(mj & META_SID) && (mj & META_FEC)) {
-        src = j;
-        fo = 1;
-        no = (int)(mj >> META_N_SHIFT);
-        ++s[STAT_FEC];
-      } else {
-        if (conceal)
-          lo = 1;
-        else
-          ho = 1;
-        ++s[STAT_LOST];
-      }
-      s[ST_MASK] = (int)mask;
-      s[ST_NEXT] = (h + 1) & 0xFFFF;
+      play_entry(s, my_meta, lane, C, m, conceal, ho, no, lo, fo, src);
     }
   }
-  uint8_t* prow = packets + (long)b * stride;
-  for (int j = lane; j < rw; j += 64) {
-    const uint32_t w = src >= 0 ? (uint32_t)rrow[(long)src * rw + j] : 0u;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (4 * j + k < stride) prow[4 * j + k] = (uint8_t)(w >> (8 * k));
-  }
+  write_packet_row(packets + (long)b * stride, rrow, src, stride, rw, lane);
   if (lane < C) mrow[lane] = (int)my_meta;
   if (lane == 0) {
     hold[b] = ho;
@@ -244,14 +159,10 @@ extern "C" int hilc_packet_header(const uint8_t* packets, const int* nbytes, con
 extern "C" int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold,
                                 int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T,
                                 int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) {
-  if (!arrivals || !offsets || !hold || !n_per_stream || !packets || !state || !meta || !ring) return HILC_ERR_NULL;
-  if ((conceal != 0 && !lost) || (m >= 1 && !fec)) return HILC_ERR_NULL;
-  if (B <= 0 || T <= 0 || max_arrivals < 0) return HILC_ERR_SHAPE;
-  if (n_max < 1 || m < 0 || m > n_max || order < -1 || order > MAX_ORDER) return HILC_ERR_RANGE;
-  if (capacity < 2 || capacity > 32 || (capacity & (capacity - 1)) || depth < 0 || depth > capacity - 2) return HILC_ERR_RANGE;
-  if (n_max > 31 || n_max + m > MAX_N) return HILC_ERR_UNSUPPORTED;
-  const long stride = (10L * (n_max + m) * T + 7) / 8;
-  if (stride > (1L << 29) || (order >= 0 && 1 + order > stride)) return HILC_ERR_SHAPE;
+  long stride = 0;
+  const int rc = check_args(arrivals, offsets, max_arrivals, hold, n_per_stream, lost, fec, packets, state, meta, ring, B, T, n_max, m,
+                            order, conceal, depth, capacity, &stride);
+  if (rc != HILC_OK) return rc;
   const int rw = (int)((stride + 3) / 4);
   const int aw = (int)((HDR + stride + 3) / 4);
   HILC_CLEAR_ERROR();

@@ -25,7 +25,7 @@ from torch import Tensor
 from . import dtx as dtx_def
 from . import engine, ops, wire
 from . import vbr as vbr_def
-from .jitter import JitterConfig
+from .jitter import AD_WORDS, JitterConfig
 from .mixer import MixConfig
 from .resample import BASE_RATE, design, device_taps, hop_samples
 from .sessions import SessionQueue, stage_layout, stage_starts
@@ -824,6 +824,10 @@ class GraphedDecodeHop(_Hop):
     function of the arrival trace.  Host holds and stops pause a slot's playout (its arrivals are still buffered); `start` clears
     its jitter state; `export` and a resume carry none; `jitter_state` is the int32 `[B, jitter.ST_WORDS]` state rows.  With `jitter`,
     `step` raises RuntimeError; without it, `play` does.  `jitter=None` captures exactly the graph without the jitter buffer.
+    `jitter=JitterConfig(..., adapt=jitter.AdaptConfig(...))`: an adaptive playout clock (jitter.py: a slot follows a sender whose
+    clock drifts, a burst of delay or a sender restart by inserting a hop, skipping an entry or anchoring again).  The first launch
+    is hilc_jitter_adapt_step in place of hilc_jitter_step, the launch count is the same; `jitter_adapt` is the int32 `[B,
+    jitter.AD_WORDS]` adapt rows, cleared with the jitter state.  `adapt=None` captures exactly the graph of the fixed buffer.
     `mix` = mixer.MixConfig(top_k) (needs `sessions`): a conference bridge's room mixer at the tail of the graph (mixer.py).  `join(slot,
     room)` / `leave(slot)` put a slot into a room (an id in [0, B)) or into none, `rooms` is the host's membership tuple (-1: none;
     initially every slot; `stop` does not leave a room).  Membership is a pinned int32 row; when it has changed since the last hop, the
@@ -903,6 +907,8 @@ class GraphedDecodeHop(_Hop):
             self._scratch += [self._cn, self._restore]
         if jitter is not None:
             self._scratch += [self._jstate, self._jmeta, self._jring]
+            if jitter.adapt is not None:
+                self._scratch += [self._jadapt]
         if mix is not None:
             # per slot: the peak-hold score (updated in place by hilc_mix_levels once per hop); per parity: the mixes; the speaker
             # marks; the room row (device, captured by address) and its pinned host mirror
@@ -949,7 +955,11 @@ class GraphedDecodeHop(_Hop):
     def _hop(self, p: int) -> Tensor:
         m = self.model
         src, dst = self.state[p], self.state[p ^ 1]
-        if self.jitter is not None:
+        if self.jitter is not None and self.jitter.adapt is not None:
+            ops.jitter_adapt_step(self.arrivals, self.offsets, self.hold, self.n_slot, self.packets, self._jstate, self._jmeta,
+                                  self._jring, self._jadapt, self.n, self.fec_stages, self.frames, self.cng_order, self.jitter,
+                                  self.action, self.lost, self.fec)
+        elif self.jitter is not None:
             ops.jitter_step(self.arrivals, self.offsets, self.hold, self.n_slot, self.packets, self._jstate, self._jmeta, self._jring,
                             self.n, self.fec_stages, self.frames, self.cng_order, self.jitter.depth, self.action, self.lost, self.fec)
         if self.sessions:
@@ -1132,6 +1142,9 @@ class GraphedDecodeHop(_Hop):
         self._jstate = torch.zeros(B, 14, dtype=torch.int32, device=dev)
         self._jmeta = torch.zeros(B, cfg.capacity, dtype=torch.int32, device=dev)
         self._jring = torch.zeros(B, cfg.capacity, (self.stride + 3) // 4, dtype=torch.int32, device=dev)
+        if cfg.adapt is not None:
+            # per slot: the adapt row (jitter.AD_*, updated in place once per hop by hilc_jitter_adapt_step)
+            self._jadapt = torch.zeros(B, AD_WORDS, dtype=torch.int32, device=dev)
 
     @property
     def jitter_state(self) -> Tensor:
@@ -1140,6 +1153,14 @@ class GraphedDecodeHop(_Hop):
         if self.jitter is None:
             raise RuntimeError("GraphedDecodeHop.jitter_state: construct with jitter=JitterConfig(...)")
         return self._jstate
+
+    @property
+    def jitter_adapt(self) -> Tensor:
+        """int32 `[B, jitter.AD_WORDS]` device view: each slot's adapt row after the last play (jitter.AD_*).  Read-only: written by
+        the graph."""
+        if self.jitter is None or self.jitter.adapt is None:
+            raise RuntimeError("GraphedDecodeHop.jitter_adapt: construct with jitter=JitterConfig(..., adapt=AdaptConfig(...))")
+        return self._jadapt
 
     def play(self, slots, packets: Tensor, nbytes, hold=None) -> Tensor:
         """one hop of a jitter receiver: this hop's arrivals, in push order — `slots` and `nbytes` (A host ints), `packets` uint8
@@ -1187,7 +1208,7 @@ class GraphedDecodeHop(_Hop):
     def start(self, slot: int, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
         """At the next step, slot `slot` begins a fresh stream (zero caches) or resumes one from its 30 decoder caches (B = 1
         tensors, host or device; 31 with `output_rate`, the resampler's history last); at most `max_loads_per_hop` resumes per hop.
-        With `jitter`, its jitter state is cleared on that hop"""
+        With `jitter`, its jitter state (and its adapt row) is cleared on that hop"""
         super().start(slot, None, cache_dec)
 
     def export(self, slot: int) -> List[Tensor]:

@@ -1058,6 +1058,38 @@ _register("jitter_step", "(Tensor arrivals, Tensor offsets, Tensor? action, Tens
           "int depth) -> ()", _jitter_step,
           lambda arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, n, m, frames, order, depth: None)
 
+
+
+def _jitter_adapt_step(arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, adapt, n, m, frames, order, depth,
+                       headroom, max_late, window, resync, force_windows):
+    B = hold.numel()
+    stride = _packet_stride(n + m, frames)
+    aw = (3 + stride + 3) // 4
+    if arrivals.dim() != 2 or arrivals.shape[1] != 1 + aw or offsets.numel() != B + 1:
+        raise RuntimeError(f"jitter_adapt_step: arrivals must be [A, {1 + aw}] and offsets [{B + 1}]")
+    if packets.shape != (B, stride) or state.shape != (B, 14) or adapt.shape != (B, 12) or meta.dim() != 2 or meta.shape[0] != B:
+        raise RuntimeError(f"jitter_adapt_step: packets must be [{B}, {stride}], state [{B}, 14], adapt [{B}, 12], meta [{B}, C]")
+    C = meta.shape[1]
+    if ring.shape != (B, C, (stride + 3) // 4):
+        raise RuntimeError(f"jitter_adapt_step: ring must be [{B}, {C}, {(stride + 3) // 4}]")
+    for name, row in (("action", action), ("n_slot", n_slot), ("lost", lost), ("fec", fec)):
+        if row is not None and row.numel() != B:
+            raise RuntimeError(f"jitter_adapt_step: {name} needs {B} entries")
+    check(lib.hilc_jitter_adapt_step(_ptr(arrivals, torch.int32), _ptr(offsets, torch.int32), arrivals.shape[0],
+                                     _ptr(action, torch.int32), _ptr(hold, torch.int32), _ptr(n_slot, torch.int32),
+                                     _ptr(lost, torch.int32), _ptr(fec, torch.int32), _ptr(packets, torch.uint8),
+                                     _ptr(state, torch.int32), _ptr(meta, torch.int32), _ptr(ring, torch.int32), B, frames, n, m, order,
+                                     int(lost is not None), depth, C, _ptr(adapt, torch.int32), headroom, max_late, window, resync,
+                                     force_windows, _stream()), "hilc_jitter_adapt_step")
+
+
+_register("jitter_adapt_step", "(Tensor arrivals, Tensor offsets, Tensor? action, Tensor(a!) hold, Tensor(b!) n_slot, Tensor(c!)? lost, "
+          "Tensor(d!)? fec, Tensor(e!) packets, Tensor(f!) state, Tensor(g!) meta, Tensor(h!) ring, Tensor(i!) adapt, int n, int m, "
+          "int frames, int order, int depth, int headroom, int max_late, int window, int resync, int force_windows) -> ()",
+          _jitter_adapt_step,
+          lambda arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, adapt, n, m, frames, order, depth,
+          headroom, max_late, window, resync, force_windows: None)
+
 # ======================================================================================================
 # per-room mixing of the receiver's output (graph_step.GraphedDecodeHop(mix=); definition: hilcodec_amd/mixer.py; semantics:
 # include/hilcodec_amd.h)
@@ -1709,6 +1741,18 @@ def jitter_step(arrivals: Tensor, offsets: Tensor, hold: Tensor, n_slot: Tensor,
     stride = wire.packet_bytes(n + m, frames).  `order`: the comfort-noise order (None: a SID is malformed)."""
     _OPS.jitter_step(arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, int(n), int(m), int(frames),
                      -1 if order is None else int(order), int(depth))
+
+
+def jitter_adapt_step(arrivals: Tensor, offsets: Tensor, hold: Tensor, n_slot: Tensor, packets: Tensor, state: Tensor, meta: Tensor,
+                      ring: Tensor, adapt: Tensor, n: int, m: int, frames: int, order: Optional[int], cfg,
+                      action: Optional[Tensor] = None, lost: Optional[Tensor] = None, fec: Optional[Tensor] = None) -> None:
+    """`jitter_step` with an adaptive playout clock (jitter.JitterModel with cfg.adapt), in place: the same arguments, and `adapt`
+    (int32 `[B, jitter.AD_WORDS]`), each slot's adapt row.  `cfg`: the jitter.JitterConfig, its `adapt` set (depth and the
+    AdaptConfig's parameters; the capacity is `meta`'s width)."""
+    a = cfg.adapt
+    _OPS.jitter_adapt_step(arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, adapt, int(n), int(m),
+                           int(frames), -1 if order is None else int(order), int(cfg.depth), int(a.headroom),
+                           a.max_late_for(meta.shape[1]), int(a.window), int(a.resync), int(a.force_windows))
 
 
 def resample_poly(x: Tensor, taps: Tensor, L: int, M: int, hist: Optional[Tensor] = None, hist_out: Optional[Tensor] = None) -> Tensor:

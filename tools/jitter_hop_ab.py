@@ -7,9 +7,11 @@ fec_stages=2.  Receivers: sessions=True, conceal=True, fec_stages=2, cng_order=8
    (a) / (A) in-order traffic:  step() fed jitter.JitterModel's decisions (the parent graph) / play() of the arrivals
    (b) / (B) 5 % loss, reordering up to D hops, 1 % duplicates
    (c) / (C) DTX-heavy: per slot 10 speech hops, then SIDs every 8 hops and silence in between, 32-hop cycle
+   (X) (Y) (Z) the play() of (A) (B) (C) on a receiver with an adaptive playout clock, JitterConfig(..., adapt=AdaptConfig())
 A traffic trace of `--hops` hops is generated once per mix (JitterConfig(depth=2, capacity=8)); every leg replays it from a start
 of all slots.  Also printed: the per-hop upload bytes and the host time of a play() / step() call.
    python tools/jitter_hop_ab.py [--hops 200] [--alternations 7] [--legs stabcABC] > profiles/jitter_hops.txt
+   python tools/jitter_hop_ab.py --legs ABCXYZ > profiles/jitter_adapt_hops.txt
 The two kernels' own times come from a separate kernel-trace run of this script (no counters in that run):
    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o t -- python tools/jitter_hop_ab.py --hops 50 --alternations 1 --legs tB"""
 import argparse
@@ -23,7 +25,7 @@ import numpy as np
 import torch
 
 from hilcodec_amd import dtx, graph_step, synth, wire
-from hilcodec_amd.jitter import JitterConfig, JitterModel
+from hilcodec_amd.jitter import AdaptConfig, JitterConfig, JitterModel
 from hilcodec_amd.models.hilcodec.streaming import HILCodec as StreamingHILCodec
 
 ap = argparse.ArgumentParser()
@@ -38,6 +40,7 @@ if not torch.cuda.is_available():
 dev = torch.device("cuda:0")
 B, n, m, K, T = args.streams, 8, 2, 8, 1
 cfg = JitterConfig(depth=2, capacity=8)
+cfg_adapt = JitterConfig(depth=2, capacity=8, adapt=AdaptConfig())
 mk = synth.model_kwargs("hil_speech")
 smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
 model = StreamingHILCodec(24000, **smk).eval()
@@ -95,6 +98,9 @@ LEGS = {  # leg: (kind, mix, name)
     "B": ("play", "b", "(B) 5 % loss + reorder + dup, play()"),
     "c": ("step", "c", "(c) DTX-heavy, step()"),
     "C": ("play", "c", "(C) DTX-heavy, play()"),
+    "X": ("adapt", "a", "(X) in-order, adaptive play()"),
+    "Y": ("adapt", "b", "(Y) 5 % loss + reorder + dup, adaptive"),
+    "Z": ("adapt", "c", "(Z) DTX-heavy, adaptive play()"),
 }
 t0 = time.time()
 traces = {mix: trace(mix, args.hops) for mix in sorted({LEGS[leg][1] for leg in args.legs if LEGS[leg][1]})}
@@ -106,7 +112,7 @@ def make(leg):
     if kind == "enc":
         return graph_step.GraphedEncodeHop(model, B, 320, n, dev, sessions=True, fec_stages=m, header=leg == "t")
     return graph_step.GraphedDecodeHop(model, B, T, n, dev, sessions=True, conceal=True, fec_stages=m, cng_order=K,
-                                       jitter=cfg if kind == "play" else None)
+                                       jitter={"play": cfg, "adapt": cfg_adapt}.get(kind))
 
 
 hoppers = {leg: make(leg) for leg in args.legs}
@@ -122,7 +128,7 @@ def one(leg, i):
         return
     slots, packets, nbytes, rows, n_list, kw = traces[mix][i]
     c0 = time.perf_counter()
-    if kind == "play":
+    if kind in ("play", "adapt"):
         h.play(slots, packets, nbytes)
     else:
         h.step(rows, n_list, **kw)
@@ -157,10 +163,11 @@ for a in range(args.alternations):
         ms = run(leg, args.hops)
         res[leg].append(ms)
         print(f"alt {a} {LEGS[leg][2]:40s} {ms:.4f} ms/hop", flush=True)
-print("# median over alternations; (t) against (s), each play() leg against the step() leg of its mix")
+print("# median over alternations; (t) against (s), each play() leg against the step() leg of its mix, each adaptive leg against the "
+      "play() leg of its mix")
 for leg in args.legs:
     med = statistics.median(res[leg])
-    base = {"t": "s", "A": "a", "B": "b", "C": "c"}.get(leg)
+    base = {"t": "s", "A": "a", "B": "b", "C": "c", "X": "A", "Y": "B", "Z": "C"}.get(leg)
     rel = ""
     if base in res:
         b = statistics.median(res[base])
