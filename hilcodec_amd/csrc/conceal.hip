@@ -12,32 +12,23 @@
 // stage s of the last frame of the last packet received (0 for s >= stored n).  Ramp word of slot b: 0 none; r in 1..F: a lost hop,
 // gains G[r - 1] -> G[r]; r in -F..-1: a received hop after -r lost ones, gains G[-r] -> G[0].
 //
-// Both kernels: one wave per slot (4 per workgroup), wave-uniform branches only.  The common case (every packet received) costs
-// one round of loads and one of stores per slot in prepare, and one load per slot in gain.
-#include "common.h"
+// Both kernels: one wave per slot (slot.h), wave-uniform branches only.  The common case (every packet received) costs one round of
+// loads and one of stores per slot in prepare, and one load per slot in gain.
+#include "slot.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
-constexpr int MAX_N = 32;          // stages per stored frame: as hilc_rvq_decode_packed
+using namespace slot;
+
 constexpr int ST_RUN = 0, ST_HAS = 1, ST_N = 2, ST_CODES = 3;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ int code_at(const uint8_t* p, int bit) {
-  const uint8_t* q = p + (bit >> 3);
-  const uint32_t v = ((uint32_t)q[0] << 8) | (uint32_t)q[1];
-  return (int)((v >> (6 - (bit & 7))) & 1023u);
-}
 
 __global__ __launch_bounds__(THREADS) void conceal_prepare_kernel(int* __restrict__ state, const int* __restrict__ action,
                                                                   int* __restrict__ hold, const int* __restrict__ lost,
                                                                   int* __restrict__ n_slot, uint8_t* __restrict__ packets,
                                                                   int* __restrict__ ramp, int B, int T, int n_max, int stride, int F) {
-  const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + ((int)threadIdx.x >> 6));
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
+  const Wave me = this_wave(B);
+  if (!me.ok) return;
+  const int b = me.b, lane = me.lane();
   const int words = n_max + 3;
   int* st = state + (long)b * words;
   uint8_t* pk = packets + (long)b * stride;
@@ -64,21 +55,18 @@ __global__ __launch_bounds__(THREADS) void conceal_prepare_kernel(int* __restric
   } else if (has && k < F) {
     const int nb = clampi(n0, 1, n_max);
     const int count = nb * T;
-    const int len = (10 * count + 7) >> 3;
+    const int len = code_bytes(count);
     // the substitute packet: stage s of every frame = stored code s, in the layout of hilc_pack_codes_10bit
     for (int j0 = 0; j0 < stride; j0 += 64) {
       const int j = j0 + lane;
-      const int i0 = (8 * j) / 10;
-      const int off = 8 * j - 10 * i0;
+      const PackedByte at = packed_byte(j);
+      const int i0 = at.i0;
       const int s0 = min(i0 / T, MAX_N - 1), s1 = min((i0 + 1) / T, MAX_N - 1);
       const uint32_t c0 = (uint32_t)__shfl(old, ST_CODES + s0) & 1023u;
       const uint32_t c1 = (uint32_t)__shfl(old, ST_CODES + s1) & 1023u;
       if (j < stride) {
         uint32_t out = 0;
-        if (j < len) {
-          const uint32_t w = (c0 << 10) | (i0 + 1 < count ? c1 : 0u);
-          out = (w >> (12 - off)) & 0xFFu;
-        }
+        if (j < len) out = at.of((c0 << 10) | (i0 + 1 < count ? c1 : 0u));
         pk[j] = (uint8_t)out;
       }
     }
@@ -96,8 +84,9 @@ __global__ __launch_bounds__(THREADS) void conceal_prepare_kernel(int* __restric
 __global__ __launch_bounds__(THREADS) void conceal_gain_kernel(float* __restrict__ wav, const int* __restrict__ ramp,
                                                                const float* __restrict__ gains, const float* __restrict__ weights,
                                                                int B, int S, int F) {
-  const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + ((int)threadIdx.x >> 6));
-  if (b >= B) return;
+  const Wave me = this_wave(B);
+  if (!me.ok) return;
+  const int b = me.b;
   const int r = ramp[b];
   if (r == 0 || r > F || r < -F) return;               // no ramp: the row is not touched
   const int a = r > 0 ? r - 1 : -r;
@@ -105,7 +94,7 @@ __global__ __launch_bounds__(THREADS) void conceal_gain_kernel(float* __restrict
   const float ga = gains[a];
   const float d = __fsub_rn(gains[c], ga);
   float* row = wav + (long)b * S;
-  for (int s = threadIdx.x & 63; s < S; s += 64) row[s] = __fmul_rn(row[s], __fadd_rn(ga, __fmul_rn(d, weights[s])));
+  for (int s = me.lane(); s < S; s += LANES) row[s] = __fmul_rn(row[s], __fadd_rn(ga, __fmul_rn(d, weights[s])));
 }
 
 }  // namespace
@@ -116,13 +105,10 @@ extern "C" int hilc_conceal_prepare(int* state, const int* action, int* hold, co
   if (B <= 0 || T <= 0) return HILC_ERR_SHAPE;
   if (n_max < 1 || fade_hops < 1) return HILC_ERR_RANGE;
   if (n_max > MAX_N) return HILC_ERR_UNSUPPORTED;
-  const long stride = (10L * n_max * T + 7) / 8;
+  const long stride = packet_bytes<long>(n_max, T);
   if (stride > (1L << 30)) return HILC_ERR_SHAPE;
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(conceal_prepare_kernel, dim3((unsigned)((B + WAVES - 1) / WAVES)), dim3(THREADS), 0, (hipStream_t)stream, state,
-                     action, hold, lost, n_per_stream, packets, ramp, B, T, n_max, (int)stride, fade_hops);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return launch(conceal_prepare_kernel, waves_grid(B), stream, state, action, hold, lost, n_per_stream, packets, ramp, B, T, n_max,
+                (int)stride, fade_hops);
 }
 
 extern "C" int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples,
@@ -130,9 +116,5 @@ extern "C" int hilc_conceal_gain(float* wav, const int* ramp, const float* gains
   if (!wav || !ramp || !gains || !weights) return HILC_ERR_NULL;
   if (B <= 0 || samples <= 0) return HILC_ERR_SHAPE;
   if (fade_hops < 1) return HILC_ERR_RANGE;
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(conceal_gain_kernel, dim3((unsigned)((B + WAVES - 1) / WAVES)), dim3(THREADS), 0, (hipStream_t)stream, wav, ramp,
-                     gains, weights, B, samples, fade_hops);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return launch(conceal_gain_kernel, waves_grid(B), stream, wav, ramp, gains, weights, B, samples, fade_hops);
 }

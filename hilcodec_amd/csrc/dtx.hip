@@ -9,15 +9,14 @@
 //   hilc_cng_synth   the receiver's launch after the decoder: per slot that produces noise, the SID's (or the stored) parameters
 //                    through the all-pole synthesis filter into the slot's wav row; the CN state row is updated in place.
 //
-// Both kernels: one wave per stream (4 per workgroup), wave-uniform branches only, the order K a template parameter (the filter
-// memory and the coefficients stay in registers).
-#include "common.h"
+// Both kernels: one wave per stream (slot.h), wave-uniform branches only, the order K a template parameter (the filter memory and
+// the coefficients stay in registers).
+#include "slot.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
-constexpr int LANES = 64;
+using namespace slot;
+
 constexpr int MAX_ORDER = 16;
 constexpr int LEVELS = 128;
 constexpr float NOISE_BOUND = 16.f; // dtx.NOISE_BOUND: a noise hop with a sample outside (-16, 16) is replaced by silence
@@ -34,13 +33,6 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 __device__ __forceinline__ int readlane_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-  const long long u = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(u & 0xFFFFFFFFll), lane);
-  const int hi = __builtin_amdgcn_readlane((int)(u >> 32), lane);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
 
 __device__ __forceinline__ uint32_t lowbias32(uint32_t h) {
   h ^= h >> 16;
@@ -60,16 +52,15 @@ __global__ __launch_bounds__(THREADS) void dtx_encode_kernel(const float* __rest
                                                              int H, int I, int n_max, int stride, int prev_words) {
   __shared__ double part[WAVES][K + 1][LANES + 1];        // +1: lane k's column read is free of bank conflicts
   __shared__ float xs[WAVES][MAX_ORDER + FRAME];
-  const int w = threadIdx.x >> 6;
-  const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + w);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
+  const Wave me = this_wave(B);
+  if (!me.ok) return;
+  const int w = me.w, b = me.b, lane = me.lane();
   const int S = 320 * T;
-  const bool reset = action != nullptr && action[b] != 0;
+  const bool reset = is_reset(action, b);
   const int run0 = reset ? 0 : run[b];
   const double thr0 = level_thr[lane];
   const double thr1 = lane + LANES < LEVELS - 1 ? level_thr[lane + LANES] : 0.0;
-  if (hold != nullptr && hold[b] != 0) {                  // held: run kept (a start on this hop clears it), nothing else
+  if (is_held(hold, b)) {                                 // held: run kept (a start on this hop clears it), nothing else
     if (lane == 0) {
       run[b] = run0;
       kind[b] = 0;
@@ -167,10 +158,7 @@ __global__ __launch_bounds__(THREADS) void dtx_encode_kernel(const float* __rest
   uint8_t* row = packets + (long)b * stride;
   for (int j = lane; j < stride; j += LANES) row[j] = (uint8_t)(j == lane ? byte : 0);
   if (lane == 0) nbytes[b] = kd == SID ? 1 + K : 0;
-  for (int e = lane; e < n_max * T; e += LANES) {
-    const int s = e / T, t = e - (e / T) * T;
-    indices[((long)s * B + b) * T + t] = -1;
-  }
+  clear_rows(indices, 0, n_max, B, b, T, lane);
   if (prev != nullptr && lane == 0) prev[(long)b * prev_words] = 0;
 }
 
@@ -179,12 +167,12 @@ __global__ __launch_bounds__(THREADS) void cng_synth_kernel(const uint8_t* __res
                                                             int* __restrict__ hold, int* __restrict__ state, float* __restrict__ wav,
                                                             int* __restrict__ restore, const float* __restrict__ gains, int B, int S,
                                                             int stride) {
-  const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + ((int)threadIdx.x >> 6));
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
+  const Wave me = this_wave(B);
+  if (!me.ok) return;
+  const int b = me.b, lane = me.lane();
   constexpr int W = ST_Q + 2 * K;
   int* st = state + (long)b * W;
-  const bool reset = action != nullptr && action[b] != 0;   // a start on this hop: the state row starts from zero
+  const bool reset = is_reset(action, b);                 // the state row starts from zero
   const int h = hold[b];
   int word = (lane < W && !reset) ? st[lane] : 0;
   const int byte = (h == 2 && lane <= K) ? (int)packets[(long)b * stride + lane] : 0;
@@ -292,19 +280,15 @@ extern "C" int hilc_dtx_encode(const float* x, const int* action, const int* hol
   if (order < 0 || order > MAX_ORDER || hangover < 0 || sid_interval < 1 || hangover > (1 << 30) || sid_interval > (1 << 30))
     return HILC_ERR_RANGE;
   if (stride < 1 + order) return HILC_ERR_SHAPE;          // a SID must fit the row
-  const dim3 grid((unsigned)((B + WAVES - 1) / WAVES));
-  HILC_CLEAR_ERROR();
   switch (order) {
-#define X(K)                                                                                                                    \
-  case K:                                                                                                                       \
-    hipLaunchKernelGGL(dtx_encode_kernel<K>, grid, dim3(THREADS), 0, (hipStream_t)stream, x, action, hold, run, kind, packets, \
-                       nbytes, indices, prev, level_thr, thr_vad, B, T, hangover, sid_interval, n_max, stride, prev_words);     \
-    break;
+#define X(K)                                                                                                                  \
+  case K:                                                                                                                     \
+    return launch(dtx_encode_kernel<K>, waves_grid(B), stream, x, action, hold, run, kind, packets, nbytes, indices, prev,    \
+                  level_thr, thr_vad, B, T, hangover, sid_interval, n_max, stride, prev_words);
     HILC_DTX_ORDERS(X)
 #undef X
   }
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return HILC_ERR_RANGE;                                  // not reached: the order was checked above
 }
 
 extern "C" int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore,
@@ -313,17 +297,12 @@ extern "C" int hilc_cng_synth(const uint8_t* packets, const int* action, int* ho
   if (B <= 0 || T <= 0 || T > (1 << 20) / 320) return HILC_ERR_SHAPE;
   if (order < 0 || order > MAX_ORDER) return HILC_ERR_RANGE;
   if (stride < 1 + order) return HILC_ERR_SHAPE;
-  const dim3 grid((unsigned)((B + WAVES - 1) / WAVES));
-  HILC_CLEAR_ERROR();
   switch (order) {
-#define X(K)                                                                                                                    \
-  case K:                                                                                                                       \
-    hipLaunchKernelGGL(cng_synth_kernel<K>, grid, dim3(THREADS), 0, (hipStream_t)stream, packets, action, hold, state, wav,    \
-                       restore, gains, B, 320 * T, stride);                                                                    \
-    break;
+#define X(K) \
+  case K:    \
+    return launch(cng_synth_kernel<K>, waves_grid(B), stream, packets, action, hold, state, wav, restore, gains, B, 320 * T, stride);
     HILC_DTX_ORDERS(X)
 #undef X
   }
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return HILC_ERR_RANGE;                                  // not reached: the order was checked above
 }

@@ -11,18 +11,12 @@
 //                              section of a received packet, the redundant section (at n = m) of a slot recovered by FEC.
 //
 // Previous-codes row of stream b (int32, 1 + m T words): [0] valid (0/1), [1 + s T + t] code of stage s < m, frame t of the last
-// encoded hop.  Code i of a packet occupies bits [10 i, 10 i + 10) as in packets.hip, so every code lies inside two bytes.
-#include "common.h"
+// encoded hop.  The packet layout and its helpers: slot.h.
+#include "slot.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
-constexpr int MAX_N = 32;          // primary + redundant stages: as hilc_rvq_decode_packed
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ uint32_t clamp_code(int64_t k) { return (uint32_t)(k < 0 ? 0 : (k > 1023 ? 1023 : k)); }
+using namespace slot;
 
 // one thread per output byte, the shape of pack_codes_kernel; thread j < 1 + m T also writes word j of the stream's next
 // previous-codes row (stride = ceil(10 (n_max + m) T / 8) >= 2.5 m T >= 1 + m T, so every word has a thread)
@@ -37,9 +31,9 @@ __global__ __launch_bounds__(THREADS) void pack_codes_fec_kernel(const int64_t* 
   const int j = (int)(e - (long)b * stride);
   const int W = 1 + m * T;
   const int* pin = prev_in + (long)b * W;
-  const bool reset = action != nullptr && action[b] != 0;   // a start or a resume on this hop: no previous hop
-  const bool held = hold != nullptr && hold[b] != 0;
-  const int nb = n_per_stream == nullptr ? n_max : clampi(n_per_stream[b], m, n_max);
+  const bool reset = is_reset(action, b);                   // no previous hop
+  const bool held = is_held(hold, b);
+  const int nb = clamp_n(n_per_stream, (long)b, m, n_max);
   if (j < W) {
     int w;
     if (held) {
@@ -48,7 +42,7 @@ __global__ __launch_bounds__(THREADS) void pack_codes_fec_kernel(const int64_t* 
       w = 1;
     } else {
       const int s = (j - 1) / T, t = (j - 1) - ((j - 1) / T) * T;
-      w = (int)clamp_code(indices[((long)s * B + b) * T + t]);
+      w = clamp_code(indices[index_at(s, B, b, T, t)]);
     }
     prev_out[(long)b * W + j] = w;
   }
@@ -59,25 +53,24 @@ __global__ __launch_bounds__(THREADS) void pack_codes_fec_kernel(const int64_t* 
     const bool valid = !reset && pin[0] != 0;
     const int count_p = nb * T;
     const int count = count_p + (valid ? m * T : 0);
-    const int len = (10 * count + 7) >> 3;
+    const int len = code_bytes(count);
     if (j == 0) nbytes[b] = len;
     if (j < len) {
-      const int i0 = (8 * j) / 10;
-      const int off = 8 * j - 10 * i0;
+      const PackedByte at = packed_byte(j);
       uint32_t w = 0;
 #pragma unroll
       for (int d = 0; d < 2; ++d) {
-        const int i = i0 + d;
+        const int i = at.i0 + d;
         uint32_t c = 0;
         if (i < count_p) {
           const int s = i / T, t = i - (i / T) * T;
-          c = clamp_code(indices[((long)s * B + b) * T + t]);
+          c = (uint32_t)clamp_code(indices[index_at(s, B, b, T, t)]);
         } else if (i < count) {
           c = (uint32_t)pin[1 + i - count_p] & 1023u;
         }
         w = (w << 10) | c;
       }
-      out = (w >> (12 - off)) & 0xFFu;
+      out = at.of(w);
     }
   }
   packets[e] = (uint8_t)out;
@@ -89,9 +82,9 @@ __global__ __launch_bounds__(THREADS) void pack_codes_fec_kernel(const int64_t* 
 __global__ __launch_bounds__(THREADS) void fec_select_kernel(const uint8_t* __restrict__ wide, const int* __restrict__ fec,
                                                              int* __restrict__ n_per_stream, uint8_t* __restrict__ out, int B, int T,
                                                              int n_max, int m, int wstride, int ostride) {
-  const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + ((int)threadIdx.x >> 6));
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
+  const Wave me = this_wave(B);
+  if (!me.ok) return;
+  const int b = me.b, lane = me.lane();
   const bool red = fec[b] != 0;
   const int n_in = n_per_stream[b];
   const int nb = red ? clampi(n_in, m, n_max) : clampi(n_in, 1, n_max);
@@ -124,14 +117,10 @@ extern "C" int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_pe
   if (B <= 0 || T <= 0 || prev_in == prev_out) return HILC_ERR_SHAPE;
   if (n_max < 1 || m < 1 || m > n_max) return HILC_ERR_RANGE;
   if (n_max + m > MAX_N) return HILC_ERR_UNSUPPORTED;
-  const long stride = (10L * (n_max + m) * T + 7) / 8;
+  const long stride = packet_bytes<long>(n_max + m, T);
   if (stride > (1L << 30)) return HILC_ERR_SHAPE;
-  const long total = (long)B * stride;
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(pack_codes_fec_kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream,
-                     indices, n_per_stream, prev_in, prev_out, action, hold, packets, nbytes, B, T, n_max, m, (int)stride);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return launch(pack_codes_fec_kernel, threads_grid(B * stride), stream, indices, n_per_stream, prev_in, prev_out, action, hold, packets,
+                nbytes, B, T, n_max, m, (int)stride);
 }
 
 extern "C" int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m,
@@ -140,12 +129,8 @@ extern "C" int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_pe
   if (B <= 0 || T <= 0) return HILC_ERR_SHAPE;
   if (n_max < 1 || m < 1 || m > n_max) return HILC_ERR_RANGE;
   if (n_max + m > MAX_N) return HILC_ERR_UNSUPPORTED;
-  const long wstride = (10L * (n_max + m) * T + 7) / 8;
+  const long wstride = packet_bytes<long>(n_max + m, T);
   if (wstride > (1L << 30)) return HILC_ERR_SHAPE;
-  const int ostride = (10 * n_max * T + 7) / 8;
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(fec_select_kernel, dim3((unsigned)((B + WAVES - 1) / WAVES)), dim3(THREADS), 0, (hipStream_t)stream, packets, fec,
-                     n_per_stream, out, B, T, n_max, m, (int)wstride, ostride);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return launch(fec_select_kernel, waves_grid(B), stream, packets, fec, n_per_stream, out, B, T, n_max, m, (int)wstride,
+                packet_bytes(n_max, T));
 }

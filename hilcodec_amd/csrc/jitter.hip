@@ -28,8 +28,8 @@ __global__ __launch_bounds__(THREADS) void packet_header_kernel(const uint8_t* _
   if (e >= (long)B * ostride) return;
   const int b = (int)(e / ostride);
   const int j = (int)(e - (long)b * ostride);
-  const bool reset = action != nullptr && action[b] != 0;   // a start or a resume on this hop: the counter restarts at 0
-  const bool held = hold != nullptr && hold[b] != 0;
+  const bool reset = is_reset(action, b);                   // the counter restarts at 0
+  const bool held = is_held(hold, b);
   const int cur = reset ? 0 : (ctr_in[b] & 0xFFFF);
   const int len = held ? 0 : clampi(nbytes[b], 0, istride);
   if (j == 0) {
@@ -46,8 +46,8 @@ __global__ __launch_bounds__(THREADS) void packet_header_kernel(const uint8_t* _
       if (kind != nullptr && kind[b] == KIND_SID) {
         v = 0x80u;
       } else {
-        const int nb = n_per_stream == nullptr ? n_max : clampi(n_per_stream[b], m > 1 ? m : 1, n_max);
-        v = (uint32_t)nb | ((m >= 1 && len == pbytes(nb + m, T)) ? 0x40u : 0u);
+        const int nb = clamp_n(n_per_stream, (long)b, m > 1 ? m : 1, n_max);
+        v = (uint32_t)nb | ((m >= 1 && len == packet_bytes(nb + m, T)) ? 0x40u : 0u);
       }
     } else if (j - HDR < len) {
       v = packets[(long)b * istride + (j - HDR)];
@@ -56,20 +56,20 @@ __global__ __launch_bounds__(THREADS) void packet_header_kernel(const uint8_t* _
   out[e] = (uint8_t)v;
 }
 
-// one wave per slot (4 per workgroup); every branch but the body copies is wave-uniform
+// one wave per slot; every branch but the body copies is wave-uniform
 __global__ __launch_bounds__(THREADS) void jitter_step_kernel(const int* __restrict__ arr, const int* __restrict__ off, int max_a, int aw,
                                                               const int* __restrict__ action, int* __restrict__ hold,
                                                               int* __restrict__ n_per_stream, int* __restrict__ lost, int* __restrict__ fec,
                                                               uint8_t* __restrict__ packets, int* __restrict__ state, int* __restrict__ meta,
                                                               int* __restrict__ ring, int B, int T, int n_max, int m, int order,
                                                               int conceal, int depth, int C, int stride, int rw) {
-  const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + ((int)threadIdx.x >> 6));
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
+  const Wave me = this_wave(B);
+  if (!me.ok) return;
+  const int b = me.b, lane = me.lane();
   int* st = state + (long)b * ST_WORDS;
   int* mrow = meta + (long)b * C;
   int* rrow = ring + (long)b * C * rw;
-  const bool start = action != nullptr && action[b] != 0;
+  const bool start = is_reset(action, b);
   int s[ST_WORDS];
 #pragma unroll
   for (int k = 0; k < ST_WORDS; ++k) s[k] = start ? 0 : st[k];
@@ -144,16 +144,11 @@ extern "C" int hilc_packet_header(const uint8_t* packets, const int* nbytes, con
   if (B <= 0 || T <= 0 || counter_in == counter_out) return HILC_ERR_SHAPE;
   if (n_max < 1 || m < 0 || m > n_max) return HILC_ERR_RANGE;
   if (n_max > 31 || n_max + m > MAX_N) return HILC_ERR_UNSUPPORTED;
-  const long istride = (10L * (n_max + m) * T + 7) / 8;
+  const long istride = packet_bytes<long>(n_max + m, T);
   if (istride > (1L << 29)) return HILC_ERR_SHAPE;
   const long ostride = HDR + istride;
-  const long total = (long)B * ostride;
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(packet_header_kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream,
-                     packets, nbytes, n_per_stream, kind, action, hold, counter_in, counter_out, out, out_nbytes, B, T, n_max, m,
-                     (int)istride, (int)ostride);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return launch(packet_header_kernel, threads_grid(B * ostride), stream, packets, nbytes, n_per_stream, kind, action, hold, counter_in,
+                counter_out, out, out_nbytes, B, T, n_max, m, (int)istride, (int)ostride);
 }
 
 extern "C" int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold,
@@ -165,10 +160,6 @@ extern "C" int hilc_jitter_step(const int* arrivals, const int* offsets, int max
   if (rc != HILC_OK) return rc;
   const int rw = (int)((stride + 3) / 4);
   const int aw = (int)((HDR + stride + 3) / 4);
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(jitter_step_kernel, dim3((unsigned)((B + WAVES - 1) / WAVES)), dim3(THREADS), 0, (hipStream_t)stream, arrivals,
-                     offsets, max_arrivals, aw, action, hold, n_per_stream, lost, fec, packets, state, meta, ring, B, T, n_max, m, order,
-                     conceal != 0 ? 1 : 0, depth, capacity, (int)stride, rw);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return launch(jitter_step_kernel, waves_grid(B), stream, arrivals, offsets, max_arrivals, aw, action, hold, n_per_stream, lost, fec,
+                packets, state, meta, ring, B, T, n_max, m, order, conceal != 0 ? 1 : 0, depth, capacity, (int)stride, rw);
 }

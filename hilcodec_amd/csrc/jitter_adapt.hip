@@ -23,20 +23,20 @@ __device__ __forceinline__ void clear_control(int* ad, int C, int depth) {
 
 __device__ __forceinline__ int sign_of(int v) { return (v > 0) - (v < 0); }
 
-// one wave per slot (4 per workgroup), the shape of jitter_step_kernel; every branch but the body copies is wave-uniform
+// one wave per slot, the shape of jitter_step_kernel; every branch but the body copies is wave-uniform
 __global__ __launch_bounds__(THREADS) void jitter_adapt_step_kernel(
     const int* __restrict__ arr, const int* __restrict__ off, int max_a, int aw, const int* __restrict__ action, int* __restrict__ hold,
     int* __restrict__ n_per_stream, int* __restrict__ lost, int* __restrict__ fec, uint8_t* __restrict__ packets, int* __restrict__ state,
     int* __restrict__ meta, int* __restrict__ ring, int* __restrict__ adapt, int B, int T, int n_max, int m, int order, int conceal,
     int depth, int C, int stride, int rw, int headroom, int max_late, int window, int resync, int force_windows) {
-  const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + ((int)threadIdx.x >> 6));
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
+  const Wave me = this_wave(B);
+  if (!me.ok) return;
+  const int b = me.b, lane = me.lane();
   int* st = state + (long)b * ST_WORDS;
   int* arow = adapt + (long)b * AD_WORDS;
   int* mrow = meta + (long)b * C;
   int* rrow = ring + (long)b * C * rw;
-  const bool start = action != nullptr && action[b] != 0;
+  const bool start = is_reset(action, b);
   int s[ST_WORDS], ad[AD_WORDS];
 #pragma unroll
   for (int k = 0; k < ST_WORDS; ++k) s[k] = start ? 0 : st[k];
@@ -196,11 +196,7 @@ extern "C" int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, i
   if (window < 1 || resync < 2 || force_windows < 0) return HILC_ERR_RANGE;
   const int rw = (int)((stride + 3) / 4);
   const int aw = (int)((HDR + stride + 3) / 4);
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(jitter_adapt_step_kernel, dim3((unsigned)((B + WAVES - 1) / WAVES)), dim3(THREADS), 0, (hipStream_t)stream,
-                     arrivals, offsets, max_arrivals, aw, action, hold, n_per_stream, lost, fec, packets, state, meta, ring, adapt, B, T,
-                     n_max, m, order, conceal != 0 ? 1 : 0, depth, capacity, (int)stride, rw, headroom, max_late, window, resync,
-                     force_windows);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return launch(jitter_adapt_step_kernel, waves_grid(B), stream, arrivals, offsets, max_arrivals, aw, action, hold, n_per_stream, lost,
+                fec, packets, state, meta, ring, adapt, B, T, n_max, m, order, conceal != 0 ? 1 : 0, depth, capacity, (int)stride, rw,
+                headroom, max_late, window, resync, force_windows);
 }

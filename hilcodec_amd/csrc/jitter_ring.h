@@ -6,15 +6,15 @@
 // words).  Ring of slot b: meta int32 [C] (jitter.meta_word, 0 when free) and body int32 [C][rw], rw = ceil(stride / 4), the packet
 // body zero past its length.  Lane j of the slot's wave owns body word j (and j + 64, ...) in every pass, so a body stored by an
 // arrival and read back when played is read by the lane that wrote it; the meta words live in lanes 0..C-1 and move by shuffles.
+// The wave-per-slot shape and the packet length: slot.h.
 #pragma once
-#include "common.h"
+#include "slot.h"
 
 namespace jring {
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
+using namespace slot;
+
 constexpr int HDR = 3;              // wire.TRANSPORT_HEADER
-constexpr int MAX_N = 32;           // primary + redundant stages: as hilc_rvq_decode_packed
 constexpr int MAX_ORDER = 16;       // dtx.MAX_ORDER
 
 // jitter.py: ST_* / STAT_* / META_*
@@ -24,10 +24,6 @@ constexpr int STAT_DECODED = 10, STAT_FEC = 11, STAT_LOST = 12, STAT_NOISE = 13;
 constexpr int ST_WORDS = 14;
 constexpr uint32_t META_SID = 1u << 16, META_FEC = 1u << 17;
 constexpr int META_N_SHIFT = 18;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ int pbytes(int n, int T) { return (10 * n * T + 7) >> 3; }   // wire.packet_bytes
 
 __device__ __forceinline__ int int16_of(int v) { return ((v + 0x8000) & 0xFFFF) - 0x8000; }
 
@@ -64,7 +60,7 @@ __device__ __forceinline__ Arrival parse_arrival(const int* __restrict__ rec, in
     else if (p.sid)
       p.ok = order >= 0 && p.n == 0 && p.body == 1 + order;
     else
-      p.ok = p.n >= 1 && p.n <= n_max && p.body == (p.fb ? pbytes(p.n + m, T) : pbytes(p.n, T));
+      p.ok = p.n >= 1 && p.n <= n_max && p.body == (p.fb ? packet_bytes(p.n + m, T) : packet_bytes(p.n, T));
   }
   return p;
 }
@@ -143,7 +139,7 @@ static inline int check_args(const void* arrivals, const void* offsets, int max_
   if (n_max < 1 || m < 0 || m > n_max || order < -1 || order > MAX_ORDER) return HILC_ERR_RANGE;
   if (capacity < 2 || capacity > 32 || (capacity & (capacity - 1)) || depth < 0 || depth > capacity - 2) return HILC_ERR_RANGE;
   if (n_max > 31 || n_max + m > MAX_N) return HILC_ERR_UNSUPPORTED;
-  *stride = (10L * (n_max + m) * T + 7) / 8;
+  *stride = packet_bytes<long>(n_max + m, T);
   if (*stride > (1L << 29) || (order >= 0 && 1 + order > *stride)) return HILC_ERR_SHAPE;
   return HILC_OK;
 }

@@ -3,33 +3,25 @@
 // hilcodec_amd/mixer.py.  Two launches, because the selection needs every slot's score:
 //
 //   hilc_mix_levels  per slot, the float64 energy of its output row (64 lane partials, added in lane order) and the peak-hold score
-//                    max(E, prev / 2), updated in place (prev = 0 on a hop with an action).  One wave per slot.
+//                    max(E, prev / 2), updated in place (prev = 0 on a hop with an action).  One wave per slot (slot.h).
 //   hilc_mix_rooms   per listener slot, its room's speakers by top_k rounds of a lexicographic (score, lowest slot) arg-max over the
 //                    B slots, then the fp32 sum of the speakers other than itself in ascending slot order, clamped to [-1, 1].
 //                    One workgroup per listener; every element of `mixed` and `speakers` is written on every hop.
 //
 // No atomics; wave-uniform or workgroup-uniform branches around every barrier.
-#include "common.h"
+#include "slot.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
-constexpr int LANES = 64;
-constexpr int MAX_TOP_K = 8;
+using namespace slot;
 
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-  const long long u = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(u & 0xFFFFFFFFll), lane);
-  const int hi = __builtin_amdgcn_readlane((int)(u >> 32), lane);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
+constexpr int MAX_TOP_K = 8;
 
 __global__ __launch_bounds__(THREADS) void mix_levels_kernel(const float* __restrict__ wav, double* __restrict__ score,
                                                              const int* __restrict__ action, int B, int L) {
-  const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + ((int)threadIdx.x >> 6));
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
+  const Wave me = this_wave(B);
+  if (!me.ok) return;
+  const int b = me.b, lane = me.lane();
   const float* x = wav + (long)b * L;
   // lane l: the squares of the samples i = l (mod 64) in increasing i (each product is exact in float64, each sum rounded)
   double p = 0.0;
@@ -37,11 +29,9 @@ __global__ __launch_bounds__(THREADS) void mix_levels_kernel(const float* __rest
     const double xd = (double)x[i];
     p = __dadd_rn(p, __dmul_rn(xd, xd));
   }
-  // the 64 partials in lane order
-  double E = readlane_d(p, 0);
-#pragma unroll
-  for (int l = 1; l < LANES; ++l) E = __dadd_rn(E, readlane_d(p, l));
+  const double E = lane_ordered_sum(p);
   if (lane == 0) {
+    // slot::is_reset, spelled out: inlined from the helper, the compiler lays this branch's blocks out in another order
     const double prev = (action != nullptr && action[b] != 0) ? 0.0 : score[b];
     const double half = __dmul_rn(0.5, prev);
     score[b] = E > half ? E : half;
@@ -136,11 +126,7 @@ __global__ __launch_bounds__(THREADS) void mix_rooms_kernel(const float* __restr
 extern "C" int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) {
   if (!wav || !score) return HILC_ERR_NULL;
   if (B < 1 || L < 1) return HILC_ERR_SHAPE;
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(mix_levels_kernel, dim3((unsigned)((B + WAVES - 1) / WAVES)), dim3(THREADS), 0, (hipStream_t)stream, wav, score,
-                     action, B, L);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return launch(mix_levels_kernel, waves_grid(B), stream, wav, score, action, B, L);
 }
 
 extern "C" int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B,
@@ -148,9 +134,5 @@ extern "C" int hilc_mix_rooms(const float* wav, const int* room, const double* s
   if (!wav || !room || !score || !mixed || !speakers) return HILC_ERR_NULL;
   if (B < 1 || L < 1) return HILC_ERR_SHAPE;
   if (top_k < 1 || top_k > MAX_TOP_K) return HILC_ERR_UNSUPPORTED;
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(mix_rooms_kernel, dim3((unsigned)B), dim3(THREADS), 0, (hipStream_t)stream, wav, room, score, top_k, mixed,
-                     speakers, B, L);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return launch(mix_rooms_kernel, dim3((unsigned)B), stream, wav, room, score, top_k, mixed, speakers, B, L);
 }

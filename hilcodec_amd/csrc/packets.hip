@@ -1,31 +1,14 @@
 // Per-stream 10-bit packets of a streaming hop: the sender's last launch (codes -> packets) and the receiver's first
-// (packets -> the dequantised latent the decoder reads).
-//
-// Packet of stream b for one hop of T frames: its first n_b stages x T codes in stage-major order (stage 0's T frames
-// first), 10 bits per code, MSB first, the last byte zero-padded: ceil(10 * n_b * T / 8) bytes — the body of
-// wire.pack_indices_10bit(indices[:n_b, b:b+1, :]) without its header.  A batch of packets is `[B][stride]` bytes,
-// stride = ceil(10 * n_max * T / 8), row b's bytes past its own length zero.
-//
-// Code i of a packet occupies bits [10 i, 10 i + 10); 10 i is even, so its bit offset inside its first byte is 0, 2, 4 or 6
-// and every code lies inside two consecutive bytes, both inside the packet.
-#include "common.h"
+// (packets -> the dequantised latent the decoder reads).  The packet layout and its helpers: slot.h.
+#include "slot.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int DEQ_MAX_N = 32;       // stages staged in LDS per frame
+using namespace slot;
+
 constexpr int DEQ_MAX_FRAMES = 16;  // frames per workgroup of the packed dequantiser
 
-__device__ __forceinline__ int clamp_n(const int* n_per_stream, int b, int n_max) {
-  if (n_per_stream == nullptr) return n_max;
-  const int v = n_per_stream[b];
-  return v < 1 ? 1 : (v > n_max ? n_max : v);
-}
-
-__device__ __forceinline__ int clamp_code(int64_t k) { return (int)(k < 0 ? 0 : (k > 1023 ? 1023 : k)); }
-
-// one thread per output byte: byte j of stream b holds bits [8 j, 8 j + 8) of the packet, i.e. parts of codes
-// i0 = 8 j / 10 and i0 + 1 (a 20-bit window, the byte at bit offset 8 j - 10 i0 in {0, 2, 4, 6, 8} of it)
+// one thread per output byte
 __global__ __launch_bounds__(THREADS) void pack_codes_kernel(const int64_t* __restrict__ indices, const int* __restrict__ n_per_stream,
                                                              uint8_t* __restrict__ packets, int* __restrict__ nbytes, int B, int T,
                                                              int n_max, int stride) {
@@ -33,26 +16,25 @@ __global__ __launch_bounds__(THREADS) void pack_codes_kernel(const int64_t* __re
   if (e >= (long)B * stride) return;
   const int b = (int)(e / stride);
   const int j = (int)(e - (long)b * stride);
-  const int nb = clamp_n(n_per_stream, b, n_max);
+  const int nb = clamp_n(n_per_stream, b, 1, n_max);
   const int count = nb * T;
-  const int len = (10 * count + 7) >> 3;
+  const int len = packet_bytes(nb, T);
   if (j == 0) nbytes[b] = len;
   uint32_t out = 0;
   if (j < len) {
-    const int i0 = (8 * j) / 10;                       // < count because 8 j < 10 count
-    const int off = 8 * j - 10 * i0;
+    const PackedByte at = packed_byte(j);              // at.i0 < count because 8 j < 10 count
     uint32_t w = 0;
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
-      const int i = i0 + d;
+      const int i = at.i0 + d;
       uint32_t c = 0;
       if (i < count) {
         const int s = i / T, t = i - (i / T) * T;
-        c = (uint32_t)clamp_code(indices[((long)s * B + b) * T + t]);
+        c = (uint32_t)clamp_code(indices[index_at(s, B, b, T, t)]);
       }
       w = (w << 10) | c;
     }
-    out = (w >> (12 - off)) & 0xFFu;
+    out = at.of(w);
   }
   packets[e] = (uint8_t)out;
 }
@@ -63,7 +45,7 @@ __global__ __launch_bounds__(THREADS) void pack_codes_kernel(const int64_t* __re
 __global__ __launch_bounds__(THREADS) void rvq_decode_packed_kernel(const uint8_t* __restrict__ packets, const int* __restrict__ n_per_stream,
                                                                     const float* __restrict__ cb, float* __restrict__ q, int B, int C,
                                                                     int T, int K, int n_max, int stride, int F) {
-  __shared__ int codes[DEQ_MAX_FRAMES][DEQ_MAX_N];
+  __shared__ int codes[DEQ_MAX_FRAMES][MAX_N];
   __shared__ int nbs[DEQ_MAX_FRAMES];
   const long frames = (long)B * T;
   const long g0 = (long)blockIdx.x * F;
@@ -72,13 +54,11 @@ __global__ __launch_bounds__(THREADS) void rvq_decode_packed_kernel(const uint8_
     const long g = g0 + f;
     if (g >= frames) continue;
     const int b = (int)(g / T), t = (int)(g - (long)(g / T) * T);
-    const int nb = clamp_n(n_per_stream, b, n_max);
+    const int nb = clamp_n(n_per_stream, b, 1, n_max);
     if (s == 0) nbs[f] = nb;
     if (s < nb) {
       const int bit = 10 * (s * T + t);
-      const uint8_t* p = packets + (long)b * stride + (bit >> 3);
-      const uint32_t v = ((uint32_t)p[0] << 8) | (uint32_t)p[1];
-      codes[f][s] = (int)((v >> (6 - (bit & 7))) & 1023u);
+      codes[f][s] = code_at(packets + (long)b * stride, bit);
     }
   }
   __syncthreads();
@@ -100,14 +80,9 @@ extern "C" int hilc_pack_codes_10bit(const int64_t* indices, const int* n_per_st
   if (!indices || !packets || !nbytes) return HILC_ERR_NULL;
   if (B <= 0 || T <= 0) return HILC_ERR_SHAPE;
   if (n_max < 1) return HILC_ERR_RANGE;
-  const long stride = (10L * n_max * T + 7) / 8;
+  const long stride = packet_bytes<long>(n_max, T);
   if (stride > (1L << 30)) return HILC_ERR_SHAPE;
-  const long total = (long)B * stride;
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(pack_codes_kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream,
-                     indices, n_per_stream, packets, nbytes, B, T, n_max, (int)stride);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return launch(pack_codes_kernel, threads_grid(B * stride), stream, indices, n_per_stream, packets, nbytes, B, T, n_max, (int)stride);
 }
 
 extern "C" int hilc_rvq_decode_packed(const uint8_t* packets, const int* n_per_stream, const float* codebooks, float* q, int B, int C,
@@ -115,13 +90,10 @@ extern "C" int hilc_rvq_decode_packed(const uint8_t* packets, const int* n_per_s
   if (!packets || !codebooks || !q) return HILC_ERR_NULL;
   if (B <= 0 || C <= 0 || T <= 0 || K <= 0 || Nq <= 0) return HILC_ERR_SHAPE;
   if (n_max < 1 || n_max > Nq) return HILC_ERR_RANGE;
-  if (K != 1024 || n_max > DEQ_MAX_N) return HILC_ERR_UNSUPPORTED;
-  const int stride = (10 * n_max * T + 7) / 8;
+  if (K != 1024 || n_max > MAX_N) return HILC_ERR_UNSUPPORTED;
+  const int stride = packet_bytes(n_max, T);
   const int F = C >= THREADS ? 1 : (THREADS / C > DEQ_MAX_FRAMES ? DEQ_MAX_FRAMES : THREADS / C);
   const long frames = (long)B * T;
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(rvq_decode_packed_kernel, dim3((unsigned)((frames + F - 1) / F)), dim3(THREADS), 0, (hipStream_t)stream,
-                     packets, n_per_stream, codebooks, q, B, C, T, K, n_max, stride, F);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return launch(rvq_decode_packed_kernel, dim3((unsigned)((frames + F - 1) / F)), stream, packets, n_per_stream, codebooks, q, B, C, T,
+                K, n_max, stride, F);
 }

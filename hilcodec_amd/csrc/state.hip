@@ -13,11 +13,11 @@
 // hilc_state_slots_hold runs at the tail of every hop, after the last write to the block the hop wrote and to its outputs, and
 // has the same idle form.  A held stream's slices are copied back from the block the hop read (so it leaves the hop as it
 // entered it) and its output rows are set to "nothing this hop"; one more work item per held stream does the outputs.
-#include "common.h"
+#include "slot.h"
 
 namespace {
 
-constexpr int THREADS = 256;
+using slot::THREADS;
 constexpr int PASS = 4 * THREADS;   // streams scanned per pass: the LDS list holds the active streams of one pass
 constexpr int PIECE = 4096;         // floats of a record per work item: 16 per thread, one round of loads (19 items per stream)
 constexpr int APPLY_WGS = 256;      // one per CU
@@ -232,7 +232,7 @@ __device__ void clear_outputs(const HoldOutputs& o, int streams, long b) {
     for (long i = t; i < o.wav_len; i += THREADS) o.wav[b * o.wav_len + i] = 0.f;
   if (o.indices != nullptr)
     for (long i = t; i < (long)o.n_max * o.frames; i += THREADS)
-      o.indices[((i / o.frames) * streams + b) * o.frames + i % o.frames] = -1;
+      o.indices[slot::index_at(i / o.frames, streams, b, o.frames, i % o.frames)] = -1;
   if (o.packets != nullptr)
     for (long i = t; i < o.stride; i += THREADS) o.packets[b * o.stride + i] = 0;
   if (o.nbytes != nullptr && t == 0) o.nbytes[b] = 0;
@@ -287,11 +287,7 @@ extern "C" int hilc_state_slots_apply(float* block, const int64_t* slice_off, co
   if (nslices <= 0 || streams <= 0 || nrecords < 0) return HILC_ERR_SHAPE;
   if (nslices > MAX_SLICES) return HILC_ERR_UNSUPPORTED;
   const Layout L = {slice_off, slice_len, nslices};
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(state_apply_kernel, dim3(APPLY_WGS), dim3(THREADS), 0, (hipStream_t)stream, block, L, streams, action,
-                     records, nrecords);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return slot::launch(state_apply_kernel, dim3(APPLY_WGS), stream, block, L, streams, action, records, nrecords);
 }
 
 extern "C" int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices,
@@ -300,11 +296,7 @@ extern "C" int hilc_state_slots_gather(const float* block, const int64_t* slice_
   if (nslices <= 0 || streams <= 0 || nslots <= 0) return HILC_ERR_SHAPE;
   if (nslices > MAX_SLICES) return HILC_ERR_UNSUPPORTED;
   const Layout L = {slice_off, slice_len, nslices};
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(state_gather_kernel, dim3(GATHER_WGS), dim3(THREADS), 0, (hipStream_t)stream, block, L, streams, slots,
-                     nslots, records);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return slot::launch(state_gather_kernel, dim3(GATHER_WGS), stream, block, L, streams, slots, nslots, records);
 }
 
 extern "C" int hilc_state_slots_hold(const float* src, float* dst, const int64_t* slice_off, const int* slice_len, int nslices,
@@ -316,8 +308,5 @@ extern "C" int hilc_state_slots_hold(const float* src, float* dst, const int64_t
   if (nslices > MAX_SLICES) return HILC_ERR_UNSUPPORTED;
   const Layout L = {slice_off, slice_len, nslices};
   const HoldOutputs o = {wav, wav_len, indices, n_max, frames, packets, stride, nbytes};
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(state_hold_kernel, dim3(HOLD_WGS), dim3(THREADS), 0, (hipStream_t)stream, src, dst, L, streams, hold, o);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return slot::launch(state_hold_kernel, dim3(HOLD_WGS), stream, src, dst, L, streams, hold, o);
 }

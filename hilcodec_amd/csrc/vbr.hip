@@ -6,27 +6,16 @@
 //   hilc_vbr_select  per slot, the float64 distortion D[s] of the hop after s stages (the residual chain of rvq_encode_kernel replayed
 //                    from the indices; 64 lane partials per frame, added in lane order), the smallest s in [n_lo, n_b] with
 //                    D[s] <= rho D[0], an optional integer token bucket (bits of credit per slot, updated in place) that caps it, and
-//                    the rows >= n_eff of the slot's indices set to -1.  One wave per slot.
+//                    the rows >= n_eff of the slot's indices set to -1.  One wave per slot (slot.h).
 //
 // No atomics, no barriers; every output element is written on every hop.
-#include "common.h"
+#include "slot.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
-constexpr int LANES = 64;
-constexpr int MAX_N = 32;          // stages: D[0..n] sits in lanes 0..n
-constexpr int MAX_J = 8;           // channels per lane: C <= 512
+using namespace slot;
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-  const long long u = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(u & 0xFFFFFFFFll), lane);
-  const int hi = __builtin_amdgcn_readlane((int)(u >> 32), lane);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
+constexpr int MAX_J = 8;           // channels per lane: C <= 512 (and n <= MAX_N: D[0..n] sits in lanes 0..n)
 
 __global__ __launch_bounds__(THREADS) void vbr_select_kernel(const float* __restrict__ z, int64_t* indices,
                                                              const float* __restrict__ codebooks, const int* __restrict__ n_per_stream,
@@ -34,9 +23,9 @@ __global__ __launch_bounds__(THREADS) void vbr_select_kernel(const float* __rest
                                                              int* __restrict__ credit, int* __restrict__ n_eff,
                                                              double* __restrict__ distortion, int B, int T, int C, int K, int n, int n_lo,
                                                              double rho, int stage_bits, int rate_bits, int burst_bits) {
-  const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + ((int)threadIdx.x >> 6));
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
+  const Wave me = this_wave(B);
+  if (!me.ok) return;
+  const int b = me.b, lane = me.lane();
   const int J = C >> 6;
   const int nb = n_per_stream == nullptr ? n : clampi(__builtin_amdgcn_readfirstlane(n_per_stream[b]), 1, n);
   const int lo = n_lo < nb ? n_lo : nb;
@@ -62,14 +51,10 @@ __global__ __launch_bounds__(THREADS) void vbr_select_kernel(const float* __rest
             const double rd = (double)r[j];
             p = __dadd_rn(p, __dmul_rn(rd, rd));
           }
-        // the 64 partials in lane order
-        double e = readlane_d(p, 0);
-#pragma unroll
-        for (int l = 1; l < LANES; ++l) e = __dadd_rn(e, readlane_d(p, l));
-        const double sum = __dadd_rn(acc, e);
+        const double sum = __dadd_rn(acc, lane_ordered_sum(p));
         acc = lane == s ? sum : acc;
         if (s < nb) {
-          const long long code = indices[((long)s * B + b) * T + t];      // wave-uniform
+          const long long code = indices[index_at(s, B, b, T, t)];        // wave-uniform
           const int k = __builtin_amdgcn_readfirstlane((int)(code < 0 ? 0 : (code > K - 1 ? K - 1 : code)));
           const float* cb = codebooks + ((long)s * K + k) * C + lane;
 #pragma unroll
@@ -97,11 +82,7 @@ __global__ __launch_bounds__(THREADS) void vbr_select_kernel(const float* __rest
     n_eff[b] = ne;
     if (credit != nullptr) credit[b] = (int)cr;
   }
-  const int cut = (n - ne) * T;                           // the rows >= n_eff of this slot
-  for (int i = lane; i < cut; i += LANES) {
-    const int s = ne + i / T, t = i - (i / T) * T;
-    indices[((long)s * B + b) * T + t] = -1;
-  }
+  clear_rows(indices, ne, n, B, b, T, lane);              // the rows >= n_eff of this slot
 }
 
 }  // namespace
@@ -119,10 +100,6 @@ extern "C" int hilc_vbr_select(const float* z, int64_t* indices, const float* co
       return HILC_ERR_RANGE;
   }
   if (n > MAX_N || (C & 63) != 0 || C > 64 * MAX_J) return HILC_ERR_UNSUPPORTED;
-  HILC_CLEAR_ERROR();
-  hipLaunchKernelGGL(vbr_select_kernel, dim3((unsigned)((B + WAVES - 1) / WAVES)), dim3(THREADS), 0, (hipStream_t)stream, z, indices,
-                     codebooks, n_per_stream, action, hold, credit, n_eff, distortion, B, T, C, K, n, n_lo, rho, stage_bits, rate_bits,
-                     burst_bits);
-  HILC_CHECK_LAUNCH();
-  return HILC_OK;
+  return launch(vbr_select_kernel, waves_grid(B), stream, z, indices, codebooks, n_per_stream, action, hold, credit, n_eff, distortion,
+                B, T, C, K, n, n_lo, rho, stage_bits, rate_bits, burst_bits);
 }

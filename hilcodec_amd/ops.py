@@ -824,6 +824,13 @@ def _packet_stride(n: int, T: int) -> int:
     return (10 * n * T + 7) // 8                      # wire.packet_bytes
 
 
+def _rows(op: str, B: int, **rows) -> None:
+    """the optional per-slot rows of a side kernel: each one given has B entries"""
+    for name, row in rows.items():
+        if row is not None and row.numel() != B:
+            raise RuntimeError(f"{op}: {name} needs {B} entries")
+
+
 def _pack_codes_10bit(indices, n_clip):
     n, B, T = indices.shape
     packets = _new(indices, B, _packet_stride(n, T), dtype=torch.uint8)
@@ -922,9 +929,7 @@ def _pack_codes_10bit_fec(indices, n_clip, prev_in, prev_out, action, hold, m):
     W = 1 + m * T
     if prev_in.shape != (B, W) or prev_out.shape != (B, W) or prev_in.dtype != torch.int32 or prev_out.dtype != torch.int32:
         raise RuntimeError(f"pack_codes_10bit_fec: prev_in and prev_out must be int32 [{B}, {W}]")
-    for name, row in (("n_clip", n_clip), ("action", action), ("hold", hold)):
-        if row is not None and row.numel() != B:
-            raise RuntimeError(f"pack_codes_10bit_fec: {name} needs {B} entries")
+    _rows("pack_codes_10bit_fec", B, n_clip=n_clip, action=action, hold=hold)
     packets = _new(indices, B, _packet_stride(n + m, T), dtype=torch.uint8)
     nbytes = _new(indices, B, dtype=torch.int32)
     check(lib.hilc_pack_codes_10bit_fec(_ptr(indices, torch.int64), _ptr(n_clip, torch.int32), _ptr(prev_in, torch.int32),
@@ -969,9 +974,7 @@ def _dtx_encode(x, action, hold, run, packets, nbytes, indices, prev, level_thr,
         raise RuntimeError(f"dtx_encode: indices must be [n, {B}, {T}]")
     if packets.dim() != 2 or packets.shape[0] != B or nbytes.numel() != B or level_thr.numel() != 127:
         raise RuntimeError(f"dtx_encode: packets must be [{B}, stride], nbytes [{B}], level_thr [127]")
-    for name, row in (("action", action), ("hold", hold)):
-        if row is not None and row.numel() != B:
-            raise RuntimeError(f"dtx_encode: {name} needs {B} entries")
+    _rows("dtx_encode", B, action=action, hold=hold)
     if prev is not None and (prev.dim() != 2 or prev.shape[0] != B):
         raise RuntimeError(f"dtx_encode: prev must be [{B}, words]")
     kind = _new(run, B, dtype=torch.int32)
@@ -995,9 +998,7 @@ def _cng_synth(packets, action, hold, state, wav, restore, gains, order):
         raise RuntimeError(f"cng_synth: wav must be a contiguous [{B}, 1, 320 T]")
     if packets.dim() != 2 or packets.shape[0] != B or state.shape != (B, 3 + 2 * order) or gains.numel() != 128:
         raise RuntimeError(f"cng_synth: packets must be [{B}, stride], state [{B}, {3 + 2 * order}], gains [128]")
-    for name, row in (("action", action), ("restore", restore)):
-        if row is not None and row.numel() != B:
-            raise RuntimeError(f"cng_synth: {name} needs {B} entries")
+    _rows("cng_synth", B, action=action, restore=restore)
     check(lib.hilc_cng_synth(_ptr(packets, torch.uint8), _ptr(action, torch.int32), _ptr(hold, torch.int32), _ptr(state, torch.int32),
                              _ptr(wav), _ptr(restore, torch.int32), _ptr(gains), B, wav.shape[2] // 320, order, packets.shape[1],
                              _stream()), "hilc_cng_synth")
@@ -1016,9 +1017,7 @@ def _packet_header(packets, nbytes, n_clip, kind, action, hold, ctr_in, ctr_out,
         raise RuntimeError(f"packet_header: packets must be [B, {_packet_stride(n + m, frames)}] and nbytes [B]")
     if ctr_in.numel() != B or ctr_out.numel() != B:
         raise RuntimeError(f"packet_header: the counter rows need {B} entries")
-    for name, row in (("n_clip", n_clip), ("kind", kind), ("action", action), ("hold", hold)):
-        if row is not None and row.numel() != B:
-            raise RuntimeError(f"packet_header: {name} needs {B} entries")
+    _rows("packet_header", B, n_clip=n_clip, kind=kind, action=action, hold=hold)
     out = _new(packets, B, 3 + packets.shape[1], dtype=torch.uint8)
     out_nbytes = _new(packets, B, dtype=torch.int32)
     check(lib.hilc_packet_header(_ptr(packets, torch.uint8), _ptr(nbytes, torch.int32), _ptr(n_clip, torch.int32), _ptr(kind, torch.int32),
@@ -1033,24 +1032,30 @@ _register("packet_header", "(Tensor packets, Tensor nbytes, Tensor? n_clip, Tens
           (packets.new_empty(packets.shape[0], 3 + packets.shape[1]), packets.new_empty(packets.shape[0], dtype=torch.int32)))
 
 
-def _jitter_step(arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, n, m, frames, order, depth):
+def _jitter_args(op, arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, n, m, frames, order, depth, adapt=None):
+    """the shape checks of a jitter step and the arguments both entry points begin with"""
     B = hold.numel()
     stride = _packet_stride(n + m, frames)
     aw = (3 + stride + 3) // 4
     if arrivals.dim() != 2 or arrivals.shape[1] != 1 + aw or offsets.numel() != B + 1:
-        raise RuntimeError(f"jitter_step: arrivals must be [A, {1 + aw}] and offsets [{B + 1}]")
-    if packets.shape != (B, stride) or state.shape != (B, 14) or meta.dim() != 2 or meta.shape[0] != B:
-        raise RuntimeError(f"jitter_step: packets must be [{B}, {stride}], state [{B}, 14], meta [{B}, C]")
+        raise RuntimeError(f"{op}: arrivals must be [A, {1 + aw}] and offsets [{B + 1}]")
+    if (packets.shape != (B, stride) or state.shape != (B, 14) or (adapt is not None and adapt.shape != (B, 12)) or meta.dim() != 2
+            or meta.shape[0] != B):
+        raise RuntimeError(f"{op}: packets must be [{B}, {stride}], state [{B}, 14], " + ("" if adapt is None else f"adapt [{B}, 12], ")
+                           + f"meta [{B}, C]")
     C = meta.shape[1]
     if ring.shape != (B, C, (stride + 3) // 4):
-        raise RuntimeError(f"jitter_step: ring must be [{B}, {C}, {(stride + 3) // 4}]")
-    for name, row in (("action", action), ("n_slot", n_slot), ("lost", lost), ("fec", fec)):
-        if row is not None and row.numel() != B:
-            raise RuntimeError(f"jitter_step: {name} needs {B} entries")
-    check(lib.hilc_jitter_step(_ptr(arrivals, torch.int32), _ptr(offsets, torch.int32), arrivals.shape[0], _ptr(action, torch.int32),
-                               _ptr(hold, torch.int32), _ptr(n_slot, torch.int32), _ptr(lost, torch.int32), _ptr(fec, torch.int32),
-                               _ptr(packets, torch.uint8), _ptr(state, torch.int32), _ptr(meta, torch.int32), _ptr(ring, torch.int32), B,
-                               frames, n, m, order, int(lost is not None), depth, C, _stream()), "hilc_jitter_step")
+        raise RuntimeError(f"{op}: ring must be [{B}, {C}, {(stride + 3) // 4}]")
+    _rows(op, B, action=action, n_slot=n_slot, lost=lost, fec=fec)
+    return (_ptr(arrivals, torch.int32), _ptr(offsets, torch.int32), arrivals.shape[0], _ptr(action, torch.int32), _ptr(hold, torch.int32),
+            _ptr(n_slot, torch.int32), _ptr(lost, torch.int32), _ptr(fec, torch.int32), _ptr(packets, torch.uint8), _ptr(state, torch.int32),
+            _ptr(meta, torch.int32), _ptr(ring, torch.int32), B, frames, n, m, order, int(lost is not None), depth, C)
+
+
+def _jitter_step(arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, n, m, frames, order, depth):
+    args = _jitter_args("jitter_step", arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, n, m, frames, order,
+                        depth)
+    check(lib.hilc_jitter_step(*args, _stream()), "hilc_jitter_step")
 
 
 _register("jitter_step", "(Tensor arrivals, Tensor offsets, Tensor? action, Tensor(a!) hold, Tensor(b!) n_slot, Tensor(c!)? lost, "
@@ -1059,28 +1064,12 @@ _register("jitter_step", "(Tensor arrivals, Tensor offsets, Tensor? action, Tens
           lambda arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, n, m, frames, order, depth: None)
 
 
-
 def _jitter_adapt_step(arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, adapt, n, m, frames, order, depth,
                        headroom, max_late, window, resync, force_windows):
-    B = hold.numel()
-    stride = _packet_stride(n + m, frames)
-    aw = (3 + stride + 3) // 4
-    if arrivals.dim() != 2 or arrivals.shape[1] != 1 + aw or offsets.numel() != B + 1:
-        raise RuntimeError(f"jitter_adapt_step: arrivals must be [A, {1 + aw}] and offsets [{B + 1}]")
-    if packets.shape != (B, stride) or state.shape != (B, 14) or adapt.shape != (B, 12) or meta.dim() != 2 or meta.shape[0] != B:
-        raise RuntimeError(f"jitter_adapt_step: packets must be [{B}, {stride}], state [{B}, 14], adapt [{B}, 12], meta [{B}, C]")
-    C = meta.shape[1]
-    if ring.shape != (B, C, (stride + 3) // 4):
-        raise RuntimeError(f"jitter_adapt_step: ring must be [{B}, {C}, {(stride + 3) // 4}]")
-    for name, row in (("action", action), ("n_slot", n_slot), ("lost", lost), ("fec", fec)):
-        if row is not None and row.numel() != B:
-            raise RuntimeError(f"jitter_adapt_step: {name} needs {B} entries")
-    check(lib.hilc_jitter_adapt_step(_ptr(arrivals, torch.int32), _ptr(offsets, torch.int32), arrivals.shape[0],
-                                     _ptr(action, torch.int32), _ptr(hold, torch.int32), _ptr(n_slot, torch.int32),
-                                     _ptr(lost, torch.int32), _ptr(fec, torch.int32), _ptr(packets, torch.uint8),
-                                     _ptr(state, torch.int32), _ptr(meta, torch.int32), _ptr(ring, torch.int32), B, frames, n, m, order,
-                                     int(lost is not None), depth, C, _ptr(adapt, torch.int32), headroom, max_late, window, resync,
-                                     force_windows, _stream()), "hilc_jitter_adapt_step")
+    args = _jitter_args("jitter_adapt_step", arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, n, m, frames,
+                        order, depth, adapt)
+    check(lib.hilc_jitter_adapt_step(*args, _ptr(adapt, torch.int32), headroom, max_late, window, resync, force_windows, _stream()),
+          "hilc_jitter_adapt_step")
 
 
 _register("jitter_adapt_step", "(Tensor arrivals, Tensor offsets, Tensor? action, Tensor(a!) hold, Tensor(b!) n_slot, Tensor(c!)? lost, "
@@ -1133,9 +1122,7 @@ def _vbr_select(z, indices, codebooks, n_clip, action, hold, credit, n_lo, rho, 
     B, T, Cc = z.shape
     n = indices.shape[0]
     Nq, K, _ = codebooks.shape
-    for name, row in (("n_clip", n_clip), ("action", action), ("hold", hold), ("credit", credit)):
-        if row is not None and row.numel() != B:
-            raise RuntimeError(f"vbr_select: {name} needs {B} entries")
+    _rows("vbr_select", B, n_clip=n_clip, action=action, hold=hold, credit=credit)
     n_eff = _new(z, B, dtype=torch.int32)
     distortion = _new(z, B, n + 1, dtype=torch.float64)
     check(lib.hilc_vbr_select(_ptr(z), _ptr(indices, torch.int64), _ptr(codebooks), _ptr(n_clip, torch.int32), _ptr(action, torch.int32),

@@ -73,6 +73,40 @@ def test_error_codes_without_gpu():
     assert lib.hilc_resblock(one, one, one, one, one, one, one, one, 1, 96, 16, 1.0, 1.0, None) == -4  # y aliases x
 
 
+def test_stage_limit_is_refused_at_33_and_passed_at_32():
+    """csrc/slot.h MAX_N = 32 is the one staging limit of the packet kernels: every launcher that checks it answers unsupported (-4)
+    to n_max + m = 33 (or n_max = 33) and lets 32 past that check.  Argument checks only, no kernel is launched: the 32-stage calls
+    carry a hop of 2^25 frames, whose packet row the check behind the limit refuses as a shape (-1) — the same call with one frame
+    and 33 stages reaches the limit, so nothing before it objects.  hilc_rvq_decode_packed and hilc_vbr_select check nothing behind
+    the limit (32 stages would launch), so only their refusal of 33 is asserted."""
+    from hilcodec_amd._lib import lib
+    p, q = ctypes.c_void_p(16), ctypes.c_void_p(32)
+    big = 1 << 25
+
+    def fec_pack(n, m, T):
+        return lib.hilc_pack_codes_10bit_fec(p, None, p, q, None, None, p, p, 1, T, n, m, None)
+
+    def fec_select(n, m, T):
+        return lib.hilc_fec_select(p, p, p, p, 1, T, n, m, None)
+
+    def header(n, m, T):
+        return lib.hilc_packet_header(p, p, None, None, None, None, p, q, p, p, 1, T, n, m, None)
+
+    def jitter(n, m, T):
+        return lib.hilc_jitter_step(p, p, 0, None, p, p, None, p, p, p, p, p, 1, T, n, m, -1, 0, 2, 8, None)
+
+    def jitter_adapt(n, m, T):
+        return lib.hilc_jitter_adapt_step(p, p, 0, None, p, p, None, p, p, p, p, p, 1, T, n, m, -1, 0, 2, 8, p, 1, 2, 4, 2, 0, None)
+
+    for call in (fec_pack, fec_select, header, jitter, jitter_adapt):
+        assert call(31, 2, 1) == -4, call.__name__
+        assert call(30, 2, big) == -1, call.__name__
+    assert lib.hilc_conceal_prepare(p, p, p, p, p, p, p, 1, 1, 33, 4, None) == -4
+    assert lib.hilc_conceal_prepare(p, p, p, p, p, p, p, 1, big, 32, 4, None) == -1
+    assert lib.hilc_rvq_decode_packed(p, None, p, p, 1, 128, 1, 1024, 33, 33, None) == -4
+    assert lib.hilc_vbr_select(p, p, p, None, None, None, None, p, p, 1, 1, 128, 1024, 33, 33, 1, 0.5, 0, 0, 0, None) == -4
+
+
 def test_cpu_tensors_raise():
     import hilcodec_amd
     from hilcodec_amd import ops
