@@ -161,18 +161,11 @@ def decode_stream(model, indices: Tensor, num_quantizers: int, num_frames: int =
 
 
 def build_streaming_model(name: str, checkpoint: Optional[str], device) -> torch.nn.Module:
-    from .models.hilcodec.streaming import HILCodec
-    mk = synth.model_kwargs(name)
-    smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
-    model = HILCodec(24000, **smk).eval()
+    sd = None
     if checkpoint:
         sd = torch.load(checkpoint, map_location="cpu")
         sd = sd.get("model", sd)
-    else:
-        sd = synth.synth_state_dict(name, seed=7)
-    model.load_offline_state_dict(sd)
-    model.remove_weight_reparameterizations()
-    return model.to(device)
+    return synth.streaming_model(name, state_dict=sd).to(device)
 
 
 def main(argv=None):

@@ -261,3 +261,20 @@ def synth_state_dict(name: str = "hil_speech", seed: int = 7,
             sd[key] = sd[key[:-len("ema_embed")] + "embed"].clone() * ema_init
     # keep module order identical to the reference (ema_embed sits between embed and ema_num)
     return {k: sd[k] for k in shapes}
+
+
+def streaming_kwargs(name: str = "hil_speech") -> dict:
+    """:func:`model_kwargs` for the streaming `HILCodec` constructor.  It is causal by construction, pads its caches with
+    zeros and has a fixed STFT basis, so it does not take `causal`, `pad_mode` or `spec_learnable`."""
+    return {k: v for k, v in model_kwargs(name).items() if k not in ("spec_learnable", "causal", "pad_mode")}
+
+
+def streaming_model(name: str = "hil_speech", seed: int = 7,
+                    state_dict: "Optional[Dict[str, torch.Tensor]]" = None) -> torch.nn.Module:
+    """The eval streaming `HILCodec` (on the CPU) with an offline state-dict loaded and the weight reparameterisations removed:
+    `state_dict` if given, :func:`synth_state_dict` `(name, seed)` otherwise."""
+    from .models.hilcodec.streaming import HILCodec      # here, so that synth imports on its own
+    model = HILCodec(24000, **streaming_kwargs(name)).eval()
+    model.load_offline_state_dict(synth_state_dict(name, seed) if state_dict is None else state_dict)
+    model.remove_weight_reparameterizations()
+    return model

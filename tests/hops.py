@@ -1,0 +1,104 @@
+"""What the hop features' tests share: the C header read back (for the one test that proves the ctypes binding against it, and for
+each feature's "my entry points exist" test), and the small helpers of the GPU hop tests.  A plain module, imported as
+`from tests.hops import ...`; fixtures stay in the test modules."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import torch
+
+from hilcodec_amd import synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "hilcodec_amd.h")
+DEV = torch.device("cuda:0")
+HOP = 320
+
+
+# ---------------------------------------------------------------- include/hilcodec_amd.h
+_KINDS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def _kind(decl):
+    """the ctypes kind of one C parameter or field declaration: any pointer is a c_void_p, a scalar its own type"""
+    return ctypes.c_void_p if "*" in decl else _KINDS[decl.replace("const ", " ").split()[0]]
+
+
+def parse_header():
+    """(prototypes, structs) of the header, comments stripped: {name: [kind per parameter]} of every `hilc_*(...);` prototype and
+    {name: [(field, kind)]} of every `typedef struct hilc_*_params`, a list such as `float in_scale, out_scale;` split"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(HEADER).read(), flags=re.S)
+    protos = {}
+    for name, args in re.findall(r"^(?:int|const char\*)\s+(hilc_\w+)\s*\(([^)]*)\)\s*;", text, re.M):
+        protos[name] = [] if args.strip() == "void" else [_kind(a) for a in args.split(",")]
+    structs = {}
+    for body, name in re.findall(r"typedef struct \w+\s*\{(.*?)\}\s*(hilc_\w+_params)\s*;", text, re.S):
+        fields = structs[name] = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            fields += [(piece.split()[-1].lstrip("*"), _kind(decl)) for piece in decl.split(",")]
+    return protos, structs
+
+
+def assert_entry_points(names, in_abi16_line=False):
+    """each of `names` is declared at the start of a header line, (on request) named in the `#define HILC_ABI_VERSION 16` line,
+    exported by the library and bound; that the binding's types are the header's is test_api_cpu's to prove, for all of them"""
+    from hilcodec_amd import _lib
+    assert _lib.ABI_VERSION == 16 and _lib.lib.hilc_abi_version() == 16
+    header = open(HEADER).read()
+    abi_line = re.search(r"#define HILC_ABI_VERSION 16\b.*", header).group(0)
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in names:
+        assert re.search(r"^int " + name + r"\(", header, re.M), name
+        assert not in_abi16_line or name in abi_line, name
+        assert hasattr(lib, name) and name in _lib.SIGNATURES, name
+
+
+# ---------------------------------------------------------------- models
+def bare_model(name="hil_speech"):
+    """the streaming model as constructed, no weights loaded: for tests of layouts and queues, which never run it"""
+    from hilcodec_amd.models.hilcodec.streaming import HILCodec
+    return HILCodec(24000, **synth.streaming_kwargs(name)).eval()
+
+
+def build_streaming(seed=7, name="hil_speech"):
+    """(streaming model, offline kwargs, offline state dict): the last two are what the oracle's legs take"""
+    sd = synth.synth_state_dict(name, seed)
+    return synth.streaming_model(name, state_dict=sd), synth.model_kwargs(name), sd
+
+
+# ---------------------------------------------------------------- hops, caches, packet rows
+def chunk(x, h, hop=HOP):
+    return x[:, :, hop * h:hop * (h + 1)].contiguous()
+
+
+def same_indices(g_idx, e_idx):
+    r = e_idx.shape[0]
+    return torch.equal(g_idx[:r], e_idx) and bool((g_idx[r:] == -1).all())
+
+
+def caches_equal(a_list, b_list):
+    return all(torch.equal(a, b) for a, b in zip(a_list, b_list))
+
+
+def row_bytes(packets, b, length=None):
+    row = packets[b].tolist()
+    return bytes(row if length is None else row[:length])
+
+
+def put_row(packets, b, blob):
+    packets[b] = 0
+    packets[b, :len(blob)] = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
+
+
+def arrival_records(slots, packets, nbytes, tbytes, B, max_a):
+    """the device form of one hop's arrivals, as GraphedDecodeHop.play stages them: records grouped by slot (stable), offsets"""
+    aw = 1 + (tbytes + 3) // 4
+    rec = np.zeros((max_a, aw), dtype=np.int32)
+    order = np.argsort(np.asarray(slots, dtype=np.int64), kind="stable")
+    A = len(slots)
+    rec[:A, 0] = np.asarray(nbytes, dtype=np.int64)[order]
+    rec.view(np.uint8)[:A, 4:4 + tbytes] = np.asarray(packets, dtype=np.uint8).reshape(A, tbytes)[order]
+    offs = np.zeros(B + 1, dtype=np.int32)
+    offs[1:] = np.cumsum(np.bincount(np.asarray(slots, dtype=np.int64), minlength=B))
+    return torch.from_numpy(rec).to(DEV), torch.from_numpy(offs).to(DEV)

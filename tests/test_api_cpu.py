@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from hilcodec_amd import synth
+from tests.hops import parse_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -26,6 +27,43 @@ def test_library_exports_every_declared_symbol():
         assert name in declared, f"{name} bound in _lib.py but not declared in the header"
     assert _lib.lib.hilc_abi_version() == _lib.ABI_VERSION
     assert b"num_quantizers" in _lib.lib.hilc_error_string(-5)
+
+
+def test_binding_matches_header_type_for_type():
+    """The ctypes binding is the one link to include/hilcodec_amd.h that no compiler checks (the .hip files include the header):
+    every prototype's parameter kinds equal `_lib.SIGNATURES[name]` element for element (any pointer <-> c_void_p, int, long, float,
+    double), every prototype is bound and every bound name declared, and the five `ctypes.Structure` mirrors have the fields of the
+    header's `hilc_*_params` structs in name, order and kind."""
+    from hilcodec_amd import _lib
+    protos, structs = parse_header()
+    apart = {"hilc_abi_version", "hilc_error_string", "hilc_last_hip_error"}          # bound one by one in _lib._load
+    assert apart <= set(protos) and set(protos) - apart == set(_lib.SIGNATURES)
+    assert len(protos) >= 67
+    for name, kinds in _lib.SIGNATURES.items():
+        assert kinds == protos[name], name
+    mirrors = {"hilc_resblock_params": _lib.ResblockParams, "hilc_up_params": _lib.UpParams, "hilc_down_params": _lib.DownParams,
+               "hilc_post_params": _lib.PostParams, "hilc_spec0_params": _lib.Spec0Params}
+    assert set(structs) == set(mirrors)
+    for name, mirror in mirrors.items():
+        assert mirror._fields_ == structs[name], name
+
+
+@pytest.mark.parametrize("name", ["hil_speech", "hil_music"])
+def test_synth_streaming_model_is_the_one_recipe(name):
+    """synth.streaming_model: eval mode, the same tensors on every call, the model stream_driver builds without a checkpoint,
+    and a given state dict in place of the seed's"""
+    from hilcodec_amd import stream_driver
+
+    def same(a, b):
+        a, b = a.state_dict(), b.state_dict()
+        return list(a) == list(b) and all(torch.equal(a[k], b[k]) for k in a)
+
+    m = synth.streaming_model(name)
+    assert not m.training and not any(sub.training for sub in m.modules())
+    assert same(m, synth.streaming_model(name))
+    assert same(m, stream_driver.build_streaming_model(name, None, "cpu"))
+    assert same(synth.streaming_model(name, state_dict=synth.synth_state_dict(name, 3)), synth.streaming_model(name, seed=3))
+    assert not same(m, synth.streaming_model(name, seed=3))
 
 
 def test_error_codes_without_gpu():
@@ -170,11 +208,8 @@ def test_weight_folds_bit_exact():
 def test_streaming_module_tree_and_mapping():
     from hilcodec_amd.models.hilcodec.streaming import HILCodec
     from oracle import hilcodec_oracle as O
-    mk = dict(synth.model_kwargs("hil_speech"))
     full = synth.model_kwargs("hil_speech")
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    m = HILCodec(24000, **mk).eval()
+    m = HILCodec(24000, **synth.streaming_kwargs("hil_speech")).eval()
     x = torch.zeros(5, 1)
     ce, cd = m.initialize_cache(x)
     enc_shapes, dec_shapes = O.stream_cache_shapes(full)
@@ -307,7 +342,7 @@ def test_streaming_model_takes_a_weight_standardised_checkpoint(golden):
     from hilcodec_amd import synth
     from hilcodec_amd.models.hilcodec.streaming import HILCodec as S
     g = golden("ws_hil_speech")
-    mk = {k: v for k, v in synth.model_kwargs("hil_speech").items() if k not in ("spec_learnable", "causal", "pad_mode")}
+    mk = synth.streaming_kwargs("hil_speech")
     sd = synth.synth_state_dict("hil_speech", seed=int(g["weight_seed"]))
     with pytest.raises(ValueError):
         S(24000, norm="weight_standardization", **mk)

@@ -63,13 +63,7 @@ def test_offline_plan_on_meta_tensors(name):
 
 
 def test_streaming_hop_on_meta_tensors_with_state_block():
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs("hil_speech"))
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    m = HILCodec(24000, **mk).eval()
-    m.load_offline_state_dict(synth.synth_state_dict("hil_speech", seed=7))
-    m.remove_weight_reparameterizations()
+    m = synth.streaming_model()
     es = engine.finalize_spec(engine.spec_to(m.encoder.build_spec("cpu"), "meta"))
     ds = engine.finalize_spec(engine.spec_to(m.decoder.build_spec("cpu"), "meta"))
     B = 6

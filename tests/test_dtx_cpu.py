@@ -4,7 +4,6 @@ their argument checks, their custom ops and fake kernels, DtxConfig, the SID wir
 (No kernel is launched here.)"""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,23 +11,14 @@ import torch
 
 from hilcodec_amd import dtx
 from hilcodec_amd.graph_step import SessionQueue
+from tests.hops import assert_entry_points
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("hilc_dtx_encode", "hilc_cng_synth")
 
 
 def test_dtx_symbols_exported_and_declared():
-    from hilcodec_amd import _lib
-    assert _lib.ABI_VERSION == 16 and _lib.lib.hilc_abi_version() == 16
-    header = open(os.path.join(ROOT, "include", "hilcodec_amd.h")).read()
-    abi_line = re.search(r"#define HILC_ABI_VERSION 16\b.*", header).group(0)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NEW:
-        assert re.search(r"^int " + name + r"\(", header, re.M), name
-        assert name in abi_line, name
-        assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert len(_lib.SIGNATURES["hilc_dtx_encode"]) == 20
-    assert len(_lib.SIGNATURES["hilc_cng_synth"]) == 12
+    assert_entry_points(NEW, in_abi16_line=True)
     import hilcodec_amd
     assert not hasattr(hilcodec_amd, "dtx") or "dtx" not in open(os.path.join(ROOT, "hilcodec_amd", "__init__.py")).read()
 

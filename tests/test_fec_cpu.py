@@ -2,38 +2,18 @@
 points (additive under ABI 16) and their argument checks, their custom ops and fake kernels, the wire helpers that define the FEC
 packet format, and the host-side checks of step(fec=...).  (No kernel is launched here.)"""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
-from hilcodec_amd import synth, wire
+from hilcodec_amd import wire
+from tests.hops import assert_entry_points, bare_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("hilc_pack_codes_10bit_fec", "hilc_fec_select")
 
 
-def _model(name="hil_speech"):
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs(name))
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    return HILCodec(24000, **mk).eval()
-
-
 def test_fec_symbols_exported_and_declared():
-    from hilcodec_amd import _lib
-    assert _lib.ABI_VERSION == 16 and _lib.lib.hilc_abi_version() == 16
-    header = open(os.path.join(ROOT, "include", "hilcodec_amd.h")).read()
-    abi_line = re.search(r"#define HILC_ABI_VERSION 16\b.*", header).group(0)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NEW:
-        assert re.search(r"^int " + name + r"\(", header, re.M), name
-        assert name in abi_line, name
-        assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert len(_lib.SIGNATURES["hilc_pack_codes_10bit_fec"]) == 13
-    assert len(_lib.SIGNATURES["hilc_fec_select"]) == 9
+    assert_entry_points(NEW, in_abi16_line=True)
 
 
 def test_pack_codes_10bit_fec_argument_checks():
@@ -138,7 +118,7 @@ def test_fec_primary_zeroes_trailing_bits():
 
 def test_session_queue_fec_checks():
     from hilcodec_amd import graph_step as G
-    q = G.SessionQueue(6, 8, 2, G.state_layout(_model(), 6, "dec"), one_sided=True)
+    q = G.SessionQueue(6, 8, 2, G.state_layout(bare_model(), 6, "dec"), one_sided=True)
     assert q.fec_slots(None) == [] and q.fec_slots(()) == []
     assert q.fec_slots([4, 1, 4], hold=[0], lost=[2]) == [1, 4]
     assert q.fec_slots(torch.tensor([3])) == [3]
@@ -160,7 +140,7 @@ def test_session_queue_fec_checks():
 
 def test_session_queue_n_min():
     from hilcodec_amd import graph_step as G
-    q = G.SessionQueue(4, 8, 2, G.state_layout(_model(), 4, "enc"), one_sided=True)
+    q = G.SessionQueue(4, 8, 2, G.state_layout(bare_model(), 4, "enc"), one_sided=True)
     q.start(0, n=1)
     q.n_min = 3                                           # what GraphedEncodeHop(fec_stages=3) sets
     for bad in (1, 2, 9):

@@ -55,14 +55,8 @@ def test_offline_encoder_decoder_compile_fullgraph():
 
 def test_streaming_hop_compile_fullgraph_with_state_block():
     from hilcodec_amd.graph_step import StateBlock
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
     dev = torch.device("cuda:0")
-    mk = dict(synth.model_kwargs("hil_speech"))
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    m = HILCodec(24000, **mk).eval()
-    m.load_offline_state_dict(synth.synth_state_dict("hil_speech", seed=7))
-    m.remove_weight_reparameterizations()
+    m = synth.streaming_model()
     B = 4
     x = synth.synth_clips(B, 640, seed=9).to(dev)
     ce, cd = m.initialize_cache(x)

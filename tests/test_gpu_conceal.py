@@ -7,24 +7,13 @@ import pytest
 import torch
 
 from hilcodec_amd import synth, wire
+from tests.hops import build_streaming, caches_equal, put_row, row_bytes
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 HOP = 320
 F = 4
-
-
-def build_streaming(seed=7, name="hil_speech"):
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs(name))
-    sd = synth.synth_state_dict(name, seed=seed)
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    model = HILCodec(24000, **mk).eval()
-    model.load_offline_state_dict(sd)
-    model.remove_weight_reparameterizations()
-    return model, synth.model_kwargs(name), sd
 
 
 @pytest.fixture(scope="module")
@@ -35,19 +24,6 @@ def built():
 @pytest.fixture(scope="module")
 def speech(built):
     return built[0]
-
-
-def caches_equal(a_list, b_list):
-    return all(torch.equal(a, b) for a, b in zip(a_list, b_list))
-
-
-def row_bytes(packets, b):
-    return bytes(packets[b].tolist())
-
-
-def put_row(packets, b, blob):
-    packets[b] = 0
-    packets[b, :len(blob)] = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
 
 
 def ramp_torch(wav_rows, a, c, G, W):

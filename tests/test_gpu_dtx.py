@@ -15,21 +15,9 @@ DEV = torch.device("cuda:0")
 HOP = 320
 
 
-def build_streaming(seed=7, name="hil_speech"):
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs(name))
-    sd = synth.synth_state_dict(name, seed=seed)
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    model = HILCodec(24000, **mk).eval()
-    model.load_offline_state_dict(sd)
-    model.remove_weight_reparameterizations()
-    return model
-
-
 @pytest.fixture(scope="module")
 def speech():
-    return build_streaming()
+    return synth.streaming_model()
 
 
 def ar2(gen, B, S, a1=-1.2, a2=0.5):

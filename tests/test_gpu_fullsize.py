@@ -86,13 +86,9 @@ def test_full_batch_properties(golden, name):
 
 def test_streaming_equals_offline_encoder_on_zero_caches():
     """A single full-length streaming call on zero caches is the offline causal encoder."""
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec as S
     dev = torch.device("cuda:0")
     model, mk = build("hil_speech")
-    smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
-    sm = S(24000, **smk).eval()
-    sm.load_offline_state_dict(synth.synth_state_dict("hil_speech", seed=7))
-    sm.remove_weight_reparameterizations()
+    sm = synth.streaming_model()
     x = synth.synth_clips(4, 9600, seed=77).to(dev)
     ce, _ = sm.initialize_cache(x)
     with torch.no_grad():

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from hilcodec_amd import synth, wire
+from tests.hops import caches_equal, chunk, same_indices
 
 pytestmark = pytest.mark.gpu
 
@@ -13,34 +14,9 @@ DEV = torch.device("cuda:0")
 HOP = 320
 
 
-def build_streaming(seed=7, name="hil_speech"):
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs(name))
-    sd = synth.synth_state_dict(name, seed=seed)
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    model = HILCodec(24000, **mk).eval()
-    model.load_offline_state_dict(sd)
-    model.remove_weight_reparameterizations()
-    return model
-
-
 @pytest.fixture(scope="module")
 def speech():
-    return build_streaming()
-
-
-def chunk(x, h):
-    return x[:, :, HOP * h: HOP * (h + 1)].contiguous()
-
-
-def same_indices(g_idx, e_idx):
-    r = e_idx.shape[0]
-    return torch.equal(g_idx[:r], e_idx) and bool((g_idx[r:] == -1).all())
-
-
-def caches_equal(a_list, b_list):
-    return all(torch.equal(a, b) for a, b in zip(a_list, b_list))
+    return synth.streaming_model()
 
 
 class EagerHeld:

@@ -8,6 +8,7 @@ import torch
 
 from hilcodec_amd import dtx, jitter, synth, wire
 from hilcodec_amd.jitter import AdaptConfig, JitterConfig, JitterModel
+from tests.hops import arrival_records
 
 pytestmark = pytest.mark.gpu
 
@@ -16,34 +17,9 @@ HOP = 320
 ADAPT = AdaptConfig(window=8, resync=3, force_windows=2)     # every branch fires within 150 hops
 
 
-def build_streaming(seed=7, name="hil_speech"):
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs(name))
-    sd = synth.synth_state_dict(name, seed=seed)
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    model = HILCodec(24000, **mk).eval()
-    model.load_offline_state_dict(sd)
-    model.remove_weight_reparameterizations()
-    return model
-
-
 @pytest.fixture(scope="module")
 def speech():
-    return build_streaming()
-
-
-def arrival_records(slots, packets, nbytes, tbytes, B, max_a):
-    """the device form of one hop's arrivals, as GraphedDecodeHop.play stages them: records grouped by slot (stable), offsets"""
-    aw = 1 + (tbytes + 3) // 4
-    rec = np.zeros((max_a, aw), dtype=np.int32)
-    order = np.argsort(np.asarray(slots, dtype=np.int64), kind="stable")
-    A = len(slots)
-    rec[:A, 0] = np.asarray(nbytes, dtype=np.int64)[order]
-    rec.view(np.uint8)[:A, 4:4 + tbytes] = np.asarray(packets, dtype=np.uint8).reshape(A, tbytes)[order]
-    offs = np.zeros(B + 1, dtype=np.int32)
-    offs[1:] = np.cumsum(np.bincount(np.asarray(slots, dtype=np.int64), minlength=B))
-    return torch.from_numpy(rec).to(DEV), torch.from_numpy(offs).to(DEV)
+    return synth.streaming_model()
 
 
 class Network:

@@ -6,27 +6,12 @@ import pytest
 import torch
 
 from hilcodec_amd import synth
+from tests.hops import build_streaming, chunk, same_indices
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 HOP = 320
-
-
-def build_streaming(seed=7, name="hil_speech"):
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs(name))
-    sd = synth.synth_state_dict(name, seed=seed)
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    model = HILCodec(24000, **mk).eval()
-    model.load_offline_state_dict(sd)
-    model.remove_weight_reparameterizations()
-    return model, synth.model_kwargs(name), sd
-
-
-def chunk(x, h):
-    return x[:, :, HOP * h: HOP * (h + 1)].contiguous()
 
 
 def eager_hop(model, x, ce, cd, n):
@@ -35,12 +20,6 @@ def eager_hop(model, x, ce, cd, n):
         idx = model.quantizer(z, n)
         wav, cd = model.decoder(model.dequantizer(idx, n), *cd)
     return z, idx, wav, ce, cd
-
-
-def same_indices(g_idx, e_idx):
-    """graph indices have the graph's n rows; the eager per-clip call has max(n) rows; rows beyond hold -1 in both forms"""
-    r = e_idx.shape[0]
-    return torch.equal(g_idx[:r], e_idx) and bool((g_idx[r:] == -1).all())
 
 
 def caches_equal(g, ce, cd, rows=None):

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from hilcodec_amd import synth, wire
+from tests.hops import chunk
 
 pytestmark = pytest.mark.gpu
 
@@ -13,25 +14,9 @@ DEV = torch.device("cuda:0")
 HOP = 320
 
 
-def build_streaming(seed=7, name="hil_speech"):
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs(name))
-    sd = synth.synth_state_dict(name, seed=seed)
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    model = HILCodec(24000, **mk).eval()
-    model.load_offline_state_dict(sd)
-    model.remove_weight_reparameterizations()
-    return model
-
-
 @pytest.fixture(scope="module")
 def speech():
-    return build_streaming()
-
-
-def chunk(x, h, hop=HOP):
-    return x[:, :, hop * h: hop * (h + 1)].contiguous()
+    return synth.streaming_model()
 
 
 def host_packets(idx, n_list):
@@ -84,7 +69,7 @@ def test_pack_codes_clamps_out_of_range():
 @pytest.mark.parametrize("name,n_max", [("hil_speech", 8), ("hil_music", 12)])
 def test_rvq_decode_packed_matches_rvq_decode(name, n_max):
     from hilcodec_amd import ops
-    model = build_streaming(seed=3, name=name)
+    model = synth.streaming_model(name, 3)
     cb = model.dequantizer._tables(DEV).codebooks
     for B, T in ((37, 1), (37, 2), (1024, 1), (5, 5)):
         idx, n_list = ragged(B, n_max, T, seed=B + 10 * T + n_max)

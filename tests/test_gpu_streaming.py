@@ -5,24 +5,13 @@ import pytest
 import torch
 
 from hilcodec_amd import synth
+from tests.hops import build_streaming
 
 pytestmark = pytest.mark.gpu
 
 
 def T(a):
     return torch.from_numpy(np.asarray(a))
-
-
-def build_streaming(seed=7, name="hil_speech"):
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs(name))
-    sd = synth.synth_state_dict(name, seed=seed)
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    model = HILCodec(24000, **mk).eval()
-    model.load_offline_state_dict(sd)
-    model.remove_weight_reparameterizations()
-    return model, synth.model_kwargs(name), sd
 
 
 def test_streaming_golden(golden):
@@ -99,12 +88,9 @@ def test_streaming_unmerged_equals_merged():
     except for the wav_std scalings, which (as in the reference) only exist in merged form."""
     from hilcodec_amd.models.hilcodec.streaming import HILCodec
     dev = torch.device("cuda:0")
-    mk = dict(synth.model_kwargs("hil_speech"))
     sd = synth.synth_state_dict("hil_speech", seed=7)
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    m1 = HILCodec(24000, **mk).eval(); m1.load_offline_state_dict(sd)
-    m2 = HILCodec(24000, **mk).eval(); m2.load_offline_state_dict(sd); m2.remove_weight_reparameterizations()
+    m1 = HILCodec(24000, **synth.streaming_kwargs("hil_speech")).eval(); m1.load_offline_state_dict(sd)
+    m2 = synth.streaming_model(state_dict=sd)
     x = synth.synth_clips(1, 640, seed=2).to(dev)
     c1, _ = m1.initialize_cache(x); c2, _ = m2.initialize_cache(x)
     z1, _ = m1.encoder(x / 0.1122080159, *c1)      # un-merged conv_pre lacks the 1/wav_std
@@ -479,9 +465,8 @@ def test_streaming_weight_standardised_checkpoint(golden, gname):
     from hilcodec_amd.models.hilcodec.streaming import HILCodec
     g = golden(gname)
     dev = torch.device("cuda:0")
-    mk = {k: v for k, v in synth.model_kwargs("hil_speech").items() if k not in ("spec_learnable", "causal", "pad_mode")}
     sd = synth.synth_state_dict("hil_speech", seed=int(g["weight_seed"]))
-    model = HILCodec(24000, **mk).eval()
+    model = HILCodec(24000, **synth.streaming_kwargs("hil_speech")).eval()
     model.load_offline_state_dict(sd, norm="weight_standardization",
                                   norm_kwargs={"eps": float(g["ws_eps"]), "scale": float(g["ws_scale"])})
     model.remove_weight_reparameterizations()

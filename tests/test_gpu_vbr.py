@@ -162,22 +162,10 @@ def test_vbr_select_many_stages(n):
 
 
 # ---------------------------------------------------------------- the sender
-def build_streaming(seed=7, name="hil_speech"):
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs(name))
-    sd = synth.synth_state_dict(name, seed=seed)
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    model = HILCodec(24000, **mk).eval()
-    model.load_offline_state_dict(sd)
-    model.remove_weight_reparameterizations()
-    return model
-
-
 @pytest.fixture(scope="module")
 def speech():
     """the streaming model with falling per-stage codebooks, scaled to its latents (module docstring)"""
-    model = build_streaming()
+    model = synth.streaming_model()
     x = synth.synth_clips(8, HOP, seed=1).to(DEV)
     with torch.no_grad():
         z, _ = model.encoder(x, *[c.to(DEV) for c in model.initialize_cache(x)[0]])

@@ -1,33 +1,15 @@
 """CPU: held streams of the graphed hops — the hilc_state_slots_hold entry point (additive under ABI 16) and its argument
 checks, its custom op and fake kernel, and the host-side hold / stop bookkeeping of SessionQueue.  (No kernel is launched here.)"""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
-from hilcodec_amd import synth
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _model(name="hil_speech"):
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs(name))
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    return HILCodec(24000, **mk).eval()
+from tests.hops import assert_entry_points, bare_model
 
 
 def test_hold_symbol_exported_and_declared():
-    from hilcodec_amd import _lib
-    assert _lib.ABI_VERSION == 16 and _lib.lib.hilc_abi_version() == 16
-    header = open(os.path.join(ROOT, "include", "hilcodec_amd.h")).read()
-    assert re.search(r"#define HILC_ABI_VERSION 16\b", header)
-    assert re.search(r"\bint hilc_state_slots_hold\(", header)
-    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "hilc_state_slots_hold")
-    assert len(_lib.SIGNATURES["hilc_state_slots_hold"]) == 16
+    assert_entry_points(["hilc_state_slots_hold"])
 
 
 def test_hold_argument_checks():
@@ -58,7 +40,7 @@ def test_hold_argument_checks():
 def test_hold_op_registered_with_fake_kernel():
     from torch._subclasses.fake_tensor import FakeTensorMode
     from hilcodec_amd import graph_step as G
-    layout = G.state_layout(_model(), 5)
+    layout = G.state_layout(bare_model(), 5)
     assert hasattr(torch.ops.hilcodec, "state_slots_hold")
     schema = str(torch.ops.hilcodec.state_slots_hold.default._schema)
     for arg in ("Tensor(a!) dst", "Tensor(b!)? wav", "Tensor(c!)? indices", "Tensor(d!)? packets", "Tensor(e!)? nbytes"):
@@ -78,7 +60,7 @@ def test_hold_op_registered_with_fake_kernel():
 
 def test_session_queue_hold_and_stop():
     from hilcodec_amd import graph_step as G
-    q = G.SessionQueue(6, 8, 2, G.state_layout(_model(), 6))
+    q = G.SessionQueue(6, 8, 2, G.state_layout(bare_model(), 6))
     assert q.held == frozenset() and q.stopped == ()
     for bad in (-1, 6, 100):
         with pytest.raises(IndexError):

@@ -3,8 +3,6 @@ its custom op and fake kernel, AdaptConfig / JitterConfig(adapt=), and the rules
 healthy stream is left alone, the drift / restart / burst traces the fixed buffer fails on, and hand-built traces for each rule.
 (No kernel is launched here.)"""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,8 +10,8 @@ import torch
 
 from hilcodec_amd import jitter, wire
 from hilcodec_amd.jitter import AdaptConfig, JitterConfig, JitterModel
+from tests.hops import assert_entry_points
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "hilc_jitter_adapt_step"
 T = 1
 
@@ -21,12 +19,7 @@ T = 1
 # ---------------------------------------------------------------- the entry point, the op, the configs
 def test_adapt_symbol_exported_and_declared():
     from hilcodec_amd import _lib
-    assert _lib.ABI_VERSION == 16 and _lib.lib.hilc_abi_version() == 16
-    header = open(os.path.join(ROOT, "include", "hilcodec_amd.h")).read()
-    abi_line = re.search(r"#define HILC_ABI_VERSION 16\b.*", header).group(0)
-    assert re.search(r"^int " + NAME + r"\(", header, re.M) and NAME in abi_line
-    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), NAME)
-    assert len(_lib.SIGNATURES[NAME]) == 27 and len(_lib.SIGNATURES["hilc_jitter_step"]) == 21
+    assert_entry_points([NAME], in_abi16_line=True)
     assert _lib.SIGNATURES[NAME][:20] == _lib.SIGNATURES["hilc_jitter_step"][:20]
     assert jitter.ST_WORDS == 14 and jitter.AD_WORDS == 12 and len(jitter.STAT_NAMES) == 9
 

@@ -2,8 +2,6 @@
 custom ops and fake kernels, MixConfig, and the rules (mixer.MixModel) on hand-built cases with literal expected values.  (No kernel
 is launched here.)"""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -11,23 +9,13 @@ import torch
 
 from hilcodec_amd import mixer
 from hilcodec_amd.mixer import MixConfig, MixModel
+from tests.hops import assert_entry_points
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("hilc_mix_levels", "hilc_mix_rooms")
 
 
 def test_mix_symbols_exported_and_declared():
-    from hilcodec_amd import _lib
-    assert _lib.ABI_VERSION == 16 and _lib.lib.hilc_abi_version() == 16
-    header = open(os.path.join(ROOT, "include", "hilcodec_amd.h")).read()
-    abi_line = re.search(r"#define HILC_ABI_VERSION 16\b.*", header).group(0)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NEW:
-        assert re.search(r"^int " + name + r"\(", header, re.M), name
-        assert name in abi_line, name
-        assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert len(_lib.SIGNATURES["hilc_mix_levels"]) == 6
-    assert len(_lib.SIGNATURES["hilc_mix_rooms"]) == 9
+    assert_entry_points(NEW, in_abi16_line=True)
 
 
 def test_mix_levels_argument_checks():

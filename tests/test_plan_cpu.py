@@ -56,12 +56,7 @@ def _specs(model_name, streaming):
     mk = dict(synth.model_kwargs(model_name))
     sd = synth.synth_state_dict(model_name, seed=7)
     if streaming:
-        from hilcodec_amd.models.hilcodec.streaming import HILCodec
-        for k in ("spec_learnable", "causal", "pad_mode"):
-            mk.pop(k)
-        m = HILCodec(24000, **mk).eval()
-        m.load_offline_state_dict(sd)
-        m.remove_weight_reparameterizations()
+        m = synth.streaming_model(model_name, state_dict=sd)
     else:
         m = hilcodec_amd.HILCodec(24000, 1, **mk).eval()
         m.load_state_dict(sd, strict=False)

@@ -2,17 +2,14 @@
 frequency response, the torch statement of the kernel against scipy's upfirdn, streaming with history against one offline call, the
 argument checks, the C entry point's refusals and the state-layout records that carry the history.  (No kernel is launched here.)"""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from hilcodec_amd import synth
 from hilcodec_amd.resample import BASE_RATE, RATES, design, hop_samples, reference
+from tests.hops import assert_entry_points, bare_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # other rate -> ((L, M, Q) into 24 kHz, (L, M, Q) out of 24 kHz, the smallest frame multiple of a hop)
 TABLE = {
     8000: ((3, 1, 80), (1, 3, 240), 3),
@@ -23,14 +20,6 @@ TABLE = {
     48000: ((1, 2, 160), (2, 1, 80), 1),
 }
 DIRECTIONS = [(r, BASE_RATE) for r in RATES] + [(BASE_RATE, r) for r in RATES]
-
-
-def _model(name="hil_speech"):
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs(name))
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    return HILCodec(24000, **mk).eval()
 
 
 def _full_filter(spec):
@@ -150,11 +139,8 @@ def test_public_names():
 
 
 def test_c_entry_point_checks():
-    from hilcodec_amd import _lib
-    header = open(os.path.join(ROOT, "include", "hilcodec_amd.h")).read()
-    assert re.search(r"\bint hilc_resample_poly\(", header)
-    assert len(_lib.SIGNATURES["hilc_resample_poly"]) == 11
-    lib = _lib.lib
+    from hilcodec_amd._lib import lib
+    assert_entry_points(["hilc_resample_poly"])
     p, q = ctypes.c_void_p(16), ctypes.c_void_p(32)
     # (x, hist_in, hist_out, y, taps, B, T_in, L, M, Q, stream)
     assert lib.hilc_resample_poly(None, None, None, p, p, 1, 640, 1, 2, 160, None) == -2
@@ -183,7 +169,7 @@ def test_op_registered_with_fake_and_refuses_cpu():
 @pytest.mark.parametrize("side,rate", [("enc", 48000), ("dec", 16000)])
 def test_state_layout_with_history(side, rate):
     from hilcodec_amd import graph_step as G
-    model = _model()
+    model = bare_model()
     s = design(rate, BASE_RATE) if side == "enc" else design(BASE_RATE, rate)
     plain = G.state_layout(model, 5, side)
     layout = G.state_layout(model, 5, side, s.history)

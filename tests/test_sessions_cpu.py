@@ -1,35 +1,17 @@
 """CPU: the per-stream session layer of the graphed hop — ABI 16 entry points, their argument checks, the state-block layout
 the kernels address, the fake kernels of the two new ops, and the host-side session checks.  (No kernel is launched here.)"""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
-from hilcodec_amd import synth
+from tests.hops import assert_entry_points, bare_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("hilc_state_slots_apply", "hilc_state_slots_gather")
 
 
-def _model(name="hil_speech"):
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs(name))
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    return HILCodec(24000, **mk).eval()
-
-
 def test_abi16_symbols_exported_and_declared():
-    from hilcodec_amd import _lib
-    assert _lib.ABI_VERSION == 16 and _lib.lib.hilc_abi_version() == 16
-    header = open(os.path.join(ROOT, "include", "hilcodec_amd.h")).read()
-    assert re.search(r"#define HILC_ABI_VERSION 16\b", header)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NEW:
-        assert re.search(r"\bint " + name + r"\(", header), name
-        assert hasattr(lib, name) and name in _lib.SIGNATURES
+    assert_entry_points(NEW)
 
 
 def test_state_slots_argument_checks():
@@ -60,7 +42,7 @@ def test_layout_matches_state_block_views(name):
     """the table the kernels address (graph_step.state_layout, host-only) is the StateBlock's views: slice k of stream b at
     buffer + off[k] + b * lens[k], 16-B aligned slice bases, one record = 76 479 floats"""
     from hilcodec_amd import graph_step as G
-    model = _model(name)
+    model = bare_model(name)
     B = 3
     layout = G.state_layout(model, B)
     assert layout.record_len == 76479 and len(layout.shapes) == 52 and layout.n_enc == 22 and layout.streams == B
@@ -87,7 +69,7 @@ def test_layout_matches_state_block_views(name):
 def test_session_ops_registered_with_fake_kernels():
     from torch._subclasses.fake_tensor import FakeTensorMode
     from hilcodec_amd import graph_step as G, ops
-    layout = G.state_layout(_model(), 5)
+    layout = G.state_layout(bare_model(), 5)
     for name in ("state_slots_apply", "state_slots_gather"):
         assert hasattr(torch.ops.hilcodec, name)
     schema = str(torch.ops.hilcodec.state_slots_apply.default._schema)
@@ -116,7 +98,7 @@ def test_session_ops_registered_with_fake_kernels():
 def test_session_queue_checks():
     """everything a GraphedHop(sessions=True) refuses is refused by the host-side queue before any launch"""
     from hilcodec_amd import graph_step as G
-    model = _model()
+    model = bare_model()
     layout = G.state_layout(model, 6)
     q = G.SessionQueue(6, 8, 2, layout)
     for bad in (-1, 6, 100):

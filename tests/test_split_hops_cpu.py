@@ -2,24 +2,14 @@
 wire.pack_indices_10bit), the two packet entry points of the C ABI and their argument checks, the fake kernels of their ops, the
 one-sided state layout and the one-sided session checks.  (No kernel is launched here.)"""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
-from hilcodec_amd import synth, wire
+from hilcodec_amd import wire
+from tests.hops import assert_entry_points, bare_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("hilc_pack_codes_10bit", "hilc_rvq_decode_packed")
-
-
-def _model(name="hil_speech"):
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec
-    mk = dict(synth.model_kwargs(name))
-    for k in ("spec_learnable", "causal", "pad_mode"):
-        mk.pop(k)
-    return HILCodec(24000, **mk).eval()
 
 
 def test_stream_packet_is_the_10bit_body():
@@ -56,13 +46,7 @@ def test_packet_n_rejects_other_lengths():
 
 
 def test_packet_symbols_exported_and_declared():
-    from hilcodec_amd import _lib
-    header = open(os.path.join(ROOT, "include", "hilcodec_amd.h")).read()
-    assert re.search(r"#define HILC_ABI_VERSION 16\b", header)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NEW:
-        assert re.search(r"\bint " + name + r"\(", header), name
-        assert hasattr(lib, name) and name in _lib.SIGNATURES
+    assert_entry_points(NEW)
 
 
 def test_packet_argument_checks():
@@ -109,7 +93,7 @@ def test_packet_ops_registered_with_fake_kernels():
 @pytest.mark.parametrize("side", ["enc", "dec"])
 def test_one_sided_layout(side):
     from hilcodec_amd import graph_step as G
-    model = _model()
+    model = bare_model()
     B = 3
     both = G.state_layout(model, B)
     assert (both.n_enc, len(both.shapes)) == (22, 52)                      # the default is today's layout
@@ -141,7 +125,7 @@ def test_one_sided_layout(side):
 @pytest.mark.parametrize("side", ["enc", "dec"])
 def test_one_sided_session_queue_checks(side):
     from hilcodec_amd import graph_step as G
-    model = _model()
+    model = bare_model()
     layout = G.state_layout(model, 6, side)
     q = G.SessionQueue(6, 8, 2, layout, one_sided=True)
     ce, cd = model.initialize_cache(torch.zeros(1, 1, 1))

@@ -2,8 +2,6 @@
 checks, its custom op and fake kernel, VbrConfig, the constructor checks of GraphedEncodeHop(vbr=), and the rules (vbr.VbrModel) on
 hand-built cases with literal expected values.  (No kernel is launched here.)"""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -11,24 +9,13 @@ import torch
 
 from hilcodec_amd import vbr
 from hilcodec_amd.vbr import VbrConfig, VbrModel
+from tests.hops import assert_entry_points
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "hilc_vbr_select"
 
 
 def test_vbr_symbol_exported_and_declared():
-    from hilcodec_amd import _lib
-    assert _lib.ABI_VERSION == 16 and _lib.lib.hilc_abi_version() == 16
-    header = open(os.path.join(ROOT, "include", "hilcodec_amd.h")).read()
-    abi_line = re.search(r"#define HILC_ABI_VERSION 16\b.*", header).group(0)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    assert re.search(r"^int " + NAME + r"\(", header, re.M)
-    assert NAME in abi_line
-    assert hasattr(lib, NAME) and NAME in _lib.SIGNATURES
-    sig = _lib.SIGNATURES[NAME]
-    assert len(sig) == 21
-    assert sig[16] is ctypes.c_double and sig.count(ctypes.c_double) == 1          # rho
-    assert sig.count(ctypes.c_void_p) == 10 and sig.count(ctypes.c_int) == 10
+    assert_entry_points([NAME], in_abi16_line=True)
 
 
 def test_vbr_select_argument_checks():

@@ -6,14 +6,9 @@ import contextlib, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from hilcodec_amd import engine, graph_step, synth
-from hilcodec_amd.models.hilcodec.streaming import HILCodec as StreamingHILCodec
 
 dev = torch.device("cuda:0")
-mk = synth.model_kwargs("hil_speech")
-smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
-model = StreamingHILCodec(24000, **smk).eval()
-model.load_offline_state_dict(synth.synth_state_dict("hil_speech", 7))
-model.remove_weight_reparameterizations()
+model = synth.streaming_model()
 xs = [synth.synth_clips(1024, 320, seed=4321 + 7 * j).to(dev) for j in range(8)]
 real = engine.exec_overrides
 for name, over in (("decoder_stage_narrow=False (shipped)", dict(decoder_stage_narrow=False)), ("no override", {}),

@@ -11,35 +11,17 @@ timed with device events around `--hops` replays per leg and alternation.  Every
    python tools/conceal_hop_ab.py [--hops 200] [--alternations 3] [--legs abcdef] > profiles/conceal_hops.txt
 The two kernels' own times come from a separate kernel-trace run of this script (no counters in that run):
    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o t -- python tools/conceal_hop_ab.py --hops 50 --alternations 1 --legs bd"""
-import argparse
-import os
-import statistics
-import sys
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import hop_ab  # first: it puts the repository root on sys.path
 import numpy as np
 import torch
 
 from hilcodec_amd import graph_step, synth, wire
-from hilcodec_amd.models.hilcodec.streaming import HILCodec as StreamingHILCodec
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--hops", type=int, default=200)
-ap.add_argument("--alternations", type=int, default=3)
-ap.add_argument("--legs", default="abcdef")
-ap.add_argument("--streams", type=int, default=1024)
-ap.add_argument("--fade-hops", type=int, default=4)
-args = ap.parse_args()
-if not torch.cuda.is_available():
-    sys.exit("conceal_hop_ab.py needs a GPU")
+args = hop_ab.parse_args(legs="abcdef", add=lambda ap: ap.add_argument("--fade-hops", type=int, default=4))
 
 dev = torch.device("cuda:0")
 B, F = args.streams, args.fade_hops
-mk = synth.model_kwargs("hil_speech")
-smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
-model = StreamingHILCodec(24000, **smk).eval()
-model.load_offline_state_dict(synth.synth_state_dict("hil_speech", 7))
-model.remove_weight_reparameterizations()
+model = synth.streaming_model()
 stride = wire.packet_bytes(8, 1)
 gen = torch.Generator(device=dev).manual_seed(9)
 packets = [torch.randint(0, 256, (B, stride), device=dev, generator=gen, dtype=torch.uint8) for _ in range(8)]
@@ -83,30 +65,11 @@ def one(leg, i):
 def run(leg, hops):
     for i in range(5):                 # warm
         one(leg, i)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for i in range(hops):
-        one(leg, i)
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / hops
+    return hop_ab.timed(hops, lambda i: one(leg, i))
 
 
-res = {leg: [] for leg in args.legs}
 print(f"# conceal_hop_ab: {B} streams, hil_speech, frames 1, n 8, fade_hops {F}, sessions=True, {args.hops} hops per leg x "
       f"{args.alternations} alternations; {torch.cuda.get_device_name(dev)}", flush=True)
-for a in range(args.alternations):
-    order = args.legs if a % 2 == 0 else args.legs[::-1]
-    for leg in order:
-        ms = run(leg, args.hops)
-        res[leg].append(ms)
-        print(f"alt {a} {LEGS[leg][2]:48s} {ms:.4f} ms/hop", flush=True)
-print("# median over alternations; difference against the conceal=False receiver")
-for leg in args.legs:
-    m = statistics.median(res[leg])
-    rel = ""
-    if "a" in res and leg != "a":
-        b = statistics.median(res["a"])
-        rel = f"  {1e3 * (m - b):+.1f} us ({100.0 * (m - b) / b:+.2f} %) vs (a)"
-    print(f"{LEGS[leg][2]:48s} {m:.4f} ms/hop  (min {min(res[leg]):.4f}, max {max(res[leg]):.4f}){rel}", flush=True)
+res = hop_ab.alternate(args.legs, args, run, lambda leg: LEGS[leg][2], 48)
+hop_ab.report(res, "# median over alternations; difference against the conceal=False receiver",
+              lambda leg: LEGS[leg][2], 48, base=lambda leg: "a")

@@ -14,34 +14,17 @@ frames = 1, K = 8), timed with device events around `--hops` replays per leg and
 The receivers' packets are host tensors (one upload of control rows and packets per hop, as from a socket).
 The two kernels' own times come from a separate kernel-trace run of this script (no counters in that run):
    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o t -- python tools/dtx_hop_ab.py --hops 50 --alternations 1 --legs tud"""
-import argparse
-import os
-import statistics
-import sys
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import hop_ab  # first: it puts the repository root on sys.path
 import torch
 
 from hilcodec_amd import dtx, graph_step, synth, wire
-from hilcodec_amd.models.hilcodec.streaming import HILCodec as StreamingHILCodec
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--hops", type=int, default=200)
-ap.add_argument("--alternations", type=int, default=5)
-ap.add_argument("--legs", default="stuabcdhi")
-ap.add_argument("--streams", type=int, default=1024)
-args = ap.parse_args()
-if not torch.cuda.is_available():
-    sys.exit("dtx_hop_ab.py needs a GPU")
+args = hop_ab.parse_args(legs="stuabcdhi", alternations=5)
 
 dev = torch.device("cuda:0")
 B, n, K = args.streams, 8, 8
 cfg = dtx.DtxConfig(order=K)
-mk = synth.model_kwargs("hil_speech")
-smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
-model = StreamingHILCodec(24000, **smk).eval()
-model.load_offline_state_dict(synth.synth_state_dict("hil_speech", 7))
-model.remove_weight_reparameterizations()
+model = synth.streaming_model()
 x = synth.synth_clips(B, 320 * 8, seed=11).to(dev)
 loud = [x[:, :, 320 * i:320 * (i + 1)].contiguous() for i in range(8)]
 quiet = [torch.zeros_like(c) for c in loud]
@@ -94,35 +77,23 @@ def one(leg, i):
 def run(leg, hops):
     for i in range(12):                # warm (past the hangover for the silent sender)
         one(leg, i)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for i in range(hops):
-        one(leg, i)
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / hops
+    return hop_ab.timed(hops, lambda i: one(leg, i))
 
 
-res = {leg: [] for leg in args.legs}
 print(f"# dtx_hop_ab: {B} streams, hil_speech, frames 1, n {n}, K {K}, {cfg}, sessions=True, packets on the host, {args.hops} hops "
       f"per leg x {args.alternations} alternations; {torch.cuda.get_device_name(dev)}", flush=True)
-for a in range(args.alternations):
-    order = args.legs if a % 2 == 0 else args.legs[::-1]
-    for leg in order:
-        ms = run(leg, args.hops)
-        res[leg].append(ms)
-        print(f"alt {a} {LEGS[leg][3]:44s} {ms:.4f} ms/hop", flush=True)
+res = hop_ab.alternate(args.legs, args, run, lambda leg: LEGS[leg][3], 44)
 if "u" in hoppers:
     kinds = hoppers["u"].kind.cpu()
     print(f"# (u) kinds after the run: {[(k, int((kinds == k).sum())) for k in (dtx.SPEECH, dtx.SID, dtx.SILENT)]}")
-print("# median over alternations; difference against the same side without DTX / CN")
-for leg in args.legs:
-    med = statistics.median(res[leg])
-    base = "s" if LEGS[leg][0] == "enc" else {"c": "h", "d": "i"}.get(leg, "a")
-    rel = ""
-    for bl in dict.fromkeys((base, "s" if LEGS[leg][0] == "enc" else "a")):
-        if bl in res and leg != bl:
-            b = statistics.median(res[bl])
-            rel += f"  {1e3 * (med - b):+.1f} us ({100.0 * (med - b) / b:+.2f} %) vs ({bl})"
-    print(f"{LEGS[leg][3]:44s} {med:.4f} ms/hop  (min {min(res[leg]):.4f}, max {max(res[leg]):.4f}){rel}", flush=True)
+
+
+def bases(leg):
+    """the same side without DTX / CN traffic, then the same side's parent graph"""
+    if LEGS[leg][0] == "enc":
+        return "s"
+    return {"c": "h", "d": "i"}.get(leg, "a") + "a"
+
+
+hop_ab.report(res, "# median over alternations; difference against the same side without DTX / CN",
+              lambda leg: LEGS[leg][3], 44, base=bases)

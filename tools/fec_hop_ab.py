@@ -15,36 +15,22 @@ the receivers also have conceal=True (the receiver FEC pairs with: what FEC cann
 socket) instead of device tensors (a control-row upload plus a device copy of the packets).
 The two kernels' own times come from a separate kernel-trace run of this script (no counters in that run):
    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o t -- python tools/fec_hop_ab.py --hops 50 --alternations 1 --legs tbd"""
-import argparse
-import os
-import statistics
-import sys
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import hop_ab  # first: it puts the repository root on sys.path
 import numpy as np
 import torch
 
 from hilcodec_amd import graph_step, synth, wire
-from hilcodec_amd.models.hilcodec.streaming import HILCodec as StreamingHILCodec
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--hops", type=int, default=200)
-ap.add_argument("--alternations", type=int, default=5)
-ap.add_argument("--legs", default="stabcdz")
-ap.add_argument("--streams", type=int, default=1024)
-ap.add_argument("--fec-stages", type=int, default=2)
-ap.add_argument("--host-packets", action="store_true")
-args = ap.parse_args()
-if not torch.cuda.is_available():
-    sys.exit("fec_hop_ab.py needs a GPU")
+def options(ap):
+    ap.add_argument("--fec-stages", type=int, default=2)
+    ap.add_argument("--host-packets", action="store_true")
+
+
+args = hop_ab.parse_args(legs="stabcdz", alternations=5, add=options)
 
 dev = torch.device("cuda:0")
 B, m, n = args.streams, args.fec_stages, 8
-mk = synth.model_kwargs("hil_speech")
-smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
-model = StreamingHILCodec(24000, **smk).eval()
-model.load_offline_state_dict(synth.synth_state_dict("hil_speech", 7))
-model.remove_weight_reparameterizations()
+model = synth.streaming_model()
 gen = torch.Generator(device=dev).manual_seed(9)
 x = synth.synth_clips(B, 320 * 8, seed=11).to(dev)
 chunks = [x[:, :, 320 * i:320 * (i + 1)].contiguous() for i in range(8)]
@@ -88,31 +74,11 @@ def one(leg, i):
 def run(leg, hops):
     for i in range(5):                 # warm
         one(leg, i)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for i in range(hops):
-        one(leg, i)
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / hops
+    return hop_ab.timed(hops, lambda i: one(leg, i))
 
 
-res = {leg: [] for leg in args.legs}
 print(f"# fec_hop_ab: {B} streams, hil_speech, frames 1, n {n}, m {m}, sessions=True (receivers: conceal=True), packets on the "
       f"{'host' if args.host_packets else 'device'}, {args.hops} hops per leg x {args.alternations} alternations; {torch.cuda.get_device_name(dev)}", flush=True)
-for a in range(args.alternations):
-    order = args.legs if a % 2 == 0 else args.legs[::-1]
-    for leg in order:
-        ms = run(leg, args.hops)
-        res[leg].append(ms)
-        print(f"alt {a} {LEGS[leg][3]:44s} {ms:.4f} ms/hop", flush=True)
-print("# median over alternations; difference against the same side with fec_stages=0")
-for leg in args.legs:
-    med = statistics.median(res[leg])
-    base = "s" if LEGS[leg][0] == "enc" else "a"
-    rel = ""
-    if base in res and leg != base:
-        b = statistics.median(res[base])
-        rel = f"  {1e3 * (med - b):+.1f} us ({100.0 * (med - b) / b:+.2f} %) vs ({base})"
-    print(f"{LEGS[leg][3]:44s} {med:.4f} ms/hop  (min {min(res[leg]):.4f}, max {max(res[leg]):.4f}){rel}", flush=True)
+res = hop_ab.alternate(args.legs, args, run, lambda leg: LEGS[leg][3], 44)
+hop_ab.report(res, "# median over alternations; difference against the same side with fec_stages=0",
+              lambda leg: LEGS[leg][3], 44, base=lambda leg: "s" if LEGS[leg][0] == "enc" else "a")

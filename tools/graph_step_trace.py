@@ -66,7 +66,6 @@ import torch
 
 from hilcodec_amd import dtx, graph_step, synth, wire
 from hilcodec_amd.jitter import JitterConfig
-from hilcodec_amd.models.hilcodec.streaming import HILCodec as StreamingHILCodec
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--log", required=True)
@@ -75,11 +74,7 @@ if not torch.cuda.is_available():
     sys.exit("graph_step_trace.py needs a GPU")
 
 dev = torch.device("cuda:0")
-mk = synth.model_kwargs("hil_speech")
-smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
-model = StreamingHILCodec(24000, **smk).eval()
-model.load_offline_state_dict(synth.synth_state_dict("hil_speech", 7))
-model.remove_weight_reparameterizations()
+model = synth.streaming_model()
 xs = [synth.synth_clips(B, HOP, seed=4321 + 7 * j).to(dev) for j in range(HOPS)]
 xs48 = [synth.synth_clips(B, HOP * 2, seed=99 + j).to(dev) for j in range(HOPS)]                 # a hop at 48 kHz
 marker = torch.full((1,), 0.5, device=dev)

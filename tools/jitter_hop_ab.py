@@ -14,38 +14,23 @@ of all slots.  Also printed: the per-hop upload bytes and the host time of a pla
    python tools/jitter_hop_ab.py --legs ABCXYZ > profiles/jitter_adapt_hops.txt
 The two kernels' own times come from a separate kernel-trace run of this script (no counters in that run):
    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o t -- python tools/jitter_hop_ab.py --hops 50 --alternations 1 --legs tB"""
-import argparse
-import os
 import statistics
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import hop_ab  # first: it puts the repository root on sys.path
 import numpy as np
 import torch
 
 from hilcodec_amd import dtx, graph_step, synth, wire
 from hilcodec_amd.jitter import AdaptConfig, JitterConfig, JitterModel
-from hilcodec_amd.models.hilcodec.streaming import HILCodec as StreamingHILCodec
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--hops", type=int, default=200)
-ap.add_argument("--alternations", type=int, default=7)
-ap.add_argument("--legs", default="stabcABC")
-ap.add_argument("--streams", type=int, default=1024)
-args = ap.parse_args()
-if not torch.cuda.is_available():
-    sys.exit("jitter_hop_ab.py needs a GPU")
+args = hop_ab.parse_args(legs="stabcABC", alternations=7)
 
 dev = torch.device("cuda:0")
 B, n, m, K, T = args.streams, 8, 2, 8, 1
 cfg = JitterConfig(depth=2, capacity=8)
 cfg_adapt = JitterConfig(depth=2, capacity=8, adapt=AdaptConfig())
-mk = synth.model_kwargs("hil_speech")
-smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
-model = StreamingHILCodec(24000, **smk).eval()
-model.load_offline_state_dict(synth.synth_state_dict("hil_speech", 7))
-model.remove_weight_reparameterizations()
+model = synth.streaming_model()
 x = synth.synth_clips(B, 320 * 8, seed=11).to(dev)
 chunks = [x[:, :, 320 * i:320 * (i + 1)].contiguous() for i in range(8)]
 tb = wire.transport_bytes(n, m, T)
@@ -140,39 +125,19 @@ def run(leg, hops):
     if LEGS[leg][0] != "enc":
         for b in range(B):               # every leg replays its trace from fresh slots (the trace starts with a start of all)
             hoppers[leg].start(b)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for i in range(hops):
-        one(leg, i)
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / hops
+    return hop_ab.timed(hops, lambda i: one(leg, i))
 
 
 for leg in args.legs:                    # warm
     run(leg, min(5, args.hops))
     host_s[leg].clear()
     sent[leg].clear()
-res = {leg: [] for leg in args.legs}
 print(f"# jitter_hop_ab: {B} streams, hil_speech, frames 1, n {n}, m {m}, K {K}, {cfg}, host packets, {args.hops} hops per leg x "
       f"{args.alternations} alternations; {torch.cuda.get_device_name(dev)}", flush=True)
-for a in range(args.alternations):
-    order = args.legs if a % 2 == 0 else args.legs[::-1]
-    for leg in order:
-        ms = run(leg, args.hops)
-        res[leg].append(ms)
-        print(f"alt {a} {LEGS[leg][2]:40s} {ms:.4f} ms/hop", flush=True)
-print("# median over alternations; (t) against (s), each play() leg against the step() leg of its mix, each adaptive leg against the "
-      "play() leg of its mix")
-for leg in args.legs:
-    med = statistics.median(res[leg])
-    base = {"t": "s", "A": "a", "B": "b", "C": "c", "X": "A", "Y": "B", "Z": "C"}.get(leg)
-    rel = ""
-    if base in res:
-        b = statistics.median(res[base])
-        rel = f"  {1e3 * (med - b):+.1f} us ({100.0 * (med - b) / b:+.2f} %) vs ({base})"
-    print(f"{LEGS[leg][2]:40s} {med:.4f} ms/hop  (min {min(res[leg]):.4f}, max {max(res[leg]):.4f}){rel}", flush=True)
+res = hop_ab.alternate(args.legs, args, run, lambda leg: LEGS[leg][2], 40)
+hop_ab.report(res, "# median over alternations; (t) against (s), each play() leg against the step() leg of its mix, each adaptive leg "
+              "against the play() leg of its mix", lambda leg: LEGS[leg][2], 40,
+              base={"t": "s", "A": "a", "B": "b", "C": "c", "X": "A", "Y": "B", "Z": "C"}.get)
 print("# per-hop upload (bytes, one pinned copy) and host time of a call (median, us; includes waiting for the previous upload)")
 for leg in args.legs:
     kind, mix, name = LEGS[leg]

@@ -52,11 +52,7 @@ if __name__ == "__main__":
             q, _, _, idx = model.quantizer(z, None, return_indices=True)
             return model.decoder(q)
     else:
-        from hilcodec_amd.models.hilcodec.streaming import HILCodec as StreamingHILCodec
-        smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
-        model = StreamingHILCodec(24000, **smk).eval()
-        model.load_offline_state_dict(sd)
-        model.remove_weight_reparameterizations()
+        model = synth.streaming_model(model_name, state_dict=sd)
         x = synth.synth_clips(B, T, seed=4321).to(dev)
         state = list(model.initialize_cache(x))
 

@@ -35,11 +35,7 @@ def step():
 
 
 if args.mode == "streaming":
-    from hilcodec_amd.models.hilcodec.streaming import HILCodec as StreamingHILCodec
-    smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
-    smodel = StreamingHILCodec(24000, **smk).eval()
-    smodel.load_offline_state_dict(synth.synth_state_dict(args.model, 7))
-    smodel.remove_weight_reparameterizations()
+    smodel = synth.streaming_model(args.model)
     smodel.encoder.exec_options.stage_launches = smodel.decoder.exec_options.stage_launches = not args.no_stage
     nq = mk["vq_kwargs"]["num_quantizers"]
     xs = synth.synth_clips(args.batch, 320, seed=4321).to(dev)

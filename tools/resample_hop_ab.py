@@ -10,36 +10,20 @@ and one offline line: `hilcodec_amd.resample` of 256 clips x 1 s at 48 -> 24 kHz
    python tools/resample_hop_ab.py [--hops 200] [--alternations 5] [--legs abcdefghi] > profiles/resample_hops.txt
 The kernel's own times come from a separate kernel-trace run of this script (no counters in that run):
    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o t -- python tools/resample_hop_ab.py --hops 50 --alternations 1"""
-import argparse
-import os
 import statistics
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import hop_ab  # first: it puts the repository root on sys.path
 import torch
 
 import hilcodec_amd
 from hilcodec_amd import graph_step, ops, synth
-from hilcodec_amd.models.hilcodec.streaming import HILCodec as StreamingHILCodec
 from hilcodec_amd.resample import hop_samples
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--hops", type=int, default=200)
-ap.add_argument("--alternations", type=int, default=5)
-ap.add_argument("--legs", default="abcdefghi")
-ap.add_argument("--streams", type=int, default=1024)
-ap.add_argument("--offline-reps", type=int, default=20)
-args = ap.parse_args()
-if not torch.cuda.is_available():
-    sys.exit("resample_hop_ab.py needs a GPU")
+args = hop_ab.parse_args(legs="abcdefghi", alternations=5, add=lambda ap: ap.add_argument("--offline-reps", type=int, default=20))
 
 dev = torch.device("cuda:0")
 B = args.streams
-mk = synth.model_kwargs("hil_speech")
-smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
-model = StreamingHILCodec(24000, **smk).eval()
-model.load_offline_state_dict(synth.synth_state_dict("hil_speech", 7))
-model.remove_weight_reparameterizations()
+model = synth.streaming_model()
 
 LEGS = {  # leg: (side, frames, rate, baseline leg, name)
     "a": ("enc", 1, 24000, None, "(a) sender F=1, 24 kHz (parent graph)"),
@@ -70,34 +54,14 @@ def run(leg, hops):
     h, ins = hoppers[leg], inputs[leg]
     for i in range(5):                 # warm
         h.step(*ins[i % 4])
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for i in range(hops):
-        h.step(*ins[i % 4])
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / hops
+    return hop_ab.timed(hops, lambda i: h.step(*ins[i % 4]))
 
 
-res = {leg: [] for leg in args.legs}
 print(f"# resample_hop_ab: {B} streams, hil_speech, n 8, sessions=False, {args.hops} hops per leg x {args.alternations} alternations; "
       f"{torch.cuda.get_device_name(dev)}", flush=True)
-for a in range(args.alternations):
-    order = args.legs if a % 2 == 0 else args.legs[::-1]
-    for leg in order:
-        ms = run(leg, args.hops)
-        res[leg].append(ms)
-        print(f"alt {a} {LEGS[leg][4]:42s} {ms:.4f} ms/hop", flush=True)
-print("# median over alternations; difference against the 24 kHz graph with the same frames per hop")
-for leg in args.legs:
-    m = statistics.median(res[leg])
-    base = LEGS[leg][3]
-    rel = ""
-    if base in res:
-        b = statistics.median(res[base])
-        rel = f"  {1e3 * (m - b):+.1f} us ({100.0 * (m - b) / b:+.2f} %) vs ({base})"
-    print(f"{LEGS[leg][4]:42s} {m:.4f} ms/hop  (min {min(res[leg]):.4f}, max {max(res[leg]):.4f}){rel}", flush=True)
+res = hop_ab.alternate(args.legs, args, run, lambda leg: LEGS[leg][4], 42)
+hop_ab.report(res, "# median over alternations; difference against the 24 kHz graph with the same frames per hop",
+              lambda leg: LEGS[leg][4], 42, base=lambda leg: LEGS[leg][3])
 
 # offline: 256 clips x 1 s at 48 kHz -> 24 kHz, one launch per call
 x = torch.rand(256, 1, 48000, device=dev, generator=gen) * 2 - 1

@@ -11,54 +11,26 @@ trained codebooks), encoder side and decoder side real-time factors (audio secon
    python tools/split_hop_ab.py [--hops 200] [--alternations 3] [--streams 1024] > profiles/split_hops.txt
 The kernels' own times come from a separate kernel-trace run (no counters in that run):
    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o t -- python tools/split_hop_ab.py --hops 50 --alternations 1 --no-sweep --no-ref"""
-import argparse
 import os
 import statistics
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import hop_ab  # first: it puts the repository root on sys.path
 import numpy as np
 import torch
 
 from hilcodec_amd import graph_step, synth
-from hilcodec_amd.models.hilcodec.streaming import HILCodec as StreamingHILCodec
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--hops", type=int, default=200)
-ap.add_argument("--alternations", type=int, default=3)
-ap.add_argument("--streams", type=int, default=1024)
-ap.add_argument("--no-sweep", action="store_true")
-ap.add_argument("--no-ref", action="store_true")
-args = ap.parse_args()
-if not torch.cuda.is_available():
-    sys.exit("split_hop_ab.py needs a GPU")
+def options(ap):
+    ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--no-ref", action="store_true")
+
+
+args = hop_ab.parse_args(add=options)
 
 dev = torch.device("cuda:0")
 HOP, N, SR = 320, 8, 24000
 HOP_MS = 1e3 * HOP / SR
-mk = synth.model_kwargs("hil_speech")
-smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
-
-
-def streaming_model(sd):
-    m = StreamingHILCodec(SR, **smk).eval()
-    m.load_offline_state_dict(sd)
-    m.remove_weight_reparameterizations()
-    return m
-
-
-model = streaming_model(synth.synth_state_dict("hil_speech", 7))
-
-
-def timed(fn, hops):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for i in range(hops):
-        fn(i)
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / hops
+model = synth.streaming_model()
 
 
 def legs_for(B, which):
@@ -91,18 +63,9 @@ B = args.streams
 print(f"# split_hop_ab: hil_speech, hop {HOP} ({HOP_MS:.2f} ms), n {N}, {args.hops} hops per leg x {args.alternations} "
       f"alternations; {torch.cuda.get_device_name(dev)}", flush=True)
 legs = legs_for(B, ("loop", "send", "recv", "s+r"))
-order = list(legs)
-res = {k: [] for k in order}
-for a in range(args.alternations):
-    for leg in (order if a % 2 == 0 else order[::-1]):
-        ms = timed(legs[leg], args.hops)
-        res[leg].append(ms)
-        print(f"alt {a} {B:5d} streams {names[leg]:34s} {ms:.4f} ms/hop", flush=True)
-print(f"# {B} streams, median over alternations")
-med = {k: statistics.median(v) for k, v in res.items()}
-for leg in order:
-    print(f"{names[leg]:34s} {med[leg]:.4f} ms/hop  (min {min(res[leg]):.4f}, max {max(res[leg]):.4f})  "
-          f"x{B * HOP_MS / med[leg]:.0f} real time", flush=True)
+res = hop_ab.alternate(list(legs), args, lambda leg, hops: hop_ab.timed(hops, legs[leg]), lambda leg: f"{B:5d} streams {names[leg]}", 48)
+med = hop_ab.report(res, f"# {B} streams, median over alternations", names.get, 34,
+                    tail=lambda leg, ms: f"  x{B * HOP_MS / ms:.0f} real time")
 print(f"sender + receiver - loopback: {1e3 * (med['s+r'] - med['loop']):+.1f} us/hop; sender + receiver measured alone: "
       f"{med['send'] + med['recv']:.4f} ms/hop", flush=True)
 del legs
@@ -111,10 +74,7 @@ if not args.no_sweep:
     print("# per side alone: streams, ms/hop (median over alternations), x real time")
     for b in (1, 8, 64, 256, 1024):
         legs = legs_for(b, ("send", "recv"))
-        r = {k: [] for k in legs}
-        for a in range(args.alternations):
-            for leg in (list(legs) if a % 2 == 0 else list(legs)[::-1]):
-                r[leg].append(timed(legs[leg], args.hops))
+        r = hop_ab.alternate(list(legs), args, lambda leg, hops: hop_ab.timed(hops, legs[leg]))
         ms = {k: statistics.median(v) for k, v in r.items()}
         print(f"sweep {b:5d} streams  sender {ms['send']:.4f} ms/hop x{b * HOP_MS / ms['send']:.1f} RT   "
               f"receiver {ms['recv']:.4f} ms/hop x{b * HOP_MS / ms['recv']:.1f} RT", flush=True)
@@ -123,16 +83,16 @@ if not args.no_sweep:
 if not args.no_ref:
     from tests.test_oracle_golden import realistic_state_dict
     g = dict(np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "realistic.npz")))
-    real = streaming_model(realistic_state_dict(g))
+    real = synth.streaming_model(state_dict=realistic_state_dict(g))
     hops = 5 * SR // HOP                                     # 375 hops: the first 5 s
     x = torch.from_numpy(g["pcm"][:hops * HOP].astype(np.float32) / 32768.0).view(1, 1, -1).to(dev)
     chunks = [x[:, :, HOP * h:HOP * (h + 1)].contiguous() for h in range(hops)]
     s = graph_step.GraphedEncodeHop(real, 1, HOP, N, dev)
     packets = [s.step(c)[0].clone() for c in chunks]
     s.reset()
-    enc_ms = timed(lambda i: s.step(chunks[i]), hops) * hops
+    enc_ms = hop_ab.timed(hops, lambda i: s.step(chunks[i])) * hops
     r = graph_step.GraphedDecodeHop(real, 1, 1, N, dev)
-    dec_ms = timed(lambda i: r.step(packets[i], [N]), hops) * hops
+    dec_ms = hop_ab.timed(hops, lambda i: r.step(packets[i], [N])) * hops
     sec = hops * HOP / SR
     print(f"# reference protocol: 1 stream, hop {HOP}, n {N}, the first {sec:.1f} s of realistic.npz's speech, one replay per hop "
           f"per side (device events around all {hops} hops)")

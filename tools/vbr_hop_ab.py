@@ -11,35 +11,19 @@ half the slots stop at or before stage 4.  (The decision changes what the packer
 measures every stage of every slot whatever it then decides.)
 The kernel's own time comes from a separate kernel-trace run of this script (no counters in that run):
    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o t -- python tools/vbr_hop_ab.py --hops 50 --alternations 1 --legs vw"""
-import argparse
 import math
-import os
-import statistics
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import hop_ab  # first: it puts the repository root on sys.path
 import numpy as np
 import torch
 
 from hilcodec_amd import graph_step, synth, vbr
-from hilcodec_amd.models.hilcodec.streaming import HILCodec as StreamingHILCodec
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--hops", type=int, default=200)
-ap.add_argument("--alternations", type=int, default=5)
-ap.add_argument("--legs", default="svw")
-ap.add_argument("--streams", type=int, default=1024)
-args = ap.parse_args()
-if not torch.cuda.is_available():
-    sys.exit("vbr_hop_ab.py needs a GPU")
+args = hop_ab.parse_args(legs="svw", alternations=5)
 
 dev = torch.device("cuda:0")
 B, n = args.streams, 8
-mk = synth.model_kwargs("hil_speech")
-smk = {k: v for k, v in mk.items() if k not in ("spec_learnable", "causal", "pad_mode")}
-model = StreamingHILCodec(24000, **smk).eval()
-model.load_offline_state_dict(synth.synth_state_dict("hil_speech", 7))
-model.remove_weight_reparameterizations()
+model = synth.streaming_model()
 x = synth.synth_clips(B, 320 * 8, seed=11).to(dev)
 chunks = [x[:, :, 320 * i:320 * (i + 1)].contiguous() for i in range(8)]
 
@@ -68,36 +52,17 @@ def run(leg, hops):
     h = hoppers[leg]
     for i in range(12):
         h.step(chunks[i % 8])
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for i in range(hops):
-        h.step(chunks[i % 8])
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / hops
+    return hop_ab.timed(hops, lambda i: h.step(chunks[i % 8]))
 
 
-res = {leg: [] for leg in args.legs}
 print(f"# vbr_hop_ab: {B} streams, hil_speech, frames 1, n {n}, target_db {target_db:.3f}, sessions=True, {args.hops} hops per leg x "
       f"{args.alternations} alternations; {torch.cuda.get_device_name(dev)}", flush=True)
-for a in range(args.alternations):
-    order = args.legs if a % 2 == 0 else args.legs[::-1]
-    for leg in order:
-        ms = run(leg, args.hops)
-        res[leg].append(ms)
-        print(f"alt {a} {LEGS[leg][1]:40s} {ms:.4f} ms/hop", flush=True)
+res = hop_ab.alternate(args.legs, args, run, lambda leg: LEGS[leg][1], 40)
 for leg in args.legs:
     if leg != "s":
         n_eff = hoppers[leg].n_eff.cpu()
         nbytes = hoppers[leg].outs[hoppers[leg].parity ^ 1][2].cpu()
         print(f"# {LEGS[leg][1]}: n_eff after the run: {np.bincount(n_eff.numpy(), minlength=n + 1).tolist()} slots at 0..{n} stages, "
               f"{float(nbytes.float().mean()):.2f} bytes per packet")
-print("# median over alternations; difference against the sender without VBR")
-for leg in args.legs:
-    med = statistics.median(res[leg])
-    rel = ""
-    if "s" in res and leg != "s":
-        b = statistics.median(res["s"])
-        rel = f"  {1e3 * (med - b):+.1f} us ({100.0 * (med - b) / b:+.2f} %) vs (s)"
-    print(f"{LEGS[leg][1]:40s} {med:.4f} ms/hop  (min {min(res[leg]):.4f}, max {max(res[leg]):.4f}){rel}", flush=True)
+hop_ab.report(res, "# median over alternations; difference against the sender without VBR", lambda leg: LEGS[leg][1], 40,
+              base=lambda leg: "s")
