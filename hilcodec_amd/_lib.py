@@ -85,6 +85,8 @@ SIGNATURES = {
     "hilc_mix_levels": [_p, _p, _p, _i, _i, _p],
     "hilc_mix_rooms": [_p, _p, _p, _i, _p, _p, _i, _i, _p],
     "hilc_vbr_select": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _p],
+    "hilc_rx_report": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
+    "hilc_fec_adapt": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
 }
 
 ABI_VERSION = 16

@@ -24,6 +24,7 @@ from torch import Tensor
 
 from . import dtx as dtx_def
 from . import engine, ops, wire
+from . import report as report_def
 from . import vbr as vbr_def
 from .jitter import AD_WORDS, JitterConfig
 from .mixer import MixConfig
@@ -341,8 +342,8 @@ class GraphedHop(_Hop):
         self.x = torch.zeros(batch, 1, hop, device=device)
         if self.sessions:
             # ONE buffer so that a hop's upload is one copy: action per slot (0 keep, -1 zero, r >= 1 load record r-1), n per
-            # slot, 1 where the slot is held, then the staged records
-            self.stage = self._new_stage(("action", "n_slot", "hold"))
+            # slot, 1 where the slot is held, (a subclass's _extra_rows) then the staged records
+            self.stage = self._new_stage(("action", "n_slot", "hold") + self._extra_rows())
             self.n_slot = self.stage.row["n_slot"]
             self.n_slot.fill_(self.n)
             self.stage.h_row["n_slot"].fill_(self.n)
@@ -415,6 +416,7 @@ class GraphedHop(_Hop):
                 st.put_starts({})
                 st.h_row["n_slot"].fill_(self.n)
                 st.h_row["hold"].zero_()
+                self._put_extra(st)
                 st.send(st.rec_off)
                 st.finish()
                 self._action_live = False
@@ -430,22 +432,35 @@ class GraphedHop(_Hop):
         return self._replay()
 
     def _upload(self) -> None:
-        """queued actions, bitrates and holds -> the graph's device buffers, on the replay stream (an action applies to exactly
-        one hop: the upload after a hop with actions clears them; the hold row goes up when it changes)"""
+        """queued actions, bitrates and holds (and a subclass's extra rows) -> the graph's device buffers, on the replay stream (an
+        action applies to exactly one hop: the upload after a hop with actions clears them; the hold row goes up when it changes)"""
         q, st = self.queue, self.stage
         held = q.held
-        if not q.pending and not self._action_live and held == self._held_live:
+        if not q.pending and not self._action_live and held == self._held_live and not self._extra_pending():
+            q.clear()                         # this hop's holds are spent (the device row already marks them)
             return
         st.wait()
         n_host = st.put_starts(q.starts)      # host records first: they go up in the one copy
         for slot, n in q.n.items():
             st.h_row["n_slot"][slot] = n
         _mark(st.h_row["hold"], held)
+        self._put_extra(st)
         st.send(st.rec_off + n_host * st.records.shape[1])
         st.finish()
         self._action_live = bool(q.starts)
         self._held_live = held
         q.clear()
+
+    # a subclass's own rows of the control stage (GraphedEncodeHop(fec_adapt=): the report row)
+    def _extra_rows(self) -> Tuple[str, ...]:
+        return ()
+
+    def _extra_pending(self) -> bool:
+        """whether an extra row must go up on this hop although nothing else changed"""
+        return False
+
+    def _put_extra(self, st: ControlStage) -> None:
+        """write the extra rows of the mirror, before an upload's copy"""
 
     def set_bitrate(self, slot: int, n: int) -> None:
         """from the next step on, slot `slot` uses the first `n` quantiser stages (1 <= n <= the graph's n)"""
@@ -634,13 +649,34 @@ class GraphedEncodeHop(GraphedHop):
     (int32 `[B]`, bits) are device views like `.indices`.  A `start` or a resume refills a slot's bucket; a held or stopped slot keeps
     it, reports n_eff = n_b and a zero distortion row; `reset` refills every bucket; `export` and a resume carry no VBR state.  DTX runs
     after the packer, unchanged: a SID or SILENT hop is still charged what VBR chose.  A receiver gets n from the header (`play()`), or
-    from `wire.packet_n(nbytes, T)` for headerless packets without FEC.  `vbr=None` captures exactly the graph without VBR."""
+    from `wire.packet_n(nbytes, T)` for headerless packets without FEC.  `vbr=None` captures exactly the graph without VBR.
+    `fec_adapt` = report.FecAdaptConfig(on_q8, off_q8, calm_reports, timeout_hops, initial_on) (needs `sessions` and `fec_stages` >= 1):
+    loss-adaptive FEC (report.py).  `step(x, hold=None, reports=(slots, blobs))` takes this hop's receiver reports — A host ints, and a
+    uint8 `[A, 3]` host tensor or a sequence of 3-byte `bytes` (`wire.pack_report`; a slot outside [0, B) or a wrong width: ValueError; a
+    slot named twice keeps its last) — which go up as one more int32 row of the control stage's single copy and apply to exactly one hop,
+    like an action.  One hilc_fec_adapt ahead of hilc_vbr_select and the packer moves each slot's switch (on at a reported loss >=
+    on_q8, off after calm_reports reports <= off_q8 in a row, back to initial_on after timeout_hops hops without an accepted report) and
+    clears word 0 of the previous-codes row the packer reads for the slots that are off and not held: their packets are the plain
+    n_b-stage ones, the header's FEC flag follows the length, and since the packer still stores every hop's codes, switching on takes
+    effect on the next packet.  `fec_on` (int32 `[B]`) and `fec_adapt_state` (int32 `[B, report.FA_WORDS]`) are device views; a `start`
+    or a resume clears a slot's row inside the graph, `reset` every row; held and stopped slots take their reports but do not age and keep
+    their previous codes; `export` and a resume carry none.  VBR, DTX and the header are untouched.  `fec_adapt=None` captures exactly
+    the graph without it."""
 
     def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, input_rate: int = BASE_RATE, fec_stages: int = 0,
-                 dtx: Optional[dtx_def.DtxConfig] = None, header: bool = False, vbr: Optional[vbr_def.VbrConfig] = None):
+                 dtx: Optional[dtx_def.DtxConfig] = None, header: bool = False, vbr: Optional[vbr_def.VbrConfig] = None,
+                 fec_adapt: Optional[report_def.FecAdaptConfig] = None):
         # what the captured chain reads is set up first: GraphedHop's constructor captures it
         self.fec_stages = _fec_stages(fec_stages, n)
+        if fec_adapt is not None:
+            if not isinstance(fec_adapt, report_def.FecAdaptConfig):
+                raise ValueError(f"fec_adapt must be a report.FecAdaptConfig or None, got {fec_adapt!r}")
+            if not sessions or not self.fec_stages:
+                raise ValueError("GraphedEncodeHop(fec_adapt=...) needs sessions=True and fec_stages >= 1")
+        self.fec_adapt = fec_adapt
+        self._reports = {}                    # slot -> report word for the next hop
+        self._report_live = False             # the device report row holds the previous hop's reports
         self.header = bool(header)
         if self.header:
             _whole_frames("GraphedEncodeHop(header=True)", hop)
@@ -669,7 +705,8 @@ class GraphedEncodeHop(GraphedHop):
                                  "an n-stage packet with a redundant section from a longer plain one")
             self._vbr_lo = min(int(n), vbr_def.floor_stages(vbr, self.fec_stages))
             self._vbr_bits = vbr_def.bucket_bits(vbr, _whole_frames("GraphedEncodeHop(vbr=...)", hop), self.fec_stages)
-        self._prev = self._run = self._ctr = self._credit = None
+        self._prev = self._run = self._ctr = self._credit = self._fa = self._fec_on = None
+        self._scratch_fill = []
         if self.fec_stages:
             # per parity, per slot: valid, then the first m stages x T frames of its last encoded hop (the hop of parity p reads
             # row p and writes row p ^ 1)
@@ -684,8 +721,16 @@ class GraphedEncodeHop(GraphedHop):
         if vbr is not None and vbr.cap_kbps is not None:
             # per slot: the token bucket's credit in bits (updated in place by hilc_vbr_select once per hop); cleared = full
             self._credit = torch.full((batch,), self._vbr_bits[2], dtype=torch.int32, device=device)
-            self._scratch_fill = [(self._credit, self._vbr_bits[2])]
-        self._scratch = [t for t in (self._prev, self._run, self._ctr, self._credit) if t is not None]
+            self._scratch_fill += [(self._credit, self._vbr_bits[2])]
+        if fec_adapt is not None:
+            # per slot: the adapt row (report.FA_*, updated in place by hilc_fec_adapt once per hop) and its switch; cleared = the
+            # row zero but for FA_ON = initial_on
+            on0 = int(fec_adapt.initial_on)
+            self._fa = torch.zeros(batch, report_def.FA_WORDS, dtype=torch.int32, device=device)
+            self._fa[:, report_def.FA_ON] = on0
+            self._fec_on = torch.full((batch,), on0, dtype=torch.int32, device=device)
+            self._scratch_fill += [(self._fa[:, report_def.FA_ON], on0), (self._fec_on, on0)]
+        self._scratch = [t for t in (self._prev, self._run, self._ctr, self._credit, self._fa) if t is not None]
         super().__init__(model, batch, hop_in, n, device, warmup, 1, sessions, max_loads_per_hop)
         self.queue.n_min = max(1, self.fec_stages)
         self.indices = self.outs[0][0]
@@ -713,6 +758,10 @@ class GraphedEncodeHop(GraphedHop):
             with engine.spectra_side_stream(self.spec_side[0]):
                 z, _ = m.encoder(x, *src.codec_enc, cache_out=dst.codec_enc)
             idx = m.quantizer(z, self.n, n_clip=n_clip)
+        if self.fec_adapt is not None:
+            # ahead of the packer (and of VBR): a slot whose switch is off loses the valid word of the row the packer reads
+            ops.fec_adapt(self._prev[p], self._fa, self._fec_on, self.fec_stages, self.frames, self.fec_adapt, self.stage.row["report"],
+                          action, hold)
         n_eff = distortion = None
         if self.vbr is not None:
             stage_bits, rate_bits, burst_bits = self._vbr_bits
@@ -752,8 +801,80 @@ class GraphedEncodeHop(GraphedHop):
             raise RuntimeError("GraphedEncodeHop.hop_index: construct with header=True")
         return self._ctr[self.parity]
 
-    def step(self, x: Tensor, hold=None) -> Tuple[Tensor, Tensor]:
-        out = super().step(x, hold)
+    @property
+    def fec_on(self) -> Tensor:
+        """int32 `[B]` device view: each slot's FEC switch after the last hop (fec_adapt only).  Read-only: written by the graph."""
+        if self._fec_on is None:
+            raise RuntimeError("GraphedEncodeHop.fec_on: construct with fec_adapt=FecAdaptConfig(...)")
+        return self._fec_on
+
+    @property
+    def fec_adapt_state(self) -> Tensor:
+        """int32 `[B, report.FA_WORDS]` device view: each slot's adapt row after the last hop (report.FA_*; fec_adapt only).
+        Read-only: written by the graph."""
+        if self._fa is None:
+            raise RuntimeError("GraphedEncodeHop.fec_adapt_state: construct with fec_adapt=FecAdaptConfig(...)")
+        return self._fa
+
+    def _report_words(self, reports) -> dict:
+        """step's `reports` = (slots, blobs) checked before anything is launched -> {slot: report word}; a slot named twice keeps
+        its last report"""
+        if reports is None:
+            return {}
+        if self.fec_adapt is None:
+            raise RuntimeError("GraphedEncodeHop.step(reports=...): construct with fec_adapt=FecAdaptConfig(...)")
+        try:
+            slots, blobs = reports
+        except (TypeError, ValueError):
+            raise ValueError("reports: a pair (slots, blobs) expected") from None
+        for name, v in (("slots", slots), ("blobs", blobs)):
+            if isinstance(v, Tensor) and v.is_cuda:
+                raise ValueError(f"reports: {name} must be on the host, not a device tensor")
+        slots = [int(s) for s in (slots.reshape(-1).tolist() if isinstance(slots, Tensor) else slots)]
+        if isinstance(blobs, Tensor):
+            if blobs.dtype != torch.uint8 or blobs.dim() != 2 or blobs.shape[1] != wire.REPORT_BYTES:
+                raise ValueError(f"reports: blobs must be uint8 [A, {wire.REPORT_BYTES}] or {wire.REPORT_BYTES}-byte bytes objects")
+            blobs = [bytes(row) for row in blobs.tolist()]
+        else:
+            blobs = list(blobs)
+        if len(blobs) != len(slots):
+            raise ValueError(f"reports: {len(slots)} slots but {len(blobs)} reports")
+        words = {}
+        for s, blob in zip(slots, blobs):
+            if not 0 <= s < self.queue.batch:
+                raise ValueError(f"reports: slot {s} outside [0, {self.queue.batch})")
+            words[s] = report_def.report_word(*wire.parse_report(blob))    # ValueError: not 3 bytes
+        return words
+
+    def _extra_rows(self) -> Tuple[str, ...]:
+        return ("report",) if self.fec_adapt is not None else ()
+
+    def _extra_pending(self) -> bool:
+        return bool(self._reports) or self._report_live
+
+    def _put_extra(self, st: ControlStage) -> None:
+        """the report row: this hop's reports, 0 elsewhere (a report applies to exactly one hop, like an action: the upload after a
+        hop with reports clears them)"""
+        if self.fec_adapt is not None:
+            row = st.h_row["report"]
+            row.zero_()
+            for slot, word in self._reports.items():
+                row[slot] = word
+            self._report_live = bool(self._reports)
+            self._reports = {}
+
+    def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
+        self._reports = {}
+        super().reset(cache_enc, cache_dec)
+
+    def step(self, x: Tensor, hold=None, reports=None) -> Tuple[Tensor, Tensor]:
+        """`reports` (fec_adapt only): (slots, blobs), this hop's receiver reports — A host ints, and a uint8 `[A, 3]` host tensor or a
+        sequence of 3-byte `bytes` (wire.pack_report)"""
+        self._reports = self._report_words(reports)
+        try:
+            out = super().step(x, hold)
+        finally:
+            self._reports = {}                # taken by the upload, or dropped with a step that raised before it
         self.indices, packets, nbytes = out[:3]
         if self.dtx is not None:
             self.kind = out[3]
@@ -838,12 +959,21 @@ class GraphedDecodeHop(_Hop):
     hop and no host copy.  `speakers` (int32 `[B]`) marks the slots among their room's top_k, `levels` (float64 `[B]`) is the peak-hold
     score of every slot; a `start` clears a slot's score inside the graph.  Graph: hilc_mix_levels and hilc_mix_rooms are the last two
     launches, after the final hilc_state_slots_hold and the hilc_cng_synth behind it: comfort noise is mixed as noise, a held slot as
-    zeros, and a held listener still gets its mix.  `mix=None` captures exactly the graph without the mixer."""
+    zeros, and a held listener still gets its mix.  `mix=None` captures exactly the graph without the mixer.
+    `report` = report.ReportConfig(window, interval) (needs `jitter`: the rule reads the jitter state, the explicit `step()` has no
+    report): receiver reports (report.py).  One hilc_rx_report directly after the jitter step classes each slot's hop from its jitter
+    counters (decoded, repaired by FEC, lost, noise), keeps a sliding window of the last `window` decoded / repaired / lost hops and
+    every `interval` classed hops emits a report (seq, loss_q8, residual_q8: `wire.pack_report`).  It only observes: wav, caches and
+    every other state are those of the receiver without it.  `reports` (uint8 `[B, 3]`: each slot's latest report, unchanged between
+    reports), `report_due` (int32 `[B]`: 1 on the hop a report was emitted) and `report_state` (int32 `[B, report.RP_WORDS]`) are device
+    views; a `start` clears a slot's row, report and flag inside the graph; `export` and a resume carry none.  `report=None` captures
+    exactly the graph without it."""
 
     def __init__(self, model, batch: int, frames: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, conceal: bool = False, fade_hops: int = 4, output_rate: int = BASE_RATE,
                  fec_stages: int = 0, cng_order: Optional[int] = None, jitter: Optional[JitterConfig] = None,
-                 max_arrivals: Optional[int] = None, mix: Optional[MixConfig] = None):
+                 max_arrivals: Optional[int] = None, mix: Optional[MixConfig] = None,
+                 report: Optional[report_def.ReportConfig] = None):
         self.batch, self.frames = int(batch), int(frames)
         self.output_rate = int(output_rate)
         self.rs, self._history = None, 0
@@ -877,6 +1007,11 @@ class GraphedDecodeHop(_Hop):
         if mix is not None and not sessions:
             raise ValueError("GraphedDecodeHop(mix=...) needs sessions=True")
         self.mix = mix
+        if report is not None and not isinstance(report, report_def.ReportConfig):
+            raise ValueError(f"report must be a report.ReportConfig or None, got {report!r}")
+        if report is not None and jitter is None:
+            raise ValueError("GraphedDecodeHop(report=...) needs jitter=JitterConfig(...): the reports are made from the jitter state")
+        self.report = report
         super().__init__(model, self.batch, int(n), device, 1, sessions, max_loads_per_hop)
         self.stride = wire.packet_bytes(self.n + self.fec_stages, self.frames)
         B = self.batch
@@ -909,6 +1044,12 @@ class GraphedDecodeHop(_Hop):
             self._scratch += [self._jstate, self._jmeta, self._jring]
             if jitter.adapt is not None:
                 self._scratch += [self._jadapt]
+        if report is not None:
+            # per slot: the report row (report.RP_*, updated in place by hilc_rx_report once per hop), its latest report, its due flag
+            self._rp = torch.zeros(B, report_def.RP_WORDS, dtype=torch.int32, device=device)
+            self._rp_bytes = torch.zeros(B, wire.REPORT_BYTES, dtype=torch.uint8, device=device)
+            self._rp_due = torch.zeros(B, dtype=torch.int32, device=device)
+            self._scratch += [self._rp, self._rp_bytes, self._rp_due]
         if mix is not None:
             # per slot: the peak-hold score (updated in place by hilc_mix_levels once per hop); per parity: the mixes; the speaker
             # marks; the room row (device, captured by address) and its pinned host mirror
@@ -962,6 +1103,8 @@ class GraphedDecodeHop(_Hop):
         elif self.jitter is not None:
             ops.jitter_step(self.arrivals, self.offsets, self.hold, self.n_slot, self.packets, self._jstate, self._jmeta, self._jring,
                             self.n, self.fec_stages, self.frames, self.cng_order, self.jitter.depth, self.action, self.lost, self.fec)
+        if self.report is not None:
+            ops.rx_report(self._jstate, self._rp, self._rp_bytes, self._rp_due, self.report, self.action)
         if self.sessions:
             ops.state_slots_apply(src.buffer, src.layout, self.action, self.records)
         packets = self.packets
@@ -1161,6 +1304,30 @@ class GraphedDecodeHop(_Hop):
         if self.jitter is None or self.jitter.adapt is None:
             raise RuntimeError("GraphedDecodeHop.jitter_adapt: construct with jitter=JitterConfig(..., adapt=AdaptConfig(...))")
         return self._jadapt
+
+    def _need_report(self, what: str) -> None:
+        if self.report is None:
+            raise RuntimeError(f"GraphedDecodeHop.{what}: construct with report=ReportConfig(...)")
+
+    @property
+    def reports(self) -> Tensor:
+        """uint8 `[B, 3]` device view: each slot's latest report (wire.parse_report; zeros before its first), unchanged between
+        reports.  Read-only: written by the graph."""
+        self._need_report("reports")
+        return self._rp_bytes
+
+    @property
+    def report_due(self) -> Tensor:
+        """int32 `[B]` device view: 1 for the slots whose report was emitted on the last play.  Read-only: written by the graph."""
+        self._need_report("report_due")
+        return self._rp_due
+
+    @property
+    def report_state(self) -> Tensor:
+        """int32 `[B, report.RP_WORDS]` device view: each slot's report row after the last play (report.RP_*).  Read-only: written
+        by the graph."""
+        self._need_report("report_state")
+        return self._rp
 
     def play(self, slots, packets: Tensor, nbytes, hold=None) -> Tensor:
         """one hop of a jitter receiver: this hop's arrivals, in push order — `slots` and `nbytes` (A host ints), `packets` uint8

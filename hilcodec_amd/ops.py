@@ -1137,6 +1137,40 @@ _register("vbr_select", "(Tensor z, Tensor(a!) indices, Tensor codebooks, Tensor
           lambda z, indices, codebooks, n_clip, action, hold, credit, n_lo, rho, stage_bits, rate_bits, burst_bits:
           (z.new_empty(z.shape[0], dtype=torch.int32), z.new_empty(z.shape[0], indices.shape[0] + 1, dtype=torch.float64)))
 
+# ======================================================================================================
+# receiver reports and loss-adaptive FEC (graph_step.GraphedDecodeHop(report=), GraphedEncodeHop(fec_adapt=); definition:
+# hilcodec_amd/report.py; semantics: include/hilcodec_amd.h)
+# ======================================================================================================
+def _rx_report(jitter_state, action, rows, reports, due, window, interval):
+    from .jitter import ST_WORDS
+    from .report import RP_WORDS
+    B = due.numel()
+    if jitter_state.shape != (B, ST_WORDS) or rows.shape != (B, RP_WORDS) or reports.shape != (B, 3):
+        raise RuntimeError(f"rx_report: jitter_state must be [{B}, {ST_WORDS}], rows [{B}, {RP_WORDS}] and reports [{B}, 3]")
+    _rows("rx_report", B, action=action)
+    check(lib.hilc_rx_report(_ptr(jitter_state, torch.int32), _ptr(action, torch.int32), _ptr(rows, torch.int32),
+                             _ptr(reports, torch.uint8), _ptr(due, torch.int32), B, window, interval, _stream()), "hilc_rx_report")
+
+
+_register("rx_report", "(Tensor jitter_state, Tensor? action, Tensor(a!) rows, Tensor(b!) reports, Tensor(c!) due, int window, "
+          "int interval) -> ()", _rx_report, lambda jitter_state, action, rows, reports, due, window, interval: None)
+
+
+def _fec_adapt(report, action, hold, rows, prev, fec_on, m, frames, on_q8, off_q8, calm_reports, timeout_hops, initial_on):
+    from .report import FA_WORDS
+    B = fec_on.numel()
+    if rows.shape != (B, FA_WORDS) or prev.shape != (B, 1 + m * frames):
+        raise RuntimeError(f"fec_adapt: rows must be [{B}, {FA_WORDS}] and prev [{B}, {1 + m * frames}]")
+    _rows("fec_adapt", B, report=report, action=action, hold=hold)
+    check(lib.hilc_fec_adapt(_ptr(report, torch.int32), _ptr(action, torch.int32), _ptr(hold, torch.int32), _ptr(rows, torch.int32),
+                             _ptr(prev, torch.int32), _ptr(fec_on, torch.int32), B, frames, m, on_q8, off_q8, calm_reports,
+                             timeout_hops, int(initial_on), _stream()), "hilc_fec_adapt")
+
+
+_register("fec_adapt", "(Tensor? report, Tensor? action, Tensor? hold, Tensor(a!) rows, Tensor(b!) prev, Tensor(c!) fec_on, int m, "
+          "int frames, int on_q8, int off_q8, int calm_reports, int timeout_hops, bool initial_on) -> ()", _fec_adapt,
+          lambda report, action, hold, rows, prev, fec_on, m, frames, on_q8, off_q8, calm_reports, timeout_hops, initial_on: None)
+
 _OPS = torch.ops.hilcodec
 
 
@@ -1791,3 +1825,21 @@ def vbr_select(z: Tensor, indices: Tensor, codebooks: Tensor, n_lo: int, rho: fl
     numbers (without it `rate_bits` must be 0)."""
     return _OPS.vbr_select(z, indices, codebooks, n_clip, action, hold, credit, int(n_lo), float(rho), int(stage_bits), int(rate_bits),
                            int(burst_bits))
+
+
+def rx_report(jitter_state: Tensor, rows: Tensor, reports: Tensor, due: Tensor, cfg, action: Optional[Tensor] = None) -> None:
+    """The reporting receiver's step after its jitter step (report.ReportModel), in place: `jitter_state` (int32 `[B, 14]`, read only)
+    -> `rows` (int32 `[B, report.RP_WORDS]`), `reports` (uint8 `[B, 3]`: each slot's latest report, written when one is emitted) and
+    `due` (int32 `[B]`: 1 where one was emitted on this hop).  `cfg`: the report.ReportConfig; `action` (int32 `[B]`, optional): the
+    session row, a start clears the slot."""
+    _OPS.rx_report(jitter_state, action, rows, reports, due, int(cfg.window), int(cfg.interval))
+
+
+def fec_adapt(prev: Tensor, rows: Tensor, fec_on: Tensor, m: int, frames: int, cfg, report: Optional[Tensor] = None,
+              action: Optional[Tensor] = None, hold: Optional[Tensor] = None) -> None:
+    """The adaptive sender's step ahead of its packer (report.FecAdaptModel), in place: `rows` (int32 `[B, report.FA_WORDS]`) take this
+    hop's `report` words (int32 `[B]`, report.report_word, 0: none; optional), word 0 of `prev` (int32 `[B, 1 + m frames]`, the
+    previous-codes rows the packer reads) is cleared for the slots that are off and not held, and `fec_on` (int32 `[B]`) is each slot's
+    switch.  `cfg`: the report.FecAdaptConfig; `action` / `hold` (int32 `[B]`, optional): the session rows."""
+    _OPS.fec_adapt(report, action, hold, rows, prev, fec_on, int(m), int(frames), int(cfg.on_q8), int(cfg.off_q8), int(cfg.calm_reports),
+                   int(cfg.timeout_hops), bool(cfg.initial_on))

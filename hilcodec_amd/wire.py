@@ -209,6 +209,29 @@ def parse_transport(packet, nbytes: int, T: int, n_max: int, m: int, K) -> Tuple
             raise ValueError(f"a {body}-byte body disagrees with its header's FEC flag")
     return hop, sid, fec, n, data[TRANSPORT_HEADER:nbytes]
 
+
+# Receiver report (hilcodec_amd/report.py: GraphedDecodeHop(report=...) emits it, GraphedEncodeHop(fec_adapt=...) takes it): feedback
+# that travels beside the media, 3 bytes: a sequence number mod 256, then the loss and the residual loss of the receiver's window as
+# fractions of 256 (loss_q8 counts the hops repaired from a redundant section as missing, residual_q8 only what the listener lost).
+REPORT_BYTES = 3
+
+
+def pack_report(seq: int, loss_q8: int, residual_q8: int) -> bytes:
+    """(seq, loss_q8, residual_q8), one byte each in that order; ValueError for a field outside [0, 255]"""
+    fields = (seq, loss_q8, residual_q8)
+    for name, v in zip(("seq", "loss_q8", "residual_q8"), fields):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 255:
+            raise ValueError(f"pack_report: {name} = {v!r} outside [0, 255]")
+    return bytes(int(v) for v in fields)
+
+
+def parse_report(blob) -> Tuple[int, int, int]:
+    """(seq, loss_q8, residual_q8) of a report; ValueError unless it is exactly REPORT_BYTES bytes"""
+    data = bytes(blob)
+    if len(data) != REPORT_BYTES:
+        raise ValueError(f"a report is {REPORT_BYTES} bytes, got {len(data)}")
+    return data[0], data[1], data[2]
+
 # ---------------------------------------------------------------- caches
 def save_cache_npz(path: str, caches: Sequence[Tensor], prefix: str) -> None:
     """prefix 'e_in' (encoder, 22 tensors) or 'd_in' (decoder, 30)."""

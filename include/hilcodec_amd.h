@@ -37,7 +37,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -630,6 +630,33 @@ int hilc_mix_rooms(const float* wav, const int* room, const double* score, int t
 int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action,
                     const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo,
                     double rho, int stage_bits, int rate_bits, int burst_bits, void* stream);
+
+/* ---- receiver reports and loss-adaptive in-band FEC (additive under ABI 16) -------------------------------------------------------
+ * Two entry points added WITHOUT a version bump, as the entry points above.  The definition, bit for bit, is hilcodec_amd/report.py.
+ * hilc_rx_report: the receiver's launch after hilc_jitter_step / hilc_jitter_adapt_step.  jitter_state int32 [B][14] (read only: the
+ * rows that launch left); action optional int32 [B]; rows int32 [B][29] (in place: report.RP_*, the last report, the interval phase, the
+ * window's counts and head, the remembered counters, the reports emitted, then 16 ring words); reports uint8 [B][3] (seq, loss_q8,
+ * residual_q8 of the slot's latest report: written when one is emitted, zeroed by action[b] != 0, else untouched); due int32 [B] (every
+ * element written: 1 where a report was emitted on this hop).  Per slot: the hop's class is the first of the counters DECODED, FEC,
+ * LOST, NOISE that differs from the remembered one (none: nothing but due changes); D, F and L hops enter a window of the last
+ * `window` such hops, 2 bits each; every class advances the phase, and at phase >= interval the phase restarts and, with N >= 1
+ * entries, seq = (seq + 1) mod 256, loss_q8 = min(255, (256 (F + L) + N / 2) / N), residual_q8 = min(255, (256 L + N / 2) / N).
+ * 8 <= window <= 256 and 1 <= interval <= 1024, B >= 1 (else HILC_ERR_SHAPE).
+ * hilc_fec_adapt: the sender's launch ahead of hilc_vbr_select / hilc_pack_codes_10bit_fec.  report optional int32 [B] (per slot 0, or
+ * 1 << 24 | seq << 16 | loss_q8 << 8 | residual_q8); action, hold optional int32 [B] (the rows of hilc_state_slots_apply /
+ * hilc_state_slots_hold); rows int32 [B][12] (in place: report.FA_*, on, calm, seen, last seq, age, loss, residual, then the counters
+ * reports, stale, turned_on, turned_off, timeout); prev int32 [B][1 + m T] (the previous-codes rows the packer reads on this hop: only
+ * word 0 of a slot that is not held and off is written, with 0); fec_on int32 [B] (every element written).  Per slot: action[b] != 0
+ * clears the row to on = initial_on; a report is accepted when none was seen since the clear or (seq - last) mod 256 is in [1, 127]
+ * (else stale), and then loss >= on_q8 switches on, loss <= off_q8 counts calm and switches off at calm_reports in a row, anything
+ * between restarts the count; a slot that is not held ages by one hop, and at timeout_hops > 0 hops without an accepted report falls
+ * back to initial_on and forgets the sequence number.  0 <= off_q8 < on_q8 <= 255, calm_reports >= 1, timeout_hops >= 0, B, T, m >= 1
+ * (else HILC_ERR_SHAPE).
+ * Both: NULL pointers (the optional rows excepted): HILC_ERR_NULL.  One wave per slot, no LDS, no atomics. */
+int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval,
+                   void* stream);
+int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m,
+                   int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream);
 
 #ifdef __cplusplus
 }
