@@ -102,3 +102,69 @@ def arrival_records(slots, packets, nbytes, tbytes, B, max_a):
     offs = np.zeros(B + 1, dtype=np.int32)
     offs[1:] = np.cumsum(np.bincount(np.asarray(slots, dtype=np.int64), minlength=B))
     return torch.from_numpy(rec).to(DEV), torch.from_numpy(offs).to(DEV)
+
+
+# ---------------------------------------------------------------- everything a hop object shows of one slot
+def slot_views(hop):
+    """the names of the per-slot device views a hop object's configuration has (an object that lacks one of them raises)"""
+    from hilcodec_amd.graph_step import GraphedDecodeHop, GraphedEncodeHop
+    names = []
+    if isinstance(hop, GraphedEncodeHop):
+        names += ["n_eff", "distortion"] * (hop.vbr is not None) + ["credit"] * (hop.vbr is not None and hop.vbr.cap_kbps is not None)
+        names += ["kind"] * (hop.dtx is not None) + ["fec_on", "fec_adapt_state"] * (hop.fec_adapt is not None)
+        names += ["hop_index"] * hop.header
+    elif isinstance(hop, GraphedDecodeHop):
+        names += ["concealed"] * hop.conceal + ["cng_state"] * (hop.cng_order is not None) + ["jitter_state"] * (hop.jitter is not None)
+        names += ["jitter_adapt"] * (hop.jitter is not None and hop.jitter.adapt is not None)
+        names += ["reports", "report_due", "report_state"] * (hop.report is not None)
+        names += ["mixed", "speakers", "levels"] * (hop.mix is not None)
+    return names
+
+
+def observe(hop, slot):
+    """clones of everything a sessions hop object exposes for slot `slot` after a hop, by name: the rows of what the last step()
+    / play() returned, its indices, every per-slot view its configuration has (`slot_views`), and every tensor of export(slot)
+    (a list).  The outputs are static views that the next-but-one call overwrites, hence the clones."""
+    from hilcodec_amd.graph_step import GraphedDecodeHop, GraphedEncodeHop
+    out = hop.outs[hop.parity ^ 1]                           # the static outputs of the graph that ran last
+    obs = {}
+    if isinstance(hop, GraphedDecodeHop):
+        obs["wav"], records = out[slot], [hop.export(slot)]
+    elif isinstance(hop, GraphedEncodeHop):
+        obs["indices"], obs["packet"], obs["nbytes"] = hop.indices[:, slot], out[1][slot], out[2][slot]
+        records = [hop.export(slot)]
+    else:
+        obs["indices"], obs["wav"], records = out[0][:, slot], out[1][slot], hop.export(slot)
+    for name in slot_views(hop):
+        obs[name] = getattr(hop, name)[slot]
+    obs = {k: v.clone() for k, v in obs.items()}
+    obs["export"] = [t.clone() for rec in records for t in rec]
+    return obs
+
+
+def first_difference(a, b):
+    """None when two observations are equal bit for bit (NaN never is), else "<attribute>: <where and what>" of the first that differs"""
+    if a.keys() != b.keys():
+        return f"attributes {sorted(a)} != {sorted(b)}"
+    for name in a:
+        xs, ys = (a[name], b[name]) if isinstance(a[name], list) else ([a[name]], [b[name]])
+        if len(xs) != len(ys):
+            return f"{name}: {len(xs)} tensors != {len(ys)}"
+        for i, (x, y) in enumerate(zip(xs, ys)):
+            if x.shape != y.shape or x.dtype != y.dtype:
+                return f"{name}[{i}]: {tuple(x.shape)} {x.dtype} != {tuple(y.shape)} {y.dtype}"
+            if not torch.equal(x, y):
+                fx, fy = x.reshape(-1), y.reshape(-1)
+                j = int(torch.nonzero(~(fx == fy))[0])
+                which = f"[{i}]" if isinstance(a[name], list) else ""
+                return f"{name}{which}: {int((~(fx == fy)).sum())} of {fx.numel()} differ, first at {j}: {fx[j].item()!r} != {fy[j].item()!r}"
+    return None
+
+
+def first_non_finite(obs):
+    """None when every floating-point value of an observation is finite, else "<attribute>: ..." of the first that is not"""
+    for name, v in obs.items():
+        for i, t in enumerate(v if isinstance(v, list) else [v]):
+            if t.is_floating_point() and not bool(torch.isfinite(t).all()):
+                return f"{name}[{i}]: {int((~torch.isfinite(t)).sum())} of {t.numel()} non-finite"
+    return None
