@@ -8,9 +8,9 @@
 //                         device-decided hold, and records the slot's gain ramp.
 //   hilc_conceal_gain     after the decoder, before hilc_state_slots_hold: multiplies the wav rows that have a ramp.
 //
-// State row of slot b (int32, n_max + 3 words): [0] run k (hops lost in a row, 0..F), [1] has-codes, [2] stored n, [3 + s] code of
-// stage s of the last frame of the last packet received (0 for s >= stored n).  Ramp word of slot b: 0 none; r in 1..F: a lost hop,
-// gains G[r - 1] -> G[r]; r in -F..-1: a received hop after -r lost ones, gains G[-r] -> G[0].
+// State row of slot b (int32, n_max + HILC_WIRE_CONCEAL_CODES words): HILC_WIRE_CONCEAL_RUN k (hops lost in a row, 0..F), _HAS, _N
+// (stored n), _CODES + s the code of stage s of the last frame of the last packet received (0 for s >= stored n).  Ramp word of slot
+// b: 0 none; r in 1..F: a lost hop, gains G[r - 1] -> G[r]; r in -F..-1: a received hop after -r lost ones, gains G[-r] -> G[0].
 //
 // Both kernels: one wave per slot (slot.h), wave-uniform branches only.  The common case (every packet received) costs one round of
 // loads and one of stores per slot in prepare, and one load per slot in gain.
@@ -20,8 +20,6 @@ namespace {
 
 using namespace slot;
 
-constexpr int ST_RUN = 0, ST_HAS = 1, ST_N = 2, ST_CODES = 3;
-
 __global__ __launch_bounds__(THREADS) void conceal_prepare_kernel(int* __restrict__ state, const int* __restrict__ action,
                                                                   int* __restrict__ hold, const int* __restrict__ lost,
                                                                   int* __restrict__ n_slot, uint8_t* __restrict__ packets,
@@ -29,16 +27,16 @@ __global__ __launch_bounds__(THREADS) void conceal_prepare_kernel(int* __restric
   const Wave me = this_wave(B);
   if (!me.ok) return;
   const int b = me.b, lane = me.lane();
-  const int words = n_max + 3;
+  const int words = n_max + HILC_WIRE_CONCEAL_CODES;
   int* st = state + (long)b * words;
   uint8_t* pk = packets + (long)b * stride;
   // every load of the slot in one round: the last frame's code of stage `lane` is read whether or not the packet arrived
   const int act = action[b], held = hold[b], gone = lost[b], n_in = n_slot[b];
   const int old = lane < words ? st[lane] : 0;
   const int fresh = lane < n_max ? code_at(pk, 10 * (lane * T + T - 1)) : 0;
-  const int run0 = __builtin_amdgcn_readfirstlane(__shfl(old, ST_RUN));
-  const int has0 = __builtin_amdgcn_readfirstlane(__shfl(old, ST_HAS));
-  const int n0 = __builtin_amdgcn_readfirstlane(__shfl(old, ST_N));
+  const int run0 = __builtin_amdgcn_readfirstlane(__shfl(old, HILC_WIRE_CONCEAL_RUN));
+  const int has0 = __builtin_amdgcn_readfirstlane(__shfl(old, HILC_WIRE_CONCEAL_HAS));
+  const int n0 = __builtin_amdgcn_readfirstlane(__shfl(old, HILC_WIRE_CONCEAL_N));
   const bool reset = act != 0;                         // a start or a resume on this hop: no stored codes, run 0
   const int k = reset ? 0 : clampi(run0, 0, F);
   const bool has = !reset && has0 != 0;
@@ -48,9 +46,9 @@ __global__ __launch_bounds__(THREADS) void conceal_prepare_kernel(int* __restric
     // host-held or stopped: the state is left as it is (a start on the same hop is applied first)
   } else if (gone == 0) {
     const int nb = clampi(n_in, 1, n_max);
-    const int s = lane - ST_CODES;
+    const int s = lane - HILC_WIRE_CONCEAL_CODES;
     const int c = __shfl(fresh, s < 0 ? 0 : s);        // lane s read stage s's code of the packet's last frame
-    word = lane == ST_RUN ? 0 : (lane == ST_HAS ? 1 : (lane == ST_N ? nb : (s < nb ? c : 0)));
+    word = lane == HILC_WIRE_CONCEAL_RUN ? 0 : (lane == HILC_WIRE_CONCEAL_HAS ? 1 : (lane == HILC_WIRE_CONCEAL_N ? nb : (s < nb ? c : 0)));
     r = k > 0 ? -k : 0;
   } else if (has && k < F) {
     const int nb = clampi(n0, 1, n_max);
@@ -62,8 +60,8 @@ __global__ __launch_bounds__(THREADS) void conceal_prepare_kernel(int* __restric
       const PackedByte at = packed_byte(j);
       const int i0 = at.i0;
       const int s0 = min(i0 / T, MAX_N - 1), s1 = min((i0 + 1) / T, MAX_N - 1);
-      const uint32_t c0 = (uint32_t)__shfl(old, ST_CODES + s0) & 1023u;
-      const uint32_t c1 = (uint32_t)__shfl(old, ST_CODES + s1) & 1023u;
+      const uint32_t c0 = (uint32_t)__shfl(old, HILC_WIRE_CONCEAL_CODES + s0) & 1023u;
+      const uint32_t c1 = (uint32_t)__shfl(old, HILC_WIRE_CONCEAL_CODES + s1) & 1023u;
       if (j < stride) {
         uint32_t out = 0;
         if (j < len) out = at.of((c0 << 10) | (i0 + 1 < count ? c1 : 0u));
@@ -71,11 +69,11 @@ __global__ __launch_bounds__(THREADS) void conceal_prepare_kernel(int* __restric
       }
     }
     if (lane == 0) n_slot[b] = nb;
-    if (lane == ST_RUN) word = k + 1;
+    if (lane == HILC_WIRE_CONCEAL_RUN) word = k + 1;
     r = k + 1;
   } else {
     // nothing received since the start, or faded out: a device-decided hold
-    if (lane == 0) hold[b] = 1;
+    if (lane == 0) hold[b] = HILC_SESSIONS_HOLD_HELD;
   }
   if (lane < words) st[lane] = word;
   if (lane == 0) ramp[b] = r;

@@ -17,12 +17,7 @@ namespace {
 
 using namespace slot;
 
-constexpr int MAX_ORDER = 16;
-constexpr int LEVELS = 128;
 constexpr float NOISE_BOUND = 16.f; // dtx.NOISE_BOUND: a noise hop with a sample outside (-16, 16) is replaced by silence
-constexpr int FRAME = 320;         // samples per codec frame at 24 kHz: a hop is T of them
-constexpr int SPEECH = 1, SID = 2, SILENT = 3;   // dtx.py kinds (HELD = 0)
-constexpr int ST_HAS = 0, ST_LEVEL = 1, ST_COUNT = 2, ST_Q = 3;
 
 // the wave's LDS writes are visible to its other lanes (a wave runs its LDS operations in order; this keeps the compiler from moving
 // the reads above the writes)
@@ -51,45 +46,45 @@ __global__ __launch_bounds__(THREADS) void dtx_encode_kernel(const float* __rest
                                                              const double* __restrict__ level_thr, double thr_vad, int B, int T,
                                                              int H, int I, int n_max, int stride, int prev_words) {
   __shared__ double part[WAVES][K + 1][LANES + 1];        // +1: lane k's column read is free of bank conflicts
-  __shared__ float xs[WAVES][MAX_ORDER + FRAME];
+  __shared__ float xs[WAVES][HILC_DTX_MAX_ORDER + HILC_RESAMPLE_HOP];
   const Wave me = this_wave(B);
   if (!me.ok) return;
   const int w = me.w, b = me.b, lane = me.lane();
-  const int S = 320 * T;
+  const int S = HILC_RESAMPLE_HOP * T;
   const bool reset = is_reset(action, b);
   const int run0 = reset ? 0 : run[b];
   const double thr0 = level_thr[lane];
-  const double thr1 = lane + LANES < LEVELS - 1 ? level_thr[lane + LANES] : 0.0;
+  const double thr1 = lane + LANES < HILC_DTX_LEVELS - 1 ? level_thr[lane + LANES] : 0.0;
   if (is_held(hold, b)) {                                 // held: run kept (a start on this hop clears it), nothing else
     if (lane == 0) {
       run[b] = run0;
-      kind[b] = 0;
+      kind[b] = HILC_DTX_HELD;
     }
     return;
   }
   // autocorrelation: lane l's partial of lag k over s = l (mod 64), s >= k, in increasing s (exact products in float64).  The hop
-  // goes through LDS one frame (320 samples, with the 16 before it) at a time: one round of independent loads per frame.
+  // goes through LDS one frame (with the HILC_DTX_MAX_ORDER samples before it) at a time: one round of independent loads per frame.
   const float* xb = x + (long)b * S;
   double p[K + 1];
 #pragma unroll
   for (int k = 0; k <= K; ++k) p[k] = 0.0;
-  for (int base = 0; base < S; base += FRAME) {
-    float v[FRAME / LANES];
+  for (int base = 0; base < S; base += HILC_RESAMPLE_HOP) {
+    float v[HILC_RESAMPLE_HOP / LANES];
 #pragma unroll
-    for (int i = 0; i < FRAME / LANES; ++i) v[i] = xb[base + i * LANES + lane];
-    const float hv = (lane < MAX_ORDER && base > 0) ? xb[base - MAX_ORDER + lane] : 0.f;
+    for (int i = 0; i < HILC_RESAMPLE_HOP / LANES; ++i) v[i] = xb[base + i * LANES + lane];
+    const float hv = (lane < HILC_DTX_MAX_ORDER && base > 0) ? xb[base - HILC_DTX_MAX_ORDER + lane] : 0.f;
     wave_sync();                                           // the previous frame's reads are done
 #pragma unroll
-    for (int i = 0; i < FRAME / LANES; ++i) xs[w][MAX_ORDER + i * LANES + lane] = v[i];
-    if (lane < MAX_ORDER) xs[w][lane] = hv;
+    for (int i = 0; i < HILC_RESAMPLE_HOP / LANES; ++i) xs[w][HILC_DTX_MAX_ORDER + i * LANES + lane] = v[i];
+    if (lane < HILC_DTX_MAX_ORDER) xs[w][lane] = hv;
     wave_sync();
 #pragma unroll
-    for (int i = 0; i < FRAME / LANES; ++i) {
+    for (int i = 0; i < HILC_RESAMPLE_HOP / LANES; ++i) {
       const int s = base + i * LANES + lane;
       const double xd = (double)v[i];
 #pragma unroll
       for (int k = 0; k <= K; ++k)
-        if (s >= k) p[k] = __dadd_rn(p[k], __dmul_rn(xd, (double)xs[w][MAX_ORDER + i * LANES + lane - k]));
+        if (s >= k) p[k] = __dadd_rn(p[k], __dmul_rn(xd, (double)xs[w][HILC_DTX_MAX_ORDER + i * LANES + lane - k]));
     }
   }
 #pragma unroll
@@ -132,22 +127,22 @@ __global__ __launch_bounds__(THREADS) void dtx_encode_kernel(const float* __rest
   // level: #{j < 127 : E_K / S < thr[j]}, lanes j and j + 64
   const double ev = __ddiv_rn(E, (double)S);
   const bool c0 = ev < thr0;
-  const bool c1 = lane + LANES < LEVELS - 1 && ev < thr1;
+  const bool c1 = lane + LANES < HILC_DTX_LEVELS - 1 && ev < thr1;
   const int L = __popcll(__ballot(c0)) + __popcll(__ballot(c1));
   // the state machine
   int r;
   if (active) r = 0;
   else if (run0 <= H) r = run0 + 1;
   else r = H + 1 + (run0 - H) % I;
-  const int kd = (active || r <= H) ? SPEECH : (r == H + 1 ? SID : SILENT);
+  const int kd = (active || r <= H) ? HILC_DTX_SPEECH : (r == H + 1 ? HILC_DTX_SID : HILC_DTX_SILENT);
   if (lane == 0) {
     run[b] = r;
     kind[b] = kd;
   }
-  if (kd == SPEECH) return;
+  if (kd == HILC_DTX_SPEECH) return;
   // SID / SILENT: the packet row, its byte count, the indices and the FEC row's valid flag
   int byte = 0;
-  if (kd == SID) {
+  if (kd == HILC_DTX_SID) {
     if (lane == 0) byte = L;
 #pragma unroll
     for (int i = 1; i <= K; ++i) {
@@ -157,7 +152,7 @@ __global__ __launch_bounds__(THREADS) void dtx_encode_kernel(const float* __rest
   }
   uint8_t* row = packets + (long)b * stride;
   for (int j = lane; j < stride; j += LANES) row[j] = (uint8_t)(j == lane ? byte : 0);
-  if (lane == 0) nbytes[b] = kd == SID ? 1 + K : 0;
+  if (lane == 0) nbytes[b] = kd == HILC_DTX_SID ? 1 + K : 0;
   clear_rows(indices, 0, n_max, B, b, T, lane);
   if (prev != nullptr && lane == 0) prev[(long)b * prev_words] = 0;
 }
@@ -170,19 +165,19 @@ __global__ __launch_bounds__(THREADS) void cng_synth_kernel(const uint8_t* __res
   const Wave me = this_wave(B);
   if (!me.ok) return;
   const int b = me.b, lane = me.lane();
-  constexpr int W = ST_Q + 2 * K;
+  constexpr int W = HILC_DTX_ST_Q + 2 * K;
   int* st = state + (long)b * W;
   const bool reset = is_reset(action, b);                 // the state row starts from zero
   const int h = hold[b];
   int word = (lane < W && !reset) ? st[lane] : 0;
-  const int byte = (h == 2 && lane <= K) ? (int)packets[(long)b * stride + lane] : 0;
-  const int has = readlane_i(word, ST_HAS);
-  const bool noise = h == 2 || (h == 3 && has != 0);
+  const int byte = (h == HILC_SESSIONS_HOLD_SID && lane <= K) ? (int)packets[(long)b * stride + lane] : 0;
+  const int has = readlane_i(word, HILC_DTX_ST_HAS);
+  const bool noise = h == HILC_SESSIONS_HOLD_SID || (h == HILC_SESSIONS_HOLD_SILENT && has != 0);
   if (!noise) {
-    if (h == 0 && lane == ST_HAS) word = 0;               // decoded this hop: the next SID starts from zero filter memory
+    if (h == HILC_SESSIONS_HOLD_ADVANCE && lane == HILC_DTX_ST_HAS) word = 0;   // decoded: the next SID starts from zero filter memory
     if (lane < W) st[lane] = word;
     if (lane == 0) {
-      if (h == 3) hold[b] = 1;                            // silent without a SID: held by the graph
+      if (h == HILC_SESSIONS_HOLD_SILENT) hold[b] = HILC_SESSIONS_HOLD_HELD;     // silent without a SID: held by the graph
       if (restore != nullptr) restore[b] = 0;
     }
     return;
@@ -190,20 +185,20 @@ __global__ __launch_bounds__(THREADS) void cng_synth_kernel(const uint8_t* __res
   int L;
   int q[K + 1];
   float mem[K + 1];
-  if (h == 2) {
-    L = min(readlane_i(byte, 0), LEVELS - 1);
+  if (h == HILC_SESSIONS_HOLD_SID) {
+    L = min(readlane_i(byte, 0), HILC_DTX_LEVELS - 1);
 #pragma unroll
     for (int i = 1; i <= K; ++i) q[i] = max(-127, min(127, (int)(int8_t)readlane_i(byte, i)));
 #pragma unroll
-    for (int i = 0; i < K; ++i) mem[i] = has != 0 ? __int_as_float(readlane_i(word, ST_Q + K + i)) : 0.f;
+    for (int i = 0; i < K; ++i) mem[i] = has != 0 ? __int_as_float(readlane_i(word, HILC_DTX_ST_Q + K + i)) : 0.f;
   } else {
-    L = readlane_i(word, ST_LEVEL);
+    L = readlane_i(word, HILC_DTX_ST_LEVEL);
 #pragma unroll
-    for (int i = 1; i <= K; ++i) q[i] = readlane_i(word, ST_Q + i - 1);
+    for (int i = 1; i <= K; ++i) q[i] = readlane_i(word, HILC_DTX_ST_Q + i - 1);
 #pragma unroll
-    for (int i = 0; i < K; ++i) mem[i] = __int_as_float(readlane_i(word, ST_Q + K + i));
+    for (int i = 0; i < K; ++i) mem[i] = __int_as_float(readlane_i(word, HILC_DTX_ST_Q + K + i));
   }
-  const uint32_t c = (uint32_t)readlane_i(word, ST_COUNT);
+  const uint32_t c = (uint32_t)readlane_i(word, HILC_DTX_ST_COUNT);
   // step-up recursion in float64, rounded once to fp32
   double ad[K + 1];
 #pragma unroll
@@ -222,7 +217,7 @@ __global__ __launch_bounds__(THREADS) void cng_synth_kernel(const uint8_t* __res
 #pragma unroll
   for (int i = 1; i <= K; ++i) a[i] = (float)ad[i];
   const float g = gains[L];
-  const uint32_t seed = (uint32_t)(b + 1) * 0x9E3779B9u;
+  const uint32_t seed = (uint32_t)(b + 1) * HILC_DTX_GOLDEN;
   float* out = wav + (long)b * S;
   bool wild = false;                                      // some |y[s]| >= NOISE_BOUND or not finite
   for (int c0 = 0; c0 < S; c0 += LANES) {
@@ -251,18 +246,18 @@ __global__ __launch_bounds__(THREADS) void cng_synth_kernel(const uint8_t* __res
   }
   // the new state row: has 1, L, c + 1, q, the filter memory
   int nw = 0;
-  if (lane == ST_HAS) nw = 1;
-  if (lane == ST_LEVEL) nw = L;
-  if (lane == ST_COUNT) nw = (int)(c + 1u);
+  if (lane == HILC_DTX_ST_HAS) nw = 1;
+  if (lane == HILC_DTX_ST_LEVEL) nw = L;
+  if (lane == HILC_DTX_ST_COUNT) nw = (int)(c + 1u);
 #pragma unroll
   for (int i = 1; i <= K; ++i)
-    if (lane == ST_Q + i - 1) nw = q[i];
+    if (lane == HILC_DTX_ST_Q + i - 1) nw = q[i];
 #pragma unroll
   for (int i = 0; i < K; ++i)
-    if (lane == ST_Q + K + i) nw = __float_as_int(mem[i]);
+    if (lane == HILC_DTX_ST_Q + K + i) nw = __float_as_int(mem[i]);
   if (lane < W) st[lane] = nw;
   if (lane == 0) {
-    hold[b] = 0;
+    hold[b] = HILC_SESSIONS_HOLD_ADVANCE;
     if (restore != nullptr) restore[b] = 1;
   }
 }
@@ -276,8 +271,8 @@ extern "C" int hilc_dtx_encode(const float* x, const int* action, const int* hol
                                int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) {
   if (!x || !run || !kind || !packets || !nbytes || !indices || !level_thr) return HILC_ERR_NULL;
   if (B <= 0 || T <= 0 || n_max <= 0 || stride <= 0 || (prev && prev_words <= 0)) return HILC_ERR_SHAPE;
-  if (T > (1 << 20) / 320) return HILC_ERR_SHAPE;
-  if (order < 0 || order > MAX_ORDER || hangover < 0 || sid_interval < 1 || hangover > (1 << 30) || sid_interval > (1 << 30))
+  if (T > (1 << 20) / HILC_RESAMPLE_HOP) return HILC_ERR_SHAPE;
+  if (order < 0 || order > HILC_DTX_MAX_ORDER || hangover < 0 || sid_interval < 1 || hangover > (1 << 30) || sid_interval > (1 << 30))
     return HILC_ERR_RANGE;
   if (stride < 1 + order) return HILC_ERR_SHAPE;          // a SID must fit the row
   switch (order) {
@@ -294,13 +289,13 @@ extern "C" int hilc_dtx_encode(const float* x, const int* action, const int* hol
 extern "C" int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore,
                               const float* gains, int B, int T, int order, int stride, void* stream) {
   if (!packets || !hold || !state || !wav || !gains) return HILC_ERR_NULL;
-  if (B <= 0 || T <= 0 || T > (1 << 20) / 320) return HILC_ERR_SHAPE;
-  if (order < 0 || order > MAX_ORDER) return HILC_ERR_RANGE;
+  if (B <= 0 || T <= 0 || T > (1 << 20) / HILC_RESAMPLE_HOP) return HILC_ERR_SHAPE;
+  if (order < 0 || order > HILC_DTX_MAX_ORDER) return HILC_ERR_RANGE;
   if (stride < 1 + order) return HILC_ERR_SHAPE;
   switch (order) {
 #define X(K) \
   case K:    \
-    return launch(cng_synth_kernel<K>, waves_grid(B), stream, packets, action, hold, state, wav, restore, gains, B, 320 * T, stride);
+    return launch(cng_synth_kernel<K>, waves_grid(B), stream, packets, action, hold, state, wav, restore, gains, B, HILC_RESAMPLE_HOP * T, stride);
     HILC_DTX_ORDERS(X)
 #undef X
   }

@@ -15,8 +15,6 @@ namespace {
 
 using namespace jring;
 
-constexpr int KIND_SID = 2;         // dtx.SID
-
 // one thread per output byte, the shape of pack_codes_kernel; thread 0 of a row writes its byte count and next counter
 __global__ __launch_bounds__(THREADS) void packet_header_kernel(const uint8_t* __restrict__ packets, const int* __restrict__ nbytes,
                                                                 const int* __restrict__ n_per_stream, const int* __restrict__ kind,
@@ -34,7 +32,7 @@ __global__ __launch_bounds__(THREADS) void packet_header_kernel(const uint8_t* _
   const int len = held ? 0 : clampi(nbytes[b], 0, istride);
   if (j == 0) {
     ctr_out[b] = held ? cur : ((cur + 1) & 0xFFFF);         // a DTX SILENT hop (len 0, not held) advances it too
-    out_nbytes[b] = len > 0 ? HDR + len : 0;
+    out_nbytes[b] = len > 0 ? HILC_WIRE_TRANSPORT_HEADER + len : 0;
   }
   uint32_t v = 0;
   if (len > 0) {
@@ -43,14 +41,14 @@ __global__ __launch_bounds__(THREADS) void packet_header_kernel(const uint8_t* _
     } else if (j == 1) {
       v = (uint32_t)cur & 0xFFu;
     } else if (j == 2) {
-      if (kind != nullptr && kind[b] == KIND_SID) {
-        v = 0x80u;
+      if (kind != nullptr && kind[b] == HILC_DTX_SID) {
+        v = HILC_WIRE_SID_BIT;
       } else {
         const int nb = clamp_n(n_per_stream, (long)b, m > 1 ? m : 1, n_max);
-        v = (uint32_t)nb | ((m >= 1 && len == packet_bytes(nb + m, T)) ? 0x40u : 0u);
+        v = (uint32_t)nb | ((m >= 1 && len == packet_bytes(nb + m, T)) ? HILC_WIRE_FEC_BIT : 0u);
       }
-    } else if (j - HDR < len) {
-      v = packets[(long)b * istride + (j - HDR)];
+    } else if (j - HILC_WIRE_TRANSPORT_HEADER < len) {
+      v = packets[(long)b * istride + (j - HILC_WIRE_TRANSPORT_HEADER)];
     }
   }
   out[e] = (uint8_t)v;
@@ -66,59 +64,59 @@ __global__ __launch_bounds__(THREADS) void jitter_step_kernel(const int* __restr
   const Wave me = this_wave(B);
   if (!me.ok) return;
   const int b = me.b, lane = me.lane();
-  int* st = state + (long)b * ST_WORDS;
+  int* st = state + (long)b * HILC_JITTER_ST_WORDS;
   int* mrow = meta + (long)b * C;
   int* rrow = ring + (long)b * C * rw;
   const bool start = is_reset(action, b);
-  int s[ST_WORDS];
+  int s[HILC_JITTER_ST_WORDS];
 #pragma unroll
-  for (int k = 0; k < ST_WORDS; ++k) s[k] = start ? 0 : st[k];
+  for (int k = 0; k < HILC_JITTER_ST_WORDS; ++k) s[k] = start ? 0 : st[k];
   uint32_t my_meta = (lane < C && !start) ? (uint32_t)mrow[lane] : 0u;
-  const int tb = HDR + stride;
+  const int tb = HILC_WIRE_TRANSPORT_HEADER + stride;
   const int a0 = clampi(off[b], 0, max_a);
   const int a1 = clampi(off[b + 1], a0, max_a);
   for (int a = a0; a < a1; ++a) {
     const int* rec = arr + (long)a * (1 + aw);
     const Arrival p = parse_arrival(rec, tb, T, n_max, m, order);
     if (!p.ok) {
-      ++s[STAT_MALFORMED];
+      ++s[HILC_JITTER_STAT_MALFORMED];
       continue;
     }
     const int i = (int)p.hop & (C - 1);
-    if (!s[ST_ANCHORED]) {
-      s[ST_ANCHORED] = 1;
-      s[ST_NEXT] = (int)p.hop;
-      s[ST_WAIT] = depth;
+    if (!s[HILC_JITTER_ST_ANCHORED]) {
+      s[HILC_JITTER_ST_ANCHORED] = 1;
+      s[HILC_JITTER_ST_NEXT] = (int)p.hop;
+      s[HILC_JITTER_ST_WAIT] = depth;
     } else {
-      const int d = int16_of((int)p.hop - s[ST_NEXT]);
+      const int d = int16_of((int)p.hop - s[HILC_JITTER_ST_NEXT]);
       if (d < 0) {
-        ++s[STAT_LATE];
+        ++s[HILC_JITTER_STAT_LATE];
         continue;
       }
       if (d >= C) {
-        ++s[STAT_EARLY];
+        ++s[HILC_JITTER_STAT_EARLY];
         continue;
       }
-      if (((uint32_t)s[ST_MASK] >> i) & 1u) {
-        ++s[STAT_DUPLICATE];
+      if (((uint32_t)s[HILC_JITTER_ST_MASK] >> i) & 1u) {
+        ++s[HILC_JITTER_STAT_DUPLICATE];
         continue;
       }
     }
     if (lane == i) my_meta = p.meta();
     store_body(rec, rrow + (long)i * rw, p.body, aw, rw, lane);
-    s[ST_MASK] = (int)((uint32_t)s[ST_MASK] | (1u << i));
-    ++s[STAT_ACCEPTED];
+    s[HILC_JITTER_ST_MASK] = (int)((uint32_t)s[HILC_JITTER_ST_MASK] | (1u << i));
+    ++s[HILC_JITTER_STAT_ACCEPTED];
   }
 
   // play
   const int hin = hold[b];
   int ho = hin, no = n_max, lo = 0, fo = 0, src = -1;
   if (hin == 0) {
-    if (!s[ST_ANCHORED]) {
-      ho = 1;
-    } else if (s[ST_WAIT] > 0) {
-      --s[ST_WAIT];
-      ho = 1;
+    if (!s[HILC_JITTER_ST_ANCHORED]) {
+      ho = HILC_SESSIONS_HOLD_HELD;
+    } else if (s[HILC_JITTER_ST_WAIT] > 0) {
+      --s[HILC_JITTER_ST_WAIT];
+      ho = HILC_SESSIONS_HOLD_HELD;
     } else {
       play_entry(s, my_meta, lane, C, m, conceal, ho, no, lo, fo, src);
     }
@@ -131,7 +129,7 @@ __global__ __launch_bounds__(THREADS) void jitter_step_kernel(const int* __restr
     if (lost != nullptr) lost[b] = lo;
     if (fec != nullptr) fec[b] = fo;
 #pragma unroll
-    for (int k = 0; k < ST_WORDS; ++k) st[k] = s[k];
+    for (int k = 0; k < HILC_JITTER_ST_WORDS; ++k) st[k] = s[k];
   }
 }
 
@@ -146,7 +144,7 @@ extern "C" int hilc_packet_header(const uint8_t* packets, const int* nbytes, con
   if (n_max > 31 || n_max + m > MAX_N) return HILC_ERR_UNSUPPORTED;
   const long istride = packet_bytes<long>(n_max + m, T);
   if (istride > (1L << 29)) return HILC_ERR_SHAPE;
-  const long ostride = HDR + istride;
+  const long ostride = HILC_WIRE_TRANSPORT_HEADER + istride;
   return launch(packet_header_kernel, threads_grid(B * ostride), stream, packets, nbytes, n_per_stream, kind, action, hold, counter_in,
                 counter_out, out, out_nbytes, B, T, n_max, m, (int)istride, (int)ostride);
 }
@@ -159,7 +157,7 @@ extern "C" int hilc_jitter_step(const int* arrivals, const int* offsets, int max
                             order, conceal, depth, capacity, &stride);
   if (rc != HILC_OK) return rc;
   const int rw = (int)((stride + 3) / 4);
-  const int aw = (int)((HDR + stride + 3) / 4);
+  const int aw = (int)((HILC_WIRE_TRANSPORT_HEADER + stride + 3) / 4);
   return launch(jitter_step_kernel, waves_grid(B), stream, arrivals, offsets, max_arrivals, aw, action, hold, n_per_stream, lost, fec,
                 packets, state, meta, ring, B, T, n_max, m, order, conceal != 0 ? 1 : 0, depth, capacity, (int)stride, rw);
 }

@@ -1,6 +1,6 @@
 // Adaptive playout of the receiver's jitter buffer (graph_step.GraphedDecodeHop(jitter=JitterConfig(..., adapt=AdaptConfig(...)))):
 // hilc_jitter_adapt_step takes the place of hilc_jitter_step as the receiver graph's first launch.  Same arrivals, ring, state row and
-// output rows (jitter_ring.h); beside them one adapt row per slot (jitter.py: AD_*), with which the slot moves its playout clock
+// output rows (jitter_ring.h); beside them one adapt row per slot (HILC_JITTER_AD_*), with which the slot moves its playout clock
 // against the sender's: an inserted hop (grow), a skipped entry (shrink) or a new anchor (resync).  The rules, bit for bit:
 // hilcodec_amd/jitter.py (JitterModel with cfg.adapt).  Integer work only.
 #include "jitter_ring.h"
@@ -9,16 +9,11 @@ namespace {
 
 using namespace jring;
 
-// jitter.py: AD_*
-constexpr int AD_DEBT = 0, AD_PENDING = 1, AD_STALE = 2, AD_MIN = 3, AD_COUNT = 4, AD_RUN = 5, AD_LAST = 6, AD_MARGIN = 7;
-constexpr int AD_GROWN = 8, AD_SHRUNK = 9, AD_FORCED = 10, AD_RESYNC = 11;
-constexpr int AD_WORDS = 12;
-
 __device__ __forceinline__ void clear_control(int* ad, int C, int depth) {
 #pragma unroll
-  for (int k = 0; k < AD_GROWN; ++k) ad[k] = 0;
-  ad[AD_MIN] = C;
-  ad[AD_MARGIN] = depth;
+  for (int k = 0; k < HILC_JITTER_AD_GROWN; ++k) ad[k] = 0;
+  ad[HILC_JITTER_AD_MIN] = C;
+  ad[HILC_JITTER_AD_MARGIN] = depth;
 }
 
 __device__ __forceinline__ int sign_of(int v) { return (v > 0) - (v < 0); }
@@ -32,137 +27,137 @@ __global__ __launch_bounds__(THREADS) void jitter_adapt_step_kernel(
   const Wave me = this_wave(B);
   if (!me.ok) return;
   const int b = me.b, lane = me.lane();
-  int* st = state + (long)b * ST_WORDS;
-  int* arow = adapt + (long)b * AD_WORDS;
+  int* st = state + (long)b * HILC_JITTER_ST_WORDS;
+  int* arow = adapt + (long)b * HILC_JITTER_AD_WORDS;
   int* mrow = meta + (long)b * C;
   int* rrow = ring + (long)b * C * rw;
   const bool start = is_reset(action, b);
-  int s[ST_WORDS], ad[AD_WORDS];
+  int s[HILC_JITTER_ST_WORDS], ad[HILC_JITTER_AD_WORDS];
 #pragma unroll
-  for (int k = 0; k < ST_WORDS; ++k) s[k] = start ? 0 : st[k];
+  for (int k = 0; k < HILC_JITTER_ST_WORDS; ++k) s[k] = start ? 0 : st[k];
 #pragma unroll
-  for (int k = 0; k < AD_WORDS; ++k) ad[k] = start ? 0 : arow[k];
+  for (int k = 0; k < HILC_JITTER_AD_WORDS; ++k) ad[k] = start ? 0 : arow[k];
   uint32_t my_meta = (lane < C && !start) ? (uint32_t)mrow[lane] : 0u;
-  const int tb = HDR + stride;
+  const int tb = HILC_WIRE_TRANSPORT_HEADER + stride;
   const int a0 = clampi(off[b], 0, max_a);
   const int a1 = clampi(off[b + 1], a0, max_a);
   for (int a = a0; a < a1; ++a) {
     const int* rec = arr + (long)a * (1 + aw);
     const Arrival p = parse_arrival(rec, tb, T, n_max, m, order);
     if (!p.ok) {
-      ++s[STAT_MALFORMED];
+      ++s[HILC_JITTER_STAT_MALFORMED];
       continue;
     }
     const int hop = (int)p.hop;
     const int i = hop & (C - 1);
-    if (!s[ST_ANCHORED]) {
-      s[ST_ANCHORED] = 1;
-      s[ST_NEXT] = hop;
-      s[ST_WAIT] = depth;
+    if (!s[HILC_JITTER_ST_ANCHORED]) {
+      s[HILC_JITTER_ST_ANCHORED] = 1;
+      s[HILC_JITTER_ST_NEXT] = hop;
+      s[HILC_JITTER_ST_WAIT] = depth;
       clear_control(ad, C, depth);
     } else {
-      const int d = int16_of(hop - s[ST_NEXT]);
+      const int d = int16_of(hop - s[HILC_JITTER_ST_NEXT]);
       if (d < 0 || d >= C) {
         if (d < 0)
-          ++s[STAT_LATE];
+          ++s[HILC_JITTER_STAT_LATE];
         else
-          ++s[STAT_EARLY];
-        const int gap = int16_of(hop - ad[AD_LAST]);
-        ad[AD_RUN] = (ad[AD_RUN] > 0 && (gap < 0 ? -gap : gap) < C) ? ad[AD_RUN] + 1 : 1;
-        ad[AD_LAST] = hop;
-        if (ad[AD_RUN] < resync) {
-          if (s[ST_WAIT] == 0) {                            // dropped, but close enough to move the clock at once
+          ++s[HILC_JITTER_STAT_EARLY];
+        const int gap = int16_of(hop - ad[HILC_JITTER_AD_LAST]);
+        ad[HILC_JITTER_AD_RUN] = (ad[HILC_JITTER_AD_RUN] > 0 && (gap < 0 ? -gap : gap) < C) ? ad[HILC_JITTER_AD_RUN] + 1 : 1;
+        ad[HILC_JITTER_AD_LAST] = hop;
+        if (ad[HILC_JITTER_AD_RUN] < resync) {
+          if (s[HILC_JITTER_ST_WAIT] == 0) {                            // dropped, but close enough to move the clock at once
             if (d < 0) {
-              if (-d <= max_late) ad[AD_DEBT] = max(ad[AD_DEBT], -d);
+              if (-d <= max_late) ad[HILC_JITTER_AD_DEBT] = max(ad[HILC_JITTER_AD_DEBT], -d);
             } else if (d - (C - 1) <= max_late) {
-              ad[AD_DEBT] = min(ad[AD_DEBT], (C - 1) - d);
+              ad[HILC_JITTER_AD_DEBT] = min(ad[HILC_JITTER_AD_DEBT], (C - 1) - d);
             }
           }
           continue;
         }
         // resync: the run of outliers is the stream; the slot anchors on this one and the ring starts empty
-        s[ST_NEXT] = hop;
-        s[ST_WAIT] = depth;
-        s[ST_IN_DTX] = 0;
-        s[ST_MASK] = 0;
+        s[HILC_JITTER_ST_NEXT] = hop;
+        s[HILC_JITTER_ST_WAIT] = depth;
+        s[HILC_JITTER_ST_IN_DTX] = 0;
+        s[HILC_JITTER_ST_MASK] = 0;
         my_meta = 0u;
         clear_control(ad, C, depth);
-        ++ad[AD_RESYNC];
-      } else if (((uint32_t)s[ST_MASK] >> i) & 1u) {
-        ++s[STAT_DUPLICATE];
-        ad[AD_RUN] = 0;
+        ++ad[HILC_JITTER_AD_RESYNC];
+      } else if (((uint32_t)s[HILC_JITTER_ST_MASK] >> i) & 1u) {
+        ++s[HILC_JITTER_STAT_DUPLICATE];
+        ad[HILC_JITTER_AD_RUN] = 0;
         continue;
       } else {
-        ad[AD_RUN] = 0;
-        if (s[ST_WAIT] == 0) ad[AD_MIN] = min(ad[AD_MIN], d);
+        ad[HILC_JITTER_AD_RUN] = 0;
+        if (s[HILC_JITTER_ST_WAIT] == 0) ad[HILC_JITTER_AD_MIN] = min(ad[HILC_JITTER_AD_MIN], d);
       }
     }
     if (lane == i) my_meta = p.meta();
     store_body(rec, rrow + (long)i * rw, p.body, aw, rw, lane);
-    s[ST_MASK] = (int)((uint32_t)s[ST_MASK] | (1u << i));
-    ++s[STAT_ACCEPTED];
+    s[HILC_JITTER_ST_MASK] = (int)((uint32_t)s[HILC_JITTER_ST_MASK] | (1u << i));
+    ++s[HILC_JITTER_STAT_ACCEPTED];
   }
 
   // play
   const int hin = hold[b];
   int ho = hin, no = n_max, lo = 0, fo = 0, src = -1;
   if (hin == 0) {
-    if (!s[ST_ANCHORED]) {
-      ho = 1;
-    } else if (s[ST_WAIT] > 0) {
-      --s[ST_WAIT];
-      ho = 1;
+    if (!s[HILC_JITTER_ST_ANCHORED]) {
+      ho = HILC_SESSIONS_HOLD_HELD;
+    } else if (s[HILC_JITTER_ST_WAIT] > 0) {
+      --s[HILC_JITTER_ST_WAIT];
+      ho = HILC_SESSIONS_HOLD_HELD;
     } else {
-      const int h = s[ST_NEXT];
+      const int h = s[HILC_JITTER_ST_NEXT];
       const int i = h & (C - 1), j = (h + 1) & (C - 1);
-      const uint32_t mask = (uint32_t)s[ST_MASK];
+      const uint32_t mask = (uint32_t)s[HILC_JITTER_ST_MASK];
       const uint32_t mj = (uint32_t)__shfl((int)my_meta, j);
       const bool present = ((mask >> i) & 1u) != 0;
-      const bool fecable = m >= 1 && ((mask >> j) & 1u) && !(mj & META_SID) && (mj & META_FEC);
-      const bool free_hop = !present && (s[ST_IN_DTX] || !fecable);     // noise or a loss whatever the clock does
-      const bool forced = force_windows > 0 && ad[AD_STALE] >= force_windows;
+      const bool fecable = m >= 1 && ((mask >> j) & 1u) && !(mj & HILC_JITTER_META_SID) && (mj & HILC_JITTER_META_FEC);
+      const bool free_hop = !present && (s[HILC_JITTER_ST_IN_DTX] || !fecable);     // noise or a loss whatever the clock does
+      const bool forced = force_windows > 0 && ad[HILC_JITTER_AD_STALE] >= force_windows;
       int step = 0;
-      if (ad[AD_DEBT] != 0) {
-        step = sign_of(ad[AD_DEBT]);
-        ad[AD_DEBT] -= step;
-        if (sign_of(ad[AD_PENDING]) == step) ad[AD_PENDING] -= step;
-      } else if (ad[AD_PENDING] != 0 && (free_hop || forced)) {
-        step = sign_of(ad[AD_PENDING]);
-        ad[AD_PENDING] -= step;
-        if (!free_hop) ++ad[AD_FORCED];
+      if (ad[HILC_JITTER_AD_DEBT] != 0) {
+        step = sign_of(ad[HILC_JITTER_AD_DEBT]);
+        ad[HILC_JITTER_AD_DEBT] -= step;
+        if (sign_of(ad[HILC_JITTER_AD_PENDING]) == step) ad[HILC_JITTER_AD_PENDING] -= step;
+      } else if (ad[HILC_JITTER_AD_PENDING] != 0 && (free_hop || forced)) {
+        step = sign_of(ad[HILC_JITTER_AD_PENDING]);
+        ad[HILC_JITTER_AD_PENDING] -= step;
+        if (!free_hop) ++ad[HILC_JITTER_AD_FORCED];
       }
       if (step != 0) {
-        ad[AD_MIN] = C;
-        ad[AD_COUNT] = 0;
-        if (ad[AD_PENDING] == 0) ad[AD_STALE] = 0;
+        ad[HILC_JITTER_AD_MIN] = C;
+        ad[HILC_JITTER_AD_COUNT] = 0;
+        if (ad[HILC_JITTER_AD_PENDING] == 0) ad[HILC_JITTER_AD_STALE] = 0;
       }
       if (step > 0) {                                       // grow: an inserted hop, the clock stands
-        ++ad[AD_GROWN];
-        if (s[ST_IN_DTX])
-          ho = 3;
+        ++ad[HILC_JITTER_AD_GROWN];
+        if (s[HILC_JITTER_ST_IN_DTX])
+          ho = HILC_SESSIONS_HOLD_SILENT;
         else if (conceal)
           lo = 1;
         else
-          ho = 1;
+          ho = HILC_SESSIONS_HOLD_HELD;
       } else {
         if (step < 0) {                                     // shrink: entry h is skipped, the hop plays h + 1
           if (present) {
-            s[ST_MASK] = (int)(mask & ~(1u << i));
+            s[HILC_JITTER_ST_MASK] = (int)(mask & ~(1u << i));
             if (lane == i) my_meta = 0u;
           }
-          s[ST_NEXT] = (h + 1) & 0xFFFF;
-          ++ad[AD_SHRUNK];
+          s[HILC_JITTER_ST_NEXT] = (h + 1) & 0xFFFF;
+          ++ad[HILC_JITTER_AD_SHRUNK];
         }
         play_entry(s, my_meta, lane, C, m, conceal, ho, no, lo, fo, src);   // its shuffles and src come after the skip
-        if (++ad[AD_COUNT] >= window) {
-          if (ad[AD_MIN] < C) {
-            const int want = headroom - ad[AD_MIN];
-            ad[AD_MARGIN] = ad[AD_MIN];
-            ad[AD_STALE] = (want != 0 && sign_of(want) == sign_of(ad[AD_PENDING])) ? ad[AD_STALE] + 1 : 0;
-            ad[AD_PENDING] = want;
+        if (++ad[HILC_JITTER_AD_COUNT] >= window) {
+          if (ad[HILC_JITTER_AD_MIN] < C) {
+            const int want = headroom - ad[HILC_JITTER_AD_MIN];
+            ad[HILC_JITTER_AD_MARGIN] = ad[HILC_JITTER_AD_MIN];
+            ad[HILC_JITTER_AD_STALE] = (want != 0 && sign_of(want) == sign_of(ad[HILC_JITTER_AD_PENDING])) ? ad[HILC_JITTER_AD_STALE] + 1 : 0;
+            ad[HILC_JITTER_AD_PENDING] = want;
           }
-          ad[AD_MIN] = C;
-          ad[AD_COUNT] = 0;
+          ad[HILC_JITTER_AD_MIN] = C;
+          ad[HILC_JITTER_AD_COUNT] = 0;
         }
       }
     }
@@ -175,9 +170,9 @@ __global__ __launch_bounds__(THREADS) void jitter_adapt_step_kernel(
     if (lost != nullptr) lost[b] = lo;
     if (fec != nullptr) fec[b] = fo;
 #pragma unroll
-    for (int k = 0; k < ST_WORDS; ++k) st[k] = s[k];
+    for (int k = 0; k < HILC_JITTER_ST_WORDS; ++k) st[k] = s[k];
 #pragma unroll
-    for (int k = 0; k < AD_WORDS; ++k) arow[k] = ad[k];
+    for (int k = 0; k < HILC_JITTER_AD_WORDS; ++k) arow[k] = ad[k];
   }
 }
 
@@ -195,7 +190,7 @@ extern "C" int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, i
   if (headroom < 0 || headroom > capacity - 2 || max_late < 1 || max_late > capacity - 2) return HILC_ERR_RANGE;
   if (window < 1 || resync < 2 || force_windows < 0) return HILC_ERR_RANGE;
   const int rw = (int)((stride + 3) / 4);
-  const int aw = (int)((HDR + stride + 3) / 4);
+  const int aw = (int)((HILC_WIRE_TRANSPORT_HEADER + stride + 3) / 4);
   return launch(jitter_adapt_step_kernel, waves_grid(B), stream, arrivals, offsets, max_arrivals, aw, action, hold, n_per_stream, lost,
                 fec, packets, state, meta, ring, adapt, B, T, n_max, m, order, conceal != 0 ? 1 : 0, depth, capacity, (int)stride, rw,
                 headroom, max_late, window, resync, force_windows);

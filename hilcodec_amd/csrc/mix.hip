@@ -15,7 +15,6 @@ namespace {
 
 using namespace slot;
 
-constexpr int MAX_TOP_K = 8;
 
 __global__ __launch_bounds__(THREADS) void mix_levels_kernel(const float* __restrict__ wav, double* __restrict__ score,
                                                              const int* __restrict__ action, int B, int L) {
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(THREADS) void mix_rooms_kernel(const float* __restr
                                                             int* __restrict__ speakers, int B, int L) {
   __shared__ double wbest[WAVES];
   __shared__ int wslot[WAVES];
-  __shared__ int sel[MAX_TOP_K];
+  __shared__ int sel[HILC_MIXER_MAX_TOP_K];
   const int b = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = room[b];
@@ -133,6 +132,6 @@ extern "C" int hilc_mix_rooms(const float* wav, const int* room, const double* s
                               int L, void* stream) {
   if (!wav || !room || !score || !mixed || !speakers) return HILC_ERR_NULL;
   if (B < 1 || L < 1) return HILC_ERR_SHAPE;
-  if (top_k < 1 || top_k > MAX_TOP_K) return HILC_ERR_UNSUPPORTED;
+  if (top_k < 1 || top_k > HILC_MIXER_MAX_TOP_K) return HILC_ERR_UNSUPPORTED;
   return launch(mix_rooms_kernel, dim3((unsigned)B), stream, wav, room, score, top_k, mixed, speakers, B, L);
 }

@@ -8,28 +8,13 @@
 //                   moves its on / off switch and, for a slot that is off, clears word 0 ("valid") of its previous-codes row, so the
 //                   packer appends no redundant section.
 //
-// The rules, bit for bit: hilcodec_amd/report.py (ReportModel, FecAdaptModel).  Every value is wave-uniform; lane 0 stores the rows
-// (plain vector stores), the ring words of a report row are stored one per lane.
+// The rules, bit for bit: hilcodec_amd/report.py (ReportModel, FecAdaptModel); the rows: include/hilcodec_amd.h (HILC_REPORT_*).
+// Every value is wave-uniform; lane 0 stores the rows (plain vector stores), the ring words of a report row are stored one per lane.
 #include "slot.h"
 
 namespace {
 
 using namespace slot;
-
-// jitter.py: ST_WORDS, STAT_*
-constexpr int ST_WORDS = 14, STAT_DECODED = 10, STAT_FEC = 11, STAT_LOST = 12, STAT_NOISE = 13;
-
-// report.py: RP_*
-constexpr int RP_SEQ = 0, RP_LOSS = 1, RP_RESIDUAL = 2, RP_PHASE = 3, RP_N = 4, RP_F = 5, RP_L = 6, RP_HEAD = 7;
-constexpr int RP_DECODED = 8, RP_REPORTS = 12, RP_RING = 13, RP_RING_WORDS = 16;
-constexpr int RP_WORDS = RP_RING + RP_RING_WORDS;
-constexpr int CLASS_NONE = 0, CLASS_D = 1, CLASS_F = 2, CLASS_L = 3, CLASS_NOISE = 4;
-
-// report.py: FA_*
-constexpr int FA_ON = 0, FA_CALM = 1, FA_SEEN = 2, FA_LAST = 3, FA_AGE = 4, FA_LOSS = 5, FA_RESIDUAL = 6;
-constexpr int FA_REPORTS = 7, FA_STALE = 8, FA_TURNED_ON = 9, FA_TURNED_OFF = 10, FA_TIMEOUT = 11;
-constexpr int FA_WORDS = 12;
-constexpr int REPORT_PRESENT = 1 << 24;
 
 __global__ __launch_bounds__(THREADS) void rx_report_kernel(const int* __restrict__ jstate, const int* __restrict__ action,
                                                             int* __restrict__ rows, uint8_t* __restrict__ reports,
@@ -37,63 +22,63 @@ __global__ __launch_bounds__(THREADS) void rx_report_kernel(const int* __restric
   const Wave me = this_wave(B);
   if (!me.ok) return;
   const int b = me.b, lane = me.lane();
-  const int* js = jstate + (long)b * ST_WORDS;
-  int* row = rows + (long)b * RP_WORDS;
+  const int* js = jstate + (long)b * HILC_JITTER_ST_WORDS;
+  int* row = rows + (long)b * HILC_REPORT_RP_WORDS;
   const bool start = is_reset(action, b);
-  int r[RP_RING];
+  int r[HILC_REPORT_RP_RING];
 #pragma unroll
-  for (int k = 0; k < RP_RING; ++k) r[k] = start ? 0 : row[k];
-  int cls = CLASS_NONE;
+  for (int k = 0; k < HILC_REPORT_RP_RING; ++k) r[k] = start ? 0 : row[k];
+  int cls = HILC_REPORT_CLASS_NONE;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {                             // D, F, L, NOISE: jitter.py's and report.py's order
-    const int now = js[STAT_DECODED + c];
-    if (cls == CLASS_NONE && now != r[RP_DECODED + c]) cls = CLASS_D + c;
-    r[RP_DECODED + c] = now;
+    const int now = js[HILC_JITTER_STAT_DECODED + c];
+    if (cls == HILC_REPORT_CLASS_NONE && now != r[HILC_REPORT_RP_DECODED + c]) cls = HILC_REPORT_CLASS_D + c;
+    r[HILC_REPORT_RP_DECODED + c] = now;
   }
   bool touched = false, emit = false;
   int w = 0, word = 0;
-  if (cls != CLASS_NONE) {
-    if (cls != CLASS_NOISE) {
-      const int head = clampi(r[RP_HEAD], 0, window - 1);   // a row this kernel wrote is in range already
+  if (cls != HILC_REPORT_CLASS_NONE) {
+    if (cls != HILC_REPORT_CLASS_NOISE) {
+      const int head = clampi(r[HILC_REPORT_RP_HEAD], 0, window - 1);   // a row this kernel wrote is in range already
       const int sh = 2 * (head & 15);
       w = head >> 4;
-      uint32_t u = start ? 0u : (uint32_t)row[RP_RING + w];
-      if (r[RP_N] >= window) {                              // the oldest entry leaves the counts
+      uint32_t u = start ? 0u : (uint32_t)row[HILC_REPORT_RP_RING + w];
+      if (r[HILC_REPORT_RP_N] >= window) {                              // the oldest entry leaves the counts
         const int old = (int)((u >> sh) & 3u);
-        r[RP_F] -= old == CLASS_F;
-        r[RP_L] -= old == CLASS_L;
+        r[HILC_REPORT_RP_F] -= old == HILC_REPORT_CLASS_F;
+        r[HILC_REPORT_RP_L] -= old == HILC_REPORT_CLASS_L;
       } else {
-        ++r[RP_N];
+        ++r[HILC_REPORT_RP_N];
       }
       u = (u & ~(3u << sh)) | ((uint32_t)cls << sh);
       word = (int)u;
       touched = true;
-      r[RP_F] += cls == CLASS_F;
-      r[RP_L] += cls == CLASS_L;
-      r[RP_HEAD] = head + 1 >= window ? 0 : head + 1;
+      r[HILC_REPORT_RP_F] += cls == HILC_REPORT_CLASS_F;
+      r[HILC_REPORT_RP_L] += cls == HILC_REPORT_CLASS_L;
+      r[HILC_REPORT_RP_HEAD] = head + 1 >= window ? 0 : head + 1;
     }
-    if (++r[RP_PHASE] >= interval) {
-      r[RP_PHASE] = 0;
-      const int N = r[RP_N];
+    if (++r[HILC_REPORT_RP_PHASE] >= interval) {
+      r[HILC_REPORT_RP_PHASE] = 0;
+      const int N = r[HILC_REPORT_RP_N];
       if (N >= 1) {
-        r[RP_SEQ] = (r[RP_SEQ] + 1) & 255;
-        r[RP_LOSS] = min(255, (256 * (r[RP_F] + r[RP_L]) + N / 2) / N);
-        r[RP_RESIDUAL] = min(255, (256 * r[RP_L] + N / 2) / N);
-        ++r[RP_REPORTS];
+        r[HILC_REPORT_RP_SEQ] = (r[HILC_REPORT_RP_SEQ] + 1) & 255;
+        r[HILC_REPORT_RP_LOSS] = min(255, (256 * (r[HILC_REPORT_RP_F] + r[HILC_REPORT_RP_L]) + N / 2) / N);
+        r[HILC_REPORT_RP_RESIDUAL] = min(255, (256 * r[HILC_REPORT_RP_L] + N / 2) / N);
+        ++r[HILC_REPORT_RP_REPORTS];
         emit = true;
       }
     }
   }
   // ring words: lane k owns word k, one store per lane (a start clears them all; else only the word entered changes)
-  if (lane < RP_RING_WORDS && (start || (touched && lane == w))) row[RP_RING + lane] = (touched && lane == w) ? word : 0;
+  if (lane < HILC_REPORT_RP_RING_WORDS && (start || (touched && lane == w))) row[HILC_REPORT_RP_RING + lane] = (touched && lane == w) ? word : 0;
   if (lane == 0) {
 #pragma unroll
-    for (int k = 0; k < RP_RING; ++k) row[k] = r[k];
+    for (int k = 0; k < HILC_REPORT_RP_RING; ++k) row[k] = r[k];
     due[b] = emit ? 1 : 0;
   }
-  if (lane < 3 && (start || emit)) {
-    const int field = lane == 0 ? r[RP_SEQ] : (lane == 1 ? r[RP_LOSS] : r[RP_RESIDUAL]);
-    reports[(long)b * 3 + lane] = emit ? (uint8_t)field : (uint8_t)0;
+  if (lane < HILC_WIRE_REPORT_BYTES && (start || emit)) {
+    const int field = lane == 0 ? r[HILC_REPORT_RP_SEQ] : (lane == 1 ? r[HILC_REPORT_RP_LOSS] : r[HILC_REPORT_RP_RESIDUAL]);
+    reports[(long)b * HILC_WIRE_REPORT_BYTES + lane] = emit ? (uint8_t)field : (uint8_t)0;
   }
 }
 
@@ -105,55 +90,55 @@ __global__ __launch_bounds__(THREADS) void fec_adapt_kernel(const int* __restric
   const Wave me = this_wave(B);
   if (!me.ok) return;
   const int b = me.b, lane = me.lane();
-  int* row = rows + (long)b * FA_WORDS;
+  int* row = rows + (long)b * HILC_REPORT_FA_WORDS;
   const bool start = is_reset(action, b);
   const bool held = is_held(hold, b);
-  int r[FA_WORDS];
+  int r[HILC_REPORT_FA_WORDS];
 #pragma unroll
-  for (int k = 0; k < FA_WORDS; ++k) r[k] = start ? 0 : row[k];
-  if (start) r[FA_ON] = initial_on;
+  for (int k = 0; k < HILC_REPORT_FA_WORDS; ++k) r[k] = start ? 0 : row[k];
+  if (start) r[HILC_REPORT_FA_ON] = initial_on;
   const int word = report != nullptr ? report[b] : 0;
-  if (word & REPORT_PRESENT) {
+  if (word & HILC_REPORT_REPORT_PRESENT) {
     const int seq = (word >> 16) & 255, loss = (word >> 8) & 255, residual = word & 255;
-    const int d = (seq - r[FA_LAST]) & 255;
-    if (r[FA_SEEN] != 0 && (d < 1 || d > 127)) {
-      ++r[FA_STALE];
+    const int d = (seq - r[HILC_REPORT_FA_LAST]) & 255;
+    if (r[HILC_REPORT_FA_SEEN] != 0 && (d < 1 || d > 127)) {
+      ++r[HILC_REPORT_FA_STALE];
     } else {
-      r[FA_SEEN] = 1;
-      r[FA_LAST] = seq;
-      r[FA_AGE] = 0;
-      r[FA_LOSS] = loss;
-      r[FA_RESIDUAL] = residual;
-      ++r[FA_REPORTS];
+      r[HILC_REPORT_FA_SEEN] = 1;
+      r[HILC_REPORT_FA_LAST] = seq;
+      r[HILC_REPORT_FA_AGE] = 0;
+      r[HILC_REPORT_FA_LOSS] = loss;
+      r[HILC_REPORT_FA_RESIDUAL] = residual;
+      ++r[HILC_REPORT_FA_REPORTS];
       if (loss >= on_q8) {
-        r[FA_CALM] = 0;
-        r[FA_TURNED_ON] += r[FA_ON] == 0;
-        r[FA_ON] = 1;
+        r[HILC_REPORT_FA_CALM] = 0;
+        r[HILC_REPORT_FA_TURNED_ON] += r[HILC_REPORT_FA_ON] == 0;
+        r[HILC_REPORT_FA_ON] = 1;
       } else if (loss <= off_q8) {
-        if (++r[FA_CALM] >= calm_reports) {
-          r[FA_TURNED_OFF] += r[FA_ON] == 1;
-          r[FA_ON] = 0;
+        if (++r[HILC_REPORT_FA_CALM] >= calm_reports) {
+          r[HILC_REPORT_FA_TURNED_OFF] += r[HILC_REPORT_FA_ON] == 1;
+          r[HILC_REPORT_FA_ON] = 0;
         }
       } else {
-        r[FA_CALM] = 0;
+        r[HILC_REPORT_FA_CALM] = 0;
       }
     }
   }
   if (!held) {
-    ++r[FA_AGE];
-    if (timeout_hops > 0 && r[FA_AGE] >= timeout_hops) {
-      r[FA_ON] = initial_on;
-      r[FA_CALM] = 0;
-      r[FA_SEEN] = 0;
-      r[FA_AGE] = 0;
-      ++r[FA_TIMEOUT];
+    ++r[HILC_REPORT_FA_AGE];
+    if (timeout_hops > 0 && r[HILC_REPORT_FA_AGE] >= timeout_hops) {
+      r[HILC_REPORT_FA_ON] = initial_on;
+      r[HILC_REPORT_FA_CALM] = 0;
+      r[HILC_REPORT_FA_SEEN] = 0;
+      r[HILC_REPORT_FA_AGE] = 0;
+      ++r[HILC_REPORT_FA_TIMEOUT];
     }
   }
   if (lane == 0) {
 #pragma unroll
-    for (int k = 0; k < FA_WORDS; ++k) row[k] = r[k];
-    if (!held && r[FA_ON] == 0) prev[(long)b * prev_words] = 0;      // the valid word: the packer appends no redundant section
-    fec_on[b] = r[FA_ON];
+    for (int k = 0; k < HILC_REPORT_FA_WORDS; ++k) row[k] = r[k];
+    if (!held && r[HILC_REPORT_FA_ON] == 0) prev[(long)b * prev_words] = 0;      // the valid word: the packer appends no redundant section
+    fec_on[b] = r[HILC_REPORT_FA_ON];
   }
 }
 
@@ -162,7 +147,7 @@ __global__ __launch_bounds__(THREADS) void fec_adapt_kernel(const int* __restric
 extern "C" int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window,
                               int interval, void* stream) {
   if (!jitter_state || !rows || !reports || !due) return HILC_ERR_NULL;
-  if (B <= 0 || window < 8 || window > 16 * RP_RING_WORDS || interval < 1 || interval > 1024) return HILC_ERR_SHAPE;
+  if (B <= 0 || window < 8 || window > 16 * HILC_REPORT_RP_RING_WORDS || interval < 1 || interval > 1024) return HILC_ERR_SHAPE;
   return launch(rx_report_kernel, waves_grid(B), stream, jitter_state, action, rows, reports, due, B, window, interval);
 }
 

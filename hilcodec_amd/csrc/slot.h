@@ -18,7 +18,7 @@ namespace slot {
 constexpr int THREADS = 256;
 constexpr int LANES = 64;
 constexpr int WAVES = THREADS / LANES;
-constexpr int MAX_N = 32;           // stages of one packet (primary + redundant): hilc_rvq_decode_packed stages that many per frame in LDS
+constexpr int MAX_N = HILC_WIRE_MAX_STAGES;   // stages of one packet (primary + redundant): hilc_rvq_decode_packed stages that many per frame in LDS
 
 // ---- one wave per slot (WAVES slots per workgroup); a ragged last workgroup's spare waves are out of range and leave at once
 struct Wave {

@@ -26,10 +26,10 @@ from . import dtx as dtx_def
 from . import engine, ops, wire
 from . import report as report_def
 from . import vbr as vbr_def
-from .jitter import AD_WORDS, JitterConfig
+from .jitter import AD_WORDS, ST_WORDS, JitterConfig
 from .mixer import MixConfig
-from .resample import BASE_RATE, design, device_taps, hop_samples
-from .sessions import SessionQueue, stage_layout, stage_starts
+from .resample import BASE_RATE, HOP, design, device_taps, hop_samples
+from .sessions import HOLD_SID, HOLD_SILENT, SessionQueue, stage_layout, stage_starts
 
 
 def state_layout(model, batch: int, side: str = "both", history: int = 0) -> ops.StateLayout:
@@ -58,17 +58,17 @@ def _int_arg(name: str, value, lo: int, hi: Optional[int] = None) -> int:
 
 def _whole_frames(who: str, hop: int) -> int:
     """the frames of a hop of `hop` samples at 24 kHz, for an option `who` that works on whole 320-sample frames"""
-    if hop % 320:
-        raise ValueError(f"{who}: hop must be a multiple of 320, got {hop}")
-    return hop // 320
+    if hop % HOP:
+        raise ValueError(f"{who}: hop must be a multiple of {HOP}, got {hop}")
+    return hop // HOP
 
 
 def _fec_stages(fec_stages, n: int) -> int:
     """the `fec_stages` argument of the sender and the receiver checked: 0 (no FEC) or an int m in [1, n] with n + m <= 32 (the
     most stages one packet holds, as hilc_rvq_decode_packed)"""
     m = _int_arg("fec_stages", fec_stages, 0, int(n))
-    if int(n) + m > 32:
-        raise ValueError(f"fec_stages = {m}: a packet holds at most 32 stages, n + m = {int(n) + m}")
+    if int(n) + m > wire.MAX_STAGES:
+        raise ValueError(f"fec_stages = {m}: a packet holds at most {wire.MAX_STAGES} stages, n + m = {int(n) + m}")
     return m
 
 
@@ -680,7 +680,7 @@ class GraphedEncodeHop(GraphedHop):
         self.header = bool(header)
         if self.header:
             _whole_frames("GraphedEncodeHop(header=True)", hop)
-        self.frames = hop // 320
+        self.frames = hop // HOP
         if dtx is not None and not isinstance(dtx, dtx_def.DtxConfig):
             raise ValueError(f"dtx must be a dtx.DtxConfig or None, got {dtx!r}")
         self.dtx = dtx
@@ -1029,8 +1029,8 @@ class GraphedDecodeHop(_Hop):
         self._scratch = []
         if self.conceal:
             # per slot: run k, has-codes, stored n, the stored frame's n codes (updated in place by hilc_conceal_prepare once per hop)
-            self._conceal = torch.zeros(B, self.n + 3, dtype=torch.int32, device=device)
-            gains, weights = wire.conceal_tables(self.fade_hops, 320 * self.frames)
+            self._conceal = torch.zeros(B, self.n + wire.CONCEAL_CODES, dtype=torch.int32, device=device)
+            gains, weights = wire.conceal_tables(self.fade_hops, HOP * self.frames)
             self._gains, self._weights = gains.to(device), weights.to(device)
             self._scratch += [self._conceal]
         if self.cng_order is not None:
@@ -1053,7 +1053,7 @@ class GraphedDecodeHop(_Hop):
         if mix is not None:
             # per slot: the peak-hold score (updated in place by hilc_mix_levels once per hop); per parity: the mixes; the speaker
             # marks; the room row (device, captured by address) and its pinned host mirror
-            L = hop_samples(self.frames, self.output_rate) if self.rs is not None else 320 * self.frames
+            L = hop_samples(self.frames, self.output_rate) if self.rs is not None else HOP * self.frames
             self._score = torch.zeros(B, dtype=torch.float64, device=device)
             self._mixed = torch.zeros(2, B, 1, L, device=device)
             self._speakers = torch.zeros(B, dtype=torch.int32, device=device)
@@ -1083,7 +1083,7 @@ class GraphedDecodeHop(_Hop):
         run; k >= 1: k hops lost in a row, at most `fade_hops`).  Read-only: written by the graph."""
         if not self.conceal:
             raise RuntimeError("GraphedDecodeHop.concealed: construct with conceal=True")
-        return self._conceal[:, 0]
+        return self._conceal[:, wire.CONCEAL_RUN]
 
     @property
     def cng_state(self) -> Tensor:
@@ -1243,9 +1243,9 @@ class GraphedDecodeHop(_Hop):
         h["n_slot"].copy_(n)
         _mark(h["hold"], held)
         if sids:
-            h["hold"][torch.tensor(sids, dtype=torch.long)] = 2
+            h["hold"][torch.tensor(sids, dtype=torch.long)] = HOLD_SID
         if quiet:
-            h["hold"][torch.tensor(quiet, dtype=torch.long)] = 3
+            h["hold"][torch.tensor(quiet, dtype=torch.long)] = HOLD_SILENT
         if self.conceal:
             _mark(h["lost"], gone)
         if self.fec_stages:
@@ -1282,7 +1282,7 @@ class GraphedDecodeHop(_Hop):
         self.fec = rows[2] if self.fec_stages else None
         self.packets = torch.zeros(B, self.stride, dtype=torch.uint8, device=dev)
         # per slot: the state row (jitter.ST_*, updated in place once per hop), the ring's meta words and bodies
-        self._jstate = torch.zeros(B, 14, dtype=torch.int32, device=dev)
+        self._jstate = torch.zeros(B, ST_WORDS, dtype=torch.int32, device=dev)
         self._jmeta = torch.zeros(B, cfg.capacity, dtype=torch.int32, device=dev)
         self._jring = torch.zeros(B, cfg.capacity, (self.stride + 3) // 4, dtype=torch.int32, device=dev)
         if cfg.adapt is not None:

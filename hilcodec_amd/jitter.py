@@ -62,6 +62,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import wire
+from .sessions import HOLD_HELD, HOLD_SID, HOLD_SILENT
 
 ST_ANCHORED, ST_WAIT, ST_NEXT, ST_IN_DTX, ST_MASK = 0, 1, 2, 3, 4
 STAT_ACCEPTED, STAT_DUPLICATE, STAT_LATE, STAT_EARLY, STAT_MALFORMED = 5, 6, 7, 8, 9
@@ -246,11 +247,11 @@ class JitterModel:
         if rows["hold"][b] != 0:
             return
         if not st[ST_ANCHORED]:
-            rows["hold"][b] = 1
+            rows["hold"][b] = HOLD_HELD
             return
         if st[ST_WAIT] > 0:
             st[ST_WAIT] -= 1
-            rows["hold"][b] = 1
+            rows["hold"][b] = HOLD_HELD
             return
         if self.cfg.adapt is not None and self._shift(b, rows):
             return
@@ -289,11 +290,11 @@ class JitterModel:
         if step > 0:
             ad[AD_GROWN] += 1
             if st[ST_IN_DTX]:
-                rows["hold"][b] = 3
+                rows["hold"][b] = HOLD_SILENT
             elif self.conceal:
                 rows["lost"][b] = 1
             else:
-                rows["hold"][b] = 1
+                rows["hold"][b] = HOLD_HELD
             return True
         if step < 0:
             if present:
@@ -323,7 +324,7 @@ class JitterModel:
             mt = int(self.meta[b, i]) & 0xFFFFFFFF
             rows["packets"][b] = self.body[b, i]
             if mt & META_SID:
-                rows["hold"][b] = 2
+                rows["hold"][b] = HOLD_SID
                 st[ST_IN_DTX] = 1
                 st[STAT_NOISE] += 1
             else:
@@ -333,7 +334,7 @@ class JitterModel:
             st[ST_MASK] = _i32(mask & ~(1 << i))
             self.meta[b, i] = 0
         elif st[ST_IN_DTX]:
-            rows["hold"][b] = 3
+            rows["hold"][b] = HOLD_SILENT
             st[STAT_NOISE] += 1
         else:
             mt = int(self.meta[b, j]) & 0xFFFFFFFF
@@ -346,7 +347,7 @@ class JitterModel:
                 if self.conceal:
                     rows["lost"][b] = 1
                 else:
-                    rows["hold"][b] = 1
+                    rows["hold"][b] = HOLD_HELD
                 st[STAT_LOST] += 1
         st[ST_NEXT] = (h + 1) & 0xFFFF
 

@@ -24,6 +24,11 @@ import torch
 from torch import Tensor
 
 from ._lib import DownParams, PostParams, ResblockParams, Spec0Params, UpParams, check, lib
+from .dtx import LEVELS, state_words
+from .jitter import AD_WORDS, ST_WORDS
+from .report import FA_WORDS, RP_WORDS
+from .resample import HOP
+from .wire import CONCEAL_CODES, REPORT_BYTES, TRANSPORT_HEADER, packet_bytes
 
 _LIB = torch.library.Library("hilcodec", "DEF")
 
@@ -820,10 +825,6 @@ _register("state_slots_hold", "(Tensor src, Tensor(a!) dst, Tensor slice_off, Te
 # ======================================================================================================
 # per-stream 10-bit packets (graph_step.GraphedEncodeHop / GraphedDecodeHop; format: wire.packet_bytes)
 # ======================================================================================================
-def _packet_stride(n: int, T: int) -> int:
-    return (10 * n * T + 7) // 8                      # wire.packet_bytes
-
-
 def _rows(op: str, B: int, **rows) -> None:
     """the optional per-slot rows of a side kernel: each one given has B entries"""
     for name, row in rows.items():
@@ -833,7 +834,7 @@ def _rows(op: str, B: int, **rows) -> None:
 
 def _pack_codes_10bit(indices, n_clip):
     n, B, T = indices.shape
-    packets = _new(indices, B, _packet_stride(n, T), dtype=torch.uint8)
+    packets = _new(indices, B, packet_bytes(n, T), dtype=torch.uint8)
     nbytes = _new(indices, B, dtype=torch.int32)
     check(lib.hilc_pack_codes_10bit(_ptr(indices, torch.int64), _ptr(n_clip, torch.int32), _ptr(packets, torch.uint8),
                                     _ptr(nbytes, torch.int32), B, T, n, _stream()), "hilc_pack_codes_10bit")
@@ -842,7 +843,7 @@ def _pack_codes_10bit(indices, n_clip):
 
 def _pack_codes_10bit_fake(indices, n_clip):
     n, B, T = indices.shape
-    return indices.new_empty(B, _packet_stride(n, T), dtype=torch.uint8), indices.new_empty(B, dtype=torch.int32)
+    return indices.new_empty(B, packet_bytes(n, T), dtype=torch.uint8), indices.new_empty(B, dtype=torch.int32)
 
 
 _register("pack_codes_10bit", "(Tensor indices, Tensor? n_clip) -> (Tensor, Tensor)", _pack_codes_10bit, _pack_codes_10bit_fake)
@@ -851,8 +852,8 @@ _register("pack_codes_10bit", "(Tensor indices, Tensor? n_clip) -> (Tensor, Tens
 def _rvq_decode_packed(packets, n_clip, codebooks, n, frames):
     B = packets.shape[0]
     Nq, K, Cc = codebooks.shape
-    if packets.dim() != 2 or packets.shape[1] != _packet_stride(n, frames):
-        raise RuntimeError(f"rvq_decode_packed: packets must be [B, {_packet_stride(n, frames)}] for n = {n}, {frames} frames")
+    if packets.dim() != 2 or packets.shape[1] != packet_bytes(n, frames):
+        raise RuntimeError(f"rvq_decode_packed: packets must be [B, {packet_bytes(n, frames)}] for n = {n}, {frames} frames")
     q = _new(codebooks, B, frames, Cc)
     check(lib.hilc_rvq_decode_packed(_ptr(packets, torch.uint8), _ptr(n_clip, torch.int32), _ptr(codebooks), _ptr(q), B, Cc, frames, K,
                                      Nq, n, _stream()), "hilc_rvq_decode_packed")
@@ -869,10 +870,10 @@ _register("rvq_decode_packed", "(Tensor packets, Tensor? n_clip, Tensor codebook
 def _conceal_prepare(state, action, hold, lost, n_slot, packets, frames, fade_hops):
     B = action.numel()
     if state.dim() != 2 or state.shape[0] != B or hold.numel() != B or lost.numel() != B or n_slot.numel() != B:
-        raise RuntimeError(f"conceal_prepare: state must be [{B}, n_max + 3] and hold, lost, n_slot [{B}]")
-    n_max = state.shape[1] - 3
-    if packets.dim() != 2 or packets.shape[0] != B or packets.shape[1] != _packet_stride(max(n_max, 0), frames):
-        raise RuntimeError(f"conceal_prepare: packets must be [{B}, {_packet_stride(max(n_max, 0), frames)}]")
+        raise RuntimeError(f"conceal_prepare: state must be [{B}, n_max + {CONCEAL_CODES}] and hold, lost, n_slot [{B}]")
+    n_max = state.shape[1] - CONCEAL_CODES
+    if packets.dim() != 2 or packets.shape[0] != B or packets.shape[1] != packet_bytes(max(n_max, 0), frames):
+        raise RuntimeError(f"conceal_prepare: packets must be [{B}, {packet_bytes(max(n_max, 0), frames)}]")
     ramp = _new(state, B, dtype=torch.int32)
     check(lib.hilc_conceal_prepare(_ptr(state, torch.int32), _ptr(action, torch.int32), _ptr(hold, torch.int32), _ptr(lost, torch.int32),
                                    _ptr(n_slot, torch.int32), _ptr(packets, torch.uint8), _ptr(ramp, torch.int32), B, frames, n_max,
@@ -930,7 +931,7 @@ def _pack_codes_10bit_fec(indices, n_clip, prev_in, prev_out, action, hold, m):
     if prev_in.shape != (B, W) or prev_out.shape != (B, W) or prev_in.dtype != torch.int32 or prev_out.dtype != torch.int32:
         raise RuntimeError(f"pack_codes_10bit_fec: prev_in and prev_out must be int32 [{B}, {W}]")
     _rows("pack_codes_10bit_fec", B, n_clip=n_clip, action=action, hold=hold)
-    packets = _new(indices, B, _packet_stride(n + m, T), dtype=torch.uint8)
+    packets = _new(indices, B, packet_bytes(n + m, T), dtype=torch.uint8)
     nbytes = _new(indices, B, dtype=torch.int32)
     check(lib.hilc_pack_codes_10bit_fec(_ptr(indices, torch.int64), _ptr(n_clip, torch.int32), _ptr(prev_in, torch.int32),
                                         _ptr(prev_out, torch.int32), _ptr(action, torch.int32), _ptr(hold, torch.int32),
@@ -941,7 +942,7 @@ def _pack_codes_10bit_fec(indices, n_clip, prev_in, prev_out, action, hold, m):
 
 def _pack_codes_10bit_fec_fake(indices, n_clip, prev_in, prev_out, action, hold, m):
     n, B, T = indices.shape
-    return indices.new_empty(B, _packet_stride(n + m, T), dtype=torch.uint8), indices.new_empty(B, dtype=torch.int32)
+    return indices.new_empty(B, packet_bytes(n + m, T), dtype=torch.uint8), indices.new_empty(B, dtype=torch.int32)
 
 
 _register("pack_codes_10bit_fec", "(Tensor indices, Tensor? n_clip, Tensor prev_in, Tensor(a!) prev_out, Tensor? action, "
@@ -950,16 +951,16 @@ _register("pack_codes_10bit_fec", "(Tensor indices, Tensor? n_clip, Tensor prev_
 
 def _fec_select(packets, fec, n_slot, n, m, frames):
     B = packets.shape[0]
-    if packets.dim() != 2 or packets.shape[1] != _packet_stride(n + m, frames) or fec.numel() != B or n_slot.numel() != B:
-        raise RuntimeError(f"fec_select: packets must be [B, {_packet_stride(n + m, frames)}] and fec, n_slot [B]")
-    out = _new(packets, B, _packet_stride(n, frames), dtype=torch.uint8)
+    if packets.dim() != 2 or packets.shape[1] != packet_bytes(n + m, frames) or fec.numel() != B or n_slot.numel() != B:
+        raise RuntimeError(f"fec_select: packets must be [B, {packet_bytes(n + m, frames)}] and fec, n_slot [B]")
+    out = _new(packets, B, packet_bytes(n, frames), dtype=torch.uint8)
     check(lib.hilc_fec_select(_ptr(packets, torch.uint8), _ptr(fec, torch.int32), _ptr(n_slot, torch.int32), _ptr(out, torch.uint8),
                               B, frames, n, m, _stream()), "hilc_fec_select")
     return out
 
 
 _register("fec_select", "(Tensor packets, Tensor fec, Tensor(a!) n_slot, int n, int m, int frames) -> Tensor", _fec_select,
-          lambda packets, fec, n_slot, n, m, frames: packets.new_empty(packets.shape[0], _packet_stride(n, frames)))
+          lambda packets, fec, n_slot, n, m, frames: packets.new_empty(packets.shape[0], packet_bytes(n, frames)))
 
 # ======================================================================================================
 # discontinuous transmission and comfort noise of the sender / receiver (graph_step.GraphedEncodeHop(dtx=),
@@ -967,13 +968,13 @@ _register("fec_select", "(Tensor packets, Tensor fec, Tensor(a!) n_slot, int n, 
 # ======================================================================================================
 def _dtx_encode(x, action, hold, run, packets, nbytes, indices, prev, level_thr, thr_vad, order, hangover, sid_interval):
     B = run.numel()
-    if x.dim() != 3 or x.shape[0] != B or x.shape[1] != 1 or x.shape[2] % 320 or x.shape[2] == 0:
-        raise RuntimeError(f"dtx_encode: x must be [{B}, 1, 320 T]")
-    T = x.shape[2] // 320
+    if x.dim() != 3 or x.shape[0] != B or x.shape[1] != 1 or x.shape[2] % HOP or x.shape[2] == 0:
+        raise RuntimeError(f"dtx_encode: x must be [{B}, 1, {HOP} T]")
+    T = x.shape[2] // HOP
     if indices.dim() != 3 or indices.shape[1] != B or indices.shape[2] != T:
         raise RuntimeError(f"dtx_encode: indices must be [n, {B}, {T}]")
-    if packets.dim() != 2 or packets.shape[0] != B or nbytes.numel() != B or level_thr.numel() != 127:
-        raise RuntimeError(f"dtx_encode: packets must be [{B}, stride], nbytes [{B}], level_thr [127]")
+    if packets.dim() != 2 or packets.shape[0] != B or nbytes.numel() != B or level_thr.numel() != LEVELS - 1:
+        raise RuntimeError(f"dtx_encode: packets must be [{B}, stride], nbytes [{B}], level_thr [{LEVELS - 1}]")
     _rows("dtx_encode", B, action=action, hold=hold)
     if prev is not None and (prev.dim() != 2 or prev.shape[0] != B):
         raise RuntimeError(f"dtx_encode: prev must be [{B}, words]")
@@ -994,13 +995,13 @@ _register("dtx_encode", "(Tensor x, Tensor? action, Tensor? hold, Tensor(a!) run
 
 def _cng_synth(packets, action, hold, state, wav, restore, gains, order):
     B = hold.numel()
-    if wav.dim() != 3 or wav.shape[0] != B or wav.shape[1] != 1 or wav.shape[2] % 320 or wav.shape[2] == 0 or not wav.is_contiguous():
-        raise RuntimeError(f"cng_synth: wav must be a contiguous [{B}, 1, 320 T]")
-    if packets.dim() != 2 or packets.shape[0] != B or state.shape != (B, 3 + 2 * order) or gains.numel() != 128:
-        raise RuntimeError(f"cng_synth: packets must be [{B}, stride], state [{B}, {3 + 2 * order}], gains [128]")
+    if wav.dim() != 3 or wav.shape[0] != B or wav.shape[1] != 1 or wav.shape[2] % HOP or wav.shape[2] == 0 or not wav.is_contiguous():
+        raise RuntimeError(f"cng_synth: wav must be a contiguous [{B}, 1, {HOP} T]")
+    if packets.dim() != 2 or packets.shape[0] != B or state.shape != (B, state_words(order)) or gains.numel() != LEVELS:
+        raise RuntimeError(f"cng_synth: packets must be [{B}, stride], state [{B}, {state_words(order)}], gains [{LEVELS}]")
     _rows("cng_synth", B, action=action, restore=restore)
     check(lib.hilc_cng_synth(_ptr(packets, torch.uint8), _ptr(action, torch.int32), _ptr(hold, torch.int32), _ptr(state, torch.int32),
-                             _ptr(wav), _ptr(restore, torch.int32), _ptr(gains), B, wav.shape[2] // 320, order, packets.shape[1],
+                             _ptr(wav), _ptr(restore, torch.int32), _ptr(gains), B, wav.shape[2] // HOP, order, packets.shape[1],
                              _stream()), "hilc_cng_synth")
 
 
@@ -1013,12 +1014,12 @@ _register("cng_synth", "(Tensor packets, Tensor? action, Tensor(a!) hold, Tensor
 # ======================================================================================================
 def _packet_header(packets, nbytes, n_clip, kind, action, hold, ctr_in, ctr_out, n, m, frames):
     B = packets.shape[0]
-    if packets.dim() != 2 or packets.shape[1] != _packet_stride(n + m, frames) or nbytes.numel() != B:
-        raise RuntimeError(f"packet_header: packets must be [B, {_packet_stride(n + m, frames)}] and nbytes [B]")
+    if packets.dim() != 2 or packets.shape[1] != packet_bytes(n + m, frames) or nbytes.numel() != B:
+        raise RuntimeError(f"packet_header: packets must be [B, {packet_bytes(n + m, frames)}] and nbytes [B]")
     if ctr_in.numel() != B or ctr_out.numel() != B:
         raise RuntimeError(f"packet_header: the counter rows need {B} entries")
     _rows("packet_header", B, n_clip=n_clip, kind=kind, action=action, hold=hold)
-    out = _new(packets, B, 3 + packets.shape[1], dtype=torch.uint8)
+    out = _new(packets, B, TRANSPORT_HEADER + packets.shape[1], dtype=torch.uint8)
     out_nbytes = _new(packets, B, dtype=torch.int32)
     check(lib.hilc_packet_header(_ptr(packets, torch.uint8), _ptr(nbytes, torch.int32), _ptr(n_clip, torch.int32), _ptr(kind, torch.int32),
                                  _ptr(action, torch.int32), _ptr(hold, torch.int32), _ptr(ctr_in, torch.int32), _ptr(ctr_out, torch.int32),
@@ -1029,20 +1030,20 @@ def _packet_header(packets, nbytes, n_clip, kind, action, hold, ctr_in, ctr_out,
 _register("packet_header", "(Tensor packets, Tensor nbytes, Tensor? n_clip, Tensor? kind, Tensor? action, Tensor? hold, Tensor ctr_in, "
           "Tensor(a!) ctr_out, int n, int m, int frames) -> (Tensor, Tensor)", _packet_header,
           lambda packets, nbytes, n_clip, kind, action, hold, ctr_in, ctr_out, n, m, frames:
-          (packets.new_empty(packets.shape[0], 3 + packets.shape[1]), packets.new_empty(packets.shape[0], dtype=torch.int32)))
+          (packets.new_empty(packets.shape[0], TRANSPORT_HEADER + packets.shape[1]), packets.new_empty(packets.shape[0], dtype=torch.int32)))
 
 
 def _jitter_args(op, arrivals, offsets, action, hold, n_slot, lost, fec, packets, state, meta, ring, n, m, frames, order, depth, adapt=None):
     """the shape checks of a jitter step and the arguments both entry points begin with"""
     B = hold.numel()
-    stride = _packet_stride(n + m, frames)
-    aw = (3 + stride + 3) // 4
+    stride = packet_bytes(n + m, frames)
+    aw = (TRANSPORT_HEADER + stride + 3) // 4
     if arrivals.dim() != 2 or arrivals.shape[1] != 1 + aw or offsets.numel() != B + 1:
         raise RuntimeError(f"{op}: arrivals must be [A, {1 + aw}] and offsets [{B + 1}]")
-    if (packets.shape != (B, stride) or state.shape != (B, 14) or (adapt is not None and adapt.shape != (B, 12)) or meta.dim() != 2
-            or meta.shape[0] != B):
-        raise RuntimeError(f"{op}: packets must be [{B}, {stride}], state [{B}, 14], " + ("" if adapt is None else f"adapt [{B}, 12], ")
-                           + f"meta [{B}, C]")
+    if (packets.shape != (B, stride) or state.shape != (B, ST_WORDS) or (adapt is not None and adapt.shape != (B, AD_WORDS))
+            or meta.dim() != 2 or meta.shape[0] != B):
+        raise RuntimeError(f"{op}: packets must be [{B}, {stride}], state [{B}, {ST_WORDS}], "
+                           + ("" if adapt is None else f"adapt [{B}, {AD_WORDS}], ") + f"meta [{B}, C]")
     C = meta.shape[1]
     if ring.shape != (B, C, (stride + 3) // 4):
         raise RuntimeError(f"{op}: ring must be [{B}, {C}, {(stride + 3) // 4}]")
@@ -1142,11 +1143,9 @@ _register("vbr_select", "(Tensor z, Tensor(a!) indices, Tensor codebooks, Tensor
 # hilcodec_amd/report.py; semantics: include/hilcodec_amd.h)
 # ======================================================================================================
 def _rx_report(jitter_state, action, rows, reports, due, window, interval):
-    from .jitter import ST_WORDS
-    from .report import RP_WORDS
     B = due.numel()
-    if jitter_state.shape != (B, ST_WORDS) or rows.shape != (B, RP_WORDS) or reports.shape != (B, 3):
-        raise RuntimeError(f"rx_report: jitter_state must be [{B}, {ST_WORDS}], rows [{B}, {RP_WORDS}] and reports [{B}, 3]")
+    if jitter_state.shape != (B, ST_WORDS) or rows.shape != (B, RP_WORDS) or reports.shape != (B, REPORT_BYTES):
+        raise RuntimeError(f"rx_report: jitter_state must be [{B}, {ST_WORDS}], rows [{B}, {RP_WORDS}] and reports [{B}, {REPORT_BYTES}]")
     _rows("rx_report", B, action=action)
     check(lib.hilc_rx_report(_ptr(jitter_state, torch.int32), _ptr(action, torch.int32), _ptr(rows, torch.int32),
                              _ptr(reports, torch.uint8), _ptr(due, torch.int32), B, window, interval, _stream()), "hilc_rx_report")
@@ -1157,7 +1156,6 @@ _register("rx_report", "(Tensor jitter_state, Tensor? action, Tensor(a!) rows, T
 
 
 def _fec_adapt(report, action, hold, rows, prev, fec_on, m, frames, on_q8, off_q8, calm_reports, timeout_hops, initial_on):
-    from .report import FA_WORDS
     B = fec_on.numel()
     if rows.shape != (B, FA_WORDS) or prev.shape != (B, 1 + m * frames):
         raise RuntimeError(f"fec_adapt: rows must be [{B}, {FA_WORDS}] and prev [{B}, {1 + m * frames}]")

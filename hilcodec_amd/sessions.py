@@ -7,6 +7,11 @@ from typing import Dict, List, Sequence, Tuple
 
 from torch import Tensor
 
+# action row of a hop: ACTION_KEEP, ACTION_ZERO (a fresh start), r >= ACTION_LOAD (load record r - ACTION_LOAD)
+ACTION_KEEP, ACTION_ZERO, ACTION_LOAD = 0, -1, 1
+# hold row of a hop: the slot advances, is held, or (receiver) makes comfort noise from the SID that arrived / while its stream is in DTX
+HOLD_ADVANCE, HOLD_HELD, HOLD_SID, HOLD_SILENT = 0, 1, 2, 3
+
 
 def stage_layout(batch: int, rows: Sequence[str], payload_words: int = 0, loads: int = 0, record_len: int = 0):
     """Word offsets of a control stage, "int32 rows per slot | payload | staged records" in one buffer of 4-byte words:
@@ -20,17 +25,18 @@ def stage_layout(batch: int, rows: Sequence[str], payload_words: int = 0, loads:
 
 
 def stage_starts(starts: Dict[int, object], action: Tensor, host_records: Tensor) -> Tuple[int, List[Tensor]]:
-    """A hop's queued starts (SessionQueue.starts) -> the action row (which the caller has zeroed: 0 keeps a slot) and the record
-    region: a fresh start writes -1; the record at index r writes r + 1, the records that live on the host first — they are copied
-    into rows [0, n_host) of `host_records`, so that they travel with the stage's pinned copy — then those on the device, which
-    the caller copies into rows n_host, n_host + 1, ... of the device region.  Returns (n_host, the device records in order)."""
+    """A hop's queued starts (SessionQueue.starts) -> the action row (which the caller has zeroed: ACTION_KEEP) and the record
+    region: a fresh start writes ACTION_ZERO; the record at index r writes r + ACTION_LOAD, the records that live on the host first —
+    they are copied into rows [0, n_host) of `host_records`, so that they travel with the stage's pinned copy — then those on the
+    device, which the caller copies into rows n_host, n_host + 1, ... of the device region.  Returns (n_host, the device records in
+    order)."""
     host = [(s, r) for s, r in starts.items() if r is not None and not r.is_cuda]
     dev = [(s, r) for s, r in starts.items() if r is not None and r.is_cuda]
     for slot, rec in starts.items():
         if rec is None:
-            action[slot] = -1
+            action[slot] = ACTION_ZERO
     for r, (slot, rec) in enumerate(host + dev):
-        action[slot] = r + 1
+        action[slot] = r + ACTION_LOAD
         if r < len(host):
             host_records[r].copy_(rec)
     return len(host), [rec for _slot, rec in dev]

@@ -36,8 +36,9 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
+from .wire import MAX_STAGES
+
 LANES = 64
-MAX_STAGES = 32
 MAX_BURST_BITS = 1 << 30                          # credit + rate_bits fits an int32
 
 

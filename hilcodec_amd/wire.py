@@ -55,6 +55,9 @@ def unpack_indices_10bit(blob: bytes) -> Tensor:
 # One stream's packet for one hop of T frames: its first n stages x T codes, stage-major, 10 bits each, MSB first, the last byte
 # zero-padded — exactly the body of pack_indices_10bit(indices[:n, b:b+1, :]) without its header.  A batch of packets is a
 # uint8 [B, packet_bytes(n_max, T)] tensor (row b zero past packet_bytes(n_b, T)) with an int32 [B] byte count.
+MAX_STAGES = 32                                   # stages of one packet, primary + redundant
+
+
 def packet_bytes(n: int, T: int) -> int:
     return (10 * int(n) * int(T) + 7) // 8
 
@@ -84,6 +87,10 @@ def unpack_stream_packet(blob: bytes, n: int, T: int) -> Tensor:
 
 # Loss concealment of the receiver (graph_step.GraphedDecodeHop(conceal=True)): a lost hop is decoded from the codes of the last
 # frame received, repeated over the hop, and faded.  These are the definitions the receiver's kernels follow.
+# Concealment row of a slot (int32, n_max + CONCEAL_CODES words): hops lost in a row, has-codes, stored n, then the last frame's codes
+CONCEAL_RUN, CONCEAL_HAS, CONCEAL_N, CONCEAL_CODES = 0, 1, 2, 3
+
+
 def conceal_packet(packet: bytes, n: int, T: int) -> bytes:
     """the substitute packet for a stream whose last received packet is `packet` (`n` stages x `T` frames): that packet's last
     frame's n codes repeated over T frames, in the packet format"""
@@ -151,7 +158,7 @@ def fec_present(nbytes: int, n: int, m: int, T: int) -> bool:
 # 4..0 n (codes: 1..31; SID: 0).  The body is the packet_bytes(n, T) codes, the fec_packet_bytes(n, m, T) codes with bit 6, or a SID
 # of dtx.sid_bytes(K) bytes.  Headed packets are not re-framed: the receiver's frames are the sender's T.
 TRANSPORT_HEADER = 3
-_SID_BIT, _FEC_BIT, _RSV_BIT = 0x80, 0x40, 0x20
+SID_BIT, FEC_BIT, RSV_BIT, N_MASK = 0x80, 0x40, 0x20, 0x1F
 
 
 def transport_bytes(n: int, m: int, T: int) -> int:
@@ -167,7 +174,7 @@ def pack_transport(hop: int, body: bytes, n: int, sid: bool = False, fec: bool =
         raise ValueError("pack_transport: a SID has n = 0 and no redundant section")
     if not sid and not 1 <= n <= 31:
         raise ValueError(f"pack_transport: n = {n} outside [1, 31]")
-    flags = (_SID_BIT if sid else 0) | (_FEC_BIT if fec else 0) | n
+    flags = (SID_BIT if sid else 0) | (FEC_BIT if fec else 0) | n
     h = int(hop) & 0xFFFF
     return bytes([h >> 8, h & 0xFF, flags]) + bytes(body)
 
@@ -183,8 +190,8 @@ def parse_transport(packet, nbytes: int, T: int, n_max: int, m: int, K) -> Tuple
     if nbytes < TRANSPORT_HEADER or len(data) < nbytes:
         raise ValueError(f"a {nbytes}-byte packet is shorter than its {TRANSPORT_HEADER}-byte header")
     hop, flags = (data[0] << 8) | data[1], data[2]
-    sid, fec, n = bool(flags & _SID_BIT), bool(flags & _FEC_BIT), flags & 0x1F
-    if flags & _RSV_BIT:
+    sid, fec, n = bool(flags & SID_BIT), bool(flags & FEC_BIT), flags & N_MASK
+    if flags & RSV_BIT:
         raise ValueError("header bit 5 is set")
     if fec and (int(m) < 1 or n < int(m)):
         raise ValueError(f"a redundant section with n = {n}, m = {m}")

@@ -399,6 +399,137 @@ int hilc_rvq_ema_stats(const float* z, const float* codebooks, const int64_t* in
 int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const float* bucket, double decay, int K,
                         int C, int n, void* stream);
 
+/* ---- row layouts, codes and limits of the per-slot entry points below (ABI 16) -----------------------------------------------------
+ * The one definition of every small int32 row, code and limit that the kernels (hilcodec_amd/csrc), the bindings and the bit-exact
+ * host models share.  HILC_<MODULE>_<NAME> is hilcodec_amd.<module>.<NAME> in Python, value for value (tests/test_api_cpu.py proves
+ * the mirror in both directions).  A "row" is one slot's int32 words; a [B][WORDS] tensor holds the rows of B slots back to back. */
+
+/* control rows of a hop, int32 [B].  Action row (hilc_state_slots_apply and every kernel that takes `action`): KEEP, ZERO = start a
+ * fresh stream, r >= LOAD = load record r - LOAD.  Hold row (hilc_state_slots_hold and every kernel that takes `hold`): ADVANCE, HELD,
+ * and on the receiver SID = a SID arrived, SILENT = the stream is in DTX (both: comfort noise; every other kernel treats them as held). */
+#define HILC_SESSIONS_ACTION_KEEP 0
+#define HILC_SESSIONS_ACTION_ZERO (-1)
+#define HILC_SESSIONS_ACTION_LOAD 1
+#define HILC_SESSIONS_HOLD_ADVANCE 0
+#define HILC_SESSIONS_HOLD_HELD 1
+#define HILC_SESSIONS_HOLD_SID 2
+#define HILC_SESSIONS_HOLD_SILENT 3
+
+/* wire format (hilcodec_amd/wire.py).  A packet holds at most MAX_STAGES stages, primary + redundant.  Transport header: TRANSPORT_HEADER
+ * bytes, bytes 0-1 the hop index mod 2^16 big-endian, byte 2 = SID_BIT | FEC_BIT | n in N_MASK, RSV_BIT zero.  A receiver report is
+ * REPORT_BYTES bytes (seq, loss_q8, residual_q8).  Concealment row of a receiver slot, n_max + CONCEAL_CODES words: RUN = hops lost in a
+ * row (0..F), HAS = has-codes (0/1), N = stored n, CODES + s for s < n_max = the code of stage s of the LAST frame of the last packet
+ * received (0 for s >= stored n). */
+#define HILC_WIRE_MAX_STAGES 32
+#define HILC_WIRE_TRANSPORT_HEADER 3
+#define HILC_WIRE_SID_BIT 0x80
+#define HILC_WIRE_FEC_BIT 0x40
+#define HILC_WIRE_RSV_BIT 0x20
+#define HILC_WIRE_N_MASK 0x1F
+#define HILC_WIRE_REPORT_BYTES 3
+#define HILC_WIRE_CONCEAL_RUN 0
+#define HILC_WIRE_CONCEAL_HAS 1
+#define HILC_WIRE_CONCEAL_N 2
+#define HILC_WIRE_CONCEAL_CODES 3
+
+/* samples per codec frame at 24 kHz (hilcodec_amd/resample.py): a hop of T frames is HOP T samples */
+#define HILC_RESAMPLE_HOP 320
+
+/* DTX and comfort noise (hilcodec_amd/dtx.py).  Kind of a sender's hop: HELD, SPEECH, SID, SILENT.  Order K <= MAX_ORDER, level L in
+ * 0..LEVELS - 1, GOLDEN the multiplier of a slot's noise seed.  CN state row of a receiver slot, ST_Q + 2 K words: ST_HAS = has-SID,
+ * ST_LEVEL = L, ST_COUNT = c (noise hops since the start, mod 2^32), ST_Q + i for i < K = q_{i+1}, then K fp32 words of filter memory
+ * y[-K..-1]. */
+#define HILC_DTX_HELD 0
+#define HILC_DTX_SPEECH 1
+#define HILC_DTX_SID 2
+#define HILC_DTX_SILENT 3
+#define HILC_DTX_MAX_ORDER 16
+#define HILC_DTX_LEVELS 128
+#define HILC_DTX_GOLDEN 0x9E3779B9u
+#define HILC_DTX_ST_HAS 0
+#define HILC_DTX_ST_LEVEL 1
+#define HILC_DTX_ST_COUNT 2
+#define HILC_DTX_ST_Q 3
+
+/* jitter buffer (hilcodec_amd/jitter.py).  State row, ST_WORDS words: ST_ANCHORED, ST_WAIT, ST_NEXT (the playout clock), ST_IN_DTX,
+ * ST_MASK (bit i: ring entry i occupied), then the counters STAT_*.  Meta word of a ring entry: h | META_SID | META_FEC |
+ * n << META_N_SHIFT, 0 when free.  Adapt row, AD_WORDS words: a slot's debt, pending shift, stale windows, window minimum and count,
+ * outlier run and its last h, the last full window's margin, then the counters AD_GROWN .. AD_RESYNC. */
+#define HILC_JITTER_ST_ANCHORED 0
+#define HILC_JITTER_ST_WAIT 1
+#define HILC_JITTER_ST_NEXT 2
+#define HILC_JITTER_ST_IN_DTX 3
+#define HILC_JITTER_ST_MASK 4
+#define HILC_JITTER_STAT_ACCEPTED 5
+#define HILC_JITTER_STAT_DUPLICATE 6
+#define HILC_JITTER_STAT_LATE 7
+#define HILC_JITTER_STAT_EARLY 8
+#define HILC_JITTER_STAT_MALFORMED 9
+#define HILC_JITTER_STAT_DECODED 10
+#define HILC_JITTER_STAT_FEC 11
+#define HILC_JITTER_STAT_LOST 12
+#define HILC_JITTER_STAT_NOISE 13
+#define HILC_JITTER_ST_WORDS 14
+#define HILC_JITTER_META_SID (1 << 16)
+#define HILC_JITTER_META_FEC (1 << 17)
+#define HILC_JITTER_META_N_SHIFT 18
+#define HILC_JITTER_AD_DEBT 0
+#define HILC_JITTER_AD_PENDING 1
+#define HILC_JITTER_AD_STALE 2
+#define HILC_JITTER_AD_MIN 3
+#define HILC_JITTER_AD_COUNT 4
+#define HILC_JITTER_AD_RUN 5
+#define HILC_JITTER_AD_LAST 6
+#define HILC_JITTER_AD_MARGIN 7
+#define HILC_JITTER_AD_GROWN 8
+#define HILC_JITTER_AD_SHRUNK 9
+#define HILC_JITTER_AD_FORCED 10
+#define HILC_JITTER_AD_RESYNC 11
+#define HILC_JITTER_AD_WORDS 12
+
+/* per-room mixing (hilcodec_amd/mixer.py): the most speakers of a room */
+#define HILC_MIXER_MAX_TOP_K 8
+
+/* receiver reports and loss-adaptive FEC (hilcodec_amd/report.py).  Report row, RP_WORDS words: RP_SEQ, RP_LOSS, RP_RESIDUAL (the
+ * last report), RP_PHASE, RP_N, RP_F, RP_L, RP_HEAD (the interval phase, the window's counts and head), RP_DECODED .. RP_NOISE (the
+ * remembered jitter counters), RP_REPORTS, then RP_RING_WORDS ring words from RP_RING, 2 bits per hop: CLASS_*.  FEC-adapt row,
+ * FA_WORDS words: FA_ON, FA_CALM, FA_SEEN, FA_LAST (seq), FA_AGE, FA_LOSS, FA_RESIDUAL, then the counters FA_REPORTS .. FA_TIMEOUT.
+ * A report travels to the sender's graph as one word: REPORT_PRESENT | seq << 16 | loss_q8 << 8 | residual_q8, 0 for none. */
+#define HILC_REPORT_RP_SEQ 0
+#define HILC_REPORT_RP_LOSS 1
+#define HILC_REPORT_RP_RESIDUAL 2
+#define HILC_REPORT_RP_PHASE 3
+#define HILC_REPORT_RP_N 4
+#define HILC_REPORT_RP_F 5
+#define HILC_REPORT_RP_L 6
+#define HILC_REPORT_RP_HEAD 7
+#define HILC_REPORT_RP_DECODED 8
+#define HILC_REPORT_RP_FEC 9
+#define HILC_REPORT_RP_LOST 10
+#define HILC_REPORT_RP_NOISE 11
+#define HILC_REPORT_RP_REPORTS 12
+#define HILC_REPORT_RP_RING 13
+#define HILC_REPORT_RP_RING_WORDS 16
+#define HILC_REPORT_RP_WORDS (HILC_REPORT_RP_RING + HILC_REPORT_RP_RING_WORDS)
+#define HILC_REPORT_CLASS_NONE 0
+#define HILC_REPORT_CLASS_D 1
+#define HILC_REPORT_CLASS_F 2
+#define HILC_REPORT_CLASS_L 3
+#define HILC_REPORT_CLASS_NOISE 4
+#define HILC_REPORT_FA_ON 0
+#define HILC_REPORT_FA_CALM 1
+#define HILC_REPORT_FA_SEEN 2
+#define HILC_REPORT_FA_LAST 3
+#define HILC_REPORT_FA_AGE 4
+#define HILC_REPORT_FA_LOSS 5
+#define HILC_REPORT_FA_RESIDUAL 6
+#define HILC_REPORT_FA_REPORTS 7
+#define HILC_REPORT_FA_STALE 8
+#define HILC_REPORT_FA_TURNED_ON 9
+#define HILC_REPORT_FA_TURNED_OFF 10
+#define HILC_REPORT_FA_TIMEOUT 11
+#define HILC_REPORT_FA_WORDS 12
+#define HILC_REPORT_REPORT_PRESENT (1 << 24)
 
 /* ---- per-stream session state of a streaming hop (ABI 16) ------------------------------------------------------------------
  * Layout: the caches of `streams` streams live in ONE fp32 block (hilcodec_amd/graph_step.py StateBlock): slice k (one
@@ -408,7 +539,7 @@ int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const fl
  * stream's nslices parts concatenated in order: sum(slice_len) floats (76 479 for both shipped models), records packed back to
  * back.  The reference's caches start at zero (`causal_layers.py:56-58,131-133,156-158`) and the codec keeps no other per-stream
  * state, so zeroing a stream's parts starts a fresh stream there and loading a record resumes one.
- * hilc_state_slots_apply: action[b] (int32, device, `streams` entries) = 0 keep, -1 zero stream b, r >= 1 copy record r-1 of
+ * hilc_state_slots_apply: action[b] (int32, device, `streams` entries) = HILC_SESSIONS_ACTION_KEEP, _ZERO (zero stream b) or r >= _LOAD: copy record r - _LOAD of
  * `records` (nrecords records; may be NULL when nrecords == 0) into stream b; any other value: keep.  Meant to run at the head
  * of every hop (captured in its graph): a fixed grid that leaves after one barrier when no action is set.
  * hilc_state_slots_gather: record i of `records` = the current state of stream slots[i] (int32, device, i < nslots); a slot
@@ -445,7 +576,7 @@ int hilc_state_slots_hold(const float* src, float* dst, const int64_t* slice_off
  * it, as hilc_rvq_decode clamps its indices.  n_max < 1: HILC_ERR_RANGE.
  * hilc_rvq_decode_packed: the dequantiser read straight from packets -> q [B][T][C] (channel-last: what the streaming Dequantizer
  * hands the decoder), bit-identical to hilc_rvq_decode_mixed(channel_last = 1, stage_major = 1) on the unpacked indices (same
- * per-element sum in stage order).  codebooks [Nq][K][C]; n_max outside 1..Nq: HILC_ERR_RANGE; K != 1024 or n_max > 32:
+ * per-element sum in stage order).  codebooks [Nq][K][C]; n_max outside 1..Nq: HILC_ERR_RANGE; K != 1024 or n_max > HILC_WIRE_MAX_STAGES:
  * HILC_ERR_UNSUPPORTED. */
 int hilc_pack_codes_10bit(const int64_t* indices, const int* n_per_stream, uint8_t* packets, int* nbytes, int B, int T, int n_max,
                           void* stream);
@@ -454,9 +585,8 @@ int hilc_rvq_decode_packed(const uint8_t* packets, const int* n_per_stream, cons
 
 /* ---- loss concealment of the packet receiver (additive under ABI 16) ------------------------------------------------------------
  * Two entry points added WITHOUT a version bump, as the packet entry points above.  A receiving hop of B streams, T frames and
- * packets of at most n_max stages (layout of hilc_rvq_decode_packed) keeps per stream b one int32 state row of n_max + 3 words at
- * state + b (n_max + 3): [0] run k = hops lost in a row (0..F), [1] has-codes (0/1), [2] stored n, [3 + s] for s < n_max the code of
- * stage s of the LAST frame of the last packet received (0 for s >= stored n).  All zero = a fresh stream.  F = fade_hops >= 1.
+ * packets of at most n_max stages (layout of hilc_rvq_decode_packed) keeps per stream b one int32 state row of n_max +
+ * HILC_WIRE_CONCEAL_CODES words (HILC_WIRE_CONCEAL_*: run k, has-codes, stored n, the last frame's codes).  All zero = a fresh stream.  F = fade_hops >= 1.
  * hilc_conceal_prepare, at the head of the hop (after hilc_state_slots_apply, before hilc_rvq_decode_packed), per stream b, every
  * array int32 [B] on the device unless named otherwise:
  *   action[b] != 0 (a start or a resume on this hop, the action row of hilc_state_slots_apply): the state row is zeroed first;
@@ -468,7 +598,7 @@ int hilc_rvq_decode_packed(const uint8_t* packets, const int* n_per_stream, cons
  *     ramp[b] = k + 1;
  *   else (lost, nothing received since the start, or k = F): hold[b] = 1 (hilc_state_slots_hold keeps the stream), ramp[b] = 0.
  * A stored run > F counts as F, a stored n is clamped to [1, n_max] and codes to 10 bits.  n_max or fade_hops < 1:
- * HILC_ERR_RANGE; n_max > 32: HILC_ERR_UNSUPPORTED.
+ * HILC_ERR_RANGE; n_max > HILC_WIRE_MAX_STAGES: HILC_ERR_UNSUPPORTED.
  * hilc_conceal_gain, after the decoder (before hilc_state_slots_hold): for each stream with ramp[b] in 1..F (a = ramp - 1,
  * c = ramp) or in -F..-1 (a = -ramp, c = 0), wav[b][s] (fp32 [B][samples]) *= gains[a] + (gains[c] - gains[a]) * weights[s], every
  * operation rounded on its own in fp32 (no contraction); gains fp32 [F + 1], weights fp32 [samples].  Any other ramp value: the row
@@ -494,7 +624,7 @@ int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, fl
 
 /* ---- in-band forward error correction of the packet sender and receiver (additive under ABI 16) --------------------------------
  * Two entry points added WITHOUT a version bump, as the packet, concealment and resampling entry points above.  With m redundant
- * stages (1 <= m <= n_max, n_max + m <= 32, else HILC_ERR_RANGE / HILC_ERR_UNSUPPORTED), the packet of stream b for hop k is the
+ * stages (1 <= m <= n_max, n_max + m <= HILC_WIRE_MAX_STAGES, else HILC_ERR_RANGE / HILC_ERR_UNSUPPORTED), the packet of stream b for hop k is the
  * 10-bit packet (layout of hilc_pack_codes_10bit) of the n_b + m stages cat(idx_k[:n_b, b], idx_{k-1}[:m, b]) — the primary codes
  * first, unchanged, then the first m stages of the stream's previous encoded hop — ceil(10 (n_b + m) T / 8) bytes; a stream without
  * a previous encoded hop sends the plain packet of its n_b stages.  A batch is uint8 [B][stride], stride = ceil(10 (n_max + m) T / 8),
@@ -521,13 +651,13 @@ int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, u
 
 /* ---- discontinuous transmission (DTX) and comfort noise (CN) of the packet sender and receiver (additive under ABI 16) ----------
  * Two entry points added WITHOUT a version bump, as the packet, concealment, resampling and FEC entry points above.  The definition,
- * bit for bit, is hilcodec_amd/dtx.py; K = order in 0..16 (else HILC_ERR_RANGE), S = 320 T samples per hop, and a SID (byte 0 the
- * level L in 0..127, bytes 1..K the int8 reflection coefficients q_i) must fit a packet row: stride >= 1 + K (else HILC_ERR_SHAPE).
+ * bit for bit, is hilcodec_amd/dtx.py; K = order in 0..HILC_DTX_MAX_ORDER (else HILC_ERR_RANGE), S = HILC_RESAMPLE_HOP T samples per hop, and a SID (byte 0 the
+ * level L in 0..HILC_DTX_LEVELS - 1, bytes 1..K the int8 reflection coefficients q_i) must fit a packet row: stride >= 1 + K (else HILC_ERR_SHAPE).
  * hilc_dtx_encode: the sender's last launch before hilc_state_slots_hold, after the packer.  x fp32 [B][S] (the encoder's 24 kHz
  * hop); action and hold optional int32 [B] (NULL = 0): the rows of hilc_state_slots_apply / hilc_state_slots_hold; run int32 [B]
- * (in place); kind int32 [B] (out: 0 held, 1 speech, 2 SID, 3 silent); packets uint8 [B][stride] and nbytes int32 [B] as the packer
+ * (in place); kind int32 [B] (out: HILC_DTX_HELD / SPEECH / SID / SILENT); packets uint8 [B][stride] and nbytes int32 [B] as the packer
  * wrote them; indices int64 [n_max][B][T]; prev optional int32 [B][prev_words] (the FEC packer's output row, word 0 its valid flag);
- * level_thr float64 [127] (dtx.level_table); thr_vad the activity threshold on R[0] / S; hangover H >= 0, sid_interval I >= 1.
+ * level_thr float64 [HILC_DTX_LEVELS - 1] (dtx.level_table); thr_vad the activity threshold on R[0] / S; hangover H >= 0, sid_interval I >= 1.
  * Per stream b: action[b] != 0 resets run[b] to 0 first; hold[b] != 0: kind 0, nothing else.  Otherwise: R[k], k <= K, in float64
  * (lane l of 64 sums x[s] x[s - k] over s = l mod 64, s >= k, in increasing s, then the 64 partials in lane order); active iff
  * R[0] / S >= thr_vad; Levinson-Durbin on R'[0] = R[0] (1 + 2^-13) -> k_i, E_K; L = #{j : E_K / S < level_thr[j]};
@@ -535,14 +665,13 @@ int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, u
  * run <= H, SID if run == H + 1, else silent.  SID: packets[b] = L, q_1..q_K, then zeros, nbytes[b] = 1 + K; silent: packets[b] = 0,
  * nbytes[b] = 0; both: indices of b = -1 and prev[b][0] = 0.  Speech rows are not touched.
  * hilc_cng_synth: the receiver's launch after the decoder.  packets uint8 [B][stride] (a SID slot's row: the SID); action optional;
- * hold int32 [B] (in place): 2 = a SID arrived, 3 = silent (the stream is in DTX), 0 = decoded, anything else = held; state int32
- * [B][3 + 2 K] (in place): has-SID, L, c (noise hops since the start, mod 2^32), q_1..q_K, then K fp32 words of filter memory
- * y[-K..-1]; wav fp32 [B][S]; restore optional int32 [B] (out: 1 where the slot produced noise, else 0); gains fp32 [128]
- * (dtx.gain_table).  Per slot: action != 0 clears the state row first.  hold 2: L = min(byte 0, 127), q_i = clamp(int8 byte i,
- * -127, 127) are stored, has = 1, the filter memory starts from zero if has was 0; the slot produces noise.  hold 3: with has, noise
- * from the stored parameters; without, hold[b] = 1.  hold 0: has = 0.  Noise: wav[b][s] = y[s] = g u[s] - a_K y[s - K] - ... -
+ * hold int32 [B] (in place): HILC_SESSIONS_HOLD_SID = a SID arrived, _SILENT = the stream is in DTX, _ADVANCE = decoded, anything else =
+ * held; state int32 [B][HILC_DTX_ST_Q + 2 K] (in place: HILC_DTX_ST_*); wav fp32 [B][S]; restore optional int32 [B] (out: 1 where the slot produced noise, else 0); gains fp32 [HILC_DTX_LEVELS]
+ * (dtx.gain_table).  Per slot: action != 0 clears the state row first.  hold SID: L = min(byte 0, HILC_DTX_LEVELS - 1), q_i = clamp(int8 byte i,
+ * -127, 127) are stored, has = 1, the filter memory starts from zero if has was 0; the slot produces noise.  hold SILENT: with has, noise
+ * from the stored parameters; without, hold[b] = HELD.  hold ADVANCE: has = 0.  Noise: wav[b][s] = y[s] = g u[s] - a_K y[s - K] - ... -
  * a_1 y[s - 1] in fp32 (each product and difference rounded, left to right), g = gains[L], a = step-up of q_i / 128 in float64
- * rounded to fp32, u[s] = fp32(h >> 8) 2^-23 - 1, h = lowbias32(((c S + s) mod 2^32) ^ ((b + 1) 0x9E3779B9 mod 2^32)); if some |y[s]| >= 16
+ * rounded to fp32, u[s] = fp32(h >> 8) 2^-23 - 1, h = lowbias32(((c S + s) mod 2^32) ^ ((b + 1) HILC_DTX_GOLDEN mod 2^32)); if some |y[s]| >= 16
  * or is not finite the row and the memory become 0; then c += 1, the memory = the last K outputs, hold[b] = 0.  Rows of slots without noise are not touched.  NULL pointers: HILC_ERR_NULL; B or
  * T <= 0: HILC_ERR_SHAPE.  Both: one wave per stream. */
 int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes,
@@ -553,23 +682,24 @@ int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* st
 
 /* ---- transport header and jitter buffer of the packet sender and receiver (additive under ABI 16) -------------------------------
  * Two entry points added WITHOUT a version bump, as the packet, concealment, resampling, FEC and DTX entry points above.  Header
- * (hilcodec_amd/wire.py, pack_transport): byte 0-1 the hop index h mod 2^16 big-endian, byte 2 = SID << 7 | FEC << 6 | n (bit 5 zero,
- * n 1..31 for codes, 0 for a SID), then the body; stride = ceil(10 (n_max + m) T / 8), a headed row is 3 + stride bytes.  m in
- * [0, n_max] (else HILC_ERR_RANGE), n_max <= 31 and n_max + m <= 32 (else HILC_ERR_UNSUPPORTED).
+ * (hilcodec_amd/wire.py, pack_transport): byte 0-1 the hop index h mod 2^16 big-endian, byte 2 = HILC_WIRE_SID_BIT | HILC_WIRE_FEC_BIT | n (HILC_WIRE_RSV_BIT
+ * zero, n 1..31 for codes, 0 for a SID), then the body; stride = ceil(10 (n_max + m) T / 8), a headed row is H + stride bytes, H =
+ * HILC_WIRE_TRANSPORT_HEADER.  m in [0, n_max] (else HILC_ERR_RANGE), n_max <= 31 and n_max + m <= HILC_WIRE_MAX_STAGES (else
+ * HILC_ERR_UNSUPPORTED).
  * hilc_packet_header: the sender's last launch.  packets uint8 [B][stride] and nbytes int32 [B] as the packer (and hilc_dtx_encode)
  * left them; n_per_stream, kind (hilc_dtx_encode's), action, hold optional int32 [B] (NULL = n_max, speech, 0, 0); counter_in and
- * counter_out distinct int32 [B] (the hop of parity p reads one, writes the other) -> out uint8 [B][3 + stride], out_nbytes int32 [B].
+ * counter_out distinct int32 [B] (the hop of parity p reads one, writes the other) -> out uint8 [B][H + stride], out_nbytes int32 [B].
  * Per stream b: c = action[b] != 0 ? 0 : counter_in[b] mod 2^16; hold[b] != 0: out[b] = 0, out_nbytes[b] = 0, counter_out[b] = c;
- * else counter_out[b] = (c + 1) mod 2^16 and, when nbytes[b] > 0, out[b] = header(c, SID iff kind[b] == 2, FEC iff m >= 1 and
+ * else counter_out[b] = (c + 1) mod 2^16 and, when nbytes[b] > 0, out[b] = header(c, SID iff kind[b] == HILC_DTX_SID, FEC iff m >= 1 and
  * nbytes[b] = ceil(10 (n_b + m) T / 8) with n_b = n_per_stream[b] clamped to [max(m, 1), n_max], n = 0 for a SID else n_b) then the
- * nbytes[b] packet bytes, out_nbytes[b] = 3 + nbytes[b]; nbytes[b] == 0: out[b] = 0, out_nbytes[b] = 0.  One thread per output byte.
+ * nbytes[b] packet bytes, out_nbytes[b] = H + nbytes[b]; nbytes[b] == 0: out[b] = 0, out_nbytes[b] = 0.  One thread per output byte.
  * hilc_jitter_step: the receiver's first launch; the rules, bit for bit, are hilcodec_amd/jitter.py (JitterModel).  arrivals int32
- * [max_arrivals][1 + ceil((3 + stride) / 4)] (word 0 the byte count, then the headed packet), grouped by slot: slot b's arrivals are
+ * [max_arrivals][1 + ceil((H + stride) / 4)] (word 0 the byte count, then the headed packet), grouped by slot: slot b's arrivals are
  * records offsets[b] .. offsets[b + 1] - 1 (int32 [B + 1], clamped to [0, max_arrivals]) in push order; action optional int32 [B];
- * hold int32 [B] (in: the host's holds and stops; out: 0, or 1 held, 2 SID, 3 silent); n_per_stream, lost (conceal != 0 only), fec
- * (m >= 1 only) int32 [B] and packets uint8 [B][stride] (out); state int32 [B][14], meta int32 [B][capacity] and ring int32
+ * hold int32 [B] (in: the host's holds and stops; out: HILC_SESSIONS_HOLD_ADVANCE, _HELD, _SID or _SILENT); n_per_stream, lost (conceal != 0 only), fec
+ * (m >= 1 only) int32 [B] and packets uint8 [B][stride] (out); state int32 [B][HILC_JITTER_ST_WORDS], meta int32 [B][capacity] and ring int32
  * [B][capacity][ceil(stride / 4)] (in place).  order = the receiver's comfort-noise order K, -1 for none (a SID needs 1 + K <=
- * stride, else HILC_ERR_SHAPE; K > 16: HILC_ERR_RANGE); capacity a power of two in [2, 32], 0 <= depth <= capacity - 2 (else
+ * stride, else HILC_ERR_SHAPE; K > HILC_DTX_MAX_ORDER: HILC_ERR_RANGE); capacity a power of two in [2, 32], 0 <= depth <= capacity - 2 (else
  * HILC_ERR_RANGE).  NULL pointers: HILC_ERR_NULL; B or T <= 0 or max_arrivals < 0: HILC_ERR_SHAPE.  One wave per slot. */
 int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action,
                        const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max,
@@ -581,7 +711,7 @@ int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, 
 /* ---- adaptive playout of the jitter buffer (additive under ABI 16) ---------------------------------------------------------------
  * One entry point added WITHOUT a version bump.  hilc_jitter_adapt_step: hilc_jitter_step with an adaptive playout clock, the
  * receiver's first launch in its place; the rules, bit for bit, are hilcodec_amd/jitter.py (JitterModel with cfg.adapt).  The
- * arguments of hilc_jitter_step with their meaning and checks, then adapt int32 [B][12] (in place: jitter.AD_*, a slot's debt,
+ * arguments of hilc_jitter_step with their meaning and checks, then adapt int32 [B][HILC_JITTER_AD_WORDS] (in place: HILC_JITTER_AD_*, a slot's debt,
  * pending shift, window and outlier run, then the counters grown, shrunk, forced, resync; NULL: HILC_ERR_NULL) and the
  * jitter.AdaptConfig: 0 <= headroom <= capacity - 2, 1 <= max_late <= capacity - 2, window >= 1, resync >= 2, force_windows >= 0
  * (else HILC_ERR_RANGE; capacity 2 leaves no max_late).  action[b] != 0 clears slot b's adapt row with its state row.  One wave
@@ -597,7 +727,7 @@ int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arri
  * hilc_mix_levels: score float64 [B], in place; action optional int32 [B].  Per slot b: p[l] = the sum over i = l (mod 64), i
  * ascending, of (double)wav[b][i]^2 (every product and sum rounded on its own in float64), E = p[0] + p[1] + ... + p[63] in that
  * order, score[b] = max(E, 0.5 prev) with prev = score[b], or 0 when action[b] != 0.  One wave per slot.
- * hilc_mix_rooms: room int32 [B] (-1: in no room, else a room id in [0, B)); score as hilc_mix_levels left it; top_k in [1, 8] (else
+ * hilc_mix_rooms: room int32 [B] (-1: in no room, else a room id in [0, B)); score as hilc_mix_levels left it; top_k in [1, HILC_MIXER_MAX_TOP_K] (else
  * HILC_ERR_UNSUPPORTED) -> mixed fp32 [B][L], speakers int32 [B], every element written.  The candidates of room r are the slots with
  * room == r and score > 0, ordered by (score descending, slot ascending); the first min(top_k, count) are its speakers (speakers[b] =
  * 1, else 0).  mixed[b] for room[b] = r >= 0: the rows of r's speakers other than b, added per sample in ascending slot order
@@ -623,7 +753,7 @@ int hilc_mix_rooms(const float* wav, const int* room, const double* score, int t
  *   clamp(c / stage_bits, lo, n_b)), credit[b] = c - n_eff stage_bits.  Without: n_eff = n_q.
  *   hold[b] != 0: n_eff[b] = n_b, distortion[b] = 0, credit[b] = c before the refill (so an action on the same hop still fills it).
  *   Finally indices[s][b][:] = -1 for s >= n_eff[b].
- * C a multiple of 64 and <= 512, n <= 32 (else HILC_ERR_UNSUPPORTED); 1 <= n <= Nq, 1 <= n_lo <= n, 0 < rho <= 1, and with credit
+ * C a multiple of 64 and <= 512, n <= HILC_WIRE_MAX_STAGES (else HILC_ERR_UNSUPPORTED); 1 <= n <= Nq, 1 <= n_lo <= n, 0 < rho <= 1, and with credit
  * stage_bits >= 1, rate_bits >= stage_bits n_lo, rate_bits <= burst_bits <= 2^30 (else HILC_ERR_RANGE); NULL pointers (the optional
  * rows excepted; credit NULL with rate_bits != 0): HILC_ERR_NULL; B, T, C, K or Nq <= 0: HILC_ERR_SHAPE.  One wave per slot, no
  * atomics; every element of n_eff and distortion is written. */
@@ -633,9 +763,9 @@ int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, co
 
 /* ---- receiver reports and loss-adaptive in-band FEC (additive under ABI 16) -------------------------------------------------------
  * Two entry points added WITHOUT a version bump, as the entry points above.  The definition, bit for bit, is hilcodec_amd/report.py.
- * hilc_rx_report: the receiver's launch after hilc_jitter_step / hilc_jitter_adapt_step.  jitter_state int32 [B][14] (read only: the
- * rows that launch left); action optional int32 [B]; rows int32 [B][29] (in place: report.RP_*, the last report, the interval phase, the
- * window's counts and head, the remembered counters, the reports emitted, then 16 ring words); reports uint8 [B][3] (seq, loss_q8,
+ * hilc_rx_report: the receiver's launch after hilc_jitter_step / hilc_jitter_adapt_step.  jitter_state int32 [B][HILC_JITTER_ST_WORDS] (read only: the
+ * rows that launch left); action optional int32 [B]; rows int32 [B][HILC_REPORT_RP_WORDS] (in place: HILC_REPORT_RP_*, the last report, the interval phase, the
+ * window's counts and head, the remembered counters, the reports emitted, then the ring words); reports uint8 [B][HILC_WIRE_REPORT_BYTES] (seq, loss_q8,
  * residual_q8 of the slot's latest report: written when one is emitted, zeroed by action[b] != 0, else untouched); due int32 [B] (every
  * element written: 1 where a report was emitted on this hop).  Per slot: the hop's class is the first of the counters DECODED, FEC,
  * LOST, NOISE that differs from the remembered one (none: nothing but due changes); D, F and L hops enter a window of the last
@@ -643,8 +773,8 @@ int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, co
  * entries, seq = (seq + 1) mod 256, loss_q8 = min(255, (256 (F + L) + N / 2) / N), residual_q8 = min(255, (256 L + N / 2) / N).
  * 8 <= window <= 256 and 1 <= interval <= 1024, B >= 1 (else HILC_ERR_SHAPE).
  * hilc_fec_adapt: the sender's launch ahead of hilc_vbr_select / hilc_pack_codes_10bit_fec.  report optional int32 [B] (per slot 0, or
- * 1 << 24 | seq << 16 | loss_q8 << 8 | residual_q8); action, hold optional int32 [B] (the rows of hilc_state_slots_apply /
- * hilc_state_slots_hold); rows int32 [B][12] (in place: report.FA_*, on, calm, seen, last seq, age, loss, residual, then the counters
+ * HILC_REPORT_REPORT_PRESENT | seq << 16 | loss_q8 << 8 | residual_q8); action, hold optional int32 [B] (the rows of hilc_state_slots_apply /
+ * hilc_state_slots_hold); rows int32 [B][HILC_REPORT_FA_WORDS] (in place: HILC_REPORT_FA_*, on, calm, seen, last seq, age, loss, residual, then the counters
  * reports, stale, turned_on, turned_off, timeout); prev int32 [B][1 + m T] (the previous-codes rows the packer reads on this hop: only
  * word 0 of a slot that is not held and off is written, with 0); fec_on int32 [B] (every element written).  Per slot: action[b] != 0
  * clears the row to on = initial_on; a report is accepted when none was seen since the clear or (seq - last) mod 256 is in [1, 127]

@@ -48,6 +48,52 @@ def test_binding_matches_header_type_for_type():
         assert mirror._fields_ == structs[name], name
 
 
+def test_layouts_match_header():
+    """The per-slot row layouts, codes and limits are the other link between C and Python that no compiler checks: the kernels take
+    them from include/hilcodec_amd.h, the bindings and the host models from the Python modules.  `#define HILC_<MODULE>_<NAME>` is
+    `hilcodec_amd.<module>.<NAME>`, value for value, in both directions: every such define has its Python name, and every public
+    upper-case int that one of those modules assigns has its define (HOST_ONLY: what a host model needs and no kernel row or code
+    depends on).  Then the derived sizes that allocations rely on."""
+    import ast
+    import importlib
+    modules = ("sessions", "wire", "resample", "dtx", "jitter", "mixer", "vbr", "report")
+    HOST_ONLY = {"LANES", "BASE_RATE", "ZERO_CROSSINGS", "MAX_BURST_BITS"}    # a wave's lanes, the filter design, an int32 bound
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "hilcodec_amd.h")).read(), flags=re.S)
+    header, env = {}, {}
+    for name, expr in re.findall(r"^#define (HILC_\w+)[ \t]+(\S.*?)[ \t]*$", text, re.M):
+        env[name] = eval(re.sub(r"\b(0x[0-9A-Fa-f]+|\d+)[uU]\b", r"\1", expr), {"__builtins__": {}}, env)
+        m = re.match(r"HILC_(%s)_(\w+)$" % "|".join(mod.upper() for mod in modules), name)
+        if m:
+            assert (m.group(1).lower(), m.group(2)) not in header, name
+            header[m.group(1).lower(), m.group(2)] = env[name]
+    python = {}
+    for mod in modules:
+        module = importlib.import_module("hilcodec_amd." + mod)
+        for node in ast.parse(open(module.__file__).read()).body:
+            if isinstance(node, ast.Assign):
+                for leaf in ast.walk(node.targets[0]):
+                    if isinstance(leaf, ast.Name) and leaf.id.isupper() and not leaf.id.startswith("_") and leaf.id not in HOST_ONLY:
+                        value = getattr(module, leaf.id)
+                        if isinstance(value, int) and not isinstance(value, bool):
+                            python[mod, leaf.id] = value
+    assert len(header) >= 90                                                # the regular expression found the section
+    assert sorted(set(header) - set(python)) == [], "in the header, not in Python"
+    assert sorted(set(python) - set(header)) == [], "in Python, not in the header"
+    for key, value in header.items():
+        assert python[key] == value, key
+    from hilcodec_amd import dtx, report, wire
+    for K in range(dtx.MAX_ORDER + 1):
+        assert dtx.state_words(K) == env["HILC_DTX_ST_Q"] + 2 * K
+    assert report.RP_WORDS == env["HILC_REPORT_RP_WORDS"] == env["HILC_REPORT_RP_RING"] + env["HILC_REPORT_RP_RING_WORDS"]
+    assert 16 * report.RP_RING_WORDS == 256                                # the widest ReportConfig.window, 2 bits per hop
+    # the conceal row: the three words before the codes, then one code per stage (GraphedDecodeHop allocates n + CONCEAL_CODES)
+    assert (wire.CONCEAL_RUN, wire.CONCEAL_HAS, wire.CONCEAL_N) == tuple(range(env["HILC_WIRE_CONCEAL_CODES"]))
+    # every row is a dense prefix of its width: no two words of a row share an index
+    for mod, pre, width in (("jitter", ("ST_", "STAT_"), "ST_WORDS"), ("jitter", ("AD_",), "AD_WORDS"), ("report", ("FA_",), "FA_WORDS")):
+        words = sorted(v for (m_, n_), v in header.items() if m_ == mod and n_.startswith(pre) and n_ != width)
+        assert words == list(range(header[mod, width])), (mod, pre)
+
+
 @pytest.mark.parametrize("name", ["hil_speech", "hil_music"])
 def test_synth_streaming_model_is_the_one_recipe(name):
     """synth.streaming_model: eval mode, the same tensors on every call, the model stream_driver builds without a checkpoint,
