@@ -87,6 +87,8 @@ SIGNATURES = {
     "hilc_vbr_select": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _p],
     "hilc_rx_report": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
     "hilc_fec_adapt": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "hilc_nack_build": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
+    "hilc_rtx_step": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
 }
 
 ABI_VERSION = 16

@@ -25,6 +25,7 @@ from torch import Tensor
 from . import dtx as dtx_def
 from . import engine, ops, wire
 from . import report as report_def
+from . import rtx as rtx_def
 from . import vbr as vbr_def
 from .jitter import AD_WORDS, ST_WORDS, JitterConfig
 from .mixer import MixConfig
@@ -661,12 +662,23 @@ class GraphedEncodeHop(GraphedHop):
     effect on the next packet.  `fec_on` (int32 `[B]`) and `fec_adapt_state` (int32 `[B, report.FA_WORDS]`) are device views; a `start`
     or a resume clears a slot's row inside the graph, `reset` every row; held and stopped slots take their reports but do not age and keep
     their previous codes; `export` and a resume carry none.  VBR, DTX and the header are untouched.  `fec_adapt=None` captures exactly
-    the graph without it."""
+    the graph without it.
+    `rtx` = rtx.RtxConfig(history, per_hop) (needs `sessions` and `header`): retransmission (rtx.py).  One hilc_rtx_step, the graph's last
+    launch, keeps each slot's last `history` headed packets (what `step` returned for it, byte for byte; held, stopped and DTX SILENT hops
+    store nothing) and answers this hop's NACKs: `step(x, hold=None, reports=None, nacks=(slots, blobs))` takes them like `reports` — A host
+    ints, and a uint8 `[A, 4]` host tensor or a sequence of 4-byte `bytes` (`wire.pack_nack`; a slot outside [0, B) or a wrong width:
+    ValueError; a slot named twice keeps its last) — as two more int32 rows of the control stage's single copy, for exactly one hop.  The
+    hops asked for that are still in the history go to `rtx_packets` (uint8 `[B, per_hop, wire.transport_bytes(n, m, T)]`) with
+    `rtx_nbytes` (int32 `[B, per_hop]`, 0: the row is unused), in request order; they are sent beside the hop's packet and reach the
+    receiver as ordinary `play()` arrivals.  `rtx_state` (int32 `[B, rtx.RX_WORDS]`) counts; all three are device views, the first two
+    overwritten by the next-but-one `step`.  A `start` or a resume empties a slot's history inside the graph (a NACK for its earlier hops
+    is a miss), `stop` and a hold keep it and such a slot still answers; `reset` clears every history; `export` and a resume carry none.
+    Every other option is untouched: a retransmission is not charged to VBR's bucket.  `rtx=None` captures exactly the graph without it."""
 
     def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, input_rate: int = BASE_RATE, fec_stages: int = 0,
                  dtx: Optional[dtx_def.DtxConfig] = None, header: bool = False, vbr: Optional[vbr_def.VbrConfig] = None,
-                 fec_adapt: Optional[report_def.FecAdaptConfig] = None):
+                 fec_adapt: Optional[report_def.FecAdaptConfig] = None, rtx: Optional[rtx_def.RtxConfig] = None):
         # what the captured chain reads is set up first: GraphedHop's constructor captures it
         self.fec_stages = _fec_stages(fec_stages, n)
         if fec_adapt is not None:
@@ -680,6 +692,14 @@ class GraphedEncodeHop(GraphedHop):
         self.header = bool(header)
         if self.header:
             _whole_frames("GraphedEncodeHop(header=True)", hop)
+        if rtx is not None:
+            if not isinstance(rtx, rtx_def.RtxConfig):
+                raise ValueError(f"rtx must be a rtx.RtxConfig or None, got {rtx!r}")
+            if not sessions or not self.header:
+                raise ValueError("GraphedEncodeHop(rtx=...) needs sessions=True and header=True")
+        self.rtx = rtx
+        self._nacks = {}                      # slot -> (word, bitmap) for the next hop
+        self._nack_live = False               # the device NACK rows hold the previous hop's NACKs
         self.frames = hop // HOP
         if dtx is not None and not isinstance(dtx, dtx_def.DtxConfig):
             raise ValueError(f"dtx must be a dtx.DtxConfig or None, got {dtx!r}")
@@ -730,7 +750,19 @@ class GraphedEncodeHop(GraphedHop):
             self._fa[:, report_def.FA_ON] = on0
             self._fec_on = torch.full((batch,), on0, dtype=torch.int32, device=device)
             self._scratch_fill += [(self._fa[:, report_def.FA_ON], on0), (self._fec_on, on0)]
+        self._rx = None
+        if rtx is not None:
+            # per slot: the history (tags and rows of headed packets, updated in place by hilc_rtx_step once per hop) and its counter
+            # row; per parity: the retransmission rows and their byte counts
+            tb = wire.transport_bytes(n, self.fec_stages, self.frames)
+            ints = dict(dtype=torch.int32, device=device)
+            self._rx = (torch.zeros(batch, rtx.history, **ints), torch.zeros(batch, rtx.history, (tb + 3) // 4, **ints),
+                        torch.zeros(batch, rtx_def.RX_WORDS, **ints))
+            self._rx_out = torch.zeros(2, batch, rtx.per_hop, tb, dtype=torch.uint8, device=device)
+            self._rx_nbytes = torch.zeros(2, batch, rtx.per_hop, **ints)
         self._scratch = [t for t in (self._prev, self._run, self._ctr, self._credit, self._fa) if t is not None]
+        if rtx is not None:
+            self._scratch += [*self._rx, self._rx_out, self._rx_nbytes]
         super().__init__(model, batch, hop_in, n, device, warmup, 1, sessions, max_loads_per_hop)
         self.queue.n_min = max(1, self.fec_stages)
         self.indices = self.outs[0][0]
@@ -782,6 +814,10 @@ class GraphedEncodeHop(GraphedHop):
         if self.header:
             packets, nbytes = ops.packet_header(packets, nbytes, self._ctr[p], self._ctr[p ^ 1], self.n, self.fec_stages, self.frames,
                                                 n_clip, kind, action, hold)
+        if self.rtx is not None:
+            # the graph's last launch: this hop's headed packets enter the history, this hop's NACKs are answered from it
+            ops.rtx_step(packets, nbytes, *self._rx, self._rx_out[p], self._rx_nbytes[p], self.stage.row["nack_base"],
+                         self.stage.row["nack_bitmap"], action)
         out = (idx, packets, nbytes) if kind is None else (idx, packets, nbytes, kind)
         return out if n_eff is None else out + (n_eff, distortion)
 
@@ -816,41 +852,74 @@ class GraphedEncodeHop(GraphedHop):
             raise RuntimeError("GraphedEncodeHop.fec_adapt_state: construct with fec_adapt=FecAdaptConfig(...)")
         return self._fa
 
-    def _report_words(self, reports) -> dict:
-        """step's `reports` = (slots, blobs) checked before anything is launched -> {slot: report word}; a slot named twice keeps
-        its last report"""
-        if reports is None:
+    def _need_rtx(self, what: str) -> None:
+        if self.rtx is None:
+            raise RuntimeError(f"GraphedEncodeHop.{what}: construct with rtx=RtxConfig(...)")
+
+    @property
+    def rtx_packets(self) -> Tensor:
+        """uint8 `[B, per_hop, wire.transport_bytes(n, m, T)]` device view: each slot's retransmissions of the last hop, in request
+        order, zero past their lengths (rtx only); overwritten by the next-but-one `step`.  Read-only: written by the graph."""
+        self._need_rtx("rtx_packets")
+        return self._rx_out[self.parity ^ 1]
+
+    @property
+    def rtx_nbytes(self) -> Tensor:
+        """int32 `[B, per_hop]` device view: the byte counts of `rtx_packets` (0: the row is unused).  Read-only: written by the
+        graph."""
+        self._need_rtx("rtx_nbytes")
+        return self._rx_nbytes[self.parity ^ 1]
+
+    @property
+    def rtx_state(self) -> Tensor:
+        """int32 `[B, rtx.RX_WORDS]` device view: each slot's counter row after the last hop (rtx.RX_*; rtx only).  Read-only:
+        written by the graph."""
+        self._need_rtx("rtx_state")
+        return self._rx[2]
+
+    def _feedback(self, name: str, pair, width: int, word, enabled: bool, needs: str) -> dict:
+        """step's `reports` / `nacks` = (slots, blobs) checked before anything is launched -> {slot: word(blob)}; a slot named
+        twice keeps its last blob"""
+        if pair is None:
             return {}
-        if self.fec_adapt is None:
-            raise RuntimeError("GraphedEncodeHop.step(reports=...): construct with fec_adapt=FecAdaptConfig(...)")
+        if not enabled:
+            raise RuntimeError(f"GraphedEncodeHop.step({name}=...): construct with {needs}")
         try:
-            slots, blobs = reports
+            slots, blobs = pair
         except (TypeError, ValueError):
-            raise ValueError("reports: a pair (slots, blobs) expected") from None
-        for name, v in (("slots", slots), ("blobs", blobs)):
+            raise ValueError(f"{name}: a pair (slots, blobs) expected") from None
+        for what, v in (("slots", slots), ("blobs", blobs)):
             if isinstance(v, Tensor) and v.is_cuda:
-                raise ValueError(f"reports: {name} must be on the host, not a device tensor")
+                raise ValueError(f"{name}: {what} must be on the host, not a device tensor")
         slots = [int(s) for s in (slots.reshape(-1).tolist() if isinstance(slots, Tensor) else slots)]
         if isinstance(blobs, Tensor):
-            if blobs.dtype != torch.uint8 or blobs.dim() != 2 or blobs.shape[1] != wire.REPORT_BYTES:
-                raise ValueError(f"reports: blobs must be uint8 [A, {wire.REPORT_BYTES}] or {wire.REPORT_BYTES}-byte bytes objects")
+            if blobs.dtype != torch.uint8 or blobs.dim() != 2 or blobs.shape[1] != width:
+                raise ValueError(f"{name}: blobs must be uint8 [A, {width}] or {width}-byte bytes objects")
             blobs = [bytes(row) for row in blobs.tolist()]
         else:
             blobs = list(blobs)
         if len(blobs) != len(slots):
-            raise ValueError(f"reports: {len(slots)} slots but {len(blobs)} reports")
+            raise ValueError(f"{name}: {len(slots)} slots but {len(blobs)} {name}")
         words = {}
         for s, blob in zip(slots, blobs):
             if not 0 <= s < self.queue.batch:
-                raise ValueError(f"reports: slot {s} outside [0, {self.queue.batch})")
-            words[s] = report_def.report_word(*wire.parse_report(blob))    # ValueError: not 3 bytes
+                raise ValueError(f"{name}: slot {s} outside [0, {self.queue.batch})")
+            words[s] = word(blob)                                           # ValueError: not `width` bytes
         return words
 
+    def _report_words(self, reports) -> dict:
+        return self._feedback("reports", reports, wire.REPORT_BYTES, lambda blob: report_def.report_word(*wire.parse_report(blob)),
+                              self.fec_adapt is not None, "fec_adapt=FecAdaptConfig(...)")
+
+    def _nack_words(self, nacks) -> dict:
+        return self._feedback("nacks", nacks, wire.NACK_BYTES, lambda blob: rtx_def.nack_words(*wire.parse_nack(blob)),
+                              self.rtx is not None, "rtx=RtxConfig(...)")
+
     def _extra_rows(self) -> Tuple[str, ...]:
-        return ("report",) if self.fec_adapt is not None else ()
+        return ("report",) * (self.fec_adapt is not None) + ("nack_base", "nack_bitmap") * (self.rtx is not None)
 
     def _extra_pending(self) -> bool:
-        return bool(self._reports) or self._report_live
+        return bool(self._reports) or self._report_live or bool(self._nacks) or self._nack_live
 
     def _put_extra(self, st: ControlStage) -> None:
         """the report row: this hop's reports, 0 elsewhere (a report applies to exactly one hop, like an action: the upload after a
@@ -862,19 +931,32 @@ class GraphedEncodeHop(GraphedHop):
                 row[slot] = word
             self._report_live = bool(self._reports)
             self._reports = {}
+        if self.rtx is not None:
+            # the NACK rows, likewise: this hop's NACKs, (0, 0) elsewhere
+            base, bitmap = st.h_row["nack_base"], st.h_row["nack_bitmap"]
+            base.zero_()
+            bitmap.zero_()
+            if self._nacks:                   # one indexed write per row: a full batch of NACKs is a thousand slots
+                slots = np.fromiter(self._nacks, dtype=np.int64, count=len(self._nacks))
+                words = np.array(list(self._nacks.values()), dtype=np.int32)
+                base.numpy()[slots], bitmap.numpy()[slots] = words[:, 0], words[:, 1]
+            self._nack_live = bool(self._nacks)
+            self._nacks = {}
 
     def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
-        self._reports = {}
+        self._reports, self._nacks = {}, {}
         super().reset(cache_enc, cache_dec)
 
-    def step(self, x: Tensor, hold=None, reports=None) -> Tuple[Tensor, Tensor]:
+    def step(self, x: Tensor, hold=None, reports=None, nacks=None) -> Tuple[Tensor, Tensor]:
         """`reports` (fec_adapt only): (slots, blobs), this hop's receiver reports — A host ints, and a uint8 `[A, 3]` host tensor or a
-        sequence of 3-byte `bytes` (wire.pack_report)"""
+        sequence of 3-byte `bytes` (wire.pack_report).  `nacks` (rtx only): (slots, blobs) likewise, this hop's NACKs, 4 bytes each
+        (wire.pack_nack)"""
         self._reports = self._report_words(reports)
+        self._nacks = self._nack_words(nacks)
         try:
             out = super().step(x, hold)
         finally:
-            self._reports = {}                # taken by the upload, or dropped with a step that raised before it
+            self._reports, self._nacks = {}, {}       # taken by the upload, or dropped with a step that raised before it
         self.indices, packets, nbytes = out[:3]
         if self.dtx is not None:
             self.kind = out[3]
@@ -967,13 +1049,22 @@ class GraphedDecodeHop(_Hop):
     every other state are those of the receiver without it.  `reports` (uint8 `[B, 3]`: each slot's latest report, unchanged between
     reports), `report_due` (int32 `[B]`: 1 on the hop a report was emitted) and `report_state` (int32 `[B, report.RP_WORDS]`) are device
     views; a `start` clears a slot's row, report and flag inside the graph; `export` and a resume carry none.  `report=None` captures
-    exactly the graph without it."""
+    exactly the graph without it.
+    `nack` = rtx.NackConfig(rtt_hops, retry_hops, max_requests, skip_fecable) (needs `jitter`: the rule reads the ring): negative
+    acknowledgements (rtx.py).  One hilc_nack_build directly after the jitter step, beside hilc_rx_report and independent of it, finds
+    the holes of each slot's ring that a retransmission can still fill — not those that would come too late, lie in DTX silence or (with
+    `skip_fecable`) are repaired by FEC — and asks for each at most `max_requests` times, `retry_hops` apart: `nacks` (uint8 `[B, 4]`:
+    each slot's latest NACK, `wire.parse_nack`, unchanged between NACKs), `nack_due` (int32 `[B]`: 1 on the hop a NACK was emitted) and
+    `nack_state` (int32 `[B, rtx.NK_WORDS]`) are device views.  It only observes: wav, caches and every other state are those of the
+    receiver without it.  The sender's answers (GraphedEncodeHop(rtx=...)) are pushed with `play()` like any packet.  A `start` or a
+    resume clears a slot's row, NACK and flag inside the graph; `export` and a resume carry none.  `nack=None` captures exactly the
+    graph without it."""
 
     def __init__(self, model, batch: int, frames: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, conceal: bool = False, fade_hops: int = 4, output_rate: int = BASE_RATE,
                  fec_stages: int = 0, cng_order: Optional[int] = None, jitter: Optional[JitterConfig] = None,
                  max_arrivals: Optional[int] = None, mix: Optional[MixConfig] = None,
-                 report: Optional[report_def.ReportConfig] = None):
+                 report: Optional[report_def.ReportConfig] = None, nack: Optional[rtx_def.NackConfig] = None):
         self.batch, self.frames = int(batch), int(frames)
         self.output_rate = int(output_rate)
         self.rs, self._history = None, 0
@@ -1012,6 +1103,11 @@ class GraphedDecodeHop(_Hop):
         if report is not None and jitter is None:
             raise ValueError("GraphedDecodeHop(report=...) needs jitter=JitterConfig(...): the reports are made from the jitter state")
         self.report = report
+        if nack is not None and not isinstance(nack, rtx_def.NackConfig):
+            raise ValueError(f"nack must be a rtx.NackConfig or None, got {nack!r}")
+        if nack is not None and jitter is None:
+            raise ValueError("GraphedDecodeHop(nack=...) needs jitter=JitterConfig(...): the NACKs are made from the jitter ring")
+        self.nack = nack
         super().__init__(model, self.batch, int(n), device, 1, sessions, max_loads_per_hop)
         self.stride = wire.packet_bytes(self.n + self.fec_stages, self.frames)
         B = self.batch
@@ -1050,6 +1146,12 @@ class GraphedDecodeHop(_Hop):
             self._rp_bytes = torch.zeros(B, wire.REPORT_BYTES, dtype=torch.uint8, device=device)
             self._rp_due = torch.zeros(B, dtype=torch.int32, device=device)
             self._scratch += [self._rp, self._rp_bytes, self._rp_due]
+        if nack is not None:
+            # per slot: the NACK row (rtx.NK_*, updated in place by hilc_nack_build once per hop), its latest NACK, its due flag
+            self._nk = torch.zeros(B, rtx_def.NK_WORDS, dtype=torch.int32, device=device)
+            self._nk_bytes = torch.zeros(B, wire.NACK_BYTES, dtype=torch.uint8, device=device)
+            self._nk_due = torch.zeros(B, dtype=torch.int32, device=device)
+            self._scratch += [self._nk, self._nk_bytes, self._nk_due]
         if mix is not None:
             # per slot: the peak-hold score (updated in place by hilc_mix_levels once per hop); per parity: the mixes; the speaker
             # marks; the room row (device, captured by address) and its pinned host mirror
@@ -1105,6 +1207,8 @@ class GraphedDecodeHop(_Hop):
                             self.n, self.fec_stages, self.frames, self.cng_order, self.jitter.depth, self.action, self.lost, self.fec)
         if self.report is not None:
             ops.rx_report(self._jstate, self._rp, self._rp_bytes, self._rp_due, self.report, self.action)
+        if self.nack is not None:
+            ops.nack_build(self._jstate, self._jmeta, self._nk, self._nk_bytes, self._nk_due, self.nack, self.fec_stages, self.action)
         if self.sessions:
             ops.state_slots_apply(src.buffer, src.layout, self.action, self.records)
         packets = self.packets
@@ -1328,6 +1432,30 @@ class GraphedDecodeHop(_Hop):
         by the graph."""
         self._need_report("report_state")
         return self._rp
+
+    def _need_nack(self, what: str) -> None:
+        if self.nack is None:
+            raise RuntimeError(f"GraphedDecodeHop.{what}: construct with nack=NackConfig(...)")
+
+    @property
+    def nacks(self) -> Tensor:
+        """uint8 `[B, 4]` device view: each slot's latest NACK (wire.parse_nack; zeros before its first), unchanged between NACKs.
+        Read-only: written by the graph."""
+        self._need_nack("nacks")
+        return self._nk_bytes
+
+    @property
+    def nack_due(self) -> Tensor:
+        """int32 `[B]` device view: 1 for the slots whose NACK was emitted on the last play.  Read-only: written by the graph."""
+        self._need_nack("nack_due")
+        return self._nk_due
+
+    @property
+    def nack_state(self) -> Tensor:
+        """int32 `[B, rtx.NK_WORDS]` device view: each slot's NACK row after the last play (rtx.NK_*).  Read-only: written by the
+        graph."""
+        self._need_nack("nack_state")
+        return self._nk
 
     def play(self, slots, packets: Tensor, nbytes, hold=None) -> Tensor:
         """one hop of a jitter receiver: this hop's arrivals, in push order — `slots` and `nbytes` (A host ints), `packets` uint8

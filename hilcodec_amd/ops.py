@@ -27,8 +27,9 @@ from ._lib import DownParams, PostParams, ResblockParams, Spec0Params, UpParams,
 from .dtx import LEVELS, state_words
 from .jitter import AD_WORDS, ST_WORDS
 from .report import FA_WORDS, RP_WORDS
+from .rtx import NK_WORDS, RX_WORDS
 from .resample import HOP
-from .wire import CONCEAL_CODES, REPORT_BYTES, TRANSPORT_HEADER, packet_bytes
+from .wire import CONCEAL_CODES, NACK_BYTES, REPORT_BYTES, TRANSPORT_HEADER, packet_bytes
 
 _LIB = torch.library.Library("hilcodec", "DEF")
 
@@ -1169,6 +1170,47 @@ _register("fec_adapt", "(Tensor? report, Tensor? action, Tensor? hold, Tensor(a!
           "int frames, int on_q8, int off_q8, int calm_reports, int timeout_hops, bool initial_on) -> ()", _fec_adapt,
           lambda report, action, hold, rows, prev, fec_on, m, frames, on_q8, off_q8, calm_reports, timeout_hops, initial_on: None)
 
+# ======================================================================================================
+# NACK and retransmission (graph_step.GraphedDecodeHop(nack=), GraphedEncodeHop(rtx=); definition: hilcodec_amd/rtx.py; semantics:
+# include/hilcodec_amd.h)
+# ======================================================================================================
+def _nack_build(jitter_state, meta, action, rows, nacks, due, m, rtt_hops, retry_hops, max_requests, skip_fecable):
+    B = due.numel()
+    if jitter_state.shape != (B, ST_WORDS) or meta.dim() != 2 or meta.shape[0] != B or rows.shape != (B, NK_WORDS) or \
+            nacks.shape != (B, NACK_BYTES):
+        raise RuntimeError(f"nack_build: jitter_state must be [{B}, {ST_WORDS}], meta [{B}, capacity], rows [{B}, {NK_WORDS}] and nacks "
+                           f"[{B}, {NACK_BYTES}]")
+    _rows("nack_build", B, action=action)
+    check(lib.hilc_nack_build(_ptr(jitter_state, torch.int32), _ptr(meta, torch.int32), _ptr(action, torch.int32), _ptr(rows, torch.int32),
+                              _ptr(nacks, torch.uint8), _ptr(due, torch.int32), B, meta.shape[1], m, rtt_hops, retry_hops, max_requests,
+                              int(skip_fecable), _stream()), "hilc_nack_build")
+
+
+_register("nack_build", "(Tensor jitter_state, Tensor meta, Tensor? action, Tensor(a!) rows, Tensor(b!) nacks, Tensor(c!) due, int m, "
+          "int rtt_hops, int retry_hops, int max_requests, bool skip_fecable) -> ()", _nack_build,
+          lambda jitter_state, meta, action, rows, nacks, due, m, rtt_hops, retry_hops, max_requests, skip_fecable: None)
+
+
+def _rtx_step(packets, nbytes, nack_base, nack_bitmap, action, tags, ring, rows, out, out_nbytes):
+    if packets.dim() != 2 or tags.dim() != 2 or out.dim() != 3:
+        raise RuntimeError("rtx_step: packets must be [B, row_bytes], tags [B, history] and out [B, per_hop, row_bytes]")
+    B, tb = packets.shape
+    R, P = tags.shape[1], out.shape[1]
+    if nbytes.numel() != B or tags.shape[0] != B or ring.shape != (B, R, (tb + 3) // 4) or rows.shape != (B, RX_WORDS) or \
+            out.shape != (B, P, tb) or out_nbytes.shape != (B, P):
+        raise RuntimeError(f"rtx_step: nbytes must be [{B}], tags [{B}, {R}], ring [{B}, {R}, {(tb + 3) // 4}], rows [{B}, {RX_WORDS}], "
+                           f"out [{B}, {P}, {tb}] and out_nbytes [{B}, {P}]")
+    _rows("rtx_step", B, nack_base=nack_base, nack_bitmap=nack_bitmap, action=action)
+    check(lib.hilc_rtx_step(_ptr(packets, torch.uint8), _ptr(nbytes, torch.int32), _ptr(nack_base, torch.int32),
+                            _ptr(nack_bitmap, torch.int32), _ptr(action, torch.int32), _ptr(tags, torch.int32), _ptr(ring, torch.int32),
+                            _ptr(rows, torch.int32), _ptr(out, torch.uint8), _ptr(out_nbytes, torch.int32), B, tb, R, P, _stream()),
+          "hilc_rtx_step")
+
+
+_register("rtx_step", "(Tensor packets, Tensor nbytes, Tensor? nack_base, Tensor? nack_bitmap, Tensor? action, Tensor(a!) tags, "
+          "Tensor(b!) ring, Tensor(c!) rows, Tensor(d!) out, Tensor(e!) out_nbytes) -> ()", _rtx_step,
+          lambda packets, nbytes, nack_base, nack_bitmap, action, tags, ring, rows, out, out_nbytes: None)
+
 _OPS = torch.ops.hilcodec
 
 
@@ -1841,3 +1883,23 @@ def fec_adapt(prev: Tensor, rows: Tensor, fec_on: Tensor, m: int, frames: int, c
     switch.  `cfg`: the report.FecAdaptConfig; `action` / `hold` (int32 `[B]`, optional): the session rows."""
     _OPS.fec_adapt(report, action, hold, rows, prev, fec_on, int(m), int(frames), int(cfg.on_q8), int(cfg.off_q8), int(cfg.calm_reports),
                    int(cfg.timeout_hops), bool(cfg.initial_on))
+
+
+def nack_build(jitter_state: Tensor, meta: Tensor, rows: Tensor, nacks: Tensor, due: Tensor, cfg, m: int = 0,
+               action: Optional[Tensor] = None) -> None:
+    """The NACKing receiver's step after its jitter step (rtx.NackModel), in place: `jitter_state` (int32 `[B, 14]`) and `meta` (int32
+    `[B, capacity]`, the ring's meta words), both read only -> `rows` (int32 `[B, rtx.NK_WORDS]`), `nacks` (uint8 `[B, 4]`: each slot's
+    latest NACK, wire.pack_nack, written when one is emitted) and `due` (int32 `[B]`: 1 where one was emitted on this hop).  `cfg`: the
+    rtx.NackConfig; `m`: the receiver's fec_stages; `action` (int32 `[B]`, optional): the session row, a start clears the slot."""
+    _OPS.nack_build(jitter_state, meta, action, rows, nacks, due, int(m), int(cfg.rtt_hops), int(cfg.retry_hops), int(cfg.max_requests),
+                    bool(cfg.skip_fecable))
+
+
+def rtx_step(packets: Tensor, nbytes: Tensor, tags: Tensor, ring: Tensor, rows: Tensor, out: Tensor, out_nbytes: Tensor,
+             nack_base: Optional[Tensor] = None, nack_bitmap: Optional[Tensor] = None, action: Optional[Tensor] = None) -> None:
+    """The retransmitting sender's step behind its header (rtx.RtxModel), in place: this hop's headed `packets` (uint8 `[B,
+    row_bytes]`) and `nbytes` (int32 `[B]`) enter the history — `tags` (int32 `[B, history]`), `ring` (int32 `[B, history, ceil(row_bytes
+    / 4)]`) — and the hops that this hop's NACKs ask for (`nack_base` / `nack_bitmap`, int32 `[B]` each: rtx.nack_words, 0: none; both or
+    neither) are copied to `out` (uint8 `[B, per_hop, row_bytes]`) with `out_nbytes` (int32 `[B, per_hop]`); `rows` (int32 `[B,
+    rtx.RX_WORDS]`) count.  `action` (int32 `[B]`, optional): the session row, a start empties the slot's history."""
+    _OPS.rtx_step(packets, nbytes, nack_base, nack_bitmap, action, tags, ring, rows, out, out_nbytes)

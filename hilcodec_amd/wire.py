@@ -239,6 +239,37 @@ def parse_report(blob) -> Tuple[int, int, int]:
         raise ValueError(f"a report is {REPORT_BYTES} bytes, got {len(data)}")
     return data[0], data[1], data[2]
 
+
+# Negative acknowledgement (hilcodec_amd/rtx.py: GraphedDecodeHop(nack=...) emits it, GraphedEncodeHop(rtx=...) answers it): feedback
+# that travels beside the media, 4 bytes: `base`, the first hop index asked for, big-endian in bytes 0-1, then a 16-bit bitmap,
+# big-endian in bytes 2-3, whose bit j asks for hop (base + 1 + j) mod 2^16 as well.  `base` itself is always asked for.
+NACK_BYTES = 4
+
+
+def pack_nack(base: int, bitmap: int) -> bytes:
+    """(base, bitmap), two bytes each, big-endian; ValueError for a field outside [0, 65535]"""
+    for name, v in (("base", base), ("bitmap", bitmap)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0xFFFF:
+            raise ValueError(f"pack_nack: {name} = {v!r} outside [0, 65535]")
+    base, bitmap = int(base), int(bitmap)
+    return bytes([base >> 8, base & 0xFF, bitmap >> 8, bitmap & 0xFF])
+
+
+def parse_nack(blob) -> Tuple[int, int]:
+    """(base, bitmap) of a NACK; ValueError unless it is exactly NACK_BYTES bytes"""
+    data = bytes(blob)
+    if len(data) != NACK_BYTES:
+        raise ValueError(f"a NACK is {NACK_BYTES} bytes, got {len(data)}")
+    return (data[0] << 8) | data[1], (data[2] << 8) | data[3]
+
+
+def nack_hops(base: int, bitmap: int) -> List[int]:
+    """the hop indices a NACK asks for, in ascending order from `base` (mod 2^16): base, then base + 1 + j for every set bit j"""
+    base, bitmap = int(base), int(bitmap)
+    if not 0 <= base <= 0xFFFF or not 0 <= bitmap <= 0xFFFF:
+        raise ValueError(f"nack_hops: base = {base} or bitmap = {bitmap} outside [0, 65535]")
+    return [base] + [(base + 1 + j) & 0xFFFF for j in range(16) if (bitmap >> j) & 1]
+
 # ---------------------------------------------------------------- caches
 def save_cache_npz(path: str, caches: Sequence[Tensor], prefix: str) -> None:
     """prefix 'e_in' (encoder, 22 tensors) or 'd_in' (decoder, 30)."""

@@ -37,7 +37,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -417,7 +417,7 @@ int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const fl
 
 /* wire format (hilcodec_amd/wire.py).  A packet holds at most MAX_STAGES stages, primary + redundant.  Transport header: TRANSPORT_HEADER
  * bytes, bytes 0-1 the hop index mod 2^16 big-endian, byte 2 = SID_BIT | FEC_BIT | n in N_MASK, RSV_BIT zero.  A receiver report is
- * REPORT_BYTES bytes (seq, loss_q8, residual_q8).  Concealment row of a receiver slot, n_max + CONCEAL_CODES words: RUN = hops lost in a
+ * REPORT_BYTES bytes (seq, loss_q8, residual_q8), a NACK NACK_BYTES bytes (base and bitmap, big-endian).  Concealment row of a receiver slot, n_max + CONCEAL_CODES words: RUN = hops lost in a
  * row (0..F), HAS = has-codes (0/1), N = stored n, CODES + s for s < n_max = the code of stage s of the LAST frame of the last packet
  * received (0 for s >= stored n). */
 #define HILC_WIRE_MAX_STAGES 32
@@ -427,6 +427,7 @@ int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const fl
 #define HILC_WIRE_RSV_BIT 0x20
 #define HILC_WIRE_N_MASK 0x1F
 #define HILC_WIRE_REPORT_BYTES 3
+#define HILC_WIRE_NACK_BYTES 4
 #define HILC_WIRE_CONCEAL_RUN 0
 #define HILC_WIRE_CONCEAL_HAS 1
 #define HILC_WIRE_CONCEAL_N 2
@@ -530,6 +531,28 @@ int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const fl
 #define HILC_REPORT_FA_TIMEOUT 11
 #define HILC_REPORT_FA_WORDS 12
 #define HILC_REPORT_REPORT_PRESENT (1 << 24)
+
+/* NACK and retransmission (hilcodec_amd/rtx.py).  NACK row of a receiver slot, NK_WORDS words: the counters NK_SENT, NK_ASKED,
+ * NK_RECOVERED, NK_EXPIRED, then NK_RING_WORDS entry words from NK_RING, indexed like the jitter ring by h mod capacity: h | count << 16
+ * | age << 24, 0 when free.  Counter row of a sender slot, RX_WORDS words: RX_STORED, RX_REQUESTS, RX_SENT, RX_MISS, RX_DROPPED; a tag
+ * word of its history is h | nbytes << 16, 0 when empty; at most MAX_HISTORY entries and MAX_PER_HOP retransmissions per hop.  A NACK
+ * travels to the sender's graph as two words: NACK_PRESENT | base and the bitmap, (0, 0) for none. */
+#define HILC_RTX_NK_SENT 0
+#define HILC_RTX_NK_ASKED 1
+#define HILC_RTX_NK_RECOVERED 2
+#define HILC_RTX_NK_EXPIRED 3
+#define HILC_RTX_NK_RING 4
+#define HILC_RTX_NK_RING_WORDS 32
+#define HILC_RTX_NK_WORDS (HILC_RTX_NK_RING + HILC_RTX_NK_RING_WORDS)
+#define HILC_RTX_RX_STORED 0
+#define HILC_RTX_RX_REQUESTS 1
+#define HILC_RTX_RX_SENT 2
+#define HILC_RTX_RX_MISS 3
+#define HILC_RTX_RX_DROPPED 4
+#define HILC_RTX_RX_WORDS 5
+#define HILC_RTX_NACK_PRESENT (1 << 16)
+#define HILC_RTX_MAX_HISTORY 64
+#define HILC_RTX_MAX_PER_HOP 4
 
 /* ---- per-stream session state of a streaming hop (ABI 16) ------------------------------------------------------------------
  * Layout: the caches of `streams` streams live in ONE fp32 block (hilcodec_amd/graph_step.py StateBlock): slice k (one
@@ -787,6 +810,35 @@ int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_
                    void* stream);
 int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m,
                    int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream);
+
+/* ---- NACK and retransmission (additive under ABI 16) ----------------------------------------------------------------------------
+ * Two entry points added WITHOUT a version bump, as the entry points above.  The definition, bit for bit, is hilcodec_amd/rtx.py.
+ * hilc_nack_build: the receiver's launch after hilc_jitter_step / hilc_jitter_adapt_step, beside hilc_rx_report.  jitter_state int32
+ * [B][HILC_JITTER_ST_WORDS] and meta int32 [B][capacity] (read only: the rows that launch left); action optional int32 [B]; rows int32
+ * [B][HILC_RTX_NK_WORDS] (in place: HILC_RTX_NK_*, the counters sent, asked, recovered, expired, then one entry word per ring entry);
+ * nacks uint8 [B][HILC_WIRE_NACK_BYTES] (base and bitmap of the slot's latest NACK, big-endian: written when one is emitted, zeroed by
+ * action[b] != 0, else untouched); due int32 [B] (every element written: 1 where a NACK was emitted on this hop).  Per anchored slot,
+ * with next = its playout clock: entry words whose hop is in the window and now in the ring count recovered, those outside the window
+ * expired, and are freed; the holes below the highest occupied entry are asked for — not those with d + 1 < rtt_hops, in a silent
+ * stretch (behind a SID, or behind nothing with ST_IN_DTX set) or, with skip_fecable and m >= 1, in front of a packet with the FEC flag
+ * — when their word is free or age >= retry_hops and count < max_requests: the first is base, those at most 16 above it the bitmap;
+ * a hole asked for restarts its age and counts, every other hole with count > 0 ages by one (at most 255).  capacity a power of two in
+ * [2, 32], rtt_hops in [1, 30], retry_hops and max_requests in [1, 255], m >= 0 (else HILC_ERR_RANGE); B >= 1 (else HILC_ERR_SHAPE).
+ * hilc_rtx_step: the sender's last launch, after hilc_packet_header.  packets uint8 [B][row_bytes] and nbytes int32 [B] as that launch
+ * left them (row_bytes = HILC_WIRE_TRANSPORT_HEADER + stride); nack_base, nack_bitmap optional int32 [B] (both or neither: per slot
+ * HILC_RTX_NACK_PRESENT | base and the bitmap, 0 and 0 for none); action optional int32 [B]; tags int32 [B][history], ring int32
+ * [B][history][ceil(row_bytes / 4)] and rows int32 [B][HILC_RTX_RX_WORDS] (in place) -> out uint8 [B][per_hop][row_bytes], out_nbytes
+ * int32 [B][per_hop], every element written.  Per slot: action[b] != 0 empties the tags; nbytes[b] > 0 stores the packet at entry h mod
+ * history, h its bytes 0-1 (the row zero past min(nbytes[b], row_bytes) bytes, tag h | nbytes << 16); a NACK's hops, base first, then
+ * base + 1 + j for every set bit j ascending, are looked up by tag: a match goes to the next free output row with its byte count, a match
+ * behind per_hop rows counts dropped, anything else a miss.  history a power of two in [2, HILC_RTX_MAX_HISTORY], per_hop in [1,
+ * HILC_RTX_MAX_PER_HOP] (else HILC_ERR_RANGE); B >= 1, HILC_WIRE_TRANSPORT_HEADER < row_bytes < 2^15 (else HILC_ERR_SHAPE); one of the
+ * two NACK rows without the other: HILC_ERR_NULL.
+ * Both: NULL pointers (the optional rows excepted): HILC_ERR_NULL.  One wave per slot, integer only, no LDS, no atomics. */
+int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B,
+                    int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream);
+int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags,
+                  int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream);
 
 #ifdef __cplusplus
 }
