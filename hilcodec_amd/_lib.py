@@ -89,6 +89,8 @@ SIGNATURES = {
     "hilc_fec_adapt": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "hilc_nack_build": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "hilc_rtx_step": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "hilc_rate_ceiling": [_p, _p, _p, _p, _p, _p, _p] + [_i] * 13 + [_p],
+    "hilc_rate_charge": [_p, _p, _p, _i, _i, _i, _p],
 }
 
 ABI_VERSION = 16

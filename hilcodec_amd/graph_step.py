@@ -24,6 +24,7 @@ from torch import Tensor
 
 from . import dtx as dtx_def
 from . import engine, ops, wire
+from . import rate as rate_def
 from . import report as report_def
 from . import rtx as rtx_def
 from . import vbr as vbr_def
@@ -407,7 +408,7 @@ class GraphedHop(_Hop):
         """zero history, or resume from caches saved earlier (`wire.save_cache` / `e_in*`, `d_in*`); with sessions also drops
         every queued action, clears every stop and puts every slot back to the default n.  (GraphedEncodeHop: with FEC, no stream
         has a previous hop afterwards; with DTX, every run counter is 0; with the header, every hop counter is 0; with a VBR
-        cap, every bucket is full)"""
+        cap, every bucket is full; with `rate`, every slot is back at its start rate with a full bucket)"""
         with torch.no_grad():
             self._load(cache_enc, cache_dec)
             if self.sessions:
@@ -673,12 +674,27 @@ class GraphedEncodeHop(GraphedHop):
     receiver as ordinary `play()` arrivals.  `rtx_state` (int32 `[B, rtx.RX_WORDS]`) counts; all three are device views, the first two
     overwritten by the next-but-one `step`.  A `start` or a resume empties a slot's history inside the graph (a NACK for its earlier hops
     is a miss), `stop` and a hold keep it and such a slot still answers; `reset` clears every history; `export` and a resume carry none.
-    Every other option is untouched: a retransmission is not charged to VBR's bucket.  `rtx=None` captures exactly the graph without it."""
+    Every other option is untouched: a retransmission is not charged to VBR's bucket.  `rtx=None` captures exactly the graph without it.
+    `rate` = rate.RateConfig(min_kbps, max_kbps, start_kbps, high_q8, low_q8, increase_q8, burst_hops, timeout_hops) (needs `sessions`;
+    `hop` a multiple of 320; min_kbps must pay for the floor of a hop — the header, max(fec_stages, 1) stages and the redundant section:
+    ValueError otherwise): report-driven rate control (rate.py).  Each slot has a rate that follows this hop's `reports` (taken as for
+    `fec_adapt`; with both, one report feeds both launches): down by half the reported loss at loss_q8 >= high_q8, up by increase_q8 / 256
+    of itself at loss_q8 <= low_q8, back to start_kbps after timeout_hops hops without an accepted report; and a token bucket filled at
+    that rate and charged with every byte the slot sends.  Two launches: hilc_rate_ceiling in front of the quantiser (behind
+    hilc_fec_adapt, which moves there) writes `n_ceil`, the most stages the bucket pays for behind the hop's header and live redundant
+    section, never fewer than min(n_b, max(fec_stages, 1)); that row takes the place of the per-stream n for the quantiser, VBR (as its
+    n_b), the packers and the header.  hilc_rate_charge, the graph's last launch, takes 8 x (`nbytes` + the hop's `rtx_nbytes`) out of
+    the bucket: header, primary codes, redundant section, a SID, nothing for a DTX silent hop, what VBR saved, retransmissions.  `n_ceil`
+    (int32 `[B]`) and `rate_state` (int32 `[B, rate.RC_WORDS]`; `rate.kbps(rate_state, frames)` on the host) are device views.  A `start`
+    or a resume resets a slot's row inside the graph (start rate, full bucket, counters 0), `reset` every row; a held or stopped slot
+    takes its reports but neither ages nor fills, reports n_ceil = its own n, and still pays for the NACKs it answers; `export` and a
+    resume carry none.  `fec_adapt`, `rtx` and VBR's `cap_kbps` work as without it.  `rate=None` captures exactly the graph without it."""
 
     def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, input_rate: int = BASE_RATE, fec_stages: int = 0,
                  dtx: Optional[dtx_def.DtxConfig] = None, header: bool = False, vbr: Optional[vbr_def.VbrConfig] = None,
-                 fec_adapt: Optional[report_def.FecAdaptConfig] = None, rtx: Optional[rtx_def.RtxConfig] = None):
+                 fec_adapt: Optional[report_def.FecAdaptConfig] = None, rtx: Optional[rtx_def.RtxConfig] = None,
+                 rate: Optional[rate_def.RateConfig] = None):
         # what the captured chain reads is set up first: GraphedHop's constructor captures it
         self.fec_stages = _fec_stages(fec_stages, n)
         if fec_adapt is not None:
@@ -698,6 +714,14 @@ class GraphedEncodeHop(GraphedHop):
             if not sessions or not self.header:
                 raise ValueError("GraphedEncodeHop(rtx=...) needs sessions=True and header=True")
         self.rtx = rtx
+        if rate is not None:
+            if not isinstance(rate, rate_def.RateConfig):
+                raise ValueError(f"rate must be a rate.RateConfig or None, got {rate!r}")
+            if not sessions:
+                raise ValueError("GraphedEncodeHop(rate=...) needs sessions=True")
+            # ValueError: a min_kbps that does not pay for the floor of a hop, a max_kbps past the int32 rows
+            self._rate_bits = rate_def.bucket(rate, _whole_frames("GraphedEncodeHop(rate=...)", hop), self.fec_stages, self.header)
+        self.rate = rate
         self._nacks = {}                      # slot -> (word, bitmap) for the next hop
         self._nack_live = False               # the device NACK rows hold the previous hop's NACKs
         self.frames = hop // HOP
@@ -760,7 +784,17 @@ class GraphedEncodeHop(GraphedHop):
                         torch.zeros(batch, rtx_def.RX_WORDS, **ints))
             self._rx_out = torch.zeros(2, batch, rtx.per_hop, tb, dtype=torch.uint8, device=device)
             self._rx_nbytes = torch.zeros(2, batch, rtx.per_hop, **ints)
-        self._scratch = [t for t in (self._prev, self._run, self._ctr, self._credit, self._fa) if t is not None]
+        self._rc = self._n_ceil = None
+        if rate is not None:
+            # per slot: the rate row (rate.RC_*, updated in place by hilc_rate_ceiling and hilc_rate_charge once per hop) and its
+            # ceiling; cleared = the row zero but for the start rate and a full bucket, the ceiling n
+            rate_q8, full = 256 * self._rate_bits.start_bits, rate.burst_hops * self._rate_bits.start_bits
+            self._rc = torch.zeros(batch, rate_def.RC_WORDS, dtype=torch.int32, device=device)
+            self._rc[:, rate_def.RC_RATE_Q8], self._rc[:, rate_def.RC_CREDIT] = rate_q8, full
+            self._n_ceil = torch.full((batch,), int(n), dtype=torch.int32, device=device)
+            self._scratch_fill += [(self._rc[:, rate_def.RC_RATE_Q8], rate_q8), (self._rc[:, rate_def.RC_CREDIT], full),
+                                   (self._n_ceil, int(n))]
+        self._scratch = [t for t in (self._prev, self._run, self._ctr, self._credit, self._fa, self._rc) if t is not None]
         if rtx is not None:
             self._scratch += [*self._rx, self._rx_out, self._rx_nbytes]
         super().__init__(model, batch, hop_in, n, device, warmup, 1, sessions, max_loads_per_hop)
@@ -789,8 +823,17 @@ class GraphedEncodeHop(GraphedHop):
         with ops.sched_workspace(self.sched[0]):
             with engine.spectra_side_stream(self.spec_side[0]):
                 z, _ = m.encoder(x, *src.codec_enc, cache_out=dst.codec_enc)
+            if self.rate is not None:
+                # in front of the quantiser: hilc_fec_adapt (it reads nothing the quantiser writes) so that the ceiling sees this hop's
+                # switch, then the ceiling, which stands in for the per-stream n from here on
+                if self.fec_adapt is not None:
+                    ops.fec_adapt(self._prev[p], self._fa, self._fec_on, self.fec_stages, self.frames, self.fec_adapt,
+                                  self.stage.row["report"], action, hold)
+                ops.rate_ceiling(self._rc, self._n_ceil, self.n, self.frames, self.fec_stages, self.header, self.rate,
+                                 self.stage.row["report"], action, hold, n_clip, self._prev[p] if self.fec_stages else None)
+                n_clip = self._n_ceil
             idx = m.quantizer(z, self.n, n_clip=n_clip)
-        if self.fec_adapt is not None:
+        if self.fec_adapt is not None and self.rate is None:
             # ahead of the packer (and of VBR): a slot whose switch is off loses the valid word of the row the packer reads
             ops.fec_adapt(self._prev[p], self._fa, self._fec_on, self.fec_stages, self.frames, self.fec_adapt, self.stage.row["report"],
                           action, hold)
@@ -818,6 +861,9 @@ class GraphedEncodeHop(GraphedHop):
             # the graph's last launch: this hop's headed packets enter the history, this hop's NACKs are answered from it
             ops.rtx_step(packets, nbytes, *self._rx, self._rx_out[p], self._rx_nbytes[p], self.stage.row["nack_base"],
                          self.stage.row["nack_bitmap"], action)
+        if self.rate is not None:
+            # the graph's last launch: what the slot really sent on this hop, retransmissions included, leaves its bucket
+            ops.rate_charge(nbytes, self._rc, self.rate, self._rx_nbytes[p] if self.rtx is not None else None)
         out = (idx, packets, nbytes) if kind is None else (idx, packets, nbytes, kind)
         return out if n_eff is None else out + (n_eff, distortion)
 
@@ -851,6 +897,22 @@ class GraphedEncodeHop(GraphedHop):
         if self._fa is None:
             raise RuntimeError("GraphedEncodeHop.fec_adapt_state: construct with fec_adapt=FecAdaptConfig(...)")
         return self._fa
+
+    @property
+    def n_ceil(self) -> Tensor:
+        """int32 `[B]` device view: the most stages each slot's bucket paid for on the last hop (rate only; a held slot: its own n).
+        Read-only: written by the graph."""
+        if self._n_ceil is None:
+            raise RuntimeError("GraphedEncodeHop.n_ceil: construct with rate=RateConfig(...)")
+        return self._n_ceil
+
+    @property
+    def rate_state(self) -> Tensor:
+        """int32 `[B, rate.RC_WORDS]` device view: each slot's rate row after the last hop (rate.RC_*; rate only; `rate.kbps(row,
+        frames)` gives RC_RATE_Q8 in kbps).  Read-only: written by the graph."""
+        if self._rc is None:
+            raise RuntimeError("GraphedEncodeHop.rate_state: construct with rate=RateConfig(...)")
+        return self._rc
 
     def _need_rtx(self, what: str) -> None:
         if self.rtx is None:
@@ -909,26 +971,27 @@ class GraphedEncodeHop(GraphedHop):
 
     def _report_words(self, reports) -> dict:
         return self._feedback("reports", reports, wire.REPORT_BYTES, lambda blob: report_def.report_word(*wire.parse_report(blob)),
-                              self.fec_adapt is not None, "fec_adapt=FecAdaptConfig(...)")
+                              self.fec_adapt is not None or self.rate is not None, "fec_adapt=FecAdaptConfig(...) or rate=RateConfig(...)")
 
     def _nack_words(self, nacks) -> dict:
         return self._feedback("nacks", nacks, wire.NACK_BYTES, lambda blob: rtx_def.nack_words(*wire.parse_nack(blob)),
                               self.rtx is not None, "rtx=RtxConfig(...)")
 
     def _extra_rows(self) -> Tuple[str, ...]:
-        return ("report",) * (self.fec_adapt is not None) + ("nack_base", "nack_bitmap") * (self.rtx is not None)
+        return ("report",) * (self.fec_adapt is not None or self.rate is not None) + ("nack_base", "nack_bitmap") * (self.rtx is not None)
 
     def _extra_pending(self) -> bool:
         return bool(self._reports) or self._report_live or bool(self._nacks) or self._nack_live
 
     def _put_extra(self, st: ControlStage) -> None:
         """the report row: this hop's reports, 0 elsewhere (a report applies to exactly one hop, like an action: the upload after a
-        hop with reports clears them)"""
-        if self.fec_adapt is not None:
+        hop with reports clears them); with fec_adapt and rate, one report feeds both launches"""
+        if self.fec_adapt is not None or self.rate is not None:
             row = st.h_row["report"]
             row.zero_()
-            for slot, word in self._reports.items():
-                row[slot] = word
+            if self._reports:                 # one indexed write, as for the NACK rows below
+                slots = np.fromiter(self._reports, dtype=np.int64, count=len(self._reports))
+                row.numpy()[slots] = np.fromiter(self._reports.values(), dtype=np.int32, count=len(self._reports))
             self._report_live = bool(self._reports)
             self._reports = {}
         if self.rtx is not None:
@@ -948,7 +1011,7 @@ class GraphedEncodeHop(GraphedHop):
         super().reset(cache_enc, cache_dec)
 
     def step(self, x: Tensor, hold=None, reports=None, nacks=None) -> Tuple[Tensor, Tensor]:
-        """`reports` (fec_adapt only): (slots, blobs), this hop's receiver reports — A host ints, and a uint8 `[A, 3]` host tensor or a
+        """`reports` (fec_adapt or rate only): (slots, blobs), this hop's receiver reports — A host ints, and a uint8 `[A, 3]` host tensor or a
         sequence of 3-byte `bytes` (wire.pack_report).  `nacks` (rtx only): (slots, blobs) likewise, this hop's NACKs, 4 bytes each
         (wire.pack_nack)"""
         self._reports = self._report_words(reports)

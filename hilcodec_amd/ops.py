@@ -27,6 +27,7 @@ from ._lib import DownParams, PostParams, ResblockParams, Spec0Params, UpParams,
 from .dtx import LEVELS, state_words
 from .jitter import AD_WORDS, ST_WORDS
 from .report import FA_WORDS, RP_WORDS
+from .rate import RC_WORDS, bucket
 from .rtx import NK_WORDS, RX_WORDS
 from .resample import HOP
 from .wire import CONCEAL_CODES, NACK_BYTES, REPORT_BYTES, TRANSPORT_HEADER, packet_bytes
@@ -1211,6 +1212,40 @@ _register("rtx_step", "(Tensor packets, Tensor nbytes, Tensor? nack_base, Tensor
           "Tensor(b!) ring, Tensor(c!) rows, Tensor(d!) out, Tensor(e!) out_nbytes) -> ()", _rtx_step,
           lambda packets, nbytes, nack_base, nack_bitmap, action, tags, ring, rows, out, out_nbytes: None)
 
+# ======================================================================================================
+# report-driven rate control of the sender (graph_step.GraphedEncodeHop(rate=); definition: hilcodec_amd/rate.py; semantics:
+# include/hilcodec_amd.h)
+# ======================================================================================================
+def _rate_ceiling(report, action, hold, n_clip, prev, rows, n_ceil, frames, n, m, header, min_bits, max_bits, start_bits, high_q8, low_q8,
+                  increase_q8, burst_hops, timeout_hops):
+    B = n_ceil.numel()
+    if rows.shape != (B, RC_WORDS) or (prev is not None and prev.shape != (B, 1 + m * frames)):
+        raise RuntimeError(f"rate_ceiling: rows must be [{B}, {RC_WORDS}] and prev [{B}, {1 + m * frames}]")
+    _rows("rate_ceiling", B, report=report, action=action, hold=hold, n_clip=n_clip)
+    check(lib.hilc_rate_ceiling(_ptr(report, torch.int32), _ptr(action, torch.int32), _ptr(hold, torch.int32), _ptr(n_clip, torch.int32),
+                                _ptr(prev, torch.int32), _ptr(rows, torch.int32), _ptr(n_ceil, torch.int32), B, frames, n, m, int(header),
+                                min_bits, max_bits, start_bits, high_q8, low_q8, increase_q8, burst_hops, timeout_hops, _stream()),
+          "hilc_rate_ceiling")
+
+
+_register("rate_ceiling", "(Tensor? report, Tensor? action, Tensor? hold, Tensor? n_clip, Tensor? prev, Tensor(a!) rows, Tensor(b!) n_ceil, "
+          "int frames, int n, int m, bool header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, "
+          "int burst_hops, int timeout_hops) -> ()", _rate_ceiling,
+          lambda report, action, hold, n_clip, prev, rows, n_ceil, frames, n, m, header, min_bits, max_bits, start_bits, high_q8, low_q8,
+          increase_q8, burst_hops, timeout_hops: None)
+
+
+def _rate_charge(nbytes, rtx_nbytes, rows, burst_hops):
+    B = nbytes.numel()
+    if rows.shape != (B, RC_WORDS) or (rtx_nbytes is not None and (rtx_nbytes.dim() != 2 or rtx_nbytes.shape[0] != B)):
+        raise RuntimeError(f"rate_charge: rows must be [{B}, {RC_WORDS}] and rtx_nbytes [{B}, per_hop]")
+    check(lib.hilc_rate_charge(_ptr(nbytes, torch.int32), _ptr(rtx_nbytes, torch.int32), _ptr(rows, torch.int32), B,
+                               0 if rtx_nbytes is None else rtx_nbytes.shape[1], burst_hops, _stream()), "hilc_rate_charge")
+
+
+_register("rate_charge", "(Tensor nbytes, Tensor? rtx_nbytes, Tensor(a!) rows, int burst_hops) -> ()", _rate_charge,
+          lambda nbytes, rtx_nbytes, rows, burst_hops: None)
+
 _OPS = torch.ops.hilcodec
 
 
@@ -1903,3 +1938,25 @@ def rtx_step(packets: Tensor, nbytes: Tensor, tags: Tensor, ring: Tensor, rows: 
     neither) are copied to `out` (uint8 `[B, per_hop, row_bytes]`) with `out_nbytes` (int32 `[B, per_hop]`); `rows` (int32 `[B,
     rtx.RX_WORDS]`) count.  `action` (int32 `[B]`, optional): the session row, a start empties the slot's history."""
     _OPS.rtx_step(packets, nbytes, nack_base, nack_bitmap, action, tags, ring, rows, out, out_nbytes)
+
+
+def rate_ceiling(rows: Tensor, n_ceil: Tensor, n: int, frames: int, m: int, header: bool, cfg, report: Optional[Tensor] = None,
+                 action: Optional[Tensor] = None, hold: Optional[Tensor] = None, n_clip: Optional[Tensor] = None,
+                 prev: Optional[Tensor] = None) -> None:
+    """The rate-controlled sender's step in front of its quantiser (rate.RateModel.ceiling), in place: `rows` (int32 `[B, rate.RC_WORDS]`)
+    take this hop's `report` words (int32 `[B]`, report.report_word, 0: none; optional), each slot's rate moves and its bucket fills, and
+    `n_ceil` (int32 `[B]`) is the most stages the bucket pays for.  `cfg`: the rate.RateConfig of a sender with `n` stages, `frames`
+    frames, `m` redundant stages and the transport header or not (rate.bucket checks it); `action` / `hold` (int32 `[B]`, optional): the
+    session rows; `n_clip` (int32 `[B]`, optional): each slot's own ceiling; `prev` (int32 `[B, 1 + m frames]`, optional, read only): the
+    previous-codes rows the packer reads on this hop."""
+    bits = bucket(cfg, frames, m, header)
+    _OPS.rate_ceiling(report, action, hold, n_clip, prev, rows, n_ceil, int(frames), int(n), int(m), bool(header), bits.min_bits,
+                      bits.max_bits, bits.start_bits, int(cfg.high_q8), int(cfg.low_q8), int(cfg.increase_q8), int(cfg.burst_hops),
+                      int(cfg.timeout_hops))
+
+
+def rate_charge(nbytes: Tensor, rows: Tensor, cfg, rtx_nbytes: Optional[Tensor] = None) -> None:
+    """The rate-controlled sender's last step (rate.RateModel.charge), in place: the credit of `rows` (int32 `[B, rate.RC_WORDS]`) pays
+    for this hop's `nbytes` (int32 `[B]`, the packets as sent) and `rtx_nbytes` (int32 `[B, per_hop]`, optional: its retransmissions),
+    down to a debt of cfg.burst_hops hops of the slot's rate."""
+    _OPS.rate_charge(nbytes, rtx_nbytes, rows, int(cfg.burst_hops))
