@@ -9,5 +9,9 @@ from .resample import Resampler, resample  # noqa: F401
 # the room mixer's eager one-call form and its configuration (the graphed form: graph_step.GraphedDecodeHop(mix=MixConfig(...)))
 from .mixer import MixConfig  # noqa: F401
 from .ops import room_mix as mix_rooms  # noqa: F401
+# the selective forwarding hop: its definition (import it by name), its configuration and the hop object
+from . import forward  # noqa: F401
+from .forward import ForwardConfig  # noqa: F401
+from .graph_step import GraphedForwardHop  # noqa: F401
 
-__all__ = ["HILCodec", "Resampler", "resample", "MixConfig", "mix_rooms"]
+__all__ = ["HILCodec", "Resampler", "resample", "MixConfig", "mix_rooms", "forward", "ForwardConfig", "GraphedForwardHop"]

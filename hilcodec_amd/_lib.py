@@ -91,6 +91,8 @@ SIGNATURES = {
     "hilc_rtx_step": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "hilc_rate_ceiling": [_p, _p, _p, _p, _p, _p, _p] + [_i] * 13 + [_p],
     "hilc_rate_charge": [_p, _p, _p, _i, _i, _i, _p],
+    "hilc_forward_classify": [_p, _p, _i, _p, _p, _p, _p] + [_i] * 7 + [_p],
+    "hilc_forward_route": [_p, _i] + [_p] * 11 + [_i] * 8 + [_p],
 }
 
 ABI_VERSION = 16

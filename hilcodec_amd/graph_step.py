@@ -24,6 +24,7 @@ from torch import Tensor
 
 from . import dtx as dtx_def
 from . import engine, ops, wire
+from . import forward as forward_def
 from . import rate as rate_def
 from . import report as report_def
 from . import rtx as rtx_def
@@ -1573,3 +1574,171 @@ class GraphedDecodeHop(_Hop):
         """the current 30 decoder caches of slot `slot` as B = 1 device tensors (one gather launch; a stopped slot: its caches
         when it stopped; 31 with `output_rate`, the resampler's history last)"""
         return super().export(slot)[1]
+
+
+class GraphedForwardHop:
+    """A selective forwarding hop (hilcodec_amd/forward.py: the rules, bit for bit): a conference server for `batch` participant slots
+    that routes packets and cuts them to each listener's number of stages without decoding.  It holds no model and no codec state: each
+    slot is a sender (its arrivals are checked and its activity kept) and a listener (it is sent the packets of its room's `cfg.fanout`
+    most active other members, each cut to its `layers` stages).  The senders are GraphedEncodeHop(header=True) of `frames` frames and
+    `n` stages, `fec_stages` = their m, `cng_order` = the K of their SIDs (None: a SID is malformed); a listener plays the rows of route
+    j into slot j of a GraphedDecodeHop(jitter=, mix=), after `start(j)` where `new_routes` is set.
+    A hop is one upload (the stage's rows — action, room, layers — the offsets and the arrival records, staged as
+    GraphedDecodeHop.play stages them) and the replay of a graph of two launches (hilc_forward_classify, hilc_forward_route); two
+    graphs are captured and replayed alternately, so what `forward` returns stays valid for one further call.
+    `cfg`: the forward.ForwardConfig; `max_arrivals`: the most arrivals of one hop (default 2 B)."""
+
+    _capture_pair, _replay = _Hop._capture_pair, _Hop._replay
+
+    def __init__(self, batch: int, frames: int, n: int, device: torch.device, fec_stages: int = 0, cng_order: Optional[int] = None,
+                 cfg: forward_def.ForwardConfig = forward_def.ForwardConfig(), max_arrivals: Optional[int] = None, warmup: int = 2):
+        if not isinstance(cfg, forward_def.ForwardConfig):
+            raise ValueError(f"GraphedForwardHop: cfg must be a forward.ForwardConfig, got {cfg!r}")
+        B = self.batch = _int_arg("batch", batch, 1)
+        self.frames, self.n, self.device, self.cfg = _int_arg("frames", frames, 1), _int_arg("n", n, 1, 31), device, cfg
+        self.fec_stages = _fec_stages(fec_stages, self.n)
+        self.cng_order = None if cng_order is None else _int_arg("cng_order", cng_order, 0, dtx_def.MAX_ORDER)
+        self.max_arrivals = _int_arg("max_arrivals", 2 * B if max_arrivals is None else max_arrivals, 1)
+        self.tstride = wire.transport_bytes(self.n, self.fec_stages, self.frames)
+        if self.cng_order is not None:
+            dtx_def.check_order(self.cng_order, self.tstride - wire.TRANSPORT_HEADER, "GraphedForwardHop(cng_order=...)")
+        aw = 1 + (self.tstride + 3) // 4                   # an arrival record: byte count, then the headed packet
+        # ONE device buffer, captured by address, uploaded up to the last arrival used: the action, room and layers rows, the CSR
+        # offsets of the arrivals [B + 1], the arrival records grouped by slot
+        st = self.stage = ControlStage(B, ("action", "room", "layers"), B + 1 + self.max_arrivals * aw, 0, 0, device)
+        self._arr_off = st.payload_off + B + 1
+        self.offsets, self._h_offsets = st.payload[:B + 1].view(torch.int32), st.h_payload[:B + 1].view(torch.int32)
+        self.arrivals = st.payload[B + 1:].view(torch.int32).view(self.max_arrivals, aw)
+        self._h_arrivals = st.h_payload[B + 1:].view(torch.int32).view(self.max_arrivals, aw)
+        F, P = cfg.fanout, cfg.burst
+        i32 = dict(dtype=torch.int32, device=device)
+        self._sd = torch.zeros(B, forward_def.SD_WORDS, **i32)
+        self._lr = torch.zeros(B, forward_def.LR_WORDS, **i32)
+        self._pick, self._pick_count = torch.zeros(B, P, **i32), torch.zeros(B, **i32)
+        self._routes, self._new_routes = torch.zeros(B, F, **i32), torch.zeros(B, F, **i32)
+        self._out = [torch.zeros(B, F, P, self.tstride, dtype=torch.uint8, device=device) for _ in (0, 1)]
+        self._out_nbytes = [torch.zeros(B, F, P, **i32) for _ in (0, 1)]
+        self._joined = set()                  # the slots joined since the last hop
+        self._action_live = False             # the mirror's action row is not all zero
+        self.parity = 0
+        self.graphs, self.outs = self._capture_pair(self._hop, warmup)
+
+    def _hop(self, p: int) -> Tuple[Tensor, Tensor]:
+        st, args = self.stage, (self.cfg, self.n, self.frames, self.fec_stages, self.cng_order)
+        ops.forward_classify(self.arrivals, self.offsets, self._sd, self._pick, self._pick_count, *args, action=st.row["action"])
+        ops.forward_route(self.arrivals, st.row["room"], st.row["layers"], self._sd, self._pick, self._pick_count, self._routes,
+                          self._new_routes, self._lr, self._out[p], self._out_nbytes[p], *args, action=st.row["action"])
+        return self._out[p], self._out_nbytes[p]
+
+    def _zero(self) -> None:
+        """every slot as constructed: in no room, n layers, no route, every row and output zero"""
+        st = self.stage
+        st.wait()
+        st.host.zero_()
+        st.h_row["room"].fill_(-1)
+        st.h_row["layers"].fill_(self.n)
+        st.dev.copy_(st.host)
+        for t in (self._sd, self._lr, self._pick, self._pick_count, self._new_routes, *self._out, *self._out_nbytes):
+            t.zero_()
+        self._routes.fill_(-1)
+
+    def _slot(self, slot) -> int:
+        s = int(slot)
+        if not 0 <= s < self.batch:
+            raise IndexError(f"slot {slot} outside [0, {self.batch})")
+        return s
+
+    def join(self, slot: int, room: int) -> None:
+        """from the next hop on, slot `slot` is a new participant of room `room` (an int in [0, B): ValueError), and of no other: its
+        sender and listener rows are cleared on that hop, and every route it owned is freed"""
+        s, r = self._slot(slot), _int_arg("room", room, 0, self.batch - 1)
+        self.stage.wait()                     # the previous upload's copy has left the pinned rows
+        self.stage.h_row["room"][s] = r
+        self._joined.add(s)
+
+    def leave(self, slot: int) -> None:
+        """from the next hop on, slot `slot` is in no room: it is sent nothing and nobody is sent its packets"""
+        s = self._slot(slot)
+        self.stage.wait()
+        self.stage.h_row["room"][s] = -1
+
+    def set_layers(self, slot: int, L: int) -> None:
+        """from the next hop on, the packets sent to slot `slot` have at most `L` stages (an int in [1, n]: ValueError; as constructed: n)"""
+        s, v = self._slot(slot), _int_arg("L", L, 1, self.n)
+        self.stage.wait()
+        self.stage.h_row["layers"][s] = v
+
+    @property
+    def rooms(self) -> Tuple[int, ...]:
+        """each slot's room as the host has it (-1: none)"""
+        return tuple(self.stage.h_row["room"].tolist())
+
+    @property
+    def layers(self) -> Tuple[int, ...]:
+        """each slot's layer count as the host has it"""
+        return tuple(self.stage.h_row["layers"].tolist())
+
+    @property
+    def routes(self) -> Tensor:
+        """int32 `[B, fanout]` device view: the owner of each listener's routes after the last hop (-1: free).  Read-only: written by
+        the graph."""
+        return self._routes
+
+    @property
+    def new_routes(self) -> Tensor:
+        """int32 `[B, fanout]` device view: 1 where a route's owner on the last hop is another than before it (the listener restarts
+        that route's decoder slot).  Read-only: written by the graph, overwritten by the next call."""
+        return self._new_routes
+
+    @property
+    def sender_state(self) -> Tensor:
+        """int32 `[B, forward.SD_WORDS]` device view: each slot's sender row after the last hop (forward.SD_*).  Read-only: written by
+        the graph."""
+        return self._sd
+
+    @property
+    def listener_state(self) -> Tensor:
+        """int32 `[B, forward.LR_WORDS]` device view: each slot's listener row after the last hop (forward.LR_*).  Read-only: written by
+        the graph."""
+        return self._lr
+
+    def forward(self, slots, packets: Tensor, nbytes) -> Tuple[Tensor, Tensor]:
+        """one hop: this hop's arrivals, in push order — `slots` and `nbytes` (A host ints), `packets` uint8 `[A,
+        wire.transport_bytes(n, m, frames)]` (host or device), 0 <= A <= max_arrivals.  Returns (out uint8 `[B, fanout, burst, tb]`,
+        out_nbytes int32 `[B, fanout, burst]`): row (b, j, k) is the k-th packet of this hop for listener b's route j, cut to its layers
+        (0 bytes: none); static views that the next-but-one call overwrites."""
+        for name, v in (("slots", slots), ("nbytes", nbytes)):
+            if isinstance(v, Tensor) and v.is_cuda:
+                raise ValueError(f"forward: {name} must be host ints, not a device tensor")
+        sl = np.asarray(slots.tolist() if isinstance(slots, Tensor) else slots, dtype=np.int64).reshape(-1)
+        nb = np.asarray(nbytes.tolist() if isinstance(nbytes, Tensor) else nbytes, dtype=np.int64).reshape(-1)
+        A, B = len(sl), self.batch
+        if A > self.max_arrivals:
+            raise ValueError(f"forward: {A} arrivals, at most max_arrivals = {self.max_arrivals}")
+        if len(nb) != A:
+            raise ValueError(f"forward: {A} slots but {len(nb)} byte counts")
+        if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or tuple(packets.shape) != (A, self.tstride):
+            raise ValueError(f"forward: packets must be uint8 [{A}, {self.tstride}]")
+        if A and (sl.min() < 0 or sl.max() >= B):
+            raise IndexError(f"forward: a slot outside [0, {B})")
+        order = np.argsort(sl, kind="stable")
+        st = self.stage
+        st.wait()
+        if self._action_live or self._joined:
+            _mark(st.h_row["action"], self._joined)
+            self._action_live = bool(self._joined)
+            self._joined = set()
+        offs = self._h_offsets.numpy()
+        offs[0] = 0
+        offs[1:] = np.cumsum(np.bincount(sl, minlength=B))
+        if A:
+            self._h_arrivals[:A, 0].copy_(torch.from_numpy(np.clip(nb[order], -1, 1 << 20).astype(np.int32)))
+        bytes_of = lambda t: t.view(torch.uint8)[:, 4:4 + self.tstride]
+        if A and not packets.is_cuda:
+            bytes_of(self._h_arrivals[:A]).copy_(packets[torch.from_numpy(order)])
+        st.send(self._arr_off + A * self.arrivals.shape[1])
+        if A and packets.is_cuda:
+            rows = packets if np.array_equal(order, np.arange(A)) else packets[torch.from_numpy(order).to(self.device)]
+            bytes_of(self.arrivals[:A]).copy_(rows)
+        st.finish()
+        return self._replay()

@@ -25,6 +25,7 @@ from torch import Tensor
 
 from ._lib import DownParams, PostParams, ResblockParams, Spec0Params, UpParams, check, lib
 from .dtx import LEVELS, state_words
+from .forward import LR_WORDS, SD_WORDS
 from .jitter import AD_WORDS, ST_WORDS
 from .report import FA_WORDS, RP_WORDS
 from .rate import RC_WORDS, bucket
@@ -1246,6 +1247,58 @@ def _rate_charge(nbytes, rtx_nbytes, rows, burst_hops):
 _register("rate_charge", "(Tensor nbytes, Tensor? rtx_nbytes, Tensor(a!) rows, int burst_hops) -> ()", _rate_charge,
           lambda nbytes, rtx_nbytes, rows, burst_hops: None)
 
+# ======================================================================================================
+# selective forwarding hop (graph_step.GraphedForwardHop; definition: hilcodec_amd/forward.py; semantics: include/hilcodec_amd.h)
+# ======================================================================================================
+def _forward_arrivals(op, arrivals, n, m, frames):
+    """the arrival records of a forwarding op checked: int32 [max_arrivals, 1 + ceil(tb / 4)]; returns tb"""
+    tb = TRANSPORT_HEADER + packet_bytes(n + m, frames)
+    if arrivals.dim() != 2 or arrivals.shape[1] != 1 + (tb + 3) // 4:
+        raise RuntimeError(f"{op}: arrivals must be int32 [max_arrivals, {1 + (tb + 3) // 4}] for n = {n}, m = {m}, frames = {frames}")
+    return tb
+
+
+def _forward_classify(arrivals, offsets, action, rows, pick, pick_count, n, m, frames, order, burst, hang_hops):
+    B = pick_count.numel()
+    _forward_arrivals("forward_classify", arrivals, n, m, frames)
+    if offsets.shape != (B + 1,) or rows.shape != (B, SD_WORDS) or pick.shape != (B, burst):
+        raise RuntimeError(f"forward_classify: offsets must be [{B + 1}], rows [{B}, {SD_WORDS}] and pick [{B}, {burst}]")
+    _rows("forward_classify", B, action=action)
+    check(lib.hilc_forward_classify(_ptr(arrivals, torch.int32), _ptr(offsets, torch.int32), arrivals.shape[0], _ptr(action, torch.int32),
+                                    _ptr(rows, torch.int32), _ptr(pick, torch.int32), _ptr(pick_count, torch.int32), B, frames, n, m,
+                                    order, burst, hang_hops, _stream()), "hilc_forward_classify")
+
+
+_register("forward_classify", "(Tensor arrivals, Tensor offsets, Tensor? action, Tensor(a!) rows, Tensor(b!) pick, Tensor(c!) pick_count, "
+          "int n, int m, int frames, int order, int burst, int hang_hops) -> ()", _forward_classify,
+          lambda arrivals, offsets, action, rows, pick, pick_count, n, m, frames, order, burst, hang_hops: None)
+
+
+def _forward_route(arrivals, action, room, layers, sender_rows, pick, pick_count, routes, new_routes, rows, out, out_nbytes, n, m, frames,
+                   order, keep_fec):
+    B = room.numel()
+    tb = _forward_arrivals("forward_route", arrivals, n, m, frames)
+    if out.dim() != 4 or out.shape[0] != B or out.shape[3] != tb:
+        raise RuntimeError(f"forward_route: out must be uint8 [{B}, fanout, burst, {tb}]")
+    F, P = out.shape[1], out.shape[2]
+    if sender_rows.shape != (B, SD_WORDS) or pick.shape != (B, P) or routes.shape != (B, F) or new_routes.shape != (B, F) or \
+            rows.shape != (B, LR_WORDS) or out_nbytes.shape != (B, F, P):
+        raise RuntimeError(f"forward_route: sender_rows must be [{B}, {SD_WORDS}], pick [{B}, {P}], routes and new_routes [{B}, {F}], rows "
+                           f"[{B}, {LR_WORDS}] and out_nbytes [{B}, {F}, {P}]")
+    _rows("forward_route", B, action=action, layers=layers, pick_count=pick_count)
+    check(lib.hilc_forward_route(_ptr(arrivals, torch.int32), arrivals.shape[0], _ptr(action, torch.int32), _ptr(room, torch.int32),
+                                 _ptr(layers, torch.int32), _ptr(sender_rows, torch.int32), _ptr(pick, torch.int32),
+                                 _ptr(pick_count, torch.int32), _ptr(routes, torch.int32), _ptr(new_routes, torch.int32),
+                                 _ptr(rows, torch.int32), _ptr(out, torch.uint8), _ptr(out_nbytes, torch.int32), B, frames, n, m, order, F,
+                                 P, int(keep_fec), _stream()), "hilc_forward_route")
+
+
+_register("forward_route", "(Tensor arrivals, Tensor? action, Tensor room, Tensor layers, Tensor sender_rows, Tensor pick, Tensor pick_count, "
+          "Tensor(a!) routes, Tensor(b!) new_routes, Tensor(c!) rows, Tensor(d!) out, Tensor(e!) out_nbytes, int n, int m, int frames, "
+          "int order, bool keep_fec) -> ()", _forward_route,
+          lambda arrivals, action, room, layers, sender_rows, pick, pick_count, routes, new_routes, rows, out, out_nbytes, n, m, frames,
+          order, keep_fec: None)
+
 _OPS = torch.ops.hilcodec
 
 
@@ -1960,3 +2013,27 @@ def rate_charge(nbytes: Tensor, rows: Tensor, cfg, rtx_nbytes: Optional[Tensor] 
     for this hop's `nbytes` (int32 `[B]`, the packets as sent) and `rtx_nbytes` (int32 `[B, per_hop]`, optional: its retransmissions),
     down to a debt of cfg.burst_hops hops of the slot's rate."""
     _OPS.rate_charge(nbytes, rtx_nbytes, rows, int(cfg.burst_hops))
+
+
+def forward_classify(arrivals: Tensor, offsets: Tensor, rows: Tensor, pick: Tensor, pick_count: Tensor, cfg, n: int, frames: int,
+                     m: int = 0, order: Optional[int] = None, action: Optional[Tensor] = None) -> None:
+    """The forwarding hop's first launch (forward.SenderModel), in place: one hop's `arrivals` (int32 `[max_arrivals, 1 + ceil(tb / 4)]`
+    records grouped by slot, tb = wire.transport_bytes(n, m, frames)) and `offsets` (int32 `[B + 1]`), as GraphedDecodeHop.play stages
+    them -> each slot's sender row (`rows`, int32 `[B, forward.SD_WORDS]`), the record indices of its first cfg.burst valid arrivals
+    (`pick`, int32 `[B, burst]`, -1 behind `pick_count`, int32 `[B]`).  `cfg`: the forward.ForwardConfig; `order`: the comfort-noise
+    order of the SIDs accepted (None: a SID is malformed); `action` (int32 `[B]`, optional): non-zero clears the slot's row."""
+    _OPS.forward_classify(arrivals, offsets, action, rows, pick, pick_count, int(n), int(m), int(frames), -1 if order is None else int(order),
+                          int(cfg.burst), int(cfg.hang_hops))
+
+
+def forward_route(arrivals: Tensor, room: Tensor, layers: Tensor, sender_rows: Tensor, pick: Tensor, pick_count: Tensor, routes: Tensor,
+                  new_routes: Tensor, rows: Tensor, out: Tensor, out_nbytes: Tensor, cfg, n: int, frames: int, m: int = 0,
+                  order: Optional[int] = None, action: Optional[Tensor] = None) -> None:
+    """The forwarding hop's second launch (forward.ListenerModel), in place: with `sender_rows`, `pick` and `pick_count` as
+    forward_classify left them on this hop, `room` and `layers` (int32 `[B]` each) -> each listener's `routes` (int32 `[B, fanout]`: the
+    owners, -1 when free), `new_routes` (1 where a route's owner changed), listener row (`rows`, int32 `[B, forward.LR_WORDS]`) and the
+    forwarded packets `out` (uint8 `[B, fanout, burst, tb]`, each cut to the listener's layers: forward.trim_packet) with `out_nbytes`
+    (int32 `[B, fanout, burst]`, 0: an empty row).  fanout and burst are read from `out`'s shape; `cfg.keep_fec` decides whether a
+    redundant section is kept."""
+    _OPS.forward_route(arrivals, action, room, layers, sender_rows, pick, pick_count, routes, new_routes, rows, out, out_nbytes, int(n), int(m),
+                       int(frames), -1 if order is None else int(order), bool(cfg.keep_fec))

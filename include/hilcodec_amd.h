@@ -37,7 +37,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream); and the selective forwarding hop int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick, int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream) and int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers, const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -572,6 +572,27 @@ int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const fl
 #define HILC_RATE_RC_WORDS 12
 #define HILC_RATE_MAX_RATE_BITS (1 << 22)
 
+/* selective forwarding (hilcodec_amd/forward.py).  Sender row of a slot, SD_WORDS words: SD_HANG (the hops it stays active, 0: not
+ * active), SD_SINCE (the hops it has been active, at most 65535), then the counters SD_CODES, SD_SIDS, SD_MALFORMED, SD_OVERFLOW.
+ * Listener row of a slot, LR_WORDS words: the counters LR_PACKETS, LR_BYTES, LR_TRIMMED, LR_SWITCHES.  A listener has at most
+ * MAX_FANOUT routes, a sender at most MAX_BURST forwarded arrivals per hop, and stays active at most MAX_HANG_HOPS hops. */
+#define HILC_FORWARD_SD_HANG 0
+#define HILC_FORWARD_SD_SINCE 1
+#define HILC_FORWARD_SD_CODES 2
+#define HILC_FORWARD_SD_SIDS 3
+#define HILC_FORWARD_SD_MALFORMED 4
+#define HILC_FORWARD_SD_OVERFLOW 5
+#define HILC_FORWARD_SD_WORDS 6
+#define HILC_FORWARD_LR_PACKETS 0
+#define HILC_FORWARD_LR_BYTES 1
+#define HILC_FORWARD_LR_TRIMMED 2
+#define HILC_FORWARD_LR_SWITCHES 3
+#define HILC_FORWARD_LR_WORDS 4
+#define HILC_FORWARD_MAX_FANOUT 8
+#define HILC_FORWARD_MAX_BURST 4
+#define HILC_FORWARD_MAX_HANG_HOPS 255
+#define HILC_FORWARD_MAX_SINCE 65535
+
 /* ---- per-stream session state of a streaming hop (ABI 16) ------------------------------------------------------------------
  * Layout: the caches of `streams` streams live in ONE fp32 block (hilcodec_amd/graph_step.py StateBlock): slice k (one
  * `[streams][C][L]` cache tensor, k < nslices, in the reference's order: 22 encoder then 30 decoder caches) starts at
@@ -882,6 +903,40 @@ int hilc_rate_ceiling(const int* report, const int* action, const int* hold, con
                       int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8,
                       int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream);
 int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream);
+
+/* ---- selective forwarding hop (additive under ABI 16) -------------------------------------------------------------------------------
+ * Two entry points added WITHOUT a version bump, as the entry points above.  The definition, bit for bit, is hilcodec_amd/forward.py.
+ * Both read one hop's arrivals in the form of hilc_jitter_step: arrivals int32 [max_arrivals][1 + ceil(tb / 4)] (word 0 the byte count,
+ * then the headed packet, tb = HILC_WIRE_TRANSPORT_HEADER + packet_bytes(n_max + m, T)), grouped by slot; offsets int32 [B + 1] (slot b's
+ * records are [offsets[b], offsets[b + 1]), clamped to [0, max_arrivals]); action optional int32 [B] (non-zero: the slot was joined on
+ * this hop).  order: the comfort-noise order of the SIDs accepted, -1 for none.
+ * hilc_forward_classify: the hop's first launch.  rows int32 [B][HILC_FORWARD_SD_WORDS] (in place: HILC_FORWARD_SD_*); pick int32
+ * [B][burst] and pick_count int32 [B] (every element written).  Per slot: action[b] != 0 clears the row; each arrival for which
+ * wire.parse_transport raises counts SD_MALFORMED; each other one SD_CODES or SD_SIDS, the first `burst` of them go to pick[b][k] (their
+ * record index, -1 behind pick_count[b]), each further one counts SD_OVERFLOW; SD_HANG = hang_hops + 1 when a valid codes arrival was
+ * seen, else max(SD_HANG - 1, 0); SD_SINCE = min(SD_SINCE + 1, HILC_FORWARD_MAX_SINCE) while SD_HANG > 0, else 0.
+ * hilc_forward_route: the hop's second launch, after hilc_forward_classify has finished for every slot.  room int32 [B] (-1: none);
+ * layers int32 [B] (clamped to [1, n_max]); sender_rows, pick, pick_count as the first launch left them (read only); routes int32
+ * [B][fanout] (in place: each route's owner, -1 when free), new_routes int32 [B][fanout], rows int32 [B][HILC_FORWARD_LR_WORDS] (in
+ * place: HILC_FORWARD_LR_*), out uint8 [B][fanout][burst][tb] and out_nbytes int32 [B][fanout][burst]: every element written.  Per
+ * listener b: action[b] != 0 frees its routes and clears its row; the slots t != b with room[t] == room[b] >= 0 and SD_HANG > 0, in
+ * (SD_HANG descending, SD_SINCE descending, slot ascending) order, the first `fanout` of them are selected; a route whose owner is not
+ * selected or has action != 0 is freed, the selected slots without a route take the free routes (ascending slot, lowest free route
+ * first); new_routes[b][j] = 1 where route j has an owner other than before this hop (LR_SWITCHES counts them); row (b, j, k), k <
+ * pick_count[owner], is arrival pick[owner][k] cut to min(n, layers[b]) stages — a SID byte for byte; else header byte 2 rewritten,
+ * the primary's first stages, then the redundant section when it has one, keep_fec != 0 and min(n, layers[b]) >= m, the pad bits zero —
+ * zero past its length, its byte count beside it; every other row zero with count 0.  LR_PACKETS, LR_BYTES count the rows written,
+ * LR_TRIMMED those whose n was cut.
+ * Both: NULL pointers (action excepted): HILC_ERR_NULL; B, T >= 1, max_arrivals >= 0, tb < 2^15 (else HILC_ERR_SHAPE); 1 <= n_max <= 31,
+ * 0 <= m <= n_max, n_max + m <= HILC_WIRE_MAX_STAGES, -1 <= order <= HILC_DTX_MAX_ORDER, 1 <= burst <= HILC_FORWARD_MAX_BURST, 0 <=
+ * hang_hops <= HILC_FORWARD_MAX_HANG_HOPS, 1 <= fanout <= HILC_FORWARD_MAX_FANOUT (else HILC_ERR_RANGE).  One wave per slot, integer only,
+ * no LDS, no atomics. */
+int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick,
+                          int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream);
+int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers,
+                       const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows,
+                       uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec,
+                       void* stream);
 
 #ifdef __cplusplus
 }
