@@ -16,6 +16,7 @@ log-magnitude spectra of the un-fused SpecBlocks (n_fft 256 / 512 / 1024 at one 
 waveform only) sit on a second branch beside the first encoder stages (`engine._early_spectra`)."""
 from __future__ import annotations
 
+import gc
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -32,7 +33,8 @@ from . import vbr as vbr_def
 from .jitter import AD_WORDS, ST_WORDS, JitterConfig
 from .mixer import MixConfig
 from .resample import BASE_RATE, HOP, design, device_taps, hop_samples
-from .sessions import HOLD_SID, HOLD_SILENT, SessionQueue, stage_layout, stage_starts
+from .sessions import (HOLD_SID, HOLD_SILENT, ONE_HOP_ROWS, Arrivals, SessionQueue, arrival_bytes, arrival_region_words, arrival_width,
+                       check_arrivals, put_arrivals, stage_layout, stage_starts)
 
 
 def state_layout(model, batch: int, side: str = "both", history: int = 0) -> ops.StateLayout:
@@ -75,8 +77,21 @@ def _fec_stages(fec_stages, n: int) -> int:
     return m
 
 
+def _config_arg(name: str, value, cls):
+    """an option that must be None or an instance of the config class `cls`: ValueError otherwise"""
+    if value is not None and not isinstance(value, cls):
+        raise ValueError(f"{name} must be a {cls.__module__.rsplit('.', 1)[-1]}.{cls.__name__} or None, got {value!r}")
+    return value
+
+
+def _needs(who: str, have, what: str) -> None:
+    """the option `who` (as a constructor call shows it) works only with `what`: ValueError unless `have`"""
+    if not have:
+        raise ValueError(f"{who} needs {what}")
+
+
 def _mark(row: Tensor, slots) -> None:
-    """a pinned int32 control row: 1 at `slots`, 0 elsewhere"""
+    """a pinned int32 control row that is not a one-hop row (hold, lost, fec): 1 at `slots`, 0 elsewhere"""
     row.zero_()
     if slots:
         row[torch.tensor(sorted(slots), dtype=torch.long)] = 1
@@ -120,9 +135,18 @@ class ControlStage:
     payload | staged records (sessions.stage_layout), so that what a hop needs goes up in one copy.  `row[name]` / `h_row[name]` are
     the `[B]` int32 rows on the device / in the mirror, `payload` / `h_payload` and `records` / `h_records` the two regions.
     A hop's upload is: `wait()`, write the mirror (`put_starts` for the queued starts), `send(words)`, `finish(...)`.
-    `sent_words` / `sent_record_words`: the words of the last upload's pinned copy / of its host records' own copy."""
+    `sent_words` / `sent_record_words`: the words of the last upload's pinned copy / of its host records' own copy.
+    The rows among sessions.ONE_HOP_ROWS apply to exactly one hop: they are written with `put_one_hop`, and `one_hop_live` says
+    whether one of them still holds entries on the device, so that the next upload has to clear it.
+    `arrivals` = (max_arrivals, row_bytes): the payload is an arrival region (sessions.arrival_region_words) — `offsets` /
+    `h_offsets` int32 `[B + 1]` and `arrivals` / `h_arrivals` int32 `[max_arrivals, arrival_width]` — which `send_arrivals` sends."""
 
-    def __init__(self, batch: int, rows: Sequence[str], payload_words: int, loads: int, record_len: int, device: torch.device):
+    def __init__(self, batch: int, rows: Sequence[str], payload_words: int, loads: int, record_len: int, device: torch.device,
+                 arrivals: Optional[Tuple[int, int]] = None):
+        if arrivals is not None:
+            if payload_words:
+                raise ValueError("ControlStage: the arrival region is the whole payload, payload_words must be 0 with arrivals")
+            payload_words = arrival_region_words(batch, *arrivals)
         self.row_off, self.payload_off, self.rec_off, total = stage_layout(batch, rows, payload_words, loads, record_len)
         self.device = device
         self.dev = torch.zeros(total, device=device)
@@ -134,21 +158,53 @@ class ControlStage:
         self.uploaded = torch.cuda.Event()
         self.sent_words = self.sent_record_words = 0
         self._n_host, self._dev_records = 0, []
+        self._live = {name: False for name in ONE_HOP_ROWS if name in self.row_off}    # the row was last written with entries
+        if arrivals is not None:
+            # uploaded up to the last arrival used: the CSR offsets of the arrivals [B + 1], the arrival records grouped by slot
+            max_arrivals, self.row_bytes = arrivals
+            self.arr_off = self.payload_off + batch + 1       # the words in front of the arrival records
+            self.offsets, self.h_offsets = self.payload[:batch + 1].view(torch.int32), self.h_payload[:batch + 1].view(torch.int32)
+            self.arrivals = self.payload[batch + 1:].view(torch.int32).view(max_arrivals, arrival_width(self.row_bytes))
+            self.h_arrivals = self.h_payload[batch + 1:].view(torch.int32).view(max_arrivals, arrival_width(self.row_bytes))
 
     def wait(self) -> None:
         """before the mirror is written: the previous upload's copy has left the pinned buffer"""
         self.uploaded.synchronize()
 
+    def put_one_hop(self, name: str, slots=(), values=()) -> None:
+        """the one-hop row `name` of the mirror: `values` at `slots` (host arrays or lists), 0 elsewhere; one indexed write: a full
+        batch of NACKs is a thousand slots"""
+        self.h_row[name].zero_()
+        self._live[name] = len(slots) > 0
+        if self._live[name]:
+            self.h_row[name].numpy()[slots] = values
+
+    @property
+    def one_hop_live(self) -> bool:
+        """whether a one-hop row holds entries as it was last written — after the `send` that follows every write: on the device"""
+        return any(self._live.values())
+
     def put_starts(self, starts) -> int:
         """the queued starts -> the mirror's action row and records (sessions.stage_starts); returns the number of host records"""
-        self.h_row["action"].zero_()
+        self.h_row["action"].zero_()          # the one-hop rule of put_one_hop, the entries written by stage_starts
         self._n_host, self._dev_records = stage_starts(starts, self.h_row["action"], self.h_records)
+        self._live["action"] = bool(starts)
         return self._n_host
 
     def send(self, words: int) -> None:
         """the first `words` words of the mirror -> the device, on the current stream"""
         self.dev[:words].copy_(self.host[:words], non_blocking=True)
         self.sent_words = words
+
+    def send_arrivals(self, arr: Arrivals, packets: Tensor) -> None:
+        """checked arrivals (sessions.check_arrivals) -> the mirror's arrival region, then `send` up to the last arrival used; packets
+        that are on the device go into the device records behind that copy, gathered first unless they came grouped by slot"""
+        put_arrivals(arr, packets, self.h_offsets, self.h_arrivals, self.row_bytes)
+        self.send(self.arr_off + arr.count * self.arrivals.shape[1])
+        if arr.count and packets.is_cuda:
+            grouped = np.array_equal(arr.order, np.arange(arr.count))
+            rows = packets if grouped else packets[torch.from_numpy(arr.order).to(self.device)]
+            arrival_bytes(self.arrivals[:arr.count], self.row_bytes).copy_(rows)
 
     def finish(self, host_records_apart: bool = False) -> None:
         """after `send`: the host records in a copy of their own (`host_records_apart`: `send` stopped short of them), the device
@@ -166,69 +222,41 @@ class ControlStage:
         self.uploaded.record(stream)
 
 
-class _Hop:
-    """What the graphed hops share: the groups' bounds and ping-pong state blocks, `parity`, warm-up and capture, replay-and-flip,
-    the per-group concatenation of the caches, and the session front end (the queue is host-only and always exists; `sessions`
-    gates the public methods and the graph's session kernels)."""
+class _GraphPair:
+    """A ping-pong pair of captured graphs over `batch` slots: `parity`, warm-up and capture, replay-and-flip, and the per-slot
+    device state the graphs update in place, allocated with its cleared value (`_slot_state`) and cleared by `_zero`."""
 
-    _scratch: Sequence[Tensor] = ()           # per-slot device buffers beside the state blocks: cleared with them (_zero, _load)
-    _scratch_fill: Sequence[Tuple[Tensor, int]] = ()      # those of them whose cleared value is not 0, with that value
+    def __init__(self, batch: int, device: torch.device):
+        self.batch, self.device = int(batch), device
+        self.parity = 0                       # the graph the next replay takes
+        self._scratch: List[Tuple[Tensor, object, bool]] = []  # every _slot_state tensor with its cleared value and rezero
 
-    def __init__(self, model, batch: int, n: int, device: torch.device, groups: int = 1, sessions: bool = False,
-                 max_loads_per_hop: int = 4):
-        self.model, self.n, self.device = model, n, device
-        groups = max(1, min(int(groups), batch))
-        self.bounds = [(batch * g // groups, batch * (g + 1) // groups) for g in range(groups)]
-        # per group: a ping-pong pair of state blocks (a cache tensor is [streams, C, pad]: a group's slice must be contiguous)
-        self.gstate = [(self._block(hi - lo), self._block(hi - lo)) for lo, hi in self.bounds]
-        self.parity = 0                       # the block holding the CURRENT caches (input of the next hop)
-        self.sessions = bool(sessions)
-        if self.sessions and max_loads_per_hop < 1:
-            raise ValueError("max_loads_per_hop must be >= 1")
-        layout = self.gstate[0][0].layout
-        self.queue = SessionQueue(batch, n, int(max_loads_per_hop) if self.sessions else 0, layout,
-                                  one_sided=layout.n_enc in (0, len(layout.shapes)))
-        if self.sessions:
-            for a, b in self.gstate:          # the kernels' layout tables, built before the capture
-                a.layout.tables(device)
-                b.layout.tables(device)
+    def _slot_state(self, *shape: int, dtype: torch.dtype = torch.int32, cleared=0, pingpong: bool = False,
+                    rezero: bool = False) -> Tensor:
+        """per-slot device state `[B, *shape]` (`pingpong`: `[2, B, *shape]`, a row per parity), as cleared: `cleared` everywhere, or,
+        for a dict {column: value}, zero but for those columns of the last dimension.  `_clear_scratch` clears it again, so a
+        feature's state cannot be allocated without being reset with the rest (`rezero`: it zeroes the tensor before it fills it)"""
+        t = torch.empty((2,) * pingpong + (self.batch,) + shape, dtype=dtype, device=self.device)
+        self._scratch.append((t, cleared, rezero))
+        self._clear(t, cleared)
+        return t
 
-    def _block(self, streams: int) -> StateBlock:
-        """a state block of `streams` streams (the sender and the receiver: one side's caches only)"""
-        return StateBlock(self.model, streams, self.device)
-
-    def _new_stage(self, rows: Sequence[str], payload_words: int = 0) -> ControlStage:
-        """the control stage of a hop with these rows and payload, and the device views every session graph reads"""
-        q = self.queue
-        stage = ControlStage(q.batch, rows, payload_words, q.max_loads, q.layout.record_len, self.device)
-        self.action, self.hold, self.records = stage.row["action"], stage.row["hold"], stage.records
-        return stage
-
-    @property
-    def state(self):
-        """(block A, block B) of a single-group schedule (the form tests and callers of earlier rounds use)"""
-        if len(self.gstate) != 1:
-            raise RuntimeError(f"{type(self).__name__}.state: the streams are split into groups — use .gstate[g]")
-        return self.gstate[0]
-
-    def _zero(self) -> None:
-        for a, b in self.gstate:
-            a.zero_()
-            b.zero_()
-        self._clear_scratch()
+    @staticmethod
+    def _clear(t: Tensor, cleared, rezero: bool = False) -> None:
+        if rezero or isinstance(cleared, dict):
+            t.zero_()
+        if not isinstance(cleared, dict):
+            t.fill_(cleared)
+            return
+        for column, value in cleared.items():
+            t[..., column].fill_(value)
 
     def _clear_scratch(self) -> None:
-        for t in self._scratch:
-            t.zero_()
-        for t, v in self._scratch_fill:
-            t.fill_(v)
+        for t, cleared, rezero in self._scratch:
+            self._clear(t, cleared, rezero)
 
-    def _load(self, cache_enc: Optional[Sequence[Tensor]], cache_dec: Optional[Sequence[Tensor]]) -> None:
-        """reset's state part: parity 0, block A zero or the given caches, the scratch buffers zero"""
-        self.parity = 0
-        for (lo, hi), (a, _b) in zip(self.bounds, self.gstate):
-            a.load_(None if cache_enc is None else [c[lo:hi] for c in cache_enc],
-                    None if cache_dec is None else [c[lo:hi] for c in cache_dec])
+    def _zero(self) -> None:
+        """everything the graphs update in place, as constructed (a subclass: with what else it owns)"""
         self._clear_scratch()
 
     def _capture_pair(self, hop, warmup: int):
@@ -245,12 +273,21 @@ class _Hop:
         torch.cuda.current_stream(device).wait_stream(side)
         torch.cuda.synchronize(device)
         graphs, outs = [], []
-        for p in (0, 1):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g), torch.no_grad():
-                out = hop(p)
-            graphs.append(g)
-            outs.append(out)
+        # no pass of the cyclic collector while a capture is open: it would finalize whatever dead cycle owns device objects (the
+        # graphs of an earlier hop whose stage.send a caller wrapped, say) in the middle of the capture, and a pass that fell into
+        # a capture has aborted the process.  Such garbage waits for the first pass after the captures
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            for p in (0, 1):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g), torch.no_grad():
+                    out = hop(p)
+                graphs.append(g)
+                outs.append(out)
+        finally:
+            if collecting:
+                gc.enable()
         self._zero()
         return graphs, outs
 
@@ -261,6 +298,69 @@ class _Hop:
         self.parity ^= 1
         return self.outs[p]
 
+    def _need(self, have, what: str, how: str) -> None:
+        """a method, argument or view `what` of an option this object was constructed without (`how` to get it): RuntimeError"""
+        if not have:
+            raise RuntimeError(f"{type(self).__name__}.{what}: construct with {how}")
+
+
+class _Hop(_GraphPair):
+    """What the graphed codec hops share on top of the graph pair: the groups' bounds and ping-pong state blocks (`parity`: the block
+    holding the CURRENT caches), the per-group concatenation of the caches, and the session front end (the queue is host-only and
+    always exists; `sessions` gates the public methods and the graph's session kernels)."""
+
+    def __init__(self, model, batch: int, n: int, device: torch.device, groups: int = 1, sessions: bool = False,
+                 max_loads_per_hop: int = 4):
+        super().__init__(batch, device)
+        self.model, self.n = model, n
+        groups = max(1, min(int(groups), batch))
+        self.bounds = [(batch * g // groups, batch * (g + 1) // groups) for g in range(groups)]
+        # per group: a ping-pong pair of state blocks (a cache tensor is [streams, C, pad]: a group's slice must be contiguous)
+        self.gstate = [(self._block(hi - lo), self._block(hi - lo)) for lo, hi in self.bounds]
+        self.sessions = bool(sessions)
+        if self.sessions and max_loads_per_hop < 1:
+            raise ValueError("max_loads_per_hop must be >= 1")
+        layout = self.gstate[0][0].layout
+        self.queue = SessionQueue(batch, n, int(max_loads_per_hop) if self.sessions else 0, layout,
+                                  one_sided=layout.n_enc in (0, len(layout.shapes)))
+        if self.sessions:
+            for a, b in self.gstate:          # the kernels' layout tables, built before the capture
+                a.layout.tables(device)
+                b.layout.tables(device)
+
+    def _block(self, streams: int) -> StateBlock:
+        """a state block of `streams` streams (the sender and the receiver: one side's caches only)"""
+        return StateBlock(self.model, streams, self.device)
+
+    def _new_stage(self, rows: Sequence[str], payload_words: int = 0, arrivals: Optional[Tuple[int, int]] = None) -> ControlStage:
+        """the control stage of a hop with these rows and payload (`arrivals`: an arrival region), and the device views every session
+        graph reads"""
+        q = self.queue
+        stage = ControlStage(q.batch, rows, payload_words, q.max_loads, q.layout.record_len, self.device, arrivals)
+        self.action, self.hold, self.records = stage.row["action"], stage.row["hold"], stage.records
+        return stage
+
+    @property
+    def state(self):
+        """(block A, block B) of a single-group schedule (the form tests and callers of earlier rounds use)"""
+        if len(self.gstate) != 1:
+            raise RuntimeError(f"{type(self).__name__}.state: the streams are split into groups — use .gstate[g]")
+        return self.gstate[0]
+
+    def _zero(self) -> None:
+        for a, b in self.gstate:
+            a.zero_()
+            b.zero_()
+        super()._zero()
+
+    def _load(self, cache_enc: Optional[Sequence[Tensor]], cache_dec: Optional[Sequence[Tensor]]) -> None:
+        """reset's state part: parity 0, block A zero or the given caches, the scratch buffers zero"""
+        self.parity = 0
+        for (lo, hi), (a, _b) in zip(self.bounds, self.gstate):
+            a.load_(None if cache_enc is None else [c[lo:hi] for c in cache_enc],
+                    None if cache_dec is None else [c[lo:hi] for c in cache_dec])
+        self._clear_scratch()
+
     def _current(self, which: str) -> List[Tensor]:
         per_group = [getattr(blocks[self.parity], which) for blocks in self.gstate]
         if len(per_group) == 1:
@@ -269,8 +369,7 @@ class _Hop:
 
     # ---------------------------------------------------------------- sessions
     def _need_sessions(self, what: str) -> None:
-        if not self.sessions:
-            raise RuntimeError(f"{type(self).__name__}.{what}: construct with sessions=True")
+        self._need(self.sessions, what, "sessions=True")
 
     def _hold_slots(self, hold) -> List[int]:
         """step's `hold` checked before anything is launched"""
@@ -350,8 +449,8 @@ class GraphedHop(_Hop):
             self.n_slot = self.stage.row["n_slot"]
             self.n_slot.fill_(self.n)
             self.stage.h_row["n_slot"].fill_(self.n)
-            self._action_live = False         # the device action row holds the previous hop's actions
             self._held_live = frozenset()     # the slots the device hold row marks
+        self._init_state()
         # the STFT side branch (engine._early_spectra) only for a single chain: with several chains the launches of the other
         # groups already fill the idle CUs, and a fork of a forked stream inside one capture crashes hipStreamEndCapture (ROCm 7.2)
         self.spec_side = [torch.cuda.Stream(device) if len(self.bounds) == 1 else None for _ in self.bounds]
@@ -422,7 +521,6 @@ class GraphedHop(_Hop):
                 self._put_extra(st)
                 st.send(st.rec_off)
                 st.finish()
-                self._action_live = False
                 self._held_live = frozenset()
 
     def step(self, x: Tensor, hold=None) -> Tuple[Tensor, Tensor]:
@@ -439,7 +537,7 @@ class GraphedHop(_Hop):
         action applies to exactly one hop: the upload after a hop with actions clears them; the hold row goes up when it changes)"""
         q, st = self.queue, self.stage
         held = q.held
-        if not q.pending and not self._action_live and held == self._held_live and not self._extra_pending():
+        if not q.pending and not st.one_hop_live and held == self._held_live and not self._extra_pending():
             q.clear()                         # this hop's holds are spent (the device row already marks them)
             return
         st.wait()
@@ -450,9 +548,11 @@ class GraphedHop(_Hop):
         self._put_extra(st)
         st.send(st.rec_off + n_host * st.records.shape[1])
         st.finish()
-        self._action_live = bool(q.starts)
         self._held_live = held
         q.clear()
+
+    def _init_state(self) -> None:
+        """a subclass's per-slot device state (_slot_state), allocated before the capture that reads it"""
 
     # a subclass's own rows of the control stage (GraphedEncodeHop(fec_adapt=): the report row)
     def _extra_rows(self) -> Tuple[str, ...]:
@@ -696,39 +796,25 @@ class GraphedEncodeHop(GraphedHop):
                  dtx: Optional[dtx_def.DtxConfig] = None, header: bool = False, vbr: Optional[vbr_def.VbrConfig] = None,
                  fec_adapt: Optional[report_def.FecAdaptConfig] = None, rtx: Optional[rtx_def.RtxConfig] = None,
                  rate: Optional[rate_def.RateConfig] = None):
-        # what the captured chain reads is set up first: GraphedHop's constructor captures it
+        # the options are checked and what they derive is set up first: GraphedHop's constructor allocates (_init_state) and captures
         self.fec_stages = _fec_stages(fec_stages, n)
-        if fec_adapt is not None:
-            if not isinstance(fec_adapt, report_def.FecAdaptConfig):
-                raise ValueError(f"fec_adapt must be a report.FecAdaptConfig or None, got {fec_adapt!r}")
-            if not sessions or not self.fec_stages:
-                raise ValueError("GraphedEncodeHop(fec_adapt=...) needs sessions=True and fec_stages >= 1")
-        self.fec_adapt = fec_adapt
+        self.fec_adapt = _config_arg("fec_adapt", fec_adapt, report_def.FecAdaptConfig)
+        _needs("GraphedEncodeHop(fec_adapt=...)", fec_adapt is None or (sessions and self.fec_stages),
+               "sessions=True and fec_stages >= 1")
         self._reports = {}                    # slot -> report word for the next hop
-        self._report_live = False             # the device report row holds the previous hop's reports
         self.header = bool(header)
         if self.header:
             _whole_frames("GraphedEncodeHop(header=True)", hop)
-        if rtx is not None:
-            if not isinstance(rtx, rtx_def.RtxConfig):
-                raise ValueError(f"rtx must be a rtx.RtxConfig or None, got {rtx!r}")
-            if not sessions or not self.header:
-                raise ValueError("GraphedEncodeHop(rtx=...) needs sessions=True and header=True")
-        self.rtx = rtx
+        self.rtx = _config_arg("rtx", rtx, rtx_def.RtxConfig)
+        _needs("GraphedEncodeHop(rtx=...)", rtx is None or (sessions and self.header), "sessions=True and header=True")
+        self.rate = _config_arg("rate", rate, rate_def.RateConfig)
         if rate is not None:
-            if not isinstance(rate, rate_def.RateConfig):
-                raise ValueError(f"rate must be a rate.RateConfig or None, got {rate!r}")
-            if not sessions:
-                raise ValueError("GraphedEncodeHop(rate=...) needs sessions=True")
+            _needs("GraphedEncodeHop(rate=...)", sessions, "sessions=True")
             # ValueError: a min_kbps that does not pay for the floor of a hop, a max_kbps past the int32 rows
             self._rate_bits = rate_def.bucket(rate, _whole_frames("GraphedEncodeHop(rate=...)", hop), self.fec_stages, self.header)
-        self.rate = rate
         self._nacks = {}                      # slot -> (word, bitmap) for the next hop
-        self._nack_live = False               # the device NACK rows hold the previous hop's NACKs
         self.frames = hop // HOP
-        if dtx is not None and not isinstance(dtx, dtx_def.DtxConfig):
-            raise ValueError(f"dtx must be a dtx.DtxConfig or None, got {dtx!r}")
-        self.dtx = dtx
+        self.dtx = _config_arg("dtx", dtx, dtx_def.DtxConfig)
         if dtx is not None:
             dtx_def.check_order(dtx.order, wire.packet_bytes(n, _whole_frames("GraphedEncodeHop(dtx=...)", hop)),
                                 "GraphedEncodeHop(dtx=...)")
@@ -741,68 +827,56 @@ class GraphedEncodeHop(GraphedHop):
             self.rs = design(self.input_rate, BASE_RATE)
             self.rs_taps = device_taps(self.rs, device)
             self._history = self.rs.history
-        if vbr is not None and not isinstance(vbr, vbr_def.VbrConfig):
-            raise ValueError(f"vbr must be a vbr.VbrConfig or None, got {vbr!r}")
-        self.vbr = vbr
+        self.vbr = _config_arg("vbr", vbr, vbr_def.VbrConfig)
         if vbr is not None:
-            if self.fec_stages and not self.header:
-                raise ValueError("GraphedEncodeHop(vbr=..., fec_stages=m) needs header=True: without the header a receiver cannot tell "
-                                 "an n-stage packet with a redundant section from a longer plain one")
+            _needs("GraphedEncodeHop(vbr=..., fec_stages=m)", self.header or not self.fec_stages, "header=True: without the header a "
+                   "receiver cannot tell an n-stage packet with a redundant section from a longer plain one")
             self._vbr_lo = min(int(n), vbr_def.floor_stages(vbr, self.fec_stages))
             self._vbr_bits = vbr_def.bucket_bits(vbr, _whole_frames("GraphedEncodeHop(vbr=...)", hop), self.fec_stages)
-        self._prev = self._run = self._ctr = self._credit = self._fa = self._fec_on = None
-        self._scratch_fill = []
-        if self.fec_stages:
-            # per parity, per slot: valid, then the first m stages x T frames of its last encoded hop (the hop of parity p reads
-            # row p and writes row p ^ 1)
-            self._prev = torch.zeros(2, batch, 1 + self.fec_stages * self.frames, dtype=torch.int32, device=device)
-        if dtx is not None:
-            # per slot: the DTX run counter (updated in place by hilc_dtx_encode once per hop)
-            self._run = torch.zeros(batch, dtype=torch.int32, device=device)
-            self._level_thr = torch.from_numpy(dtx_def.level_table()).to(device)
-        if self.header:
-            # per parity, per slot: the hop counter (the hop of parity p reads row p and writes row p ^ 1)
-            self._ctr = torch.zeros(2, batch, dtype=torch.int32, device=device)
-        if vbr is not None and vbr.cap_kbps is not None:
-            # per slot: the token bucket's credit in bits (updated in place by hilc_vbr_select once per hop); cleared = full
-            self._credit = torch.full((batch,), self._vbr_bits[2], dtype=torch.int32, device=device)
-            self._scratch_fill += [(self._credit, self._vbr_bits[2])]
-        if fec_adapt is not None:
-            # per slot: the adapt row (report.FA_*, updated in place by hilc_fec_adapt once per hop) and its switch; cleared = the
-            # row zero but for FA_ON = initial_on
-            on0 = int(fec_adapt.initial_on)
-            self._fa = torch.zeros(batch, report_def.FA_WORDS, dtype=torch.int32, device=device)
-            self._fa[:, report_def.FA_ON] = on0
-            self._fec_on = torch.full((batch,), on0, dtype=torch.int32, device=device)
-            self._scratch_fill += [(self._fa[:, report_def.FA_ON], on0), (self._fec_on, on0)]
-        self._rx = None
-        if rtx is not None:
-            # per slot: the history (tags and rows of headed packets, updated in place by hilc_rtx_step once per hop) and its counter
-            # row; per parity: the retransmission rows and their byte counts
-            tb = wire.transport_bytes(n, self.fec_stages, self.frames)
-            ints = dict(dtype=torch.int32, device=device)
-            self._rx = (torch.zeros(batch, rtx.history, **ints), torch.zeros(batch, rtx.history, (tb + 3) // 4, **ints),
-                        torch.zeros(batch, rtx_def.RX_WORDS, **ints))
-            self._rx_out = torch.zeros(2, batch, rtx.per_hop, tb, dtype=torch.uint8, device=device)
-            self._rx_nbytes = torch.zeros(2, batch, rtx.per_hop, **ints)
-        self._rc = self._n_ceil = None
-        if rate is not None:
-            # per slot: the rate row (rate.RC_*, updated in place by hilc_rate_ceiling and hilc_rate_charge once per hop) and its
-            # ceiling; cleared = the row zero but for the start rate and a full bucket, the ceiling n
-            rate_q8, full = 256 * self._rate_bits.start_bits, rate.burst_hops * self._rate_bits.start_bits
-            self._rc = torch.zeros(batch, rate_def.RC_WORDS, dtype=torch.int32, device=device)
-            self._rc[:, rate_def.RC_RATE_Q8], self._rc[:, rate_def.RC_CREDIT] = rate_q8, full
-            self._n_ceil = torch.full((batch,), int(n), dtype=torch.int32, device=device)
-            self._scratch_fill += [(self._rc[:, rate_def.RC_RATE_Q8], rate_q8), (self._rc[:, rate_def.RC_CREDIT], full),
-                                   (self._n_ceil, int(n))]
-        self._scratch = [t for t in (self._prev, self._run, self._ctr, self._credit, self._fa, self._rc) if t is not None]
-        if rtx is not None:
-            self._scratch += [*self._rx, self._rx_out, self._rx_nbytes]
         super().__init__(model, batch, hop_in, n, device, warmup, 1, sessions, max_loads_per_hop)
         self.queue.n_min = max(1, self.fec_stages)
         self.indices = self.outs[0][0]
         self.kind = self.outs[0][3] if dtx is not None else None
         self.n_eff, self.distortion = self.outs[0][-2:] if vbr is not None else (None, None)
+
+    def _init_state(self) -> None:
+        n, m, T = self.n, self.fec_stages, self.frames
+        self._prev = self._run = self._ctr = self._credit = self._fa = self._fec_on = self._rx = self._rc = self._n_ceil = None
+        if m:
+            # per parity, per slot: valid, then the first m stages x T frames of its last encoded hop (the hop of parity p reads
+            # row p and writes row p ^ 1)
+            self._prev = self._slot_state(1 + m * T, pingpong=True)
+        if self.dtx is not None:
+            # per slot: the DTX run counter (updated in place by hilc_dtx_encode once per hop)
+            self._run = self._slot_state()
+            self._level_thr = torch.from_numpy(dtx_def.level_table()).to(self.device)
+        if self.header:
+            # per parity, per slot: the hop counter (the hop of parity p reads row p and writes row p ^ 1)
+            self._ctr = self._slot_state(pingpong=True)
+        if self.vbr is not None and self.vbr.cap_kbps is not None:
+            # per slot: the token bucket's credit in bits (updated in place by hilc_vbr_select once per hop); cleared = full
+            # (a clearing zeroes it and then fills it, as it did before the allocator: its launches stay what they were)
+            self._credit = self._slot_state(cleared=self._vbr_bits[2], rezero=True)
+        if self.fec_adapt is not None:
+            # per slot: the adapt row (report.FA_*, updated in place by hilc_fec_adapt once per hop) and its switch; cleared = the
+            # row zero but for FA_ON = initial_on
+            on0 = int(self.fec_adapt.initial_on)
+            self._fa = self._slot_state(report_def.FA_WORDS, cleared={report_def.FA_ON: on0})
+            self._fec_on = self._slot_state(cleared=on0)
+        if self.rtx is not None:
+            # per slot: the history (tags and rows of headed packets, updated in place by hilc_rtx_step once per hop) and its counter
+            # row; per parity: the retransmission rows and their byte counts
+            tb, history, per_hop = wire.transport_bytes(n, m, T), self.rtx.history, self.rtx.per_hop
+            self._rx = (self._slot_state(history), self._slot_state(history, (tb + 3) // 4), self._slot_state(rtx_def.RX_WORDS))
+            self._rx_out = self._slot_state(per_hop, tb, dtype=torch.uint8, pingpong=True)
+            self._rx_nbytes = self._slot_state(per_hop, pingpong=True)
+        if self.rate is not None:
+            # per slot: the rate row (rate.RC_*, updated in place by hilc_rate_ceiling and hilc_rate_charge once per hop) and its
+            # ceiling; cleared = the row zero but for the start rate and a full bucket, the ceiling n
+            start = self._rate_bits.start_bits
+            self._rc = self._slot_state(rate_def.RC_WORDS, cleared={rate_def.RC_RATE_Q8: 256 * start,
+                                                                     rate_def.RC_CREDIT: self.rate.burst_hops * start})
+            self._n_ceil = self._slot_state(cleared=int(n))
 
     def _block(self, streams: int) -> StateBlock:
         return StateBlock(self.model, streams, self.device, "enc", self._history)
@@ -872,72 +946,62 @@ class GraphedEncodeHop(GraphedHop):
     def credit(self) -> Tensor:
         """int32 `[B]` device view: each slot's token-bucket credit in bits after the last hop (vbr with a cap only).  Read-only:
         written by the graph."""
-        if self._credit is None:
-            raise RuntimeError("GraphedEncodeHop.credit: construct with vbr=VbrConfig(..., cap_kbps=...)")
+        self._need(self._credit is not None, "credit", "vbr=VbrConfig(..., cap_kbps=...)")
         return self._credit
 
     @property
     def hop_index(self) -> Tensor:
         """int32 `[B]` device view: each slot's hop counter, the h its next sent packet carries unless a start intervenes (header=True
         only).  Read-only: written by the graph."""
-        if self._ctr is None:
-            raise RuntimeError("GraphedEncodeHop.hop_index: construct with header=True")
+        self._need(self.header, "hop_index", "header=True")
         return self._ctr[self.parity]
 
     @property
     def fec_on(self) -> Tensor:
         """int32 `[B]` device view: each slot's FEC switch after the last hop (fec_adapt only).  Read-only: written by the graph."""
-        if self._fec_on is None:
-            raise RuntimeError("GraphedEncodeHop.fec_on: construct with fec_adapt=FecAdaptConfig(...)")
+        self._need(self._fec_on is not None, "fec_on", "fec_adapt=FecAdaptConfig(...)")
         return self._fec_on
 
     @property
     def fec_adapt_state(self) -> Tensor:
         """int32 `[B, report.FA_WORDS]` device view: each slot's adapt row after the last hop (report.FA_*; fec_adapt only).
         Read-only: written by the graph."""
-        if self._fa is None:
-            raise RuntimeError("GraphedEncodeHop.fec_adapt_state: construct with fec_adapt=FecAdaptConfig(...)")
+        self._need(self._fa is not None, "fec_adapt_state", "fec_adapt=FecAdaptConfig(...)")
         return self._fa
 
     @property
     def n_ceil(self) -> Tensor:
         """int32 `[B]` device view: the most stages each slot's bucket paid for on the last hop (rate only; a held slot: its own n).
         Read-only: written by the graph."""
-        if self._n_ceil is None:
-            raise RuntimeError("GraphedEncodeHop.n_ceil: construct with rate=RateConfig(...)")
+        self._need(self._n_ceil is not None, "n_ceil", "rate=RateConfig(...)")
         return self._n_ceil
 
     @property
     def rate_state(self) -> Tensor:
         """int32 `[B, rate.RC_WORDS]` device view: each slot's rate row after the last hop (rate.RC_*; rate only; `rate.kbps(row,
         frames)` gives RC_RATE_Q8 in kbps).  Read-only: written by the graph."""
-        if self._rc is None:
-            raise RuntimeError("GraphedEncodeHop.rate_state: construct with rate=RateConfig(...)")
+        self._need(self._rc is not None, "rate_state", "rate=RateConfig(...)")
         return self._rc
-
-    def _need_rtx(self, what: str) -> None:
-        if self.rtx is None:
-            raise RuntimeError(f"GraphedEncodeHop.{what}: construct with rtx=RtxConfig(...)")
 
     @property
     def rtx_packets(self) -> Tensor:
         """uint8 `[B, per_hop, wire.transport_bytes(n, m, T)]` device view: each slot's retransmissions of the last hop, in request
         order, zero past their lengths (rtx only); overwritten by the next-but-one `step`.  Read-only: written by the graph."""
-        self._need_rtx("rtx_packets")
+        self._need(self.rtx is not None, "rtx_packets", "rtx=RtxConfig(...)")
         return self._rx_out[self.parity ^ 1]
 
     @property
     def rtx_nbytes(self) -> Tensor:
         """int32 `[B, per_hop]` device view: the byte counts of `rtx_packets` (0: the row is unused).  Read-only: written by the
         graph."""
-        self._need_rtx("rtx_nbytes")
+        self._need(self.rtx is not None, "rtx_nbytes", "rtx=RtxConfig(...)")
         return self._rx_nbytes[self.parity ^ 1]
 
     @property
     def rtx_state(self) -> Tensor:
         """int32 `[B, rtx.RX_WORDS]` device view: each slot's counter row after the last hop (rtx.RX_*; rtx only).  Read-only:
         written by the graph."""
-        self._need_rtx("rtx_state")
+        self._need(self.rtx is not None, "rtx_state", "rtx=RtxConfig(...)")
         return self._rx[2]
 
     def _feedback(self, name: str, pair, width: int, word, enabled: bool, needs: str) -> dict:
@@ -945,8 +1009,7 @@ class GraphedEncodeHop(GraphedHop):
         twice keeps its last blob"""
         if pair is None:
             return {}
-        if not enabled:
-            raise RuntimeError(f"GraphedEncodeHop.step({name}=...): construct with {needs}")
+        self._need(enabled, f"step({name}=...)", needs)
         try:
             slots, blobs = pair
         except (TypeError, ValueError):
@@ -982,29 +1045,27 @@ class GraphedEncodeHop(GraphedHop):
         return ("report",) * (self.fec_adapt is not None or self.rate is not None) + ("nack_base", "nack_bitmap") * (self.rtx is not None)
 
     def _extra_pending(self) -> bool:
-        return bool(self._reports) or self._report_live or bool(self._nacks) or self._nack_live
+        return bool(self._reports or self._nacks)
 
     def _put_extra(self, st: ControlStage) -> None:
         """the report row: this hop's reports, 0 elsewhere (a report applies to exactly one hop, like an action: the upload after a
         hop with reports clears them); with fec_adapt and rate, one report feeds both launches"""
-        if self.fec_adapt is not None or self.rate is not None:
-            row = st.h_row["report"]
-            row.zero_()
-            if self._reports:                 # one indexed write, as for the NACK rows below
-                slots = np.fromiter(self._reports, dtype=np.int64, count=len(self._reports))
-                row.numpy()[slots] = np.fromiter(self._reports.values(), dtype=np.int32, count=len(self._reports))
-            self._report_live = bool(self._reports)
+        if "report" in st.h_row and not self._reports:
+            st.put_one_hop("report")
+        elif "report" in st.h_row:
+            slots = np.fromiter(self._reports, dtype=np.int64, count=len(self._reports))
+            st.put_one_hop("report", slots, np.fromiter(self._reports.values(), dtype=np.int32, count=len(slots)))
             self._reports = {}
-        if self.rtx is not None:
-            # the NACK rows, likewise: this hop's NACKs, (0, 0) elsewhere
-            base, bitmap = st.h_row["nack_base"], st.h_row["nack_bitmap"]
-            base.zero_()
-            bitmap.zero_()
-            if self._nacks:                   # one indexed write per row: a full batch of NACKs is a thousand slots
-                slots = np.fromiter(self._nacks, dtype=np.int64, count=len(self._nacks))
-                words = np.array(list(self._nacks.values()), dtype=np.int32)
-                base.numpy()[slots], bitmap.numpy()[slots] = words[:, 0], words[:, 1]
-            self._nack_live = bool(self._nacks)
+        if self.rtx is not None and not self._nacks:
+            st.put_one_hop("nack_base")
+            st.put_one_hop("nack_bitmap")
+        elif self.rtx is not None:
+            # the NACK rows, likewise: this hop's NACKs, (0, 0) elsewhere; one indexed write per row: a full batch of NACKs is a
+            # thousand slots
+            slots = np.fromiter(self._nacks, dtype=np.int64, count=len(self._nacks))
+            words = np.array(list(self._nacks.values()), dtype=np.int32)
+            st.put_one_hop("nack_base", slots, words[:, 0])
+            st.put_one_hop("nack_bitmap", slots, words[:, 1])
             self._nacks = {}
 
     def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
@@ -1140,38 +1201,25 @@ class GraphedDecodeHop(_Hop):
         if not 1 <= int(n) <= len(model.dequantizer.layers):
             raise ValueError(f"n = {n} outside [1, {len(model.dequantizer.layers)}]")
         self.conceal = bool(conceal)
-        if self.conceal and not sessions:
-            raise ValueError("GraphedDecodeHop(conceal=True) needs sessions=True")
+        _needs("GraphedDecodeHop(conceal=True)", sessions or not self.conceal, "sessions=True")
         self.fade_hops = _int_arg("fade_hops", fade_hops, 1)
         self.fec_stages = _fec_stages(fec_stages, int(n))
         self.cng_order = None
         if cng_order is not None:
             self.cng_order = _int_arg("cng_order", cng_order, 0, dtx_def.MAX_ORDER)
-            if not sessions:
-                raise ValueError("GraphedDecodeHop(cng_order=...) needs sessions=True")
+            _needs("GraphedDecodeHop(cng_order=...)", sessions, "sessions=True")
             dtx_def.check_order(self.cng_order, wire.packet_bytes(int(n), self.frames), "GraphedDecodeHop(cng_order=...)")
-        if jitter is not None and not isinstance(jitter, JitterConfig):
-            raise ValueError(f"jitter must be a jitter.JitterConfig or None, got {jitter!r}")
-        if jitter is not None and not sessions:
-            raise ValueError("GraphedDecodeHop(jitter=...) needs sessions=True")
-        self.jitter = jitter
-        if jitter is None and max_arrivals is not None:
-            raise ValueError("GraphedDecodeHop(max_arrivals=...) needs jitter=JitterConfig(...)")
-        if mix is not None and not isinstance(mix, MixConfig):
-            raise ValueError(f"mix must be a mixer.MixConfig or None, got {mix!r}")
-        if mix is not None and not sessions:
-            raise ValueError("GraphedDecodeHop(mix=...) needs sessions=True")
-        self.mix = mix
-        if report is not None and not isinstance(report, report_def.ReportConfig):
-            raise ValueError(f"report must be a report.ReportConfig or None, got {report!r}")
-        if report is not None and jitter is None:
-            raise ValueError("GraphedDecodeHop(report=...) needs jitter=JitterConfig(...): the reports are made from the jitter state")
-        self.report = report
-        if nack is not None and not isinstance(nack, rtx_def.NackConfig):
-            raise ValueError(f"nack must be a rtx.NackConfig or None, got {nack!r}")
-        if nack is not None and jitter is None:
-            raise ValueError("GraphedDecodeHop(nack=...) needs jitter=JitterConfig(...): the NACKs are made from the jitter ring")
-        self.nack = nack
+        self.jitter = _config_arg("jitter", jitter, JitterConfig)
+        _needs("GraphedDecodeHop(jitter=...)", sessions or jitter is None, "sessions=True")
+        _needs("GraphedDecodeHop(max_arrivals=...)", jitter is not None or max_arrivals is None, "jitter=JitterConfig(...)")
+        self.mix = _config_arg("mix", mix, MixConfig)
+        _needs("GraphedDecodeHop(mix=...)", sessions or mix is None, "sessions=True")
+        self.report = _config_arg("report", report, report_def.ReportConfig)
+        _needs("GraphedDecodeHop(report=...)", jitter is not None or report is None,
+               "jitter=JitterConfig(...): the reports are made from the jitter state")
+        self.nack = _config_arg("nack", nack, rtx_def.NackConfig)
+        _needs("GraphedDecodeHop(nack=...)", jitter is not None or nack is None,
+               "jitter=JitterConfig(...): the NACKs are made from the jitter ring")
         super().__init__(model, self.batch, int(n), device, 1, sessions, max_loads_per_hop)
         self.stride = wire.packet_bytes(self.n + self.fec_stages, self.frames)
         B = self.batch
@@ -1186,47 +1234,37 @@ class GraphedDecodeHop(_Hop):
             self.packets = st.payload.view(torch.uint8)[:B * self.stride].view(B, self.stride)
             self._h_packets = st.h_payload.view(torch.uint8)[:B * self.stride].view(B, self.stride)
         self.n_slot.fill_(self.n)
-        self._scratch = []
         if self.conceal:
             # per slot: run k, has-codes, stored n, the stored frame's n codes (updated in place by hilc_conceal_prepare once per hop)
-            self._conceal = torch.zeros(B, self.n + wire.CONCEAL_CODES, dtype=torch.int32, device=device)
+            self._conceal = self._slot_state(self.n + wire.CONCEAL_CODES)
             gains, weights = wire.conceal_tables(self.fade_hops, HOP * self.frames)
             self._gains, self._weights = gains.to(device), weights.to(device)
-            self._scratch += [self._conceal]
         if self.cng_order is not None:
             # per slot: the CN state row (dtx.state_words, updated in place by hilc_cng_synth once per hop); device-only: the slots
             # that produced noise this hop (their decoder caches are copied back)
-            self._cn = torch.zeros(B, dtx_def.state_words(self.cng_order), dtype=torch.int32, device=device)
+            self._cn = self._slot_state(dtx_def.state_words(self.cng_order))
             self._cn_gains = torch.from_numpy(dtx_def.gain_table()).to(device)
-            self._restore = torch.zeros(B, dtype=torch.int32, device=device)
-            self._scratch += [self._cn, self._restore]
-        if jitter is not None:
-            self._scratch += [self._jstate, self._jmeta, self._jring]
-            if jitter.adapt is not None:
-                self._scratch += [self._jadapt]
+            self._restore = self._slot_state()
         if report is not None:
             # per slot: the report row (report.RP_*, updated in place by hilc_rx_report once per hop), its latest report, its due flag
-            self._rp = torch.zeros(B, report_def.RP_WORDS, dtype=torch.int32, device=device)
-            self._rp_bytes = torch.zeros(B, wire.REPORT_BYTES, dtype=torch.uint8, device=device)
-            self._rp_due = torch.zeros(B, dtype=torch.int32, device=device)
-            self._scratch += [self._rp, self._rp_bytes, self._rp_due]
+            self._rp = self._slot_state(report_def.RP_WORDS)
+            self._rp_bytes = self._slot_state(wire.REPORT_BYTES, dtype=torch.uint8)
+            self._rp_due = self._slot_state()
         if nack is not None:
             # per slot: the NACK row (rtx.NK_*, updated in place by hilc_nack_build once per hop), its latest NACK, its due flag
-            self._nk = torch.zeros(B, rtx_def.NK_WORDS, dtype=torch.int32, device=device)
-            self._nk_bytes = torch.zeros(B, wire.NACK_BYTES, dtype=torch.uint8, device=device)
-            self._nk_due = torch.zeros(B, dtype=torch.int32, device=device)
-            self._scratch += [self._nk, self._nk_bytes, self._nk_due]
+            self._nk = self._slot_state(rtx_def.NK_WORDS)
+            self._nk_bytes = self._slot_state(wire.NACK_BYTES, dtype=torch.uint8)
+            self._nk_due = self._slot_state()
         if mix is not None:
             # per slot: the peak-hold score (updated in place by hilc_mix_levels once per hop); per parity: the mixes; the speaker
             # marks; the room row (device, captured by address) and its pinned host mirror
             L = hop_samples(self.frames, self.output_rate) if self.rs is not None else HOP * self.frames
-            self._score = torch.zeros(B, dtype=torch.float64, device=device)
+            self._score = self._slot_state(dtype=torch.float64)
             self._mixed = torch.zeros(2, B, 1, L, device=device)
             self._speakers = torch.zeros(B, dtype=torch.int32, device=device)
             self._room = torch.full((B,), -1, dtype=torch.int32, device=device)
             self._h_room = torch.full((B,), -1, dtype=torch.int32).pin_memory()
             self._room_dirty, self._room_sent = False, torch.cuda.Event()
-            self._scratch += [self._score]
         self.sched = ops.SchedWorkspace(device)
         self.graphs, self.outs = self._capture_pair(self._hop, warmup)
 
@@ -1247,16 +1285,14 @@ class GraphedDecodeHop(_Hop):
     def concealed(self) -> Tensor:
         """int32 `[B]` device view: each slot's run of lost hops after the last step (0: decoded from a received packet, or no
         run; k >= 1: k hops lost in a row, at most `fade_hops`).  Read-only: written by the graph."""
-        if not self.conceal:
-            raise RuntimeError("GraphedDecodeHop.concealed: construct with conceal=True")
+        self._need(self.conceal, "concealed", "conceal=True")
         return self._conceal[:, wire.CONCEAL_RUN]
 
     @property
     def cng_state(self) -> Tensor:
         """int32 `[B, dtx.state_words(cng_order)]` device view: each slot's CN state (has-SID, L, c, q, filter memory) after the last
         step.  Read-only: written by the graph."""
-        if self.cng_order is None:
-            raise RuntimeError("GraphedDecodeHop.cng_state: construct with cng_order=K")
+        self._need(self.cng_order is not None, "cng_state", "cng_order=K")
         return self._cn
 
     def _hop(self, p: int) -> Tensor:
@@ -1307,19 +1343,15 @@ class GraphedDecodeHop(_Hop):
         return wav
 
     # ---------------------------------------------------------------- room mixing
-    def _need_mix(self, what: str) -> None:
-        if self.mix is None:
-            raise RuntimeError(f"GraphedDecodeHop.{what}: construct with mix=MixConfig(...)")
-
     def join(self, slot: int, room: int) -> None:
         """from the next hop on, slot `slot` is a member of room `room` (an int in [0, B): ValueError), and of no other"""
-        self._need_mix("join")
+        self._need(self.mix is not None, "join", "mix=MixConfig(...)")
         s = self.queue.slot(slot)
         self._set_room(s, _int_arg("room", room, 0, self.batch - 1))
 
     def leave(self, slot: int) -> None:
         """from the next hop on, slot `slot` is in no room (its mix is zero and nobody hears it)"""
-        self._need_mix("leave")
+        self._need(self.mix is not None, "leave", "mix=MixConfig(...)")
         self._set_room(self.queue.slot(slot), -1)
 
     def _set_room(self, slot: int, room: int) -> None:
@@ -1338,26 +1370,26 @@ class GraphedDecodeHop(_Hop):
     @property
     def rooms(self) -> Tuple[int, ...]:
         """each slot's room as the host has it (-1: none)"""
-        self._need_mix("rooms")
+        self._need(self.mix is not None, "rooms", "mix=MixConfig(...)")
         return tuple(self._h_room.tolist())
 
     @property
     def mixed(self) -> Tensor:
         """fp32 `[B,1,L]` device view: every slot's mix after the last hop (zeros before the first); overwritten by the next-but-one
         call.  Read-only: written by the graph."""
-        self._need_mix("mixed")
+        self._need(self.mix is not None, "mixed", "mix=MixConfig(...)")
         return self._mixed[self.parity ^ 1]
 
     @property
     def speakers(self) -> Tensor:
         """int32 `[B]` device view: 1 for the slots among their room's top_k after the last hop.  Read-only: written by the graph."""
-        self._need_mix("speakers")
+        self._need(self.mix is not None, "speakers", "mix=MixConfig(...)")
         return self._speakers
 
     @property
     def levels(self) -> Tensor:
         """float64 `[B]` device view: every slot's peak-hold score after the last hop.  Read-only: written by the graph."""
-        self._need_mix("levels")
+        self._need(self.mix is not None, "levels", "mix=MixConfig(...)")
         return self._score
 
     def _check(self, packets: Tensor, n_per_stream, held=(), fec=()) -> Tensor:
@@ -1389,18 +1421,15 @@ class GraphedDecodeHop(_Hop):
             raise RuntimeError("GraphedDecodeHop.step: a receiver with jitter=... takes play(slots, packets, nbytes)")
         held = self._hold_slots(hold)
         gone = SessionQueue.host_slots(lost)
-        if gone and not self.conceal:
-            raise RuntimeError("GraphedDecodeHop.step(lost=...): construct with conceal=True")
+        self._need(self.conceal or not gone, "step(lost=...)", "conceal=True")
         if self.conceal:
             gone = self.queue.lost_slots(gone, held)
         red = SessionQueue.host_slots(fec)
-        if red and not self.fec_stages:
-            raise RuntimeError("GraphedDecodeHop.step(fec=...): construct with fec_stages >= 1")
+        self._need(self.fec_stages or not red, "step(fec=...)", "fec_stages >= 1")
         if self.fec_stages:
             red = self.queue.fec_slots(red, held, gone)
         sids, quiet = SessionQueue.host_slots(sid), SessionQueue.host_slots(silent)
-        if (sids or quiet) and self.cng_order is None:
-            raise RuntimeError("GraphedDecodeHop.step(sid=..., silent=...): construct with cng_order=K")
+        self._need(self.cng_order is not None or not (sids or quiet), "step(sid=..., silent=...)", "cng_order=K")
         if self.cng_order is not None:
             sids, quiet = self.queue.cn_slots(sids, quiet, held, gone, red)
         held = set(held) | self.queue.stops
@@ -1435,131 +1464,92 @@ class GraphedDecodeHop(_Hop):
         B, dev = self.batch, self.device
         self.max_arrivals = _int_arg("max_arrivals", max_arrivals, 1)
         self.tstride = wire.transport_bytes(self.n, self.fec_stages, self.frames)
-        aw = 1 + (self.tstride + 3) // 4                   # an arrival record: byte count, then the headed packet
         # ONE device buffer, captured by address, uploaded up to the last arrival used: action per slot, the host's holds
-        # (hilc_jitter_step adds its own), the CSR offsets of the arrivals [B + 1], the arrival records grouped by slot, the staged
+        # (hilc_jitter_step adds its own), the arrival region (an arrival record: byte count, then the headed packet), the staged
         # records.  The n, lost and fec rows and the packet matrix are written by hilc_jitter_step and are never uploaded.
-        st = self.stage = self._new_stage(("action", "hold"), B + 1 + self.max_arrivals * aw)
-        self._arr_off = st.payload_off + B + 1              # the words in front of the arrival records
-        self.offsets, self._h_offsets = st.payload[:B + 1].view(torch.int32), st.h_payload[:B + 1].view(torch.int32)
-        self.arrivals = st.payload[B + 1:].view(torch.int32).view(self.max_arrivals, aw)
-        self._h_arrivals = st.h_payload[B + 1:].view(torch.int32).view(self.max_arrivals, aw)
+        st = self.stage = self._new_stage(("action", "hold"), arrivals=(self.max_arrivals, self.tstride))
+        self.offsets, self.arrivals = st.offsets, st.arrivals
         rows = torch.zeros(3, B, dtype=torch.int32, device=dev)
         self.n_slot = rows[0]
         self.lost = rows[1] if self.conceal else None
         self.fec = rows[2] if self.fec_stages else None
         self.packets = torch.zeros(B, self.stride, dtype=torch.uint8, device=dev)
         # per slot: the state row (jitter.ST_*, updated in place once per hop), the ring's meta words and bodies
-        self._jstate = torch.zeros(B, ST_WORDS, dtype=torch.int32, device=dev)
-        self._jmeta = torch.zeros(B, cfg.capacity, dtype=torch.int32, device=dev)
-        self._jring = torch.zeros(B, cfg.capacity, (self.stride + 3) // 4, dtype=torch.int32, device=dev)
+        self._jstate = self._slot_state(ST_WORDS)
+        self._jmeta = self._slot_state(cfg.capacity)
+        self._jring = self._slot_state(cfg.capacity, (self.stride + 3) // 4)
         if cfg.adapt is not None:
             # per slot: the adapt row (jitter.AD_*, updated in place once per hop by hilc_jitter_adapt_step)
-            self._jadapt = torch.zeros(B, AD_WORDS, dtype=torch.int32, device=dev)
+            self._jadapt = self._slot_state(AD_WORDS)
 
     @property
     def jitter_state(self) -> Tensor:
         """int32 `[B, jitter.ST_WORDS]` device view: each slot's jitter state row after the last play (jitter.ST_* / STAT_*).
         Read-only: written by the graph."""
-        if self.jitter is None:
-            raise RuntimeError("GraphedDecodeHop.jitter_state: construct with jitter=JitterConfig(...)")
+        self._need(self.jitter is not None, "jitter_state", "jitter=JitterConfig(...)")
         return self._jstate
 
     @property
     def jitter_adapt(self) -> Tensor:
         """int32 `[B, jitter.AD_WORDS]` device view: each slot's adapt row after the last play (jitter.AD_*).  Read-only: written by
         the graph."""
-        if self.jitter is None or self.jitter.adapt is None:
-            raise RuntimeError("GraphedDecodeHop.jitter_adapt: construct with jitter=JitterConfig(..., adapt=AdaptConfig(...))")
+        self._need(self.jitter is not None and self.jitter.adapt is not None, "jitter_adapt",
+                   "jitter=JitterConfig(..., adapt=AdaptConfig(...))")
         return self._jadapt
-
-    def _need_report(self, what: str) -> None:
-        if self.report is None:
-            raise RuntimeError(f"GraphedDecodeHop.{what}: construct with report=ReportConfig(...)")
 
     @property
     def reports(self) -> Tensor:
         """uint8 `[B, 3]` device view: each slot's latest report (wire.parse_report; zeros before its first), unchanged between
         reports.  Read-only: written by the graph."""
-        self._need_report("reports")
+        self._need(self.report is not None, "reports", "report=ReportConfig(...)")
         return self._rp_bytes
 
     @property
     def report_due(self) -> Tensor:
         """int32 `[B]` device view: 1 for the slots whose report was emitted on the last play.  Read-only: written by the graph."""
-        self._need_report("report_due")
+        self._need(self.report is not None, "report_due", "report=ReportConfig(...)")
         return self._rp_due
 
     @property
     def report_state(self) -> Tensor:
         """int32 `[B, report.RP_WORDS]` device view: each slot's report row after the last play (report.RP_*).  Read-only: written
         by the graph."""
-        self._need_report("report_state")
+        self._need(self.report is not None, "report_state", "report=ReportConfig(...)")
         return self._rp
-
-    def _need_nack(self, what: str) -> None:
-        if self.nack is None:
-            raise RuntimeError(f"GraphedDecodeHop.{what}: construct with nack=NackConfig(...)")
 
     @property
     def nacks(self) -> Tensor:
         """uint8 `[B, 4]` device view: each slot's latest NACK (wire.parse_nack; zeros before its first), unchanged between NACKs.
         Read-only: written by the graph."""
-        self._need_nack("nacks")
+        self._need(self.nack is not None, "nacks", "nack=NackConfig(...)")
         return self._nk_bytes
 
     @property
     def nack_due(self) -> Tensor:
         """int32 `[B]` device view: 1 for the slots whose NACK was emitted on the last play.  Read-only: written by the graph."""
-        self._need_nack("nack_due")
+        self._need(self.nack is not None, "nack_due", "nack=NackConfig(...)")
         return self._nk_due
 
     @property
     def nack_state(self) -> Tensor:
         """int32 `[B, rtx.NK_WORDS]` device view: each slot's NACK row after the last play (rtx.NK_*).  Read-only: written by the
         graph."""
-        self._need_nack("nack_state")
+        self._need(self.nack is not None, "nack_state", "nack=NackConfig(...)")
         return self._nk
 
     def play(self, slots, packets: Tensor, nbytes, hold=None) -> Tensor:
         """one hop of a jitter receiver: this hop's arrivals, in push order — `slots` and `nbytes` (A host ints), `packets` uint8
         `[A, wire.transport_bytes(n, m, frames)]` (host or device) — and `hold`: slots (host ints) held on this hop (playout
         pauses).  Returns the hop's waveform, a static view that the next-but-one call overwrites."""
-        if self.jitter is None:
-            raise RuntimeError("GraphedDecodeHop.play: construct with jitter=JitterConfig(...)")
+        self._need(self.jitter is not None, "play", "jitter=JitterConfig(...)")
         held = set(self._hold_slots(hold)) | self.queue.stops
-        for name, v in (("slots", slots), ("nbytes", nbytes)):
-            if isinstance(v, Tensor) and v.is_cuda:
-                raise ValueError(f"play: {name} must be host ints, not a device tensor")
-        sl = np.asarray(slots.tolist() if isinstance(slots, Tensor) else slots, dtype=np.int64).reshape(-1)
-        nb = np.asarray(nbytes.tolist() if isinstance(nbytes, Tensor) else nbytes, dtype=np.int64).reshape(-1)
-        A, B = len(sl), self.batch
-        if A > self.max_arrivals:
-            raise ValueError(f"play: {A} arrivals, at most max_arrivals = {self.max_arrivals}")
-        if len(nb) != A:
-            raise ValueError(f"play: {A} slots but {len(nb)} byte counts")
-        if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or tuple(packets.shape) != (A, self.tstride):
-            raise ValueError(f"play: packets must be uint8 [{A}, {self.tstride}]")
-        if A and (sl.min() < 0 or sl.max() >= B):
-            raise IndexError(f"play: a slot outside [0, {B})")
-        order = np.argsort(sl, kind="stable")
+        arr = check_arrivals("play", slots, packets, nbytes, self.batch, self.max_arrivals, self.tstride)
         st, q = self.stage, self.queue
         st.wait()
         _mark(st.h_row["hold"], held)
-        offs = self._h_offsets.numpy()
-        offs[0] = 0
-        offs[1:] = np.cumsum(np.bincount(sl, minlength=B))
-        if A:
-            self._h_arrivals[:A, 0].copy_(torch.from_numpy(np.clip(nb[order], -1, 1 << 20).astype(np.int32)))
         st.put_starts(q.starts)
         q.clear()
-        bytes_of = lambda t: t.view(torch.uint8)[:, 4:4 + self.tstride]
-        if A and not packets.is_cuda:
-            bytes_of(self._h_arrivals[:A]).copy_(packets[torch.from_numpy(order)])
-        st.send(self._arr_off + A * self.arrivals.shape[1])
-        if A and packets.is_cuda:
-            rows = packets if np.array_equal(order, np.arange(A)) else packets[torch.from_numpy(order).to(self.device)]
-            bytes_of(self.arrivals[:A]).copy_(rows)
+        st.send_arrivals(arr, packets)
         st.finish(host_records_apart=True)
         self._send_rooms()
         return self._replay()
@@ -1576,7 +1566,7 @@ class GraphedDecodeHop(_Hop):
         return super().export(slot)[1]
 
 
-class GraphedForwardHop:
+class GraphedForwardHop(_GraphPair):
     """A selective forwarding hop (hilcodec_amd/forward.py: the rules, bit for bit): a conference server for `batch` participant slots
     that routes packets and cuts them to each listener's number of stages without decoding.  It holds no model and no codec state: each
     slot is a sender (its arrivals are checked and its activity kept) and a listener (it is sent the packets of its room's `cfg.fanout`
@@ -1588,39 +1578,30 @@ class GraphedForwardHop:
     graphs are captured and replayed alternately, so what `forward` returns stays valid for one further call.
     `cfg`: the forward.ForwardConfig; `max_arrivals`: the most arrivals of one hop (default 2 B)."""
 
-    _capture_pair, _replay = _Hop._capture_pair, _Hop._replay
-
     def __init__(self, batch: int, frames: int, n: int, device: torch.device, fec_stages: int = 0, cng_order: Optional[int] = None,
                  cfg: forward_def.ForwardConfig = forward_def.ForwardConfig(), max_arrivals: Optional[int] = None, warmup: int = 2):
         if not isinstance(cfg, forward_def.ForwardConfig):
             raise ValueError(f"GraphedForwardHop: cfg must be a forward.ForwardConfig, got {cfg!r}")
-        B = self.batch = _int_arg("batch", batch, 1)
-        self.frames, self.n, self.device, self.cfg = _int_arg("frames", frames, 1), _int_arg("n", n, 1, 31), device, cfg
+        super().__init__(_int_arg("batch", batch, 1), device)
+        B = self.batch
+        self.frames, self.n, self.cfg = _int_arg("frames", frames, 1), _int_arg("n", n, 1, 31), cfg
         self.fec_stages = _fec_stages(fec_stages, self.n)
         self.cng_order = None if cng_order is None else _int_arg("cng_order", cng_order, 0, dtx_def.MAX_ORDER)
         self.max_arrivals = _int_arg("max_arrivals", 2 * B if max_arrivals is None else max_arrivals, 1)
         self.tstride = wire.transport_bytes(self.n, self.fec_stages, self.frames)
         if self.cng_order is not None:
             dtx_def.check_order(self.cng_order, self.tstride - wire.TRANSPORT_HEADER, "GraphedForwardHop(cng_order=...)")
-        aw = 1 + (self.tstride + 3) // 4                   # an arrival record: byte count, then the headed packet
-        # ONE device buffer, captured by address, uploaded up to the last arrival used: the action, room and layers rows, the CSR
-        # offsets of the arrivals [B + 1], the arrival records grouped by slot
-        st = self.stage = ControlStage(B, ("action", "room", "layers"), B + 1 + self.max_arrivals * aw, 0, 0, device)
-        self._arr_off = st.payload_off + B + 1
-        self.offsets, self._h_offsets = st.payload[:B + 1].view(torch.int32), st.h_payload[:B + 1].view(torch.int32)
-        self.arrivals = st.payload[B + 1:].view(torch.int32).view(self.max_arrivals, aw)
-        self._h_arrivals = st.h_payload[B + 1:].view(torch.int32).view(self.max_arrivals, aw)
+        # ONE device buffer, captured by address, uploaded up to the last arrival used: the action, room and layers rows, the
+        # arrival region (an arrival record: byte count, then the headed packet)
+        st = self.stage = ControlStage(B, ("action", "room", "layers"), 0, 0, 0, device, arrivals=(self.max_arrivals, self.tstride))
+        self.offsets, self.arrivals = st.offsets, st.arrivals
         F, P = cfg.fanout, cfg.burst
-        i32 = dict(dtype=torch.int32, device=device)
-        self._sd = torch.zeros(B, forward_def.SD_WORDS, **i32)
-        self._lr = torch.zeros(B, forward_def.LR_WORDS, **i32)
-        self._pick, self._pick_count = torch.zeros(B, P, **i32), torch.zeros(B, **i32)
-        self._routes, self._new_routes = torch.zeros(B, F, **i32), torch.zeros(B, F, **i32)
-        self._out = [torch.zeros(B, F, P, self.tstride, dtype=torch.uint8, device=device) for _ in (0, 1)]
-        self._out_nbytes = [torch.zeros(B, F, P, **i32) for _ in (0, 1)]
+        self._sd, self._lr = self._slot_state(forward_def.SD_WORDS), self._slot_state(forward_def.LR_WORDS)
+        self._pick, self._pick_count = self._slot_state(P), self._slot_state()
+        self._routes, self._new_routes = self._slot_state(F, cleared=-1), self._slot_state(F)
+        self._out = [self._slot_state(F, P, self.tstride, dtype=torch.uint8) for _ in (0, 1)]
+        self._out_nbytes = [self._slot_state(F, P) for _ in (0, 1)]
         self._joined = set()                  # the slots joined since the last hop
-        self._action_live = False             # the mirror's action row is not all zero
-        self.parity = 0
         self.graphs, self.outs = self._capture_pair(self._hop, warmup)
 
     def _hop(self, p: int) -> Tuple[Tensor, Tensor]:
@@ -1638,9 +1619,7 @@ class GraphedForwardHop:
         st.h_row["room"].fill_(-1)
         st.h_row["layers"].fill_(self.n)
         st.dev.copy_(st.host)
-        for t in (self._sd, self._lr, self._pick, self._pick_count, self._new_routes, *self._out, *self._out_nbytes):
-            t.zero_()
-        self._routes.fill_(-1)
+        super()._zero()
 
     def _slot(self, slot) -> int:
         s = int(slot)
@@ -1707,38 +1686,12 @@ class GraphedForwardHop:
         wire.transport_bytes(n, m, frames)]` (host or device), 0 <= A <= max_arrivals.  Returns (out uint8 `[B, fanout, burst, tb]`,
         out_nbytes int32 `[B, fanout, burst]`): row (b, j, k) is the k-th packet of this hop for listener b's route j, cut to its layers
         (0 bytes: none); static views that the next-but-one call overwrites."""
-        for name, v in (("slots", slots), ("nbytes", nbytes)):
-            if isinstance(v, Tensor) and v.is_cuda:
-                raise ValueError(f"forward: {name} must be host ints, not a device tensor")
-        sl = np.asarray(slots.tolist() if isinstance(slots, Tensor) else slots, dtype=np.int64).reshape(-1)
-        nb = np.asarray(nbytes.tolist() if isinstance(nbytes, Tensor) else nbytes, dtype=np.int64).reshape(-1)
-        A, B = len(sl), self.batch
-        if A > self.max_arrivals:
-            raise ValueError(f"forward: {A} arrivals, at most max_arrivals = {self.max_arrivals}")
-        if len(nb) != A:
-            raise ValueError(f"forward: {A} slots but {len(nb)} byte counts")
-        if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or tuple(packets.shape) != (A, self.tstride):
-            raise ValueError(f"forward: packets must be uint8 [{A}, {self.tstride}]")
-        if A and (sl.min() < 0 or sl.max() >= B):
-            raise IndexError(f"forward: a slot outside [0, {B})")
-        order = np.argsort(sl, kind="stable")
+        arr = check_arrivals("forward", slots, packets, nbytes, self.batch, self.max_arrivals, self.tstride)
         st = self.stage
         st.wait()
-        if self._action_live or self._joined:
-            _mark(st.h_row["action"], self._joined)
-            self._action_live = bool(self._joined)
+        if st.one_hop_live or self._joined:   # the join row: 1 for the slots joined since the last hop
+            st.put_one_hop("action", sorted(self._joined), 1)
             self._joined = set()
-        offs = self._h_offsets.numpy()
-        offs[0] = 0
-        offs[1:] = np.cumsum(np.bincount(sl, minlength=B))
-        if A:
-            self._h_arrivals[:A, 0].copy_(torch.from_numpy(np.clip(nb[order], -1, 1 << 20).astype(np.int32)))
-        bytes_of = lambda t: t.view(torch.uint8)[:, 4:4 + self.tstride]
-        if A and not packets.is_cuda:
-            bytes_of(self._h_arrivals[:A]).copy_(packets[torch.from_numpy(order)])
-        st.send(self._arr_off + A * self.arrivals.shape[1])
-        if A and packets.is_cuda:
-            rows = packets if np.array_equal(order, np.arange(A)) else packets[torch.from_numpy(order).to(self.device)]
-            bytes_of(self.arrivals[:A]).copy_(rows)
+        st.send_arrivals(arr, packets)
         st.finish()
         return self._replay()

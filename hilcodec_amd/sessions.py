@@ -3,14 +3,18 @@ the layout and filling of the control stage that carries it to the device.  No d
 module calls into CUDA: the tensors it writes are the stage's host mirror (or plain CPU tensors in the tests)."""
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Sequence, Tuple
 
+import numpy as np
+import torch
 from torch import Tensor
 
 # action row of a hop: ACTION_KEEP, ACTION_ZERO (a fresh start), r >= ACTION_LOAD (load record r - ACTION_LOAD)
 ACTION_KEEP, ACTION_ZERO, ACTION_LOAD = 0, -1, 1
 # hold row of a hop: the slot advances, is held, or (receiver) makes comfort noise from the SID that arrived / while its stream is in DTX
 HOLD_ADVANCE, HOLD_HELD, HOLD_SID, HOLD_SILENT = 0, 1, 2, 3
+# the rows of a control stage whose entries apply to exactly one hop: the upload after a hop that wrote one must clear it on the device
+ONE_HOP_ROWS = ("action", "report", "nack_base", "nack_bitmap")
 
 
 def stage_layout(batch: int, rows: Sequence[str], payload_words: int = 0, loads: int = 0, record_len: int = 0):
@@ -40,6 +44,67 @@ def stage_starts(starts: Dict[int, object], action: Tensor, host_records: Tensor
         if r < len(host):
             host_records[r].copy_(rec)
     return len(host), [rec for _slot, rec in dev]
+
+
+# ---------------------------------------------------------------- one hop's arrivals (GraphedDecodeHop.play, GraphedForwardHop.forward)
+def arrival_width(row_bytes: int) -> int:
+    """the words of an arrival record: the byte count, then the headed packet of at most `row_bytes` bytes"""
+    return 1 + (int(row_bytes) + 3) // 4
+
+
+def arrival_region_words(batch: int, max_arrivals: int, row_bytes: int) -> int:
+    """the payload words of an arrival region: the CSR offsets of the arrivals [batch + 1], then `max_arrivals` records"""
+    return int(batch) + 1 + int(max_arrivals) * arrival_width(row_bytes)
+
+
+def arrival_bytes(records: Tensor, row_bytes: int) -> Tensor:
+    """the packet bytes uint8 [A, row_bytes] of arrival records int32 [A, arrival_width(row_bytes)], as a view"""
+    return records.view(torch.uint8)[:, 4:4 + int(row_bytes)]
+
+
+class Arrivals(NamedTuple):
+    """one hop's arrivals, checked: their number A, the slots in push order, the stable order that groups them by slot, and the byte
+    counts in that order, clipped to [-1, 2^20] (a kernel needs no more to see a bad count)"""
+    count: int
+    slots: np.ndarray
+    order: np.ndarray
+    nbytes: np.ndarray
+
+
+def check_arrivals(who: str, slots, packets, nbytes, batch: int, max_arrivals: int, row_bytes: int) -> Arrivals:
+    """One hop's arrivals in push order — `slots` and `nbytes` A host ints (lists, arrays or host tensors), `packets` uint8 [A,
+    row_bytes] on the host or the device — checked for the caller `who` ("play" / "forward": the messages' prefix) before anything is
+    written: ValueError for a device tensor of ints, more than `max_arrivals`, a length mismatch or another packet shape or dtype,
+    IndexError for a slot outside [0, batch)."""
+    for name, v in (("slots", slots), ("nbytes", nbytes)):
+        if isinstance(v, Tensor) and v.is_cuda:
+            raise ValueError(f"{who}: {name} must be host ints, not a device tensor")
+    sl = np.asarray(slots.tolist() if isinstance(slots, Tensor) else slots, dtype=np.int64).reshape(-1)
+    nb = np.asarray(nbytes.tolist() if isinstance(nbytes, Tensor) else nbytes, dtype=np.int64).reshape(-1)
+    A = len(sl)
+    if A > max_arrivals:
+        raise ValueError(f"{who}: {A} arrivals, at most max_arrivals = {max_arrivals}")
+    if len(nb) != A:
+        raise ValueError(f"{who}: {A} slots but {len(nb)} byte counts")
+    if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or tuple(packets.shape) != (A, row_bytes):
+        raise ValueError(f"{who}: packets must be uint8 [{A}, {row_bytes}]")
+    if A and (sl.min() < 0 or sl.max() >= batch):
+        raise IndexError(f"{who}: a slot outside [0, {batch})")
+    order = np.argsort(sl, kind="stable")
+    return Arrivals(A, sl, order, np.clip(nb[order], -1, 1 << 20).astype(np.int32))
+
+
+def put_arrivals(arr: Arrivals, packets: Tensor, offsets: Tensor, records: Tensor, row_bytes: int) -> None:
+    """checked arrivals -> the mirror's views: the CSR `offsets` int32 [batch + 1], the byte counts of `records` int32 [max_arrivals,
+    arrival_width(row_bytes)] grouped by slot and, where `packets` are on the host, their bytes (packets on the device are copied on
+    the device: ControlStage.send_arrivals).  Records from A on are left as they are: the offsets end at A"""
+    offs = offsets.numpy()
+    offs[0] = 0
+    offs[1:] = np.cumsum(np.bincount(arr.slots, minlength=len(offs) - 1))
+    if arr.count:
+        records[:arr.count, 0].copy_(torch.from_numpy(arr.nbytes))
+        if not packets.is_cuda:
+            arrival_bytes(records[:arr.count], row_bytes).copy_(packets[torch.from_numpy(arr.order)])
 
 
 class SessionQueue:

@@ -91,16 +91,21 @@ def put_row(packets, b, blob):
     packets[b, :len(blob)] = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
 
 
+def arrival_arrays(arrived, tbytes):
+    """[(slot, bytes)] -> (slots, packets uint8 [A, tbytes], nbytes)"""
+    packets = np.zeros((len(arrived), tbytes), dtype=np.uint8)
+    for a, (_, p) in enumerate(arrived):
+        packets[a, :len(p)] = np.frombuffer(p, dtype=np.uint8)
+    return [s for s, _ in arrived], packets, [len(p) for _, p in arrived]
+
+
 def arrival_records(slots, packets, nbytes, tbytes, B, max_a):
-    """the device form of one hop's arrivals, as GraphedDecodeHop.play stages them: records grouped by slot (stable), offsets"""
-    aw = 1 + (tbytes + 3) // 4
-    rec = np.zeros((max_a, aw), dtype=np.int32)
-    order = np.argsort(np.asarray(slots, dtype=np.int64), kind="stable")
-    A = len(slots)
-    rec[:A, 0] = np.asarray(nbytes, dtype=np.int64)[order]
-    rec.view(np.uint8)[:A, 4:4 + tbytes] = np.asarray(packets, dtype=np.uint8).reshape(A, tbytes)[order]
-    offs = np.zeros(B + 1, dtype=np.int32)
-    offs[1:] = np.cumsum(np.bincount(np.asarray(slots, dtype=np.int64), minlength=B))
+    """the device form of one hop's arrivals, as GraphedDecodeHop.play stages them: forward.arrival_records moved to the device.
+    That function clips the byte counts to [-1, 2^20]; the counts given here lie inside that range, so the clip changes nothing"""
+    from hilcodec_amd import forward
+    counts = np.asarray(nbytes, dtype=np.int64)
+    assert counts.size == 0 or (counts.min() >= -1 and counts.max() <= 1 << 20), counts
+    rec, offs = forward.arrival_records(slots, packets, nbytes, tbytes, B, max_a)
     return torch.from_numpy(rec).to(DEV), torch.from_numpy(offs).to(DEV)
 
 

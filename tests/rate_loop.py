@@ -6,6 +6,7 @@ from hilcodec_amd import rate, report, wire
 from hilcodec_amd.jitter import JitterConfig, JitterModel
 from hilcodec_amd.rate import RateConfig, RateModel
 from hilcodec_amd.report import ReportConfig, ReportModel
+from tests.hops import arrival_arrays
 
 N, T = 8, 1                                                  # stages and frames of the loop's sender; its packets carry the header
 LOOP_RATE = RateConfig(min_kbps=2.625, max_kbps=9.0)         # binary-exact: 35 and 120 bits per hop
@@ -61,14 +62,6 @@ class ReportLine:
     def reports_for(self, t):
         slots_blobs = self.line.pop(t, [])
         return [s for s, _ in slots_blobs], [b for _, b in slots_blobs]
-
-
-def arrival_arrays(arrived, tbytes):
-    """[(slot, bytes)] -> (slots, packets uint8 [A, tbytes], nbytes)"""
-    packets = np.zeros((len(arrived), tbytes), dtype=np.uint8)
-    for a, (_, p) in enumerate(arrived):
-        packets[a, :len(p)] = np.frombuffer(p, dtype=np.uint8)
-    return [s for s, _ in arrived], packets, [len(p) for _, p in arrived]
 
 
 def cap_at(caps, t):

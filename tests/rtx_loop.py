@@ -6,6 +6,7 @@ import numpy as np
 from hilcodec_amd import jitter, rtx, wire
 from hilcodec_amd.jitter import JitterConfig, JitterModel
 from hilcodec_amd.rtx import NackConfig, NackModel, RtxConfig, RtxModel
+from tests.hops import arrival_arrays
 
 HOPS = 400
 LOOP_JITTER = JitterConfig(depth=4, capacity=8)
@@ -65,14 +66,6 @@ class Channel:
             else:
                 out.append((s, p))
         return out
-
-
-def arrival_arrays(arrived, tbytes):
-    """[(slot, bytes)] -> (slots, packets uint8 [A, tbytes], nbytes)"""
-    packets = np.zeros((len(arrived), tbytes), dtype=np.uint8)
-    for a, (_, p) in enumerate(arrived):
-        packets[a, :len(p)] = np.frombuffer(p, dtype=np.uint8)
-    return [s for s, _ in arrived], packets, [len(p) for _, p in arrived]
 
 
 def run_models(drops, jcfg=LOOP_JITTER, ncfg=LOOP_NACK, rcfg=LOOP_RTX, hops=HOPS, h0=0, nack=True, drop_rtx=(), B=2, n=4, seed=5):

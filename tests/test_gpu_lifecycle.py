@@ -155,6 +155,57 @@ def test_forced_upload_twin(models, name):
         for slot in range(2 * SIZE):
             diff = first_difference(observe(a.hop, slot), observe(b.hop, slot))
             assert diff is None, L.explain("forced-upload twin", cfg, seeds, k, slot, diff, a)
+    del a.hop.stage.send                                     # the wrapper refers to the driver: a cycle that would keep the hop alive
     skipped = [k for k in range(HOPS) if k not in sent]
     print(f"{name}: uploads skipped on hops {skipped}, predicted {L.skipped_uploads(a.scripts)}")
     assert skipped == L.skipped_uploads(a.scripts)
+
+
+def test_reset_restores_every_per_slot_state(models):
+    """a sender with every option: after 6 hops with a start, a stop, a hold, reports and NACKs, reset() puts every per-slot tensor
+    the allocator registered (_slot_state) back to what it held right after construction, bit for bit — the DTX run counter and the
+    header's hop counter among them — and the same 6 hops then give the first run's packets, byte counts, indices and views"""
+    import torch
+    from hilcodec_amd import wire
+    from hilcodec_amd.graph_step import GraphedEncodeHop
+    from hilcodec_amd.rate import RateConfig
+    from hilcodec_amd.rtx import RtxConfig
+    model, target = models["tx-all"]
+    B, hops = 4, 6
+    hop = GraphedEncodeHop(model, B, HOP, L.N, DEV, sessions=True, input_rate=L.INPUT_RATE, fec_stages=L.M, header=True, dtx=L.DTX,
+                           vbr=L.vbr_config(target), fec_adapt=L.FEC_ADAPT, rtx=RtxConfig(history=4, per_hop=2),
+                           rate=RateConfig(min_kbps=6.0, max_kbps=12.0, start_kbps=6.0, burst_hops=1))
+    # every feature's state went through the allocator: previous codes, DTX run, hop counter, credit, adapt row and switch, the
+    # three history tensors with the two retransmission outputs, rate row and ceiling
+    assert len(hop._scratch) == 13
+    fresh = [t.clone() for t, *_ in hop._scratch]
+    xs = [synth.synth_clips(B, HOP * L.INPUT_RATE // 24000, seed=50 + k).to(DEV) for k in range(hops)]
+    xs[4][0], xs[5][0] = 0.0, 0.0                            # slot 0 ends in silence: its DTX run counter is not 0 at the reset
+    views = slot_views(hop) + ["rtx_packets", "rtx_nbytes", "rtx_state", "n_ceil", "rate_state"]
+
+    def run():
+        seen = []
+        for k in range(hops):
+            if k == 1:
+                hop.start(2)
+            if k == 2:
+                hop.stop(1)
+            opt = {}
+            if k in (2, 4):
+                opt["reports"] = ([0, 3], [wire.pack_report(k, 0, 0)] * 2)    # two calm reports: slots 0 and 3 switch FEC off
+            if k in (3, 5):
+                opt["nacks"] = ([0, 2], [wire.pack_nack(k - 2, 1), wire.pack_nack(0, 3)])
+            packets, nbytes = hop.step(xs[k], hold=[3] if k == 3 else None, **opt)
+            seen.append([packets.clone(), nbytes.clone(), hop.indices.clone()] + [getattr(hop, name).clone() for name in views])
+        return seen
+
+    first = run()
+    moved = [not torch.equal(t, f) for (t, *_), f in zip(hop._scratch, fresh)]
+    assert all(moved), moved                                 # the comparison below is not empty: every tensor did change
+    hop.reset()
+    for i, ((t, cleared, _), f) in enumerate(zip(hop._scratch, fresh)):
+        assert torch.equal(t, f), f"registered tensor {i} {tuple(t.shape)} {t.dtype} (cleared = {cleared}) differs after reset()"
+    assert hop.stopped == ()
+    for k, (a, b) in enumerate(zip(first, run())):
+        for name, x, y in zip(["packets", "nbytes", "indices"] + views, a, b):
+            assert torch.equal(x, y), f"hop {k}: {name} differs on the second run"

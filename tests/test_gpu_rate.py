@@ -10,8 +10,8 @@ from hilcodec_amd import dtx, jitter, rate, report, rtx, synth, wire
 from hilcodec_amd.rate import RateConfig, RateModel
 from hilcodec_amd.report import FecAdaptConfig, report_word
 from hilcodec_amd.vbr import VbrConfig
-from tests.hops import caches_equal
-from tests.rate_loop import LOOP_JITTER, LOOP_RATE, LOOP_REPORT, Link, ReportLine, Trace, arrival_arrays, run_models
+from tests.hops import arrival_arrays, caches_equal
+from tests.rate_loop import LOOP_JITTER, LOOP_RATE, LOOP_REPORT, Link, ReportLine, Trace, run_models
 
 pytestmark = pytest.mark.gpu
 

@@ -145,7 +145,7 @@ def test_pipelined_hop_refuses_sessions():
 @pytest.mark.parametrize("B", [1, 5, 1024])
 def test_stage_layout_matches_the_three_layouts(B):
     """sessions.stage_layout gives the word offsets the three hops used to compute by hand (written out here as literals)"""
-    from hilcodec_amd.sessions import stage_layout
+    from hilcodec_amd.sessions import arrival_region_words, stage_layout
     for loads, L in ((0, 37), (3, 37)):
         # GraphedHop / GraphedEncodeHop: action, n, hold, then the records
         rows, pay, rec, total = stage_layout(B, ("action", "n_slot", "hold"), 0, loads, L)
@@ -166,7 +166,8 @@ def test_stage_layout_matches_the_three_layouts(B):
         for max_arrivals in (1, 2 * B, 2 * B + 1):
             for tstride in (3, 13, 16, 257):
                 aw = 1 + (tstride + 3) // 4
-                rows, pay, rec, total = stage_layout(B, ("action", "hold"), B + 1 + max_arrivals * aw, loads, L)
+                assert arrival_region_words(B, max_arrivals, tstride) == B + 1 + max_arrivals * aw
+                rows, pay, rec, total = stage_layout(B, ("action", "hold"), arrival_region_words(B, max_arrivals, tstride), loads, L)
                 assert rows == {"action": 0, "hold": B} and pay == 2 * B
                 assert pay + B + 1 == 3 * B + 1                                    # where the arrival records begin
                 assert rec == 3 * B + 1 + max_arrivals * aw and total == rec + loads * L
@@ -199,3 +200,96 @@ def test_stage_starts_rule():
     assert action.tolist() == [3, -1, 4, -1, 1, 2]
     assert h_records[:, 0].tolist() == [4.0, 5.0, 7.0, 0.0] and bool((h_records[:3] == h_records[:3, :1]).all())
     assert stage_starts({}, action.zero_(), h_records) == (0, []) and not action.any()
+
+
+# ---------------------------------------------------------------- one hop's arrivals (sessions.check_arrivals / put_arrivals)
+class _OnDevice(torch.Tensor):
+    """a host tensor that says it lives on the device: what the refusals look at, without a device"""
+    is_cuda = True
+
+
+def _stage_arrivals(who, slots, packets, nbytes, B, max_a, tb, offsets, records):
+    """what GraphedDecodeHop.play and GraphedForwardHop.forward do with a hop's arrivals, on plain host tensors"""
+    from hilcodec_amd.sessions import check_arrivals, put_arrivals
+    arr = check_arrivals(who, slots, packets, nbytes, B, max_a, tb)
+    put_arrivals(arr, packets, offsets, records, tb)
+    return arr
+
+
+@pytest.mark.parametrize("B", [1, 5, 64])
+@pytest.mark.parametrize("tb", [13, 16])
+def test_arrival_staging_matches_the_numpy_statement(B, tb):
+    """seeded arrivals — unsorted slots with repeats, byte counts inside and outside [-1, 2^20], slots and counts as lists, arrays
+    and host tensors — staged by sessions.check_arrivals / put_arrivals equal forward.arrival_records bit for bit, offsets and
+    records, for A in {0, 1, max_arrivals}"""
+    import numpy as np
+    from hilcodec_amd import forward
+    from hilcodec_amd.sessions import arrival_region_words, arrival_width
+    max_a = 2 * B + 1
+    aw = arrival_width(tb)
+    assert aw == 1 + (tb + 3) // 4 and arrival_region_words(B, max_a, tb) == B + 1 + max_a * aw
+    rng = np.random.default_rng(100 * B + tb)
+    wild = np.array([-7, -2, -1, 0, 1 << 20, (1 << 20) + 1, 1 << 31, -(1 << 40)], dtype=np.int64)
+    for A in (0, 1, max_a):
+        slots = rng.integers(0, B, A)
+        if A == max_a and B > 1:
+            assert len(set(slots.tolist())) < A and list(slots) != sorted(slots)       # repeats, and not already grouped
+        nbytes = np.where(rng.random(A) < 0.5, rng.integers(0, tb + 1, A), rng.choice(wild, A))
+        if A == max_a:
+            nbytes[:len(wild)] = wild[:A]
+        packets = rng.integers(0, 256, (A, tb), dtype=np.uint8)
+        packets[:, 0] = np.arange(A) & 0xFF                                            # the push order, readable in the records
+        rec, offs = forward.arrival_records(slots, packets, nbytes, tb, B, max_a)
+        forms = {"list": list, "array": np.asarray, "tensor": lambda v: torch.from_numpy(np.asarray(v))}
+        for name, form in forms.items():
+            offsets, records = torch.zeros(B + 1, dtype=torch.int32), torch.zeros(max_a, aw, dtype=torch.int32)
+            arr = _stage_arrivals("play", form(slots.tolist()), torch.from_numpy(packets), form(nbytes.tolist()), B, max_a, tb,
+                                  offsets, records)
+            assert arr.count == A and arr.order.tolist() == sorted(range(A), key=lambda a: slots[a]), name
+            assert np.array_equal(offsets.numpy(), offs) and offsets.numpy().dtype == offs.dtype, name
+            assert np.array_equal(records.numpy(), rec) and records.numpy().dtype == rec.dtype, name
+        # grouped by slot, and within a slot in push order; the counts clipped
+        got = records.numpy()
+        for b in range(B):
+            pushed = [a for a in range(A) if slots[a] == b]
+            lo, hi = int(offsets[b]), int(offsets[b + 1])
+            assert got.view(np.uint8)[lo:hi, 4].tolist() == [a & 0xFF for a in pushed]
+            assert got[lo:hi, 0].tolist() == [int(min(max(nbytes[a], -1), 1 << 20)) for a in pushed]
+
+
+@pytest.mark.parametrize("who", ["play", "forward"])
+def test_arrival_staging_refusals(who):
+    """every refusal of play / forward comes from the one function, with the caller's name in front, before anything is written"""
+    B, max_a, tb = 4, 6, 13
+    packets = torch.zeros(3, tb, dtype=torch.uint8)
+    device_ints = torch.Tensor._make_subclass(_OnDevice, torch.zeros(3))
+    assert isinstance(device_ints, torch.Tensor) and device_ints.is_cuda
+    cases = [
+        (ValueError, f"{who}: slots must be host ints, not a device tensor", (device_ints, packets, [1, 2, 3])),
+        (ValueError, f"{who}: nbytes must be host ints, not a device tensor", ([0, 1, 2], packets, device_ints)),
+        (ValueError, f"{who}: 7 arrivals, at most max_arrivals = 6", ([0] * 7, torch.zeros(7, tb, dtype=torch.uint8), [1] * 7)),
+        (ValueError, f"{who}: 3 slots but 2 byte counts", ([0, 1, 2], packets, [1, 2])),
+        (ValueError, f"{who}: packets must be uint8 [3, 13]", ([0, 1, 2], torch.zeros(3, tb + 1, dtype=torch.uint8), [1, 2, 3])),
+        (ValueError, f"{who}: packets must be uint8 [3, 13]", ([0, 1, 2], torch.zeros(2, tb, dtype=torch.uint8), [1, 2, 3])),
+        (ValueError, f"{who}: packets must be uint8 [3, 13]", ([0, 1, 2], torch.zeros(3, tb, dtype=torch.int32), [1, 2, 3])),
+        (ValueError, f"{who}: packets must be uint8 [3, 13]", ([0, 1, 2], packets.numpy(), [1, 2, 3])),
+        (IndexError, f"{who}: a slot outside [0, 4)", ([0, 4, 2], packets, [1, 2, 3])),
+        (IndexError, f"{who}: a slot outside [0, 4)", ([0, -1, 2], packets, [1, 2, 3])),
+    ]
+    offsets = torch.full((B + 1,), 77, dtype=torch.int32)
+    records = torch.full((max_a, 1 + (tb + 3) // 4), 77, dtype=torch.int32)
+    for kind, message, (slots, pk, nbytes) in cases:
+        with pytest.raises(kind) as e:
+            _stage_arrivals(who, slots, pk, nbytes, B, max_a, tb, offsets, records)
+        assert str(e.value) == message and type(e.value) is kind
+        assert bool((offsets == 77).all()) and bool((records == 77).all())
+    _stage_arrivals(who, [3, 0, 3], packets, [5, 6, 7], B, max_a, tb, offsets, records)       # and an accepted hop does write
+    assert offsets.tolist() == [0, 1, 1, 1, 3] and records[:3, 0].tolist() == [6, 5, 7] and bool((records[3:] == 77).all())
+
+
+def test_control_stage_refuses_a_payload_beside_arrivals():
+    """the arrival region is the stage's whole payload: a payload size of the caller's own beside it is refused, before anything
+    is allocated"""
+    from hilcodec_amd.graph_step import ControlStage
+    with pytest.raises(ValueError, match="payload_words must be 0 with arrivals"):
+        ControlStage(4, ("action", "hold"), 5, 0, 0, torch.device("cpu"), arrivals=(2, 13))

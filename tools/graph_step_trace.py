@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 B, HOP, N, M, K, HOPS = 16, 320, 8, 2, 8, 6
 COMBOS = ["hop_g1", "hop_g2", "hop_sessions", "hop_sessions_g2", "pipelined_g1", "pipelined_g2",
           "send_plain", "send_sessions", "send_all", "recv_plain", "recv_sessions", "recv_all_but_jitter", "recv_jitter_only",
-          "recv_jitter_all"]
+          "recv_jitter_all", "send_feedback", "recv_jitter_feedback", "forward"]
 MARK = "erfinv"
 
 
@@ -65,7 +65,13 @@ import numpy as np
 import torch
 
 from hilcodec_amd import dtx, graph_step, synth, wire
-from hilcodec_amd.jitter import JitterConfig
+from hilcodec_amd.forward import ForwardConfig
+from hilcodec_amd.jitter import AdaptConfig, JitterConfig
+from hilcodec_amd.mixer import MixConfig
+from hilcodec_amd.rate import RateConfig
+from hilcodec_amd.report import FecAdaptConfig, ReportConfig
+from hilcodec_amd.rtx import NackConfig, RtxConfig
+from hilcodec_amd.vbr import VbrConfig
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--log", required=True)
@@ -183,9 +189,52 @@ def run_recv(sessions, everything):
         h.step(pk, n_list, **opt)
 
 
-def run_jitter(everything):
+def run_send_feedback():
+    """the sender with vbr (cap), fec_adapt, rtx and rate: reports and NACKs on hops 2 and 3, then two hops that only clear them"""
+    h = graph_step.GraphedEncodeHop(model, B, HOP, N, dev, sessions=True, fec_stages=M, header=True,
+                                    vbr=VbrConfig(12.0, cap_kbps=4.5, burst_hops=2), fec_adapt=FecAdaptConfig(), rtx=RtxConfig(),
+                                    rate=RateConfig(min_kbps=6.0, max_kbps=12.0))
+    for k in range(HOPS):
+        if k == 1:
+            h.start(2)
+            h.stop(7)
+        opt = {}
+        if k in (2, 3):
+            opt["reports"] = ([0, 5, 9], [wire.pack_report(k, 40 * (k - 1), 0)] * 3)
+            opt["nacks"] = ([4, 5], torch.tensor([list(wire.pack_nack(k - 2, 1))] * 2, dtype=torch.uint8))
+        h.step(xs[k], hold=[1, 12] if k == 3 else None, **opt)
+    h.reset()
+    h.step(xs[0])
+
+
+def run_forward():
+    """the forwarding hop: a join, a leave and a set_layers between hops, host packets on even hops and device packets on odd hops"""
+    h = graph_step.GraphedForwardHop(B, 1, N, dev, fec_stages=M, cfg=ForwardConfig(fanout=3))
+    rng = np.random.default_rng(6)
+    for b in range(B):
+        h.join(b, b // 8)
+    for k in range(HOPS):
+        order = rng.permutation(B).tolist() if k < 4 else list(range(B))           # in slot order: no gather on the device path
+        slots = [b for b in order if (k + b) % 5]
+        rows = rng.integers(0, 256, (len(slots), h.tstride), dtype=np.uint8)
+        rows[:, 0], rows[:, 1], rows[:, 2] = k >> 8, k & 0xFF, (wire.FEC_BIT if k else 0) | N
+        pk = torch.from_numpy(rows)
+        if k % 2:
+            pk = pk.to(dev)
+        if k == 2:
+            h.join(3, 1)
+            h.leave(12)
+        if k == 3:
+            h.set_layers(5, 4)
+        h.forward(slots, pk, [h.tstride] * len(slots))
+
+
+def run_jitter(everything, feedback=False):
     kw = dict(conceal=True, output_rate=48000, fec_stages=M, cng_order=K) if everything else {}
-    h = graph_step.GraphedDecodeHop(model, B, 1, N, dev, sessions=True, jitter=JitterConfig(depth=2, capacity=8), **kw)
+    jcfg = JitterConfig(depth=2, capacity=8, adapt=AdaptConfig() if feedback else None)
+    if feedback:
+        kw.update(mix=MixConfig(2), report=ReportConfig(8, 4), nack=NackConfig())
+    h = graph_step.GraphedDecodeHop(model, B, 1, N, dev, sessions=True, jitter=jcfg, **kw)
     m = M if everything else 0
     rng = np.random.default_rng(4)
     plain, wide = wire.packet_bytes(N, 1), wire.fec_packet_bytes(N, m, 1) if m else wire.packet_bytes(N, 1)
@@ -215,6 +264,10 @@ def run_jitter(everything):
             h.stop(7)
         if k == 4:
             h.start(7)
+        if feedback and k == 2:
+            h.join(5, 3)
+        if feedback and k == 4:
+            h.leave(6)
         h.play(slots, pk, nbytes, hold=[1, 12] if k == 3 else None)
 
 
@@ -223,7 +276,8 @@ RUN = {"hop_g1": lambda: run_hop(1, False), "hop_g2": lambda: run_hop(2, False),
        "send_plain": lambda: run_send(False, False), "send_sessions": lambda: run_send(True, False),
        "send_all": lambda: run_send(True, True), "recv_plain": lambda: run_recv(False, False),
        "recv_sessions": lambda: run_recv(True, False), "recv_all_but_jitter": lambda: run_recv(True, True),
-       "recv_jitter_only": lambda: run_jitter(False), "recv_jitter_all": lambda: run_jitter(True)}
+       "recv_jitter_only": lambda: run_jitter(False), "recv_jitter_all": lambda: run_jitter(True),
+       "send_feedback": run_send_feedback, "recv_jitter_feedback": lambda: run_jitter(True, True), "forward": run_forward}
 
 host = {}
 torch.cuda.synchronize()
