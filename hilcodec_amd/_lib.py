@@ -84,6 +84,8 @@ SIGNATURES = {
     "hilc_jitter_adapt_step": [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p],
     "hilc_mix_levels": [_p, _p, _p, _i, _i, _p],
     "hilc_mix_rooms": [_p, _p, _p, _i, _p, _p, _i, _i, _p],
+    "hilc_mix_gains": [_p, _p, _p, _p] + [_d] * 8 + [_i, _i, _p],
+    "hilc_mix_rooms_dyn": [_p, _p, _p, _i, _p, _p, _d, _d, _i, _p, _p, _p, _i, _i, _p],
     "hilc_vbr_select": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _p],
     "hilc_rx_report": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
     "hilc_fec_adapt": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],

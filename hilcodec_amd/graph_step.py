@@ -1167,6 +1167,13 @@ class GraphedDecodeHop(_Hop):
     score of every slot; a `start` clears a slot's score inside the graph.  Graph: hilc_mix_levels and hilc_mix_rooms are the last two
     launches, after the final hilc_state_slots_hold and the hilc_cng_synth behind it: comfort noise is mixed as noise, a held slot as
     zeros, and a held listener still gets its mix.  `mix=None` captures exactly the graph without the mixer.
+    `MixConfig(top_k, level=mixer.LevelConfig(...))`: per-speaker levelling, one more launch (hilc_mix_gains behind hilc_mix_levels):
+    every slot's gain follows its smoothed power towards the target level, hops under the gate do not count, and the speakers' rows
+    enter the sums with their gains; `gains` (float64 `[B, 2]`) is every slot's gain at the hop's start and end.
+    `MixConfig(top_k, limit=mixer.LimitConfig(...))`: a per-listener limiter with state in place of the clamp; `limiter_state` (float64
+    `[B, 2]`) is every listener's envelope and gain.  With either, hilc_mix_rooms_dyn is the last launch in place of hilc_mix_rooms; a
+    `start` or a resume clears a slot's rows inside the graph; `export` and a resume carry none.  `MixConfig(top_k)` captures exactly the
+    two launches above.
     `report` = report.ReportConfig(window, interval) (needs `jitter`: the rule reads the jitter state, the explicit `step()` has no
     report): receiver reports (report.py).  One hilc_rx_report directly after the jitter step classes each slot's hop from its jitter
     counters (decoded, repaired by FEC, lost, noise), keeps a sliding window of the last `window` decoded / repaired / lost hops and
@@ -1260,6 +1267,11 @@ class GraphedDecodeHop(_Hop):
             # marks; the room row (device, captured by address) and its pinned host mirror
             L = hop_samples(self.frames, self.output_rate) if self.rs is not None else HOP * self.frames
             self._score = self._slot_state(dtype=torch.float64)
+            # with levelling: the hop-start and hop-end gain and the smoothed power (hilc_mix_gains); with the limiter: its envelope
+            # and gain (hilc_mix_rooms_dyn); cleared to (1, 1), 0 and (0, 1)
+            self._mix_gains = self._slot_state(2, dtype=torch.float64, cleared=1) if mix.level is not None else None
+            self._mix_power = self._slot_state(dtype=torch.float64) if mix.level is not None else None
+            self._mix_limiter = self._slot_state(2, dtype=torch.float64, cleared={1: 1}) if mix.limit is not None else None
             self._mixed = torch.zeros(2, B, 1, L, device=device)
             self._speakers = torch.zeros(B, dtype=torch.int32, device=device)
             self._room = torch.full((B,), -1, dtype=torch.int32, device=device)
@@ -1337,9 +1349,15 @@ class GraphedDecodeHop(_Hop):
             # the final hold treated the CN slots (hold 2 / 3) as held: their caches are as they were, the noise overwrites the zeros
             ops.cng_synth(self.packets, self.hold, self._cn, wav, self._cn_gains, self.cng_order, self.action)
         if self.mix is not None:
-            # the graph's last two launches: the rows are final (noise written, held rows zero)
+            # the graph's last two launches (three with levelling): the rows are final (noise written, held rows zero)
             ops.mix_levels(wav, self._score, self.action)
-            ops.mix_rooms(wav, self._room, self._score, self.mix.top_k, self._mixed[p], self._speakers)
+            if self.mix.level is not None:
+                ops.mix_gains(wav, self._mix_gains, self._mix_power, self.mix.level, self.action)
+            if self.mix.level is not None or self.mix.limit is not None:
+                ops.mix_rooms_dyn(wav, self._room, self._score, self.mix.top_k, self._mixed[p], self._speakers, self._mix_gains,
+                                  self._mix_limiter, self.mix.limit, self.action)
+            else:
+                ops.mix_rooms(wav, self._room, self._score, self.mix.top_k, self._mixed[p], self._speakers)
         return wav
 
     # ---------------------------------------------------------------- room mixing
@@ -1391,6 +1409,20 @@ class GraphedDecodeHop(_Hop):
         """float64 `[B]` device view: every slot's peak-hold score after the last hop.  Read-only: written by the graph."""
         self._need(self.mix is not None, "levels", "mix=MixConfig(...)")
         return self._score
+
+    @property
+    def gains(self) -> Tensor:
+        """float64 `[B, 2]` device view: every slot's levelling gain at the start and at the end of the last hop ((1, 1) as cleared).
+        Read-only: written by the graph."""
+        self._need(self.mix is not None and self.mix.level is not None, "gains", "mix=MixConfig(..., level=LevelConfig(...))")
+        return self._mix_gains
+
+    @property
+    def limiter_state(self) -> Tensor:
+        """float64 `[B, 2]` device view: every listener's limiter envelope and gain after the last hop ((0, 1) as cleared).
+        Read-only: written by the graph."""
+        self._need(self.mix is not None and self.mix.limit is not None, "limiter_state", "mix=MixConfig(..., limit=LimitConfig(...))")
+        return self._mix_limiter
 
     def _check(self, packets: Tensor, n_per_stream, held=(), fec=()) -> Tensor:
         """n_per_stream as a tensor; the entries of `held` slots are not range-checked and become the graph's n, those of `fec`

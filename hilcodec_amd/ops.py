@@ -1116,6 +1116,37 @@ def _mix_rooms(wav, room, score, top_k, mixed, speakers):
 _register("mix_rooms", "(Tensor wav, Tensor room, Tensor score, int top_k, Tensor(a!) mixed, Tensor(b!) speakers) -> ()", _mix_rooms,
           lambda wav, room, score, top_k, mixed, speakers: None)
 
+
+def _mix_gains(wav, gains, power, action, gate2, lo, hi, up, down, min_gain, max_gain, smooth):
+    B, L = _mix_rows("mix_gains", wav)
+    if gains.shape != (B, 2) or power.shape != (B,) or (action is not None and action.numel() != B):
+        raise RuntimeError(f"mix_gains: gains must be float64 [{B}, 2], power float64 [{B}] and action int32 [{B}]")
+    check(lib.hilc_mix_gains(_ptr(wav), _ptr(gains, torch.float64), _ptr(power, torch.float64), _ptr(action, torch.int32), gate2, lo,
+                             hi, up, down, min_gain, max_gain, smooth, B, L, _stream()), "hilc_mix_gains")
+
+
+_register("mix_gains", "(Tensor wav, Tensor(a!) gains, Tensor(b!) power, Tensor? action, float gate2, float lo, float hi, float up, "
+          "float down, float min_gain, float max_gain, float smooth) -> ()", _mix_gains,
+          lambda wav, gains, power, action, gate2, lo, hi, up, down, min_gain, max_gain, smooth: None)
+
+
+def _mix_rooms_dyn(wav, room, score, top_k, gains, limiter, ceiling, release, sub, action, mixed, speakers):
+    B, L = _mix_rows("mix_rooms_dyn", wav)
+    if room.shape != (B,) or score.shape != (B,) or speakers.shape != (B,) or (action is not None and action.numel() != B):
+        raise RuntimeError(f"mix_rooms_dyn: room, score, speakers and action must be [{B}]")
+    if (gains is not None and gains.shape != (B, 2)) or (limiter is not None and limiter.shape != (B, 2)):
+        raise RuntimeError(f"mix_rooms_dyn: gains and limiter must be float64 [{B}, 2]")
+    if mixed.shape != wav.shape or mixed.data_ptr() == wav.data_ptr():
+        raise RuntimeError(f"mix_rooms_dyn: mixed must be [{B}, 1, {L}] and a buffer other than wav")
+    check(lib.hilc_mix_rooms_dyn(_ptr(wav), _ptr(room, torch.int32), _ptr(score, torch.float64), top_k, _ptr(gains, torch.float64),
+                                 _ptr(limiter, torch.float64), ceiling, release, sub, _ptr(action, torch.int32), _ptr(mixed),
+                                 _ptr(speakers, torch.int32), B, L, _stream()), "hilc_mix_rooms_dyn")
+
+
+_register("mix_rooms_dyn", "(Tensor wav, Tensor room, Tensor score, int top_k, Tensor? gains, Tensor(a!)? limiter, float ceiling, "
+          "float release, int sub, Tensor? action, Tensor(b!) mixed, Tensor(c!) speakers) -> ()", _mix_rooms_dyn,
+          lambda wav, room, score, top_k, gains, limiter, ceiling, release, sub, action, mixed, speakers: None)
+
 # ======================================================================================================
 # quality-targeted variable bitrate of the sender (graph_step.GraphedEncodeHop(vbr=); definition: hilcodec_amd/vbr.py; semantics:
 # include/hilcodec_amd.h)
@@ -1926,20 +1957,51 @@ def mix_rooms(wav: Tensor, room: Tensor, score: Tensor, top_k: int, mixed: Tenso
     _OPS.mix_rooms(wav, room, score, int(top_k), mixed, speakers)
 
 
-def room_mix(wav: Tensor, room: Tensor, score: Optional[Tensor] = None, top_k: int = 3) -> Tuple[Tensor, Tensor, Tensor]:
-    """`hilcodec_amd.mix_rooms`: one hop of the room mixer for callers without a graph (two launches; mixer.MixModel bit for bit).
-    wav fp32 `[B, 1, L]` and room int32 `[B]` on the GPU; `score` float64 `[B]`: the state returned by the previous call (updated in
-    place; None: a fresh one).  Returns (mixed fp32 `[B, 1, L]`, speakers int32 `[B]`, score)."""
-    from .mixer import MixConfig
+def mix_gains(wav: Tensor, gains: Tensor, power: Tensor, level, action: Optional[Tensor] = None) -> None:
+    """The mixer's levelling step (mixer.py, "Gain"), in place: per slot `gains` (float64 `[B, 2]`) becomes (the previous hop-end gain,
+    this hop's end gain) and `power` (float64 `[B]`) the smoothed power, by the rule of `level` (a mixer.LevelConfig) on the energy of
+    the slot's `wav` row; a slot with an `action` starts from gains (1, 1) and power 0."""
+    _OPS.mix_gains(wav, gains, power, action, level.gate2, level.lo, level.hi, float(level.up), float(level.down),
+                   float(level.min_gain), float(level.max_gain), float(level.smooth))
+
+
+def mix_rooms_dyn(wav: Tensor, room: Tensor, score: Tensor, top_k: int, mixed: Tensor, speakers: Tensor, gains: Optional[Tensor] = None,
+                  limiter: Optional[Tensor] = None, limit=None, action: Optional[Tensor] = None) -> None:
+    """`mix_rooms` with levelled terms (`gains` float64 `[B, 2]` as `mix_gains` left it) and / or the limiter of `limit` (a
+    mixer.LimitConfig; its state `limiter` float64 `[B, 2]`, in place) instead of the clamp (mixer.py, "Mix" and "Limit"); a slot with an
+    `action` starts from limiter (0, 1).  Neither row: `mix_rooms`."""
+    if (limiter is None) != (limit is None):
+        raise RuntimeError("mix_rooms_dyn: limiter (the state row) and limit (its LimitConfig) come together")
+    ceiling, release, sub = (1.0, 0.5, 16) if limit is None else (float(limit.ceiling), float(limit.release), int(limit.sub))
+    _OPS.mix_rooms_dyn(wav, room, score, int(top_k), gains, limiter, ceiling, release, sub, action, mixed, speakers)
+
+
+def room_mix(wav: Tensor, room: Tensor, score: Optional[Tensor] = None, top_k: int = 3,
+             dynamics=None) -> Tuple[Tensor, Tensor, Tensor]:
+    """`hilcodec_amd.mix_rooms`: one hop of the room mixer for callers without a graph (two launches, three with levelling;
+    mixer.MixModel bit for bit).  wav fp32 `[B, 1, L]` and room int32 `[B]` on the GPU; `score` float64 `[B]`: the state returned by the
+    previous call (updated in place; None: a fresh one); `dynamics`: a mixer.Dynamics for B slots on wav's device, whose levelling and
+    limiter rows are updated in place (None: the plain clamped sum).  Returns (mixed fp32 `[B, 1, L]`, speakers int32 `[B]`, score)."""
+    from .mixer import Dynamics, MixConfig
     top_k = int(MixConfig(top_k).top_k)
+    if dynamics is not None and not isinstance(dynamics, Dynamics):
+        raise ValueError(f"mix_rooms: dynamics must be a mixer.Dynamics or None, got {dynamics!r}")
     wav = wav.contiguous()
     B = wav.shape[0]
+    if dynamics is not None and (dynamics.batch != B or dynamics.device.type != wav.device.type
+                                 or (dynamics.device.index is not None and dynamics.device.index != wav.device.index)):
+        raise ValueError(f"mix_rooms: dynamics holds {dynamics.batch} slots on {dynamics.device}, wav has {B} on {wav.device}")
     if score is None:
         score = torch.zeros(B, dtype=torch.float64, device=wav.device)
     mixed = torch.empty_like(wav)
     speakers = torch.empty(B, dtype=torch.int32, device=wav.device)
     mix_levels(wav, score)
-    mix_rooms(wav, room, score, top_k, mixed, speakers)
+    if dynamics is None or (dynamics.level is None and dynamics.limit is None):
+        mix_rooms(wav, room, score, top_k, mixed, speakers)
+        return mixed, speakers, score
+    if dynamics.level is not None:
+        mix_gains(wav, dynamics.gains, dynamics.power, dynamics.level)
+    mix_rooms_dyn(wav, room, score, top_k, mixed, speakers, dynamics.gains, dynamics.limiter, dynamics.limit)
     return mixed, speakers, score
 
 

@@ -37,7 +37,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream); and the selective forwarding hop int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick, int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream) and int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers, const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream) with per-speaker levelling and a limiter int hilc_mix_gains(const float* wav, double* gains, double* power, const int* action, double gate2, double lo, double hi, double up, double down, double min_gain, double max_gain, double smooth, int B, int L, void* stream) and int hilc_mix_rooms_dyn(const float* wav, const int* room, const double* score, int top_k, const double* gains, double* limiter, double ceiling, double release, int sub, const int* action, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream); and the selective forwarding hop int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick, int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream) and int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers, const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -488,8 +488,12 @@ int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const fl
 #define HILC_JITTER_AD_RESYNC 11
 #define HILC_JITTER_AD_WORDS 12
 
-/* per-room mixing (hilcodec_amd/mixer.py): the most speakers of a room */
+/* per-room mixing (hilcodec_amd/mixer.py): the most speakers of a room; the limiter's sub-frame (LimitConfig.sub) in samples, and the
+ * longest hop it takes (at most HILC_MIXER_MAX_LIMIT_L / HILC_MIXER_MIN_SUB = 512 sub-frames) */
 #define HILC_MIXER_MAX_TOP_K 8
+#define HILC_MIXER_MIN_SUB 16
+#define HILC_MIXER_MAX_SUB 512
+#define HILC_MIXER_MAX_LIMIT_L 8192
 
 /* receiver reports and loss-adaptive FEC (hilcodec_amd/report.py).  Report row, RP_WORDS words: RP_SEQ, RP_LOSS, RP_RESIDUAL (the
  * last report), RP_PHASE, RP_N, RP_F, RP_L, RP_HEAD (the interval phase, the window's counts and head), RP_DECODED .. RP_NOISE (the
@@ -799,6 +803,33 @@ int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arri
 int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream);
 int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L,
                    void* stream);
+
+/* ---- per-speaker levelling and a limiter for the room mixer (additive under ABI 16) ------------------------------------------------
+ * Two entry points added WITHOUT a version bump, as the entry points above; hilc_mix_levels and hilc_mix_rooms are unchanged.  The
+ * definition, bit for bit, is hilcodec_amd/mixer.py (LevelConfig, LimitConfig); every float64 operation below is one operation rounded
+ * on its own.  A slot with action[b] != 0 (action optional int32 [B]) first takes its rows as cleared: gains (1, 1), power 0, limiter
+ * (0, 1).
+ * hilc_mix_gains: gains float64 [B][2] (the hop-start and hop-end gain), power float64 [B], in place, every slot on every hop.  E as
+ * in hilc_mix_levels, m = E / L, g0 = the previous gains[b][1], pw = the previous power[b].  If m >= gate2: pw = m when pw == 0, else
+ * pw + smooth (m - pw); v = (g0 g0) pw; v < lo: g1 = min(g0 up, max_gain); v > hi: g1 = max(g0 down, min_gain); else g1 = g0.
+ * Otherwise pw and g1 = g0 stay.  gains[b] = (g0, g1), power[b] = pw.  One wave per slot.  Constants outside gate2 > 0, 0 < lo < hi,
+ * up > 1, 0 < down < 1, 0 < min_gain <= 1 <= max_gain, 0 < smooth <= 1: HILC_ERR_UNSUPPORTED.
+ * hilc_mix_rooms_dyn: hilc_mix_rooms (the same selection, on the raw score) with two optional rows.  gains (NULL: none), as
+ * hilc_mix_gains left it: speaker j's sample i enters the sum as fp32((double)wav[j][i] (g0 + (g1 - g0) ((double)(i + 1) / (double)L)))
+ * with j's (g0, g1).  limiter float64 [B][2] (NULL: none, the clamp of hilc_mix_rooms), the envelope and the gain, in place: on the
+ * listener's sum acc (a row of zeros without terms or for room[b] < 0), sub-frame s = samples [s sub, min((s + 1) sub, L)), n_s of
+ * them: p_s = max |acc[i]| (fp32), e_s = max(p_s, release e_(s-1)), G_s = ceiling / e_s when e_s > ceiling, else 1; the sample at offset
+ * k of sub-frame s takes g = G_s when G_s <= G_(s-1), else G_(s-1) + (G_s - G_(s-1)) ((double)(k + 1) / (double)n_s); mixed =
+ * min(max(fp32((double)acc g), -1), 1); limiter[b] = (e_last, G_last).  So |mixed| <= fp32(ceiling) up to one fp32 ulp.  With a limiter:
+ * sub outside [HILC_MIXER_MIN_SUB, HILC_MIXER_MAX_SUB], L > HILC_MIXER_MAX_LIMIT_L, ceiling outside (0, 1] or release outside (0, 1):
+ * HILC_ERR_UNSUPPORTED; without one, ceiling, release and sub are not read.  Both rows NULL: hilc_mix_rooms bit for bit.  One workgroup
+ * per listener slot, no atomics; every element of mixed, speakers and the limiter row is written on every hop.
+ * Both: NULL pointers (action and the optional rows excepted): HILC_ERR_NULL; B or L < 1: HILC_ERR_SHAPE; top_k as hilc_mix_rooms. */
+int hilc_mix_gains(const float* wav, double* gains, double* power, const int* action, double gate2, double lo, double hi, double up,
+                   double down, double min_gain, double max_gain, double smooth, int B, int L, void* stream);
+int hilc_mix_rooms_dyn(const float* wav, const int* room, const double* score, int top_k, const double* gains, double* limiter,
+                       double ceiling, double release, int sub, const int* action, float* mixed, int* speakers, int B, int L,
+                       void* stream);
 
 /* ---- quality-targeted variable bitrate of the packet sender (additive under ABI 16) ----------------------------------------------
  * One entry point added WITHOUT a version bump, as the entry points above.  The definition, bit for bit, is hilcodec_amd/vbr.py.
