@@ -277,9 +277,78 @@ def _chainable(blocks: Sequence[ResBlockSpec]) -> bool:
                and rb.dw2_b is not None for rb in blocks)
 
 
-def _pairs(seq: Optional[Sequence[Tensor]], start: int, n: int) -> Optional[List[Sequence[Tensor]]]:
-    """the two depthwise caches of each of n consecutive blocks, the first block's at seq[start]; None where there is no list"""
-    return None if seq is None else [seq[start + 2 * i: start + 2 * i + 2] for i in range(n)]
+class _Caches:
+    """The cursor over one streaming step's cache list (order of `encoder_cache_shapes` / `decoder_cache_shapes`): hands out each
+    layer's cache with the place of its successor — `caches_out[i]`, or None = a fresh tensor, the reference's protocol — and takes
+    back what the op returned, so the new list grows in the order the old one is read.  Offline (`caches` None) it hands out None
+    and passes results through: one call site serves both modes."""
+
+    def __init__(self, caches: Optional[Sequence[Tensor]] = None, caches_out: Optional[Sequence[Tensor]] = None, expected: int = 0):
+        self.streaming = caches is not None
+        self.i = 0                  # caches handed out so far
+        self.new: List[Tensor] = []
+        self.out = caches_out if self.streaming else None
+        if self.streaming:
+            for name, seq in (("caches", caches), ("caches_out", self.out)):
+                if seq is not None and len(seq) != expected:
+                    raise RuntimeError(f"expected {expected} {name}, got {len(seq)}")
+            self.caches = [c.contiguous() for c in caches]
+
+    def next(self) -> tuple:
+        """(hist, hist_out) of the next layer"""
+        if not self.streaming:
+            return None, None
+        i = self.i
+        self.i = i + 1
+        return self.caches[i], (None if self.out is None else self.out[i])
+
+    def block(self) -> tuple:
+        """(hist, hist_out) of the next residual block: its two depthwise caches"""
+        if not self.streaming:
+            return None, None
+        i = self.i
+        self.i = i + 2
+        return self.caches[i:i + 2], (None if self.out is None else self.out[i:i + 2])
+
+    def blocks(self, n: int) -> tuple:
+        """the same for the next n blocks, as `ops.resblock_chain` and the stage ops take them"""
+        if not self.streaming:
+            return None, None
+        i = self.i
+        self.i = i + 2 * n
+        return ([self.caches[j:j + 2] for j in range(i, i + 2 * n, 2)],
+                None if self.out is None else [self.out[j:j + 2] for j in range(i, i + 2 * n, 2)])
+
+    def take(self, r, layer_first: bool = False):
+        """What an op returned -> y.  Streaming it is (y, new cache), (y, [block caches]) or a stage op's (y, [block caches], layer
+        cache[, closing conv's cache]); `layer_first`: the layer's cache stands in FRONT of the blocks' in the list (decoder stages).
+        The new caches are the successors of everything handed out since the last call, in that order."""
+        if not self.streaming:
+            return r
+        if layer_first:
+            self.new.append(r[2])
+            self.new.extend(r[1])
+            self.new.extend(r[3:])
+        elif isinstance(r[1], Tensor):
+            self.new.append(r[1])
+        else:
+            self.new.extend(r[1])
+            self.new.extend(r[2:])
+        if len(self.new) != self.i:
+            raise RuntimeError(f"internal error: {len(self.new)} new caches kept after cache {self.i - 1} was handed out")
+        return r[0]
+
+    def done(self, y):
+        """y offline, (y, new caches) streaming"""
+        if not self.streaming:
+            return y
+        if self.i != len(self.caches):
+            raise RuntimeError(f"internal error: the step read {self.i} of {len(self.caches)} caches")
+        if self.out is not None:
+            for i in range(self.i):
+                if self.new[i] is not self.out[i]:
+                    raise RuntimeError(f"internal error: new cache {i} is not caches_out[{i}]")
+        return y, self.new
 
 
 # the argument tuples of the stage ops (`ops.encoder_stage0`, `ops.encoder_stage`, `ops.decoder_stage`, `ops.decoder_stage_post`)
@@ -300,68 +369,69 @@ def _post_args(ds: "DecoderSpec") -> tuple:
     return (ds.post_w, ds.post_b, ds.post_in_scale, ds.post_out_scale, ds.tanh)
 
 
-def _resblock(rb: ResBlockSpec, x: Tensor, caches: Optional[Sequence[Tensor]], new_caches: Optional[list],
-              outs: Optional[Sequence[Tensor]] = None, opts: ExecOptions = _DEFAULT_OPTIONS) -> Tensor:
-    """One residual block; streaming: `caches` = its two depthwise caches, `outs` = where the next hop's caches go
-    (persistent state block) or None (fresh tensors, the reference's protocol)."""
-    o0, o1 = (outs[0], outs[1]) if outs is not None else (None, None)
-    if caches is None and _fusable(rb, x, False, opts.wide_blocks):
-        # one launch per block: x is read once, y written once, everything else stays in LDS
-        return ops.resblock(x, rb.pw1_packed, rb.dw1_w, rb.dw1_b, rb.pw2_packed, rb.dw2_w, rb.dw2_b,
-                            rb.pre_scale, rb.out_scale)
-    if caches is not None and x.shape[2] >= 4 and _fusable(rb, x, True, opts.wide_blocks):
-        # streaming hop: same kernel, the two depthwise caches patch the first tile's halo columns; the wide blocks of a hop
-        # (C = 256 ... 768) take its narrow-tile shapes
-        y, cs = ops.resblock(x, rb.pw1_packed, rb.dw1_w, rb.dw1_b, rb.pw2_packed, rb.dw2_w, rb.dw2_b,
-                             rb.pre_scale, rb.out_scale, hist=(caches[0], caches[1]), hist_out=outs)
-        new_caches.extend(cs)
-        return y
-    if (caches is not None and FUSE_STREAM and ops.dws_conv_stream_profitable(x.shape[2], rb.dw1_w.shape[1], 1)
-            and ops.dws_conv_stream_profitable(x.shape[2], rb.dw2_w.shape[1], 1)):
-        # wide layers of a streaming hop (T <= 128): two launches, whole-clip tiles, caches read/written in the epilogue
-        g, c0 = ops.dws_conv_stream(x, rb.pw1_wt, rb.dw1_w, rb.dw1_b, caches[0], in_scale=rb.pre_scale,
-                                    in_elu=True, out_elu=True, hist_out=o0)
-        y, c1 = ops.dws_conv_stream(g, rb.pw2_wt, rb.dw2_w, rb.dw2_b, caches[1], res=x,
-                                    out_scale=rb.out_scale, hist_out=o1)
-        new_caches.extend([c0, c1])
-        return y
-    if caches is None and FUSE_DWS and rb.dw1_w.shape[1] == 5 and rb.dw2_w.shape[1] == 5:
-        # two launches per block: [ELU, pw, dw, ELU] and [pw, dw, *scale + shortcut]; the pointwise
-        # outputs never leave LDS
-        g = ops.dws_conv(x, rb.pw1_wt, rb.dw1_w, rb.dw1_b, in_scale=rb.pre_scale, in_elu=True, out_elu=True)
-        return ops.dws_conv(g, rb.pw2_wt, rb.dw2_w, rb.dw2_b, res=x, out_scale=rb.out_scale)
-    h = ops.pw_conv(x, rb.pw1_wt, in_scale=rb.pre_scale, in_elu=True)
-    if caches is None:
-        g = ops.dw_conv(h, rb.dw1_w, rb.dw1_b)
-        h2 = ops.pw_conv(g, rb.pw2_wt, in_scale=1.0, in_elu=True)
-        return ops.dw_conv(h2, rb.dw2_w, rb.dw2_b, res=x, out_scale=rb.out_scale)
-    g, c0 = ops.dw_conv(h, rb.dw1_w, rb.dw1_b, hist=caches[0], want_hist=True, hist_out=o0)
-    h2 = ops.pw_conv(g, rb.pw2_wt, in_scale=1.0, in_elu=True)
-    y, c1 = ops.dw_conv(h2, rb.dw2_w, rb.dw2_b, res=x, out_scale=rb.out_scale, hist=caches[1], want_hist=True,
-                        hist_out=o1)
-    new_caches.extend([c0, c1])
-    return y
+def _dws_layer(cur: _Caches, fused: bool, x: Tensor, pw_wt: Tensor, dw_w: Tensor, dw_b: Optional[Tensor], res=None, stride: int = 1,
+               in_scale: float = 1.0, in_elu: bool = False, out_scale: float = 1.0, out_elu: bool = False) -> Tensor:
+    """Pointwise conv -> causal depthwise conv (with the next cache of `cur`, streaming).  `fused`: one launch, the pointwise outputs
+    never leave LDS (a hop: whole-clip tiles, the cache read and written in the epilogue); else pointwise GEMM + depthwise launch.
+    `res` is added to the output; a function in its place is called where the tensor is needed, behind the pointwise launch."""
+    hist, hist_out = cur.next()
+    if fused:
+        res = res() if callable(res) else res
+        if cur.streaming:
+            return cur.take(ops.dws_conv_stream(x, pw_wt, dw_w, dw_b, hist, res=res, stride=stride, in_scale=in_scale, in_elu=in_elu,
+                                                out_scale=out_scale, out_elu=out_elu, hist_out=hist_out))
+        return ops.dws_conv(x, pw_wt, dw_w, dw_b, res=res, stride=stride, in_scale=in_scale, in_elu=in_elu, out_scale=out_scale, out_elu=out_elu)
+    h = ops.pw_conv(x, pw_wt, in_scale=in_scale, in_elu=in_elu)
+    return cur.take(ops.dw_conv(h, dw_w, dw_b, res=res() if callable(res) else res, stride=stride, hist=hist, want_hist=cur.streaming,
+                                out_scale=out_scale, out_elu=out_elu, hist_out=hist_out))
 
 
-def _stage_blocks(blocks: Sequence[ResBlockSpec], x: Tensor, caches: Optional[Sequence[Tensor]], ci: int, new_caches: Optional[list],
-                  caches_out: Optional[Sequence[Tensor]], opts: ExecOptions) -> Tensor:
+def _up_layer(cur: _Caches, st: "DecStageSpec", x: Tensor) -> Tensor:
+    """A decoder stage's up-sampling layer as a launch of its own: [Scale, ELU, depthwise transposed conv, pointwise conv + bias]"""
+    hist, hist_out = cur.next()
+    if (FUSE_STREAM if cur.streaming else FUSE_UPSAMPLE) and (x.shape[2] * st.ratio) % 4 == 0:
+        # the up-sampled tensor only exists inside the GEMM's loader
+        return cur.take(ops.up_conv(x, st.tr_w, st.pw_wt, st.pw_b, st.ratio, in_scale=st.in_scale, in_elu=True, hist=hist,
+                                    want_hist=cur.streaming, taps=st.taps, hist_out=hist_out))
+    u = cur.take(ops.dw_convtr(x, st.tr_w, st.ratio, hist=hist, want_hist=cur.streaming, in_scale=st.in_scale, in_elu=True, hist_out=hist_out))
+    return ops.pw_conv(u, st.pw_wt, st.pw_b)
+
+
+def _resblock(rb: ResBlockSpec, x: Tensor, cur: _Caches, opts: ExecOptions = _DEFAULT_OPTIONS) -> Tensor:
+    """One residual block; streaming: with the next two caches of `cur`."""
+    k1, k2 = rb.dw1_w.shape[1], rb.dw2_w.shape[1]
+    if (not cur.streaming or x.shape[2] >= 4) and _fusable(rb, x, cur.streaming, opts.wide_blocks):
+        # one launch per block: x is read once, y written once, everything else stays in LDS.  A streaming hop: same kernel, the two
+        # depthwise caches patch the first tile's halo columns; the wide blocks of a hop (C = 256 ... 768) take its narrow-tile shapes
+        hist, hist_out = cur.block()
+        return cur.take(ops.resblock(x, rb.pw1_packed, rb.dw1_w, rb.dw1_b, rb.pw2_packed, rb.dw2_w, rb.dw2_b, rb.pre_scale, rb.out_scale,
+                                     hist=hist, hist_out=hist_out))
+    if cur.streaming:       # wide layers of a streaming hop (T <= 128)
+        fused = FUSE_STREAM and ops.dws_conv_stream_profitable(x.shape[2], k1, 1) and ops.dws_conv_stream_profitable(x.shape[2], k2, 1)
+    else:
+        fused = FUSE_DWS and k1 == 5 and k2 == 5
+    # two layers: [ELU, pw, dw] and [pw, dw, *scale + shortcut]; the ELU between them in the epilogue of a fused first launch, else in
+    # the second pointwise GEMM's loader
+    g = _dws_layer(cur, fused, x, rb.pw1_wt, rb.dw1_w, rb.dw1_b, in_scale=rb.pre_scale, in_elu=True, out_elu=fused)
+    return _dws_layer(cur, fused, g, rb.pw2_wt, rb.dw2_w, rb.dw2_b, res=x, in_elu=not fused, out_scale=rb.out_scale)
+
+
+def _stage_blocks(blocks: Sequence[ResBlockSpec], x: Tensor, cur: _Caches, opts: ExecOptions) -> Tensor:
     """The residual blocks of one stage: ONE chain launch where the kernel exists (the blocks run back to back per tile, the
     activations between them stay in registers: `ops.resblock_chain`); otherwise block by block."""
     n = len(blocks)
-    streaming = caches is not None
-    hist, hist_out = _pairs(caches, ci, n), _pairs(caches_out, ci, n)
-    if (streaming and FUSE_RESBLOCK and FUSE_STREAM and opts.stage_launches and n >= 2 and x.shape[2] >= 4 and _chainable(blocks)
-            and (x.shape[1] <= FUSE_RESBLOCK_MAX_C or opts.wide_blocks)
-            and ops.resblock_chain_supported(x.shape[1], x.shape[2], n, x.shape[0])):
-        y, cs = ops.resblock_chain(x, [rb.chain_args for rb in blocks], hist, hist_out)
-        new_caches.extend(cs)
-        return y
-    if (not streaming and FUSE_RESBLOCK and opts.stage_launches and n >= 2
-            and all(rb.pw1_chain is not None and _fusable(rb, x, False, opts.wide_blocks) for rb in blocks)
-            and ops.resblock_chain_supported(x.shape[1], x.shape[2], n, x.shape[0], streaming=False)):
-        return ops.resblock_chain(x, [rb.chain_args for rb in blocks])
-    for i, rb in enumerate(blocks):
-        x = _resblock(rb, x, hist[i] if streaming else None, new_caches, hist_out[i] if hist_out is not None else None, opts=opts)
+    chain = FUSE_RESBLOCK and opts.stage_launches and n >= 2
+    if cur.streaming:
+        chain = (chain and FUSE_STREAM and x.shape[2] >= 4 and _chainable(blocks) and (x.shape[1] <= FUSE_RESBLOCK_MAX_C or opts.wide_blocks)
+                 and ops.resblock_chain_supported(x.shape[1], x.shape[2], n, x.shape[0]))
+    else:
+        chain = (chain and all(rb.pw1_chain is not None and _fusable(rb, x, False, opts.wide_blocks) for rb in blocks)
+                 and ops.resblock_chain_supported(x.shape[1], x.shape[2], n, x.shape[0], streaming=False))
+    if chain:
+        hist, hist_out = cur.blocks(n)
+        return cur.take(ops.resblock_chain(x, [rb.chain_args for rb in blocks], hist, hist_out))
+    for rb in blocks:
+        x = _resblock(rb, x, cur, opts)
     return x
 
 
@@ -411,22 +481,14 @@ def _spec_fused(sb: SpecBlockSpec, wav: Tensor, wav_hist: Optional[Tensor]) -> b
                 and ops.spec_block_profitable(sb.n_fft, sb.hop, sb.wt.shape[1], wav.shape[2]))
 
 
-def _spec_block(sb: SpecBlockSpec, x: Tensor, wav: Tensor, wav_hist: Optional[Tensor]) -> Tensor:
+def _spec_block(sb: SpecBlockSpec, x: Optional[Tensor], wav: Tensor, wav_hist: Optional[Tensor]) -> Tensor:
+    """x + out_scale * (W logspec(wav) + bias) `[B, C, T_f]` (`seanet.py:220-246`; streaming, merged: `streaming.py:346-366`); x None:
+    the branch ALONE — what `x.add_()` adds.  It depends on the waveform only."""
     if _spec_fused(sb, wav, wav_hist):
         return ops.spec_block(wav, sb.fused[0], sb.fused[1], sb.fused[2], sb.bias, x, sb.n_fft, sb.hop, sb.mean, sb.std,
                               sb.normalize, sb.out_scale, hist=wav_hist)
     s = ops.stft_logmag(wav, sb.basis_t, sb.n_fft, sb.hop, sb.mean, sb.std, sb.normalize, hist=wav_hist)
     return ops.pw_conv(s, sb.wt, sb.bias, res=x, out_scale=sb.out_scale)
-
-
-def _spec_branch(sb: SpecBlockSpec, wav: Tensor, wav_hist: Optional[Tensor]) -> Tensor:
-    """The SpecBlock's branch ALONE: out_scale * (W logspec(wav) + bias) `[B, C, T_f]` — what `x.add_()` adds
-    (`seanet.py:220-246`; streaming, merged: `streaming.py:346-366`).  It depends on the waveform only."""
-    if _spec_fused(sb, wav, wav_hist):
-        return ops.spec_block(wav, sb.fused[0], sb.fused[1], sb.fused[2], sb.bias, None, sb.n_fft, sb.hop, sb.mean, sb.std,
-                              sb.normalize, sb.out_scale, hist=wav_hist)
-    s = ops.stft_logmag(wav, sb.basis_t, sb.n_fft, sb.hop, sb.mean, sb.std, sb.normalize, hist=wav_hist)
-    return ops.pw_conv(s, sb.wt, sb.bias, out_scale=sb.out_scale)
 
 
 def _early_branches(todo: Sequence[SpecBlockSpec], wav: Tensor, wav_hist: Optional[Tensor], side) -> Optional[dict]:
@@ -441,17 +503,13 @@ def _early_branches(todo: Sequence[SpecBlockSpec], wav: Tensor, wav_hist: Option
     side.wait_stream(main)
     with torch.cuda.stream(side):
         for sb in todo:
-            r = _spec_branch(sb, wav, wav_hist)
+            r = _spec_block(sb, None, wav, wav_hist)
             if not capturing:
                 r.record_stream(main)
             done = torch.cuda.Event()
             done.record(side)
             early[id(sb)] = (r, done)
     return early
-
-
-def _contig(caches: Optional[Sequence[Tensor]]):
-    return None if caches is None else [c.contiguous() for c in caches]
 
 
 # The linear-addressing GEMM cores and the fused residual block address an activation tensor with 32-bit byte offsets
@@ -490,6 +548,22 @@ def _decoder_clip_elems(ds: "DecoderSpec", F: int) -> int:
     return best
 
 
+def _cache_count(spec) -> int:
+    """len(encoder_cache_shapes(spec)) or len(decoder_cache_shapes(spec)) without reading a shape (every hop asks): one cache in front,
+    one behind, and per stage its layer's and two per residual block"""
+    return 2 + sum(1 + 2 * len(st.blocks) for st in spec.stages)
+
+
+def _begin(x: Tensor, opts: ExecOptions, offline: bool, clip_elems, spec) -> tuple:
+    """how run_encoder and run_decoder open: (contiguous fp32 input, the options in force, the clip ranges of an offline batch that
+    has to run in chunks — else None)"""
+    x = x.contiguous().float()
+    chunks = None
+    if offline and not torch.compiler.is_compiling():
+        chunks = _clip_chunks(x.shape[0], clip_elems(spec, x.shape[2]))
+    return x, _effective(opts), (chunks if chunks is not None and len(chunks) > 1 else None)
+
+
 def run_encoder(es: EncoderSpec, wav: Tensor, caches: Optional[Sequence[Tensor]] = None,
                 channel_last_out: bool = False, caches_out: Optional[Sequence[Tensor]] = None,
                 opts: ExecOptions = _DEFAULT_OPTIONS):
@@ -499,25 +573,14 @@ def run_encoder(es: EncoderSpec, wav: Tensor, caches: Optional[Sequence[Tensor]]
     reference's protocol (`streaming.py:482-517`: cache_out never aliases cache_in)."""
     if wav.dim() != 3 or wav.shape[1] != 1:
         raise RuntimeError(f"expected [B,1,T] waveform, got {tuple(wav.shape)}")
-    opts = _effective(opts)
-    wav = wav.contiguous().float()
-    streaming = caches is not None
-    if not streaming and not torch.compiler.is_compiling():
-        chunks = _clip_chunks(wav.shape[0], _encoder_clip_elems(es, wav.shape[2]))
-        if len(chunks) > 1:
-            return torch.cat([run_encoder(es, wav[lo:hi], None, channel_last_out, None, opts) for lo, hi in chunks], dim=0)
-    caches = _contig(caches)
-    new_caches: Optional[list] = [] if streaming else None
-
-    def out(i):
-        return caches_out[i] if caches_out is not None else None
-
-    wav_hist = None
-    ci = 0
+    wav, opts, chunks = _begin(wav, opts, caches is None, _encoder_clip_elems, es)
+    if chunks:
+        return torch.cat([run_encoder(es, wav[lo:hi], None, channel_last_out, None, opts) for lo, hi in chunks], dim=0)
+    cur = _Caches(caches, caches_out, _cache_count(es))
+    streaming = cur.streaming
+    wav_hist, tail_out = cur.next()
     if streaming:
-        wav_hist = caches[0]
-        new_caches.append(ops.tail(wav, wav_hist, es.wav_cache_len, out=out(0)))
-        ci = 1
+        cur.take((None, ops.tail(wav, wav_hist, es.wav_cache_len, out=tail_out)))
     sb0 = es.stages[0].spec
     fuse_pre = _pre_fusable(es, wav, wav_hist)
     fuse_stage0 = fuse_pre and _stage0_fusable(es, wav, streaming, opts)
@@ -546,166 +609,93 @@ def run_encoder(es: EncoderSpec, wav: Tensor, caches: Optional[Sequence[Tensor]]
             r, done = early[id(sb)]
             torch.cuda.current_stream(wav.device).wait_event(done)
             return r
-        return _spec_branch(sb, wav, wav_hist)
+        return _spec_block(sb, None, wav, wav_hist)
 
     for si, st in enumerate(es.stages):
         stage0 = fuse_stage0 and si == 0
         if not (fuse_pre and si == 0) and not (defer and si > 0):
             x = _spec_block(st.spec, x, wav, wav_hist)
-        nxt = later[si] if defer else None
-        nb = len(st.blocks)
+        nxt = later[si]
         if stage0 or _enc_stage_fusable(st, x, streaming, opts):
             # the whole stage — its residual blocks and its down-sampling layer — is one launch; the stage's output never reaches HBM.
             # Stage 0 with the first conv and its SpecBlock in front (offline: seanet.py:368-378; a hop: streaming.py:490-511, with the
             # waveform cache in front of every stream's t = 0): neither the [64 x T] tensor in front of the stage nor the one behind its
             # blocks ever exists.  A hop launches it here, not above, so that the side branches have been forked by now.
             blocks, down = [rb.chain_args for rb in st.blocks], _down_args(st)
-            state = dict(res=branch_of(nxt) if defer else None, hist=_pairs(caches, ci, nb), hist_out=_pairs(caches_out, ci, nb),
-                         down_hist=caches[ci + 2 * nb] if streaming else None, down_hist_out=out(ci + 2 * nb))
+            res = branch_of(nxt) if defer else None
+            hist, hist_out = cur.blocks(len(st.blocks))
+            down_hist, down_hist_out = cur.next()
+            state = dict(res=res, hist=hist, hist_out=hist_out, down_hist=down_hist, down_hist_out=down_hist_out)
             if stage0:
-                r = ops.encoder_stage0(wav, _spec0_args(es), blocks, down, wav_hist=wav_hist, **state)
+                x = cur.take(ops.encoder_stage0(wav, _spec0_args(es), blocks, down, wav_hist=wav_hist, **state))
             else:
-                r = ops.encoder_stage(x, blocks, down, **state)
-            if streaming:
-                x, cs_, c = r
-                new_caches.extend(cs_)
-                new_caches.append(c)
-            else:
-                x = r
-            ci += 2 * nb + 1
+                x = cur.take(ops.encoder_stage(x, blocks, down, **state))
             continue
-        x = _stage_blocks(st.blocks, x, caches, ci, new_caches, caches_out, opts)
-        ci += 2 * len(st.blocks)
+        x = _stage_blocks(st.blocks, x, cur, opts)
+        k = st.down_dw_w.shape[1]
         # (a shortcut the fused layer cannot take — a long hop at a stride above 8 — falls through to pointwise GEMM + depthwise conv, which can)
-        if streaming and FUSE_STREAM and ops.dws_conv_stream_profitable(x.shape[2], st.down_dw_w.shape[1], st.ratio, defer, x.shape[0],
-                                                                         st.down_dw_w.shape[0]):
-            x, c = ops.dws_conv_stream(x, st.down_pw_wt, st.down_dw_w, st.down_dw_b, caches[ci], res=branch_of(nxt) if defer else None,
-                                       stride=st.ratio, in_scale=st.down_in_scale, in_elu=True, hist_out=out(ci))
-            new_caches.append(c)
-        elif streaming:
-            h = ops.pw_conv(x, st.down_pw_wt, in_scale=st.down_in_scale, in_elu=True)
-            x, c = ops.dw_conv(h, st.down_dw_w, st.down_dw_b, res=branch_of(nxt) if defer else None, stride=st.ratio, hist=caches[ci],
-                               want_hist=True, hist_out=out(ci))
-            new_caches.append(c)
-        elif FUSE_DWS and st.down_dw_w.shape[1] == 2 * st.ratio:
-            x = ops.dws_conv(x, st.down_pw_wt, st.down_dw_w, st.down_dw_b, stride=st.ratio,
-                             in_scale=st.down_in_scale, in_elu=True)
+        if streaming:
+            fused = FUSE_STREAM and ops.dws_conv_stream_profitable(x.shape[2], k, st.ratio, defer, x.shape[0], st.down_dw_w.shape[0])
         else:
-            h = ops.pw_conv(x, st.down_pw_wt, in_scale=st.down_in_scale, in_elu=True)
-            x = ops.dw_conv(h, st.down_dw_w, st.down_dw_b, stride=st.ratio)
-        ci += 1
+            fused = FUSE_DWS and k == 2 * st.ratio
+        x = _dws_layer(cur, fused, x, st.down_pw_wt, st.down_dw_w, st.down_dw_b, res=(lambda: branch_of(nxt)) if defer else None,
+                       stride=st.ratio, in_scale=st.down_in_scale, in_elu=True)
     if not defer:
         x = _spec_block(es.spec_post, x, wav, wav_hist)
-    if streaming:
-        h, c = ops.dw_conv(x, es.post_dw_w, None, in_elu=True, hist=caches[ci], want_hist=True, hist_out=out(ci))
-        new_caches.append(c)
-    else:
-        h = ops.dw_conv(x, es.post_dw_w, None, in_elu=True)
+    hist, hist_out = cur.next()
+    h = cur.take(ops.dw_conv(x, es.post_dw_w, None, in_elu=True, hist=hist, want_hist=streaming, hist_out=hist_out))
     h = ops.pw_conv(h, es.post_pw_wt, es.post_pw_b)
     if es.l2norm:
         z = ops.l2norm(h, eps=1e-12, scale=float(es.dim) ** 0.5, channel_last_out=channel_last_out)
     else:
         z = h.transpose(1, 2).contiguous() if channel_last_out else h
-    return (z, new_caches) if streaming else z
+    return cur.done(z)
 
 
 def run_decoder(ds: DecoderSpec, q: Tensor, caches: Optional[Sequence[Tensor]] = None,
                 caches_out: Optional[Sequence[Tensor]] = None, opts: ExecOptions = _DEFAULT_OPTIONS):
     """q `[B,dim,F]` (channel-major) -> wav `[B,1,F*hop]`, and the new cache list if streaming (`caches_out` as in
     run_encoder)."""
-    streaming = caches is not None
-    opts = _effective(opts)
-    caches = _contig(caches)
-    new_caches: Optional[list] = [] if streaming else None
-
-    def out(i):
-        return caches_out[i] if caches_out is not None else None
-
-    q = q.contiguous().float()
-    if not streaming and not torch.compiler.is_compiling():
-        chunks = _clip_chunks(q.shape[0], _decoder_clip_elems(ds, q.shape[2]))
-        if len(chunks) > 1:
-            return torch.cat([run_decoder(ds, q[lo:hi], None, None, opts) for lo, hi in chunks], dim=0)
-    ci = 0
-    if streaming and FUSE_STREAM and ops.dws_conv_stream_profitable(q.shape[2], ds.pre_dw_w.shape[1], 1):
-        x, c = ops.dws_conv_stream(q, ds.pre_pw_wt, ds.pre_dw_w, ds.pre_dw_b, caches[0], hist_out=out(0))
-        new_caches.append(c)
-    elif streaming:
-        h = ops.pw_conv(q, ds.pre_pw_wt)
-        x, c = ops.dw_conv(h, ds.pre_dw_w, ds.pre_dw_b, hist=caches[0], want_hist=True, hist_out=out(0))
-        new_caches.append(c)
-    elif FUSE_DWS and ds.pre_dw_w.shape[1] == 5:
-        x = ops.dws_conv(q, ds.pre_pw_wt, ds.pre_dw_w, ds.pre_dw_b)
+    q, opts, chunks = _begin(q, opts, caches is None, _decoder_clip_elems, ds)
+    if chunks:
+        return torch.cat([run_decoder(ds, q[lo:hi], None, None, opts) for lo, hi in chunks], dim=0)
+    cur = _Caches(caches, caches_out, _cache_count(ds))
+    streaming = cur.streaming
+    k = ds.pre_dw_w.shape[1]
+    if streaming:
+        fused = FUSE_STREAM and ops.dws_conv_stream_profitable(q.shape[2], k, 1)
     else:
-        h = ops.pw_conv(q, ds.pre_pw_wt)
-        x = ops.dw_conv(h, ds.pre_dw_w, ds.pre_dw_b)
-    ci = 1
+        fused = FUSE_DWS and k == 5
+    x = _dws_layer(cur, fused, q, ds.pre_pw_wt, ds.pre_dw_w, ds.pre_dw_b)
     for st in ds.stages:
         width, t = st.pw_wt.shape[1], x.shape[2] * st.ratio
         nb = 0
         if ((FUSE_STREAM if streaming else FUSE_UPSAMPLE) and FUSE_RESBLOCK and opts.stage_launches
                 and (opts.decoder_stage_narrow if width <= FUSE_RESBLOCK_MAX_C else opts.wide_blocks)):
             nb = _stage_fusable_blocks(st, x, streaming, opts.decoder_stage_narrow)
-        if nb > 0:
-            # the stage — up-sampling layer and residual blocks — is one launch; the tensor between them never exists.  Where LDS holds
-            # one block only behind the up-sampling phase (a hop's C = 384, the offline model's C = 768) the other blocks follow as
-            # launches of their own.
-            up, blocks = _up_args(st), [rb.chain_args for rb in st.blocks[:nb]]
-            hist, hist_out = _pairs(caches, ci + 1, nb), _pairs(caches_out, ci + 1, nb)
-            up_hist = caches[ci] if streaming else None
-            if (st is ds.stages[-1] and nb == len(st.blocks) and ds.post_w.dim() == 2 and ds.post_w.shape[0] == width
-                    and ops.decoder_stage_post_supported(width, t, nb, st.ratio, ds.post_w.shape[1])):
-                # the LAST stage and the closing conv (seanet.py:453-476, streaming.py:639-648) in one launch: the stage's [B, C, T] output
-                # — the step's largest tensor — is neither written nor read; a hop reads the conv's cache at a stream's t = 0 and
-                # writes it from its last column group
-                cp = ci + 1 + 2 * nb
-                r = ops.decoder_stage_post(x, up, blocks, _post_args(ds), hist, up_hist, caches[cp] if streaming else None,
-                                           hist_out, out(ci), out(cp))
-                if not streaming:
-                    return r
-                wav, cs_, cu, cpost = r
-                new_caches.append(cu)
-                new_caches.extend(cs_)
-                new_caches.append(cpost)
-                return wav, new_caches
-            r = ops.decoder_stage(x, up, blocks, hist, up_hist, hist_out, out(ci))
-            if streaming:
-                x, cs_, cu = r
-                new_caches.append(cu)
-                new_caches.extend(cs_)
-            else:
-                x = r
-            ci += 1 + 2 * nb
-            if nb < len(st.blocks):
-                x = _stage_blocks(st.blocks[nb:], x, caches, ci, new_caches, caches_out, opts)
-                ci += 2 * (len(st.blocks) - nb)
+        if nb == 0:
+            x = _stage_blocks(st.blocks, _up_layer(cur, st, x), cur, opts)
             continue
-        if streaming and FUSE_STREAM and t % 4 == 0:
-            x, cu = ops.up_conv(x, st.tr_w, st.pw_wt, st.pw_b, st.ratio, in_scale=st.in_scale, in_elu=True,
-                                hist=caches[ci], want_hist=True, taps=st.taps, hist_out=out(ci))
-            new_caches.append(cu)
-        elif streaming:
-            u, cu = ops.dw_convtr(x, st.tr_w, st.ratio, hist=caches[ci], want_hist=True,
-                                  in_scale=st.in_scale, in_elu=True, hist_out=out(ci))
-            new_caches.append(cu)
-            x = ops.pw_conv(u, st.pw_wt, st.pw_b)
-        elif FUSE_UPSAMPLE and t % 4 == 0:
-            # the up-sampled tensor only exists inside the GEMM's loader
-            x = ops.up_conv(x, st.tr_w, st.pw_wt, st.pw_b, st.ratio, in_scale=st.in_scale, in_elu=True, taps=st.taps)
-        else:
-            u = ops.dw_convtr(x, st.tr_w, st.ratio, in_scale=st.in_scale, in_elu=True)
-            x = ops.pw_conv(u, st.pw_wt, st.pw_b)
-        ci += 1
-        x = _stage_blocks(st.blocks, x, caches, ci, new_caches, caches_out, opts)
-        ci += 2 * len(st.blocks)
-    if streaming:
-        wav, c = ops.conv_post(x, ds.post_w, ds.post_b, in_scale=ds.post_in_scale, in_elu=True,
-                               out_scale=ds.post_out_scale, do_tanh=ds.tanh, hist=caches[ci], want_hist=True,
-                               hist_out=out(ci))
-        new_caches.append(c)
-        return wav, new_caches
-    return ops.conv_post(x, ds.post_w, ds.post_b, in_scale=ds.post_in_scale, in_elu=True,
-                         out_scale=ds.post_out_scale, do_tanh=ds.tanh)
+        # the stage — up-sampling layer and residual blocks — is one launch; the tensor between them never exists.  Where LDS holds
+        # one block only behind the up-sampling phase (a hop's C = 384, the offline model's C = 768) the other blocks follow as
+        # launches of their own.
+        up, blocks = _up_args(st), [rb.chain_args for rb in st.blocks[:nb]]
+        up_hist, up_hist_out = cur.next()
+        hist, hist_out = cur.blocks(nb)
+        if (st is ds.stages[-1] and nb == len(st.blocks) and ds.post_w.dim() == 2 and ds.post_w.shape[0] == width
+                and ops.decoder_stage_post_supported(width, t, nb, st.ratio, ds.post_w.shape[1])):
+            # the LAST stage and the closing conv (seanet.py:453-476, streaming.py:639-648) in one launch: the stage's [B, C, T] output
+            # — the step's largest tensor — is neither written nor read; a hop reads the conv's cache at a stream's t = 0 and
+            # writes it from its last column group
+            post_hist, post_hist_out = cur.next()
+            return cur.done(cur.take(ops.decoder_stage_post(x, up, blocks, _post_args(ds), hist, up_hist, post_hist, hist_out, up_hist_out,
+                                                            post_hist_out), layer_first=True))
+        x = cur.take(ops.decoder_stage(x, up, blocks, hist, up_hist, hist_out, up_hist_out), layer_first=True)
+        if nb < len(st.blocks):
+            x = _stage_blocks(st.blocks[nb:], x, cur, opts)
+    hist, hist_out = cur.next()
+    return cur.done(cur.take(ops.conv_post(x, ds.post_w, ds.post_b, in_scale=ds.post_in_scale, in_elu=True, out_scale=ds.post_out_scale,
+                                           do_tanh=ds.tanh, hist=hist, want_hist=streaming, hist_out=hist_out)))
 
 
 def encoder_cache_shapes(es: EncoderSpec) -> List[Tuple[int, int]]:

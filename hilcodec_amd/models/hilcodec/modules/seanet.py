@@ -107,7 +107,7 @@ class SEANetResnetBlock(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:
         sp = self._cache.get((str(x.device), self._key()), lambda: engine.finalize_block(self.spec(x.device)))
-        return engine._resblock(sp, x.contiguous().float(), None, None)
+        return engine._resblock(sp, x.contiguous().float(), engine._Caches())
 
 
 class L2Norm(nn.Module):

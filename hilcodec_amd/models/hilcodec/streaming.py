@@ -190,9 +190,8 @@ class ResBlock(nn.Module):
         return engine.ResBlockSpec(pw1, dw1, b1, pw2, dw2, b2, self.pre_scale, out_scale)
 
     def forward(self, x: Tensor, cache: tp.List[Tensor]) -> tp.Tuple[Tensor, tp.List[Tensor]]:
-        new_cache: tp.List[Tensor] = []
-        y = engine._resblock(engine.finalize_block(self.spec(x.device), streaming=True), x.contiguous().float(), cache, new_cache)
-        return y, new_cache
+        cur = engine._Caches(cache, None, 2)
+        return cur.done(engine._resblock(engine.finalize_block(self.spec(x.device), streaming=True), x.contiguous().float(), cur))
 
 
 class L2Norm(nn.Module):

@@ -7,6 +7,7 @@ import torch
 
 import hilcodec_amd
 from hilcodec_amd import engine, ops, synth
+from tests.test_plan_cpu import _Recorder, _launches, _specs
 
 OPS = ["spec_block", "spec_block_conv_pre", "spec_block_pack", "pw_conv", "dws_conv", "dws_conv_stream", "up_conv_expand_taps", "up_conv", "resblock_pack", "resblock", "dw_conv",
        "dw_convtr", "conv_pre", "conv_post", "stft_logmag", "tail", "l2norm", "rvq_encode", "rvq_decode",
@@ -107,3 +108,49 @@ def test_dynamo_fullgraph_traces_the_module_classes():
     fresh = hilcodec_amd.HILCodec(24000, 1, **mk).eval()
     with pytest.raises(Exception, match="prepare"):
         torch.compile(fresh.encoder, fullgraph=True, backend="aot_eager")(torch.empty(1, 1, 640, device="meta"))
+
+
+@pytest.mark.parametrize("which", ["caches", "caches_out"])
+@pytest.mark.parametrize("delta", [-1, 1], ids=["one too few", "one too many"])
+@pytest.mark.parametrize("half", ["encoder", "decoder"])
+def test_a_cache_list_of_the_wrong_length_is_refused_before_the_first_launch(half, delta, which):
+    es, ds = _specs("hil_speech", True)
+    B = 37
+    if half == "encoder":
+        shapes, x = engine.encoder_cache_shapes(es), torch.empty(B, 1, 320, device="meta")
+        run = lambda caches, out: engine.run_encoder(es, x, caches, caches_out=out)
+    else:
+        shapes, x = engine.decoder_cache_shapes(ds), torch.empty(B, ds.pre_pw_wt.shape[0], 1, device="meta")
+        run = lambda caches, out: engine.run_decoder(ds, x, caches, caches_out=out)
+    good = [torch.empty(B, c, l, device="meta") for c, l in shapes]
+    bad = good[:-1] if delta < 0 else good + [torch.empty_like(good[-1])]
+    good_out, bad_out = [torch.empty_like(t) for t in good], [torch.empty_like(t) for t in bad]
+    rec = _Recorder()
+    for label, seq in (("x", x), ("good", good), ("bad", bad), ("good_out", good_out), ("bad_out", bad_out), ("es", es), ("ds", ds)):
+        rec.name_tree(seq, label)
+    with rec, pytest.raises(RuntimeError, match=f"expected {len(good)} {which}, got {len(good) + delta}"):
+        run(bad, None) if which == "caches" else run(good, bad_out)
+    assert not rec.rows         # nothing reached the dispatcher, no hilcodec op and no ATen op
+    with rec:                   # ... and the right lists run
+        _, new = run(good, good_out)
+    assert len(new) == len(good) and _launches(rec.rows)
+
+
+def test_the_cursor_reports_caches_kept_out_of_step():
+    old, out = [torch.empty(2, 3, 4, device="meta") for _ in range(3)], [torch.empty(2, 3, 4, device="meta") for _ in range(3)]
+    cur = engine._Caches(old, out, 3)
+    hist, hist_out = cur.next()
+    assert hist is old[0] and hist_out is out[0]
+    with pytest.raises(RuntimeError, match="internal error: 2 new caches kept after cache 0"):
+        cur.take((None, [out[0], out[1]]))
+    cur = engine._Caches(old, out, 3)
+    cur.next(), cur.block()
+    assert cur.take((None, [out[2], out[1]], out[0]), layer_first=True) is None          # a stage op's blocks swapped
+    with pytest.raises(RuntimeError, match=r"internal error: new cache 1 is not caches_out\[1\]"):
+        cur.done(None)
+    cur = engine._Caches(old, None, 3)
+    cur.next()
+    cur.take((None, out[0]))
+    with pytest.raises(RuntimeError, match="internal error: the step read 1 of 3 caches"):
+        cur.done(None)
+    assert engine._Caches().next() == (None, None) and engine._Caches().take("y") == "y" and engine._Caches().done("y") == "y"

@@ -5,7 +5,9 @@ is launched and the real batch sizes are free (B = 640 takes the clip chunks, B 
 Every tensor argument is recorded by WHERE IT CAME FROM (a field of the spec, the waveform, cache i in / out, output j of op k), so a
 cache mix-up — two caches of a block swapped, an offset off by one — changes the trace although every shape stays right.  The
 scenarios are those of `tools/launch_table.py`; each streaming one is walked with fresh caches and with a state block
-(`caches_out`), and two more use a 960-sample hop.
+(`caches_out`), and two more use a 960-sample hop.  Three of them are walked again with the engine's module switches off — each
+alone and all together — and with `stream_defer_spec=False`: the lower rungs of every launch ladder, which `tools/ab_engine_flag.py`
+reaches.
 
   python tests/test_plan_cpu.py --dump DIR      one JSON file of full rows per scenario (diff two trees when a hash differs)
   python tests/test_plan_cpu.py --write         rewrite the fixture from THIS tree (only for a change that is meant to move the plan)"""
@@ -43,12 +45,27 @@ SCENARIOS = _launch_table_scenarios()       # name: (model, mode, batch, samples
 SCENARIOS["streaming hop 960 (3 frames), 1024 streams"] = ("hil_speech", "streaming", 1024, 960, {})
 SCENARIOS["streaming hop 960 (3 frames), 37 streams"] = ("hil_speech", "streaming", 37, 960, {})
 
-# (scenario, state block) — a streaming scenario is walked twice
-CASES = [(name, block) for name, sc in SCENARIOS.items() for block in ((False, True) if sc[1] == "streaming" else (False,))]
+SWITCHES = ("FUSE_DWS", "FUSE_UPSAMPLE", "FUSE_RESBLOCK", "FUSE_STREAM", "FUSE_SPECBLOCK", "STREAM_STAGE0")
+# (scenario, switches set to False, exec options on top of the scenario's): what no default plan reaches
+VARIANTS = [("offline ragged T5000 B7", off, {}) for off in (("FUSE_DWS",), ("FUSE_UPSAMPLE",), ("FUSE_RESBLOCK",), ("FUSE_SPECBLOCK",), SWITCHES)]
+for _base in ("streaming hop 320, 37 streams (ragged runs)", "streaming hop 960 (3 frames), 37 streams"):
+    VARIANTS += [(_base, off, {}) for off in (("FUSE_RESBLOCK",), ("FUSE_STREAM",), ("FUSE_SPECBLOCK",), ("STREAM_STAGE0",), SWITCHES)]
+    VARIANTS.append((_base, (), {"stream_defer_spec": False}))
 
 
-def _key(name, block):
-    return name + (" [caches_out]" if block else "")
+def _blocks(name):
+    return (False, True) if SCENARIOS[name][1] == "streaming" else (False,)
+
+
+# (scenario, state block, switches off, extra exec options) — a streaming scenario is walked twice.  The variants come first so
+# that `--write` leaves every line of the fixture that was there before them where it was, the last one included.
+CASES = ([(name, block, off, extra) for name, off, extra in VARIANTS for block in _blocks(name)]
+         + [(name, block, (), {}) for name in SCENARIOS for block in _blocks(name)])
+
+
+def _key(name, block, off=(), extra={}):
+    what = ["all switches" if off == SWITCHES else " ".join(off)] * bool(off) + [f"{k}={v}" for k, v in extra.items()]
+    return name + (" {" + ", ".join(what) + (" off" if off else "") + "}" if what else "") + (" [caches_out]" if block else "")
 
 
 @functools.lru_cache(maxsize=None)
@@ -109,12 +126,23 @@ class _Recorder(TorchDispatchMode):
         return out
 
 
-def trace(name, block):
-    """the rows of one scenario: run_encoder, then run_decoder on what it returned"""
+def trace(name, block, off=(), extra={}):
+    """the rows of one scenario: run_encoder, then run_decoder on what it returned; `off` = the module switches that are False meanwhile"""
+    saved = {sw: getattr(engine, sw) for sw in off}
+    try:
+        for sw in off:
+            setattr(engine, sw, False)
+        return _trace(name, block, extra)
+    finally:
+        for sw, v in saved.items():
+            setattr(engine, sw, v)
+
+
+def _trace(name, block, extra):
     model_name, mode, B, T, opts = SCENARIOS[name]
     streaming = mode == "streaming"
     es, ds = _specs(model_name, streaming)
-    opts = engine.ExecOptions(**opts)
+    opts = engine.ExecOptions(**dict(opts, **extra))
     rec = _Recorder()
     rec.name_tree(es, "es")
     rec.name_tree(ds, "ds")
@@ -162,13 +190,13 @@ def _golden():
 
 
 def test_fixture_lists_every_case():
-    assert sorted(_golden()) == sorted(_key(n, b) for n, b in CASES)
+    assert sorted(_golden()) == sorted(_key(*c) for c in CASES) and len(set(_key(*c) for c in CASES)) == len(CASES)
 
 
-@pytest.mark.parametrize("name,block", CASES, ids=[_key(n, b) for n, b in CASES])
-def test_plan_matches_the_recorded_trace(name, block):
-    rows = trace(name, block)
-    want = _golden()[_key(name, block)]
+@pytest.mark.parametrize("name,block,off,extra", CASES, ids=[_key(*c) for c in CASES])
+def test_plan_matches_the_recorded_trace(name, block, off, extra):
+    rows = trace(name, block, off, extra)
+    want = _golden()[_key(name, block, off, extra)]
     assert _launches(rows) == want["ops"]
     assert _digest(rows) == want["sha256"], "same ops, another argument: `python tests/test_plan_cpu.py --dump DIR` in both trees and diff"
 
@@ -184,11 +212,11 @@ def test_launch_counts_of_the_default_plans(name, block, count):
 if __name__ == "__main__":
     if len(sys.argv) == 3 and sys.argv[1] == "--dump":
         os.makedirs(sys.argv[2], exist_ok=True)
-        for i, (n, b) in enumerate(CASES):
+        for i, c in enumerate(CASES):
             with open(os.path.join(sys.argv[2], f"{i:02d}.json"), "w") as f:
-                json.dump({"scenario": _key(n, b), "rows": trace(n, b)}, f, indent=0)
+                json.dump({"scenario": _key(*c), "rows": trace(*c)}, f, indent=0)
     elif sys.argv[1:] == ["--write"]:
         with open(GOLDEN, "w") as f:       # one scenario per line
-            f.write("{\n" + ",\n".join(f"{json.dumps(_key(n, b))}: {json.dumps(summary(trace(n, b)), sort_keys=True)}" for n, b in CASES) + "\n}\n")
+            f.write("{\n" + ",\n".join(f"{json.dumps(_key(*c))}: {json.dumps(summary(trace(*c)), sort_keys=True)}" for c in CASES) + "\n}\n")
     else:
         sys.exit(__doc__)
