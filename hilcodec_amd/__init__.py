@@ -13,5 +13,8 @@ from .ops import room_mix as mix_rooms  # noqa: F401
 from . import forward  # noqa: F401
 from .forward import ForwardConfig  # noqa: F401
 from .graph_step import GraphedForwardHop  # noqa: F401
+# its downlink control (rate control and NACK answers per listener): the definition (import it by name) and the configuration
+from . import downlink  # noqa: F401
+from .downlink import DownlinkConfig  # noqa: F401
 
-__all__ = ["HILCodec", "Resampler", "resample", "MixConfig", "mix_rooms", "forward", "ForwardConfig", "GraphedForwardHop"]
+__all__ = ["HILCodec", "Resampler", "resample", "MixConfig", "mix_rooms", "forward", "ForwardConfig", "GraphedForwardHop", "downlink", "DownlinkConfig"]

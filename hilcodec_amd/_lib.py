@@ -95,6 +95,8 @@ SIGNATURES = {
     "hilc_rate_charge": [_p, _p, _p, _i, _i, _i, _p],
     "hilc_forward_classify": [_p, _p, _i, _p, _p, _p, _p] + [_i] * 7 + [_p],
     "hilc_forward_route": [_p, _i] + [_p] * 11 + [_i] * 8 + [_p],
+    "hilc_downlink_store": [_p, _i] + [_p] * 6 + [_i] * 6 + [_p],
+    "hilc_downlink_step": [_p] * 19 + [_i] * 18 + [_p],
 }
 
 ABI_VERSION = 16

@@ -9,11 +9,11 @@
 //                          newcomers and writes every output row, one lane per byte, cut to the listener's layers.
 //
 // The rules, bit for bit: hilcodec_amd/forward.py (SenderModel, ListenerModel); the rows: include/hilcodec_amd.h (HILC_FORWARD_*).
-#include "jitter_ring.h"
+#include "trim.h"
 
 namespace {
 
-using namespace jring;
+using namespace trim;
 
 // Wave-uniform control flow over the slot's arrivals; the counters live in registers and lane 0 stores them.  Lane k < burst keeps
 // the k-th picked record index.
@@ -65,57 +65,18 @@ __global__ __launch_bounds__(THREADS) void forward_classify_kernel(const int* __
 // a candidate's rank as two ints, compared lexicographically, larger first: hi = SD_HANG << 16 | SD_SINCE, lo = -slot; hi < 0: none
 __device__ __forceinline__ bool ahead(int ha, int la, int hb, int lb) { return ha > hb || (ha == hb && la > lb); }
 
-// What row (b, j, k) is cut from: the arrival record (null: an empty row), and the cut of forward.trim_packet
-struct Cut {
-  const uint8_t* src;                // the headed packet's bytes; null: the row is empty
-  int len;                           // bytes of the output row
-  int flags;                         // its header byte 2
-  int body;                          // the source's body bytes
-  int prim, end, shift;              // body bits [0, prim) come from the same source bit, [prim, end) from source bit + shift
-  bool sid, trimmed;
-};
-
+// What row (b, j, k) is cut from: the arrival record (an empty Cut: an empty row), and the cut of forward.trim_packet (trim.h)
 __device__ __forceinline__ Cut cut_of(const int* __restrict__ arr, int max_a, int aw, const int* __restrict__ pick,
                                       const int* __restrict__ pick_count, int t, int k, int burst, int L, int tb, int T, int n_max, int m,
                                       int order, int keep_fec) {
-  Cut c;
-  c.src = nullptr;
-  c.len = c.flags = c.body = c.prim = c.end = c.shift = 0;
-  c.sid = c.trimmed = false;
-  if (t < 0 || k >= min(pick_count[t], burst)) return c;
+  if (t < 0 || k >= min(pick_count[t], burst)) return no_cut();
   const int a = pick[(long)t * burst + k];
-  if (a < 0 || a >= max_a) return c;
+  if (a < 0 || a >= max_a) return no_cut();
   const int* rec = arr + (long)a * (1 + aw);
   const Arrival p = parse_arrival(rec, tb, T, n_max, m, order);
-  if (!p.ok) return c;                                      // never for a record the first launch picked
-  c.src = (const uint8_t*)(rec + 1);
-  c.sid = p.sid;
-  c.body = p.body;
-  if (p.sid) {
-    c.len = HILC_WIRE_TRANSPORT_HEADER + p.body;
-    return c;
-  }
-  const int keep = min(p.n, L);
-  const bool red = p.fb && keep_fec != 0 && keep >= m;
-  c.prim = 10 * keep * T;
-  c.end = c.prim + (red ? 10 * m * T : 0);
-  c.shift = 10 * (p.n - keep) * T;
-  c.flags = keep | (red ? HILC_WIRE_FEC_BIT : 0);
-  c.len = HILC_WIRE_TRANSPORT_HEADER + code_bytes(c.end / 10);
-  c.trimmed = keep < p.n;
-  return c;
+  if (!p.ok) return no_cut();                               // never for a record the first launch picked
+  return cut_packet((const uint8_t*)(rec + 1), p.sid, p.fb, p.n, p.body, L, T, m, keep_fec);
 }
-
-// the 8 bits from bit `bit` on of a body of `body` bytes (behind the header), zero past its last byte
-__device__ __forceinline__ uint32_t window8(const uint8_t* __restrict__ src, int bit, int body) {
-  const int q = bit >> 3;
-  const uint32_t hi = q < body ? src[HILC_WIRE_TRANSPORT_HEADER + q] : 0u;
-  const uint32_t lo = q + 1 < body ? src[HILC_WIRE_TRANSPORT_HEADER + q + 1] : 0u;
-  return (((hi << 8) | lo) >> (8 - (bit & 7))) & 0xFFu;
-}
-
-// the `count` leading bits of a byte, count clamped to [0, 8]
-__device__ __forceinline__ uint32_t lead_bits(int count) { return (0xFF00u >> clampi(count, 0, 8)) & 0xFFu; }
 
 // Lane j < fanout holds route j's owner, lane k < fanout round k's pick; both move by shuffles under wave-uniform control flow.
 __global__ __launch_bounds__(THREADS) void forward_route_kernel(const int* __restrict__ arr, int max_a, int aw,
@@ -236,20 +197,7 @@ __global__ __launch_bounds__(THREADS) void forward_route_kernel(const int* __res
     const int k = (e - j * per_route) / tb;
     const int q = e - j * per_route - k * tb;               // the byte of the row
     const Cut c = cut_of(arr, max_a, aw, pick, pick_count, t, k, burst, L, tb, T, n_max, m, order, keep_fec);
-    uint32_t v = 0;
-    if (q < c.len) {
-      if (c.sid || q < 2) {
-        v = c.src[q];
-      } else if (q == 2) {
-        v = (uint32_t)c.flags;
-      } else {
-        const int bit = 8 * (q - HILC_WIRE_TRANSPORT_HEADER);
-        const uint32_t ma = lead_bits(c.prim - bit), mb = lead_bits(c.end - bit) & ~ma;
-        if (ma) v = window8(c.src, bit, c.body) & ma;
-        if (mb) v |= window8(c.src, bit + c.shift, c.body) & mb;
-      }
-    }
-    orow[e] = (uint8_t)v;
+    orow[e] = (uint8_t)cut_byte(c, q);
   }
 }
 

@@ -47,9 +47,10 @@ Limits.  Speaker selection rests on the senders' DTX: silence arrives as SIDs or
 member is always active and the earliest ones keep the routes: use fanout >= room size - 1 there.  hang_hops should exceed the
 sender's DTX hang-over, so that the first SID of a silence is still forwarded.
 
-Out of scope: answering listeners' NACKs from a history at the forwarder; per-listener byte budgets; deriving `layers` from
-receiver reports (a caller can feed rate.py's ceiling into set_layers); level-based selection for senders without DTX; re-stamping
-hop indices; more than one room per slot."""
+Feedback.  Answering listeners' NACKs from a history at the forwarder, per-listener byte budgets and deriving the layers from receiver
+reports are downlink.py's (GraphedForwardHop(downlink=)): two further launches that read what these two wrote; `layers` stays the cap.
+
+Out of scope: level-based selection for senders without DTX; re-stamping hop indices; more than one room per slot."""
 from __future__ import annotations
 
 from dataclasses import dataclass

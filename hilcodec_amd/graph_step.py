@@ -25,6 +25,7 @@ from torch import Tensor
 
 from . import dtx as dtx_def
 from . import engine, ops, wire
+from . import downlink as downlink_def
 from . import forward as forward_def
 from . import rate as rate_def
 from . import report as report_def
@@ -1608,12 +1609,21 @@ class GraphedForwardHop(_GraphPair):
     A hop is one upload (the stage's rows — action, room, layers — the offsets and the arrival records, staged as
     GraphedDecodeHop.play stages them) and the replay of a graph of two launches (hilc_forward_classify, hilc_forward_route); two
     graphs are captured and replayed alternately, so what `forward` returns stays valid for one further call.
-    `cfg`: the forward.ForwardConfig; `max_arrivals`: the most arrivals of one hop (default 2 B)."""
+    `cfg`: the forward.ForwardConfig; `max_arrivals`: the most arrivals of one hop (default 2 B).
+    `downlink` (a downlink.DownlinkConfig; hilcodec_amd/downlink.py: the rules): the listeners' receiver reports and NACKs come back with
+    a hop (`forward(..., reports=, nacks=)`, one per listener and route), and two further launches follow the two above in the same
+    graph, one behind the other (hilc_downlink_store, hilc_downlink_step): with `rate`, each listener's downlink gets a rate that
+    follows its reports and a bucket, and the hop's rows are cut to the layers the bucket pays for (`eff_layers`; `set_layers` stays the
+    cap); with `history`, every sender slot's arrivals are kept and the NACKs are answered from them (`rtx_packets`, `rtx_nbytes`,
+    `rtx_routes`: a retransmission is played into the client's slot of that route like any arrival).  The feedback rows travel in the
+    same upload, and apply to exactly one hop.  Without `downlink` nothing of this is allocated or launched."""
 
     def __init__(self, batch: int, frames: int, n: int, device: torch.device, fec_stages: int = 0, cng_order: Optional[int] = None,
-                 cfg: forward_def.ForwardConfig = forward_def.ForwardConfig(), max_arrivals: Optional[int] = None, warmup: int = 2):
+                 cfg: forward_def.ForwardConfig = forward_def.ForwardConfig(), max_arrivals: Optional[int] = None, warmup: int = 2,
+                 downlink: Optional[downlink_def.DownlinkConfig] = None):
         if not isinstance(cfg, forward_def.ForwardConfig):
             raise ValueError(f"GraphedForwardHop: cfg must be a forward.ForwardConfig, got {cfg!r}")
+        self.downlink = _config_arg("downlink", downlink, downlink_def.DownlinkConfig)
         super().__init__(_int_arg("batch", batch, 1), device)
         B = self.batch
         self.frames, self.n, self.cfg = _int_arg("frames", frames, 1), _int_arg("n", n, 1, 31), cfg
@@ -1625,23 +1635,65 @@ class GraphedForwardHop(_GraphPair):
             dtx_def.check_order(self.cng_order, self.tstride - wire.TRANSPORT_HEADER, "GraphedForwardHop(cng_order=...)")
         # ONE device buffer, captured by address, uploaded up to the last arrival used: the action, room and layers rows, the
         # arrival region (an arrival record: byte count, then the headed packet)
-        st = self.stage = ControlStage(B, ("action", "room", "layers"), 0, 0, 0, device, arrivals=(self.max_arrivals, self.tstride))
-        self.offsets, self.arrivals = st.offsets, st.arrivals
         F, P = cfg.fanout, cfg.burst
+        # with `downlink`: behind them the feedback rows in use, int32 [B, fanout] each (fanout stage rows laid end to end)
+        self._fb_names = () if downlink is None else \
+            ("report",) * (downlink.rate is not None) + ("nack_base", "nack_bitmap") * (downlink.history > 0)
+        fb_rows = tuple(f"{name}{j}" for name in self._fb_names for j in range(F))
+        st = self.stage = ControlStage(B, ("action", "room", "layers") + fb_rows, 0, 0, 0, device,
+                                       arrivals=(self.max_arrivals, self.tstride))
+        self.offsets, self.arrivals = st.offsets, st.arrivals
+        self._fb = {name: st.dev[st.row_off[name + "0"]:st.row_off[name + "0"] + B * F].view(torch.int32).view(B, F)
+                    for name in self._fb_names}
+        self._h_fb = {name: st.host[st.row_off[name + "0"]:st.row_off[name + "0"] + B * F].view(torch.int32).view(B, F)
+                      for name in self._fb_names}
+        self._fb_live = False                 # the feedback rows hold entries on the device
         self._sd, self._lr = self._slot_state(forward_def.SD_WORDS), self._slot_state(forward_def.LR_WORDS)
         self._pick, self._pick_count = self._slot_state(P), self._slot_state()
         self._routes, self._new_routes = self._slot_state(F, cleared=-1), self._slot_state(F)
         self._out = [self._slot_state(F, P, self.tstride, dtype=torch.uint8) for _ in (0, 1)]
         self._out_nbytes = [self._slot_state(F, P) for _ in (0, 1)]
         self._joined = set()                  # the slots joined since the last hop
+        if downlink is not None:
+            self._init_downlink(downlink)
         self.graphs, self.outs = self._capture_pair(self._hop, warmup)
+
+    def _init_downlink(self, dl: downlink_def.DownlinkConfig) -> None:
+        """the state of the two downlink launches: the listener rows (as after a reset), the routes' memory, the senders' histories,
+        and per parity the rows that `forward` returns instead of the route launch's, the layers they were cut to and the
+        retransmissions"""
+        F, P, R, Q = self.cfg.fanout, self.cfg.burst, dl.history, dl.per_hop
+        bits = downlink_def.bucket(dl, self.frames, self.fec_stages, F, self.cfg.keep_fec)      # ValueError: the rates do not fit
+        burst_hops = 0 if dl.rate is None else dl.rate.burst_hops
+        self._dl = self._slot_state(downlink_def.DL_WORDS, cleared={downlink_def.DL_RATE_Q8: 256 * bits.start_bits,
+                                                                    downlink_def.DL_CREDIT: burst_hops * bits.start_bits})
+        self._dl_mem = self._slot_state(F)
+        self._dl_out = [self._slot_state(F, P, self.tstride, dtype=torch.uint8) for _ in (0, 1)]
+        self._dl_nbytes = [self._slot_state(F, P) for _ in (0, 1)]
+        self._eff = [self._slot_state(cleared=self.n) for _ in (0, 1)]
+        self._hist = None
+        if R > 0:
+            self._hist = (self._slot_state(R), self._slot_state(R, arrival_width(self.tstride)), self._slot_state(downlink_def.DS_WORDS))
+            self._rtx = [(self._slot_state(Q, self.tstride, dtype=torch.uint8), self._slot_state(Q), self._slot_state(Q, cleared=-1))
+                         for _ in (0, 1)]
 
     def _hop(self, p: int) -> Tuple[Tensor, Tensor]:
         st, args = self.stage, (self.cfg, self.n, self.frames, self.fec_stages, self.cng_order)
         ops.forward_classify(self.arrivals, self.offsets, self._sd, self._pick, self._pick_count, *args, action=st.row["action"])
         ops.forward_route(self.arrivals, st.row["room"], st.row["layers"], self._sd, self._pick, self._pick_count, self._routes,
                           self._new_routes, self._lr, self._out[p], self._out_nbytes[p], *args, action=st.row["action"])
-        return self._out[p], self._out_nbytes[p]
+        if self.downlink is None:
+            return self._out[p], self._out_nbytes[p]
+        history = {}
+        if self._hist is not None:
+            tags, ring, rows = self._hist
+            ops.downlink_store(self.arrivals, self._pick, self._pick_count, tags, ring, rows, self.n, self.frames, self.fec_stages,
+                               action=st.row["action"])
+            history = dict(zip(("rtx_out", "rtx_nbytes", "rtx_routes"), self._rtx[p]), tags=tags, ring=ring)
+        ops.downlink_step(self._routes, self._new_routes, self._out[p], self._out_nbytes[p], st.row["layers"], self._dl, self._dl_mem,
+                          self._eff[p], self._dl_out[p], self._dl_nbytes[p], self.downlink, self.cfg, self.n, self.frames,
+                          self.fec_stages, action=st.row["action"], **self._fb, **history)
+        return self._dl_out[p], self._dl_nbytes[p]
 
     def _zero(self) -> None:
         """every slot as constructed: in no room, n layers, no route, every row and output zero"""
@@ -1713,17 +1765,84 @@ class GraphedForwardHop(_GraphPair):
         the graph."""
         return self._lr
 
-    def forward(self, slots, packets: Tensor, nbytes) -> Tuple[Tensor, Tensor]:
+    def _last(self, what: str, need_history: bool = False):
+        """a downlink view (RuntimeError without the option it belongs to); ping-pong rows: those of the graph that ran last"""
+        self._need(self.downlink is not None, what, "downlink=DownlinkConfig(...)")
+        self._need(not need_history or self.downlink.history > 0, what, "downlink=DownlinkConfig(history=...)")
+        return self.parity ^ 1
+
+    @property
+    def eff_layers(self) -> Tensor:
+        """int32 `[B]` device view: the layers each listener's rows of the last hop were cut to (downlink only; at most its `layers`).
+        Read-only: written by the graph, overwritten by the next-but-one call."""
+        p = self._last("eff_layers")
+        return self._eff[p]
+
+    @property
+    def downlink_state(self) -> Tensor:
+        """int32 `[B, downlink.DL_WORDS]` device view: each listener's downlink row after the last hop (downlink.DL_*; downlink only;
+        downlink.kbps gives its rate in kbps).  Read-only: written by the graph."""
+        self._last("downlink_state")
+        return self._dl
+
+    @property
+    def history_state(self) -> Tensor:
+        """int32 `[B, downlink.DS_WORDS]` device view: the counter row of each sender slot's history after the last hop
+        (downlink.DS_*; downlink with history only).  Read-only: written by the graph."""
+        self._last("history_state", True)
+        return self._hist[2]
+
+    @property
+    def rtx_packets(self) -> Tensor:
+        """uint8 `[B, per_hop, tb]` device view: the retransmissions of the last hop, zero rows where there is none (downlink with
+        history only).  Read-only: written by the graph, overwritten by the next-but-one call."""
+        p = self._last("rtx_packets", True)
+        return self._rtx[p][0]
+
+    @property
+    def rtx_nbytes(self) -> Tensor:
+        """int32 `[B, per_hop]` device view: the byte counts of `rtx_packets`, 0 for no retransmission (downlink with history only)"""
+        p = self._last("rtx_nbytes", True)
+        return self._rtx[p][1]
+
+    @property
+    def rtx_routes(self) -> Tensor:
+        """int32 `[B, per_hop]` device view: the route each row of `rtx_packets` belongs to, -1 for no retransmission (downlink with
+        history only)"""
+        p = self._last("rtx_routes", True)
+        return self._rtx[p][2]
+
+    def _feedback(self, reports, nacks) -> Optional[dict]:
+        """forward's `reports` / `nacks` checked before anything is uploaded -> the feedback rows (downlink.feedback_rows), None for
+        none"""
+        dl = self.downlink
+        if reports is not None:
+            self._need(dl is not None and dl.rate is not None, "forward(reports=...)", "downlink=DownlinkConfig(rate=...)")
+        if nacks is not None:
+            self._need(dl is not None and dl.history > 0, "forward(nacks=...)", "downlink=DownlinkConfig(history=...)")
+        if reports is None and nacks is None:
+            return None
+        return downlink_def.feedback_rows(self.batch, self.cfg.fanout, reports, nacks)
+
+    def forward(self, slots, packets: Tensor, nbytes, reports=None, nacks=None) -> Tuple[Tensor, Tensor]:
         """one hop: this hop's arrivals, in push order — `slots` and `nbytes` (A host ints), `packets` uint8 `[A,
         wire.transport_bytes(n, m, frames)]` (host or device), 0 <= A <= max_arrivals.  Returns (out uint8 `[B, fanout, burst, tb]`,
         out_nbytes int32 `[B, fanout, burst]`): row (b, j, k) is the k-th packet of this hop for listener b's route j, cut to its layers
-        (0 bytes: none); static views that the next-but-one call overwrites."""
+        (0 bytes: none); static views that the next-but-one call overwrites.
+        `reports` (downlink with rate only) / `nacks` (downlink with history only): (listeners, routes, blobs), this hop's feedback — A
+        host ints twice, and a uint8 `[A, 3]` / `[A, 4]` host tensor or a sequence of `bytes` (wire.pack_report / wire.pack_nack); a
+        (listener, route) pair named twice keeps its last blob.  With `downlink` the rows returned are cut to `eff_layers`."""
+        fb = self._feedback(reports, nacks)
         arr = check_arrivals("forward", slots, packets, nbytes, self.batch, self.max_arrivals, self.tstride)
         st = self.stage
         st.wait()
         if st.one_hop_live or self._joined:   # the join row: 1 for the slots joined since the last hop
             st.put_one_hop("action", sorted(self._joined), 1)
             self._joined = set()
+        if fb is not None or self._fb_live:   # the feedback rows, likewise: this hop's feedback, 0 elsewhere
+            for name in self._fb_names:
+                self._h_fb[name].zero_() if fb is None else self._h_fb[name].copy_(torch.from_numpy(fb[name]))
+            self._fb_live = fb is not None
         st.send_arrivals(arr, packets)
         st.finish()
         return self._replay()

@@ -24,6 +24,8 @@ import torch
 from torch import Tensor
 
 from ._lib import DownParams, PostParams, ResblockParams, Spec0Params, UpParams, check, lib
+from .downlink import DL_WORDS, DS_WORDS
+from .downlink import bucket as downlink_bucket
 from .dtx import LEVELS, state_words
 from .forward import LR_WORDS, SD_WORDS
 from .jitter import AD_WORDS, ST_WORDS
@@ -1330,6 +1332,77 @@ _register("forward_route", "(Tensor arrivals, Tensor? action, Tensor room, Tenso
           lambda arrivals, action, room, layers, sender_rows, pick, pick_count, routes, new_routes, rows, out, out_nbytes, n, m, frames,
           order, keep_fec: None)
 
+# ======================================================================================================
+# downlink control of the forwarding hop (graph_step.GraphedForwardHop(downlink=); definition: hilcodec_amd/downlink.py; semantics:
+# include/hilcodec_amd.h)
+# ======================================================================================================
+def _downlink_store(arrivals, action, pick, pick_count, tags, ring, rows, n, m, frames):
+    B = pick_count.numel()
+    tb = _forward_arrivals("downlink_store", arrivals, n, m, frames)
+    if pick.dim() != 2 or tags.dim() != 2:
+        raise RuntimeError("downlink_store: pick must be [B, burst] and tags [B, history]")
+    P, R = pick.shape[1], tags.shape[1]
+    if pick.shape[0] != B or tags.shape[0] != B or ring.shape != (B, R, 1 + (tb + 3) // 4) or rows.shape != (B, DS_WORDS):
+        raise RuntimeError(f"downlink_store: pick must be [{B}, {P}], tags [{B}, {R}], ring [{B}, {R}, {1 + (tb + 3) // 4}] and rows "
+                           f"[{B}, {DS_WORDS}]")
+    _rows("downlink_store", B, action=action)
+    check(lib.hilc_downlink_store(_ptr(arrivals, torch.int32), arrivals.shape[0], _ptr(action, torch.int32), _ptr(pick, torch.int32),
+                                  _ptr(pick_count, torch.int32), _ptr(tags, torch.int32), _ptr(ring, torch.int32), _ptr(rows, torch.int32),
+                                  B, frames, n, m, P, R, _stream()), "hilc_downlink_store")
+
+
+_register("downlink_store", "(Tensor arrivals, Tensor? action, Tensor pick, Tensor pick_count, Tensor(a!) tags, Tensor(b!) ring, "
+          "Tensor(c!) rows, int n, int m, int frames) -> ()", _downlink_store,
+          lambda arrivals, action, pick, pick_count, tags, ring, rows, n, m, frames: None)
+
+
+def _downlink_step(routes, new_routes, packets, nbytes, layers, action, report, nack_base, nack_bitmap, tags, ring, rows, memory, eff_layers,
+                   out, out_nbytes, rtx_out, rtx_nbytes, rtx_routes, n, m, frames, keep_fec, rate_on, min_bits, max_bits, start_bits, high_q8,
+                   low_q8, increase_q8, burst_hops, timeout_hops):
+    B = layers.numel()
+    tb = TRANSPORT_HEADER + packet_bytes(n + m, frames)
+    if packets.dim() != 4 or packets.shape[0] != B or packets.shape[3] != tb:
+        raise RuntimeError(f"downlink_step: packets must be uint8 [{B}, fanout, burst, {tb}]")
+    F, P = packets.shape[1], packets.shape[2]
+    if routes.shape != (B, F) or new_routes.shape != (B, F) or nbytes.shape != (B, F, P) or rows.shape != (B, DL_WORDS) or \
+            memory.shape != (B, F) or eff_layers.shape != (B,) or out.shape != (B, F, P, tb) or out_nbytes.shape != (B, F, P):
+        raise RuntimeError(f"downlink_step: routes, new_routes and memory must be [{B}, {F}], nbytes and out_nbytes [{B}, {F}, {P}], rows "
+                           f"[{B}, {DL_WORDS}], eff_layers [{B}] and out [{B}, {F}, {P}, {tb}]")
+    for name, row in (("report", report), ("nack_base", nack_base), ("nack_bitmap", nack_bitmap)):
+        if row is not None and row.shape != (B, F):
+            raise RuntimeError(f"downlink_step: {name} must be [{B}, {F}]")
+    history = [tags, ring, rtx_out, rtx_nbytes, rtx_routes]
+    if any(t is None for t in history) and not all(t is None for t in history):
+        raise RuntimeError("downlink_step: tags, ring, rtx_out, rtx_nbytes and rtx_routes come together or not at all")
+    R = Q = 0
+    if tags is not None:
+        if tags.dim() != 2 or rtx_out.dim() != 3:
+            raise RuntimeError("downlink_step: tags must be [B, history] and rtx_out [B, per_hop, row_bytes]")
+        R, Q = tags.shape[1], rtx_out.shape[1]
+        if tags.shape[0] != B or ring.shape != (B, R, 1 + (tb + 3) // 4) or rtx_out.shape != (B, Q, tb) or rtx_nbytes.shape != (B, Q) or \
+                rtx_routes.shape != (B, Q):
+            raise RuntimeError(f"downlink_step: tags must be [{B}, {R}], ring [{B}, {R}, {1 + (tb + 3) // 4}], rtx_out [{B}, {Q}, {tb}], "
+                               f"rtx_nbytes and rtx_routes [{B}, {Q}]")
+    _rows("downlink_step", B, action=action)
+    check(lib.hilc_downlink_step(_ptr(routes, torch.int32), _ptr(new_routes, torch.int32), _ptr(packets, torch.uint8),
+                                 _ptr(nbytes, torch.int32), _ptr(layers, torch.int32), _ptr(action, torch.int32),
+                                 _ptr(report, torch.int32), _ptr(nack_base, torch.int32), _ptr(nack_bitmap, torch.int32),
+                                 _ptr(tags, torch.int32), _ptr(ring, torch.int32), _ptr(rows, torch.int32), _ptr(memory, torch.int32),
+                                 _ptr(eff_layers, torch.int32), _ptr(out, torch.uint8), _ptr(out_nbytes, torch.int32),
+                                 _ptr(rtx_out, torch.uint8), _ptr(rtx_nbytes, torch.int32), _ptr(rtx_routes, torch.int32), B, frames, n, m,
+                                 F, P, int(keep_fec), R, max(Q, 1), int(rate_on), min_bits, max_bits, start_bits, high_q8, low_q8,
+                                 increase_q8, burst_hops, timeout_hops, _stream()), "hilc_downlink_step")
+
+
+_register("downlink_step", "(Tensor routes, Tensor new_routes, Tensor packets, Tensor nbytes, Tensor layers, Tensor? action, Tensor? report, "
+          "Tensor? nack_base, Tensor? nack_bitmap, Tensor? tags, Tensor? ring, Tensor(a!) rows, Tensor(b!) memory, Tensor(c!) eff_layers, "
+          "Tensor(d!) out, Tensor(e!) out_nbytes, Tensor(f!)? rtx_out, Tensor(g!)? rtx_nbytes, Tensor(h!)? rtx_routes, int n, int m, "
+          "int frames, bool keep_fec, bool rate_on, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, "
+          "int burst_hops, int timeout_hops) -> ()", _downlink_step,
+          lambda routes, new_routes, packets, nbytes, layers, action, report, nack_base, nack_bitmap, tags, ring, rows, memory, eff_layers,
+          out, out_nbytes, rtx_out, rtx_nbytes, rtx_routes, n, m, frames, keep_fec, rate_on, min_bits, max_bits, start_bits, high_q8, low_q8,
+          increase_q8, burst_hops, timeout_hops: None)
+
 _OPS = torch.ops.hilcodec
 
 
@@ -2099,3 +2172,37 @@ def forward_route(arrivals: Tensor, room: Tensor, layers: Tensor, sender_rows: T
     redundant section is kept."""
     _OPS.forward_route(arrivals, action, room, layers, sender_rows, pick, pick_count, routes, new_routes, rows, out, out_nbytes, int(n), int(m),
                        int(frames), -1 if order is None else int(order), bool(cfg.keep_fec))
+
+
+def downlink_store(arrivals: Tensor, pick: Tensor, pick_count: Tensor, tags: Tensor, ring: Tensor, rows: Tensor, n: int, frames: int,
+                   m: int = 0, action: Optional[Tensor] = None) -> None:
+    """The forwarding hop's third launch (downlink.DownlinkModel.store), in place: the arrivals that forward_classify picked on this hop
+    (`arrivals`, `pick` int32 `[B, burst]`, `pick_count` int32 `[B]`) enter each sender slot's history — `tags` (int32 `[B, history]`),
+    `ring` (int32 `[B, history, 1 + ceil(tb / 4)]`: arrival records) — and `rows` (int32 `[B, downlink.DS_WORDS]`) count.  burst and
+    history are read from the shapes; `action` (int32 `[B]`, optional): non-zero empties the slot's history."""
+    _OPS.downlink_store(arrivals, action, pick, pick_count, tags, ring, rows, int(n), int(m), int(frames))
+
+
+def downlink_step(routes: Tensor, new_routes: Tensor, packets: Tensor, nbytes: Tensor, layers: Tensor, rows: Tensor, memory: Tensor,
+                  eff_layers: Tensor, out: Tensor, out_nbytes: Tensor, cfg, fcfg, n: int, frames: int, m: int = 0,
+                  action: Optional[Tensor] = None, report: Optional[Tensor] = None, nack_base: Optional[Tensor] = None,
+                  nack_bitmap: Optional[Tensor] = None, tags: Optional[Tensor] = None, ring: Optional[Tensor] = None,
+                  rtx_out: Optional[Tensor] = None, rtx_nbytes: Optional[Tensor] = None, rtx_routes: Optional[Tensor] = None) -> None:
+    """The forwarding hop's fourth launch (downlink.DownlinkModel.step), in place: with `routes`, `new_routes`, `packets` (uint8 `[B,
+    fanout, burst, tb]`) and `nbytes` as forward_route left them on this hop, `layers` (int32 `[B]`) and this hop's feedback (`report`,
+    `nack_base`, `nack_bitmap`: int32 `[B, fanout]` each, downlink.feedback_rows; optional) -> each listener's row (`rows`, int32 `[B,
+    downlink.DL_WORDS]`), its routes' `memory` (int32 `[B, fanout]`), `eff_layers` (int32 `[B]`), the rows cut to them (`out`,
+    `out_nbytes`, the shapes of `packets`, `nbytes`) and, with cfg.history, the retransmissions answered from `tags` and `ring`
+    (downlink_store): `rtx_out` (uint8 `[B, per_hop, tb]`), `rtx_nbytes` and `rtx_routes` (int32 `[B, per_hop]`).  `cfg`: the
+    downlink.DownlinkConfig (downlink.bucket checks it), `fcfg`: the forward.ForwardConfig."""
+    bits = downlink_bucket(cfg, frames, m, packets.shape[1] if packets.dim() == 4 else fcfg.fanout, fcfg.keep_fec)
+    if (cfg.history > 0) != (tags is not None):
+        raise RuntimeError("downlink_step: tags, ring and the rtx rows are given exactly with cfg.history > 0")
+    if tags is not None and (tags.dim() != 2 or tags.shape[1] != cfg.history or rtx_out is None or rtx_out.dim() != 3 or
+                             rtx_out.shape[1] != cfg.per_hop):
+        raise RuntimeError(f"downlink_step: tags must be [B, {cfg.history}] and rtx_out [B, {cfg.per_hop}, row_bytes]")
+    r = cfg.rate
+    _OPS.downlink_step(routes, new_routes, packets, nbytes, layers, action, report, nack_base, nack_bitmap, tags, ring, rows, memory,
+                       eff_layers, out, out_nbytes, rtx_out, rtx_nbytes, rtx_routes, int(n), int(m), int(frames), bool(fcfg.keep_fec),
+                       r is not None, bits.min_bits, bits.max_bits, bits.start_bits, *((int(r.high_q8), int(r.low_q8), int(r.increase_q8),
+                       int(r.burst_hops), int(r.timeout_hops)) if r is not None else (0, 0, 0, 1, 0)))

@@ -37,7 +37,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream) with per-speaker levelling and a limiter int hilc_mix_gains(const float* wav, double* gains, double* power, const int* action, double gate2, double lo, double hi, double up, double down, double min_gain, double max_gain, double smooth, int B, int L, void* stream) and int hilc_mix_rooms_dyn(const float* wav, const int* room, const double* score, int top_k, const double* gains, double* limiter, double ceiling, double release, int sub, const int* action, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream); and the selective forwarding hop int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick, int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream) and int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers, const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream) with per-speaker levelling and a limiter int hilc_mix_gains(const float* wav, double* gains, double* power, const int* action, double gate2, double lo, double hi, double up, double down, double min_gain, double max_gain, double smooth, int B, int L, void* stream) and int hilc_mix_rooms_dyn(const float* wav, const int* room, const double* score, int top_k, const double* gains, double* limiter, double ceiling, double release, int sub, const int* action, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream); and the selective forwarding hop int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick, int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream) and int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers, const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec, void* stream); and its downlink control int hilc_downlink_store(const int* arrivals, int max_arrivals, const int* action, const int* pick, const int* pick_count, int* tags, int* ring, int* rows, int B, int T, int n_max, int m, int burst, int history, void* stream) and int hilc_downlink_step(const int* routes, const int* new_routes, const uint8_t* in, const int* in_nbytes, const int* layers, const int* action, const int* report, const int* nack_base, const int* nack_bitmap, const int* tags, const int* ring, int* rows, int* memory, int* eff_layers, uint8_t* out, int* out_nbytes, uint8_t* rtx_out, int* rtx_nbytes, int* rtx_routes, int B, int T, int n_max, int m, int fanout, int burst, int keep_fec, int history, int per_hop, int rate_on, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -597,6 +597,38 @@ int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const fl
 #define HILC_FORWARD_MAX_HANG_HOPS 255
 #define HILC_FORWARD_MAX_SINCE 65535
 
+/* downlink control of the forwarding hop (hilcodec_amd/downlink.py).  Listener row of a slot, DL_WORDS words: DL_RATE_Q8 (bits per hop x
+ * 256), DL_CREDIT (the bucket, bits), DL_AGE (hops since the last accepted report), DL_LOSS (the loss_q8 the rate last followed),
+ * DL_LAYERS (the layers of the last hop's rows), then the counters.  One memory word per (listener, route): MEM_SEEN | last << 8 |
+ * loss_q8, 0 when cleared.  Counter row of a sender's history, DS_WORDS words: DS_STORED, DS_REPLACED.  A history holds at most
+ * MAX_HISTORY packets, a listener is sent at most MAX_PER_HOP retransmissions per hop. */
+#define HILC_DOWNLINK_DL_RATE_Q8 0
+#define HILC_DOWNLINK_DL_CREDIT 1
+#define HILC_DOWNLINK_DL_AGE 2
+#define HILC_DOWNLINK_DL_LOSS 3
+#define HILC_DOWNLINK_DL_LAYERS 4
+#define HILC_DOWNLINK_DL_REPORTS 5
+#define HILC_DOWNLINK_DL_STALE 6
+#define HILC_DOWNLINK_DL_DECREASED 7
+#define HILC_DOWNLINK_DL_INCREASED 8
+#define HILC_DOWNLINK_DL_TIMEOUT 9
+#define HILC_DOWNLINK_DL_LIMITED 10
+#define HILC_DOWNLINK_DL_PACKETS 11
+#define HILC_DOWNLINK_DL_BYTES 12
+#define HILC_DOWNLINK_DL_TRIMMED 13
+#define HILC_DOWNLINK_DL_NACK_STALE 14
+#define HILC_DOWNLINK_DL_REQUESTS 15
+#define HILC_DOWNLINK_DL_RTX_SENT 16
+#define HILC_DOWNLINK_DL_RTX_MISS 17
+#define HILC_DOWNLINK_DL_RTX_DROPPED 18
+#define HILC_DOWNLINK_DL_WORDS 19
+#define HILC_DOWNLINK_DS_STORED 0
+#define HILC_DOWNLINK_DS_REPLACED 1
+#define HILC_DOWNLINK_DS_WORDS 2
+#define HILC_DOWNLINK_MEM_SEEN (1 << 16)
+#define HILC_DOWNLINK_MAX_HISTORY 64
+#define HILC_DOWNLINK_MAX_PER_HOP 4
+
 /* ---- per-stream session state of a streaming hop (ABI 16) ------------------------------------------------------------------
  * Layout: the caches of `streams` streams live in ONE fp32 block (hilcodec_amd/graph_step.py StateBlock): slice k (one
  * `[streams][C][L]` cache tensor, k < nslices, in the reference's order: 22 encoder then 30 decoder caches) starts at
@@ -968,6 +1000,49 @@ int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action,
                        const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows,
                        uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec,
                        void* stream);
+
+/* ---- downlink control of the forwarding hop (additive under ABI 16) -----------------------------------------------------------------
+ * Two entry points added WITHOUT a version bump: the third and fourth launch of a forwarding hop.  The definition, bit for bit, is
+ * hilcodec_amd/downlink.py.  tb, aw = ceil(tb / 4) and the arrival records are those of hilc_forward_classify.
+ * hilc_downlink_store: after hilc_forward_classify.  pick int32 [B][burst] and pick_count int32 [B] as that launch left them (read only);
+ * tags int32 [B][history], ring int32 [B][history][1 + aw] and rows int32 [B][HILC_DOWNLINK_DS_WORDS] (in place).  Per sender slot t:
+ * action[t] != 0 empties its tags (the counters stay); each picked arrival, in pick order, goes to entry h mod history, h its own bytes
+ * 0-1: the row becomes its arrival record, zero past the packet's length, the tag h | nbytes << 16; DS_STORED counts them, DS_REPLACED
+ * those whose entry's tag was not 0.  A pick outside [0, max_arrivals) or with a byte count outside [HILC_WIRE_TRANSPORT_HEADER, tb] is
+ * skipped (never for what hilc_forward_classify picked).
+ * hilc_downlink_step: after hilc_forward_route and hilc_downlink_store have finished for every slot.  routes, new_routes int32
+ * [B][fanout], in uint8 [B][fanout][burst][tb] and in_nbytes int32 [B][fanout][burst] as the route launch left them, layers int32 [B],
+ * tags and ring as the store launch left them (all read only; tags and ring are not read with history == 0 and may be NULL); report
+ * (report words, read with rate_on != 0), nack_base and nack_bitmap (NACK words as hilc_rtx_step's, read with history > 0; both or
+ * neither) optional int32 [B][fanout], NULL: no feedback; rows int32 [B][HILC_DOWNLINK_DL_WORDS] and memory int32 [B][fanout] (in place);
+ * eff_layers int32 [B], out uint8 [B][fanout][burst][tb], out_nbytes int32 [B][fanout][burst] and, with history > 0, rtx_out uint8
+ * [B][per_hop][tb], rtx_nbytes and rtx_routes int32 [B][per_hop]: every element written.  Per listener b: action[b] != 0 resets the row
+ * (DL_RATE_Q8 = 256 start_bits, DL_CREDIT = burst_hops start_bits, the rest 0) and clears its routes' memory; a route that is free or new
+ * on this hop has its memory cleared and its feedback dropped (DL_STALE for a report, DL_NACK_STALE for a NACK); with rate_on != 0 the
+ * other reports are accepted by hilc_rate_ceiling's rule into the route's memory word (else DL_STALE), and on a hop with an accepted
+ * report DL_LOSS = the least stored loss_q8 over the routes that have one, DL_AGE = 0 and the rate moves once by hilc_rate_ceiling's
+ * arithmetic; then DL_AGE += 1 with the timeout of hilc_rate_ceiling (it clears every route's seen flag) and the bucket fills;
+ * Lmax = layers[b] clamped to [1, n_max]; L_eff = the largest L in [1, Lmax] for which 8 x the bytes of the non-empty rows cut to L stages
+ * is at most DL_CREDIT, 1 if none is, Lmax with rate_on == 0 or without rows; DL_LAYERS = eff_layers[b] = L_eff, DL_LIMITED += 1 when a
+ * row's n is cut; out row (b, j, k) is in row (b, j, k) cut to L_eff stages by the rule of hilc_forward_route, zero past its length, its
+ * byte count beside it (DL_PACKETS, DL_BYTES, DL_TRIMMED count); with history > 0 the NACKs of the other routes, ascending
+ * (DL_REQUESTS), are answered from the owner's history as hilc_rtx_step answers them — DL_RTX_SENT, DL_RTX_MISS, DL_RTX_DROPPED — each row
+ * cut to L_eff stages, rtx_routes its route, the rows not used zero with count 0 and route -1; with rate_on != 0 DL_CREDIT = max(DL_CREDIT
+ * - 8 (the bytes of out and of rtx_out), -burst_hops (rate >> 8)).
+ * Both: NULL pointers (action, the feedback rows and what history == 0 leaves unread excepted): HILC_ERR_NULL; B, T >= 1, max_arrivals >=
+ * 0, tb < 2^15, and with rate_on != 0: 1 <= min_bits <= start_bits <= max_bits <= HILC_RATE_MAX_RATE_BITS, burst_hops >= 1, max_bits
+ * burst_hops <= 2^30, timeout_hops >= 0 (else HILC_ERR_SHAPE); n_max, m, fanout, burst as hilc_forward_route; history a power of two in
+ * [2, HILC_DOWNLINK_MAX_HISTORY] (hilc_downlink_step: or 0), 1 <= per_hop <= HILC_DOWNLINK_MAX_PER_HOP, history > 0 or rate_on != 0, and
+ * with rate_on != 0: 0 <= low_q8 < high_q8 <= 255, 0 <= increase_q8 <= 65535 (else HILC_ERR_RANGE).  One wave per slot, integer only, no
+ * LDS, no atomics. */
+int hilc_downlink_store(const int* arrivals, int max_arrivals, const int* action, const int* pick, const int* pick_count, int* tags,
+                        int* ring, int* rows, int B, int T, int n_max, int m, int burst, int history, void* stream);
+int hilc_downlink_step(const int* routes, const int* new_routes, const uint8_t* in, const int* in_nbytes, const int* layers,
+                       const int* action, const int* report, const int* nack_base, const int* nack_bitmap, const int* tags,
+                       const int* ring, int* rows, int* memory, int* eff_layers, uint8_t* out, int* out_nbytes, uint8_t* rtx_out,
+                       int* rtx_nbytes, int* rtx_routes, int B, int T, int n_max, int m, int fanout, int burst, int keep_fec, int history,
+                       int per_hop, int rate_on, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8,
+                       int burst_hops, int timeout_hops, void* stream);
 
 #ifdef __cplusplus
 }
