@@ -97,6 +97,8 @@ SIGNATURES = {
     "hilc_forward_route": [_p, _i] + [_p] * 11 + [_i] * 8 + [_p],
     "hilc_downlink_store": [_p, _i] + [_p] * 6 + [_i] * 6 + [_p],
     "hilc_downlink_step": [_p] * 19 + [_i] * 18 + [_p],
+    "hilc_audio_level": [_p, _p, _p, _p, _i, _i, _p],
+    "hilc_forward_rank": [_p] * 7 + [_i] * 7 + [_p],
 }
 
 ABI_VERSION = 16

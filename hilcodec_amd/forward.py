@@ -43,14 +43,19 @@ Listener rule (hilc_forward_route, per slot b, after the sender rule has run for
    [1, n]), zero past its length, its byte count beside it; every other row is zero with count 0.
 6. LR_PACKETS and LR_BYTES count the rows written and their bytes, LR_TRIMMED the packets whose n was cut.
 
-Limits.  Speaker selection rests on the senders' DTX: silence arrives as SIDs or as nothing.  Against senders without DTX every
-member is always active and the earliest ones keep the routes: use fanout >= room size - 1 there.  hang_hops should exceed the
-sender's DTX hang-over, so that the first SID of a silence is still forwarded.
+Limits.  By these two rules alone, speaker selection rests on the senders' DTX: silence arrives as SIDs or as nothing.  Against
+senders without DTX every member is always active and the earliest ones keep the routes: use fanout >= room size - 1 there, or the
+senders' audio levels (below).  hang_hops should exceed the sender's DTX hang-over, so that the first SID of a silence is still
+forwarded.
 
 Feedback.  Answering listeners' NACKs from a history at the forwarder, per-listener byte budgets and deriving the layers from receiver
 reports are downlink.py's (GraphedForwardHop(downlink=)): two further launches that read what these two wrote; `layers` stays the cap.
 
-Out of scope: level-based selection for senders without DTX; re-stamping hop indices; more than one room per slot."""
+Senders without DTX.  Level-based selection is audio_level.py's (GraphedForwardHop(speakers=)): the senders say how loud each hop was,
+one further launch between these two keeps a smoothed loudness per sender and hands hilc_forward_route shadow sender rows whose
+(SD_HANG, SD_SINCE) order is the loudness order; the rules above stay what they are.
+
+Out of scope: re-stamping hop indices; more than one room per slot."""
 from __future__ import annotations
 
 from dataclasses import dataclass

@@ -24,6 +24,7 @@ import torch
 from torch import Tensor
 
 from . import dtx as dtx_def
+from . import audio_level as level_def
 from . import engine, ops, wire
 from . import downlink as downlink_def
 from . import forward as forward_def
@@ -790,13 +791,18 @@ class GraphedEncodeHop(GraphedHop):
     (int32 `[B]`) and `rate_state` (int32 `[B, rate.RC_WORDS]`; `rate.kbps(rate_state, frames)` on the host) are device views.  A `start`
     or a resume resets a slot's row inside the graph (start rate, full bucket, counters 0), `reset` every row; a held or stopped slot
     takes its reports but neither ages nor fills, reports n_ceil = its own n, and still pays for the NACKs it answers; `export` and a
-    resume carry none.  `fec_adapt`, `rtx` and VBR's `cap_kbps` work as without it.  `rate=None` captures exactly the graph without it."""
+    resume carry none.  `fec_adapt`, `rtx` and VBR's `cap_kbps` work as without it.  `rate=None` captures exactly the graph without it.
+    `audio_level=True`: one hilc_audio_level launch measures each slot's 24 kHz hop (behind the input resampler where there is one) in
+    front of the encoder: `.audio_level` (int32 `[B]` device view, valid until the next-but-one `step`, like `.indices`) is the hop's
+    level, -dBov in 1 dB steps in [0, 127] (audio_level.py: the rule), 127 for a held or stopped slot.  It is what a forwarding hop
+    takes as `forward(levels=)`; it travels beside the packet, and nothing else the hop returns changes.  `audio_level=False` captures
+    exactly the graph without it."""
 
     def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, input_rate: int = BASE_RATE, fec_stages: int = 0,
                  dtx: Optional[dtx_def.DtxConfig] = None, header: bool = False, vbr: Optional[vbr_def.VbrConfig] = None,
                  fec_adapt: Optional[report_def.FecAdaptConfig] = None, rtx: Optional[rtx_def.RtxConfig] = None,
-                 rate: Optional[rate_def.RateConfig] = None):
+                 rate: Optional[rate_def.RateConfig] = None, audio_level: bool = False):
         # the options are checked and what they derive is set up first: GraphedHop's constructor allocates (_init_state) and captures
         self.fec_stages = _fec_stages(fec_stages, n)
         self.fec_adapt = _config_arg("fec_adapt", fec_adapt, report_def.FecAdaptConfig)
@@ -814,6 +820,7 @@ class GraphedEncodeHop(GraphedHop):
             # ValueError: a min_kbps that does not pay for the floor of a hop, a max_kbps past the int32 rows
             self._rate_bits = rate_def.bucket(rate, _whole_frames("GraphedEncodeHop(rate=...)", hop), self.fec_stages, self.header)
         self._nacks = {}                      # slot -> (word, bitmap) for the next hop
+        self._measure_level = bool(audio_level)
         self.frames = hop // HOP
         self.dtx = _config_arg("dtx", dtx, dtx_def.DtxConfig)
         if dtx is not None:
@@ -842,7 +849,7 @@ class GraphedEncodeHop(GraphedHop):
 
     def _init_state(self) -> None:
         n, m, T = self.n, self.fec_stages, self.frames
-        self._prev = self._run = self._ctr = self._credit = self._fa = self._fec_on = self._rx = self._rc = self._n_ceil = None
+        self._prev = self._run = self._ctr = self._credit = self._fa = self._fec_on = self._rx = self._rc = self._n_ceil = self._level = None
         if m:
             # per parity, per slot: valid, then the first m stages x T frames of its last encoded hop (the hop of parity p reads
             # row p and writes row p ^ 1)
@@ -878,6 +885,10 @@ class GraphedEncodeHop(GraphedHop):
             self._rc = self._slot_state(rate_def.RC_WORDS, cleared={rate_def.RC_RATE_Q8: 256 * start,
                                                                      rate_def.RC_CREDIT: self.rate.burst_hops * start})
             self._n_ceil = self._slot_state(cleared=int(n))
+        if self._measure_level:
+            # per parity, per slot: the hop's level (the hop of parity p writes row p); cleared = silence
+            self._level = self._slot_state(pingpong=True, cleared=level_def.MAX_LEVEL)
+            self._level_thr = torch.from_numpy(dtx_def.level_table()).to(self.device)
 
     def _block(self, streams: int) -> StateBlock:
         return StateBlock(self.model, streams, self.device, "enc", self._history)
@@ -896,6 +907,8 @@ class GraphedEncodeHop(GraphedHop):
         x = self.x
         if self.rs is not None:
             x = ops.resample_poly(x, self.rs_taps, self.rs.L, self.rs.M, hist=src.hist, hist_out=dst.hist)
+        if self._level is not None:
+            ops.audio_level(x, self._level_thr, self._level[p], hold)
         with ops.sched_workspace(self.sched[0]):
             with engine.spectra_side_stream(self.spec_side[0]):
                 z, _ = m.encoder(x, *src.codec_enc, cache_out=dst.codec_enc)
@@ -942,6 +955,13 @@ class GraphedEncodeHop(GraphedHop):
             ops.rate_charge(nbytes, self._rc, self.rate, self._rx_nbytes[p] if self.rtx is not None else None)
         out = (idx, packets, nbytes) if kind is None else (idx, packets, nbytes, kind)
         return out if n_eff is None else out + (n_eff, distortion)
+
+    @property
+    def audio_level(self) -> Tensor:
+        """int32 `[B]` device view: the level of each slot's last hop, -dBov in 1 dB steps (audio_level=True only; a held slot: 127);
+        overwritten by the next-but-one `step`.  Read-only: written by the graph."""
+        self._need(self._level is not None, "audio_level", "audio_level=True")
+        return self._level[self.parity ^ 1]
 
     @property
     def credit(self) -> Tensor:
@@ -1616,14 +1636,22 @@ class GraphedForwardHop(_GraphPair):
     follows its reports and a bucket, and the hop's rows are cut to the layers the bucket pays for (`eff_layers`; `set_layers` stays the
     cap); with `history`, every sender slot's arrivals are kept and the NACKs are answered from them (`rtx_packets`, `rtx_nbytes`,
     `rtx_routes`: a retransmission is played into the client's slot of that route like any arrival).  The feedback rows travel in the
-    same upload, and apply to exactly one hop.  Without `downlink` nothing of this is allocated or launched."""
+    same upload, and apply to exactly one hop.  Without `downlink` nothing of this is allocated or launched.
+    `speakers` (an audio_level.SpeakerConfig; hilcodec_amd/audio_level.py: the rules): level-based speaker selection, for senders without
+    DTX.  `forward(..., levels=)` takes one level per arrival (what the sender's `audio_level` said: 0..127, -1: unknown); the host reduces
+    them to the loudest per slot into one more one-hop row of the same upload, and one launch (hilc_forward_rank) between the two above
+    keeps each sender's smoothed loudness and writes a ping-pong pair of shadow sender rows, which hilc_forward_route reads in place of
+    the real ones: it then selects a room's loudest speakers, with a margin for those on stage.  `speaker_state` and `speaker_rank` show
+    the result; `sender_state` stays the real rows, and the downlink launches follow unchanged.  `speakers=None` allocates nothing and
+    captures exactly the graph without it."""
 
     def __init__(self, batch: int, frames: int, n: int, device: torch.device, fec_stages: int = 0, cng_order: Optional[int] = None,
                  cfg: forward_def.ForwardConfig = forward_def.ForwardConfig(), max_arrivals: Optional[int] = None, warmup: int = 2,
-                 downlink: Optional[downlink_def.DownlinkConfig] = None):
+                 downlink: Optional[downlink_def.DownlinkConfig] = None, speakers: Optional[level_def.SpeakerConfig] = None):
         if not isinstance(cfg, forward_def.ForwardConfig):
             raise ValueError(f"GraphedForwardHop: cfg must be a forward.ForwardConfig, got {cfg!r}")
         self.downlink = _config_arg("downlink", downlink, downlink_def.DownlinkConfig)
+        self.speakers = _config_arg("speakers", speakers, level_def.SpeakerConfig)
         super().__init__(_int_arg("batch", batch, 1), device)
         B = self.batch
         self.frames, self.n, self.cfg = _int_arg("frames", frames, 1), _int_arg("n", n, 1, 31), cfg
@@ -1640,7 +1668,8 @@ class GraphedForwardHop(_GraphPair):
         self._fb_names = () if downlink is None else \
             ("report",) * (downlink.rate is not None) + ("nack_base", "nack_bitmap") * (downlink.history > 0)
         fb_rows = tuple(f"{name}{j}" for name in self._fb_names for j in range(F))
-        st = self.stage = ControlStage(B, ("action", "room", "layers") + fb_rows, 0, 0, 0, device,
+        # with `speakers`: the one-hop row loud (128 - the loudest level of the slot's arrivals, 0: none)
+        st = self.stage = ControlStage(B, ("action", "room", "layers") + ("loud",) * (speakers is not None) + fb_rows, 0, 0, 0, device,
                                        arrivals=(self.max_arrivals, self.tstride))
         self.offsets, self.arrivals = st.offsets, st.arrivals
         self._fb = {name: st.dev[st.row_off[name + "0"]:st.row_off[name + "0"] + B * F].view(torch.int32).view(B, F)
@@ -1654,6 +1683,11 @@ class GraphedForwardHop(_GraphPair):
         self._out = [self._slot_state(F, P, self.tstride, dtype=torch.uint8) for _ in (0, 1)]
         self._out_nbytes = [self._slot_state(F, P) for _ in (0, 1)]
         self._joined = set()                  # the slots joined since the last hop
+        self._shadow = self._sp = None
+        if speakers is not None:
+            # per parity, per slot: the shadow sender row (the hop of parity p reads row p and writes row p ^ 1); per slot: the speaker row
+            self._shadow = self._slot_state(forward_def.SD_WORDS, pingpong=True)
+            self._sp = self._slot_state(level_def.SP_WORDS)
         if downlink is not None:
             self._init_downlink(downlink)
         self.graphs, self.outs = self._capture_pair(self._hop, warmup)
@@ -1680,7 +1714,13 @@ class GraphedForwardHop(_GraphPair):
     def _hop(self, p: int) -> Tuple[Tensor, Tensor]:
         st, args = self.stage, (self.cfg, self.n, self.frames, self.fec_stages, self.cng_order)
         ops.forward_classify(self.arrivals, self.offsets, self._sd, self._pick, self._pick_count, *args, action=st.row["action"])
-        ops.forward_route(self.arrivals, st.row["room"], st.row["layers"], self._sd, self._pick, self._pick_count, self._routes,
+        ranked = self._sd
+        if self.speakers is not None:
+            # between the two: the route launch sorts by the shadow rows' (SD_HANG, SD_SINCE), which is the loudness key's order
+            ranked = self._shadow[p ^ 1]
+            ops.forward_rank(self._sd, st.row["loud"], st.row["room"], self._shadow[p], ranked, self._sp, self.cfg, self.speakers,
+                             action=st.row["action"])
+        ops.forward_route(self.arrivals, st.row["room"], st.row["layers"], ranked, self._pick, self._pick_count, self._routes,
                           self._new_routes, self._lr, self._out[p], self._out_nbytes[p], *args, action=st.row["action"])
         if self.downlink is None:
             return self._out[p], self._out_nbytes[p]
@@ -1765,6 +1805,19 @@ class GraphedForwardHop(_GraphPair):
         the graph."""
         return self._lr
 
+    @property
+    def speaker_state(self) -> Tensor:
+        """int32 `[B, audio_level.SP_WORDS]` device view: each slot's speaker row after the last hop (audio_level.SP_*; speakers only).
+        Read-only: written by the graph."""
+        self._need(self._sp is not None, "speaker_state", "speakers=SpeakerConfig(...)")
+        return self._sp
+
+    @property
+    def speaker_rank(self) -> Tensor:
+        """int32 `[B]` device view, the SP_RANK column of `speaker_state`: each slot's place among its room's speakers, one hop behind
+        (0: the room's dominant speaker, -1: no candidate; speakers only).  Read-only: written by the graph."""
+        return self.speaker_state[:, level_def.SP_RANK]
+
     def _last(self, what: str, need_history: bool = False):
         """a downlink view (RuntimeError without the option it belongs to); ping-pong rows: those of the graph that ran last"""
         self._need(self.downlink is not None, what, "downlink=DownlinkConfig(...)")
@@ -1824,16 +1877,23 @@ class GraphedForwardHop(_GraphPair):
             return None
         return downlink_def.feedback_rows(self.batch, self.cfg.fanout, reports, nacks)
 
-    def forward(self, slots, packets: Tensor, nbytes, reports=None, nacks=None) -> Tuple[Tensor, Tensor]:
+    def forward(self, slots, packets: Tensor, nbytes, levels=None, reports=None, nacks=None) -> Tuple[Tensor, Tensor]:
         """one hop: this hop's arrivals, in push order — `slots` and `nbytes` (A host ints), `packets` uint8 `[A,
         wire.transport_bytes(n, m, frames)]` (host or device), 0 <= A <= max_arrivals.  Returns (out uint8 `[B, fanout, burst, tb]`,
         out_nbytes int32 `[B, fanout, burst]`): row (b, j, k) is the k-th packet of this hop for listener b's route j, cut to its layers
         (0 bytes: none); static views that the next-but-one call overwrites.
         `reports` (downlink with rate only) / `nacks` (downlink with history only): (listeners, routes, blobs), this hop's feedback — A
         host ints twice, and a uint8 `[A, 3]` / `[A, 4]` host tensor or a sequence of `bytes` (wire.pack_report / wire.pack_nack); a
-        (listener, route) pair named twice keeps its last blob.  With `downlink` the rows returned are cut to `eff_layers`."""
+        (listener, route) pair named twice keeps its last blob.  With `downlink` the rows returned are cut to `eff_layers`.
+        `levels` (speakers only: ValueError without): A host ints, each arrival's audio level as its sender measured it — 0..127, or -1
+        for unknown, which counts as the floor level (anything else: ValueError); None: every arrival is unknown."""
+        if levels is not None and self.speakers is None:
+            raise ValueError("GraphedForwardHop.forward(levels=...): construct with speakers=SpeakerConfig(...)")
+        if isinstance(levels, Tensor) and levels.is_cuda:
+            raise ValueError("forward: levels must be host ints, not a device tensor")
         fb = self._feedback(reports, nacks)
         arr = check_arrivals("forward", slots, packets, nbytes, self.batch, self.max_arrivals, self.tstride)
+        loud = None if self.speakers is None else level_def.loud_row(self.batch, arr.slots, levels, self.speakers)
         st = self.stage
         st.wait()
         if st.one_hop_live or self._joined:   # the join row: 1 for the slots joined since the last hop
@@ -1843,6 +1903,9 @@ class GraphedForwardHop(_GraphPair):
             for name in self._fb_names:
                 self._h_fb[name].zero_() if fb is None else self._h_fb[name].copy_(torch.from_numpy(fb[name]))
             self._fb_live = fb is not None
+        if loud is not None:                  # the loudness row, likewise: the slots with an arrival on this hop, 0 elsewhere
+            heard = np.flatnonzero(loud)
+            st.put_one_hop("loud", heard, loud[heard])
         st.send_arrivals(arr, packets)
         st.finish()
         return self._replay()

@@ -24,6 +24,7 @@ import torch
 from torch import Tensor
 
 from ._lib import DownParams, PostParams, ResblockParams, Spec0Params, UpParams, check, lib
+from .audio_level import SP_WORDS
 from .downlink import DL_WORDS, DS_WORDS
 from .downlink import bucket as downlink_bucket
 from .dtx import LEVELS, state_words
@@ -1403,6 +1404,39 @@ _register("downlink_step", "(Tensor routes, Tensor new_routes, Tensor packets, T
           out, out_nbytes, rtx_out, rtx_nbytes, rtx_routes, n, m, frames, keep_fec, rate_on, min_bits, max_bits, start_bits, high_q8, low_q8,
           increase_q8, burst_hops, timeout_hops: None)
 
+# ======================================================================================================
+# audio level and level-based speaker selection (graph_step.GraphedEncodeHop(audio_level=True), GraphedForwardHop(speakers=);
+# definition: hilcodec_amd/audio_level.py; semantics: include/hilcodec_amd.h)
+# ======================================================================================================
+def _audio_level(x, thr, hold, level):
+    B = level.numel()
+    if x.dim() not in (2, 3) or x.shape[0] != B or x.numel() == 0 or thr.shape != (LEVELS - 1,):
+        raise RuntimeError(f"audio_level: x must be fp32 [{B}, 1, L] or [{B}, L] and thr float64 [{LEVELS - 1}]")
+    _rows("audio_level", B, hold=hold)
+    check(lib.hilc_audio_level(_ptr(x), _ptr(thr, torch.float64), _ptr(hold, torch.int32), _ptr(level, torch.int32), B, x.numel() // B,
+                               _stream()), "hilc_audio_level")
+
+
+_register("audio_level", "(Tensor x, Tensor thr, Tensor? hold, Tensor(a!) level) -> ()", _audio_level, lambda x, thr, hold, level: None)
+
+
+def _forward_rank(sender_rows, loud, room, action, shadow_prev, shadow, rows, fanout, hang_hops, floor_level, attack_shift, decay_q8,
+                  margin_db):
+    B = room.numel()
+    if sender_rows.shape != (B, SD_WORDS) or shadow_prev.shape != (B, SD_WORDS) or shadow.shape != (B, SD_WORDS) or \
+            rows.shape != (B, SP_WORDS):
+        raise RuntimeError(f"forward_rank: sender_rows, shadow_prev and shadow must be [{B}, {SD_WORDS}] and rows [{B}, {SP_WORDS}]")
+    _rows("forward_rank", B, loud=loud, action=action)
+    check(lib.hilc_forward_rank(_ptr(sender_rows, torch.int32), _ptr(loud, torch.int32), _ptr(room, torch.int32), _ptr(action, torch.int32),
+                                _ptr(shadow_prev, torch.int32), _ptr(shadow, torch.int32), _ptr(rows, torch.int32), B, fanout, hang_hops,
+                                floor_level, attack_shift, decay_q8, margin_db, _stream()), "hilc_forward_rank")
+
+
+_register("forward_rank", "(Tensor sender_rows, Tensor loud, Tensor room, Tensor? action, Tensor shadow_prev, Tensor(a!) shadow, "
+          "Tensor(b!) rows, int fanout, int hang_hops, int floor_level, int attack_shift, int decay_q8, int margin_db) -> ()", _forward_rank,
+          lambda sender_rows, loud, room, action, shadow_prev, shadow, rows, fanout, hang_hops, floor_level, attack_shift, decay_q8,
+          margin_db: None)
+
 _OPS = torch.ops.hilcodec
 
 
@@ -2206,3 +2240,25 @@ def downlink_step(routes: Tensor, new_routes: Tensor, packets: Tensor, nbytes: T
                        eff_layers, out, out_nbytes, rtx_out, rtx_nbytes, rtx_routes, int(n), int(m), int(frames), bool(fcfg.keep_fec),
                        r is not None, bits.min_bits, bits.max_bits, bits.start_bits, *((int(r.high_q8), int(r.low_q8), int(r.increase_q8),
                        int(r.burst_hops), int(r.timeout_hops)) if r is not None else (0, 0, 0, 1, 0)))
+
+
+def audio_level(x: Tensor, thr: Tensor, level: Optional[Tensor] = None, hold: Optional[Tensor] = None) -> Tensor:
+    """The sender's level launch (audio_level.hop_level): `x` (fp32 `[B, 1, L]` or `[B, L]`, the 24 kHz hop the encoder reads) -> `level`
+    (int32 `[B]`, written in place when given, else new): each row's -dBov in 1 dB steps, 0..127.  `thr`: dtx.level_table() on the device
+    (float64 `[127]`); `hold` (int32 `[B]`, optional): a non-zero entry gives 127 and its row is not read."""
+    if level is None:
+        level = _new(x, x.shape[0], dtype=torch.int32)
+    _OPS.audio_level(x, thr, hold, level)
+    return level
+
+
+def forward_rank(sender_rows: Tensor, loud: Tensor, room: Tensor, shadow_prev: Tensor, shadow: Tensor, rows: Tensor, cfg, speakers,
+                 action: Optional[Tensor] = None) -> None:
+    """The forwarding hop's launch between forward_classify and forward_route (audio_level.RankModel): with `sender_rows` (int32 `[B,
+    forward.SD_WORDS]`) as forward_classify left them on this hop, the one-hop row `loud` (int32 `[B]`: 128 - level, 0: none;
+    audio_level.loud_row), `room` (int32 `[B]`) and `shadow_prev`, the shadow rows of the previous hop -> this hop's `shadow` rows (int32
+    `[B, forward.SD_WORDS]`, another tensor than `shadow_prev`: forward_route takes them as its sender_rows) and the speaker rows (`rows`,
+    int32 `[B, audio_level.SP_WORDS]`, in place).  `cfg`: the forward.ForwardConfig, `speakers`: the audio_level.SpeakerConfig; `action`
+    (int32 `[B]`, optional): non-zero clears the slot's row."""
+    _OPS.forward_rank(sender_rows, loud, room, action, shadow_prev, shadow, rows, int(cfg.fanout), int(cfg.hang_hops),
+                      int(speakers.floor_level), int(speakers.attack_shift), int(speakers.decay_q8), int(speakers.margin_db))

@@ -37,7 +37,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream) with per-speaker levelling and a limiter int hilc_mix_gains(const float* wav, double* gains, double* power, const int* action, double gate2, double lo, double hi, double up, double down, double min_gain, double max_gain, double smooth, int B, int L, void* stream) and int hilc_mix_rooms_dyn(const float* wav, const int* room, const double* score, int top_k, const double* gains, double* limiter, double ceiling, double release, int sub, const int* action, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream); and the selective forwarding hop int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick, int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream) and int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers, const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec, void* stream); and its downlink control int hilc_downlink_store(const int* arrivals, int max_arrivals, const int* action, const int* pick, const int* pick_count, int* tags, int* ring, int* rows, int B, int T, int n_max, int m, int burst, int history, void* stream) and int hilc_downlink_step(const int* routes, const int* new_routes, const uint8_t* in, const int* in_nbytes, const int* layers, const int* action, const int* report, const int* nack_base, const int* nack_bitmap, const int* tags, const int* ring, int* rows, int* memory, int* eff_layers, uint8_t* out, int* out_nbytes, uint8_t* rtx_out, int* rtx_nbytes, int* rtx_routes, int B, int T, int n_max, int m, int fanout, int burst, int keep_fec, int history, int per_hop, int rate_on, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream) with per-speaker levelling and a limiter int hilc_mix_gains(const float* wav, double* gains, double* power, const int* action, double gate2, double lo, double hi, double up, double down, double min_gain, double max_gain, double smooth, int B, int L, void* stream) and int hilc_mix_rooms_dyn(const float* wav, const int* room, const double* score, int top_k, const double* gains, double* limiter, double ceiling, double release, int sub, const int* action, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream); and the selective forwarding hop int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick, int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream) and int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers, const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec, void* stream); and its downlink control int hilc_downlink_store(const int* arrivals, int max_arrivals, const int* action, const int* pick, const int* pick_count, int* tags, int* ring, int* rows, int B, int T, int n_max, int m, int burst, int history, void* stream) and int hilc_downlink_step(const int* routes, const int* new_routes, const uint8_t* in, const int* in_nbytes, const int* layers, const int* action, const int* report, const int* nack_base, const int* nack_bitmap, const int* tags, const int* ring, int* rows, int* memory, int* eff_layers, uint8_t* out, int* out_nbytes, uint8_t* rtx_out, int* rtx_nbytes, int* rtx_routes, int B, int T, int n_max, int m, int fanout, int burst, int keep_fec, int history, int per_hop, int rate_on, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream); and the audio level with level-based speaker selection int hilc_audio_level(const float* x, const double* thr, const int* hold, int* level, int B, int L, void* stream) and int hilc_forward_rank(const int* sd, const int* loud, const int* room, const int* action, const int* shadow_prev, int* shadow, int* rows, int B, int fanout, int hang_hops, int floor_level, int attack_shift, int decay_q8, int margin_db, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -629,6 +629,21 @@ int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const fl
 #define HILC_DOWNLINK_MAX_HISTORY 64
 #define HILC_DOWNLINK_MAX_PER_HOP 4
 
+/* audio level and level-based speaker selection of the forwarding hop (hilcodec_amd/audio_level.py).  Speaker row of a slot, WORDS
+ * words: SCORE (the smoothed loudness, 256 x (128 - level), in [0, 256 MAX_LOUD]), RANK (its place in its room on the previous hop's
+ * keys, -1: none), STAGE (1: among the first `fanout`), then the counters LEVELLED (codes hops that came with a level) and STAGED.  A
+ * loudness is 128 - level in [1, MAX_LOUD], 0: no level on this hop. */
+#define HILC_SPEAKER_SCORE 0
+#define HILC_SPEAKER_RANK 1
+#define HILC_SPEAKER_STAGE 2
+#define HILC_SPEAKER_LEVELLED 3
+#define HILC_SPEAKER_STAGED 4
+#define HILC_SPEAKER_WORDS 5
+#define HILC_SPEAKER_MAX_LOUD 128
+#define HILC_SPEAKER_MAX_ATTACK_SHIFT 4
+#define HILC_SPEAKER_MAX_DECAY_Q8 32768
+#define HILC_SPEAKER_MAX_MARGIN_DB 32
+
 /* ---- per-stream session state of a streaming hop (ABI 16) ------------------------------------------------------------------
  * Layout: the caches of `streams` streams live in ONE fp32 block (hilcodec_amd/graph_step.py StateBlock): slice k (one
  * `[streams][C][L]` cache tensor, k < nslices, in the reference's order: 22 encoder then 30 decoder caches) starts at
@@ -1043,6 +1058,35 @@ int hilc_downlink_step(const int* routes, const int* new_routes, const uint8_t* 
                        int* rtx_nbytes, int* rtx_routes, int B, int T, int n_max, int m, int fanout, int burst, int keep_fec, int history,
                        int per_hop, int rate_on, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8,
                        int burst_hops, int timeout_hops, void* stream);
+
+/* ---- audio level and level-based speaker selection (additive under ABI 16) ----------------------------------------------------------
+ * Two entry points added WITHOUT a version bump, as the entry points above.  The definition, bit for bit, is hilcodec_amd/audio_level.py.
+ * hilc_audio_level: the sender's level launch.  x fp32 [B][L] (the 24 kHz hop the encoder reads); thr float64 [HILC_DTX_LEVELS - 1]
+ * (dtx.level_table); hold optional int32 [B]; level int32 [B] (every element written).  Per slot: hold[b] != 0 gives HILC_DTX_LEVELS - 1
+ * and the row is not read; else E is the energy of hilc_mix_levels (lane l sums the squares of the samples i = l mod 64 in ascending i
+ * in float64, the 64 partials are added in lane order, every product and sum rounded on its own), m = E / (double)L, and level[b] = #{j
+ * < HILC_DTX_LEVELS - 1 : m < thr[j]}: -dBov in 1 dB steps, 127 for silence, 0 for a full-scale square.  B, L >= 1 (else
+ * HILC_ERR_SHAPE).
+ * hilc_forward_rank: the forwarding hop's launch between hilc_forward_classify and hilc_forward_route.  sd int32
+ * [B][HILC_FORWARD_SD_WORDS] as the first launch left it (read only); loud int32 [B] (0: no level on this hop, else 128 - level; clamped
+ * to [0, HILC_SPEAKER_MAX_LOUD]); room int32 [B]; action optional int32 [B]; shadow_prev int32 [B][HILC_FORWARD_SD_WORDS], the rows this
+ * launch wrote on the previous hop (read only; another buffer than shadow); shadow int32 [B][HILC_FORWARD_SD_WORDS] (every element
+ * written); rows int32 [B][HILC_SPEAKER_WORDS] (in place).  Per slot b: action[b] != 0 clears its row and counts its previous shadow row
+ * as zero; talk = SD_HANG == hang_hops + 1; target = 256 loud[b] when talk, else 0 (LEVELLED += 1 when talk and loud[b] > 0); SCORE (read
+ * clamped to [0, 256 HILC_SPEAKER_MAX_LOUD]) += (target - SCORE + 2^attack_shift - 1) >> attack_shift when target > SCORE, else SCORE =
+ * max(target, SCORE - decay_q8); RANK = -1 unless room[b] >= 0, action[b] == 0 and b's previous shadow SD_HANG > 0, else the number of
+ * slots s != b with room[s] == room[b], action[s] == 0 and a previous shadow SD_HANG > 0 that are ahead of b in hilc_forward_route's order
+ * of the previous shadow rows (SD_HANG descending, SD_SINCE descending, slot ascending, with that launch's clamps); STAGE = 0 <= RANK <
+ * fanout (STAGED += STAGE); candidate = SD_HANG > 0 and SCORE >= 256 (HILC_SPEAKER_MAX_LOUD - floor_level); key = ((SCORE + (STAGE ? 256
+ * margin_db : 0)) << 8) | min(max(SD_SINCE, 0), 255) < 2^24; shadow[b] = sd[b] but SD_HANG = candidate ? 1 + (key >> 16) : 0 and SD_SINCE
+ * = candidate ? key & 0xFFFF : 0.  hilc_forward_route handed `shadow` as its sender_rows then selects by key.  B >= 1 (else
+ * HILC_ERR_SHAPE); shadow must be neither shadow_prev nor sd (else HILC_ERR_UNSUPPORTED); 1 <= fanout <= HILC_FORWARD_MAX_FANOUT, 0 <=
+ * hang_hops <= HILC_FORWARD_MAX_HANG_HOPS, 0 <= floor_level < HILC_SPEAKER_MAX_LOUD, 0 <= attack_shift <= HILC_SPEAKER_MAX_ATTACK_SHIFT, 1
+ * <= decay_q8 <= HILC_SPEAKER_MAX_DECAY_Q8, 0 <= margin_db <= HILC_SPEAKER_MAX_MARGIN_DB (else HILC_ERR_RANGE).
+ * Both: NULL pointers (hold, action excepted): HILC_ERR_NULL.  One wave per slot, no LDS, no atomics. */
+int hilc_audio_level(const float* x, const double* thr, const int* hold, int* level, int B, int L, void* stream);
+int hilc_forward_rank(const int* sd, const int* loud, const int* room, const int* action, const int* shadow_prev, int* shadow, int* rows,
+                      int B, int fanout, int hang_hops, int floor_level, int attack_shift, int decay_q8, int margin_db, void* stream);
 
 #ifdef __cplusplus
 }
