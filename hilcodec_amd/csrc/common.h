@@ -100,3 +100,11 @@ struct SpecFinish {
 };
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Host-side pointer test of the entry points ("Pointer alignment"): true if any of the (possibly NULL) operands is
+// not 16-byte aligned.  An operand that some kernel reads or writes as f32x4 / f32x2 either switches the launch to a scalar path
+// or is refused with HILC_ERR_UNSUPPORTED in front of the entry's first launch — never dereferenced as a vector.
+template <class... P>
+static inline bool misaligned16(const P*... p) {
+  return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) != 0;
+}

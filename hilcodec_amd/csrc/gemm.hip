@@ -256,7 +256,7 @@ extern "C" int hilc_pw_conv(const float* x, const float* wt, const float* bias, 
                             void* stream) {
   if (!x || !wt || !y) return HILC_ERR_NULL;
   if (B <= 0 || K <= 0 || M <= 0 || T <= 0) return HILC_ERR_SHAPE;
-  if (M % 4 != 0) return HILC_ERR_UNSUPPORTED;  // weight rows are read as float4
+  if (M % 4 != 0 || misaligned16(wt)) return HILC_ERR_UNSUPPORTED;  // weight rows are read as float4 (gemm_core.h, gemm_lin.h: no scalar form)
   if (T == 1 && B <= 65535L * 32) {             // single-frame layers of a streaming hop: latency-bound, own kernel
     Frame1Args f{};
     f.x = x; f.wt = wt; f.bias = bias; f.res = res; f.y = y; f.B = B; f.K = K; f.M = M;
@@ -319,6 +319,7 @@ static int up_conv_entry(const float* x, const float* hist, float* hist_out, con
   if (!x || !tr_w || !wt || !y) return HILC_ERR_NULL;
   if (B <= 0 || K <= 0 || M <= 0 || Tin <= 0 || stride <= 0) return HILC_ERR_SHAPE;
   if (M % 4 != 0 || ((long)Tin * stride) % 4 != 0) return HILC_ERR_UNSUPPORTED;
+  if (misaligned16(wt)) return HILC_ERR_UNSUPPORTED;   // float4 weight rows; in front of the up_hist_kernel launch: a refusal writes nothing
   const long Tout = (long)Tin * stride;
   if (Tout > 0x7fffffffL) return HILC_ERR_SHAPE;
   const long ncols = (long)B * Tout;
@@ -386,7 +387,7 @@ extern "C" int hilc_dws_conv(const float* x, const float* wt, const float* dw_w,
                              float in_scale, int in_elu, float out_scale, int out_elu, void* stream) {
   if (!x || !wt || !dw_w || !y) return HILC_ERR_NULL;
   if (B <= 0 || K <= 0 || M <= 0 || T <= 0) return HILC_ERR_SHAPE;
-  if (M % 4 != 0) return HILC_ERR_UNSUPPORTED;
+  if (M % 4 != 0 || misaligned16(wt)) return HILC_ERR_UNSUPPORTED;
   const bool aligned = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   PwTileLoader ld;
   ld.x = x; ld.K = K; ld.T = T; ld.in_scale = in_scale; ld.in_elu = in_elu;
@@ -485,6 +486,7 @@ extern "C" int hilc_dws_conv_stream(const float* x, const float* wt, const float
   if (!x || !wt || !dw_w || !y) return HILC_ERR_NULL;
   if (B <= 0 || K <= 0 || M <= 0 || T <= 0 || ksize <= 0 || stride <= 0) return HILC_ERR_SHAPE;
   if (M % 4 != 0 || T % stride != 0 || ksize < stride || ksize > 32) return HILC_ERR_UNSUPPORTED;
+  if (misaligned16(wt)) return HILC_ERR_UNSUPPORTED;
   if (hist != nullptr && hist == hist_out) return HILC_ERR_UNSUPPORTED;
   const int pad = ksize - stride;
   if (pad == 0 && (hist != nullptr || hist_out != nullptr)) return HILC_ERR_SHAPE;
@@ -555,6 +557,8 @@ extern "C" int hilc_dws_conv_stream(const float* x, const float* wt, const float
     if (lin) return launch_gemm_lin(wt, x, M, K, M, T, ntiles, in_scale, in_elu != 0, cols, ep, (hipStream_t)stream);
     return launch_gemm(wt, M, K, M, ntiles, true, ld, ep, (hipStream_t)stream);
   }
+  // DwSegEpilogue reads the taps of the codec's two down-sampling shapes as f32x4 (k = 16) / f32x2 (k = 10) words per row
+  if (((ksize == 16 && stride == 8) || (ksize == 10 && stride == 5)) && misaligned16(dw_w)) return HILC_ERR_UNSUPPORTED;
   DwSegEpilogue ep;
   ep.y = y; ep.dw_w = dw_w; ep.dw_b = dw_b; ep.res = res; ep.hist = hist; ep.hist_out = hist_out; ep.B = B; ep.M = M;
   ep.T = T; ep.To = T / stride; ep.k = ksize; ep.stride = stride; ep.pad = pad; ep.cpt = cpt;
@@ -571,6 +575,7 @@ extern "C" int hilc_stft_logmag(const float* wav, const float* hist, int hist_le
   if (!wav || !basis_t || !spec) return HILC_ERR_NULL;
   if (B <= 0 || T <= 0 || n_fft < 2 || (n_fft & 1) || hop <= 0) return HILC_ERR_SHAPE;
   if (hist != nullptr && hist_len < n_fft - 1) return HILC_ERR_SHAPE;
+  if (misaligned16(basis_t)) return HILC_ERR_UNSUPPORTED;   // the A operand of the GEMM: float4 rows
   int Tf = (T - 1) / hop + 1;
   int M = n_fft + 2;
   int m_pad = ((M + 31) / 32) * 32;

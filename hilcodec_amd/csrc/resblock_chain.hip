@@ -55,10 +55,13 @@ extern "C" int hilc_resblock_chain_row_classes(int C) {
 }
 
 namespace {
-int fill_blocks(ResArgs& a, const hilc_resblock_params* blocks, int nblk) {
+int fill_blocks(ResArgs& a, const hilc_resblock_params* blocks, int nblk, int streaming) {
   for (int i = 0; i < nblk; ++i) {
     const hilc_resblock_params& p = blocks[i];
     if (!p.w1t || !p.dw1_w || !p.dw1_b || !p.w2t || !p.dw2_w || !p.dw2_b) return HILC_ERR_NULL;
+    // packed weights: 16-B words per lane (resblock_gemm.h: load_word); caches: one f32x4 per row (resblock_kernel.h)
+    if (misaligned16(p.w1t, p.w2t)) return HILC_ERR_UNSUPPORTED;
+    if (streaming && misaligned16(p.hist1, p.hist2, p.hist1_out, p.hist2_out)) return HILC_ERR_UNSUPPORTED;
     if ((p.hist1 && p.hist1 == p.hist1_out) || (p.hist2 && p.hist2 == p.hist2_out)) return HILC_ERR_UNSUPPORTED;
     ResBlk& b = a.blk[i];
     b.w1t = p.w1t; b.dw1_w = p.dw1_w; b.dw1_b = p.dw1_b; b.w2t = p.w2t; b.dw2_w = p.dw2_w; b.dw2_b = p.dw2_b;
@@ -82,7 +85,7 @@ extern "C" int hilc_resblock_chain(const float* x, float* y, const hilc_resblock
   a.dn = ResDown{};
   a.up = ResUp{};
   a.post = ResPost{};
-  if (const int rc = fill_blocks(a, blocks, nblk)) return rc;
+  if (const int rc = fill_blocks(a, blocks, nblk, streaming)) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (!streaming) {        // offline: the carry form's contiguous runs (hilc_resblock), the blocks of the stage back to back per tile
     switch (C) {
@@ -130,12 +133,15 @@ extern "C" int hilc_encoder_stage(const float* x, const hilc_resblock_params* bl
       (reinterpret_cast<uintptr_t>(down->res) & 15) || (reinterpret_cast<uintptr_t>(down->hist) & 15) ||
       (reinterpret_cast<uintptr_t>(down->hist_out) & 15))
     return HILC_ERR_UNSUPPORTED;
+  // packed 16-B words; the wide stages (C = 256 / 512) read a row's 2r taps as f32x2 (r = 5) / f32x4 (r = 8) words, the narrow ones
+  // stage them word by word
+  if (misaligned16(down->w_lo, down->w_hi) || (C >= 256 && misaligned16(down->dw_w))) return HILC_ERR_UNSUPPORTED;
   if (down->hist && down->hist == down->hist_out) return HILC_ERR_UNSUPPORTED;
   if (down->res == down->y) return HILC_ERR_UNSUPPORTED;
   if (streaming && (long)B * 2 * C * T * 4 >= (1L << 32)) return HILC_ERR_UNSUPPORTED;
   ResArgs a{};
   a.x = x; a.y = down->y; a.T = T; a.tiles = 0; a.nblk = nblk; a.sched = nullptr; a.dbg = HILC_CHAIN_DBG;
-  if (const int rc = fill_blocks(a, blocks, nblk)) return rc;
+  if (const int rc = fill_blocks(a, blocks, nblk, streaming)) return rc;
   a.up = ResUp{};
   a.post = ResPost{};
   ResDown& d = a.dn;
@@ -176,6 +182,8 @@ extern "C" int hilc_encoder_stage0(const hilc_spec0_params* spec, const hilc_res
   if (B <= 0 || T <= 0) return HILC_ERR_SHAPE;
   if (!hilc_encoder_stage0_supported(T, nblk, down->stride, spec->n_fft, spec->hop, spec->pre_ksize, streaming)) return HILC_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(down->y) & 15) || (reinterpret_cast<uintptr_t>(down->res) & 15) || down->res == down->y) return HILC_ERR_UNSUPPORTED;
+  // the packed tables stream as 16-B words per lane; spec->wav / spec->hist are staged sample by sample (any float alignment)
+  if (misaligned16(down->w_lo, down->w_hi, spec->dft_packed, spec->pw_packed)) return HILC_ERR_UNSUPPORTED;
   if (streaming) {
     if ((reinterpret_cast<uintptr_t>(down->hist) & 15) || (reinterpret_cast<uintptr_t>(down->hist_out) & 15)) return HILC_ERR_UNSUPPORTED;
     if (down->hist && down->hist == down->hist_out) return HILC_ERR_UNSUPPORTED;
@@ -184,7 +192,7 @@ extern "C" int hilc_encoder_stage0(const hilc_spec0_params* spec, const hilc_res
   }
   ResArgs a{};
   a.x = spec->wav; a.y = down->y; a.T = T; a.tiles = 0; a.nblk = nblk; a.sched = nullptr; a.dbg = HILC_CHAIN_DBG;
-  if (const int rc = fill_blocks(a, blocks, nblk)) return rc;
+  if (const int rc = fill_blocks(a, blocks, nblk, streaming)) return rc;
   a.up = ResUp{};
   a.post = ResPost{};
   ResDown& d = a.dn;
@@ -255,12 +263,14 @@ int decoder_stage_entry(const hilc_up_params* up, const hilc_resblock_params* bl
   if (B <= 0 || C <= 0 || T <= 0) return HILC_ERR_SHAPE;
   if (!hilc_decoder_stage_supported(C, T, nblk, up->stride, streaming)) return HILC_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(y) & 15) || (reinterpret_cast<uintptr_t>(up->tr_w) & 15)) return HILC_ERR_UNSUPPORTED;
+  // packed 16-B words; up->x / up->hist / up->hist_out are read and written sample by sample (any float alignment)
+  if (misaligned16(up->w_lo, up->w_hi)) return HILC_ERR_UNSUPPORTED;
   if (up->hist && up->hist == up->hist_out) return HILC_ERR_UNSUPPORTED;
   if (streaming && (long)B * C * T * 4 >= (1L << 32)) return HILC_ERR_UNSUPPORTED;
   ResArgs a{};
   a.x = up->x; a.y = y; a.T = T; a.tiles = 0; a.nblk = nblk; a.sched = nullptr; a.dbg = HILC_CHAIN_DBG;
   a.dn = ResDown{};
-  if (const int rc = fill_blocks(a, blocks, nblk)) return rc;
+  if (const int rc = fill_blocks(a, blocks, nblk, streaming)) return rc;
   ResUp& u = a.up;
   u.xin = up->x; u.tr_w = up->tr_w; u.w_lo = up->w_lo; u.w_hi = up->w_hi; u.bias = up->bias; u.hist = up->hist;
   u.hist_out = streaming ? up->hist_out : nullptr; u.in_scale = up->in_scale;

@@ -516,7 +516,8 @@ extern "C" int hilc_rvq_encode_mixed(const float* z, const float* codebooks, con
   // forms, hence offline and streaming indices, identical; tests/test_gpu_rvq.py pins that on every box it runs on, and runs
   // this branch too.  (An argument, not an environment variable: the library keeps no process-global switches.)
   const bool valu_only = (flags & HILC_RVQ_VALU_ONLY) != 0;
-  if (nframes >= 32 * 256 && !valu_only)
+  // (the matrix-pipe form reads codebooks_t and norms as 16-B words: a 4-byte-aligned view of either keeps the VALU form, same indices)
+  if (nframes >= 32 * 256 && !valu_only && !misaligned16(codebooks_t, norms))
     hipLaunchKernelGGL((rvq_encode_mfma_kernel<128>), dim3((unsigned)((nframes + 31) / 32)), dim3(256), 0, (hipStream_t)stream, a);
   else if (nframes <= 16 * 512)
     hipLaunchKernelGGL((rvq_encode_kernel<128, 4, 512>), dim3((unsigned)((nframes + 3) / 4)), dim3(512), 0, (hipStream_t)stream, a);

@@ -366,6 +366,7 @@ extern "C" int hilc_spec_block(const float* wav, const float* hist, int hist_len
   if (hist != nullptr && hist_len < n_fft - 1) return HILC_ERR_SHAPE;
   if (!hilc_spec_block_supported(n_fft, hop, n_fft, T)) return HILC_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 15)) return HILC_ERR_UNSUPPORTED;
+  if (misaligned16(dft_packed, pw_packed)) return HILC_ERR_UNSUPPORTED;      // streamed as 16-B words per lane (stream_gemm.h)
   SpecArgs a;
   a.wav = wav; a.hist = hist; a.hist_len = hist_len;
   a.dft = dft_packed; a.nyq = nyq_sin; a.pw = pw_packed; a.bias = bias; a.x = x; a.y = y;
@@ -388,6 +389,7 @@ extern "C" int hilc_spec_block_conv_pre(const float* wav, const float* hist, int
   if (hist != nullptr && hist_len < n_fft - 1) return HILC_ERR_SHAPE;
   if (n_fft != 64 || hop != 1 || pre_ksize != 5 || !hilc_spec_block_supported(n_fft, hop, n_fft, T)) return HILC_ERR_UNSUPPORTED;
   if (reinterpret_cast<uintptr_t>(y) & 15) return HILC_ERR_UNSUPPORTED;
+  if (misaligned16(dft_packed, pw_packed)) return HILC_ERR_UNSUPPORTED;      // streamed as 16-B words per lane (stream_gemm.h)
   SpecArgs a;
   a.wav = wav; a.hist = hist; a.hist_len = hist_len;
   a.dft = dft_packed; a.nyq = nyq_sin; a.pw = pw_packed; a.bias = bias; a.x = nullptr; a.y = y;

@@ -51,6 +51,24 @@ def _ptr(t: Optional[Tensor], dtype=torch.float32) -> Optional[int]:
     return t.data_ptr()
 
 
+def _al16(t: Optional[Tensor]) -> Optional[Tensor]:
+    """An input operand the library refuses unless it is 16-byte aligned ("Pointer alignment", class R): a contiguous
+    tensor may start at any float of its storage (`rec[:, :, k:k + T]` with B = 1, a cache kept as a view), so such a view is
+    copied to a fresh allocation first.  The aligned tensor is returned as it is: no allocation, no launch.  The caller keeps the
+    result in a local until the launch is enqueued."""
+    return t if t is None or t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _al16_out(op: str, **outs: Optional[Tensor]) -> None:
+    """Caller-owned outputs of the same class cannot be copied: a misaligned one is an error that names the operand."""
+    for name, t in outs.items():
+        for i, u in enumerate(t if isinstance(t, (list, tuple)) else [t]):
+            if u is not None and u.data_ptr() % 16 != 0:
+                which = f"{name}[{i}]" if isinstance(t, (list, tuple)) else name
+                raise RuntimeError(f"{op}: `{which}` must be 16-byte aligned (data_ptr() % 16 == {u.data_ptr() % 16}): the kernel writes "
+                                   "it as 16-byte words and the caller owns it, so it cannot be copied")
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -130,6 +148,7 @@ def _pw_conv(x, wt, bias, res, in_scale, in_elu, out_scale):
     M = wt.shape[1]
     if wt.shape[0] != K:
         raise RuntimeError(f"pw_conv: weight rows {wt.shape[0]} != input channels {K}")
+    wt = _al16(wt)
     y = _new(x, B, M, T)
     with _timed("pw_conv", 2.0 * B * T * K * M, f"K{K} M{M} T{T}"):
         check(lib.hilc_pw_conv(_ptr(x), _ptr(wt), _ptr(bias), _ptr(res), _ptr(y), B, K, M, T,
@@ -146,6 +165,7 @@ def _dws_conv(x, wt, dw_w, dw_b, res, stride, in_scale, in_elu, out_scale, out_e
     B, K, T = x.shape
     M, k = wt.shape[1], dw_w.shape[1]
     To = (T + stride - 1) // stride
+    wt = _al16(wt)
     y = _new(x, B, M, To)
     with _timed("dws_conv", 2.0 * B * T * K * M, f"K{K} M{M} T{T} k{k} s{stride}"):
         check(lib.hilc_dws_conv(_ptr(x), _ptr(wt), _ptr(dw_w), _ptr(dw_b), _ptr(res), _ptr(y), B, K, M, T, k,
@@ -166,6 +186,11 @@ def _dws_conv_stream(x, wt, dw_w, dw_b, hist, hist_out, res, stride, in_scale, i
     for h in (hist, hist_out):
         if h is not None and tuple(h.shape) != (B, M, pad):
             raise RuntimeError(f"cache must be [{B},{M},{pad}], got {tuple(h.shape)}")
+    wt = _al16(wt)
+    if T > 128:                      # hops longer than one tile have no scalar loader
+        x = _al16(x)
+    elif (k, stride) in ((16, 8), (10, 5)):      # the two shapes whose taps are read as 16- / 8-byte words per row
+        dw_w = _al16(dw_w)
     y = _new(x, B, M, T // stride)
     with _timed("dws_conv", 2.0 * B * T * K * M, f"K{K} M{M} T{T} k{k} s{stride} stream"):
         check(lib.hilc_dws_conv_stream(_ptr(x), _ptr(wt), _ptr(dw_w), _ptr(dw_b), _ptr(hist), _ptr(hist_out),
@@ -198,6 +223,7 @@ def _up_conv(x, hist, hist_out, tr_w, taps, wt, bias, stride, in_scale, in_elu):
     for h in (hist, hist_out):
         if h is not None and h.numel() != B * K:
             raise RuntimeError(f"cache must be [{B},{K},1], got {tuple(h.shape)}")
+    wt = _al16(wt)
     y = _new(x, B, M, Tin * stride)
     with _timed("up_conv", 2.0 * B * Tin * stride * K * M,
                 f"K{K} M{M} Tin{Tin} r{stride}" + (" stream" if hist is not None or hist_out is not None else "")):
@@ -284,6 +310,8 @@ def _resblock(x, w1p, dw1_w, dw1_b, w2p, dw2_w, dw2_b, hist1, hist2, hist1_out, 
     for h in (hist1, hist2, hist1_out, hist2_out):
         if h is not None and tuple(h.shape) != (B, Cc, 4):
             raise RuntimeError(f"resblock caches must be [{B},{Cc},4], got {tuple(h.shape)}")
+    x, w1p, w2p, hist1, hist2 = _al16(x), _al16(w1p), _al16(w2p), _al16(hist1), _al16(hist2)
+    _al16_out("resblock", hist1_out=hist1_out, hist2_out=hist2_out)
     y = torch.empty_like(x)
     with _timed("resblock", 4.0 * B * T * Cc * Cc, f"C{Cc} T{T}" + (" stream" if streaming else "")):
         check(lib.hilc_resblock_balanced(_ptr(x), _ptr(w1p), _ptr(dw1_w), _ptr(dw1_b), _ptr(w2p), _ptr(dw2_w),
@@ -303,6 +331,13 @@ _register("resblock", "(Tensor x, Tensor w1p, Tensor dw1_w, Tensor dw1_b, Tensor
 def _void(obj):
     """a ctypes struct, or an array of them, as a `const void *` argument of the C ABI"""
     return ctypes.cast(ctypes.pointer(obj), ctypes.c_void_p)
+
+
+def _al16_blocks(op, params, hist_in, hist_out):
+    """The blocks' operands a stage launch refuses unless 16-byte aligned: the two packed matrices of each block (parameters 0 and 3
+    of every 6) and the caches.  Inputs are copied where they are not (`_al16`), caches the caller owns as outputs raise."""
+    _al16_out(op, hist_out=list(hist_out))
+    return [_al16(t) if i % 3 == 0 else t for i, t in enumerate(params)], [_al16(h) for h in hist_in]
 
 
 def _block_params(op, B, Cc, streaming, params, hist_in, hist_out, pre_scales, out_scales):
@@ -344,6 +379,8 @@ def _up_params(op, xin, tr_w, w_lo, w_hi, bias, uhist, uhist_out, in_scale, stri
 def _resblock_chain(x, params, hist_in, hist_out, pre_scales, out_scales):
     B, Cc, T = x.shape
     streaming = len(hist_in) > 0                   # no caches: the offline causal model (zero padding in front of every clip)
+    x = _al16(x)
+    params, hist_in = _al16_blocks("resblock_chain", params, hist_in, hist_out)
     blocks = _block_params("resblock_chain", B, Cc, streaming, params, hist_in, hist_out, pre_scales, out_scales)
     n = len(blocks)
     y = torch.empty_like(x)
@@ -363,6 +400,11 @@ def _encoder_stage(x, params, hist_in, hist_out, pre_scales, out_scales, w_lo, w
     streaming = dhist_out is not None
     if T % stride != 0:
         raise RuntimeError("encoder_stage: T must be a multiple of the stride")
+    x, w_lo, w_hi, dhist, dres = _al16(x), _al16(w_lo), _al16(w_hi), _al16(dhist), _al16(dres)
+    if Cc >= 256:                    # the wide stages read a row's taps as 16- / 8-byte words
+        ddw_w = _al16(ddw_w)
+    params, hist_in = _al16_blocks("encoder_stage", params, hist_in, hist_out)
+    _al16_out("encoder_stage", dhist_out=dhist_out)
     blocks = _block_params("encoder_stage", B, Cc, streaming, params, hist_in, hist_out, pre_scales, out_scales)
     n = len(blocks)
     y = torch.empty(B, 2 * Cc, T // stride, device=x.device, dtype=torch.float32)
@@ -384,6 +426,8 @@ def _decoder_stage(xin, tr_w, w_lo, w_hi, bias, uhist, uhist_out, in_scale, stri
     B, K2, Tin = xin.shape
     Cc, T = K2 // 2, Tin * stride
     streaming = len(hist_in) > 0 or uhist_out is not None        # no caches at all: the offline causal model
+    tr_w, w_lo, w_hi = _al16(tr_w), _al16(w_lo), _al16(w_hi)
+    params, hist_in = _al16_blocks("decoder_stage", params, hist_in, hist_out)
     blocks = _block_params("decoder_stage", B, Cc, streaming, params, hist_in, hist_out, pre_scales, out_scales)
     n = len(blocks)
     up = _up_params("decoder_stage", xin, tr_w, w_lo, w_hi, bias, uhist, uhist_out, in_scale, stride)
@@ -409,6 +453,9 @@ def _encoder_stage0(wav, wav_hist, dft_packed, nyq_sin, pw_packed, bias, pre_w, 
         raise RuntimeError("encoder_stage0: wav [B,1,T], a 64-channel first conv, T a multiple of the stride")
     if wav_hist is not None and (wav_hist.shape[0] != B or wav_hist.numel() // B < 63):
         raise RuntimeError(f"encoder_stage0: the waveform history must be [{B},1,>=63], got {tuple(wav_hist.shape)}")
+    dft_packed, pw_packed, w_lo, w_hi, dhist, dres = _al16(dft_packed), _al16(pw_packed), _al16(w_lo), _al16(w_hi), _al16(dhist), _al16(dres)
+    params, hist_in = _al16_blocks("encoder_stage0", params, hist_in, hist_out)
+    _al16_out("encoder_stage0", dhist_out=dhist_out)
     blocks = _block_params("encoder_stage0", B, Cc, streaming, params, hist_in, hist_out, pre_scales, out_scales)
     n = len(blocks)
     y = torch.empty(B, 2 * Cc, T // stride, device=wav.device, dtype=torch.float32)
@@ -442,6 +489,9 @@ def _decoder_stage_post(xin, tr_w, w_lo, w_hi, bias, uhist, uhist_out, in_scale,
     for h in (post_hist, post_hist_out):
         if h is not None and tuple(h.shape) != (B, Cc, post_w.shape[1] - 1):
             raise RuntimeError(f"decoder_stage_post: the closing conv's cache must be [{B},{Cc},{post_w.shape[1] - 1}], got {tuple(h.shape)}")
+    tr_w, w_lo, w_hi, post_hist = _al16(tr_w), _al16(w_lo), _al16(w_hi), _al16(post_hist)
+    params, hist_in = _al16_blocks("decoder_stage_post", params, hist_in, hist_out)
+    _al16_out("decoder_stage_post", post_hist_out=post_hist_out)
     blocks = _block_params("decoder_stage_post", B, Cc, streaming, params, hist_in, hist_out, pre_scales, out_scales)
     n = len(blocks)
     up = _up_params("decoder_stage_post", xin, tr_w, w_lo, w_hi, bias, uhist, uhist_out, in_scale, stride)
@@ -529,6 +579,9 @@ _register("conv_pre", "(Tensor wav, Tensor? hist, Tensor w, Tensor? bias, float 
 def _conv_post(x, hist, w, bias, hist_out, in_scale, in_elu, out_scale, do_tanh):
     B, Cc, T = x.shape
     k = w.shape[1]
+    # not refused, but the one fall-back that is not bit-identical: the generic kernel sums the channels in sequence, the 16-byte path
+    # in eight classes (include/hilcodec_amd.h).  The model's waveform must not depend on where a view starts: copy, keep the class order.
+    x, hist = _al16(x), _al16(hist)
     y = _new(x, B, 1, T)
     with _timed("conv_post", 4.0 * B * T * (1 + Cc)):
         check(lib.hilc_conv_post(_ptr(x), _ptr(hist), _ptr(w), _ptr(bias), _ptr(y), _ptr(hist_out), B, Cc, T, k,
@@ -544,6 +597,7 @@ _register("conv_post", "(Tensor x, Tensor? hist, Tensor w, Tensor? bias, Tensor(
 def _stft_logmag(wav, hist, basis_t, n_fft, hop, mean, std, normalize):
     B, one, T = wav.shape
     Tf = (T - 1) // hop + 1
+    basis_t = _al16(basis_t)
     spec = _new(wav, B, n_fft // 2 + 1, Tf)
     hl = hist.shape[-1] if hist is not None else 0
     with _timed("stft", 2.0 * B * Tf * n_fft * (n_fft + 2), f"N{n_fft} hop{hop}"):
@@ -574,6 +628,7 @@ def _spec_block(wav, hist, dft_packed, nyq_sin, pw_packed, bias, x, n_fft, hop, 
     Tf = (T - 1) // hop + 1
     if x is not None and tuple(x.shape) != (B, n_fft, Tf):
         raise RuntimeError(f"spec_block: x must be [{B},{n_fft},{Tf}], got {tuple(x.shape)}")
+    x, dft_packed, pw_packed = _al16(x), _al16(dft_packed), _al16(pw_packed)
     y = torch.empty(B, n_fft, Tf, device=wav.device, dtype=torch.float32)
     with _timed("spec_block", 2.0 * B * Tf * n_fft * (n_fft + 1 + n_fft // 2 + 1), f"N{n_fft} hop{hop}"):
         check(lib.hilc_spec_block(_ptr(wav), _ptr(hist), hl, _ptr(dft_packed), _ptr(nyq_sin), _ptr(pw_packed), _ptr(bias), _ptr(x), _ptr(y),
@@ -592,6 +647,7 @@ def _spec_block_conv_pre(wav, hist, dft_packed, nyq_sin, pw_packed, bias, pre_w,
     B, one, T = wav.shape
     hl = hist.shape[-1] if hist is not None else 0
     Cc, k = pre_w.shape
+    dft_packed, pw_packed = _al16(dft_packed), _al16(pw_packed)
     y = _new(wav, B, Cc, T)
     with _timed("spec_block", 2.0 * B * T * n_fft * (n_fft + 1 + n_fft // 2 + 1) + 2.0 * B * T * Cc * k,
                 f"N{n_fft} hop{hop} +conv_pre"):

@@ -16,6 +16,11 @@
  *  - "hist" arguments are the streaming caches of `models/hilcodec/causal_layers.py:147-188`
  *    (the samples *before* t = 0 of the layer's input); NULL means zero history, which is the
  *    causal zero padding of the offline model (`models/hilcodec/modules/conv.py:222-236`).
+ *  - alignment: a float operand needs the 4 bytes of a float unless its entry says otherwise.  Where an entry names operands that
+ *    "must be 16-byte aligned for the fast path", a 4-byte-aligned view of one switches the launch to a path that reads and writes
+ *    it word by word, with the same results bit for bit (the one exception is stated at hilc_conv_post); where it names operands
+ *    that are "refused", a pointer that is not 16-byte aligned returns HILC_ERR_UNSUPPORTED in front of the first launch.  The
+ *    table of every (entry, operand) pair is DESIGN.md, "Pointer alignment".
  *  - prologue  pro(v) = in_elu ? ELU(v * in_scale) : v * in_scale   (Scale + ELU modules,
  *    `models/hilcodec/modules/seanet.py:165-178`, torch.nn.ELU(alpha=1));
  *    it is applied to `x` only — histories hold already-activated samples, as the reference's
@@ -49,7 +54,8 @@ const char* hilc_last_hip_error(void);
  * Replaces: nn.Conv1d(k=1) inside SConv1d/NormConv1d (`models/hilcodec/modules/conv.py:115-134,
  * 202-236`) plus the ELU / Scale in front of it (`seanet.py:26-52,322-340`) and, with `res`, the
  * `x.add_(y.mul_(scale))` of SpecBlock (`seanet.py:241-246`).
- * wt is the folded weight TRANSPOSED to `[K][M]` (k-major).  bias, res may be NULL.  res may alias y. */
+ * wt is the folded weight TRANSPOSED to `[K][M]` (k-major).  bias, res may be NULL.  res may alias y.
+ * Alignment: x, y and res must be 16-byte aligned for the fast path; wt is refused unless it is; bias needs only the 4 bytes of a float. */
 int hilc_pw_conv(const float* x, const float* wt, const float* bias, const float* res, float* y,
                  int B, int K, int M, int T, float in_scale, int in_elu, float out_scale, void* stream);
 
@@ -59,7 +65,9 @@ int hilc_pw_conv(const float* x, const float* wt, const float* bias, const float
  * with h(t<0) = h(t>=T) = 0, pad = (ksize-1)-(stride-1), T_out = ceil(T/stride).  Supported: ksize 5 /
  * stride 1 (residual-block halves, `seanet.py:26-52,129-148`; decoder/encoder pre/post pairs) and
  * ksize = 2*stride (encoder down-sampling, `seanet.py:322-340`; res/out_elu/out_scale unused there).
- * The [M x T] intermediate h lives only in LDS: one HBM read of x and one write of y per block half. */
+ * The [M x T] intermediate h lives only in LDS: one HBM read of x and one write of y per block half.
+ * Alignment: x, and for ksize 5 y and res, must be 16-byte aligned for the fast path; wt is refused unless it is; dw_w, dw_b (and y of the
+ * strided form) need only the 4 bytes of a float. */
 int hilc_dws_conv(const float* x, const float* wt, const float* dw_w, const float* dw_b, const float* res,
                   float* y, int B, int K, int M, int T, int ksize, int stride, float in_scale, int in_elu,
                   float out_scale, int out_elu, void* stream);
@@ -74,7 +82,9 @@ int hilc_dws_conv_wave_row(int B, int M, int T, int has_res);
  * y[b,m,t] = sum_k wt[k][m] * u[b,k,t] + bias[m],   t < Tin*stride
  * The up-sampled tensor u only exists as the GEMM's B operand (computed in the loader).
  * Replaces: `seanet.py:424-441` (Scale, ELU, SConvTranspose1d, SConv1d k=1 with bias). Requires
- * (Tin*stride) % 4 == 0 and M % 4 == 0 (else HILC_ERR_UNSUPPORTED: use hilc_dw_convtr + hilc_pw_conv). */
+ * (Tin*stride) % 4 == 0 and M % 4 == 0 (else HILC_ERR_UNSUPPORTED: use hilc_dw_convtr + hilc_pw_conv).
+ * Alignment (the three entry points of this stage): tr_w, tr_w_expanded and y must be 16-byte aligned for the fast path; wt is refused
+ * unless it is, before anything is written; x, hist, hist_out and bias need only the 4 bytes of a float. */
 int hilc_up_conv(const float* x, const float* tr_w, const float* wt, const float* bias, float* y,
                  int B, int K, int M, int Tin, int stride, float in_scale, int in_elu, void* stream);
 
@@ -98,7 +108,10 @@ int hilc_up_conv_expanded(const float* x, const float* hist, float* hist_out, co
  * `causal_layers.py:147-165`): T <= 128 samples per stream and call, T % stride == 0, any ksize >= stride; longer
  * hops (T % 4 == 0; per-clip tiles with a recomputed halo) for ksize == 2 * stride.
  * hist `[B][M][ksize-stride]` = the last pointwise outputs of the previous hop (NULL = zeros), hist_out receives
- * the new cache (must not alias hist).  A tile holds whole clips, so nothing is recomputed. */
+ * the new cache (must not alias hist).  A tile holds whole clips, so nothing is recomputed.
+ * Alignment: T <= 128: x, and for ksize 5 y, res, hist and hist_out, must be 16-byte aligned for the fast path; wt is refused unless it
+ * is, and so is dw_w for ksize 16 / stride 8 and ksize 10 / stride 5 (a row's taps are read as 16- / 8-byte words).  T > 128: x and wt
+ * are refused unless 16-byte aligned.  Everything else needs only the 4 bytes of a float. */
 int hilc_dws_conv_stream(const float* x, const float* wt, const float* dw_w, const float* dw_b, const float* hist,
                          float* hist_out, const float* res, float* y, int B, int K, int M, int T, int ksize,
                          int stride, float in_scale, int in_elu, float out_scale, int out_elu, void* stream);
@@ -109,7 +122,9 @@ int hilc_dws_conv_stream(const float* x, const float* wt, const float* dw_w, con
  * stay in LDS.  w1t / w2t are the two `[C][C]` pointwise matrices in the PACKED layout written by
  * hilc_resblock_pack_weights (below), dw*_w `[C][5]`.  y must not alias x.
  * Replaces: SEANetResnetBlock.forward (`seanet.py:129-148`) with skip='identity', kernel 5.
- * hilc_resblock_supported(C, T) tells the caller whether this specialisation exists. */
+ * hilc_resblock_supported(C, T) tells the caller whether this specialisation exists.
+ * Alignment (hilc_resblock, _stream, _balanced): x, y, w1t, w2t and the four caches are refused unless 16-byte aligned; the depthwise
+ * taps and biases need only the 4 bytes of a float. */
 int hilc_resblock(const float* x, const float* w1t, const float* dw1_w, const float* dw1_b, const float* w2t,
                   const float* dw2_w, const float* dw2_b, float* y, int B, int C, int T, float pre_scale,
                   float out_scale, void* stream);
@@ -161,7 +176,9 @@ int hilc_resblock_balanced(const float* x, const float* w1t, const float* dw1_w,
  * streaming: C in {512, 768} with whole streams tiling 32 columns, and C = 256 (32-column tiles, four waves, runs of whole streams:
  * measured slower inside a 1024-stream hop than one launch per block, so the engine leaves it off); offline: C in {256, 384, 512} (C = 768: one block per launch,
  * the carry slots of a second do not fit LDS); nblk = 2, or 3 at the decoder's widths (96, 192, streaming 768, offline 384).
- * Else HILC_ERR_UNSUPPORTED: launch the blocks one by one. */
+ * Else HILC_ERR_UNSUPPORTED: launch the blocks one by one.
+ * Alignment: x, y and of every block w1t, w2t and (streaming) the four caches are refused unless 16-byte aligned; the depthwise taps and
+ * biases need only the 4 bytes of a float. */
 typedef struct hilc_resblock_params {
   const float* w1t; const float* dw1_w; const float* dw1_b;
   const float* w2t; const float* dw2_w; const float* dw2_b;
@@ -185,7 +202,9 @@ int hilc_resblock_chain(const float* x, float* y, const hilc_resblock_params* bl
  * up-sampling layer and the stage's FIRST block, the carry slots of a second do not fit LDS), C = 384 with r = 5 (tr_w = the EXPANDED
  * tap table `[2C][r][8]` of hilc_up_conv_expand_taps; nblk 1..3; a streaming hop (ABI 15) on 32-column carry tiles, runs of whole
  * streams, twelve waves — rounds 4-5: nblk = 1 on 64-column halo tiles),
- * C = 192 with r = 4 and C = 96 with r = 2 (streaming hops and, with streaming = 0, the offline model: hist* ignored); nblk 1..3. */
+ * C = 192 with r = 4 and C = 96 with r = 2 (streaming hops and, with streaming = 0, the offline model: hist* ignored); nblk 1..3.
+ * Alignment: y, up->tr_w, up->w_lo, up->w_hi and the blocks' operands named at hilc_resblock_chain are refused unless 16-byte aligned;
+ * up->x, up->hist, up->hist_out, up->bias and the blocks' taps and biases need only the 4 bytes of a float. */
 typedef struct hilc_up_params {
   const float* x; const float* tr_w; const float* w_lo; const float* w_hi; const float* bias;
   const float* hist; float* hist_out;
@@ -203,7 +222,9 @@ int hilc_decoder_stage(const hilc_up_params* up, const hilc_resblock_params* blo
  * the offline model (`up->hist`, the blocks' caches and `post->hist` are ignored).  streaming = 1 (ABI 15): a hop (`streaming.py:639-648`) on the
  * carry form's runs of whole streams, with every cache of hilc_decoder_stage plus the closing conv's — equal, bit for bit, to
  * hilc_decoder_stage(streaming) followed by hilc_conv_post with the same caches.  hilc_decoder_stage_post_supported names the shapes;
- * everything else: HILC_ERR_UNSUPPORTED. */
+ * everything else: HILC_ERR_UNSUPPORTED.
+ * Alignment: as hilc_decoder_stage; post->wav, post->hist and post->hist_out are refused unless 16-byte aligned; post->w and post->bias
+ * need only the 4 bytes of a float. */
 typedef struct hilc_post_params {
   const float* w;      /* [C][ksize] */
   const float* bias;   /* [1] or NULL */
@@ -227,7 +248,10 @@ int hilc_decoder_stage_post(const hilc_up_params* up, const hilc_resblock_params
  * r = 5 and C = 512 with r = 8 — offline in the carry form of the narrow-tile shapes; a streaming hop (ABI 15): C = 256 on 32-column carry
  * tiles (runs of whole streams; T % 40 == 0, i.e. whole frames of the hop), C = 512 on whole-stream tiles (T in {8, 16, 32}); nblk 1..2;
  * T % 4 == 0, T % r == 0.  hilc_encoder_stage_supported names the shapes; everything else HILC_ERR_UNSUPPORTED (callers launch the
- * blocks and hilc_dws_conv[_stream] instead). */
+ * blocks and hilc_dws_conv[_stream] instead).
+ * Alignment: x, down->w_lo, w_hi, res, y, hist, hist_out, the blocks' operands named at hilc_resblock_chain and, for C = 256 / 512,
+ * down->dw_w are refused unless 16-byte aligned; down->dw_b, down->dw_w of the narrow stages and the blocks' taps and biases need only the
+ * 4 bytes of a float. */
 typedef struct hilc_down_params {
   const float* w_lo; const float* w_hi; const float* dw_w; const float* dw_b;
   const float* hist; float* hist_out; const float* res; float* y;
@@ -244,7 +268,9 @@ int hilc_encoder_stage(const float* x, const hilc_resblock_params* blocks, int n
  * reaches HBM.  `spec`: the arguments of hilc_spec_block_conv_pre (packed tables from hilc_spec_block_pack).  streaming = 0: the offline
  * model (`spec->hist`, the blocks' caches and `down->hist` are ignored).  streaming = 1 (ABI 15, `streaming.py:490-511`): a hop on runs of whole
  * streams, T >= 128 (a 128-column tile then holds at most one stream start: its waveform segment is staged as two pieces, each with the 63
- * samples in front of it — a stream's history at t = 0), with every cache of hilc_encoder_stage(streaming). */
+ * samples in front of it — a stream's history at t = 0), with every cache of hilc_encoder_stage(streaming).
+ * Alignment: spec->dft_packed, spec->pw_packed, down->w_lo, w_hi, res, y, hist, hist_out and the blocks' operands named at
+ * hilc_resblock_chain are refused unless 16-byte aligned; spec->wav, spec->hist and every other operand need only the 4 bytes of a float. */
 typedef struct hilc_spec0_params {
   const float* wav;         /* [B][T] */
   const float* dft_packed; const float* nyq_sin; const float* pw_packed; const float* bias;
@@ -266,7 +292,9 @@ int hilc_encoder_stage0(const hilc_spec0_params* spec, const hilc_resblock_param
  * hist_out (optional) receives the last `pad` samples of [hist | pro(x)]  -> next call's hist.
  * Replaces: depthwise SConv1d (`conv.py:202-236`, groups=C: `seanet.py:42-51,330-339,352-355,
  * 417-419`), CausalConv1d (`causal_layers.py:147-165`) and the residual tail of
- * SEANetResnetBlock.forward (`seanet.py:144-148`). res may alias y. */
+ * SEANetResnetBlock.forward (`seanet.py:144-148`). res may alias y.
+ * Alignment: x and y must be 16-byte aligned for the fast path (ksize 5, stride 1, T % 4 == 0); everything else needs only the 4 bytes
+ * of a float. */
 int hilc_dw_conv(const float* x, const float* hist, const float* w, const float* bias, const float* res,
                  float* y, float* hist_out, int B, int C, int T, int ksize, int stride,
                  float in_scale, int in_elu, float out_scale, int out_elu, void* stream);
@@ -275,13 +303,15 @@ int hilc_dw_conv(const float* x, const float* hist, const float* w, const float*
  * y[b,c,q*stride+p] = w[c][p] * xe[q] + w[c][p+stride] * xe[q-1],  T_out = T*stride,
  * xe(-1) = hist[b,c,0] (0 if NULL).  hist_out (optional) receives pro(x[b,c,T-1]).
  * Replaces: SConvTranspose1d (`conv.py:239-282`, right-trim k-s) and CausalConvTranspose1d
- * (`causal_layers.py:168-188`) for groups=C, k=2s, plus the Scale+ELU in front (`seanet.py:424-441`). */
+ * (`causal_layers.py:168-188`) for groups=C, k=2s, plus the Scale+ELU in front (`seanet.py:424-441`).
+ * Alignment: every operand needs only the 4 bytes of a float. */
 int hilc_dw_convtr(const float* x, const float* hist, const float* w, float* y, float* hist_out,
                    int B, int C, int T, int stride, float in_scale, int in_elu, void* stream);
 
 /* ---- first encoder conv: Conv1d(1 -> C, ksize, causal, bias) on the waveform --------------------
  * y[b,c,t] = sum_j w[c][j] * (in_scale * we[b, t-(ksize-1)+j]) + bias[c];  we(t<0) = hist[b, hist_len+t] or 0.
- * Replaces: `seanet.py:280-286` (Scale(1/wav_std) + SConv1d) / `streaming.py:490`. */
+ * Replaces: `seanet.py:280-286` (Scale(1/wav_std) + SConv1d) / `streaming.py:490`.
+ * Alignment: wav and y must be 16-byte aligned for the fast path (ksize 5, T % 4 == 0); everything else needs only the 4 bytes of a float. */
 int hilc_conv_pre(const float* wav, const float* hist, int hist_len, const float* w, const float* bias,
                   float* y, int B, int C, int T, int ksize, float in_scale, void* stream);
 
@@ -289,7 +319,10 @@ int hilc_conv_pre(const float* wav, const float* hist, int hist_len, const float
  * y[b,0,t] = act((sum_c sum_j w[c][j] * xe[b,c,t-(ksize-1)+j] + bias[0]) * out_scale), act = tanh if do_tanh.
  * Replaces: `seanet.py:457-473` / `streaming.py:643-647`. hist/hist_out as in hilc_dw_conv.
  * Order of the channel sum (ksize 5, T % 4 == 0, 16-B aligned x): eight classes c mod 8, each an fmaf chain over (c, tap) ascending, the
- * classes added in ascending order — the order of hilc_decoder_stage_post's closing phase. */
+ * classes added in ascending order — the order of hilc_decoder_stage_post's closing phase.
+ * Alignment: x and hist must be 16-byte aligned for that fast path; a 4-byte-aligned view of either takes the generic kernel, which sums
+ * the channels in sequence (c ascending, then taps): the one fall-back whose bits differ.  w, bias, y and hist_out need only the 4 bytes
+ * of a float. */
 int hilc_conv_post(const float* x, const float* hist, const float* w, const float* bias, float* y,
                    float* hist_out, int B, int C, int T, int ksize, float in_scale, int in_elu,
                    float out_scale, int do_tanh, void* stream);
@@ -300,7 +333,8 @@ int hilc_conv_post(const float* x, const float* hist, const float* w, const floa
  * (. - mean)/std if normalize==1 (0: plain log-magnitude, streaming model with merged normalisation)
  * basis_t: `[n_fft][m_pad]` fp32, row n holds (cos_0, sin_0, cos_1, sin_1, ...)*hann for sample n,
  *          m_pad = round_up(n_fft+2, 32), zero padded (host-built from the reference's basis).
- * Replaces: CausalSTFT (`conv.py:285-358`, `causal_layers.py:72-144`) + `seanet.py:224-236`. */
+ * Replaces: CausalSTFT (`conv.py:285-358`, `causal_layers.py:72-144`) + `seanet.py:224-236`.
+ * Alignment: basis_t is refused unless 16-byte aligned; wav, hist and spec need only the 4 bytes of a float. */
 int hilc_stft_logmag(const float* wav, const float* hist, int hist_len, const float* basis_t, float* spec,
                      int B, int T, int n_fft, int hop, float mean, float std, int normalize, void* stream);
 
@@ -317,7 +351,9 @@ int hilc_stft_logmag(const float* wav, const float* hist, int hist_len, const fl
  *              cos_{N/2-1}, sin_{N/2-1}) * hann — the reference basis without the all-zero sin_0 row and without sin_{N/2};
  *   which = 1: the k-major `[n_fft/2+1][C]` conv weight (hilc_pw_conv's layout);
  * nyq_sin `[n_fft]`: the sin_{N/2} row of the reference basis (|.| <= 1.4e-4, evaluated as a scalar chain).
- * hilc_spec_block_packed_floats(n_fft, which) = size of a packed operand. */
+ * hilc_spec_block_packed_floats(n_fft, which) = size of a packed operand.
+ * Alignment (hilc_spec_block and hilc_spec_block_conv_pre): x, y, dft_packed and pw_packed are refused unless 16-byte aligned; wav, hist,
+ * nyq_sin, bias, pre_w and pre_b need only the 4 bytes of a float. */
 int hilc_spec_block_supported(int n_fft, int hop, int C, int T);
 int hilc_spec_block_packed_floats(int n_fft, int which);
 int hilc_spec_block_pack(const float* w, float* packed, int K, int n_fft, int which, void* stream);
@@ -335,13 +371,15 @@ int hilc_spec_block_conv_pre(const float* wav, const float* hist, int hist_len, 
 
 /* ---- streaming cache update: out[row][i] = last `pad` samples of [hist[row][0..hist_len) | x[row][0..T)] ----
  * Replaces: `cache = x[:, :, -causal_padding:]` after `torch.cat((cache, x), dim=2)`
- * (`causal_layers.py:160-162`, waveform cache `streaming.py:486-488`). hist may be NULL (zeros). */
+ * (`causal_layers.py:160-162`, waveform cache `streaming.py:486-488`). hist may be NULL (zeros).
+ * Alignment: every operand needs only the 4 bytes of a float. */
 int hilc_tail(const float* x, const float* hist, float* out, long rows, int T, int pad, int hist_len,
               void* stream);
 
 /* ---- L2 normalisation over channels: y = x / max(||x||_2, eps) * scale ---------------------------
  * x `[B][C][T]`; y `[B][C][T]` or, if channel_last_out, `[B][T][C]` (streaming encoder output).
- * Replaces: L2Norm (`seanet.py:151-162`, `streaming.py:279-286`). */
+ * Replaces: L2Norm (`seanet.py:151-162`, `streaming.py:279-286`).
+ * Alignment: x and y need only the 4 bytes of a float. */
 int hilc_l2norm(const float* x, float* y, int B, int C, int T, float eps, float scale,
                 int channel_last_out, void* stream);
 
@@ -358,7 +396,9 @@ int hilc_l2norm(const float* x, float* y, int B, int C, int T, float eps, float 
  * (4 or 16 frames per workgroup), 8 192 frames and more on the matrix pipe (v_mfma_f32_32x32x2_f32, 32 frames per workgroup,
  * the A operand read straight from codebooks_t) — same bits, same indices.  flags: 0, or HILC_RVQ_VALU_ONLY = keep large batches
  * on the VALU form too (16 frames per workgroup; the caller's switch should an fp32 MFMA ever stop being a sequential fmaf chain
- * over ascending k); any other bit: HILC_ERR_UNSUPPORTED. */
+ * over ascending k); any other bit: HILC_ERR_UNSUPPORTED.
+ * Alignment: codebooks_t and norms must be 16-byte aligned for the matrix-pipe form (else large batches keep the VALU form: same indices);
+ * everything else needs only the 4 bytes of a float. */
 #define HILC_RVQ_VALU_ONLY 1
 int hilc_rvq_encode(const float* z, const float* codebooks, const float* codebooks_t, const float* norms,
                     int64_t* indices, float* q, float* frame_err, int B, int C, int T, int K, int Nq, int n,
@@ -377,7 +417,8 @@ int hilc_rvq_encode_mixed(const float* z, const float* codebooks, const float* c
 int hilc_mse_finalize(const float* frame_err, float* loss, int frames, double count, void* stream);
 
 /* ---- residual VQ decode (Dequantizer): q = sum_{i<n} E_i[idx_i] ---------------------------------
- * Replaces: Dequantizer.forward (`streaming.py:148-157`) / F.embedding sums in ResidualVQ. */
+ * Replaces: Dequantizer.forward (`streaming.py:148-157`) / F.embedding sums in ResidualVQ.
+ * Alignment: codebooks and q need only the 4 bytes of a float. */
 int hilc_rvq_decode(const int64_t* indices, const float* codebooks, float* q, int B, int C, int T,
                     int K, int Nq, int n, int channel_last, int stage_major, void* stream);
 
