@@ -99,6 +99,8 @@ SIGNATURES = {
     "hilc_downlink_step": [_p] * 19 + [_i] * 18 + [_p],
     "hilc_audio_level": [_p, _p, _p, _p, _i, _i, _p],
     "hilc_forward_rank": [_p] * 7 + [_i] * 7 + [_p],
+    "hilc_rx_bwe": [_p, _p, _p, _i, _p, _p, _p, _p] + [_i] * 14 + [_p],
+    "hilc_rate_cap": [_p] * 5 + [_i] * 4 + [_p],
 }
 
 ABI_VERSION = 16

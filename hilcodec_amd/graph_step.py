@@ -25,6 +25,7 @@ from torch import Tensor
 
 from . import dtx as dtx_def
 from . import audio_level as level_def
+from . import bwe as bwe_def
 from . import engine, ops, wire
 from . import downlink as downlink_def
 from . import forward as forward_def
@@ -141,14 +142,18 @@ class ControlStage:
     The rows among sessions.ONE_HOP_ROWS apply to exactly one hop: they are written with `put_one_hop`, and `one_hop_live` says
     whether one of them still holds entries on the device, so that the next upload has to clear it.
     `arrivals` = (max_arrivals, row_bytes): the payload is an arrival region (sessions.arrival_region_words) — `offsets` /
-    `h_offsets` int32 `[B + 1]` and `arrivals` / `h_arrivals` int32 `[max_arrivals, arrival_width]` — which `send_arrivals` sends."""
+    `h_offsets` int32 `[B + 1]` and `arrivals` / `h_arrivals` int32 `[max_arrivals, arrival_width]` — which `send_arrivals` sends;
+    `times=True`: the region also carries `times` / `h_times` int32 `[max_arrivals]`, the arrival ticks parallel to the records."""
 
     def __init__(self, batch: int, rows: Sequence[str], payload_words: int, loads: int, record_len: int, device: torch.device,
-                 arrivals: Optional[Tuple[int, int]] = None):
+                 arrivals: Optional[Tuple[int, int]] = None, times: bool = False):
+        if times and arrivals is None:
+            raise ValueError("ControlStage: arrival times belong to an arrival region")
+        n_times = arrivals[0] if times else 0
         if arrivals is not None:
             if payload_words:
                 raise ValueError("ControlStage: the arrival region is the whole payload, payload_words must be 0 with arrivals")
-            payload_words = arrival_region_words(batch, *arrivals)
+            payload_words = arrival_region_words(batch, *arrivals) + n_times
         self.row_off, self.payload_off, self.rec_off, total = stage_layout(batch, rows, payload_words, loads, record_len)
         self.device = device
         self.dev = torch.zeros(total, device=device)
@@ -163,11 +168,16 @@ class ControlStage:
         self._live = {name: False for name in ONE_HOP_ROWS if name in self.row_off}    # the row was last written with entries
         if arrivals is not None:
             # uploaded up to the last arrival used: the CSR offsets of the arrivals [B + 1], the arrival records grouped by slot
+            # `times`: the arrival ticks int32 [max_arrivals], parallel to the records, between the offsets and the records (they go up
+            # whole: a few words per slot); without them the region is offsets | records
             max_arrivals, self.row_bytes = arrivals
-            self.arr_off = self.payload_off + batch + 1       # the words in front of the arrival records
+            first = batch + 1 + n_times
+            self.arr_off = self.payload_off + first           # the words in front of the arrival records
             self.offsets, self.h_offsets = self.payload[:batch + 1].view(torch.int32), self.h_payload[:batch + 1].view(torch.int32)
-            self.arrivals = self.payload[batch + 1:].view(torch.int32).view(max_arrivals, arrival_width(self.row_bytes))
-            self.h_arrivals = self.h_payload[batch + 1:].view(torch.int32).view(max_arrivals, arrival_width(self.row_bytes))
+            self.times = self.payload[batch + 1:first].view(torch.int32) if times else None
+            self.h_times = self.h_payload[batch + 1:first].view(torch.int32) if times else None
+            self.arrivals = self.payload[first:].view(torch.int32).view(max_arrivals, arrival_width(self.row_bytes))
+            self.h_arrivals = self.h_payload[first:].view(torch.int32).view(max_arrivals, arrival_width(self.row_bytes))
 
     def wait(self) -> None:
         """before the mirror is written: the previous upload's copy has left the pinned buffer"""
@@ -198,10 +208,13 @@ class ControlStage:
         self.dev[:words].copy_(self.host[:words], non_blocking=True)
         self.sent_words = words
 
-    def send_arrivals(self, arr: Arrivals, packets: Tensor) -> None:
+    def send_arrivals(self, arr: Arrivals, packets: Tensor, times: Optional[np.ndarray] = None) -> None:
         """checked arrivals (sessions.check_arrivals) -> the mirror's arrival region, then `send` up to the last arrival used; packets
-        that are on the device go into the device records behind that copy, gathered first unless they came grouped by slot"""
+        that are on the device go into the device records behind that copy, gathered first unless they came grouped by slot.  `times`
+        (a stage with arrival times only): their ticks int32 [A] in the records' slot-grouped order, in the same copy"""
         put_arrivals(arr, packets, self.h_offsets, self.h_arrivals, self.row_bytes)
+        if self.h_times is not None and arr.count:
+            self.h_times.numpy()[:arr.count] = times
         self.send(self.arr_off + arr.count * self.arrivals.shape[1])
         if arr.count and packets.is_cuda:
             grouped = np.array_equal(arr.order, np.arange(arr.count))
@@ -334,11 +347,12 @@ class _Hop(_GraphPair):
         """a state block of `streams` streams (the sender and the receiver: one side's caches only)"""
         return StateBlock(self.model, streams, self.device)
 
-    def _new_stage(self, rows: Sequence[str], payload_words: int = 0, arrivals: Optional[Tuple[int, int]] = None) -> ControlStage:
-        """the control stage of a hop with these rows and payload (`arrivals`: an arrival region), and the device views every session
-        graph reads"""
+    def _new_stage(self, rows: Sequence[str], payload_words: int = 0, arrivals: Optional[Tuple[int, int]] = None,
+                   times: bool = False) -> ControlStage:
+        """the control stage of a hop with these rows and payload (`arrivals`: an arrival region, `times`: with arrival ticks), and the
+        device views every session graph reads"""
         q = self.queue
-        stage = ControlStage(q.batch, rows, payload_words, q.max_loads, q.layout.record_len, self.device, arrivals)
+        stage = ControlStage(q.batch, rows, payload_words, q.max_loads, q.layout.record_len, self.device, arrivals, times)
         self.action, self.hold, self.records = stage.row["action"], stage.row["hold"], stage.records
         return stage
 
@@ -796,13 +810,24 @@ class GraphedEncodeHop(GraphedHop):
     front of the encoder: `.audio_level` (int32 `[B]` device view, valid until the next-but-one `step`, like `.indices`) is the hop's
     level, -dBov in 1 dB steps in [0, 127] (audio_level.py: the rule), 127 for a held or stopped slot.  It is what a forwarding hop
     takes as `forward(levels=)`; it travels beside the packet, and nothing else the hop returns changes.  `audio_level=False` captures
-    exactly the graph without it."""
+    exactly the graph without it.
+    `cap` = bwe.CapConfig(timeout_hops) (needs `rate`): the receiver's delay-based bandwidth estimate as a ceiling of the rate (bwe.py).
+    `step(x, hold=None, reports=None, nacks=None, caps=(slots, blobs))` takes this hop's rate caps like `reports` — A host ints, and a
+    uint8 `[A, 3]` host tensor or a sequence of 3-byte `bytes` (`wire.pack_cap`, what GraphedDecodeHop(bwe=...) shows as
+    `caps[cap_due]`; a slot outside [0, B) or a wrong width: ValueError; a slot named twice keeps its last) — as one more int32 row of
+    the control stage's single copy, for exactly one hop.  One hilc_rate_cap directly in front of hilc_rate_ceiling accepts a cap by
+    that kernel's sequence rule, keeps it (clamped to the rate's bounds) until the next one or until timeout_hops hops without one, and
+    holds the slot's rate at or below it; hilc_rate_ceiling, unchanged, runs on the clamped rate.  The slot's rate is therefore the
+    smaller of the loss-based rate and the receiver's estimate: the reports keep probing upward and handle the standing queue a delay
+    gradient cannot see.  `cap_state` (int32 `[B, bwe.CP_WORDS]`) is a device view.  A `start` or a resume clears a slot's row inside
+    the graph, `reset` every row; held and stopped slots take their caps but do not age; `export` and a resume carry none.  `cap=None`
+    captures exactly the graph without it."""
 
     def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, input_rate: int = BASE_RATE, fec_stages: int = 0,
                  dtx: Optional[dtx_def.DtxConfig] = None, header: bool = False, vbr: Optional[vbr_def.VbrConfig] = None,
                  fec_adapt: Optional[report_def.FecAdaptConfig] = None, rtx: Optional[rtx_def.RtxConfig] = None,
-                 rate: Optional[rate_def.RateConfig] = None, audio_level: bool = False):
+                 rate: Optional[rate_def.RateConfig] = None, audio_level: bool = False, cap: Optional[bwe_def.CapConfig] = None):
         # the options are checked and what they derive is set up first: GraphedHop's constructor allocates (_init_state) and captures
         self.fec_stages = _fec_stages(fec_stages, n)
         self.fec_adapt = _config_arg("fec_adapt", fec_adapt, report_def.FecAdaptConfig)
@@ -820,6 +845,9 @@ class GraphedEncodeHop(GraphedHop):
             # ValueError: a min_kbps that does not pay for the floor of a hop, a max_kbps past the int32 rows
             self._rate_bits = rate_def.bucket(rate, _whole_frames("GraphedEncodeHop(rate=...)", hop), self.fec_stages, self.header)
         self._nacks = {}                      # slot -> (word, bitmap) for the next hop
+        self.cap = _config_arg("cap", cap, bwe_def.CapConfig)
+        _needs("GraphedEncodeHop(cap=...)", cap is None or rate is not None, "rate=RateConfig(...): a cap is a ceiling of the rate")
+        self._caps = {}                       # slot -> cap word for the next hop
         self._measure_level = bool(audio_level)
         self.frames = hop // HOP
         self.dtx = _config_arg("dtx", dtx, dtx_def.DtxConfig)
@@ -850,6 +878,7 @@ class GraphedEncodeHop(GraphedHop):
     def _init_state(self) -> None:
         n, m, T = self.n, self.fec_stages, self.frames
         self._prev = self._run = self._ctr = self._credit = self._fa = self._fec_on = self._rx = self._rc = self._n_ceil = self._level = None
+        self._cp = None
         if m:
             # per parity, per slot: valid, then the first m stages x T frames of its last encoded hop (the hop of parity p reads
             # row p and writes row p ^ 1)
@@ -885,6 +914,9 @@ class GraphedEncodeHop(GraphedHop):
             self._rc = self._slot_state(rate_def.RC_WORDS, cleared={rate_def.RC_RATE_Q8: 256 * start,
                                                                      rate_def.RC_CREDIT: self.rate.burst_hops * start})
             self._n_ceil = self._slot_state(cleared=int(n))
+        if self.cap is not None:
+            # per slot: the cap row (bwe.CP_*, updated in place by hilc_rate_cap once per hop)
+            self._cp = self._slot_state(bwe_def.CP_WORDS)
         if self._measure_level:
             # per parity, per slot: the hop's level (the hop of parity p writes row p); cleared = silence
             self._level = self._slot_state(pingpong=True, cleared=level_def.MAX_LEVEL)
@@ -918,6 +950,10 @@ class GraphedEncodeHop(GraphedHop):
                 if self.fec_adapt is not None:
                     ops.fec_adapt(self._prev[p], self._fa, self._fec_on, self.fec_stages, self.frames, self.fec_adapt,
                                   self.stage.row["report"], action, hold)
+                if self.cap is not None:
+                    # directly in front of the ceiling: the rate it moves and fills the bucket with is at most the receiver's cap
+                    ops.rate_cap(self._cp, self._rc, self.cap, self._rate_bits.min_bits, self._rate_bits.max_bits,
+                                 self.stage.row["cap"], action, hold)
                 ops.rate_ceiling(self._rc, self._n_ceil, self.n, self.frames, self.fec_stages, self.header, self.rate,
                                  self.stage.row["report"], action, hold, n_clip, self._prev[p] if self.fec_stages else None)
                 n_clip = self._n_ceil
@@ -1005,6 +1041,13 @@ class GraphedEncodeHop(GraphedHop):
         return self._rc
 
     @property
+    def cap_state(self) -> Tensor:
+        """int32 `[B, bwe.CP_WORDS]` device view: each slot's cap row after the last hop (bwe.CP_*; cap only).  Read-only: written by
+        the graph."""
+        self._need(self._cp is not None, "cap_state", "cap=CapConfig(...)")
+        return self._cp
+
+    @property
     def rtx_packets(self) -> Tensor:
         """uint8 `[B, per_hop, wire.transport_bytes(n, m, T)]` device view: each slot's retransmissions of the last hop, in request
         order, zero past their lengths (rtx only); overwritten by the next-but-one `step`.  Read-only: written by the graph."""
@@ -1062,11 +1105,16 @@ class GraphedEncodeHop(GraphedHop):
         return self._feedback("nacks", nacks, wire.NACK_BYTES, lambda blob: rtx_def.nack_words(*wire.parse_nack(blob)),
                               self.rtx is not None, "rtx=RtxConfig(...)")
 
+    def _cap_words(self, caps) -> dict:
+        return self._feedback("caps", caps, wire.CAP_BYTES, lambda blob: bwe_def.cap_word(*wire.parse_cap(blob)),
+                              self.cap is not None, "cap=CapConfig(...)")
+
     def _extra_rows(self) -> Tuple[str, ...]:
-        return ("report",) * (self.fec_adapt is not None or self.rate is not None) + ("nack_base", "nack_bitmap") * (self.rtx is not None)
+        return (("report",) * (self.fec_adapt is not None or self.rate is not None) + ("nack_base", "nack_bitmap") * (self.rtx is not None)
+                + ("cap",) * (self.cap is not None))
 
     def _extra_pending(self) -> bool:
-        return bool(self._reports or self._nacks)
+        return bool(self._reports or self._nacks or self._caps)
 
     def _put_extra(self, st: ControlStage) -> None:
         """the report row: this hop's reports, 0 elsewhere (a report applies to exactly one hop, like an action: the upload after a
@@ -1088,21 +1136,29 @@ class GraphedEncodeHop(GraphedHop):
             st.put_one_hop("nack_base", slots, words[:, 0])
             st.put_one_hop("nack_bitmap", slots, words[:, 1])
             self._nacks = {}
+        if self.cap is not None and not self._caps:
+            st.put_one_hop("cap")
+        elif self.cap is not None:
+            # the cap row, likewise: this hop's caps, 0 elsewhere
+            slots = np.fromiter(self._caps, dtype=np.int64, count=len(self._caps))
+            st.put_one_hop("cap", slots, np.fromiter(self._caps.values(), dtype=np.int32, count=len(slots)))
+            self._caps = {}
 
     def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
-        self._reports, self._nacks = {}, {}
+        self._reports, self._nacks, self._caps = {}, {}, {}
         super().reset(cache_enc, cache_dec)
 
-    def step(self, x: Tensor, hold=None, reports=None, nacks=None) -> Tuple[Tensor, Tensor]:
+    def step(self, x: Tensor, hold=None, reports=None, nacks=None, caps=None) -> Tuple[Tensor, Tensor]:
         """`reports` (fec_adapt or rate only): (slots, blobs), this hop's receiver reports — A host ints, and a uint8 `[A, 3]` host tensor or a
         sequence of 3-byte `bytes` (wire.pack_report).  `nacks` (rtx only): (slots, blobs) likewise, this hop's NACKs, 4 bytes each
-        (wire.pack_nack)"""
+        (wire.pack_nack).  `caps` (cap only): (slots, blobs) likewise, this hop's rate caps, 3 bytes each (wire.pack_cap)"""
         self._reports = self._report_words(reports)
         self._nacks = self._nack_words(nacks)
+        self._caps = self._cap_words(caps)
         try:
             out = super().step(x, hold)
         finally:
-            self._reports, self._nacks = {}, {}       # taken by the upload, or dropped with a step that raised before it
+            self._reports, self._nacks, self._caps = {}, {}, {}       # taken by the upload, or dropped with a step that raised before it
         self.indices, packets, nbytes = out[:3]
         if self.dtx is not None:
             self.kind = out[3]
@@ -1211,13 +1267,27 @@ class GraphedDecodeHop(_Hop):
     `nack_state` (int32 `[B, rtx.NK_WORDS]`) are device views.  It only observes: wav, caches and every other state are those of the
     receiver without it.  The sender's answers (GraphedEncodeHop(rtx=...)) are pushed with `play()` like any packet.  A `start` or a
     resume clears a slot's row, NACK and flag inside the graph; `export` and a resume carry none.  `nack=None` captures exactly the
-    graph without it."""
+    graph without it.
+    `bwe` = bwe.BweConfig(min_kbps, max_kbps, window, rate_window, alpha_q8, beta_q8, increase_q16, interval, reset_ticks) (needs
+    `jitter`: the rule reads `play()`'s arrivals; at most bwe.MAX_FRAMES frames and a cap of at most 65535 bits per hop: ValueError
+    otherwise): the delay-based bandwidth estimate (bwe.py).  `play(slots, packets, nbytes, hold=None, times=...)` then takes each
+    arrival's tick — A host ints in units of 1/24000 s, any origin, taken mod 2^32 — which travel in the control stage's single copy as
+    an int32 array parallel to the arrival records.  One hilc_rx_bwe directly after the jitter step, beside hilc_rx_report and
+    hilc_nack_build and independent of both, measures each slot's delay gradient (how much further apart its packets arrive than they
+    were sent: exact from the header's hop index), runs the over-use detector and an AIMD controller on the incoming rate and emits the
+    slot's cap (seq, bits per hop: `wire.pack_cap`) every `interval` hops and at once after a decrease: `caps` (uint8 `[B, 3]`: each
+    slot's latest cap, unchanged between caps), `cap_due` (int32 `[B]`: 1 on the hop a cap was emitted) and `bwe_state` (int32 `[B,
+    bwe.BW_WORDS]`; `bwe.kbps(bwe_state, frames)` on the host) are device views.  The caps go to the sender:
+    GraphedEncodeHop(cap=...).step(caps=).  It only observes: wav, caches and every other state are those of the receiver without it.
+    A `start` or a resume clears a slot's row, cap and flag inside the graph; `export` and a resume carry none.  `bwe=None` captures
+    exactly the graph without it, with today's stage layout and upload."""
 
     def __init__(self, model, batch: int, frames: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, conceal: bool = False, fade_hops: int = 4, output_rate: int = BASE_RATE,
                  fec_stages: int = 0, cng_order: Optional[int] = None, jitter: Optional[JitterConfig] = None,
                  max_arrivals: Optional[int] = None, mix: Optional[MixConfig] = None,
-                 report: Optional[report_def.ReportConfig] = None, nack: Optional[rtx_def.NackConfig] = None):
+                 report: Optional[report_def.ReportConfig] = None, nack: Optional[rtx_def.NackConfig] = None,
+                 bwe: Optional[bwe_def.BweConfig] = None):
         self.batch, self.frames = int(batch), int(frames)
         self.output_rate = int(output_rate)
         self.rs, self._history = None, 0
@@ -1248,6 +1318,13 @@ class GraphedDecodeHop(_Hop):
         self.nack = _config_arg("nack", nack, rtx_def.NackConfig)
         _needs("GraphedDecodeHop(nack=...)", jitter is not None or nack is None,
                "jitter=JitterConfig(...): the NACKs are made from the jitter ring")
+        self.bwe = _config_arg("bwe", bwe, bwe_def.BweConfig)
+        _needs("GraphedDecodeHop(bwe=...)", jitter is not None or bwe is None,
+               "jitter=JitterConfig(...): the estimate is made from play()'s arrivals")
+        if bwe is not None:
+            bwe_def.bits(bwe, self.frames)                              # ValueError: bounds past a uint16 cap, too many frames
+            if wire.transport_bytes(int(n), self.fec_stages, self.frames) > bwe_def.MAX_ROW_BYTES:
+                raise ValueError(f"GraphedDecodeHop(bwe=...): a headed packet of more than {bwe_def.MAX_ROW_BYTES} bytes")
         super().__init__(model, self.batch, int(n), device, 1, sessions, max_loads_per_hop)
         self.stride = wire.packet_bytes(self.n + self.fec_stages, self.frames)
         B = self.batch
@@ -1283,6 +1360,13 @@ class GraphedDecodeHop(_Hop):
             self._nk = self._slot_state(rtx_def.NK_WORDS)
             self._nk_bytes = self._slot_state(wire.NACK_BYTES, dtype=torch.uint8)
             self._nk_due = self._slot_state()
+        if bwe is not None:
+            # per slot: the estimate row (bwe.BW_*, updated in place by hilc_rx_bwe once per hop), its latest cap, its due flag; cleared
+            # = the row zero but for the estimate at max_kbps and the detector's starting threshold
+            self._bw = self._slot_state(bwe_def.BW_WORDS, cleared={bwe_def.BW_RATE_Q8: 256 * bwe_def.bits(bwe, self.frames).max_bits,
+                                                                   bwe_def.BW_THR: bwe_def.THR_START})
+            self._bw_bytes = self._slot_state(wire.CAP_BYTES, dtype=torch.uint8)
+            self._bw_due = self._slot_state()
         if mix is not None:
             # per slot: the peak-hold score (updated in place by hilc_mix_levels once per hop); per parity: the mixes; the speaker
             # marks; the room row (device, captured by address) and its pinned host mirror
@@ -1342,6 +1426,9 @@ class GraphedDecodeHop(_Hop):
             ops.rx_report(self._jstate, self._rp, self._rp_bytes, self._rp_due, self.report, self.action)
         if self.nack is not None:
             ops.nack_build(self._jstate, self._jmeta, self._nk, self._nk_bytes, self._nk_due, self.nack, self.fec_stages, self.action)
+        if self.bwe is not None:
+            ops.rx_bwe(self.arrivals, self.offsets, self.stage.times, self._bw, self._bw_bytes, self._bw_due, self.bwe, self.n,
+                       self.frames, self.fec_stages, self.cng_order, self.action)
         if self.sessions:
             ops.state_slots_apply(src.buffer, src.layout, self.action, self.records)
         packets = self.packets
@@ -1520,7 +1607,7 @@ class GraphedDecodeHop(_Hop):
         # ONE device buffer, captured by address, uploaded up to the last arrival used: action per slot, the host's holds
         # (hilc_jitter_step adds its own), the arrival region (an arrival record: byte count, then the headed packet), the staged
         # records.  The n, lost and fec rows and the packet matrix are written by hilc_jitter_step and are never uploaded.
-        st = self.stage = self._new_stage(("action", "hold"), arrivals=(self.max_arrivals, self.tstride))
+        st = self.stage = self._new_stage(("action", "hold"), arrivals=(self.max_arrivals, self.tstride), times=self.bwe is not None)
         self.offsets, self.arrivals = st.offsets, st.arrivals
         rows = torch.zeros(3, B, dtype=torch.int32, device=dev)
         self.n_slot = rows[0]
@@ -1590,19 +1677,67 @@ class GraphedDecodeHop(_Hop):
         self._need(self.nack is not None, "nack_state", "nack=NackConfig(...)")
         return self._nk
 
-    def play(self, slots, packets: Tensor, nbytes, hold=None) -> Tensor:
+    @property
+    def caps(self) -> Tensor:
+        """uint8 `[B, 3]` device view: each slot's latest rate cap (wire.parse_cap; zeros before its first), unchanged between caps.
+        Read-only: written by the graph."""
+        self._need(self.bwe is not None, "caps", "bwe=BweConfig(...)")
+        return self._bw_bytes
+
+    @property
+    def cap_due(self) -> Tensor:
+        """int32 `[B]` device view: 1 for the slots whose cap was emitted on the last play.  Read-only: written by the graph."""
+        self._need(self.bwe is not None, "cap_due", "bwe=BweConfig(...)")
+        return self._bw_due
+
+    @property
+    def bwe_state(self) -> Tensor:
+        """int32 `[B, bwe.BW_WORDS]` device view: each slot's estimate row after the last play (bwe.BW_*; `bwe.kbps(row, frames)`
+        gives BW_RATE_Q8 in kbps).  Read-only: written by the graph."""
+        self._need(self.bwe is not None, "bwe_state", "bwe=BweConfig(...)")
+        return self._bw
+
+    def _arrival_times(self, times, arr: Arrivals) -> Optional[np.ndarray]:
+        """play's `times` checked before anything is written -> the ticks int32 [A] in the records' slot-grouped order (None without
+        `bwe`): A host ints, taken mod 2^32"""
+        if self.bwe is None:
+            self._need(times is None, "play(times=...)", "bwe=BweConfig(...)")
+            return None
+        if times is None:
+            if arr.count:
+                raise ValueError("play: a receiver with bwe= needs `times`, the arrival tick of every packet")
+            return np.zeros(0, dtype=np.int32)
+        if isinstance(times, Tensor):
+            if times.is_cuda:
+                raise ValueError("play: times must be host ints, not a device tensor")
+            times = times.numpy()
+        try:
+            ticks = np.asarray(times)
+            if ticks.dtype.kind not in "iu":
+                ticks = np.array([int(t) & 0xFFFFFFFF for t in ticks.reshape(-1).tolist()], dtype=np.int64)
+        except OverflowError:                                           # Python ints past 64 bits
+            ticks = np.array([int(t) & 0xFFFFFFFF for t in times], dtype=np.int64)
+        ticks = ticks.reshape(-1)
+        if len(ticks) != arr.count:
+            raise ValueError(f"play: {arr.count} slots but {len(ticks)} times")
+        return (ticks.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)[arr.order]
+
+    def play(self, slots, packets: Tensor, nbytes, hold=None, times=None) -> Tensor:
         """one hop of a jitter receiver: this hop's arrivals, in push order — `slots` and `nbytes` (A host ints), `packets` uint8
         `[A, wire.transport_bytes(n, m, frames)]` (host or device) — and `hold`: slots (host ints) held on this hop (playout
-        pauses).  Returns the hop's waveform, a static view that the next-but-one call overwrites."""
+        pauses).  `times` (with `bwe` only, then required whenever A > 0): the arrivals' ticks, A host ints in units of 1/24000 s
+        (ValueError for a device tensor or another length).  Returns the hop's waveform, a static view that the next-but-one call
+        overwrites."""
         self._need(self.jitter is not None, "play", "jitter=JitterConfig(...)")
         held = set(self._hold_slots(hold)) | self.queue.stops
         arr = check_arrivals("play", slots, packets, nbytes, self.batch, self.max_arrivals, self.tstride)
+        ticks = self._arrival_times(times, arr)
         st, q = self.stage, self.queue
         st.wait()
         _mark(st.h_row["hold"], held)
         st.put_starts(q.starts)
         q.clear()
-        st.send_arrivals(arr, packets)
+        st.send_arrivals(arr, packets, ticks)
         st.finish(host_records_apart=True)
         self._send_rooms()
         return self._replay()

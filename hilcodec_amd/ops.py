@@ -27,6 +27,8 @@ from ._lib import DownParams, PostParams, ResblockParams, Spec0Params, UpParams,
 from .audio_level import SP_WORDS
 from .downlink import DL_WORDS, DS_WORDS
 from .downlink import bucket as downlink_bucket
+from .bwe import BW_WORDS, CP_WORDS
+from .bwe import bits as bwe_bits
 from .dtx import LEVELS, state_words
 from .forward import LR_WORDS, SD_WORDS
 from .jitter import AD_WORDS, ST_WORDS
@@ -34,7 +36,7 @@ from .report import FA_WORDS, RP_WORDS
 from .rate import RC_WORDS, bucket
 from .rtx import NK_WORDS, RX_WORDS
 from .resample import HOP
-from .wire import CONCEAL_CODES, NACK_BYTES, REPORT_BYTES, TRANSPORT_HEADER, packet_bytes
+from .wire import CAP_BYTES, CONCEAL_CODES, NACK_BYTES, REPORT_BYTES, TRANSPORT_HEADER, packet_bytes
 
 _LIB = torch.library.Library("hilcodec", "DEF")
 
@@ -1338,6 +1340,44 @@ _register("rate_charge", "(Tensor nbytes, Tensor? rtx_nbytes, Tensor(a!) rows, i
           lambda nbytes, rtx_nbytes, rows, burst_hops: None)
 
 # ======================================================================================================
+# delay-based bandwidth estimate (graph_step.GraphedDecodeHop(bwe=) / GraphedEncodeHop(cap=); definition: hilcodec_amd/bwe.py;
+# semantics: include/hilcodec_amd.h)
+# ======================================================================================================
+def _rx_bwe(arrivals, offsets, times, action, rows, caps, due, n, m, frames, order, min_bits, max_bits, window, rate_window, alpha_q8,
+            beta_q8, increase_q16, interval, reset_ticks):
+    B = due.numel()
+    aw = (TRANSPORT_HEADER + packet_bytes(n + m, frames) + 3) // 4
+    if arrivals.dim() != 2 or arrivals.shape[1] != 1 + aw or offsets.numel() != B + 1 or times.numel() != arrivals.shape[0]:
+        raise RuntimeError(f"rx_bwe: arrivals must be [A, {1 + aw}], offsets [{B + 1}] and times [A]")
+    if rows.shape != (B, BW_WORDS) or caps.shape != (B, CAP_BYTES):
+        raise RuntimeError(f"rx_bwe: rows must be [{B}, {BW_WORDS}] and caps [{B}, {CAP_BYTES}]")
+    _rows("rx_bwe", B, action=action)
+    check(lib.hilc_rx_bwe(_ptr(arrivals, torch.int32), _ptr(offsets, torch.int32), _ptr(times, torch.int32), arrivals.shape[0],
+                          _ptr(action, torch.int32), _ptr(rows, torch.int32), _ptr(caps, torch.uint8), _ptr(due, torch.int32), B, frames,
+                          n, m, order, min_bits, max_bits, window, rate_window, alpha_q8, beta_q8, increase_q16, interval, reset_ticks,
+                          _stream()), "hilc_rx_bwe")
+
+
+_register("rx_bwe", "(Tensor arrivals, Tensor offsets, Tensor times, Tensor? action, Tensor(a!) rows, Tensor(b!) caps, Tensor(c!) due, "
+          "int n, int m, int frames, int order, int min_bits, int max_bits, int window, int rate_window, int alpha_q8, int beta_q8, "
+          "int increase_q16, int interval, int reset_ticks) -> ()", _rx_bwe,
+          lambda arrivals, offsets, times, action, rows, caps, due, n, m, frames, order, min_bits, max_bits, window, rate_window, alpha_q8,
+          beta_q8, increase_q16, interval, reset_ticks: None)
+
+
+def _rate_cap(cap, action, hold, rows, rate_rows, min_bits, max_bits, timeout_hops):
+    B = rows.shape[0]
+    if rows.shape != (B, CP_WORDS) or rate_rows.shape != (B, RC_WORDS):
+        raise RuntimeError(f"rate_cap: rows must be [{B}, {CP_WORDS}] and rate_rows [{B}, {RC_WORDS}]")
+    _rows("rate_cap", B, cap=cap, action=action, hold=hold)
+    check(lib.hilc_rate_cap(_ptr(cap, torch.int32), _ptr(action, torch.int32), _ptr(hold, torch.int32), _ptr(rows, torch.int32),
+                            _ptr(rate_rows, torch.int32), B, min_bits, max_bits, timeout_hops, _stream()), "hilc_rate_cap")
+
+
+_register("rate_cap", "(Tensor? cap, Tensor? action, Tensor? hold, Tensor(a!) rows, Tensor(b!) rate_rows, int min_bits, int max_bits, "
+          "int timeout_hops) -> ()", _rate_cap, lambda cap, action, hold, rows, rate_rows, min_bits, max_bits, timeout_hops: None)
+
+# ======================================================================================================
 # selective forwarding hop (graph_step.GraphedForwardHop; definition: hilcodec_amd/forward.py; semantics: include/hilcodec_amd.h)
 # ======================================================================================================
 def _forward_arrivals(op, arrivals, n, m, frames):
@@ -2238,6 +2278,29 @@ def rate_charge(nbytes: Tensor, rows: Tensor, cfg, rtx_nbytes: Optional[Tensor] 
     for this hop's `nbytes` (int32 `[B]`, the packets as sent) and `rtx_nbytes` (int32 `[B, per_hop]`, optional: its retransmissions),
     down to a debt of cfg.burst_hops hops of the slot's rate."""
     _OPS.rate_charge(nbytes, rtx_nbytes, rows, int(cfg.burst_hops))
+
+
+def rx_bwe(arrivals: Tensor, offsets: Tensor, times: Tensor, rows: Tensor, caps: Tensor, due: Tensor, cfg, n: int, frames: int,
+           m: int = 0, order: Optional[int] = None, action: Optional[Tensor] = None) -> None:
+    """The estimating receiver's step after its jitter step (bwe.BweModel), in place: one hop's `arrivals` (int32 `[max_arrivals, 1 +
+    ceil(tb / 4)]` records grouped by slot, tb = wire.transport_bytes(n, m, frames)), `offsets` (int32 `[B + 1]`) and the records'
+    arrival ticks `times` (int32 `[max_arrivals]`, 1/24000 s mod 2^32), all read only -> `rows` (int32 `[B, bwe.BW_WORDS]`), `caps`
+    (uint8 `[B, 3]`: each slot's latest cap, wire.pack_cap, written when one is emitted) and `due` (int32 `[B]`: 1 where one was emitted
+    on this hop).  `cfg`: the bwe.BweConfig (bwe.bits checks it against `frames`); `order`: the comfort-noise order of the SIDs accepted
+    (None: a SID is malformed); `action` (int32 `[B]`, optional): the session row, a start clears the slot."""
+    lo, hi = bwe_bits(cfg, frames)
+    _OPS.rx_bwe(arrivals, offsets, times, action, rows, caps, due, int(n), int(m), int(frames), -1 if order is None else int(order), lo, hi,
+                int(cfg.window), int(cfg.rate_window), int(cfg.alpha_q8), int(cfg.beta_q8), cfg.increase(frames), int(cfg.interval),
+                int(cfg.reset_ticks))
+
+
+def rate_cap(rows: Tensor, rate_rows: Tensor, cfg, min_bits: int, max_bits: int, cap: Optional[Tensor] = None,
+             action: Optional[Tensor] = None, hold: Optional[Tensor] = None) -> None:
+    """The capped sender's step directly in front of rate_ceiling (bwe.CapModel), in place: `rows` (int32 `[B, bwe.CP_WORDS]`) take this
+    hop's `cap` words (int32 `[B]`, bwe.cap_word, 0: none; optional) and RC_RATE_Q8 of `rate_rows` (int32 `[B, rate.RC_WORDS]`) is kept
+    at or below the slot's cap.  `cfg`: the bwe.CapConfig; `min_bits` / `max_bits`: the bounds of the sender's rate (its rate.bucket);
+    `action` / `hold` (int32 `[B]`, optional): the session rows."""
+    _OPS.rate_cap(cap, action, hold, rows, rate_rows, int(min_bits), int(max_bits), int(cfg.timeout_hops))
 
 
 def forward_classify(arrivals: Tensor, offsets: Tensor, rows: Tensor, pick: Tensor, pick_count: Tensor, cfg, n: int, frames: int,

@@ -270,6 +270,28 @@ def nack_hops(base: int, bitmap: int) -> List[int]:
         raise ValueError(f"nack_hops: base = {base} or bitmap = {bitmap} outside [0, 65535]")
     return [base] + [(base + 1 + j) & 0xFFFF for j in range(16) if (bitmap >> j) & 1]
 
+
+# Rate cap (hilcodec_amd/bwe.py: GraphedDecodeHop(bwe=...) emits it, GraphedEncodeHop(cap=...) takes it): the receiver's delay-based
+# bandwidth estimate, feedback that travels beside the media, 3 bytes: a sequence number mod 256, then the most bits per hop the
+# sender should send, a big-endian uint16.
+CAP_BYTES = 3
+
+
+def pack_cap(seq: int, cap_bits: int) -> bytes:
+    """(seq, cap_bits): one byte, then two bytes big-endian; ValueError for a seq outside [0, 255] or a cap outside [0, 65535]"""
+    for name, v, top in (("seq", seq, 255), ("cap_bits", cap_bits, 0xFFFF)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= top:
+            raise ValueError(f"pack_cap: {name} = {v!r} outside [0, {top}]")
+    return bytes([int(seq), int(cap_bits) >> 8, int(cap_bits) & 0xFF])
+
+
+def parse_cap(blob) -> Tuple[int, int]:
+    """(seq, cap_bits) of a rate cap; ValueError unless it is exactly CAP_BYTES bytes"""
+    data = bytes(blob)
+    if len(data) != CAP_BYTES:
+        raise ValueError(f"a rate cap is {CAP_BYTES} bytes, got {len(data)}")
+    return data[0], (data[1] << 8) | data[2]
+
 # ---------------------------------------------------------------- caches
 def save_cache_npz(path: str, caches: Sequence[Tensor], prefix: str) -> None:
     """prefix 'e_in' (encoder, 22 tensors) or 'd_in' (decoder, 30)."""

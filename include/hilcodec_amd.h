@@ -42,7 +42,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream) with per-speaker levelling and a limiter int hilc_mix_gains(const float* wav, double* gains, double* power, const int* action, double gate2, double lo, double hi, double up, double down, double min_gain, double max_gain, double smooth, int B, int L, void* stream) and int hilc_mix_rooms_dyn(const float* wav, const int* room, const double* score, int top_k, const double* gains, double* limiter, double ceiling, double release, int sub, const int* action, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream); and the selective forwarding hop int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick, int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream) and int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers, const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec, void* stream); and its downlink control int hilc_downlink_store(const int* arrivals, int max_arrivals, const int* action, const int* pick, const int* pick_count, int* tags, int* ring, int* rows, int B, int T, int n_max, int m, int burst, int history, void* stream) and int hilc_downlink_step(const int* routes, const int* new_routes, const uint8_t* in, const int* in_nbytes, const int* layers, const int* action, const int* report, const int* nack_base, const int* nack_bitmap, const int* tags, const int* ring, int* rows, int* memory, int* eff_layers, uint8_t* out, int* out_nbytes, uint8_t* rtx_out, int* rtx_nbytes, int* rtx_routes, int B, int T, int n_max, int m, int fanout, int burst, int keep_fec, int history, int per_hop, int rate_on, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream); and the audio level with level-based speaker selection int hilc_audio_level(const float* x, const double* thr, const int* hold, int* level, int B, int L, void* stream) and int hilc_forward_rank(const int* sd, const int* loud, const int* room, const int* action, const int* shadow_prev, int* shadow, int* rows, int B, int fanout, int hang_hops, int floor_level, int attack_shift, int decay_q8, int margin_db, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream) with per-speaker levelling and a limiter int hilc_mix_gains(const float* wav, double* gains, double* power, const int* action, double gate2, double lo, double hi, double up, double down, double min_gain, double max_gain, double smooth, int B, int L, void* stream) and int hilc_mix_rooms_dyn(const float* wav, const int* room, const double* score, int top_k, const double* gains, double* limiter, double ceiling, double release, int sub, const int* action, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream); and the selective forwarding hop int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick, int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream) and int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers, const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec, void* stream); and its downlink control int hilc_downlink_store(const int* arrivals, int max_arrivals, const int* action, const int* pick, const int* pick_count, int* tags, int* ring, int* rows, int B, int T, int n_max, int m, int burst, int history, void* stream) and int hilc_downlink_step(const int* routes, const int* new_routes, const uint8_t* in, const int* in_nbytes, const int* layers, const int* action, const int* report, const int* nack_base, const int* nack_bitmap, const int* tags, const int* ring, int* rows, int* memory, int* eff_layers, uint8_t* out, int* out_nbytes, uint8_t* rtx_out, int* rtx_nbytes, int* rtx_routes, int B, int T, int n_max, int m, int fanout, int burst, int keep_fec, int history, int per_hop, int rate_on, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream); and the audio level with level-based speaker selection int hilc_audio_level(const float* x, const double* thr, const int* hold, int* level, int B, int L, void* stream) and int hilc_forward_rank(const int* sd, const int* loud, const int* room, const int* action, const int* shadow_prev, int* shadow, int* rows, int B, int fanout, int hang_hops, int floor_level, int attack_shift, int decay_q8, int margin_db, void* stream); and the delay-based bandwidth estimate int hilc_rx_bwe(const int* arrivals, const int* offsets, const int* times, int max_arrivals, const int* action, int* rows, uint8_t* caps, int* due, int B, int T, int n_max, int m, int order, int min_bits, int max_bits, int window, int rate_window, int alpha_q8, int beta_q8, int increase_q16, int interval, int reset_ticks, void* stream) and int hilc_rate_cap(const int* cap, const int* action, const int* hold, int* rows, int* rate_rows, int B, int min_bits, int max_bits, int timeout_hops, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -469,6 +469,7 @@ int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const fl
 #define HILC_WIRE_N_MASK 0x1F
 #define HILC_WIRE_REPORT_BYTES 3
 #define HILC_WIRE_NACK_BYTES 4
+#define HILC_WIRE_CAP_BYTES 3
 #define HILC_WIRE_CONCEAL_RUN 0
 #define HILC_WIRE_CONCEAL_HAS 1
 #define HILC_WIRE_CONCEAL_N 2
@@ -616,6 +617,78 @@ int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const fl
 #define HILC_RATE_RC_LIMITED 11
 #define HILC_RATE_RC_WORDS 12
 #define HILC_RATE_MAX_RATE_BITS (1 << 22)
+
+/* delay-based bandwidth estimate (hilcodec_amd/bwe.py).  Estimate row of a receiver slot, BW_WORDS words: BW_RATE_Q8 (the estimate, bits
+ * per hop x 256), BW_THR (the detector's adaptive threshold, Q16), BW_SEEN, BW_LAST_H, BW_LAST_T (the last sampled arrival: hop index and
+ * tick), BW_ACC, BW_SM (the accumulated delay in ticks, smoothed in Q8), BW_COUNT, BW_PREV_M, BW_OVER_TICKS, BW_OVER_COUNT, BW_SIGNAL
+ * (SIGNAL_*), BW_STATE (STATE_*), BW_PHASE, BW_SEQ (the cap's clock), BW_N, BW_HEAD, BW_RN, BW_RHEAD (the two rings' fill and next entry),
+ * the counters BW_SAMPLES .. BW_CAPS, then the trend ring at BW_TREND (MAX_WINDOW pairs tick, smoothed delay) and the rate ring at BW_RING
+ * (MAX_WINDOW pairs tick, bits).  Cap row of a sender slot, CP_WORDS words: CP_CAP_Q8, CP_SEEN, CP_LAST (seq), CP_AGE, then the counters
+ * CP_CAPS .. CP_CLAMPED.  A cap travels to the sender's graph as one word: CAP_PRESENT | seq << 16 | cap_bits, 0 for none. */
+#define HILC_BWE_BW_RATE_Q8 0
+#define HILC_BWE_BW_THR 1
+#define HILC_BWE_BW_SEEN 2
+#define HILC_BWE_BW_LAST_H 3
+#define HILC_BWE_BW_LAST_T 4
+#define HILC_BWE_BW_ACC 5
+#define HILC_BWE_BW_SM 6
+#define HILC_BWE_BW_COUNT 7
+#define HILC_BWE_BW_PREV_M 8
+#define HILC_BWE_BW_OVER_TICKS 9
+#define HILC_BWE_BW_OVER_COUNT 10
+#define HILC_BWE_BW_SIGNAL 11
+#define HILC_BWE_BW_STATE 12
+#define HILC_BWE_BW_PHASE 13
+#define HILC_BWE_BW_SEQ 14
+#define HILC_BWE_BW_N 15
+#define HILC_BWE_BW_HEAD 16
+#define HILC_BWE_BW_RN 17
+#define HILC_BWE_BW_RHEAD 18
+#define HILC_BWE_BW_SAMPLES 19
+#define HILC_BWE_BW_OLD 20
+#define HILC_BWE_BW_RESET 21
+#define HILC_BWE_BW_MALFORMED 22
+#define HILC_BWE_BW_OVERUSE 23
+#define HILC_BWE_BW_UNDERUSE 24
+#define HILC_BWE_BW_DECREASED 25
+#define HILC_BWE_BW_INCREASED 26
+#define HILC_BWE_BW_CAPS 27
+#define HILC_BWE_BW_TREND 28
+#define HILC_BWE_MAX_WINDOW 32
+#define HILC_BWE_BW_RING 92
+#define HILC_BWE_BW_WORDS 156
+#define HILC_BWE_HOP_TICKS 320
+#define HILC_BWE_SIGNAL_NORMAL 0
+#define HILC_BWE_SIGNAL_OVERUSE 1
+#define HILC_BWE_SIGNAL_UNDERUSE 2
+#define HILC_BWE_STATE_HOLD 0
+#define HILC_BWE_STATE_INCREASE 1
+#define HILC_BWE_THR_START (25 << 15)
+#define HILC_BWE_THR_MIN (6 << 16)
+#define HILC_BWE_THR_MAX (600 << 16)
+#define HILC_BWE_THR_SKIP (15 << 16)
+#define HILC_BWE_K_UP 6082
+#define HILC_BWE_K_DOWN 27263
+#define HILC_BWE_OVER_TICKS 240
+#define HILC_BWE_ADAPT_TICKS 2400
+#define HILC_BWE_COUNT_MAX 60
+#define HILC_BWE_RATE_MIN 4
+#define HILC_BWE_ACC_MAX (1 << 20)
+#define HILC_BWE_SLOPE_MAX (1 << 22)
+#define HILC_BWE_MAX_RESET_TICKS (1 << 17)
+#define HILC_BWE_MAX_FRAMES 1024
+#define HILC_BWE_MAX_ROW_BYTES (1 << 15)
+#define HILC_BWE_MAX_CAP_BITS 65535
+#define HILC_BWE_CP_CAP_Q8 0
+#define HILC_BWE_CP_SEEN 1
+#define HILC_BWE_CP_LAST 2
+#define HILC_BWE_CP_AGE 3
+#define HILC_BWE_CP_CAPS 4
+#define HILC_BWE_CP_STALE 5
+#define HILC_BWE_CP_TIMEOUT 6
+#define HILC_BWE_CP_CLAMPED 7
+#define HILC_BWE_CP_WORDS 8
+#define HILC_BWE_CAP_PRESENT (1 << 24)
 
 /* selective forwarding (hilcodec_amd/forward.py).  Sender row of a slot, SD_WORDS words: SD_HANG (the hops it stays active, 0: not
  * active), SD_SINCE (the hops it has been active, at most 65535), then the counters SD_CODES, SD_SIDS, SD_MALFORMED, SD_OVERFLOW.
@@ -1128,6 +1201,37 @@ int hilc_downlink_step(const int* routes, const int* new_routes, const uint8_t* 
 int hilc_audio_level(const float* x, const double* thr, const int* hold, int* level, int B, int L, void* stream);
 int hilc_forward_rank(const int* sd, const int* loud, const int* room, const int* action, const int* shadow_prev, int* shadow, int* rows,
                       int B, int fanout, int hang_hops, int floor_level, int attack_shift, int decay_q8, int margin_db, void* stream);
+
+/* ---- delay-based bandwidth estimate (additive under ABI 16) ------------------------------------------------------------------------
+ * Two entry points added WITHOUT a version bump, as the entry points above.  The definition, bit for bit, is hilcodec_amd/bwe.py.
+ * hilc_rx_bwe: the receiver's launch after hilc_jitter_step / hilc_jitter_adapt_step, beside hilc_rx_report and hilc_nack_build and
+ * independent of both.  arrivals, offsets, max_arrivals: one hop's arrivals in the form of hilc_jitter_step (read only); times int32
+ * [max_arrivals]: the arrival tick (1/24000 s, mod 2^32) of each arrival record; action optional int32 [B]; rows int32
+ * [B][HILC_BWE_BW_WORDS] (in place: HILC_BWE_BW_*); caps uint8 [B][HILC_WIRE_CAP_BYTES] (seq, then the cap in bits per hop as a big-endian
+ * uint16: written when one is emitted, zeroed by an action); due int32 [B] (every element written: 1 where a cap was emitted).  Per slot:
+ * action[b] != 0 clears the row (the estimate 256 max_bits, the threshold HILC_BWE_THR_START); each arrival that hilc_jitter_step's header
+ * check accepts and whose hop index is ahead of the last sampled one gives one delay sample d = int32(t - last t) - 320 T int16(h - last
+ * h), which goes through the accumulated and smoothed delay, the least-squares trend over the last `window` samples, the adaptive
+ * threshold and the over-use detector; the AIMD controller then lowers the estimate to beta_q8 / 256 of the measured incoming rate on an
+ * over-use, holds it on an under-use and raises it by increase_q16 / 65536 per hop index otherwise; every `interval` hops, and at once
+ * after a decrease, the slot's cap is emitted.  B >= 1, max_arrivals >= 0, 1 <= T <= HILC_BWE_MAX_FRAMES, 1 <= n_max <= 31, 0 <= m <= n_max,
+ * n_max + m <= HILC_WIRE_MAX_STAGES, -1 <= order <= HILC_DTX_MAX_ORDER, tb <= HILC_BWE_MAX_ROW_BYTES, 1 <= min_bits <= max_bits <=
+ * HILC_BWE_MAX_CAP_BITS, 2 <= window <= HILC_BWE_MAX_WINDOW, HILC_BWE_RATE_MIN <= rate_window <= HILC_BWE_MAX_WINDOW, 1 <= alpha_q8 <= 256,
+ * 1 <= beta_q8 <= 255, 0 <= increase_q16 <= 65535, 1 <= interval <= 1024, 1 <= reset_ticks <= HILC_BWE_MAX_RESET_TICKS (else
+ * HILC_ERR_SHAPE).  One thread per slot: a slot's arrivals are a sequence.
+ * hilc_rate_cap: the sender's launch directly in front of hilc_rate_ceiling.  cap optional int32 [B] (per slot 0, or HILC_BWE_CAP_PRESENT |
+ * seq << 16 | cap_bits); action, hold optional int32 [B]; rows int32 [B][HILC_BWE_CP_WORDS] (in place: HILC_BWE_CP_*); rate_rows int32
+ * [B][HILC_RATE_RC_WORDS] (in place: HILC_RATE_RC_RATE_Q8 only).  Per slot: action[b] != 0 clears the cap row; a cap is accepted by
+ * hilc_rate_ceiling's sequence rule (else stale) and stored as 256 clamp(cap_bits, min_bits, max_bits); a slot that is not held ages by
+ * one hop and at timeout_hops > 0 hops without an accepted cap forgets it; while it has one, the rate row's rate is at most the cap
+ * (counted clamped when that lowered it).  B >= 1, 1 <= min_bits <= max_bits <= HILC_RATE_MAX_RATE_BITS, timeout_hops >= 0 (else
+ * HILC_ERR_SHAPE).  One wave per slot.
+ * Both: NULL pointers (the optional rows excepted): HILC_ERR_NULL.  Integer only, no LDS, no atomics. */
+int hilc_rx_bwe(const int* arrivals, const int* offsets, const int* times, int max_arrivals, const int* action, int* rows, uint8_t* caps,
+                int* due, int B, int T, int n_max, int m, int order, int min_bits, int max_bits, int window, int rate_window, int alpha_q8,
+                int beta_q8, int increase_q16, int interval, int reset_ticks, void* stream);
+int hilc_rate_cap(const int* cap, const int* action, const int* hold, int* rows, int* rate_rows, int B, int min_bits, int max_bits,
+                  int timeout_hops, void* stream);
 
 #ifdef __cplusplus
 }
