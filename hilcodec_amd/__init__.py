@@ -16,5 +16,11 @@ from .graph_step import GraphedForwardHop  # noqa: F401
 # its downlink control (rate control and NACK answers per listener): the definition (import it by name) and the configuration
 from . import downlink  # noqa: F401
 from .downlink import DownlinkConfig  # noqa: F401
+# SRTP packet protection: the definition (import it by name), its configuration, and the two launches outside a graph, on any rows
+# and state (the graphed form: graph_step.GraphedEncodeHop(srtp=SrtpConfig()) / GraphedDecodeHop(srtp=SrtpConfig()))
+from . import srtp  # noqa: F401
+from .srtp import SrtpConfig  # noqa: F401
+from .ops import srtp_protect, srtp_unprotect  # noqa: F401
 
-__all__ = ["HILCodec", "Resampler", "resample", "MixConfig", "mix_rooms", "forward", "ForwardConfig", "GraphedForwardHop", "downlink", "DownlinkConfig"]
+__all__ = ["HILCodec", "Resampler", "resample", "MixConfig", "mix_rooms", "forward", "ForwardConfig", "GraphedForwardHop", "downlink", "DownlinkConfig",
+           "srtp", "SrtpConfig", "srtp_protect", "srtp_unprotect"]

@@ -101,6 +101,8 @@ SIGNATURES = {
     "hilc_forward_rank": [_p] * 7 + [_i] * 7 + [_p],
     "hilc_rx_bwe": [_p, _p, _p, _i, _p, _p, _p, _p] + [_i] * 14 + [_p],
     "hilc_rate_cap": [_p] * 5 + [_i] * 4 + [_p],
+    "hilc_srtp_protect": [_p] * 7 + [_i, _i, _p],
+    "hilc_srtp_unprotect": [_p, _p, _i, _p, _p, _p, _p, _i, _i, _p],
 }
 
 ABI_VERSION = 16

@@ -26,6 +26,7 @@ from torch import Tensor
 from . import dtx as dtx_def
 from . import audio_level as level_def
 from . import bwe as bwe_def
+from . import srtp as srtp_def
 from . import engine, ops, wire
 from . import downlink as downlink_def
 from . import forward as forward_def
@@ -324,6 +325,8 @@ class _Hop(_GraphPair):
     holding the CURRENT caches), the per-group concatenation of the caches, and the session front end (the queue is host-only and
     always exists; `sessions` gates the public methods and the graph's session kernels)."""
 
+    srtp = None                               # GraphedEncodeHop / GraphedDecodeHop(srtp=): the SrtpConfig
+
     def __init__(self, model, batch: int, n: int, device: torch.device, groups: int = 1, sessions: bool = False,
                  max_loads_per_hop: int = 4):
         super().__init__(batch, device)
@@ -408,6 +411,43 @@ class _Hop(_GraphPair):
         `n`: its number of quantiser stages (default: the graph's n).  At most `max_loads_per_hop` resumes per hop."""
         self._need_sessions("start")
         self.queue.start(slot, cache_enc, cache_dec, n)
+
+    # ---------------------------------------------------------------- SRTP keys (GraphedEncodeHop / GraphedDecodeHop with srtp=)
+    def _init_keys(self) -> None:
+        """per slot: the key rows the SRTP launch reads (srtp.KEY_*; device, captured by address) and their host table"""
+        self._keys = srtp_def.KeyTable(self.batch)
+        self._keys_dev = self._slot_state(srtp_def.KEY_WORDS)
+
+    def _send_keys(self) -> None:
+        """before a replay, on its stream: the key table, when it has changed since the last hop"""
+        if self.srtp is not None and self._keys.dirty:
+            self._keys_dev.copy_(torch.from_numpy(self._keys.rows))
+            self._keys.dirty = False
+
+    def _start_keyed(self, slot: int, queue_start) -> None:
+        """a start on an srtp hop: the header restarts SEQ at 0, so the slot needs a key set since its previous start (ValueError);
+        the key counts as used once the start is queued"""
+        if self.srtp is None:
+            return queue_start()
+        s = self.queue.slot(slot)
+        if not self._keys.fresh[s]:
+            self._keys.started(s)             # raises
+        queue_start()
+        self._keys.started(s)
+
+    def set_key(self, slot: int, master_key, master_salt, ssrc: Optional[int] = None, roc: int = 0) -> None:
+        """from the next hop on, slot `slot` protects / unprotects under the session keys derived (RFC 3711 4.3.1) from `master_key`
+        (16 bytes) and `master_salt` (14 bytes), with `ssrc` (default: the slot) in the counter blocks; a start of the slot begins
+        at rollover counter `roc` (a late joiner's receiver).  The key row is built on the host and goes up before the next replay.
+        ValueError: wrong lengths, a slot, ssrc or roc out of range, or a key the slot had before (its previous one, or one it was
+        started under since the last reset).  Keys never appear in a repr or an error message."""
+        self._need(self.srtp is not None, "set_key", "srtp=SrtpConfig()")
+        self._keys.set_key(self.queue.slot(slot), master_key, master_salt, ssrc, roc)
+
+    def clear_key(self, slot: int) -> None:
+        """from the next hop on, slot `slot` has no key: a sender slot sends nothing, a receiver slot rejects every arrival"""
+        self._need(self.srtp is not None, "clear_key", "srtp=SrtpConfig()")
+        self._keys.clear_key(self.queue.slot(slot))
 
     def stop(self, slot: int) -> None:
         """from the next step on, slot `slot` is held (does not advance) on every step until the next `start(slot, ...)`"""
@@ -821,13 +861,25 @@ class GraphedEncodeHop(GraphedHop):
     smaller of the loss-based rate and the receiver's estimate: the reports keep probing upward and handle the standing queue a delay
     gradient cannot see.  `cap_state` (int32 `[B, bwe.CP_WORDS]`) is a device view.  A `start` or a resume clears a slot's row inside
     the graph, `reset` every row; held and stopped slots take their caps but do not age; `export` and a resume carry none.  `cap=None`
-    captures exactly the graph without it."""
+    captures exactly the graph without it.
+    `srtp` = srtp.SrtpConfig() (needs `sessions` and `header`): packet protection, RFC 3711's AES_CM_128_HMAC_SHA1_80 (srtp.py: the
+    rules).  One hilc_srtp_protect behind hilc_packet_header, in front of hilc_rtx_step (the history holds ciphertext: a retransmission
+    is the packet that was sent, byte for byte) and of hilc_rate_charge (the bucket pays for the tag; hilc_rate_ceiling does not
+    anticipate the 10 bytes, the bucket absorbs them as it does retransmissions).  `step` returns rows `[B, wire.srtp_bytes(n, m,
+    T)]`: the 3 header bytes clear, the rest encrypted, a 10-byte tag; `rtx_packets` widens the same way; `srtp_state` (int32 `[B,
+    srtp.TX_WORDS]`) is a device view.  `set_key(slot, master_key, master_salt, ssrc=None, roc=0)` / `clear_key(slot)`: the key table is
+    built on the host and goes up before the next replay, only when it changed; a slot without a key sends nothing.  `start(slot)`
+    needs a `set_key(slot, ...)` since the slot's previous start (the header restarts at hop 0 and the same key would reuse its
+    keystream): ValueError otherwise, as for a `set_key` equal to the slot's previous one or to a key the slot was started under since
+    the last `reset`.  A `start` or a resume clears the slot's TX row inside the graph, `reset` every row and every key; `export` and a
+    resume carry no key and no row.  `srtp=None` captures exactly the graph without it."""
 
     def __init__(self, model, batch: int, hop: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
                  max_loads_per_hop: int = 4, input_rate: int = BASE_RATE, fec_stages: int = 0,
                  dtx: Optional[dtx_def.DtxConfig] = None, header: bool = False, vbr: Optional[vbr_def.VbrConfig] = None,
                  fec_adapt: Optional[report_def.FecAdaptConfig] = None, rtx: Optional[rtx_def.RtxConfig] = None,
-                 rate: Optional[rate_def.RateConfig] = None, audio_level: bool = False, cap: Optional[bwe_def.CapConfig] = None):
+                 rate: Optional[rate_def.RateConfig] = None, audio_level: bool = False, cap: Optional[bwe_def.CapConfig] = None,
+                 srtp: Optional[srtp_def.SrtpConfig] = None):
         # the options are checked and what they derive is set up first: GraphedHop's constructor allocates (_init_state) and captures
         self.fec_stages = _fec_stages(fec_stages, n)
         self.fec_adapt = _config_arg("fec_adapt", fec_adapt, report_def.FecAdaptConfig)
@@ -848,6 +900,8 @@ class GraphedEncodeHop(GraphedHop):
         self.cap = _config_arg("cap", cap, bwe_def.CapConfig)
         _needs("GraphedEncodeHop(cap=...)", cap is None or rate is not None, "rate=RateConfig(...): a cap is a ceiling of the rate")
         self._caps = {}                       # slot -> cap word for the next hop
+        self.srtp = _config_arg("srtp", srtp, srtp_def.SrtpConfig)
+        _needs("GraphedEncodeHop(srtp=...)", srtp is None or (sessions and self.header), "sessions=True and header=True")
         self._measure_level = bool(audio_level)
         self.frames = hop // HOP
         self.dtx = _config_arg("dtx", dtx, dtx_def.DtxConfig)
@@ -878,7 +932,9 @@ class GraphedEncodeHop(GraphedHop):
     def _init_state(self) -> None:
         n, m, T = self.n, self.fec_stages, self.frames
         self._prev = self._run = self._ctr = self._credit = self._fa = self._fec_on = self._rx = self._rc = self._n_ceil = self._level = None
-        self._cp = None
+        self._cp = self._tx = None
+        # the bytes of a sent row: the headed packet, with srtp its tag behind it
+        self._sent_bytes = wire.srtp_bytes(n, m, T) if self.srtp is not None else wire.transport_bytes(n, m, T)
         if m:
             # per parity, per slot: valid, then the first m stages x T frames of its last encoded hop (the hop of parity p reads
             # row p and writes row p ^ 1)
@@ -903,7 +959,7 @@ class GraphedEncodeHop(GraphedHop):
         if self.rtx is not None:
             # per slot: the history (tags and rows of headed packets, updated in place by hilc_rtx_step once per hop) and its counter
             # row; per parity: the retransmission rows and their byte counts
-            tb, history, per_hop = wire.transport_bytes(n, m, T), self.rtx.history, self.rtx.per_hop
+            tb, history, per_hop = self._sent_bytes, self.rtx.history, self.rtx.per_hop
             self._rx = (self._slot_state(history), self._slot_state(history, (tb + 3) // 4), self._slot_state(rtx_def.RX_WORDS))
             self._rx_out = self._slot_state(per_hop, tb, dtype=torch.uint8, pingpong=True)
             self._rx_nbytes = self._slot_state(per_hop, pingpong=True)
@@ -917,6 +973,11 @@ class GraphedEncodeHop(GraphedHop):
         if self.cap is not None:
             # per slot: the cap row (bwe.CP_*, updated in place by hilc_rate_cap once per hop)
             self._cp = self._slot_state(bwe_def.CP_WORDS)
+        if self.srtp is not None:
+            # per slot: the key row (srtp.KEY_*, uploaded when set_key / clear_key changed it) and the TX row (srtp.TX_*, updated in
+            # place by hilc_srtp_protect once per hop)
+            self._init_keys()
+            self._tx = self._slot_state(srtp_def.TX_WORDS)
         if self._measure_level:
             # per parity, per slot: the hop's level (the hop of parity p writes row p); cleared = silence
             self._level = self._slot_state(pingpong=True, cleared=level_def.MAX_LEVEL)
@@ -982,6 +1043,10 @@ class GraphedEncodeHop(GraphedHop):
         if self.header:
             packets, nbytes = ops.packet_header(packets, nbytes, self._ctr[p], self._ctr[p ^ 1], self.n, self.fec_stages, self.frames,
                                                 n_clip, kind, action, hold)
+        if self.srtp is not None:
+            # behind the header, in front of the history and the bill: the history holds ciphertext, so a retransmission is the packet
+            # that was sent byte for byte, and the bucket pays for the tag
+            packets, nbytes = ops.srtp_protect(packets, nbytes, self._keys_dev, self._tx, action=action)
         if self.rtx is not None:
             # the graph's last launch: this hop's headed packets enter the history, this hop's NACKs are answered from it
             ops.rtx_step(packets, nbytes, *self._rx, self._rx_out[p], self._rx_nbytes[p], self.stage.row["nack_base"],
@@ -1048,9 +1113,17 @@ class GraphedEncodeHop(GraphedHop):
         return self._cp
 
     @property
+    def srtp_state(self) -> Tensor:
+        """int32 `[B, srtp.TX_WORDS]` device view: each slot's TX row after the last hop (srtp.TX_*; srtp only).  Read-only: written
+        by the graph."""
+        self._need(self._tx is not None, "srtp_state", "srtp=SrtpConfig()")
+        return self._tx
+
+    @property
     def rtx_packets(self) -> Tensor:
-        """uint8 `[B, per_hop, wire.transport_bytes(n, m, T)]` device view: each slot's retransmissions of the last hop, in request
-        order, zero past their lengths (rtx only); overwritten by the next-but-one `step`.  Read-only: written by the graph."""
+        """uint8 `[B, per_hop, wire.transport_bytes(n, m, T)]` (with srtp: `wire.srtp_bytes(n, m, T)`) device view: each slot's
+        retransmissions of the last hop, in request order, zero past their lengths (rtx only); overwritten by the next-but-one
+        `step`.  Read-only: written by the graph."""
         self._need(self.rtx is not None, "rtx_packets", "rtx=RtxConfig(...)")
         return self._rx_out[self.parity ^ 1]
 
@@ -1146,6 +1219,8 @@ class GraphedEncodeHop(GraphedHop):
 
     def reset(self, cache_enc: Optional[Sequence[Tensor]] = None, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
         self._reports, self._nacks, self._caps = {}, {}, {}
+        if self.srtp is not None:
+            self._keys.reset()                # every key and, with the scratch rows, every TX row
         super().reset(cache_enc, cache_dec)
 
     def step(self, x: Tensor, hold=None, reports=None, nacks=None, caps=None) -> Tuple[Tensor, Tensor]:
@@ -1155,6 +1230,7 @@ class GraphedEncodeHop(GraphedHop):
         self._reports = self._report_words(reports)
         self._nacks = self._nack_words(nacks)
         self._caps = self._cap_words(caps)
+        self._send_keys()
         try:
             out = super().step(x, hold)
         finally:
@@ -1168,8 +1244,9 @@ class GraphedEncodeHop(GraphedHop):
 
     def start(self, slot: int, cache_enc: Optional[Sequence[Tensor]] = None, n: Optional[int] = None) -> None:
         """At the next step, slot `slot` begins a fresh stream or resumes one from its 22 encoder caches (B = 1 tensors, host or
-        device; 23 with `input_rate`, the resampler's history last); `n`: its number of quantiser stages (default: the graph's n)"""
-        super().start(slot, cache_enc, None, n)
+        device; 23 with `input_rate`, the resampler's history last); `n`: its number of quantiser stages (default: the graph's n).
+        With `srtp`: ValueError unless `set_key(slot, ...)` was called since the slot's previous start"""
+        self._start_keyed(slot, lambda: _Hop.start(self, slot, cache_enc, None, n))
 
     def export(self, slot: int) -> List[Tensor]:
         """the current 22 encoder caches of slot `slot` as B = 1 device tensors (23 with `input_rate`: the resampler's history last)"""
@@ -1280,6 +1357,14 @@ class GraphedDecodeHop(_Hop):
     bwe.BW_WORDS]`; `bwe.kbps(bwe_state, frames)` on the host) are device views.  The caps go to the sender:
     GraphedEncodeHop(cap=...).step(caps=).  It only observes: wav, caches and every other state are those of the receiver without it.
     A `start` or a resume clears a slot's row, cap and flag inside the graph; `export` and a resume carry none.  `bwe=None` captures
+    exactly the graph without it, with today's stage layout and upload.
+    `srtp` = srtp.SrtpConfig() (needs `jitter`): packet protection, the receiving side (srtp.py: the rules).  `play()` takes protected
+    rows of `wire.srtp_bytes(n, m, frames)` bytes and the stage's arrival region is sized for them; hilc_srtp_unprotect is the graph's
+    first launch and writes the plain records (a device-only buffer of the plain width) that every later launch reads: the jitter step
+    and hilc_rx_bwe are handed that buffer and are otherwise what they were.  An arrival that is too short, a replay (64-packet window)
+    or fails its tag comes out as a record of 0 bytes, which the jitter step and `bwe` drop as malformed; `bwe` therefore measures the
+    plain sizes, 80 bits per packet under the wire.  `srtp_state` (int32 `[B, srtp.RX_WORDS]`) is a device view.  `set_key`, `clear_key`
+    and the fresh-key rule of `start` are the sender's; `roc` starts a late joiner at a known rollover counter.  `srtp=None` captures
     exactly the graph without it, with today's stage layout and upload."""
 
     def __init__(self, model, batch: int, frames: int, n: int, device: torch.device, warmup: int = 2, sessions: bool = False,
@@ -1287,7 +1372,7 @@ class GraphedDecodeHop(_Hop):
                  fec_stages: int = 0, cng_order: Optional[int] = None, jitter: Optional[JitterConfig] = None,
                  max_arrivals: Optional[int] = None, mix: Optional[MixConfig] = None,
                  report: Optional[report_def.ReportConfig] = None, nack: Optional[rtx_def.NackConfig] = None,
-                 bwe: Optional[bwe_def.BweConfig] = None):
+                 bwe: Optional[bwe_def.BweConfig] = None, srtp: Optional[srtp_def.SrtpConfig] = None):
         self.batch, self.frames = int(batch), int(frames)
         self.output_rate = int(output_rate)
         self.rs, self._history = None, 0
@@ -1325,6 +1410,11 @@ class GraphedDecodeHop(_Hop):
             bwe_def.bits(bwe, self.frames)                              # ValueError: bounds past a uint16 cap, too many frames
             if wire.transport_bytes(int(n), self.fec_stages, self.frames) > bwe_def.MAX_ROW_BYTES:
                 raise ValueError(f"GraphedDecodeHop(bwe=...): a headed packet of more than {bwe_def.MAX_ROW_BYTES} bytes")
+        self.srtp = _config_arg("srtp", srtp, srtp_def.SrtpConfig)
+        _needs("GraphedDecodeHop(srtp=...)", jitter is not None or srtp is None,
+               "jitter=JitterConfig(...): play()'s arrivals are what is unprotected")
+        if srtp is not None and wire.transport_bytes(int(n), self.fec_stages, self.frames) > srtp_def.MAX_ROW_BYTES:
+            raise ValueError(f"GraphedDecodeHop(srtp=...): a headed packet of more than {srtp_def.MAX_ROW_BYTES} bytes")
         super().__init__(model, self.batch, int(n), device, 1, sessions, max_loads_per_hop)
         self.stride = wire.packet_bytes(self.n + self.fec_stages, self.frames)
         B = self.batch
@@ -1415,6 +1505,10 @@ class GraphedDecodeHop(_Hop):
     def _hop(self, p: int) -> Tensor:
         m = self.model
         src, dst = self.state[p], self.state[p ^ 1]
+        if self.srtp is not None:
+            # the graph's first launch: the protected arrivals become the plain records of the jitter step and the estimate
+            ops.srtp_unprotect(self._wire_arrivals, self.offsets, self._keys_dev, self._rxs, self.tstride, plain=self.arrivals,
+                               action=self.action)
         if self.jitter is not None and self.jitter.adapt is not None:
             ops.jitter_adapt_step(self.arrivals, self.offsets, self.hold, self.n_slot, self.packets, self._jstate, self._jmeta,
                                   self._jring, self._jadapt, self.n, self.fec_stages, self.frames, self.cng_order, self.jitter,
@@ -1607,8 +1701,18 @@ class GraphedDecodeHop(_Hop):
         # ONE device buffer, captured by address, uploaded up to the last arrival used: action per slot, the host's holds
         # (hilc_jitter_step adds its own), the arrival region (an arrival record: byte count, then the headed packet), the staged
         # records.  The n, lost and fec rows and the packet matrix are written by hilc_jitter_step and are never uploaded.
-        st = self.stage = self._new_stage(("action", "hold"), arrivals=(self.max_arrivals, self.tstride), times=self.bwe is not None)
+        # with srtp the arrivals are protected packets, 10 bytes wider; hilc_srtp_unprotect writes the plain records every later launch
+        # reads into a device-only buffer of the width they check
+        self.wstride = self.tstride + (wire.SRTP_TAG_BYTES if self.srtp is not None else 0)
+        st = self.stage = self._new_stage(("action", "hold"), arrivals=(self.max_arrivals, self.wstride), times=self.bwe is not None)
         self.offsets, self.arrivals = st.offsets, st.arrivals
+        self._wire_arrivals = None
+        if self.srtp is not None:
+            self._wire_arrivals = st.arrivals
+            self.arrivals = torch.zeros(self.max_arrivals, 1 + (self.tstride + 3) // 4, dtype=torch.int32, device=dev)
+            # per slot: the key row (srtp.KEY_*) and the RX row (srtp.RX_*, updated in place by hilc_srtp_unprotect once per hop)
+            self._init_keys()
+            self._rxs = self._slot_state(srtp_def.RX_WORDS)
         rows = torch.zeros(3, B, dtype=torch.int32, device=dev)
         self.n_slot = rows[0]
         self.lost = rows[1] if self.conceal else None
@@ -1678,6 +1782,13 @@ class GraphedDecodeHop(_Hop):
         return self._nk
 
     @property
+    def srtp_state(self) -> Tensor:
+        """int32 `[B, srtp.RX_WORDS]` device view: each slot's RX row after the last play (srtp.RX_*; srtp only).  Read-only: written
+        by the graph."""
+        self._need(self.srtp is not None, "srtp_state", "srtp=SrtpConfig()")
+        return self._rxs
+
+    @property
     def caps(self) -> Tensor:
         """uint8 `[B, 3]` device view: each slot's latest rate cap (wire.parse_cap; zeros before its first), unchanged between caps.
         Read-only: written by the graph."""
@@ -1724,13 +1835,13 @@ class GraphedDecodeHop(_Hop):
 
     def play(self, slots, packets: Tensor, nbytes, hold=None, times=None) -> Tensor:
         """one hop of a jitter receiver: this hop's arrivals, in push order — `slots` and `nbytes` (A host ints), `packets` uint8
-        `[A, wire.transport_bytes(n, m, frames)]` (host or device) — and `hold`: slots (host ints) held on this hop (playout
-        pauses).  `times` (with `bwe` only, then required whenever A > 0): the arrivals' ticks, A host ints in units of 1/24000 s
-        (ValueError for a device tensor or another length).  Returns the hop's waveform, a static view that the next-but-one call
-        overwrites."""
+        `[A, wire.transport_bytes(n, m, frames)]` (with srtp: `wire.srtp_bytes(n, m, frames)`; host or device) — and `hold`: slots
+        (host ints) held on this hop (playout pauses).  `times` (with `bwe` only, then required whenever A > 0): the arrivals'
+        ticks, A host ints in units of 1/24000 s (ValueError for a device tensor or another length).  Returns the hop's waveform,
+        a static view that the next-but-one call overwrites."""
         self._need(self.jitter is not None, "play", "jitter=JitterConfig(...)")
         held = set(self._hold_slots(hold)) | self.queue.stops
-        arr = check_arrivals("play", slots, packets, nbytes, self.batch, self.max_arrivals, self.tstride)
+        arr = check_arrivals("play", slots, packets, nbytes, self.batch, self.max_arrivals, self.wstride)
         ticks = self._arrival_times(times, arr)
         st, q = self.stage, self.queue
         st.wait()
@@ -1740,13 +1851,15 @@ class GraphedDecodeHop(_Hop):
         st.send_arrivals(arr, packets, ticks)
         st.finish(host_records_apart=True)
         self._send_rooms()
+        self._send_keys()
         return self._replay()
 
     def start(self, slot: int, cache_dec: Optional[Sequence[Tensor]] = None) -> None:
         """At the next step, slot `slot` begins a fresh stream (zero caches) or resumes one from its 30 decoder caches (B = 1
         tensors, host or device; 31 with `output_rate`, the resampler's history last); at most `max_loads_per_hop` resumes per hop.
-        With `jitter`, its jitter state (and its adapt row) is cleared on that hop"""
-        super().start(slot, None, cache_dec)
+        With `jitter`, its jitter state (and its adapt row) is cleared on that hop.  With `srtp`: ValueError unless `set_key(slot,
+        ...)` was called since the slot's previous start"""
+        self._start_keyed(slot, lambda: _Hop.start(self, slot, None, cache_dec))
 
     def export(self, slot: int) -> List[Tensor]:
         """the current 30 decoder caches of slot `slot` as B = 1 device tensors (one gather launch; a stopped slot: its caches

@@ -35,8 +35,11 @@ from .jitter import AD_WORDS, ST_WORDS
 from .report import FA_WORDS, RP_WORDS
 from .rate import RC_WORDS, bucket
 from .rtx import NK_WORDS, RX_WORDS
+from .srtp import KEY_WORDS as SRTP_KEY_WORDS
+from .srtp import RX_WORDS as SRTP_RX_WORDS
+from .srtp import TX_WORDS as SRTP_TX_WORDS
 from .resample import HOP
-from .wire import CAP_BYTES, CONCEAL_CODES, NACK_BYTES, REPORT_BYTES, TRANSPORT_HEADER, packet_bytes
+from .wire import CAP_BYTES, CONCEAL_CODES, NACK_BYTES, REPORT_BYTES, SRTP_TAG_BYTES, TRANSPORT_HEADER, packet_bytes
 
 _LIB = torch.library.Library("hilcodec", "DEF")
 
@@ -1378,6 +1381,44 @@ _register("rate_cap", "(Tensor? cap, Tensor? action, Tensor? hold, Tensor(a!) ro
           "int timeout_hops) -> ()", _rate_cap, lambda cap, action, hold, rows, rate_rows, min_bits, max_bits, timeout_hops: None)
 
 # ======================================================================================================
+# SRTP packet protection (graph_step.GraphedEncodeHop(srtp=) / GraphedDecodeHop(srtp=); definition: hilcodec_amd/srtp.py; semantics:
+# include/hilcodec_amd.h)
+# ======================================================================================================
+def _srtp_protect(packets, nbytes, keys, rows, action, out, out_nbytes):
+    if packets.dim() != 2:
+        raise RuntimeError("srtp_protect: packets must be [B, row_bytes]")
+    B, tb = packets.shape
+    if nbytes.numel() != B or keys.shape != (B, SRTP_KEY_WORDS) or rows.shape != (B, SRTP_TX_WORDS) or \
+            out.shape != (B, tb + SRTP_TAG_BYTES) or out_nbytes.numel() != B:
+        raise RuntimeError(f"srtp_protect: nbytes must be [{B}], keys [{B}, {SRTP_KEY_WORDS}], rows [{B}, {SRTP_TX_WORDS}], "
+                           f"out [{B}, {tb + SRTP_TAG_BYTES}] and out_nbytes [{B}]")
+    _rows("srtp_protect", B, action=action)
+    check(lib.hilc_srtp_protect(_ptr(packets, torch.uint8), _ptr(nbytes, torch.int32), _ptr(keys, torch.int32), _ptr(rows, torch.int32),
+                                _ptr(action, torch.int32), _ptr(out, torch.uint8), _ptr(out_nbytes, torch.int32), B, tb, _stream()),
+          "hilc_srtp_protect")
+
+
+_register("srtp_protect", "(Tensor packets, Tensor nbytes, Tensor keys, Tensor(a!) rows, Tensor? action, Tensor(b!) out, "
+          "Tensor(c!) out_nbytes) -> ()", _srtp_protect, lambda packets, nbytes, keys, rows, action, out, out_nbytes: None)
+
+
+def _srtp_unprotect(arrivals, offsets, keys, rows, action, plain, row_bytes):
+    B = rows.shape[0]
+    pw, aw = (row_bytes + SRTP_TAG_BYTES + 3) // 4, (row_bytes + 3) // 4
+    if arrivals.dim() != 2 or arrivals.shape[1] != 1 + pw or offsets.numel() != B + 1 or plain.shape != (arrivals.shape[0], 1 + aw):
+        raise RuntimeError(f"srtp_unprotect: arrivals must be [A, {1 + pw}], offsets [{B + 1}] and plain [A, {1 + aw}]")
+    if keys.shape != (B, SRTP_KEY_WORDS) or rows.shape != (B, SRTP_RX_WORDS):
+        raise RuntimeError(f"srtp_unprotect: keys must be [{B}, {SRTP_KEY_WORDS}] and rows [{B}, {SRTP_RX_WORDS}]")
+    _rows("srtp_unprotect", B, action=action)
+    check(lib.hilc_srtp_unprotect(_ptr(arrivals, torch.int32), _ptr(offsets, torch.int32), arrivals.shape[0], _ptr(keys, torch.int32),
+                                  _ptr(rows, torch.int32), _ptr(action, torch.int32), _ptr(plain, torch.int32), B, row_bytes, _stream()),
+          "hilc_srtp_unprotect")
+
+
+_register("srtp_unprotect", "(Tensor arrivals, Tensor offsets, Tensor keys, Tensor(a!) rows, Tensor? action, Tensor(b!) plain, "
+          "int row_bytes) -> ()", _srtp_unprotect, lambda arrivals, offsets, keys, rows, action, plain, row_bytes: None)
+
+# ======================================================================================================
 # selective forwarding hop (graph_step.GraphedForwardHop; definition: hilcodec_amd/forward.py; semantics: include/hilcodec_amd.h)
 # ======================================================================================================
 def _forward_arrivals(op, arrivals, n, m, frames):
@@ -2301,6 +2342,37 @@ def rate_cap(rows: Tensor, rate_rows: Tensor, cfg, min_bits: int, max_bits: int,
     at or below the slot's cap.  `cfg`: the bwe.CapConfig; `min_bits` / `max_bits`: the bounds of the sender's rate (its rate.bucket);
     `action` / `hold` (int32 `[B]`, optional): the session rows."""
     _OPS.rate_cap(cap, action, hold, rows, rate_rows, int(min_bits), int(max_bits), int(cfg.timeout_hops))
+
+
+def srtp_protect(packets: Tensor, nbytes: Tensor, keys: Tensor, rows: Tensor, out: Optional[Tensor] = None,
+                 out_nbytes: Optional[Tensor] = None, action: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """The protecting sender's step behind packet_header (srtp.SenderModel), outside a graph on any rows and state: `packets` (uint8
+    `[B, row_bytes]`) and `nbytes` (int32 `[B]`), read only, under `keys` (int32 `[B, srtp.KEY_WORDS]`, srtp.key_row per slot, zero: no
+    key) and the TX `rows` (int32 `[B, srtp.TX_WORDS]`, in place) -> (`out` uint8 `[B, row_bytes + 10]`, `out_nbytes` int32 `[B]`),
+    allocated when not given.  `action` (int32 `[B]`, optional): the session row, a start clears the slot's row.  A byte tensor may be
+    any contiguous view: rows that are not word-aligned are read and written byte by byte."""
+    if packets.dim() != 2:
+        raise RuntimeError("srtp_protect: packets must be [B, row_bytes]")
+    B, tb = packets.shape
+    if out is None:
+        out = _new(packets, B, tb + SRTP_TAG_BYTES, dtype=torch.uint8)
+    if out_nbytes is None:
+        out_nbytes = _new(packets, B, dtype=torch.int32)
+    _OPS.srtp_protect(packets, nbytes, keys, rows, action, out, out_nbytes)
+    return out, out_nbytes
+
+
+def srtp_unprotect(arrivals: Tensor, offsets: Tensor, keys: Tensor, rows: Tensor, row_bytes: int, plain: Optional[Tensor] = None,
+                   action: Optional[Tensor] = None) -> Tensor:
+    """The protected receiver's step in front of its jitter step (srtp.ReceiverModel), outside a graph on any rows and state: one hop's
+    protected `arrivals` (int32 `[max_arrivals, 1 + ceil((row_bytes + 10) / 4)]` records grouped by slot) and `offsets` (int32 `[B +
+    1]`), read only, under `keys` (int32 `[B, srtp.KEY_WORDS]`) and the RX `rows` (int32 `[B, srtp.RX_WORDS]`, in place) -> `plain`
+    (int32 `[max_arrivals, 1 + ceil(row_bytes / 4)]`, zeros when not given): the records jitter_step takes, a rejected arrival as a
+    record of 0 bytes; records outside every slot's range are left as they are.  `row_bytes`: wire.transport_bytes(n, m, frames)."""
+    if plain is None:
+        plain = torch.zeros(arrivals.shape[0], 1 + (int(row_bytes) + 3) // 4, device=arrivals.device, dtype=torch.int32)
+    _OPS.srtp_unprotect(arrivals, offsets, keys, rows, action, plain, int(row_bytes))
+    return plain
 
 
 def forward_classify(arrivals: Tensor, offsets: Tensor, rows: Tensor, pick: Tensor, pick_count: Tensor, cfg, n: int, frames: int,

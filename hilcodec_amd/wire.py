@@ -292,6 +292,16 @@ def parse_cap(blob) -> Tuple[int, int]:
         raise ValueError(f"a rate cap is {CAP_BYTES} bytes, got {len(data)}")
     return data[0], (data[1] << 8) | data[2]
 
+
+# Packet protection (hilcodec_amd/srtp.py: GraphedEncodeHop(srtp=...) / GraphedDecodeHop(srtp=...)): a protected packet is the headed
+# packet with its first 3 bytes clear, the rest encrypted, and an authentication tag of 10 bytes behind it.
+SRTP_TAG_BYTES = 10
+
+
+def srtp_bytes(n: int, m: int, T: int) -> int:
+    """the widest protected packet of a sender with n stages, m redundant ones and T frames"""
+    return transport_bytes(n, m, T) + SRTP_TAG_BYTES
+
 # ---------------------------------------------------------------- caches
 def save_cache_npz(path: str, caches: Sequence[Tensor], prefix: str) -> None:
     """prefix 'e_in' (encoder, 22 tensors) or 'd_in' (decoder, 30)."""

@@ -42,7 +42,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream) with per-speaker levelling and a limiter int hilc_mix_gains(const float* wav, double* gains, double* power, const int* action, double gate2, double lo, double hi, double up, double down, double min_gain, double max_gain, double smooth, int B, int L, void* stream) and int hilc_mix_rooms_dyn(const float* wav, const int* room, const double* score, int top_k, const double* gains, double* limiter, double ceiling, double release, int sub, const int* action, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream); and the selective forwarding hop int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick, int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream) and int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers, const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec, void* stream); and its downlink control int hilc_downlink_store(const int* arrivals, int max_arrivals, const int* action, const int* pick, const int* pick_count, int* tags, int* ring, int* rows, int B, int T, int n_max, int m, int burst, int history, void* stream) and int hilc_downlink_step(const int* routes, const int* new_routes, const uint8_t* in, const int* in_nbytes, const int* layers, const int* action, const int* report, const int* nack_base, const int* nack_bitmap, const int* tags, const int* ring, int* rows, int* memory, int* eff_layers, uint8_t* out, int* out_nbytes, uint8_t* rtx_out, int* rtx_nbytes, int* rtx_routes, int B, int T, int n_max, int m, int fanout, int burst, int keep_fec, int history, int per_hop, int rate_on, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream); and the audio level with level-based speaker selection int hilc_audio_level(const float* x, const double* thr, const int* hold, int* level, int B, int L, void* stream) and int hilc_forward_rank(const int* sd, const int* loud, const int* room, const int* action, const int* shadow_prev, int* shadow, int* rows, int B, int fanout, int hang_hops, int floor_level, int attack_shift, int decay_q8, int margin_db, void* stream); and the delay-based bandwidth estimate int hilc_rx_bwe(const int* arrivals, const int* offsets, const int* times, int max_arrivals, const int* action, int* rows, uint8_t* caps, int* due, int B, int T, int n_max, int m, int order, int min_bits, int max_bits, int window, int rate_window, int alpha_q8, int beta_q8, int increase_q16, int interval, int reset_ticks, void* stream) and int hilc_rate_cap(const int* cap, const int* action, const int* hold, int* rows, int* rate_rows, int B, int min_bits, int max_bits, int timeout_hops, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream) with per-speaker levelling and a limiter int hilc_mix_gains(const float* wav, double* gains, double* power, const int* action, double gate2, double lo, double hi, double up, double down, double min_gain, double max_gain, double smooth, int B, int L, void* stream) and int hilc_mix_rooms_dyn(const float* wav, const int* room, const double* score, int top_k, const double* gains, double* limiter, double ceiling, double release, int sub, const int* action, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream); and the selective forwarding hop int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick, int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream) and int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers, const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec, void* stream); and its downlink control int hilc_downlink_store(const int* arrivals, int max_arrivals, const int* action, const int* pick, const int* pick_count, int* tags, int* ring, int* rows, int B, int T, int n_max, int m, int burst, int history, void* stream) and int hilc_downlink_step(const int* routes, const int* new_routes, const uint8_t* in, const int* in_nbytes, const int* layers, const int* action, const int* report, const int* nack_base, const int* nack_bitmap, const int* tags, const int* ring, int* rows, int* memory, int* eff_layers, uint8_t* out, int* out_nbytes, uint8_t* rtx_out, int* rtx_nbytes, int* rtx_routes, int B, int T, int n_max, int m, int fanout, int burst, int keep_fec, int history, int per_hop, int rate_on, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream); and the audio level with level-based speaker selection int hilc_audio_level(const float* x, const double* thr, const int* hold, int* level, int B, int L, void* stream) and int hilc_forward_rank(const int* sd, const int* loud, const int* room, const int* action, const int* shadow_prev, int* shadow, int* rows, int B, int fanout, int hang_hops, int floor_level, int attack_shift, int decay_q8, int margin_db, void* stream); and the delay-based bandwidth estimate int hilc_rx_bwe(const int* arrivals, const int* offsets, const int* times, int max_arrivals, const int* action, int* rows, uint8_t* caps, int* due, int B, int T, int n_max, int m, int order, int min_bits, int max_bits, int window, int rate_window, int alpha_q8, int beta_q8, int increase_q16, int interval, int reset_ticks, void* stream) and int hilc_rate_cap(const int* cap, const int* action, const int* hold, int* rows, int* rate_rows, int B, int min_bits, int max_bits, int timeout_hops, void* stream); and SRTP packet protection int hilc_srtp_protect(const uint8_t* packets, const int* nbytes, const int* keys, int* rows, const int* action, uint8_t* out, int* out_nbytes, int B, int row_bytes, void* stream) and int hilc_srtp_unprotect(const int* arrivals, const int* offsets, int max_arrivals, const int* keys, int* rows, const int* action, int* plain, int B, int row_bytes, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -470,6 +470,7 @@ int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const fl
 #define HILC_WIRE_REPORT_BYTES 3
 #define HILC_WIRE_NACK_BYTES 4
 #define HILC_WIRE_CAP_BYTES 3
+#define HILC_WIRE_SRTP_TAG_BYTES 10
 #define HILC_WIRE_CONCEAL_RUN 0
 #define HILC_WIRE_CONCEAL_HAS 1
 #define HILC_WIRE_CONCEAL_N 2
@@ -689,6 +690,41 @@ int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const fl
 #define HILC_BWE_CP_CLAMPED 7
 #define HILC_BWE_CP_WORDS 8
 #define HILC_BWE_CAP_PRESENT (1 << 24)
+
+/* SRTP packet protection (hilcodec_amd/srtp.py), RFC 3711's AES_CM_128_HMAC_SHA1_80.  Key row of a slot, KEY_WORDS words, every word a
+ * big-endian uint32 held in an int32: KEY_VALID (1: the slot has a key), KEY_SSRC, KEY_ROC (the rollover counter a start gives the slot's
+ * row), the 44 AES round-key words of the session encryption key from KEY_RK, the 14-byte session salt and 2 zero bytes as 4 words from
+ * KEY_SALT, and the HMAC-SHA1 midstates after the blocks k_a ^ ipad and k_a ^ opad, 5 words each, from KEY_INNER and KEY_OUTER.  Sender
+ * row, TX_WORDS words: TX_ROC, TX_LAST (the last SEQ sent), TX_SENT, then the counters TX_PROTECTED, TX_NOKEY.  Receiver row, RX_WORDS
+ * words: RX_ROC, RX_SL (the highest authenticated SEQ), RX_SEEN, RX_WIN_LO, RX_WIN_HI (the 64-packet replay window: bit k is the packet k
+ * below the highest authenticated index), then the counters RX_OK, RX_AUTH_FAIL, RX_REPLAY, RX_SHORT, RX_NOKEY. */
+#define HILC_SRTP_KEY_VALID 0
+#define HILC_SRTP_KEY_SSRC 1
+#define HILC_SRTP_KEY_ROC 2
+#define HILC_SRTP_KEY_RK 3
+#define HILC_SRTP_KEY_SALT 47
+#define HILC_SRTP_KEY_INNER 51
+#define HILC_SRTP_KEY_OUTER 56
+#define HILC_SRTP_KEY_WORDS 61
+#define HILC_SRTP_TX_ROC 0
+#define HILC_SRTP_TX_LAST 1
+#define HILC_SRTP_TX_SENT 2
+#define HILC_SRTP_TX_PROTECTED 3
+#define HILC_SRTP_TX_NOKEY 4
+#define HILC_SRTP_TX_WORDS 5
+#define HILC_SRTP_RX_ROC 0
+#define HILC_SRTP_RX_SL 1
+#define HILC_SRTP_RX_SEEN 2
+#define HILC_SRTP_RX_WIN_LO 3
+#define HILC_SRTP_RX_WIN_HI 4
+#define HILC_SRTP_RX_OK 5
+#define HILC_SRTP_RX_AUTH_FAIL 6
+#define HILC_SRTP_RX_REPLAY 7
+#define HILC_SRTP_RX_SHORT 8
+#define HILC_SRTP_RX_NOKEY 9
+#define HILC_SRTP_RX_WORDS 10
+#define HILC_SRTP_WINDOW 64
+#define HILC_SRTP_MAX_ROW_BYTES (1 << 15)
 
 /* selective forwarding (hilcodec_amd/forward.py).  Sender row of a slot, SD_WORDS words: SD_HANG (the hops it stays active, 0: not
  * active), SD_SINCE (the hops it has been active, at most 65535), then the counters SD_CODES, SD_SIDS, SD_MALFORMED, SD_OVERFLOW.
@@ -1232,6 +1268,39 @@ int hilc_rx_bwe(const int* arrivals, const int* offsets, const int* times, int m
                 int beta_q8, int increase_q16, int interval, int reset_ticks, void* stream);
 int hilc_rate_cap(const int* cap, const int* action, const int* hold, int* rows, int* rate_rows, int B, int min_bits, int max_bits,
                   int timeout_hops, void* stream);
+
+/* ---- SRTP packet protection (additive under ABI 16) ---------------------------------------------------------------------------------
+ * Two entry points added WITHOUT a version bump, as the entry points above.  The definition, bit for bit, is hilcodec_amd/srtp.py; the
+ * transform is AES_CM_128_HMAC_SHA1_80 of RFC 3711.  A protected packet is a headed packet (hilc_packet_header) whose first
+ * HILC_WIRE_TRANSPORT_HEADER bytes stay clear, whose other bytes are XORed with the AES-128 counter-mode keystream from keystream byte 0
+ * (RFC 3711 4.1.1: counter block j = ((k_s 2^16) ^ (SSRC 2^64) ^ (i 2^16)) + j, i = ROC 2^16 + SEQ, SEQ the header's hop index, 3.3.1)
+ * and that carries HILC_WIRE_SRTP_TAG_BYTES tag bytes behind it: the first 10 bytes of HMAC-SHA1 over header, ciphertext and the ROC
+ * as 4 bytes big-endian (4.2).  keys int32 [B][HILC_SRTP_KEY_WORDS] (read only, built on the host: key derivation 4.3.1 with kdr = 0, the
+ * AES key expansion and the two HMAC pad blocks are done there); action optional int32 [B]: action[b] != 0 clears the slot's row and sets
+ * its ROC to the key row's KEY_ROC (0 without a valid key).
+ * hilc_srtp_protect: the sender's launch behind hilc_packet_header, in front of hilc_rtx_step and hilc_rate_charge.  packets uint8
+ * [B][row_bytes] and nbytes int32 [B] (read only); rows int32 [B][HILC_SRTP_TX_WORDS] (in place); out uint8 [B][row_bytes +
+ * HILC_WIRE_SRTP_TAG_BYTES] and out_nbytes int32 [B] (every element written).  Per slot, nb = min(nbytes, row_bytes): nb <
+ * HILC_WIRE_TRANSPORT_HEADER (nothing sent) leaves the row alone, out zero, out_nbytes 0; a slot without a valid key sends nothing (out
+ * zero, out_nbytes 0, TX_NOKEY += 1); else TX_ROC += 1 if the slot has sent before and SEQ < TX_LAST as unsigned 16 bit (3.3.1: the
+ * sender's rollover), TX_LAST = SEQ, and out is the packet protected under TX_ROC, zero past nb + 10 bytes, out_nbytes = nb + 10.
+ * hilc_srtp_unprotect: the receiver's first launch.  arrivals int32 [max_arrivals][1 + ceil((row_bytes + 10) / 4)] and offsets int32
+ * [B + 1]: one hop's arrivals in the form of hilc_jitter_step, each record a protected packet (read only); rows int32
+ * [B][HILC_SRTP_RX_WORDS] (in place); plain int32 [max_arrivals][1 + ceil(row_bytes / 4)]: the records of every slot's range are written,
+ * in the form hilc_jitter_step takes.  Per slot and arrival, in order: no valid key: RX_NOKEY; a byte count below
+ * HILC_WIRE_TRANSPORT_HEADER + 10 or above row_bytes + 10: RX_SHORT; the ROC estimate v from (RX_SL, RX_ROC, SEQ) by 3.3.1 (the slot's
+ * first packet: v = RX_ROC), v = -1: RX_REPLAY; the index v 2^16 + SEQ more than 63 below the highest authenticated one or its window
+ * bit set (3.3.2): RX_REPLAY; a tag that differs in any of its 10 bytes, all compared (4.2): RX_AUTH_FAIL; each of these writes a
+ * record of 0 bytes, all words zero, and changes nothing but its counter.  Otherwise the record is the decrypted packet with its byte
+ * count less 10, RX_OK += 1, the window bit is set and, for a new highest index, the window moves up, RX_SL = SEQ and RX_ROC = v (3.3.1).
+ * Both: B >= 1, max_arrivals >= 0, HILC_WIRE_TRANSPORT_HEADER < row_bytes <= HILC_SRTP_MAX_ROW_BYTES (else HILC_ERR_SHAPE); NULL pointers
+ * (action excepted): HILC_ERR_NULL.  One thread per slot, workgroups of 64, one 256-word AES table in LDS; the byte rows of
+ * hilc_srtp_protect are read and written as words where base and row width are multiples of 4 and byte by byte otherwise, so any view
+ * is accepted.  Integer only, no atomics. */
+int hilc_srtp_protect(const uint8_t* packets, const int* nbytes, const int* keys, int* rows, const int* action, uint8_t* out,
+                      int* out_nbytes, int B, int row_bytes, void* stream);
+int hilc_srtp_unprotect(const int* arrivals, const int* offsets, int max_arrivals, const int* keys, int* rows, const int* action,
+                        int* plain, int B, int row_bytes, void* stream);
 
 #ifdef __cplusplus
 }
