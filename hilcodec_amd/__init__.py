@@ -21,6 +21,10 @@ from .downlink import DownlinkConfig  # noqa: F401
 from . import srtp  # noqa: F401
 from .srtp import SrtpConfig  # noqa: F401
 from .ops import srtp_protect, srtp_unprotect  # noqa: F401
+# SRTP on the forwarding hop (GraphedForwardHop(srtp=SrtpConfig())): the definition (import it by name) and its egress launch outside a
+# graph
+from . import forward_srtp  # noqa: F401
+from .ops import srtp_protect_routes  # noqa: F401
 
 __all__ = ["HILCodec", "Resampler", "resample", "MixConfig", "mix_rooms", "forward", "ForwardConfig", "GraphedForwardHop", "downlink", "DownlinkConfig",
-           "srtp", "SrtpConfig", "srtp_protect", "srtp_unprotect"]
+           "srtp", "SrtpConfig", "srtp_protect", "srtp_unprotect", "forward_srtp", "srtp_protect_routes"]

@@ -103,6 +103,7 @@ SIGNATURES = {
     "hilc_rate_cap": [_p] * 5 + [_i] * 4 + [_p],
     "hilc_srtp_protect": [_p] * 7 + [_i, _i, _p],
     "hilc_srtp_unprotect": [_p, _p, _i, _p, _p, _p, _p, _i, _i, _p],
+    "hilc_srtp_protect_routes": [_p] * 11 + [_i, _i, _i, _i, _p],
 }
 
 ABI_VERSION = 16

@@ -1,10 +1,13 @@
 // SRTP packet protection of the graphed hops (graph_step.GraphedEncodeHop(srtp=SrtpConfig()), GraphedDecodeHop(srtp=SrtpConfig())): the
-// default transform of RFC 3711, AES_CM_128_HMAC_SHA1_80.  Two launches, one per side, integer work only:
+// default transform of RFC 3711, AES_CM_128_HMAC_SHA1_80.  One launch per side, and one for the forwarder's routes; integer work only:
 //
 //   hilc_srtp_protect    the sender's launch behind hilc_packet_header and in front of hilc_rtx_step / hilc_rate_charge: encrypts bytes
 //                        [3, nbytes) of each slot's headed packet in AES-128 counter mode and appends the 10-byte HMAC-SHA1 tag.
 //   hilc_srtp_unprotect  the receiver's first launch: takes the hop's protected arrival records slot by slot in push order (index
 //                        estimate, replay window, tag, decryption) and writes plain records for the jitter step.
+//   hilc_srtp_protect_routes  the forwarder's last launch (GraphedForwardHop(srtp=); rules: hilcodec_amd/forward_srtp.py): protects
+//                        every row a listener is sent under that listener's key and the route's own SSRC and index state.  One
+//                        thread per ROW, not per route: see the kernel.
 //
 // The rules, bit for bit: hilcodec_amd/srtp.py (SenderModel, ReceiverModel); the rows: include/hilcodec_amd.h (HILC_SRTP_*).  One THREAD
 // per slot: the rollover counter and the replay window make a slot's packets a sequence, and a packet is five SHA-1 compressions and at
@@ -389,6 +392,139 @@ __global__ __launch_bounds__(WG) void srtp_unprotect_kernel(const int* __restric
   for (int k2 = 0; k2 < HILC_SRTP_RX_WORDS; ++k2) row[k2] = r[k2];
 }
 
+// ---- the forwarder's egress (graph_step.GraphedForwardHop(srtp=); the rules, bit for bit: hilcodec_amd/forward_srtp.py, RouteModel)
+// A route's index state: the receiver rule's steps 2, 3 and 5 (srtp.py) on the route row's (RT_ROC, RT_SL, RT_SEEN, window), so the
+// egress refuses exactly what the client's replay window would, and no index leaves twice.
+struct RouteIndex {
+  uint32_t roc, sl;
+  bool seen;
+  uint64_t window;
+  // SEQ -> accepted (v: the rollover counter it is sent under; the state moves) or refused (the state stays)
+  __device__ __forceinline__ bool admit(uint32_t seq, uint32_t& v) {
+    bool before = false;                    // v = -1
+    long long delta = 1;
+    v = roc;
+    if (seen) {
+      if (sl < 32768u) {
+        if ((int)seq - (int)sl > 32768) {
+          before = roc == 0u;
+          v = roc - 1u;
+        }
+      } else if ((int)sl - 32768 > (int)seq) {
+        v = roc + 1u;
+      }
+      delta = (long long)(((uint64_t)v << 16) | seq) - (long long)(((uint64_t)roc << 16) | sl);
+    }
+    if (before || (delta <= 0 && (-delta >= HILC_SRTP_WINDOW || ((window >> (int)(-delta)) & 1ull)))) return false;
+    if (delta > 0) {
+      window = (!seen || delta >= HILC_SRTP_WINDOW) ? 1ull : ((window << (int)delta) | 1ull);
+      sl = seq;
+      roc = v;
+      seen = true;
+    } else {
+      window |= 1ull << (int)(-delta);
+    }
+    return true;
+  }
+};
+
+// One THREAD per output row (b, j, k).  The P rows of a route sit side by side in one workgroup (64 / P whole routes, the other lanes
+// idle); a route's sequential part is a few integer steps per row, so thread k replays the rule for the rows in front of its own and
+// then runs its own packet's AES / SHA-1 chain: the launch costs one packet's chain whatever the burst.  Every thread reads the
+// route row, a barrier follows, and the thread of the route's last row, which has replayed all of them, writes the row back.
+__global__ __launch_bounds__(WG) void srtp_protect_routes_kernel(const uint8_t* __restrict__ in_rows, const int* __restrict__ nbytes,
+                                                                 const int* __restrict__ routes, const int* __restrict__ new_routes,
+                                                                 const int* __restrict__ action, const int* __restrict__ rekey_up,
+                                                                 const int* __restrict__ rekey_down, const int* __restrict__ keys,
+                                                                 int* rt_rows, uint8_t* __restrict__ out, int* __restrict__ out_nbytes,
+                                                                 int B, int F, int P, int tb, int in_aligned, int out_aligned) {
+  __shared__ uint32_t te[256];
+  load_te0(te);
+  const int per_wg = WG / P;                             // whole routes of a workgroup
+  const int lane_route = (int)threadIdx.x / P, k = (int)threadIdx.x - lane_route * P;
+  const long route = (long)blockIdx.x * per_wg + lane_route;
+  const bool mine = lane_route < per_wg && route < (long)B * F;
+  int r[HILC_FSRTP_RT_WORDS];
+  int* rt = rt_rows + (mine ? route : 0) * HILC_FSRTP_RT_WORDS;
+#pragma unroll
+  for (int i = 0; i < HILC_FSRTP_RT_WORDS; ++i) r[i] = mine ? rt[i] : 0;
+  __syncthreads();                                       // every reader of a route row is in front of its one writer
+  if (!mine) return;
+  const int b = (int)(route / F), j = (int)(route - (long)b * F);
+  const int* key = keys + (long)b * HILC_SRTP_KEY_WORDS;
+  const bool valid = key[HILC_SRTP_KEY_VALID] != 0;
+  const int t = routes[route];
+  bool restart = new_routes[route] != 0 || is_reset(action, b) || is_reset(rekey_down, b);
+  if (t >= 0 && t < B) restart = restart || is_reset(action, t) || is_reset(rekey_up, t);
+  if (restart) {
+    if (r[HILC_FSRTP_RT_EPOCH] < HILC_FSRTP_MAX_EPOCH) {
+      ++r[HILC_FSRTP_RT_EPOCH];
+      r[HILC_FSRTP_RT_SEEN] = 0;
+    } else {
+      r[HILC_FSRTP_RT_SEEN] = HILC_FSRTP_SEEN_EXHAUSTED;  // no SSRC is left for another stream
+    }
+    r[HILC_FSRTP_RT_ROC] = r[HILC_FSRTP_RT_SL] = r[HILC_FSRTP_RT_WIN_LO] = r[HILC_FSRTP_RT_WIN_HI] = 0;
+  }
+  const bool exhausted = r[HILC_FSRTP_RT_SEEN] == HILC_FSRTP_SEEN_EXHAUSTED;
+  RouteIndex ix = {(uint32_t)r[HILC_FSRTP_RT_ROC], (uint32_t)r[HILC_FSRTP_RT_SL] & 0xFFFFu, r[HILC_FSRTP_RT_SEEN] == 1,
+                   (uint32_t)r[HILC_FSRTP_RT_WIN_LO] | ((uint64_t)(uint32_t)r[HILC_FSRTP_RT_WIN_HI] << 32)};
+  const long row0 = route * P;
+  bool send = false;
+  uint32_t v = 0u, seq = 0u;
+  int nb = 0;
+  for (int q = 0; q <= k; ++q) {                         // the rows in front of this thread's, then its own
+    const Row rq = {const_cast<uint8_t*>(in_rows) + (row0 + q) * tb, tb, in_aligned != 0};
+    nb = min(nbytes[row0 + q], tb);
+    send = false;
+    if (nb < HEAD) continue;
+    if (!valid) {
+      ++r[HILC_FSRTP_RT_NOKEY];
+    } else if (exhausted) {
+      ++r[HILC_FSRTP_RT_EXHAUSTED];
+    } else {
+      seq = rq.be(0) >> 16;
+      send = ix.admit(seq, v);
+      if (send)
+        ++r[HILC_FSRTP_RT_PROTECTED];
+      else
+        ++r[HILC_FSRTP_RT_STALE];
+    }
+  }
+  if (k == P - 1) {
+    if (!exhausted) {
+      r[HILC_FSRTP_RT_ROC] = (int)ix.roc;
+      r[HILC_FSRTP_RT_SL] = (int)ix.sl;
+      r[HILC_FSRTP_RT_SEEN] = ix.seen ? 1 : 0;
+      r[HILC_FSRTP_RT_WIN_LO] = (int)(uint32_t)ix.window;
+      r[HILC_FSRTP_RT_WIN_HI] = (int)(uint32_t)(ix.window >> 32);
+    }
+#pragma unroll
+    for (int i = 0; i < HILC_FSRTP_RT_WORDS; ++i) rt[i] = r[i];
+  }
+  const Row in = {const_cast<uint8_t*>(in_rows) + (row0 + k) * tb, tb, in_aligned != 0};
+  const Row o = {out + (row0 + k) * (tb + TAG), tb + TAG, out_aligned != 0};
+  if (!send) {
+    o.zero(0);
+    out_nbytes[row0 + k] = 0;
+    return;
+  }
+  Key ky;
+#pragma unroll
+  for (int i = 0; i < 44; ++i) ky.rk[i] = (uint32_t)key[HILC_SRTP_KEY_RK + i];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) ky.iv[i] = (uint32_t)key[HILC_SRTP_KEY_SALT + i];
+  // the route's own SSRC: base + MAX_FANOUT epoch + route (mod 2^32)
+  ky.iv[1] ^= (uint32_t)key[HILC_SRTP_KEY_SSRC] + (uint32_t)HILC_FORWARD_MAX_FANOUT * (uint32_t)r[HILC_FSRTP_RT_EPOCH] + (uint32_t)j;
+  crypt(te, ky, v, seq, in, nb, o);
+  uint32_t tag[3];
+  hmac_tag(key, o, nb, v, tag);            // reads back the ciphertext this thread wrote
+  for (int w = nb >> 2; w < o.words(); ++w) {
+    const uint32_t ct = 4 * w < nb ? o.be(w) & keep(nb, w) : 0u;
+    o.put(w, ct | place(tag[0], nb - 4 * w) | place(tag[1], nb + 4 - 4 * w) | place(tag[2], nb + 8 - 4 * w));
+  }
+  out_nbytes[row0 + k] = nb + TAG;
+}
+
 static inline dim3 slots_grid(int B) { return dim3((unsigned)((B + WG - 1) / WG)); }
 
 static inline bool word_aligned(const void* p, long stride) { return ((reinterpret_cast<uintptr_t>(p) | (uintptr_t)stride) & 3) == 0; }
@@ -416,6 +552,24 @@ extern "C" int hilc_srtp_unprotect(const int* arrivals, const int* offsets, int 
   HILC_CLEAR_ERROR();
   hipLaunchKernelGGL(srtp_unprotect_kernel, slots_grid(B), dim3(WG), 0, (hipStream_t)stream, arrivals, offsets, max_arrivals, keys, rows,
                      action, plain, B, row_bytes);
+  HILC_CHECK_LAUNCH();
+  return HILC_OK;
+}
+
+extern "C" int hilc_srtp_protect_routes(const uint8_t* rows, const int* nbytes, const int* routes, const int* new_routes,
+                                        const int* action, const int* rekey_up, const int* rekey_down, const int* keys, int* route_rows,
+                                        uint8_t* out, int* out_nbytes, int B, int fanout, int burst, int row_bytes, void* stream) {
+  if (!rows || !nbytes || !routes || !new_routes || !keys || !route_rows || !out || !out_nbytes) return HILC_ERR_NULL;
+  if (B <= 0 || fanout < 1 || fanout > HILC_FORWARD_MAX_FANOUT || burst < 1 || burst > HILC_FORWARD_MAX_BURST || row_bytes <= HEAD ||
+      row_bytes > HILC_SRTP_MAX_ROW_BYTES)
+    return HILC_ERR_SHAPE;
+  const int in_aligned = word_aligned(rows, row_bytes), out_aligned = word_aligned(out, row_bytes + TAG);
+  const long n_routes = (long)B * fanout;
+  const int per_wg = WG / burst;
+  HILC_CLEAR_ERROR();
+  hipLaunchKernelGGL(srtp_protect_routes_kernel, dim3((unsigned)((n_routes + per_wg - 1) / per_wg)), dim3(WG), 0, (hipStream_t)stream,
+                     rows, nbytes, routes, new_routes, action, rekey_up, rekey_down, keys, route_rows, out, out_nbytes, B, fanout, burst,
+                     row_bytes, in_aligned, out_aligned);
   HILC_CHECK_LAUNCH();
   return HILC_OK;
 }

@@ -55,6 +55,10 @@ Senders without DTX.  Level-based selection is audio_level.py's (GraphedForwardH
 one further launch between these two keeps a smoothed loudness per sender and hands hilc_forward_route shadow sender rows whose
 (SD_HANG, SD_SINCE) order is the loudness order; the rules above stay what they are.
 
+Protected calls.  SRTP hop by hop is forward_srtp.py's (GraphedForwardHop(srtp=)): hilc_srtp_unprotect in front of these two launches
+hands them plain records (a rejected arrival is a record of 0 bytes: malformed by rule 2 of the sender rule), one launch behind
+them protects every output row under its listener's key and its route's own SSRC; the rules above stay what they are.
+
 Out of scope: re-stamping hop indices; more than one room per slot."""
 from __future__ import annotations
 

@@ -30,6 +30,7 @@ from . import srtp as srtp_def
 from . import engine, ops, wire
 from . import downlink as downlink_def
 from . import forward as forward_def
+from . import forward_srtp as fsrtp_def
 from . import rate as rate_def
 from . import report as report_def
 from . import rtx as rtx_def
@@ -1891,15 +1892,30 @@ class GraphedForwardHop(_GraphPair):
     keeps each sender's smoothed loudness and writes a ping-pong pair of shadow sender rows, which hilc_forward_route reads in place of
     the real ones: it then selects a room's loudest speakers, with a margin for those on stage.  `speaker_state` and `speaker_rank` show
     the result; `sender_state` stays the real rows, and the downlink launches follow unchanged.  `speakers=None` allocates nothing and
-    captures exactly the graph without it."""
+    captures exactly the graph without it.
+    `srtp` (a srtp.SrtpConfig; hilcodec_amd/forward_srtp.py: the rules): SRTP hop by hop.  The arrivals are protected packets under each
+    sender's uplink key (`set_uplink_key`), 10 bytes wider; hilc_srtp_unprotect runs as the graph's first launch and writes the plain
+    records every launch above reads into a device-only buffer (a rejected arrival: a record of 0 bytes, which counts as malformed).
+    hilc_srtp_protect_routes runs last, on the rows the hop would have returned, and `forward` returns its rows instead: each protected
+    under its listener's downlink key (`set_downlink_key`) and the route's own SSRC, `forward_srtp.route_ssrc(base, j,
+    route_epoch[b][j])`; the client re-keys and restarts route j whenever that epoch changes.  The slots given a key travel as two
+    more one-hop rows of the same upload.  `speakers` and `downlink=DownlinkConfig(rate=...)` work unchanged under it; `downlink.history
+    > 0` raises ValueError: a NACK answer is cut again at answer time, so it could put other plaintext under an index already used (a
+    per-route history of ciphertext is the follow-up).  `srtp=None` allocates nothing and captures exactly the graphs without it."""
 
     def __init__(self, batch: int, frames: int, n: int, device: torch.device, fec_stages: int = 0, cng_order: Optional[int] = None,
                  cfg: forward_def.ForwardConfig = forward_def.ForwardConfig(), max_arrivals: Optional[int] = None, warmup: int = 2,
-                 downlink: Optional[downlink_def.DownlinkConfig] = None, speakers: Optional[level_def.SpeakerConfig] = None):
+                 downlink: Optional[downlink_def.DownlinkConfig] = None, speakers: Optional[level_def.SpeakerConfig] = None,
+                 srtp: Optional[srtp_def.SrtpConfig] = None):
         if not isinstance(cfg, forward_def.ForwardConfig):
             raise ValueError(f"GraphedForwardHop: cfg must be a forward.ForwardConfig, got {cfg!r}")
         self.downlink = _config_arg("downlink", downlink, downlink_def.DownlinkConfig)
         self.speakers = _config_arg("speakers", speakers, level_def.SpeakerConfig)
+        self.srtp = _config_arg("srtp", srtp, srtp_def.SrtpConfig)
+        if srtp is not None and downlink is not None and downlink.history > 0:
+            raise ValueError("GraphedForwardHop(srtp=...) with downlink.history > 0: a NACK answer is cut again at answer time, so it "
+                             "could put other plaintext under an index already used; answers under srtp need a per-route history of "
+                             "ciphertext")
         super().__init__(_int_arg("batch", batch, 1), device)
         B = self.batch
         self.frames, self.n, self.cfg = _int_arg("frames", frames, 1), _int_arg("n", n, 1, 31), cfg
@@ -1912,13 +1928,16 @@ class GraphedForwardHop(_GraphPair):
         # ONE device buffer, captured by address, uploaded up to the last arrival used: the action, room and layers rows, the
         # arrival region (an arrival record: byte count, then the headed packet)
         F, P = cfg.fanout, cfg.burst
+        # with `srtp` the arrivals are protected packets, 10 bytes wider, and two more one-hop rows say which slots were given a key
+        self.wstride = self.tstride + (wire.SRTP_TAG_BYTES if srtp is not None else 0)
         # with `downlink`: behind them the feedback rows in use, int32 [B, fanout] each (fanout stage rows laid end to end)
         self._fb_names = () if downlink is None else \
             ("report",) * (downlink.rate is not None) + ("nack_base", "nack_bitmap") * (downlink.history > 0)
         fb_rows = tuple(f"{name}{j}" for name in self._fb_names for j in range(F))
         # with `speakers`: the one-hop row loud (128 - the loudest level of the slot's arrivals, 0: none)
-        st = self.stage = ControlStage(B, ("action", "room", "layers") + ("loud",) * (speakers is not None) + fb_rows, 0, 0, 0, device,
-                                       arrivals=(self.max_arrivals, self.tstride))
+        key_rows = ("rekey_up", "rekey_down") * (srtp is not None)
+        st = self.stage = ControlStage(B, ("action", "room", "layers") + ("loud",) * (speakers is not None) + fb_rows + key_rows, 0, 0, 0,
+                                       device, arrivals=(self.max_arrivals, self.wstride))
         self.offsets, self.arrivals = st.offsets, st.arrivals
         self._fb = {name: st.dev[st.row_off[name + "0"]:st.row_off[name + "0"] + B * F].view(torch.int32).view(B, F)
                     for name in self._fb_names}
@@ -1938,7 +1957,23 @@ class GraphedForwardHop(_GraphPair):
             self._sp = self._slot_state(level_def.SP_WORDS)
         if downlink is not None:
             self._init_downlink(downlink)
+        if srtp is not None:
+            self._init_srtp()
         self.graphs, self.outs = self._capture_pair(self._hop, warmup)
+
+    def _init_srtp(self) -> None:
+        """the state of the two SRTP launches: the plain records hilc_srtp_unprotect writes for every later launch, the two key tables
+        and their device rows, the ingress rows (srtp.RX_*), the route rows (forward_srtp.RT_*) and per parity the protected rows that
+        `forward` returns"""
+        F, P = self.cfg.fanout, self.cfg.burst
+        self._wire_arrivals = self.arrivals
+        self.arrivals = torch.zeros(self.max_arrivals, arrival_width(self.tstride), dtype=torch.int32, device=self.device)
+        self._keys = fsrtp_def.ForwardKeys(self.batch)
+        self._up_dev, self._down_dev = self._slot_state(srtp_def.KEY_WORDS), self._slot_state(srtp_def.KEY_WORDS)
+        self._rxs = self._slot_state(srtp_def.RX_WORDS)
+        self._rt = self._slot_state(F, fsrtp_def.RT_WORDS)
+        self._sout = [self._slot_state(F, P, self.wstride, dtype=torch.uint8) for _ in (0, 1)]
+        self._sout_nbytes = [self._slot_state(F, P) for _ in (0, 1)]
 
     def _init_downlink(self, dl: downlink_def.DownlinkConfig) -> None:
         """the state of the two downlink launches: the listener rows (as after a reset), the routes' memory, the senders' histories,
@@ -1960,6 +1995,19 @@ class GraphedForwardHop(_GraphPair):
                          for _ in (0, 1)]
 
     def _hop(self, p: int) -> Tuple[Tensor, Tensor]:
+        if self.srtp is None:
+            return self._plain_hop(p)
+        st = self.stage
+        # the clear row of the ingress is rekey_up: an RX row lives as long as its key, a join under the same key keeps its window
+        ops.srtp_unprotect(self._wire_arrivals, self.offsets, self._up_dev, self._rxs, self.tstride, plain=self.arrivals,
+                           action=st.row["rekey_up"])
+        rows, nbytes = self._plain_hop(p)
+        return ops.srtp_protect_routes(rows, nbytes, self._routes, self._new_routes, self._down_dev, self._rt, out=self._sout[p],
+                                       out_nbytes=self._sout_nbytes[p], action=st.row["action"], rekey_up=st.row["rekey_up"],
+                                       rekey_down=st.row["rekey_down"])
+
+    def _plain_hop(self, p: int) -> Tuple[Tensor, Tensor]:
+        """the launches on plain records: classify, (rank,) route, (store, downlink step)"""
         st, args = self.stage, (self.cfg, self.n, self.frames, self.fec_stages, self.cng_order)
         ops.forward_classify(self.arrivals, self.offsets, self._sd, self._pick, self._pick_count, *args, action=st.row["action"])
         ranked = self._sd
@@ -1992,6 +2040,68 @@ class GraphedForwardHop(_GraphPair):
         st.h_row["layers"].fill_(self.n)
         st.dev.copy_(st.host)
         super()._zero()
+        if self.srtp is not None:
+            self.arrivals.zero_()
+            self._keys.up.dirty = self._keys.down.dirty = True       # the device key rows are zero again
+
+    def reset(self) -> None:
+        """every slot as constructed (in no room, n layers, no route, every row and counter zero) and the first graph next; with
+        `srtp`: both key tables empty and every route row zero, its epoch included"""
+        self._joined = set()
+        self._fb_live = False
+        if self.srtp is not None:
+            self._keys.reset()
+        self._zero()
+        self.parity = 0
+
+    # ---------------------------------------------------------------- SRTP (srtp=SrtpConfig())
+    def set_uplink_key(self, slot: int, master_key, master_salt, ssrc: Optional[int] = None, roc: int = 0) -> None:
+        """from the next hop on, slot `slot`'s arrivals are unprotected under the session keys derived from `master_key` (16 bytes)
+        and `master_salt` (14 bytes) with `ssrc` (default: the slot): what its GraphedEncodeHop(srtp=) was given with set_key.  Its
+        ingress row is cleared on that hop and begins at rollover counter `roc`, and every route it owns restarts (its SEQ restarts
+        with its key).  ValueError: wrong lengths, ssrc or roc out of range, or a key the slot had before; never the key itself."""
+        self._need(self.srtp is not None, "set_uplink_key", "srtp=SrtpConfig()")
+        self._keys.set_uplink_key(self._slot(slot), master_key, master_salt, ssrc, roc)
+
+    def set_downlink_key(self, slot: int, master_key, master_salt, ssrc: Optional[int] = None) -> None:
+        """from the next hop on, the rows sent to listener `slot` are protected under the session keys derived from `master_key` and
+        `master_salt`; `ssrc` (default: the slot) is the base of its routes' SSRCs (forward_srtp.route_ssrc).  Every route of the
+        listener restarts on that hop.  ValueError as set_uplink_key."""
+        self._need(self.srtp is not None, "set_downlink_key", "srtp=SrtpConfig()")
+        self._keys.set_downlink_key(self._slot(slot), master_key, master_salt, ssrc)
+
+    def clear_keys(self, slot: int) -> None:
+        """from the next hop on, slot `slot` has neither key: its arrivals are rejected and it is sent nothing"""
+        self._need(self.srtp is not None, "clear_keys", "srtp=SrtpConfig()")
+        self._keys.clear_keys(self._slot(slot))
+
+    def _send_keys(self) -> None:
+        """before a replay, on its stream: each key table that has changed since the last hop"""
+        for table, dev in ((self._keys.up, self._up_dev), (self._keys.down, self._down_dev)):
+            if table.dirty:
+                dev.copy_(torch.from_numpy(table.rows))
+                table.dirty = False
+
+    @property
+    def route_epoch(self) -> Tensor:
+        """int32 `[B, fanout]` device view, the RT_EPOCH column of `egress_state`: the epoch of each listener's routes after the last
+        hop; a client re-keys route j to forward_srtp.route_ssrc(base, j, epoch) and restarts it when its epoch changed (srtp only)"""
+        self._need(self.srtp is not None, "route_epoch", "srtp=SrtpConfig()")
+        return self._rt[:, :, fsrtp_def.RT_EPOCH]
+
+    @property
+    def egress_state(self) -> Tensor:
+        """int32 `[B, fanout, forward_srtp.RT_WORDS]` device view: each route's row after the last hop (forward_srtp.RT_*; srtp only).
+        Read-only: written by the graph."""
+        self._need(self.srtp is not None, "egress_state", "srtp=SrtpConfig()")
+        return self._rt
+
+    @property
+    def ingress_state(self) -> Tensor:
+        """int32 `[B, srtp.RX_WORDS]` device view: each sender slot's RX row after the last hop (srtp.RX_*; srtp only).  Read-only:
+        written by the graph."""
+        self._need(self.srtp is not None, "ingress_state", "srtp=SrtpConfig()")
+        return self._rxs
 
     def _slot(self, slot) -> int:
         s = int(slot)
@@ -2129,7 +2239,8 @@ class GraphedForwardHop(_GraphPair):
         """one hop: this hop's arrivals, in push order — `slots` and `nbytes` (A host ints), `packets` uint8 `[A,
         wire.transport_bytes(n, m, frames)]` (host or device), 0 <= A <= max_arrivals.  Returns (out uint8 `[B, fanout, burst, tb]`,
         out_nbytes int32 `[B, fanout, burst]`): row (b, j, k) is the k-th packet of this hop for listener b's route j, cut to its layers
-        (0 bytes: none); static views that the next-but-one call overwrites.
+        (0 bytes: none); static views that the next-but-one call overwrites.  With `srtp` the arrivals and the rows returned are
+        protected packets, both `wire.srtp_bytes(n, m, frames)` wide.
         `reports` (downlink with rate only) / `nacks` (downlink with history only): (listeners, routes, blobs), this hop's feedback — A
         host ints twice, and a uint8 `[A, 3]` / `[A, 4]` host tensor or a sequence of `bytes` (wire.pack_report / wire.pack_nack); a
         (listener, route) pair named twice keeps its last blob.  With `downlink` the rows returned are cut to `eff_layers`.
@@ -2140,7 +2251,7 @@ class GraphedForwardHop(_GraphPair):
         if isinstance(levels, Tensor) and levels.is_cuda:
             raise ValueError("forward: levels must be host ints, not a device tensor")
         fb = self._feedback(reports, nacks)
-        arr = check_arrivals("forward", slots, packets, nbytes, self.batch, self.max_arrivals, self.tstride)
+        arr = check_arrivals("forward", slots, packets, nbytes, self.batch, self.max_arrivals, self.wstride)
         loud = None if self.speakers is None else level_def.loud_row(self.batch, arr.slots, levels, self.speakers)
         st = self.stage
         st.wait()
@@ -2154,6 +2265,12 @@ class GraphedForwardHop(_GraphPair):
         if loud is not None:                  # the loudness row, likewise: the slots with an arrival on this hop, 0 elsewhere
             heard = np.flatnonzero(loud)
             st.put_one_hop("loud", heard, loud[heard])
+        if self.srtp is not None and (st.one_hop_live or self._keys.pending):
+            up, down = self._keys.take()                  # the key rows, likewise: the slots given a key since the last hop
+            st.put_one_hop("rekey_up", up, 1)
+            st.put_one_hop("rekey_down", down, 1)
         st.send_arrivals(arr, packets)
         st.finish()
+        if self.srtp is not None:
+            self._send_keys()
         return self._replay()

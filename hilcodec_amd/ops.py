@@ -31,6 +31,7 @@ from .bwe import BW_WORDS, CP_WORDS
 from .bwe import bits as bwe_bits
 from .dtx import LEVELS, state_words
 from .forward import LR_WORDS, SD_WORDS
+from .forward_srtp import RT_WORDS as FSRTP_RT_WORDS
 from .jitter import AD_WORDS, ST_WORDS
 from .report import FA_WORDS, RP_WORDS
 from .rate import RC_WORDS, bucket
@@ -1418,6 +1419,29 @@ def _srtp_unprotect(arrivals, offsets, keys, rows, action, plain, row_bytes):
 _register("srtp_unprotect", "(Tensor arrivals, Tensor offsets, Tensor keys, Tensor(a!) rows, Tensor? action, Tensor(b!) plain, "
           "int row_bytes) -> ()", _srtp_unprotect, lambda arrivals, offsets, keys, rows, action, plain, row_bytes: None)
 
+
+# the forwarding hop's egress (graph_step.GraphedForwardHop(srtp=); definition: hilcodec_amd/forward_srtp.py)
+def _srtp_protect_routes(rows, nbytes, routes, new_routes, action, rekey_up, rekey_down, keys, route_rows, out, out_nbytes):
+    if rows.dim() != 4:
+        raise RuntimeError("srtp_protect_routes: rows must be [B, fanout, burst, row_bytes]")
+    B, F, P, tb = rows.shape
+    if nbytes.shape != (B, F, P) or routes.shape != (B, F) or new_routes.shape != (B, F) or keys.shape != (B, SRTP_KEY_WORDS) or \
+            route_rows.shape != (B, F, FSRTP_RT_WORDS) or out.shape != (B, F, P, tb + SRTP_TAG_BYTES) or out_nbytes.shape != (B, F, P):
+        raise RuntimeError(f"srtp_protect_routes: nbytes must be [{B}, {F}, {P}], routes and new_routes [{B}, {F}], keys [{B}, "
+                           f"{SRTP_KEY_WORDS}], route_rows [{B}, {F}, {FSRTP_RT_WORDS}], out [{B}, {F}, {P}, {tb + SRTP_TAG_BYTES}] and "
+                           f"out_nbytes [{B}, {F}, {P}]")
+    _rows("srtp_protect_routes", B, action=action, rekey_up=rekey_up, rekey_down=rekey_down)
+    check(lib.hilc_srtp_protect_routes(_ptr(rows, torch.uint8), _ptr(nbytes, torch.int32), _ptr(routes, torch.int32),
+                                       _ptr(new_routes, torch.int32), _ptr(action, torch.int32), _ptr(rekey_up, torch.int32),
+                                       _ptr(rekey_down, torch.int32), _ptr(keys, torch.int32), _ptr(route_rows, torch.int32),
+                                       _ptr(out, torch.uint8), _ptr(out_nbytes, torch.int32), B, F, P, tb, _stream()),
+          "hilc_srtp_protect_routes")
+
+
+_register("srtp_protect_routes", "(Tensor rows, Tensor nbytes, Tensor routes, Tensor new_routes, Tensor? action, Tensor? rekey_up, "
+          "Tensor? rekey_down, Tensor keys, Tensor(a!) route_rows, Tensor(b!) out, Tensor(c!) out_nbytes) -> ()", _srtp_protect_routes,
+          lambda rows, nbytes, routes, new_routes, action, rekey_up, rekey_down, keys, route_rows, out, out_nbytes: None)
+
 # ======================================================================================================
 # selective forwarding hop (graph_step.GraphedForwardHop; definition: hilcodec_amd/forward.py; semantics: include/hilcodec_amd.h)
 # ======================================================================================================
@@ -2373,6 +2397,27 @@ def srtp_unprotect(arrivals: Tensor, offsets: Tensor, keys: Tensor, rows: Tensor
         plain = torch.zeros(arrivals.shape[0], 1 + (int(row_bytes) + 3) // 4, device=arrivals.device, dtype=torch.int32)
     _OPS.srtp_unprotect(arrivals, offsets, keys, rows, action, plain, int(row_bytes))
     return plain
+
+
+def srtp_protect_routes(rows: Tensor, nbytes: Tensor, routes: Tensor, new_routes: Tensor, keys: Tensor, route_rows: Tensor,
+                        out: Optional[Tensor] = None, out_nbytes: Optional[Tensor] = None, action: Optional[Tensor] = None,
+                        rekey_up: Optional[Tensor] = None, rekey_down: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """The protected forwarder's last step (forward_srtp.RouteModel), outside a graph on any rows and state: a hop's final `rows` (uint8
+    `[B, fanout, burst, row_bytes]`) and `nbytes` (int32 `[B, fanout, burst]`) with the `routes` and `new_routes` (int32 `[B, fanout]`)
+    of the route launch, read only, under the listeners' downlink `keys` (int32 `[B, srtp.KEY_WORDS]`) and the `route_rows` (int32 `[B,
+    fanout, forward_srtp.RT_WORDS]`, in place) -> (`out` uint8 `[B, fanout, burst, row_bytes + 10]`, `out_nbytes` int32 `[B, fanout,
+    burst]`), allocated when not given.  `action`, `rekey_up`, `rekey_down` (int32 `[B]`, optional): the slots joined, given an uplink
+    key, given a downlink key on this hop; each restarts the routes it touches.  A byte tensor may be any contiguous view: rows that
+    are not word-aligned are read and written byte by byte."""
+    if rows.dim() != 4:
+        raise RuntimeError("srtp_protect_routes: rows must be [B, fanout, burst, row_bytes]")
+    B, F, P, tb = rows.shape
+    if out is None:
+        out = _new(rows, B, F, P, tb + SRTP_TAG_BYTES, dtype=torch.uint8)
+    if out_nbytes is None:
+        out_nbytes = _new(rows, B, F, P, dtype=torch.int32)
+    _OPS.srtp_protect_routes(rows, nbytes, routes, new_routes, action, rekey_up, rekey_down, keys, route_rows, out, out_nbytes)
+    return out, out_nbytes
 
 
 def forward_classify(arrivals: Tensor, offsets: Tensor, rows: Tensor, pick: Tensor, pick_count: Tensor, cfg, n: int, frames: int,

@@ -14,7 +14,7 @@ ACTION_KEEP, ACTION_ZERO, ACTION_LOAD = 0, -1, 1
 # hold row of a hop: the slot advances, is held, or (receiver) makes comfort noise from the SID that arrived / while its stream is in DTX
 HOLD_ADVANCE, HOLD_HELD, HOLD_SID, HOLD_SILENT = 0, 1, 2, 3
 # the rows of a control stage whose entries apply to exactly one hop: the upload after a hop that wrote one must clear it on the device
-ONE_HOP_ROWS = ("action", "report", "nack_base", "nack_bitmap", "loud", "cap")
+ONE_HOP_ROWS = ("action", "report", "nack_base", "nack_bitmap", "loud", "cap", "rekey_up", "rekey_down")
 
 
 def stage_layout(batch: int, rows: Sequence[str], payload_words: int = 0, loads: int = 0, record_len: int = 0):

@@ -47,9 +47,9 @@ A rejected arrival comes out as a record of 0 bytes, every word zero: the jitter
 so nothing behind this launch knows about SRTP.  An accepted one comes out as the plain record (byte count, then the packet, zero
 past it).
 
-Not covered: key exchange (DTLS-SRTP belongs to the host), SRTCP (reports, NACKs and caps travel unprotected), the timing of
-table lookups on a GPU that others share, and graph_step.GraphedForwardHop: it trims packets, so it would unprotect on ingress and
-protect per listener route with a ROC per route, which the two stand-alone ops (any rows, any state) are shaped for."""
+Not covered: key exchange (DTLS-SRTP belongs to the host), SRTCP (reports, NACKs and caps travel unprotected) and the timing of
+table lookups on a GPU that others share.  graph_step.GraphedForwardHop(srtp=) trims packets, so it unprotects on ingress with this
+module's receiver rule and protects per listener route under rules of its own: forward_srtp.py."""
 from __future__ import annotations
 
 import hashlib

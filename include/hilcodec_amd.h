@@ -42,7 +42,7 @@ extern "C" {
 #define HILC_ERR_UNSUPPORTED (-4) /* configuration outside what the kernels cover   */
 #define HILC_ERR_RANGE (-5)       /* n outside 1..Nq (reference: AssertionError)    */
 
-#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream) with per-speaker levelling and a limiter int hilc_mix_gains(const float* wav, double* gains, double* power, const int* action, double gate2, double lo, double hi, double up, double down, double min_gain, double max_gain, double smooth, int B, int L, void* stream) and int hilc_mix_rooms_dyn(const float* wav, const int* room, const double* score, int top_k, const double* gains, double* limiter, double ceiling, double release, int sub, const int* action, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream); and the selective forwarding hop int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick, int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream) and int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers, const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec, void* stream); and its downlink control int hilc_downlink_store(const int* arrivals, int max_arrivals, const int* action, const int* pick, const int* pick_count, int* tags, int* ring, int* rows, int B, int T, int n_max, int m, int burst, int history, void* stream) and int hilc_downlink_step(const int* routes, const int* new_routes, const uint8_t* in, const int* in_nbytes, const int* layers, const int* action, const int* report, const int* nack_base, const int* nack_bitmap, const int* tags, const int* ring, int* rows, int* memory, int* eff_layers, uint8_t* out, int* out_nbytes, uint8_t* rtx_out, int* rtx_nbytes, int* rtx_routes, int B, int T, int n_max, int m, int fanout, int burst, int keep_fec, int history, int per_hop, int rate_on, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream); and the audio level with level-based speaker selection int hilc_audio_level(const float* x, const double* thr, const int* hold, int* level, int B, int L, void* stream) and int hilc_forward_rank(const int* sd, const int* loud, const int* room, const int* action, const int* shadow_prev, int* shadow, int* rows, int B, int fanout, int hang_hops, int floor_level, int attack_shift, int decay_q8, int margin_db, void* stream); and the delay-based bandwidth estimate int hilc_rx_bwe(const int* arrivals, const int* offsets, const int* times, int max_arrivals, const int* action, int* rows, uint8_t* caps, int* due, int B, int T, int n_max, int m, int order, int min_bits, int max_bits, int window, int rate_window, int alpha_q8, int beta_q8, int increase_q16, int interval, int reset_ticks, void* stream) and int hilc_rate_cap(const int* cap, const int* action, const int* hold, int* rows, int* rate_rows, int B, int min_bits, int max_bits, int timeout_hops, void* stream); and SRTP packet protection int hilc_srtp_protect(const uint8_t* packets, const int* nbytes, const int* keys, int* rows, const int* action, uint8_t* out, int* out_nbytes, int B, int row_bytes, void* stream) and int hilc_srtp_unprotect(const int* arrivals, const int* offsets, int max_arrivals, const int* keys, int* rows, const int* action, int* plain, int B, int row_bytes, void* stream) */
+#define HILC_ABI_VERSION 16   /* 2: packed residual-block weights; 3: hilc_spec_block; 4: hilc_spec_block_conv_pre; 5: waveform history in both; 6-7: *_x3 (experimental; REMOVED in 14); 8: hilc_dws_conv_wave_row; 9: hilc_resblock_stream_supported (wide blocks in hilc_resblock_stream); 10: hilc_resblock_chain; 11: hilc_encoder_stage; 12: batched cache updates (REMOVED in 14); 13: hilc_decoder_stage; 14: the entry points that only served rejected experiments are gone (split-bf16 decoder GEMMs, batched cache updates); hilc_decoder_stage_post, hilc_encoder_stage0; 15: hilc_rvq_encode[_mixed] take `flags` (HILC_RVQ_VALU_ONLY replaces the HILC_RVQ_VALU environment variable); 16: per-stream sessions of a graphed hop, two new entry points — int hilc_state_slots_apply(float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* action, const float* records, int nrecords, void* stream) and int hilc_state_slots_gather(const float* block, const int64_t* slice_off, const int* slice_len, int nslices, int streams, const int* slots, int nslots, float* records, void* stream); no struct changes; additive under 16 (no version bump): hilc_state_slots_hold, hilc_pack_codes_10bit, hilc_rvq_decode_packed, and the receiver's loss concealment int hilc_conceal_prepare(int* state, const int* action, int* hold, const int* lost, int* n_per_stream, uint8_t* packets, int* ramp, int B, int T, int n_max, int fade_hops, void* stream) and int hilc_conceal_gain(float* wav, const int* ramp, const float* gains, const float* weights, int B, int samples, int fade_hops, void* stream); and the polyphase sample-rate converter int hilc_resample_poly(const float* x, const float* hist_in, float* hist_out, float* y, const float* taps, int B, int T_in, int L, int M, int Q, void* stream); and in-band forward error correction int hilc_pack_codes_10bit_fec(const int64_t* indices, const int* n_per_stream, const int* prev_in, int* prev_out, const int* action, const int* hold, uint8_t* packets, int* nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_fec_select(const uint8_t* packets, const int* fec, int* n_per_stream, uint8_t* out, int B, int T, int n_max, int m, void* stream); and discontinuous transmission with comfort noise int hilc_dtx_encode(const float* x, const int* action, const int* hold, int* run, int* kind, uint8_t* packets, int* nbytes, int64_t* indices, int* prev, const double* level_thr, double thr_vad, int B, int T, int order, int hangover, int sid_interval, int n_max, int stride, int prev_words, void* stream) and int hilc_cng_synth(const uint8_t* packets, const int* action, int* hold, int* state, float* wav, int* restore, const float* gains, int B, int T, int order, int stride, void* stream); and the transport header and jitter buffer int hilc_packet_header(const uint8_t* packets, const int* nbytes, const int* n_per_stream, const int* kind, const int* action, const int* hold, const int* counter_in, int* counter_out, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, void* stream) and int hilc_jitter_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, void* stream) with its adaptive form int hilc_jitter_adapt_step(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* hold, int* n_per_stream, int* lost, int* fec, uint8_t* packets, int* state, int* meta, int* ring, int B, int T, int n_max, int m, int order, int conceal, int depth, int capacity, int* adapt, int headroom, int max_late, int window, int resync, int force_windows, void* stream); and per-room mixing of the receiver's output int hilc_mix_levels(const float* wav, double* score, const int* action, int B, int L, void* stream) and int hilc_mix_rooms(const float* wav, const int* room, const double* score, int top_k, float* mixed, int* speakers, int B, int L, void* stream) with per-speaker levelling and a limiter int hilc_mix_gains(const float* wav, double* gains, double* power, const int* action, double gate2, double lo, double hi, double up, double down, double min_gain, double max_gain, double smooth, int B, int L, void* stream) and int hilc_mix_rooms_dyn(const float* wav, const int* room, const double* score, int top_k, const double* gains, double* limiter, double ceiling, double release, int sub, const int* action, float* mixed, int* speakers, int B, int L, void* stream); and quality-targeted variable bitrate of the sender int hilc_vbr_select(const float* z, int64_t* indices, const float* codebooks, const int* n_per_stream, const int* action, const int* hold, int* credit, int* n_eff, double* distortion, int B, int T, int C, int K, int Nq, int n, int n_lo, double rho, int stage_bits, int rate_bits, int burst_bits, void* stream); and receiver reports with loss-adaptive FEC int hilc_rx_report(const int* jitter_state, const int* action, int* rows, uint8_t* reports, int* due, int B, int window, int interval, void* stream) and int hilc_fec_adapt(const int* report, const int* action, const int* hold, int* rows, int* prev, int* fec_on, int B, int T, int m, int on_q8, int off_q8, int calm_reports, int timeout_hops, int initial_on, void* stream); and NACK with retransmission int hilc_nack_build(const int* jitter_state, const int* meta, const int* action, int* rows, uint8_t* nacks, int* due, int B, int capacity, int m, int rtt_hops, int retry_hops, int max_requests, int skip_fecable, void* stream) and int hilc_rtx_step(const uint8_t* packets, const int* nbytes, const int* nack_base, const int* nack_bitmap, const int* action, int* tags, int* ring, int* rows, uint8_t* out, int* out_nbytes, int B, int row_bytes, int history, int per_hop, void* stream); and report-driven rate control of the sender int hilc_rate_ceiling(const int* report, const int* action, const int* hold, const int* n_per_stream, const int* prev, int* rows, int* n_ceil, int B, int T, int n_max, int m, int header, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream) and int hilc_rate_charge(const int* nbytes, const int* rtx_nbytes, int* rows, int B, int per_hop, int burst_hops, void* stream); and the selective forwarding hop int hilc_forward_classify(const int* arrivals, const int* offsets, int max_arrivals, const int* action, int* rows, int* pick, int* pick_count, int B, int T, int n_max, int m, int order, int burst, int hang_hops, void* stream) and int hilc_forward_route(const int* arrivals, int max_arrivals, const int* action, const int* room, const int* layers, const int* sender_rows, const int* pick, const int* pick_count, int* routes, int* new_routes, int* rows, uint8_t* out, int* out_nbytes, int B, int T, int n_max, int m, int order, int fanout, int burst, int keep_fec, void* stream); and its downlink control int hilc_downlink_store(const int* arrivals, int max_arrivals, const int* action, const int* pick, const int* pick_count, int* tags, int* ring, int* rows, int B, int T, int n_max, int m, int burst, int history, void* stream) and int hilc_downlink_step(const int* routes, const int* new_routes, const uint8_t* in, const int* in_nbytes, const int* layers, const int* action, const int* report, const int* nack_base, const int* nack_bitmap, const int* tags, const int* ring, int* rows, int* memory, int* eff_layers, uint8_t* out, int* out_nbytes, uint8_t* rtx_out, int* rtx_nbytes, int* rtx_routes, int B, int T, int n_max, int m, int fanout, int burst, int keep_fec, int history, int per_hop, int rate_on, int min_bits, int max_bits, int start_bits, int high_q8, int low_q8, int increase_q8, int burst_hops, int timeout_hops, void* stream); and the audio level with level-based speaker selection int hilc_audio_level(const float* x, const double* thr, const int* hold, int* level, int B, int L, void* stream) and int hilc_forward_rank(const int* sd, const int* loud, const int* room, const int* action, const int* shadow_prev, int* shadow, int* rows, int B, int fanout, int hang_hops, int floor_level, int attack_shift, int decay_q8, int margin_db, void* stream); and the delay-based bandwidth estimate int hilc_rx_bwe(const int* arrivals, const int* offsets, const int* times, int max_arrivals, const int* action, int* rows, uint8_t* caps, int* due, int B, int T, int n_max, int m, int order, int min_bits, int max_bits, int window, int rate_window, int alpha_q8, int beta_q8, int increase_q16, int interval, int reset_ticks, void* stream) and int hilc_rate_cap(const int* cap, const int* action, const int* hold, int* rows, int* rate_rows, int B, int min_bits, int max_bits, int timeout_hops, void* stream); and SRTP packet protection int hilc_srtp_protect(const uint8_t* packets, const int* nbytes, const int* keys, int* rows, const int* action, uint8_t* out, int* out_nbytes, int B, int row_bytes, void* stream) and int hilc_srtp_unprotect(const int* arrivals, const int* offsets, int max_arrivals, const int* keys, int* rows, const int* action, int* plain, int B, int row_bytes, void* stream); and SRTP on the forwarding hop's routes int hilc_srtp_protect_routes(const uint8_t* rows, const int* nbytes, const int* routes, const int* new_routes, const int* action, const int* rekey_up, const int* rekey_down, const int* keys, int* route_rows, uint8_t* out, int* out_nbytes, int B, int fanout, int burst, int row_bytes, void* stream) */
 
 int hilc_abi_version(void);
 const char* hilc_error_string(int code);
@@ -726,6 +726,25 @@ int hilc_rvq_ema_update(float* embed, float* ema_num, float* ema_embed, const fl
 #define HILC_SRTP_WINDOW 64
 #define HILC_SRTP_MAX_ROW_BYTES (1 << 15)
 
+/* SRTP on the forwarding hop's routes (hilcodec_amd/forward_srtp.py).  Route row of a (listener, route), RT_WORDS words: RT_EPOCH (the
+ * restarts of the route's stream: its SSRC is the key row's KEY_SSRC + HILC_FORWARD_MAX_FANOUT * RT_EPOCH + route), the index state
+ * RT_ROC, RT_SL, RT_SEEN (0: nothing sent since the restart, 1: sent, SEEN_EXHAUSTED: restarted at MAX_EPOCH, sends nothing more),
+ * RT_WIN_LO, RT_WIN_HI (the receiver row's meaning: bit k is the index k below the highest one sent), then the counters RT_PROTECTED,
+ * RT_NOKEY, RT_STALE, RT_EXHAUSTED. */
+#define HILC_FSRTP_RT_EPOCH 0
+#define HILC_FSRTP_RT_ROC 1
+#define HILC_FSRTP_RT_SL 2
+#define HILC_FSRTP_RT_SEEN 3
+#define HILC_FSRTP_RT_WIN_LO 4
+#define HILC_FSRTP_RT_WIN_HI 5
+#define HILC_FSRTP_RT_PROTECTED 6
+#define HILC_FSRTP_RT_NOKEY 7
+#define HILC_FSRTP_RT_STALE 8
+#define HILC_FSRTP_RT_EXHAUSTED 9
+#define HILC_FSRTP_RT_WORDS 10
+#define HILC_FSRTP_SEEN_EXHAUSTED 2
+#define HILC_FSRTP_MAX_EPOCH ((1 << 28) - 1)
+
 /* selective forwarding (hilcodec_amd/forward.py).  Sender row of a slot, SD_WORDS words: SD_HANG (the hops it stays active, 0: not
  * active), SD_SINCE (the hops it has been active, at most 65535), then the counters SD_CODES, SD_SIDS, SD_MALFORMED, SD_OVERFLOW.
  * Listener row of a slot, LR_WORDS words: the counters LR_PACKETS, LR_BYTES, LR_TRIMMED, LR_SWITCHES.  A listener has at most
@@ -1301,6 +1320,32 @@ int hilc_srtp_protect(const uint8_t* packets, const int* nbytes, const int* keys
                       int* out_nbytes, int B, int row_bytes, void* stream);
 int hilc_srtp_unprotect(const int* arrivals, const int* offsets, int max_arrivals, const int* keys, int* rows, const int* action,
                         int* plain, int B, int row_bytes, void* stream);
+
+/* ---- SRTP on the forwarding hop's routes (additive under ABI 16) --------------------------------------------------------------------
+ * One entry point added WITHOUT a version bump.  The definition, bit for bit, is hilcodec_amd/forward_srtp.py (RouteModel).  The
+ * forwarder relays arrivals — reordered, retransmitted, from a route whose owner changes — so hilc_srtp_protect's sender rule does not
+ * hold for it; each (listener, route) keeps the receiver's index state instead and refuses what that state would call a replay.
+ * hilc_srtp_protect_routes: the forwarding hop's last launch.  rows uint8 [B][fanout][burst][row_bytes] and nbytes int32
+ * [B][fanout][burst]: the hop's final rows (hilc_forward_route's or hilc_downlink_step's), read only; routes, new_routes int32
+ * [B][fanout] as hilc_forward_route left them; action, rekey_up, rekey_down optional int32 [B] (a slot joined / given an uplink / a
+ * downlink key on this hop); keys int32 [B][HILC_SRTP_KEY_WORDS]: each listener's downlink key row; route_rows int32
+ * [B][fanout][HILC_FSRTP_RT_WORDS] (in place); out uint8 [B][fanout][burst][row_bytes + HILC_WIRE_SRTP_TAG_BYTES] and out_nbytes int32
+ * [B][fanout][burst]: every element written.  Per (b, j), t = routes[b][j]: new_routes[b][j], action[b], rekey_down[b], or (0 <= t < B
+ * and (action[t] or rekey_up[t])) non-zero restarts the route: RT_EPOCH += 1 and RT_ROC, RT_SL, RT_SEEN and the window are cleared; at
+ * HILC_FSRTP_MAX_EPOCH the epoch stays and RT_SEEN becomes HILC_FSRTP_SEEN_EXHAUSTED.  Then its rows in k order, nb = min(nbytes,
+ * row_bytes): nb < HILC_WIRE_TRANSPORT_HEADER: out zero, out_nbytes 0; no valid key: the same, RT_NOKEY += 1; an exhausted route: the
+ * same, RT_EXHAUSTED += 1; the ROC estimate v from (RT_SL, RT_ROC, SEQ) by RFC 3711 3.3.1 (the first packet: v = RT_ROC): v = -1, an
+ * index more than 63 below the highest sent, or its window bit set: the same, RT_STALE += 1; otherwise the window takes the index as
+ * hilc_srtp_unprotect's does, out is the packet protected under index v 2^16 + SEQ, the key row and SSRC = KEY_SSRC +
+ * HILC_FORWARD_MAX_FANOUT * RT_EPOCH + j (mod 2^32), zero past nb + 10 bytes, out_nbytes = nb + 10, RT_PROTECTED += 1.
+ * B >= 1, 1 <= fanout <= HILC_FORWARD_MAX_FANOUT, 1 <= burst <= HILC_FORWARD_MAX_BURST, HILC_WIRE_TRANSPORT_HEADER < row_bytes <=
+ * HILC_SRTP_MAX_ROW_BYTES (else HILC_ERR_SHAPE); NULL pointers (the three optional rows excepted): HILC_ERR_NULL.  One thread per
+ * output row, the rows of a route in one workgroup of 64 (64 / burst whole routes): each thread replays the integer rule for the rows in
+ * front of its own and runs its own packet's AES / SHA-1 chain; the thread of a route's last row writes the route row.  Byte rows are
+ * read and written as words where base and row width are multiples of 4 and byte by byte otherwise.  Integer only, no atomics. */
+int hilc_srtp_protect_routes(const uint8_t* rows, const int* nbytes, const int* routes, const int* new_routes, const int* action,
+                             const int* rekey_up, const int* rekey_down, const int* keys, int* route_rows, uint8_t* out, int* out_nbytes,
+                             int B, int fanout, int burst, int row_bytes, void* stream);
 
 #ifdef __cplusplus
 }
