@@ -512,10 +512,13 @@ def _early_branches(todo: Sequence[SpecBlockSpec], wav: Tensor, wav_hist: Option
     return early
 
 
-# The linear-addressing GEMM cores and the fused residual block address an activation tensor with 32-bit byte offsets
-# (csrc/gemm_epilogues.h: lin_ok, csrc/resblock.hip): a tensor of 4 GiB or more silently took the generic core / two
-# launches (10-20 % slower).  Clips are independent and results batch-invariant bit for bit (tests/test_gpu_fullsize.py),
-# so an offline batch whose LARGEST activation would reach the limit is run as equal clip chunks that each stay below it.
+# The linear-addressing GEMM cores address an activation tensor with 32-bit byte offsets (csrc/gemm_epilogues.h: lin_ok): with an
+# x of 4 GiB or more hilc_pw_conv / hilc_dws_conv / hilc_up_conv silently take the generic core (10-20 % slower, same bits).  Clips
+# are independent and results batch-invariant bit for bit (tests/test_gpu_fullsize.py), so an offline batch whose LARGEST activation
+# would reach the limit is run as equal clip chunks that each stay below it.  The fused OFFLINE block, chain and stage launches have no
+# such limit (64-bit offsets; only their streaming forms refuse 4 GiB), so a single clip above it — which cannot be chunked — still
+# runs them; a mono clip of 466 s has its 4 GiB tensors only inside and between the last two decoder stage launches, a launch outside
+# them that met one would take the generic core (DESIGN.md "Large tensors", tests/test_gpu_large.py).
 OFFSET_LIMIT_BYTES = 1 << 32
 
 
@@ -633,9 +636,9 @@ def run_encoder(es: EncoderSpec, wav: Tensor, caches: Optional[Sequence[Tensor]]
             continue
         x = _stage_blocks(st.blocks, x, cur, opts)
         k = st.down_dw_w.shape[1]
-        # (a shortcut the fused layer cannot take — a long hop at a stride above 8 — falls through to pointwise GEMM + depthwise conv, which can)
+        # (a shortcut the fused layer cannot take — a long hop at a stride above 8 — or a long hop whose x reaches 4 GiB falls through to pointwise GEMM + depthwise conv)
         if streaming:
-            fused = FUSE_STREAM and ops.dws_conv_stream_profitable(x.shape[2], k, st.ratio, defer, x.shape[0], st.down_dw_w.shape[0])
+            fused = FUSE_STREAM and ops.dws_conv_stream_profitable(x.shape[2], k, st.ratio, defer, x.shape[0], st.down_dw_w.shape[0], x.shape[1])
         else:
             fused = FUSE_DWS and k == 2 * st.ratio
         x = _dws_layer(cur, fused, x, st.down_pw_wt, st.down_dw_w, st.down_dw_b, res=(lambda: branch_of(nxt)) if defer else None,

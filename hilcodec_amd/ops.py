@@ -1619,12 +1619,16 @@ def dws_conv(x: Tensor, wt: Tensor, dw_w: Tensor, dw_b: Optional[Tensor] = None,
                          bool(out_elu))
 
 
-def dws_conv_stream_supported(T: int, k: int, stride: int, has_res: bool = False, B: int = 1, M: int = 1) -> bool:
+def dws_conv_stream_supported(T: int, k: int, stride: int, has_res: bool = False, B: int = 1, M: int = 1, K: int = 1) -> bool:
     """whole-clip tiles: a hop of at most 128 samples per stream, a multiple of the stride; longer hops for the
-    down-sampling form (k = 2 * stride): per-clip tiles with a recomputed halo — which take a shortcut `res` only in their
-    flat-tile form (csrc/gemm.hip: stride <= 8, fewer than 2^31 outputs, a tile holds at most two stream starts)"""
+    down-sampling form (k = 2 * stride): per-clip tiles with a recomputed halo — the linear-addressing core only, so an x `[B,K,T]` of
+    2^32 bytes or more is refused (csrc/gemm.hip: `lin_ok`) — which take a shortcut `res` only in their
+    flat-tile form (csrc/gemm.hip: stride <= 8, fewer than 2^31 outputs, a tile holds at most two stream starts).  The byte bound needs the
+    caller's B and K: with the defaults (1, 1) it never binds, and a long hop that the library then refuses raises from the wrapper."""
     if T > 128:
         if not (k == 2 * stride and stride <= 16 and T % 4 == 0 and T % stride == 0):
+            return False
+        if B * K * T * 4 >= (1 << 32):
             return False
         if not has_res:
             return True
@@ -1637,12 +1641,12 @@ def dws_conv_stream_supported(T: int, k: int, stride: int, has_res: bool = False
     return T % stride == 0 and stride <= k <= 32
 
 
-def dws_conv_stream_profitable(T: int, k: int, stride: int, has_res: bool = False, B: int = 1, M: int = 1) -> bool:
+def dws_conv_stream_profitable(T: int, k: int, stride: int, has_res: bool = False, B: int = 1, M: int = 1, K: int = 1) -> bool:
     """where the fused hop beats pointwise GEMM + cached depthwise conv (measured, tools/layer_profile.py
     --mode streaming): not for 2- or 3-sample hops of the tiled core, whose depthwise taps are nearly all cache reads."""
     if T == 1 and stride == 1:
         return k <= 32  # single-frame layers: the latency-bound 32 x 32-tile kernel (csrc/frame1.hip), taps in its epilogue
-    return dws_conv_stream_supported(T, k, stride, has_res, B, M) and T // stride >= 1 and T >= 4
+    return dws_conv_stream_supported(T, k, stride, has_res, B, M, K) and T // stride >= 1 and T >= 4
 
 
 def _state_out(given: Optional[Tensor], like: Tensor, *shape) -> Tensor:

@@ -21,6 +21,9 @@
  *    it word by word, with the same results bit for bit (the one exception is stated at hilc_conv_post); where it names operands
  *    that are "refused", a pointer that is not 16-byte aligned returns HILC_ERR_UNSUPPORTED in front of the first launch.  The
  *    table of every (entry, operand) pair is DESIGN.md, "Pointer alignment".
+ *  - size: an entry's "Size:" line says what it does with an activation tensor of 4 GiB or more (byte offsets that no longer fit 32 bits):
+ *    the same kernel, another core with the same results bit for bit, or HILC_ERR_UNSUPPORTED in front of the first launch with nothing
+ *    written.  Dimensions themselves are ints: B, C, T and T * stride stay below 2^31.  DESIGN.md, "Large tensors".
  *  - prologue  pro(v) = in_elu ? ELU(v * in_scale) : v * in_scale   (Scale + ELU modules,
  *    `models/hilcodec/modules/seanet.py:165-178`, torch.nn.ELU(alpha=1));
  *    it is applied to `x` only — histories hold already-activated samples, as the reference's
@@ -55,7 +58,8 @@ const char* hilc_last_hip_error(void);
  * 202-236`) plus the ELU / Scale in front of it (`seanet.py:26-52,322-340`) and, with `res`, the
  * `x.add_(y.mul_(scale))` of SpecBlock (`seanet.py:241-246`).
  * wt is the folded weight TRANSPOSED to `[K][M]` (k-major).  bias, res may be NULL.  res may alias y.
- * Alignment: x, y and res must be 16-byte aligned for the fast path; wt is refused unless it is; bias needs only the 4 bytes of a float. */
+ * Alignment: x, y and res must be 16-byte aligned for the fast path; wt is refused unless it is; bias needs only the 4 bytes of a float.
+ * Size: x of 4 GiB or more takes the generic core (same fmaf chains, same bits); y / res of 4 GiB or more with a smaller x keep the fast path. */
 int hilc_pw_conv(const float* x, const float* wt, const float* bias, const float* res, float* y,
                  int B, int K, int M, int T, float in_scale, int in_elu, float out_scale, void* stream);
 
@@ -67,7 +71,8 @@ int hilc_pw_conv(const float* x, const float* wt, const float* bias, const float
  * ksize = 2*stride (encoder down-sampling, `seanet.py:322-340`; res/out_elu/out_scale unused there).
  * The [M x T] intermediate h lives only in LDS: one HBM read of x and one write of y per block half.
  * Alignment: x, and for ksize 5 y and res, must be 16-byte aligned for the fast path; wt is refused unless it is; dw_w, dw_b (and y of the
- * strided form) need only the 4 bytes of a float. */
+ * strided form) need only the 4 bytes of a float.
+ * Size: x of 4 GiB or more takes the generic core (same bits), for both kernel shapes. */
 int hilc_dws_conv(const float* x, const float* wt, const float* dw_w, const float* dw_b, const float* res,
                   float* y, int B, int K, int M, int T, int ksize, int stride, float in_scale, int in_elu,
                   float out_scale, int out_elu, void* stream);
@@ -84,7 +89,8 @@ int hilc_dws_conv_wave_row(int B, int M, int T, int has_res);
  * Replaces: `seanet.py:424-441` (Scale, ELU, SConvTranspose1d, SConv1d k=1 with bias). Requires
  * (Tin*stride) % 4 == 0 and M % 4 == 0 (else HILC_ERR_UNSUPPORTED: use hilc_dw_convtr + hilc_pw_conv).
  * Alignment (the three entry points of this stage): tr_w, tr_w_expanded and y must be 16-byte aligned for the fast path; wt is refused
- * unless it is, before anything is written; x, hist, hist_out and bias need only the 4 bytes of a float. */
+ * unless it is, before anything is written; x, hist, hist_out and bias need only the 4 bytes of a float.
+ * Size (the three entry points): x of 4 GiB or more, or 2^31 output columns B * Tin * stride, take the generic core (same bits). */
 int hilc_up_conv(const float* x, const float* tr_w, const float* wt, const float* bias, float* y,
                  int B, int K, int M, int Tin, int stride, float in_scale, int in_elu, void* stream);
 
@@ -111,7 +117,9 @@ int hilc_up_conv_expanded(const float* x, const float* hist, float* hist_out, co
  * the new cache (must not alias hist).  A tile holds whole clips, so nothing is recomputed.
  * Alignment: T <= 128: x, and for ksize 5 y, res, hist and hist_out, must be 16-byte aligned for the fast path; wt is refused unless it
  * is, and so is dw_w for ksize 16 / stride 8 and ksize 10 / stride 5 (a row's taps are read as 16- / 8-byte words).  T > 128: x and wt
- * are refused unless 16-byte aligned.  Everything else needs only the 4 bytes of a float. */
+ * are refused unless 16-byte aligned.  Everything else needs only the 4 bytes of a float.
+ * Size: T > 128: an x of 4 GiB or more is HILC_ERR_UNSUPPORTED, nothing written (that form has the linear core only; fall back to hilc_pw_conv +
+ * hilc_dw_conv, same bits).  T <= 128: it takes the generic core (from the launcher; not run at 4 GiB by the tests). */
 int hilc_dws_conv_stream(const float* x, const float* wt, const float* dw_w, const float* dw_b, const float* hist,
                          float* hist_out, const float* res, float* y, int B, int K, int M, int T, int ksize,
                          int stride, float in_scale, int in_elu, float out_scale, int out_elu, void* stream);
@@ -124,7 +132,10 @@ int hilc_dws_conv_stream(const float* x, const float* wt, const float* dw_w, con
  * Replaces: SEANetResnetBlock.forward (`seanet.py:129-148`) with skip='identity', kernel 5.
  * hilc_resblock_supported(C, T) tells the caller whether this specialisation exists.
  * Alignment (hilc_resblock, _stream, _balanced): x, y, w1t, w2t and the four caches are refused unless 16-byte aligned; the depthwise
- * taps and biases need only the 4 bytes of a float. */
+ * taps and biases need only the 4 bytes of a float.
+ * Size: hilc_resblock (and hilc_resblock_balanced with streaming = 0) takes any size, 64-bit offsets.  hilc_resblock_stream (and streaming = 1)
+ * walks a flat 32-bit column space: B * C * T * 4 >= 2^32 is HILC_ERR_UNSUPPORTED (fall back to two hilc_dws_conv_stream or to hilc_pw_conv +
+ * hilc_dw_conv launches per half). */
 int hilc_resblock(const float* x, const float* w1t, const float* dw1_w, const float* dw1_b, const float* w2t,
                   const float* dw2_w, const float* dw2_b, float* y, int B, int C, int T, float pre_scale,
                   float out_scale, void* stream);
@@ -178,7 +189,9 @@ int hilc_resblock_balanced(const float* x, const float* w1t, const float* dw1_w,
  * the carry slots of a second do not fit LDS); nblk = 2, or 3 at the decoder's widths (96, 192, streaming 768, offline 384).
  * Else HILC_ERR_UNSUPPORTED: launch the blocks one by one.
  * Alignment: x, y and of every block w1t, w2t and (streaming) the four caches are refused unless 16-byte aligned; the depthwise taps and
- * biases need only the 4 bytes of a float. */
+ * biases need only the 4 bytes of a float.
+ * Size: streaming = 0 takes any size; streaming = 1 refuses B * C * T * 4 >= 2^32 (HILC_ERR_UNSUPPORTED; hilc_resblock_chain_supported knows no
+ * batch size and cannot say so: launch the blocks one by one). */
 typedef struct hilc_resblock_params {
   const float* w1t; const float* dw1_w; const float* dw1_b;
   const float* w2t; const float* dw2_w; const float* dw2_b;
@@ -204,7 +217,9 @@ int hilc_resblock_chain(const float* x, float* y, const hilc_resblock_params* bl
  * streams, twelve waves — rounds 4-5: nblk = 1 on 64-column halo tiles),
  * C = 192 with r = 4 and C = 96 with r = 2 (streaming hops and, with streaming = 0, the offline model: hist* ignored); nblk 1..3.
  * Alignment: y, up->tr_w, up->w_lo, up->w_hi and the blocks' operands named at hilc_resblock_chain are refused unless 16-byte aligned;
- * up->x, up->hist, up->hist_out, up->bias and the blocks' taps and biases need only the 4 bytes of a float. */
+ * up->x, up->hist, up->hist_out, up->bias and the blocks' taps and biases need only the 4 bytes of a float.
+ * Size (hilc_decoder_stage and hilc_decoder_stage_post): streaming = 0 takes any size; streaming = 1 refuses B * C * T * 4 >= 2^32
+ * (HILC_ERR_UNSUPPORTED in front of the launch). */
 typedef struct hilc_up_params {
   const float* x; const float* tr_w; const float* w_lo; const float* w_hi; const float* bias;
   const float* hist; float* hist_out;
@@ -251,7 +266,8 @@ int hilc_decoder_stage_post(const hilc_up_params* up, const hilc_resblock_params
  * blocks and hilc_dws_conv[_stream] instead).
  * Alignment: x, down->w_lo, w_hi, res, y, hist, hist_out, the blocks' operands named at hilc_resblock_chain and, for C = 256 / 512,
  * down->dw_w are refused unless 16-byte aligned; down->dw_b, down->dw_w of the narrow stages and the blocks' taps and biases need only the
- * 4 bytes of a float. */
+ * 4 bytes of a float.
+ * Size: streaming = 0 takes any size; streaming = 1 refuses B * 2C * T * 4 >= 2^32 (HILC_ERR_UNSUPPORTED in front of the launch). */
 typedef struct hilc_down_params {
   const float* w_lo; const float* w_hi; const float* dw_w; const float* dw_b;
   const float* hist; float* hist_out; const float* res; float* y;
@@ -270,7 +286,8 @@ int hilc_encoder_stage(const float* x, const hilc_resblock_params* blocks, int n
  * streams, T >= 128 (a 128-column tile then holds at most one stream start: its waveform segment is staged as two pieces, each with the 63
  * samples in front of it — a stream's history at t = 0), with every cache of hilc_encoder_stage(streaming).
  * Alignment: spec->dft_packed, spec->pw_packed, down->w_lo, w_hi, res, y, hist, hist_out and the blocks' operands named at
- * hilc_resblock_chain are refused unless 16-byte aligned; spec->wav, spec->hist and every other operand need only the 4 bytes of a float. */
+ * hilc_resblock_chain are refused unless 16-byte aligned; spec->wav, spec->hist and every other operand need only the 4 bytes of a float.
+ * Size: streaming = 0 takes any size; streaming = 1 refuses B * 128 * T * 4 >= 2^32 (HILC_ERR_UNSUPPORTED in front of the launch). */
 typedef struct hilc_spec0_params {
   const float* wav;         /* [B][T] */
   const float* dft_packed; const float* nyq_sin; const float* pw_packed; const float* bias;
@@ -294,7 +311,9 @@ int hilc_encoder_stage0(const hilc_spec0_params* spec, const hilc_resblock_param
  * 417-419`), CausalConv1d (`causal_layers.py:147-165`) and the residual tail of
  * SEANetResnetBlock.forward (`seanet.py:144-148`). res may alias y.
  * Alignment: x and y must be 16-byte aligned for the fast path (ksize 5, stride 1, T % 4 == 0); everything else needs only the 4 bytes
- * of a float. */
+ * of a float.
+ * Size: any (64-bit offsets), as for hilc_dw_convtr, hilc_conv_pre, hilc_conv_post and hilc_l2norm below — and, from its launcher only (not run at
+ * 4 GiB by the tests), hilc_tail. */
 int hilc_dw_conv(const float* x, const float* hist, const float* w, const float* bias, const float* res,
                  float* y, float* hist_out, int B, int C, int T, int ksize, int stride,
                  float in_scale, int in_elu, float out_scale, int out_elu, void* stream);
@@ -334,7 +353,8 @@ int hilc_conv_post(const float* x, const float* hist, const float* w, const floa
  * basis_t: `[n_fft][m_pad]` fp32, row n holds (cos_0, sin_0, cos_1, sin_1, ...)*hann for sample n,
  *          m_pad = round_up(n_fft+2, 32), zero padded (host-built from the reference's basis).
  * Replaces: CausalSTFT (`conv.py:285-358`, `causal_layers.py:72-144`) + `seanet.py:224-236`.
- * Alignment: basis_t is refused unless 16-byte aligned; wav, hist and spec need only the 4 bytes of a float. */
+ * Alignment: basis_t is refused unless 16-byte aligned; wav, hist and spec need only the 4 bytes of a float.
+ * Size: any (64-bit offsets; both the flat and the per-clip segment form). */
 int hilc_stft_logmag(const float* wav, const float* hist, int hist_len, const float* basis_t, float* spec,
                      int B, int T, int n_fft, int hop, float mean, float std, int normalize, void* stream);
 
@@ -353,7 +373,8 @@ int hilc_stft_logmag(const float* wav, const float* hist, int hist_len, const fl
  * nyq_sin `[n_fft]`: the sin_{N/2} row of the reference basis (|.| <= 1.4e-4, evaluated as a scalar chain).
  * hilc_spec_block_packed_floats(n_fft, which) = size of a packed operand.
  * Alignment (hilc_spec_block and hilc_spec_block_conv_pre): x, y, dft_packed and pw_packed are refused unless 16-byte aligned; wav, hist,
- * nyq_sin, bias, pre_w and pre_b need only the 4 bytes of a float. */
+ * nyq_sin, bias, pre_w and pre_b need only the 4 bytes of a float.
+ * Size: any (64-bit offsets). */
 int hilc_spec_block_supported(int n_fft, int hop, int C, int T);
 int hilc_spec_block_packed_floats(int n_fft, int which);
 int hilc_spec_block_pack(const float* w, float* packed, int K, int n_fft, int which, void* stream);
@@ -398,7 +419,8 @@ int hilc_l2norm(const float* x, float* y, int B, int C, int T, float eps, float 
  * on the VALU form too (16 frames per workgroup; the caller's switch should an fp32 MFMA ever stop being a sequential fmaf chain
  * over ascending k); any other bit: HILC_ERR_UNSUPPORTED.
  * Alignment: codebooks_t and norms must be 16-byte aligned for the matrix-pipe form (else large batches keep the VALU form: same indices);
- * everything else needs only the 4 bytes of a float. */
+ * everything else needs only the 4 bytes of a float.
+ * Size: any, in both forms and in hilc_rvq_decode (64-bit offsets; the frame count B * T is a long). */
 #define HILC_RVQ_VALU_ONLY 1
 int hilc_rvq_encode(const float* z, const float* codebooks, const float* codebooks_t, const float* norms,
                     int64_t* indices, float* q, float* frame_err, int B, int C, int T, int K, int Nq, int n,

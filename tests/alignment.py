@@ -155,3 +155,45 @@ def ref_resblock(x, blk, hist):
 def ref_l2norm(x, eps, scale, channel_last_out):
     y = x / x.pow(2).sum(dim=1, keepdim=True).sqrt().clamp_min(eps) * scale
     return y.transpose(1, 2).contiguous() if channel_last_out else y
+
+
+# ---- compositions for the chain and stage launches (tests/test_gpu_alignment.py, test_gpu_redzone.py, test_gpu_large.py) -----------
+def ref_blocks(a, x, streaming, out):
+    for j, b in enumerate(a["blocks"]):
+        x, new = ref_resblock(x, b, a["caches"][j] if streaming else None)
+        if streaming:
+            out[f"b{j}.hist1_out"], out[f"b{j}.hist2_out"] = new
+    return x
+
+
+def ref_encoder_stage(a, streaming, stage0, r, in_scale, N=64):
+    """hilc_encoder_stage / hilc_encoder_stage0: [first conv + SpecBlock,] the blocks, the down-sampling layer"""
+    out = {}
+    if stage0:
+        x = ref_conv_pre(a["wav"], a["whist"], a["pre_w"], a["pre_b"], 1 / 0.1122080159)
+        x = ref_spec_block(a["wav"], a["whist"], a["basis_t"], a["swt"], a["sbias"], x, N, 1, -4.0, 2.8, 1, 0.37)
+    else:
+        x = a["x"]
+    x = ref_blocks(a, x, streaming, out)
+    y, h = ref_dws(x, a["wd"], a["ddw"], a["ddb"], a["dhist"], a["dres"], r, in_scale, True, 1.0, False)
+    out["down.y"] = y
+    if streaming:
+        out["down.hist_out"] = h
+    return out
+
+
+def ref_decoder_stage(a, streaming, post, r):
+    """hilc_decoder_stage / hilc_decoder_stage_post: the up-sampling layer, the blocks[, the closing conv]"""
+    out = {}
+    y, h = ref_up_conv(a["xin"], a["uhist"], a["tw"], a["wu"], a["bu"], r, 0.7071, True)
+    if streaming:
+        out["up.hist_out"] = h
+    y = ref_blocks(a, y, streaming, out)
+    if post:
+        w, h = ref_conv_post(y, a["phist"], a["pw"], a["pb"], 0.5, True, 0.1122, True)
+        out["post.wav"] = w
+        if streaming:
+            out["post.hist_out"] = h
+    else:
+        out["y"] = y
+    return out

@@ -348,6 +348,10 @@ def test_dws_conv_stream_mirror_knows_which_long_hops_take_a_shortcut():
     assert ops.dws_conv_stream_supported(360, 18, 9) and not ops.dws_conv_stream_profitable(360, 18, 9, True, 4, 64)
     assert not ops.dws_conv_stream_supported(320, 4, 2, True, 1 << 24, 128)                                           # 2^31 outputs
     assert ops.dws_conv_stream_supported(40, 10, 5, True) and ops.dws_conv_stream_supported(8, 16, 8, True)         # short hops: whole-clip tiles
+    # long hops run on the linear-addressing core only: an x [B,K,T] of 2^32 bytes is refused (csrc/gemm.hip: lin_ok), with or without a shortcut
+    assert ops.dws_conv_stream_supported(160, 8, 4, True, 419430, 32, 16) and not ops.dws_conv_stream_supported(160, 8, 4, True, 419431, 32, 16)
+    assert ops.dws_conv_stream_supported(160, 8, 4, False, 419430, 32, 16) and not ops.dws_conv_stream_profitable(160, 8, 4, False, 419431, 32, 16)
+    assert ops.dws_conv_stream_supported(8, 16, 8, True, 1 << 24, 1024, 512)                                         # short hops fall back to the generic core
 
 
 def test_exec_options_are_launch_structure_only():
@@ -377,7 +381,7 @@ def test_clip_chunks_keep_activations_below_32bit_offsets():
         ch = engine._clip_chunks(b, per_clip)
         assert ch[0][0] == 0 and ch[-1][1] == b and all(a[1] == c[0] for a, c in zip(ch, ch[1:]))
         assert all((hi - lo) * per_clip * 4 < 2 ** 32 for lo, hi in ch) and max(hi - lo for lo, hi in ch) - min(hi - lo for lo, hi in ch) <= len(ch)
-    assert engine._clip_chunks(4, 2 ** 31) == [(0, 1), (1, 2), (2, 3), (3, 4)]          # a single clip above the limit still runs (generic cores)
+    assert engine._clip_chunks(4, 2 ** 31) == [(0, 1), (1, 2), (2, 3), (3, 4)]          # a single clip above the limit still runs: the fused offline stage launches take any size, the launches outside them the generic cores (tests/test_gpu_large.py)
 
 
 def test_streaming_model_takes_a_weight_standardised_checkpoint(golden):

@@ -413,12 +413,7 @@ def block_structs(e, p, raw, streaming):
     return arr
 
 
-def ref_blocks(a, x, streaming, out):
-    for j, b in enumerate(a["blocks"]):
-        x, new = A.ref_resblock(x, b, a["caches"][j] if streaming else None)
-        if streaming:
-            out[f"b{j}.hist1_out"], out[f"b{j}.hist2_out"] = new
-    return x
+ref_blocks = A.ref_blocks          # (the compositions live in tests/alignment.py: tests/test_gpu_large.py shares them)
 
 
 def _resblock(name, B, C, T, streaming):
@@ -538,18 +533,7 @@ def _enc(name, B, C, T, r, n, streaming, stage0=False):
             return Built(ins, outs, aux, call)
 
         def ref(a):
-            out = {}
-            if stage0:
-                x = A.ref_conv_pre(a["wav"], a["whist"], a["pre_w"], a["pre_b"], 1 / 0.1122080159)
-                x = A.ref_spec_block(a["wav"], a["whist"], a["basis_t"], a["swt"], a["sbias"], x, N, 1, -4.0, 2.8, 1, 0.37)
-            else:
-                x = a["x"]
-            x = ref_blocks(a, x, streaming, out)
-            y, h = A.ref_dws(x, a["wd"], a["ddw"], a["ddb"], a["dhist"], a["dres"], r, in_scale, True, 1.0, False)
-            out["down.y"] = y
-            if streaming:
-                out["down.hist_out"] = h
-            return out
+            return A.ref_encoder_stage(a, streaming, stage0, r, in_scale, N)
         return build, ref
 
 
@@ -610,19 +594,7 @@ def _dec(name, B, C, Tin, r, n, streaming, post=False):
             return Built(ins, outs, aux, call)
 
         def ref(a):
-            out = {}
-            y, h = A.ref_up_conv(a["xin"], a["uhist"], a["tw"], a["wu"], a["bu"], r, 0.7071, True)
-            if streaming:
-                out["up.hist_out"] = h
-            y = ref_blocks(a, y, streaming, out)
-            if post:
-                w, h = A.ref_conv_post(y, a["phist"], a["pw"], a["pb"], 0.5, True, 0.1122, True)
-                out["post.wav"] = w
-                if streaming:
-                    out["post.hist_out"] = h
-            else:
-                out["y"] = y
-            return out
+            return A.ref_decoder_stage(a, streaming, post, r)
         return build, ref
 
 
