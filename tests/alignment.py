@@ -1,4 +1,4 @@
-"""Helpers of the pointer-alignment tests (tests/test_alignment_cpu.py, tests/test_gpu_alignment.py).
+"""Helpers of the pointer-alignment tests (tests/test_alignment_cpu.py, tests/test_gpu_alignment.py; the row table: tests/entry_rows.py).
 
 `skew(t, k)`: a contiguous copy of `t` whose first element sits `4 * k` bytes behind a 16-byte boundary — what a caller gets from
 `rec[:, :, k:k + T]` with B = 1, or from a cache kept as a view.  The references below are the plain definitions of the entry
@@ -157,7 +157,7 @@ def ref_l2norm(x, eps, scale, channel_last_out):
     return y.transpose(1, 2).contiguous() if channel_last_out else y
 
 
-# ---- compositions for the chain and stage launches (tests/test_gpu_alignment.py, test_gpu_redzone.py, test_gpu_large.py) -----------
+# ---- compositions for the chain and stage launches (the rows of tests/entry_rows.py, the families of tests/large_families.py) ------
 def ref_blocks(a, x, streaming, out):
     for j, b in enumerate(a["blocks"]):
         x, new = ref_resblock(x, b, a["caches"][j] if streaming else None)

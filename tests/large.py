@@ -1,5 +1,6 @@
 """Helpers of the large-tensor tests (tests/test_large_cpu.py, tests/test_gpu_large.py): entry points on activation tensors just
-below and at 4 GiB, where byte offsets stop fitting 32 bits ("Large tensors").
+below and at 4 GiB, where byte offsets stop fitting 32 bits ("Large tensors").  The cases are here; what builds a case's
+operands, call and reference is in tests/large_families.py.
 
 The method.  Every entry point is causal with a short receptive field, so an input that is periodic in time with period P gives, after
 the receptive field, an output that is periodic with P (times the op's rate).  A float64 reference of THREE periods then stands for
@@ -203,7 +204,7 @@ CASES = {}
 
 
 def case(name, family, tolrow, P, layers, below, at, b3=None, exact=True, stream_guard=None, **kw):
-    """family: the builder of tests/test_gpu_large.py; tolrow: the row of tests/test_gpu_alignment.py whose tolerance the case uses;
+    """family: the builder of tests/large_families.py; tolrow: the row of tests/entry_rows.py whose tolerance the case uses;
     layers: for `receptive_field`; below / at / b3: the dimensions of the sizes; exact: "below" and "at" promise the same bits;
     stream_guard: the product (in bytes) a streaming form's launch path refuses from 2^32 on — None: an offline / flat form"""
     sizes = {"below": dict(below), "at": dict(at)}

@@ -265,7 +265,7 @@ def slot_map(size: int = 4) -> Dict[int, int]:
 # ---------------------------------------------------------------- the jitter receiver's arrivals
 def network_trace(seed: int, hops: int, size: int = 4):
     """per hop (network slots, packets uint8 [A, tbytes], byte counts) of one class's senders: one Network, events left to the scripts"""
-    from tests.test_gpu_jitter_adapt import Network
+    from tests.hops import Network
     net = Network(size, N, M, K, 1, seed=seed, **NETWORK)
     return [net.hop()[:3] for _ in range(hops)]
 

@@ -4,7 +4,8 @@
 `StateBlock`: [front zone | operand | back zone].  The zones hold a pattern that shows when it is read — a quiet NaN for the float
 types, 0 or 1 for the integer types (two runs: a stray integer read can equal the baseline in at most one of them, and neither
 value can send a kernel that took it for an index to a wild address) — and `check(zone)` shows when one was written.  No GPU code
-of its own: torch fills, views and compares, on whatever device `t` is on."""
+of its own: torch fills, views and compares, on whatever device `t` is on.  The rows that run inside the zones are `ALL_ROWS` of
+tests/entry_rows.py and `MISC` of tests/slot_cases.py; the byte-row entry points are named below."""
 import types
 
 import torch
@@ -14,6 +15,13 @@ from tests.alignment import skew_bytes
 NAN32 = 0x7FC5A5A5                      # quiet NaNs with a payload no kernel produces
 NAN64 = 0x7FF8A5A5A5A5A5A5
 INT_FILLS = (0, 1)
+
+# what tests/test_gpu_redzone.py runs besides the C-ABI rows (tests/entry_rows.py) and the per-slot float cases (tests/slot_cases.py),
+# named here for the ledger of tests/test_redzone_cpu.py: the kernels that move variable-length byte rows, one case each ...
+BYTE_ENTRY_POINTS = ("pack_codes_10bit", "pack_codes_10bit_fec", "rvq_decode_packed", "packet_header", "jitter_step", "srtp_protect",
+                     "srtp_unprotect", "srtp_protect_routes")
+# ... and the same kind of case for entry points that were on the ledger's LATER list
+MORE_ENTRY_POINTS = ("fec_select", "conceal_prepare")
 
 
 def zone_bytes(nbytes: int) -> int:

@@ -7,7 +7,7 @@ import torch
 
 import hilcodec_amd
 from hilcodec_amd import engine, ops, synth
-from tests.test_plan_cpu import _Recorder, _launches, _specs
+from tests.plan import Recorder, launches, specs
 
 OPS = ["spec_block", "spec_block_conv_pre", "spec_block_pack", "pw_conv", "dws_conv", "dws_conv_stream", "up_conv_expand_taps", "up_conv", "resblock_pack", "resblock", "dw_conv",
        "dw_convtr", "conv_pre", "conv_post", "stft_logmag", "tail", "l2norm", "rvq_encode", "rvq_decode",
@@ -114,7 +114,7 @@ def test_dynamo_fullgraph_traces_the_module_classes():
 @pytest.mark.parametrize("delta", [-1, 1], ids=["one too few", "one too many"])
 @pytest.mark.parametrize("half", ["encoder", "decoder"])
 def test_a_cache_list_of_the_wrong_length_is_refused_before_the_first_launch(half, delta, which):
-    es, ds = _specs("hil_speech", True)
+    es, ds = specs("hil_speech", True)
     B = 37
     if half == "encoder":
         shapes, x = engine.encoder_cache_shapes(es), torch.empty(B, 1, 320, device="meta")
@@ -125,7 +125,7 @@ def test_a_cache_list_of_the_wrong_length_is_refused_before_the_first_launch(hal
     good = [torch.empty(B, c, l, device="meta") for c, l in shapes]
     bad = good[:-1] if delta < 0 else good + [torch.empty_like(good[-1])]
     good_out, bad_out = [torch.empty_like(t) for t in good], [torch.empty_like(t) for t in bad]
-    rec = _Recorder()
+    rec = Recorder()
     for label, seq in (("x", x), ("good", good), ("bad", bad), ("good_out", good_out), ("bad_out", bad_out), ("es", es), ("ds", ds)):
         rec.name_tree(seq, label)
     with rec, pytest.raises(RuntimeError, match=f"expected {len(good)} {which}, got {len(good) + delta}"):
@@ -133,7 +133,7 @@ def test_a_cache_list_of_the_wrong_length_is_refused_before_the_first_launch(hal
     assert not rec.rows         # nothing reached the dispatcher, no hilcodec op and no ATen op
     with rec:                   # ... and the right lists run
         _, new = run(good, good_out)
-    assert len(new) == len(good) and _launches(rec.rows)
+    assert len(new) == len(good) and launches(rec.rows)
 
 
 def test_the_cursor_reports_caches_kept_out_of_step():

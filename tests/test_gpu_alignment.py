@@ -1,8 +1,9 @@
 """Every entry point of the hot path on 4-byte-aligned views: fall back or refuse ("Pointer alignment").
 
-One row per entry point and shape.  A row builds its operands on the device, calls the C ABI with raw pointers, and has a plain
-float64 reference on the CPU (tests/alignment.py).  The call runs once with every operand 16-byte aligned, then once per operand
-and k = 1, 2, 3 with only that operand moved 4 * k bytes off (`skew`).  The row's table gives the audited class of every operand:
+One row per entry point and shape: the `BASE` rows of tests/entry_rows.py, which holds the table and what runs a row.  A row builds
+its operands on the device, calls the C ABI with raw pointers, and has a plain float64 reference on the CPU (tests/alignment.py).
+The call runs once with every operand 16-byte aligned, then once per operand and k = 1, 2, 3 with only that operand moved 4 * k
+bytes off (`skew`).  The row's table gives the audited class of every operand:
 
   S / F  the call succeeds, is within the op's tolerance of the float64 reference and — caches and every other output included —
          `torch.equal` to the aligned call (the fall-backs promise the same fmaf chains);
@@ -12,794 +13,15 @@ and k = 1, 2, 3 with only that operand moved 4 * k bytes off (`skew`).  The row'
 The tolerance of a row is the one the op's own test in tests/test_gpu_ops.py uses; it may not be below 4 x the rounding of the
 reference itself (float32 against float64 on the CPU, the `FLOORS` table as measured, asserted again at run time).
 Copyable R operands are tested a second time through `hilcodec_amd.ops`, where the wrapper copies them: equal to the aligned call."""
-import ctypes
-import types
-
-import numpy as np
 import pytest
 import torch
 
 from hilcodec_amd import synth
-from tests import alignment as A
 from tests.alignment import skew
+from tests.entry_rows import BASE, BLK, FLOORS, KS, ROWS, SENT, aligned, built, check_ok, env, raw_blocks, rnd, run, sentinel  # noqa: F401  (env: the fixture)
+from tests.slot_cases import CASES, MISC, misc_run
 
 pytestmark = pytest.mark.gpu
-
-SENT = -12345.5          # what every caller-owned output holds before a call (no kernel here produces it)
-RS = 0.5773502691896258
-KS = (1, 2, 3)
-
-
-def rnd(seed, *shape):
-    return torch.from_numpy(synth.normalish(seed, int(np.prod(shape)))).view(*shape)
-
-
-@pytest.fixture(scope="module")
-def env():
-    from hilcodec_amd import _lib, fold, ops
-    return types.SimpleNamespace(ops=ops, fold=fold, lib=_lib.lib, L=_lib, dev=torch.device("cuda:0"),
-                                 stream=lambda: torch.cuda.current_stream().cuda_stream)
-
-
-def void(obj):
-    return ctypes.cast(ctypes.pointer(obj), ctypes.c_void_p)
-
-
-class Built:
-    """ins: operand -> aligned device tensor (None = NULL); outs: operand -> shape of a caller-owned output; aux: what `ref` needs
-    (CPU float32 tensors and scalars); call(p) -> return code, p = operand -> pointer."""
-
-    def __init__(self, ins, outs, aux, call):
-        self.ins, self.outs, self.aux, self.call = ins, outs, aux, call
-
-
-def cast(aux, dtype):
-    def one(v):
-        if torch.is_tensor(v):
-            return v.to(dtype) if v.is_floating_point() else v
-        if isinstance(v, (list, tuple)):
-            return type(v)(one(u) for u in v)
-        return v
-    return {k: one(v) for k, v in aux.items()}
-
-
-# ======================================================================================================================
-# rows: name -> (tolerance, bit-identical to the aligned call, {operand: class}, build(env) -> Built, ref(aux) -> {output: tensor})
-# ======================================================================================================================
-ROWS = {}
-
-
-def row(name, tol, cls, exact=True):
-    def deco(fn):
-        build, ref = fn()
-        ROWS[name] = types.SimpleNamespace(name=name, tol=tol, cls=cls, exact=exact, build=build, ref=ref)
-        return fn
-    return deco
-
-
-def _pw(name, B, K, M, T, tol=1e-5):
-    t1 = T == 1
-    cls = {"x": "S" if t1 else "F", "wt": "R", "bias": "S", "res": "S" if t1 else "F", "y": "S" if t1 else "F"}
-
-    @row(name, tol, cls)
-    def _():
-        def build(e):
-            x, w, b, r = rnd(B * 7 + K, B, K, T), rnd(K + M, K, M) / K ** 0.5, rnd(M, M) * 0.1, rnd(3, B, M, T)
-            ins = {"x": x, "wt": w, "bias": b, "res": r}
-
-            def call(p):
-                return e.lib.hilc_pw_conv(p["x"], p["wt"], p["bias"], p["res"], p["y"], B, K, M, T, 0.77, 1, 0.61, e.stream())
-            return Built(ins, {"y": (B, M, T)}, dict(ins), call)
-
-        def ref(a):
-            return {"y": A.ref_pw_conv(a["x"], a["wt"], a["bias"], a["res"], 0.77, True, 0.61)}
-        return build, ref
-
-
-_pw("pw_conv-3x33x96x8", 3, 33, 96, 8)      # one ragged tile
-_pw("pw_conv-2x17x64x132", 2, 17, 64, 132)      # T > BN = 128, ragged last tile
-_pw("pw_conv-frame1-5x33x96x1", 5, 33, 96, 1)      # the single-frame kernel
-
-
-def _dwc(name, B, C, T, k, s, hist, res):
-    cls = {"x": "F", "hist": "S", "w": "S", "bias": "S", "res": "S", "y": "F", "hist_out": "S"}
-    cls = {o: c for o, c in cls.items() if (hist or o not in ("hist", "hist_out")) and (res or o != "res")}
-
-    @row(name, 5e-6, cls)
-    def _():
-        pad = k - s
-        To = (T + s - 1) // s
-
-        def build(e):
-            ins = {"x": rnd(C + T, B, C, T), "w": rnd(C + k, C, k), "bias": rnd(C, C) * 0.1}
-            if hist:
-                ins["hist"] = rnd(5, B, C, pad) * 0.7
-            if res:
-                ins["res"] = rnd(6, B, C, To)
-            outs = {"y": (B, C, To)}
-            if hist:
-                outs["hist_out"] = (B, C, pad)
-
-            def call(p):
-                return e.lib.hilc_dw_conv(p["x"], p.get("hist"), p["w"], p["bias"], p.get("res"), p["y"], p.get("hist_out"), B, C, T, k, s,
-                                          0.9, 1, 0.4, 1, e.stream())
-            return Built(ins, outs, dict(ins), call)
-
-        def ref(a):
-            y, h = A.ref_dw_conv(a["x"], a.get("hist"), a["w"], a["bias"], a.get("res"), s, 0.9, True, 0.4, True)
-            return {"y": y, "hist_out": h} if hist else {"y": y}
-        return build, ref
-
-
-_dwc("dw_conv-24x36-k5", 2, 24, 36, 5, 1, False, False)
-_dwc("dw_conv-24x36-k5-hist-res", 2, 24, 36, 5, 1, True, True)
-_dwc("dw_conv-16x40-k8s4-hist", 2, 16, 40, 8, 4, True, False)
-
-
-@row("dw_convtr-16x12-r4", 5e-6, {"x": "S", "hist": "S", "w": "S", "y": "S", "hist_out": "S"})
-def _():
-    B, C, T, r = 2, 16, 12, 4
-
-    def build(e):
-        ins = {"x": rnd(1, B, C, T), "hist": rnd(2, B, C, 1) * 0.5, "w": rnd(3, C, 2 * r)}
-
-        def call(p):
-            return e.lib.hilc_dw_convtr(p["x"], p["hist"], p["w"], p["y"], p["hist_out"], B, C, T, r, 0.7, 1, e.stream())
-        return Built(ins, {"y": (B, C, T * r), "hist_out": (B, C, 1)}, dict(ins), call)
-
-    def ref(a):
-        y, h = A.ref_dw_convtr(a["x"], a["hist"], a["w"], r, 0.7, True)
-        return {"y": y, "hist_out": h}
-    return build, ref
-
-
-@row("conv_pre-24x36-k5", 2e-5, {"wav": "F", "hist": "S", "w": "S", "bias": "S", "y": "F"})
-def _():
-    B, C, T, k, HL = 2, 24, 36, 5, 6
-
-    def build(e):
-        ins = {"wav": synth.synth_clips(B, T, seed=5), "hist": synth.synth_clips(B, HL, seed=6), "w": rnd(1, C, k), "bias": rnd(2, C) * 0.1}
-
-        def call(p):
-            return e.lib.hilc_conv_pre(p["wav"], p["hist"], HL, p["w"], p["bias"], p["y"], B, C, T, k, 1 / 0.1122080159, e.stream())
-        return Built(ins, {"y": (B, C, T)}, dict(ins), call)
-
-    def ref(a):
-        return {"y": A.ref_conv_pre(a["wav"], a["hist"], a["w"], a["bias"], 1 / 0.1122080159)}
-    return build, ref
-
-
-# The one row that is NOT bit-identical to its aligned call, as include/hilcodec_amd.h documents for hilc_conv_post: with ksize 5,
-# T % 4 == 0 and 16-byte aligned x / hist the channels are summed in eight classes c mod 8 (csrc/dwconv.hip, conv_post_k5_kernel:
-# `for (c = wave; c < C; c += NCLS)`, then `part[0] + part[1] + ...`), the generic kernel sums them in sequence (conv_post_kernel:
-# `for (c = 0; c < C; ++c)`).  The caches are copies and stay bit-identical.
-@row("conv_post-24x36-k5-hist", 2e-6, {"x": "F", "hist": "F", "w": "S", "bias": "S", "y": "S", "hist_out": "S"}, exact=("hist_out",))
-def _():
-    B, C, T, k = 2, 24, 36, 5
-
-    def build(e):
-        ins = {"x": rnd(9, B, C, T), "hist": rnd(8, B, C, 4) * 0.6, "w": rnd(3, C, k) / 20, "bias": rnd(4, 1) * 0.1}
-
-        def call(p):
-            return e.lib.hilc_conv_post(p["x"], p["hist"], p["w"], p["bias"], p["y"], p["hist_out"], B, C, T, k, 0.707, 1, 0.1122080159, 1,
-                                        e.stream())
-        return Built(ins, {"y": (B, 1, T), "hist_out": (B, C, 4)}, dict(ins), call)
-
-    def ref(a):
-        y, h = A.ref_conv_post(a["x"], a["hist"], a["w"], a["bias"], 0.707, True, 0.1122080159, True)
-        return {"y": y, "hist_out": h}
-    return build, ref
-
-
-def _dws(name, B, K, M, T, r, res):
-    k5 = r == 1
-    cls = {"x": "F", "wt": "R", "dw_w": "S", "dw_b": "S", "y": "F" if k5 else "S"}
-    if res:
-        cls["res"] = "F"
-
-    @row(name, 2e-5, cls)
-    def _():
-        k = 5 if k5 else 2 * r
-        To = (T + r - 1) // r
-
-        def build(e):
-            ins = {"x": rnd(B * 3 + K + T, B, K, T), "wt": rnd(K + M, K, M) / K ** 0.5, "dw_w": rnd(M + k, M, k) * 0.5, "dw_b": rnd(M, M) * 0.1}
-            if res:
-                ins["res"] = rnd(11, B, M, To)
-
-            def call(p):
-                return e.lib.hilc_dws_conv(p["x"], p["wt"], p["dw_w"], p["dw_b"], p.get("res"), p["y"], B, K, M, T, k, r, 0.86, 1,
-                                           0.37 if k5 else 1.0, 0, e.stream())
-            return Built(ins, {"y": (B, M, To)}, dict(ins), call)
-
-        def ref(a):
-            return {"y": A.ref_dws(a["x"], a["wt"], a["dw_w"], a["dw_b"], None, a.get("res"), r, 0.86, True, 0.37 if k5 else 1.0, False)[0]}
-        return build, ref
-
-
-_dws("dws_conv-k5-2x33x96x36", 2, 33, 96, 36, 1, False)
-_dws("dws_conv-k5-2x33x96x36-res", 2, 33, 96, 36, 1, True)
-_dws("dws_conv-k5-1x16x128x260", 1, 16, 128, 260, 1, False)
-_dws("dws_conv-k5-1x16x128x260-res", 1, 16, 128, 260, 1, True)
-_dws("dws_conv-r2-2x16x32x64", 2, 16, 32, 64, 2, False)
-_dws("dws_conv-r4-2x16x32x64", 2, 16, 32, 64, 4, False)
-
-
-def _dwss(name, B, K, M, T, k, r, cls, res=True):
-    @row(name, 2e-5, cls)
-    def _():
-        pad = k - r
-        k5 = r == 1
-
-        def build(e):
-            ins = {"x": rnd(B + K + T, B, K, T), "wt": rnd(K + M, K, M) / K ** 0.5, "dw_w": rnd(M + k, M, k) * 0.5, "dw_b": rnd(M, M) * 0.1,
-                   "hist": rnd(12, B, M, pad) * 0.7}
-            if res:
-                ins["res"] = rnd(11, B, M, T // r)
-
-            def call(p):
-                return e.lib.hilc_dws_conv_stream(p["x"], p["wt"], p["dw_w"], p["dw_b"], p["hist"], p["hist_out"], p.get("res"), p["y"], B, K, M, T,
-                                                  k, r, 0.86, 1, 0.37 if k5 else 1.0, 1 if k5 else 0, e.stream())
-            return Built(ins, {"y": (B, M, T // r), "hist_out": (B, M, pad)}, dict(ins), call)
-
-        def ref(a):
-            y, h = A.ref_dws(a["x"], a["wt"], a["dw_w"], a["dw_b"], a["hist"], a.get("res"), r, 0.86, True, 0.37 if k5 else 1.0, k5)
-            return {"y": y, "hist_out": h}
-        return build, ref
-
-
-# T <= 128: whole clips per tile.  k5: the `al` switch between Dw5SegEpilogue and DwSegEpilogue; k = 2r with r = 5 / 8: DwSegEpilogue
-# reads a row's taps as f32x2 / f32x4 words (gemm_epilogues.h, `body<MB, KS>`), so dw_w is refused there
-_dwss("dws_conv_stream-k5-5x32x32x8", 5, 32, 32, 8, 5, 1,
-      {"x": "F", "wt": "R", "dw_w": "S", "dw_b": "S", "hist": "F", "hist_out": "F", "res": "F", "y": "F"})
-_dwss("dws_conv_stream-r5-5x16x32x40", 5, 16, 32, 40, 10, 5,
-      {"x": "F", "wt": "R", "dw_w": "R", "dw_b": "S", "hist": "S", "hist_out": "S", "res": "S", "y": "S"})
-_dwss("dws_conv_stream-frame1-5x32x32x1", 5, 32, 32, 1, 5, 1,
-      {"x": "S", "wt": "R", "dw_w": "S", "dw_b": "S", "hist": "S", "hist_out": "S", "res": "S", "y": "S"})
-# T > 128: no scalar loader (x refused); DwStrideFlatEpilogue reads hist and res and writes y and hist_out word by word
-# (gemm_epilogues.h: `hist[(bq * M + m) * r + j]`, `y[yo] = ... res[yo]`, `hist_out[...] = smem[...]`; its f32x4 reads are LDS)
-_dwss("dws_conv_stream-r4-3x16x32x160", 3, 16, 32, 160, 8, 4,
-      {"x": "R", "wt": "R", "dw_w": "S", "dw_b": "S", "hist": "S", "hist_out": "S", "res": "S", "y": "S"})
-
-
-def _up(name, entry, B, K, M, Tin, r):
-    stream = entry != "hilc_up_conv"
-    cls = {"x": "S", "tr_w": "F", "wt": "R", "bias": "S", "y": "F"}
-    if stream:
-        cls.update({"hist": "S", "hist_out": "S"})
-    if entry == "hilc_up_conv_expanded":
-        cls["expanded"] = "F"
-
-    @row(name, 3e-5, cls)
-    def _():
-        def build(e):
-            ins = {"x": rnd(100 + K, B, K, Tin), "tr_w": rnd(80, K, 2 * r) * 0.3, "wt": rnd(81, K, M) / K ** 0.5, "bias": rnd(82, M) * 0.1}
-            aux = dict(ins)
-            outs = {"y": (B, M, Tin * r)}
-            if stream:
-                aux["hist"] = ins["hist"] = rnd(30, B, K, 1) * 0.6
-                outs["hist_out"] = (B, K, 1)
-            if "expanded" in cls:
-                ins["expanded"] = e.ops.up_conv_taps(ins["tr_w"].to(e.dev), r)        # a layout table: no arithmetic
-
-            def call(p):
-                if entry == "hilc_up_conv":
-                    return e.lib.hilc_up_conv(p["x"], p["tr_w"], p["wt"], p["bias"], p["y"], B, K, M, Tin, r, 0.7071, 1, e.stream())
-                if entry == "hilc_up_conv_stream":
-                    return e.lib.hilc_up_conv_stream(p["x"], p["hist"], p["hist_out"], p["tr_w"], p["wt"], p["bias"], p["y"], B, K, M, Tin, r,
-                                                     0.7071, 1, e.stream())
-                return e.lib.hilc_up_conv_expanded(p["x"], p["hist"], p["hist_out"], p["tr_w"], p["expanded"], p["wt"], p["bias"], p["y"], B, K, M,
-                                                   Tin, r, 0.7071, 1, e.stream())
-            return Built(ins, outs, aux, call)
-
-        def ref(a):
-            y, h = A.ref_up_conv(a["x"], a.get("hist"), a["tr_w"], a["wt"], a["bias"], r, 0.7071, True)
-            return {"y": y, "hist_out": h} if stream else {"y": y}
-        return build, ref
-
-
-# tolerance: tests/test_gpu_ops.py uses 3e-5 for up_conv
-_up("up_conv-2x32x16x6-r2", "hilc_up_conv", 2, 32, 16, 6, 2)
-_up("up_conv_stream-2x32x16x4-r4", "hilc_up_conv_stream", 2, 32, 16, 4, 4)
-_up("up_conv_expanded-2x48x24x4-r5", "hilc_up_conv_expanded", 2, 48, 24, 4, 5)
-
-
-def _stft(name, B, T, n_fft, hop, hist):
-    cls = {"wav": "S", "basis_t": "R", "spec": "S"}
-    if hist:
-        cls["hist"] = "S"
-
-    @row(name, 2e-5, cls)
-    def _():
-        HL = n_fft - 1 + 5
-
-        def build(e):
-            ins = {"wav": synth.synth_clips(B, T, seed=n_fft), "basis_t": e.fold.stft_basis_layout(synth.stft_basis(n_fft))}
-            if hist:
-                ins["hist"] = synth.synth_clips(B, HL, seed=77)
-            Tf = (T - 1) // hop + 1
-
-            def call(p):
-                return e.lib.hilc_stft_logmag(p["wav"], p.get("hist"), HL if hist else 0, p["basis_t"], p["spec"], B, T, n_fft, hop, 0.0, 1.0, 2,
-                                              e.stream())
-            return Built(ins, {"spec": (B, n_fft // 2 + 1, Tf)}, dict(ins), call)
-
-        def ref(a):
-            return {"spec": A.ref_stft(a["wav"], a.get("hist"), a["basis_t"], n_fft, hop, 0.0, 1.0, 2)}
-        return build, ref
-
-
-_stft("stft_logmag-n16-T64-hist", 2, 64, 16, 1, True)      # the generic loader
-_stft("stft_logmag-n16-T512-seg", 1, 512, 16, 1, False)      # per-clip LDS segments (Tf >= 512)
-
-
-def _spec(name, pre):
-    cls = {"wav": "S", "hist": "S", "dft_packed": "R", "nyq_sin": "S", "pw_packed": "R", "bias": "S", "y": "R"}
-    cls.update({"pre_w": "S", "pre_b": "S"} if pre else {"x": "R"})
-
-    @row(name, 2e-4, cls)
-    def _():
-        B, T, N = 2, 128, 64
-
-        def build(e):
-            bt = e.fold.stft_basis_layout(synth.stft_basis(N))
-            wt = rnd(N + 1, N // 2 + 1, N) / (N // 2 + 1) ** 0.5
-            dft_p, nyq, pw_p = e.ops.spec_block_tables(bt.to(e.dev), wt.to(e.dev), N)          # layout only
-            ins = {"wav": synth.synth_clips(B, T, seed=T + B), "hist": synth.synth_clips(B, N - 1, seed=3), "dft_packed": dft_p, "nyq_sin": nyq,
-                   "pw_packed": pw_p, "bias": rnd(N + 2, N) * 0.1}
-            aux = {"wav": ins["wav"], "hist": ins["hist"], "bias": ins["bias"], "basis_t": bt, "wt": wt}
-            if pre:
-                aux["pre_w"] = ins["pre_w"] = rnd(71, N, 5) * 0.5
-                aux["pre_b"] = ins["pre_b"] = rnd(72, N) * 0.1
-            else:
-                aux["x"] = ins["x"] = rnd(9, B, N, T)
-
-            def call(p):
-                if pre:
-                    return e.lib.hilc_spec_block_conv_pre(p["wav"], p["hist"], N - 1, p["dft_packed"], p["nyq_sin"], p["pw_packed"], p["bias"],
-                                                          p["pre_w"], p["pre_b"], 1 / 0.1122080159, p["y"], B, T, N, 1, 5, -4.0, 2.8, 1, 0.37,
-                                                          e.stream())
-                return e.lib.hilc_spec_block(p["wav"], p["hist"], N - 1, p["dft_packed"], p["nyq_sin"], p["pw_packed"], p["bias"], p["x"], p["y"],
-                                             B, T, N, 1, -4.0, 2.8, 1, 0.37, e.stream())
-            return Built(ins, {"y": (B, N, T)}, aux, call)
-
-        def ref(a):
-            x = A.ref_conv_pre(a["wav"], a["hist"], a["pre_w"], a["pre_b"], 1 / 0.1122080159) if pre else a["x"]
-            return {"y": A.ref_spec_block(a["wav"], a["hist"], a["basis_t"], a["wt"], a["bias"], x, 64, 1, -4.0, 2.8, 1, 0.37)}
-        return build, ref
-
-
-_spec("spec_block-n64-T128", False)
-_spec("spec_block_conv_pre-n64-T128", True)
-
-
-# ---- the stage kernel's entries ------------------------------------------------------------------------------------------------------
-def raw_blocks(C, n):
-    return [(rnd(10 * j + 1, C, C) / C ** 0.5, rnd(10 * j + 2, C, 5) * 0.5, rnd(10 * j + 3, C) * 0.2, rnd(10 * j + 4, C, C) / C ** 0.5,
-             rnd(10 * j + 5, C, 5) * 0.5, rnd(10 * j + 6, C) * 0.2, (1 + j * RS ** 2) ** -0.5, 0.4 + 0.1 * j) for j in range(n)]
-
-
-BLK = ("w1t", "dw1_w", "dw1_b", "w2t", "dw2_w", "dw2_b")
-
-
-def block_cls(n, streaming):
-    cls = {}
-    for j in range(n):
-        cls.update({f"b{j}.w1t": "R", f"b{j}.dw1_w": "S", f"b{j}.dw1_b": "S", f"b{j}.w2t": "R", f"b{j}.dw2_w": "S", f"b{j}.dw2_b": "S"})
-        if streaming:
-            cls.update({f"b{j}.hist1": "R", f"b{j}.hist2": "R", f"b{j}.hist1_out": "R", f"b{j}.hist2_out": "R"})
-    return cls
-
-
-def block_operands(e, raw, B, C, streaming, pack, ins, outs, aux):
-    aux["blocks"] = [tuple(b) for b in raw]
-    aux["caches"] = []
-    for j, b in enumerate(raw):
-        for nm, t in zip(BLK, b[:6]):
-            ins[f"b{j}.{nm}"] = pack(t.to(e.dev)) if nm in ("w1t", "w2t") else t
-        if streaming:
-            h1, h2 = rnd(7 + j, B, C, 4) * 0.7, rnd(8 + j, B, C, 4) * 0.7
-            ins[f"b{j}.hist1"], ins[f"b{j}.hist2"] = h1, h2
-            outs[f"b{j}.hist1_out"] = outs[f"b{j}.hist2_out"] = (B, C, 4)
-            aux["caches"].append((h1, h2))
-
-
-def block_structs(e, p, raw, streaming):
-    n = len(raw)
-    arr = (e.L.ResblockParams * n)()
-    for j, b in enumerate(raw):
-        caches = [p.get(f"b{j}.{nm}") for nm in ("hist1", "hist2", "hist1_out", "hist2_out")] if streaming else [None] * 4
-        arr[j] = e.L.ResblockParams(*[p[f"b{j}.{nm}"] for nm in BLK], *caches, float(b[6]), float(b[7]))
-    return arr
-
-
-ref_blocks = A.ref_blocks          # (the compositions live in tests/alignment.py: tests/test_gpu_large.py shares them)
-
-
-def _resblock(name, B, C, T, streaming):
-    cls = {"x": "R", "y": "R"}
-    cls.update(block_cls(1, streaming))
-
-    @row(name, 2e-5, cls)
-    def _():
-        raw = raw_blocks(C, 1)
-
-        def build(e):
-            ins, outs, aux = {"x": rnd(C + T, B, C, T)}, {"y": (B, C, T)}, {}
-            aux["x"] = ins["x"]
-            block_operands(e, raw, B, C, streaming, e.ops.resblock_pack, ins, outs, aux)
-
-            def call(p):
-                w = [p[f"b0.{nm}"] for nm in BLK]
-                if not streaming:
-                    return e.lib.hilc_resblock(p["x"], *w, p["y"], B, C, T, float(raw[0][6]), float(raw[0][7]), e.stream())
-                return e.lib.hilc_resblock_stream(p["x"], *w, p["b0.hist1"], p["b0.hist2"], p["b0.hist1_out"], p["b0.hist2_out"], p["y"], B, C, T,
-                                                  float(raw[0][6]), float(raw[0][7]), e.stream())
-            return Built(ins, outs, aux, call)
-
-        def ref(a):
-            out = {}
-            out["y"] = ref_blocks(a, a["x"], streaming, out)
-            return out
-        return build, ref
-
-
-_resblock("resblock-64x8x2", 2, 64, 8, False)
-_resblock("resblock_stream-64x8x3", 3, 64, 8, True)
-
-
-def _chain(name, B, C, T, n, streaming):
-    cls = {"x": "R", "y": "R"}
-    cls.update(block_cls(n, streaming))
-
-    @row(name, 5e-5, cls)
-    def _():
-        raw = raw_blocks(C, n)
-
-        def build(e):
-            ins, outs, aux = {"x": rnd(C + T, B, C, T)}, {"y": (B, C, T)}, {}
-            aux["x"] = ins["x"]
-            block_operands(e, raw, B, C, streaming, lambda w: e.ops.resblock_chain_pack(w, streaming), ins, outs, aux)
-
-            def call(p):
-                return e.lib.hilc_resblock_chain(p["x"], p["y"], void(block_structs(e, p, raw, streaming)), n, int(streaming), B, C, T, e.stream())
-            return Built(ins, outs, aux, call)
-
-        def ref(a):
-            out = {}
-            out["y"] = ref_blocks(a, a["x"], streaming, out)
-            return out
-        return build, ref
-
-
-_chain("resblock_chain-64x8x2-offline", 2, 64, 8, 2, False)
-_chain("resblock_chain-64x8x3-stream", 3, 64, 8, 2, True)
-
-
-def _enc(name, B, C, T, r, n, streaming, stage0=False):
-    # down.dw_w: the wide stages (C = 256 / 512, `DWIDE`) read a row's taps as f32x2 / f32x4 words (resblock_kernel.h: `taps_of`), the
-    # narrow ones one by one (`a.dn.dw_w[mc * 2 * DR + j]`)
-    cls = {"down.w_lo": "R", "down.w_hi": "R", "down.dw_w": "R" if C >= 256 else "S", "down.dw_b": "S", "down.res": "R", "down.y": "R"}
-    if stage0:
-        cls.update({"spec.wav": "S", "spec.dft_packed": "R", "spec.nyq_sin": "S", "spec.pw_packed": "R", "spec.bias": "S", "spec.pre_w": "S",
-                    "spec.pre_b": "S"})
-    else:
-        cls["x"] = "R"
-    if streaming:
-        cls.update({"down.hist": "R", "down.hist_out": "R"})
-        if stage0:
-            cls["spec.hist"] = "S"
-    cls.update(block_cls(n, streaming))
-
-    @row(name, 2e-4 if stage0 else 5e-5, cls)
-    def _():
-        raw = raw_blocks(C, n)
-        in_scale = (1 + n * RS ** 2) ** -0.5
-        N = 64
-
-        def build(e):
-            ins, outs, aux = {}, {"down.y": (B, 2 * C, T // r)}, {}
-            pack = lambda w: e.ops.resblock_chain_pack(w, streaming)          # noqa: E731
-            if stage0:
-                bt = e.fold.stft_basis_layout(synth.stft_basis(N))
-                wt = rnd(N + 1, N // 2 + 1, C) / (N // 2 + 1) ** 0.5
-                dft_p, nyq, pw_p = e.ops.spec_block_tables(bt.to(e.dev), wt.to(e.dev), N)
-                ins.update({"spec.wav": synth.synth_clips(B, T, seed=T + B), "spec.dft_packed": dft_p, "spec.nyq_sin": nyq, "spec.pw_packed": pw_p,
-                            "spec.bias": rnd(N + 2, C) * 0.1, "spec.pre_w": rnd(71, C, 5) * 0.5, "spec.pre_b": rnd(72, C) * 0.1})
-                if streaming:
-                    ins["spec.hist"] = synth.synth_clips(B, N - 1, seed=9)
-                aux.update({"wav": ins["spec.wav"], "whist": ins.get("spec.hist"), "sbias": ins["spec.bias"], "pre_w": ins["spec.pre_w"],
-                            "pre_b": ins["spec.pre_b"], "basis_t": bt, "swt": wt})
-            else:
-                aux["x"] = ins["x"] = rnd(C + T + r, B, C, T)
-            block_operands(e, raw, B, C, streaming, pack, ins, outs, aux)
-            wd = rnd(70, C, 2 * C) / C ** 0.5                               # k-major [C, 2C]
-            ins["down.w_lo"], ins["down.w_hi"] = pack(wd[:, :C].contiguous().to(e.dev)), pack(wd[:, C:].contiguous().to(e.dev))
-            ins["down.dw_w"], ins["down.dw_b"], ins["down.res"] = rnd(73, 2 * C, 2 * r) * 0.3, rnd(74, 2 * C) * 0.1, rnd(75, B, 2 * C, T // r) * 0.5
-            aux.update({"wd": wd, "ddw": ins["down.dw_w"], "ddb": ins["down.dw_b"], "dres": ins["down.res"], "dhist": None})
-            if streaming:
-                aux["dhist"] = ins["down.hist"] = rnd(30, B, 2 * C, r) * 0.6
-                outs["down.hist_out"] = (B, 2 * C, r)
-
-            def call(p):
-                down = e.L.DownParams(p["down.w_lo"], p["down.w_hi"], p["down.dw_w"], p["down.dw_b"], p.get("down.hist"), p.get("down.hist_out"),
-                                      p["down.res"], p["down.y"], in_scale, r)
-                blocks = block_structs(e, p, raw, streaming)
-                if stage0:
-                    spec = e.L.Spec0Params(p["spec.wav"], p["spec.dft_packed"], p["spec.nyq_sin"], p["spec.pw_packed"], p["spec.bias"], p["spec.pre_w"],
-                                           p["spec.pre_b"], p.get("spec.hist"), N - 1 if streaming else 0, 1 / 0.1122080159, -4.0, 2.8, 0.37, 1, N, 1, 5)
-                    return e.lib.hilc_encoder_stage0(void(spec), void(blocks), n, void(down), int(streaming), B, T, e.stream())
-                return e.lib.hilc_encoder_stage(p["x"], void(blocks), n, void(down), int(streaming), B, C, T, e.stream())
-            return Built(ins, outs, aux, call)
-
-        def ref(a):
-            return A.ref_encoder_stage(a, streaming, stage0, r, in_scale, N)
-        return build, ref
-
-
-# tolerances: 5e-5 (test_encoder_stage_offline_vs_oracle_composition), 2e-4 (test_encoder_stage0_vs_oracle_composition)
-_enc("encoder_stage-128x8-r4-offline", 2, 128, 8, 4, 2, False)
-_enc("encoder_stage-128x8-r4-stream", 3, 128, 8, 4, 2, True)
-_enc("encoder_stage-512x8-r8-offline", 2, 512, 8, 8, 2, False)
-_enc("encoder_stage-512x8-r8-stream", 3, 512, 8, 8, 2, True)
-_enc("encoder_stage0-T8-offline", 2, 64, 8, 2, 2, False, stage0=True)
-_enc("encoder_stage0-T128-stream", 3, 64, 128, 2, 2, True, stage0=True)
-
-
-def _dec(name, B, C, Tin, r, n, streaming, post=False):
-    cls = {"up.x": "S", "up.tr_w": "R", "up.w_lo": "R", "up.w_hi": "R", "up.bias": "S"}
-    if streaming:
-        cls.update({"up.hist": "S", "up.hist_out": "S"})
-    if post:
-        cls.update({"post.w": "S", "post.bias": "S", "post.wav": "R"})
-        if streaming:
-            cls.update({"post.hist": "R", "post.hist_out": "R"})
-    else:
-        cls["y"] = "R"
-    cls.update(block_cls(n, streaming))
-
-    @row(name, 2e-5 if post else 5e-5, cls)
-    def _():
-        raw = raw_blocks(C, n)
-        T = Tin * r
-
-        def build(e):
-            ins, outs, aux = {"up.x": rnd(100 + C, B, 2 * C, Tin)}, {}, {}
-            pack = lambda w: e.ops.resblock_chain_pack(w, streaming)          # noqa: E731
-            tw, wu, bu = rnd(80, 2 * C, 2 * r) * 0.3, rnd(81, 2 * C, C) / (2 * C) ** 0.5, rnd(82, C) * 0.1
-            taps = e.ops.up_conv_taps(tw.to(e.dev), r)                       # r = 5: the expanded table
-            ins.update({"up.tr_w": tw if taps is None else taps, "up.w_lo": pack(wu[:C].contiguous().to(e.dev)),
-                        "up.w_hi": pack(wu[C:].contiguous().to(e.dev)), "up.bias": bu})
-            aux.update({"xin": ins["up.x"], "tw": tw, "wu": wu, "bu": bu, "uhist": None, "phist": None})
-            if streaming:
-                aux["uhist"] = ins["up.hist"] = rnd(30, B, 2 * C, 1) * 0.6
-                outs["up.hist_out"] = (B, 2 * C, 1)
-            block_operands(e, raw, B, C, streaming, pack, ins, outs, aux)
-            if post:
-                aux["pw"], aux["pb"] = ins["post.w"], ins["post.bias"] = rnd(83, C, 5) * 0.2, rnd(84, 1) * 0.1
-                outs["post.wav"] = (B, 1, T)
-                if streaming:
-                    aux["phist"] = ins["post.hist"] = rnd(31, B, C, 4) * 0.6
-                    outs["post.hist_out"] = (B, C, 4)
-            else:
-                outs["y"] = (B, C, T)
-
-            def call(p):
-                up = e.L.UpParams(p["up.x"], p["up.tr_w"], p["up.w_lo"], p["up.w_hi"], p["up.bias"], p.get("up.hist"), p.get("up.hist_out"), 0.7071, r)
-                blocks = block_structs(e, p, raw, streaming)
-                if post:
-                    ps = e.L.PostParams(p["post.w"], p["post.bias"], p["post.wav"], p.get("post.hist"), p.get("post.hist_out"), 0.5, 0.1122, 1, 5)
-                    return e.lib.hilc_decoder_stage_post(void(up), void(blocks), n, void(ps), int(streaming), B, C, T, e.stream())
-                return e.lib.hilc_decoder_stage(void(up), void(blocks), n, p["y"], int(streaming), B, C, T, e.stream())
-            return Built(ins, outs, aux, call)
-
-        def ref(a):
-            return A.ref_decoder_stage(a, streaming, post, r)
-        return build, ref
-
-
-# tolerances: 5e-5 (test_decoder_stage_offline_vs_oracle_composition), 2e-5 (test_decoder_stage_post_equals_stage_then_conv_post_and_oracle)
-_dec("decoder_stage-96-r2-Tin2-offline", 2, 96, 2, 2, 3, False)
-_dec("decoder_stage-96-r2-Tin2-stream", 3, 96, 2, 2, 3, True)
-_dec("decoder_stage-384-r5-Tin4-offline", 2, 384, 4, 5, 3, False)
-_dec("decoder_stage-384-r5-Tin4-stream", 3, 384, 4, 5, 3, True)
-_dec("decoder_stage_post-96-r2-Tin2-offline", 2, 96, 2, 2, 3, False, post=True)
-_dec("decoder_stage_post-96-r2-Tin2-stream", 3, 96, 2, 2, 3, True, post=True)
-
-
-# ---- the remaining float entry points: every operand is read and written word by word (class S) --------------------------------------
-@row("l2norm-3x128x5", 1e-6, {"x": "S", "y": "S"})
-def _():
-    B, C, T = 3, 128, 5
-
-    def build(e):
-        ins = {"x": rnd(1, B, C, T)}
-        return Built(ins, {"y": (B, T, C)}, dict(ins), lambda p: e.lib.hilc_l2norm(p["x"], p["y"], B, C, T, 1e-12, 1.0, 1, e.stream()))
-    return build, lambda a: {"y": A.ref_l2norm(a["x"], 1e-12, 1.0, True)}
-
-
-@row("tail-2x3x7-pad9", 0.0, {"x": "S", "hist": "S", "out": "S"})
-def _():
-    def build(e):
-        ins = {"x": rnd(1, 2, 3, 7), "hist": rnd(2, 2, 3, 10)}
-        return Built(ins, {"out": (2, 3, 9)}, dict(ins), lambda p: e.lib.hilc_tail(p["x"], p["hist"], p["out"], 6, 7, 9, 10, e.stream()))
-    return build, lambda a: {"out": torch.cat([a["hist"], a["x"]], dim=2)[:, :, -9:]}
-
-
-def _rvq_tables(Nq, K, C):
-    cb = rnd(5, Nq, K, C) * 0.3
-    return cb, cb.transpose(1, 2).contiguous(), cb.pow(2).sum(-1)
-
-
-def _rvq_enc(name, B, T):
-    # 8 192 frames and more: the matrix-pipe form reads codebooks_t and norms as 16-byte words and falls back to the VALU form (csrc/rvq.hip)
-    @row(name, 1e-5, {"z": "S", "codebooks": "S", "codebooks_t": "F", "norms": "F", "indices": "S", "q": "S", "frame_err": "S"})
-    def _():
-        Nq, K, C, n = 3, 1024, 128, 2
-
-        def build(e):
-            cb, cbt, nrm = _rvq_tables(Nq, K, C)
-            ins = {"z": rnd(7, B, C, T) * 0.4, "codebooks": cb, "codebooks_t": cbt, "norms": nrm}
-
-            def call(p):
-                return e.lib.hilc_rvq_encode(p["z"], p["codebooks"], p["codebooks_t"], p["norms"], p["indices"], p["q"], p["frame_err"], B, C, T, K, Nq,
-                                             n, 0, 0, 0, e.stream())
-            return Built(ins, {"indices": ((B, n, T), torch.int64), "q": (B, C, T), "frame_err": (B * T,)}, dict(ins), call)
-
-        def ref(a):
-            """the quantised sum of the indices the call returned must be what float64 sums; the indices themselves are pinned by
-            tests/test_gpu_rvq.py and, here, by equality with the aligned call"""
-            return {}
-        return build, ref
-
-
-_rvq_enc("rvq_encode-valu-2x128x9", 2, 9)
-_rvq_enc("rvq_encode-mfma-8x128x1024", 8, 1024)
-
-
-@row("rvq_decode-2x128x9", 1e-6, {"indices": "S", "codebooks": "S", "q": "S"})
-def _():
-    B, T, Nq, K, C, n = 2, 9, 3, 1024, 128, 3
-
-    def build(e):
-        cb = _rvq_tables(Nq, K, C)[0]
-        idx = torch.from_numpy(np.random.RandomState(3).randint(0, K, size=(B, n, T))).to(torch.int64)
-        ins = {"indices": idx, "codebooks": cb}
-        return Built(ins, {"q": (B, C, T)}, dict(ins),
-                     lambda p: e.lib.hilc_rvq_decode(p["indices"], p["codebooks"], p["q"], B, C, T, K, Nq, n, 0, 0, e.stream()))
-
-    def ref(a):
-        q = sum(a["codebooks"][s][a["indices"][:, s]] for s in range(n))          # [B, T, C]
-        return {"q": q.transpose(1, 2)}
-    return build, ref
-
-
-# The floor of every row: the largest difference between its reference evaluated in float32 and in float64 on the CPU, as measured
-# (figures of one CPU; the float32 sums depend on the host's BLAS blocking, so the sweep measures the floor again where it runs
-# and asserts tolerance >= 4 x that).  The RVQ encode rows
-# compare integers and consistency, `tail` copies: no rounding.
-FLOORS = {
-    "pw_conv-3x33x96x8": 3.68e-07,
-    "pw_conv-2x17x64x132": 3.48e-07,
-    "pw_conv-frame1-5x33x96x1": 2.42e-07,
-    "dw_conv-24x36-k5": 2.28e-07,
-    "dw_conv-24x36-k5-hist-res": 2.50e-07,
-    "dw_conv-16x40-k8s4-hist": 1.12e-07,
-    "dw_convtr-16x12-r4": 2.36e-07,
-    "conv_pre-24x36-k5": 9.12e-07,
-    "conv_post-24x36-k5-hist": 8.82e-08,
-    "dws_conv-k5-2x33x96x36": 2.41e-07,
-    "dws_conv-k5-2x33x96x36-res": 2.41e-07,
-    "dws_conv-k5-1x16x128x260": 2.98e-07,
-    "dws_conv-k5-1x16x128x260-res": 2.87e-07,
-    "dws_conv-r2-2x16x32x64": 4.59e-07,
-    "dws_conv-r4-2x16x32x64": 4.53e-07,
-    "dws_conv_stream-k5-5x32x32x8": 4.83e-07,
-    "dws_conv_stream-r5-5x16x32x40": 6.90e-07,
-    "dws_conv_stream-frame1-5x32x32x1": 3.10e-07,
-    "dws_conv_stream-r4-3x16x32x160": 6.07e-07,
-    "up_conv-2x32x16x6-r2": 1.76e-07,
-    "up_conv_stream-2x32x16x4-r4": 1.79e-07,
-    "up_conv_expanded-2x48x24x4-r5": 2.23e-07,
-    "stft_logmag-n16-T64-hist": 1.49e-07,
-    "stft_logmag-n16-T512-seg": 1.31e-07,
-    "spec_block-n64-T128": 4.66e-07,
-    "spec_block_conv_pre-n64-T128": 9.52e-07,
-    "resblock-64x8x2": 2.59e-07,
-    "resblock_stream-64x8x3": 8.59e-07,
-    "resblock_chain-64x8x2-offline": 3.78e-07,
-    "resblock_chain-64x8x3-stream": 8.59e-07,
-    "encoder_stage-128x8-r4-offline": 6.37e-07,
-    "encoder_stage-128x8-r4-stream": 1.11e-06,
-    "encoder_stage-512x8-r8-offline": 9.13e-07,
-    "encoder_stage-512x8-r8-stream": 1.81e-06,
-    "encoder_stage0-T8-offline": 3.69e-07,
-    "encoder_stage0-T128-stream": 1.54e-06,
-    "decoder_stage-96-r2-Tin2-offline": 3.34e-07,
-    "decoder_stage-96-r2-Tin2-stream": 8.02e-07,
-    "decoder_stage-384-r5-Tin4-offline": 6.44e-07,
-    "decoder_stage-384-r5-Tin4-stream": 1.01e-06,
-    "decoder_stage_post-96-r2-Tin2-offline": 2.41e-08,
-    "decoder_stage_post-96-r2-Tin2-stream": 8.02e-07,
-    "l2norm-3x128x5": 1.78e-08,
-    "tail-2x3x7-pad9": 0.00e+00,
-    "rvq_encode-valu-2x128x9": 0.00e+00,
-    "rvq_encode-mfma-8x128x1024": 0.00e+00,
-    "rvq_decode-2x128x9": 1.19e-07,
-}
-
-# ======================================================================================================================
-# the sweep
-# ======================================================================================================================
-_BUILT, _ALIGNED, _REF = {}, {}, {}
-
-
-def built(e, name):
-    if name not in _BUILT:
-        b = ROWS[name].build(e)
-        b.ins = {k: (None if v is None else v.to(e.dev).contiguous()) for k, v in b.ins.items()}
-        for t in b.ins.values():
-            assert t is None or t.data_ptr() % 16 == 0
-        _BUILT[name] = b
-    return _BUILT[name]
-
-
-def reference(e, name):
-    """float64 reference of the row and the floor under its tolerance: 4 x the largest difference between the same reference in
-    float32 and in float64 — computed once per row"""
-    if name not in _REF:
-        b = built(e, name)
-        r64 = ROWS[name].ref(cast(b.aux, torch.float64))
-        r32 = ROWS[name].ref(cast(b.aux, torch.float32))
-        floor = max([float((r32[k].double() - r64[k]).abs().max()) for k in r64] + [0.0])
-        _REF[name] = (r64, floor)
-    return _REF[name]
-
-
-def run(e, name, operand=None, k=0):
-    """one call of the row with `operand` (an input or an output) skewed by k; -> (return code, {output: CPU tensor})"""
-    b = built(e, name)
-    ins = {o: (skew(t, k) if o == operand else t) for o, t in b.ins.items()}
-    outs = {}
-    for o, shape in b.outs.items():
-        shape, dtype = shape if isinstance(shape[0], tuple) else (shape, torch.float32)
-        t = torch.full(shape, SENT if dtype.is_floating_point else int(SENT), dtype=dtype, device=e.dev)
-        outs[o] = skew(t, k) if o == operand else t
-    p = {o: (None if t is None else t.data_ptr()) for o, t in list(ins.items()) + list(outs.items())}
-    if operand is not None:
-        assert p[operand] % 16 != 0 and all(v is None or v % 16 == 0 for o, v in p.items() if o != operand)
-    before = {o: t.clone() for o, t in ins.items() if t is not None}
-    rc = b.call(p)
-    torch.cuda.synchronize()
-    for o, t in before.items():
-        assert torch.equal(ins[o], t), f"{name}: the call changed its input `{o}`"
-    return rc, {o: t.cpu() for o, t in outs.items()}
-
-
-def sentinel(t):
-    return bool((t == (SENT if t.is_floating_point() else int(SENT))).all())
-
-
-def check_ok(e, name, outs, what):
-    r = ROWS[name]
-    ref, floor = reference(e, name)
-    assert r.tol >= 4 * floor or not ref, f"{name}: tolerance {r.tol:.1e} is below 4 x the reference's own rounding {floor:.2e}"
-    for o, want in ref.items():
-        assert outs[o].shape == want.shape, (name, o, outs[o].shape, want.shape)
-        d = float((outs[o].double() - want).abs().max())
-        print(f"{name} [{what}] {o}: max |y - ref64| = {d:.3e} (tolerance {r.tol:.1e}, floor {floor:.2e})")
-        assert d <= r.tol, f"{name} [{what}] `{o}`: {d:.3e} > {r.tol:.1e}"
-    for o, t in outs.items():
-        assert not sentinel(t), f"{name} [{what}]: output `{o}` was not written"
-
-
-def aligned(e, name):
-    if name not in _ALIGNED:
-        rc, outs = run(e, name)
-        assert rc == 0, f"{name}: the aligned call failed with {rc}"
-        check_ok(e, name, outs, "aligned")
-        _ALIGNED[name] = outs
-    return _ALIGNED[name]
 
 
 def test_every_operand_has_a_class(env):
@@ -811,12 +33,12 @@ def test_every_operand_has_a_class(env):
         assert set(r.cls.values()) <= {"S", "F", "R"}, name
 
 
-@pytest.mark.parametrize("name", list(ROWS))
+@pytest.mark.parametrize("name", BASE)
 def test_aligned_call(env, name):
     aligned(env, name)
 
 
-@pytest.mark.parametrize("name,operand", [(n, o) for n, r in ROWS.items() for o in r.cls])
+@pytest.mark.parametrize("name,operand", [(n, o) for n in BASE for o in ROWS[n].cls])
 def test_one_operand_skewed(env, name, operand):
     e, r = env, ROWS[name]
     base = aligned(e, name)
@@ -1096,168 +318,23 @@ def test_ops_name_the_misaligned_output(env, name):
 
 
 # ======================================================================================================================
-# the per-slot float entry points (resampler, mixer, concealment gain, comfort noise, audio level, VBR: every operand class S; the
-# state-slot copies: class F, decided in the kernel).
+# the per-slot float entry points (tests/slot_cases.py: resampler, mixer, concealment gain, comfort noise, audio level, VBR: every
+# operand class S; the state-slot copies: class F, decided in the kernel).
 # Each has its definition as a host model in hilcodec_amd/*.py, bit for bit; the aligned call must equal that definition and every
 # call with one operand skewed — float32, float64, int32, int64 and uint8 rows alike — must equal the aligned call.
 # ======================================================================================================================
-def _misc_cases(dev):
-    """name -> (operands {name: CPU tensor}, written operand names, fn(ops, t) -> {returned: tensor}, expected {name: CPU tensor})"""
-    from hilcodec_amd import audio_level, dtx, mixer, vbr, wire
-    from hilcodec_amd.resample import design, device_taps, reference
-    cases = {}
-    g = torch.Generator().manual_seed(1)
-    # polyphase resampler, 16 kHz -> 24 kHz, a ragged hop with a history
-    sp = design(16000, 24000)
-    t = {"x": torch.rand(2, 1, 37, generator=g) * 2 - 1, "hist": torch.randn(2, 1, sp.Q - 1, generator=g) * 0.5, "hist_out": torch.full((2, 1, sp.Q - 1), SENT),
-         "taps": device_taps(sp, dev).cpu()}
-    y, h = reference(t["x"], sp, t["hist"])
-    cases["resample_poly"] = (t, ("hist_out",), lambda ops, t: {"y": ops.resample_poly(t["x"], t["taps"], sp.L, sp.M, hist=t["hist"], hist_out=t["hist_out"])},
-                              {"y": y, "hist_out": h})
-    # mixer: levels, then rooms
-    B, L = 6, 70
-    rng = np.random.default_rng(7)
-    wav = rng.uniform(-0.9, 0.9, (B, 1, L)).astype(np.float32)
-    prev = rng.random(B) * np.array([1.0, 0.0, 1e4, 1.0, 1.0, 0.5])
-    action = np.array([0, 0, 1, 0, 0, 0], dtype=np.int32)
-    model = mixer.MixModel(B, mixer.MixConfig(1))
-    model.score = torch.from_numpy(prev.copy())
-    model.step(wav, [-1] * B, action)
-    t = {"wav": torch.from_numpy(wav), "score": torch.from_numpy(prev.copy()), "action": torch.from_numpy(action)}
-    cases["mix_levels"] = (t, ("score",), lambda ops, t: ops.mix_levels(t["wav"], t["score"], t["action"]) or {}, {"score": model.score.clone()})
-    room = np.array([0, 0, 0, 1, -1, 1])
-    score = rng.choice(np.array([0.0, 0.25, 1.0, 4.0]), B)
-    speakers = mixer.select(room, score, 3)
-    t = {"wav": torch.from_numpy(wav), "room": torch.from_numpy(room.astype(np.int32)), "score": torch.from_numpy(score),
-         "mixed": torch.full((B, 1, L), SENT), "speakers": torch.full((B,), -9, dtype=torch.int32)}
-    cases["mix_rooms"] = (t, ("mixed", "speakers"), lambda ops, t: ops.mix_rooms(t["wav"], t["room"], t["score"], 3, t["mixed"], t["speakers"]) or {},
-                          {"mixed": torch.from_numpy(mixer.mix(wav.reshape(B, L), room, speakers)).view(B, 1, L), "speakers": torch.from_numpy(speakers)})
-    # concealment gain: every ramp word of a 4-hop fade, an idle row and one out of range
-    F, S = 4, 320
-    G, W = wire.conceal_tables(F, S)
-    ramp = torch.tensor([0, F + 1] + list(range(-F, 0)) + list(range(1, F + 1)), dtype=torch.int32)
-    cw = torch.randn(len(ramp), 1, S, generator=g)
-    exp = cw.clone()
-    for b, r in enumerate(ramp.tolist()):
-        if r != 0 and abs(r) <= F:
-            a, c = (r - 1, r) if r > 0 else (-r, 0)
-            exp[b] = cw[b] * (G[a] + (G[c] - G[a]) * W)              # fp32, one rounding per operation
-    t = {"wav": cw, "ramp": ramp, "gains": G, "weights": W}
-    cases["conceal_gain"] = (t, ("wav",), lambda ops, t: ops.conceal_gain(t["wav"], t["ramp"], t["gains"], t["weights"]) or {}, {"wav": exp})
-    # comfort noise: a SID in every slot's row, then what dtx.cng_model makes of it
-    K, T, B = 10, 1, 5
-    stride = max(wire.packet_bytes(8, T), 1 + K)
-    packets = torch.randint(0, 256, (B, stride), generator=g, dtype=torch.uint8)
-    packets[:, 0] = torch.randint(0, 100, (B,), generator=g, dtype=torch.uint8)
-    hold = torch.full((B,), 2, dtype=torch.int32)
-    hold[3] = 0
-    state = torch.zeros(B, dtx.state_words(K), dtype=torch.int32)
-    e_state, e_hold, e_restore, noise = dtx.cng_model(state, packets, hold, None, K, T)
-    t = {"packets": packets, "hold": hold, "state": state, "wav": torch.full((B, 1, 320 * T), 7.0), "gains": torch.from_numpy(dtx.gain_table()),
-         "restore": torch.full((B,), 5, dtype=torch.int32)}
-    cases["cng_synth"] = (t, ("hold", "state", "wav", "restore"),
-                          lambda ops, t, K=K: ops.cng_synth(t["packets"], t["hold"], t["state"], t["wav"], t["gains"], K, None, t["restore"]) or {},
-                          {"hold": e_hold, "state": e_state, "restore": e_restore,
-                           "wav": torch.where(e_restore.bool()[:, None], noise, torch.full((B, 320 * T), 7.0)).view(B, 1, 320 * T)})
-    # audio level of a hop
-    x = (torch.rand(5, 1, 320, generator=g) * 2 - 1) * torch.tensor([1.0, 0.1, 1e-3, 0.0, 0.5]).view(5, 1, 1)
-    t = {"x": x, "thr": torch.from_numpy(dtx.level_table()), "hold": torch.tensor([0, 0, 0, 0, 1], dtype=torch.int32), "level": torch.full((5,), -9, dtype=torch.int32)}
-    want = audio_level.hop_level(x.numpy()).copy()
-    want[4] = 127
-    cases["audio_level"] = (t, ("level",), lambda ops, t: (ops.audio_level(t["x"], t["thr"], t["level"], t["hold"]), {})[1], {"level": torch.from_numpy(want.astype(np.int32))})
-    # quality-targeted bitrate: vbr.VbrModel
-    B, T, n, C, K = 5, 3, 8, 128, 1024
-    cb = torch.randn(n + 1, K, C, generator=g) * 0.05
-    cfg = vbr.VbrConfig(0.01, n_min=2)
-    z = torch.randn(B, T, C, generator=g)
-    idx = torch.randint(0, K, (n, B, T), generator=g)
-    n_b = torch.randint(1, n + 1, (B,), generator=g, dtype=torch.int32)
-    e_n, e_D, e_idx = vbr.VbrModel(B, cfg, n, T).step(z, idx, cb, n_b, None, None)
-    t = {"z": z, "indices": idx.clone(), "codebooks": cb, "n_clip": n_b}
-
-    def vbr_fn(ops, t):
-        n_eff, D = ops.vbr_select(t["z"], t["indices"], t["codebooks"], min(n, vbr.floor_stages(cfg, 0)), cfg.rho, *vbr.bucket_bits(cfg, T, 0), t["n_clip"])
-        return {"n_eff": n_eff, "distortion": D}
-    cases["vbr_select"] = (t, ("indices",), vbr_fn, {"n_eff": e_n, "distortion": e_D, "indices": e_idx})
-    # the state-slot entry points: `move` (csrc/state.hip) copies a piece as f32x4 words where both addresses are 16-byte aligned and its length
-    # is a multiple of 4, word by word otherwise — decided per piece in the kernel.  Slices of 32, 15 and 16 floats per stream: in an aligned
-    # block both forms occur, in a skewed one only the second; the result is a copy either way.
-    from hilcodec_amd.ops import StateLayout
-    B = 5
-    layout = StateLayout([(B, 8, 4), (B, 3, 5), (B, 1, 16)], 1)
-    block = torch.randn(layout.total, generator=g)
-    records = torch.randn(3, layout.record_len, generator=g)
-    action = torch.tensor([0, -1, 2, 1, 3], dtype=torch.int32)
-
-    def part(k, b):
-        return slice(layout.off[k] + b * layout.lens[k], layout.off[k] + (b + 1) * layout.lens[k])
-    rec_off = [sum(layout.lens[:k]) for k in range(len(layout.lens))]
-    want = block.clone()
-    for k in range(len(layout.lens)):
-        for b, a in enumerate(action.tolist()):
-            if a == -1:
-                want[part(k, b)] = 0
-            elif a >= 1:
-                want[part(k, b)] = records[a - 1, rec_off[k]: rec_off[k] + layout.lens[k]]
-    t = {"block": block, "action": action, "records": records}
-    cases["state_slots_apply"] = (t, ("block",), lambda ops, t: ops.state_slots_apply(t["block"], layout, t["action"], t["records"]) or {}, {"block": want})
-    slots = torch.tensor([4, 0, 2], dtype=torch.int32)
-    rec = torch.stack([torch.cat([block[part(k, b)] for k in range(len(layout.lens))]) for b in slots.tolist()])
-    cases["state_slots_gather"] = ({"block": block, "slots": slots}, (), lambda ops, t: {"records": ops.state_slots_gather(t["block"], layout, t["slots"])},
-                                   {"records": rec})
-    dst = torch.randn(layout.total, generator=g)
-    hold = torch.tensor([0, 1, 0, 2, 0], dtype=torch.int32)
-    want = dst.clone()
-    for k in range(len(layout.lens)):
-        for b, h in enumerate(hold.tolist()):
-            if h:
-                want[part(k, b)] = block[part(k, b)]
-    wav = torch.randn(B, 1, 37, generator=g)
-    want_wav = wav.clone()
-    want_wav[hold != 0] = 0
-    t = {"src": block, "dst": dst, "hold": hold, "wav": wav}
-    cases["state_slots_hold"] = (t, ("dst", "wav"), lambda ops, t: ops.state_slots_hold(t["src"], t["dst"], layout, t["hold"], wav=t["wav"]) or {},
-                                 {"dst": want, "wav": want_wav})
-    return cases
-
-
-MISC = {"resample_poly": ("x", "hist", "hist_out", "taps"), "mix_levels": ("wav", "score", "action"),
-        "mix_rooms": ("wav", "room", "score", "mixed", "speakers"), "conceal_gain": ("wav", "ramp", "gains", "weights"),
-        "cng_synth": ("packets", "hold", "state", "wav", "gains", "restore"), "audio_level": ("x", "thr", "hold", "level"),
-        "vbr_select": ("z", "indices", "codebooks", "n_clip"), "state_slots_apply": ("block", "action", "records"),
-        "state_slots_gather": ("block", "slots"), "state_slots_hold": ("src", "dst", "hold", "wav")}
-_MISC = {}
-
-
-def _misc_run(e, name, operand=None, k=0):
-    if not _MISC:
-        _MISC.update(_misc_cases(e.dev))
-    t0, writes, fn, expected = _MISC[name]
-    assert tuple(t0) == MISC[name]
-    t = {o: v.clone().to(e.dev) for o, v in t0.items()}
-    if operand is not None:
-        t[operand] = skew(t[operand], k)
-    got = dict(fn(e.ops, t))
-    torch.cuda.synchronize()
-    for o, v in t0.items():
-        if o not in writes:
-            assert torch.equal(t[o].cpu(), v), f"{name}: the call changed its input `{o}`"
-    got.update({o: t[o] for o in writes})
-    return {o: v.cpu() for o, v in got.items()}, expected
-
-
 @pytest.mark.parametrize("name,operand", [(n, o) for n, ops_ in MISC.items() for o in (None,) + ops_])
 def test_per_slot_entry_points(env, name, operand):
-    base, expected = _misc_run(env, name)
+    base, expected = misc_run(env, name)
     assert set(base) == set(expected)
     for o, want in expected.items():
         assert base[o].dtype == want.dtype and torch.equal(base[o], want), f"{name}: `{o}` differs from the host model"
     if operand is None:
         return
     for k in KS:
-        got, _ = _misc_run(env, name, operand, k)
+        got, _ = misc_run(env, name, operand, k)
         for o in base:
-            assert torch.equal(got[o], base[o]), f"{name} [{operand} + {skew(_MISC[name][0][operand], k).data_ptr() % 16} B]: `{o}` differs from the aligned call"
+            assert torch.equal(got[o], base[o]), f"{name} [{operand} + {skew(CASES[name][0][operand], k).data_ptr() % 16} B]: `{o}` differs from the aligned call"
 
 
 # ======================================================================================================================

@@ -2,24 +2,11 @@
 read (metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype /
 data / config.workload / roofline, and with --full cpu_baseline / other_configs), for the headline mode, the streaming schedules,
 the launch-structure A/B switch and the multi-GPU plumbing at world size 1."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
+from tests.models import run_bench
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def run_bench(*args, launcher=()):
-    out = subprocess.run([sys.executable, *launcher, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True,
-                         cwd=ROOT, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
-    assert len(lines) == 1, out.stdout[-2000:]          # exactly one JSON line
-    return json.loads(lines[0])
 
 
 def check_common(d, steps, warmup):

@@ -13,9 +13,8 @@ from hilcodec_amd.jitter import JitterConfig
 from hilcodec_amd.rate import RateConfig, RateModel
 from hilcodec_amd.report import ReportConfig, report_word
 from tests.bwe_loop import LOOP_BWE, LOOP_CAP, TimedLink, run_models
-from tests.hops import arrival_arrays, arrival_records, caches_equal
+from tests.hops import Network, arrival_arrays, arrival_records, caches_equal
 from tests.rate_loop import LOOP_JITTER, LOOP_RATE, LOOP_REPORT, ReportLine, Trace
-from tests.test_gpu_jitter_adapt import Network
 
 pytestmark = pytest.mark.gpu
 

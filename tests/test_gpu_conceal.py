@@ -7,13 +7,13 @@ import pytest
 import torch
 
 from hilcodec_amd import synth, wire
-from tests.hops import build_streaming, caches_equal, put_row, row_bytes
+from tests.hops import CONCEAL_FADE as F
+from tests.hops import build_streaming, caches_equal, prepare_model, put_row, row_bytes
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 HOP = 320
-F = 4
 
 
 @pytest.fixture(scope="module")
@@ -42,38 +42,7 @@ def random_packets(B, n_max, T, gen):
     return out, n_list
 
 
-# ---------------------------------------------------------------- host model of hilc_conceal_prepare
-def prepare_model(state, action, hold, lost, n_slot, packets, T, F):
-    """the table of the issue, per slot, on host copies; returns (state, hold, n_slot, packets, ramp)"""
-    state, hold, n_slot, packets = state.clone(), hold.clone(), n_slot.clone(), packets.clone()
-    B, words = state.shape
-    n_max = words - 3
-    ramp = torch.zeros(B, dtype=torch.int32)
-    for b in range(B):
-        row = state[b]
-        if int(action[b]) != 0:
-            row.zero_()
-        k = min(max(int(row[0]), 0), F)
-        has = int(row[1]) != 0
-        if int(hold[b]) != 0:
-            continue
-        if int(lost[b]) == 0:
-            nb = min(max(int(n_slot[b]), 1), n_max)
-            codes = wire.unpack_stream_packet(row_bytes(packets, b), nb, T)[:, -1]
-            row.zero_()
-            row[1], row[2] = 1, nb
-            row[3:3 + nb] = codes.to(torch.int32)
-            ramp[b] = -k
-        elif has and k < F:
-            nb = min(max(int(row[2]), 1), n_max)
-            codes = (row[3:3 + nb].long() & 1023).view(nb, 1).expand(nb, T).contiguous()
-            put_row(packets, b, wire.pack_stream_packet(codes))
-            n_slot[b] = nb
-            row[0] = k + 1
-            ramp[b] = k + 1
-        else:
-            hold[b] = 1
-    return state, hold, n_slot, packets, ramp
+# ---------------------------------------------------------------- hilc_conceal_prepare against its host model (tests/hops.py)
 
 
 @pytest.mark.parametrize("B", [37, 1024])

@@ -8,7 +8,7 @@ import torch
 
 from hilcodec_amd import synth, wire
 from hilcodec_amd.resample import hop_samples
-from tests.hops import build_streaming, caches_equal, put_row, row_bytes
+from tests.hops import build_streaming, caches_equal, pack_model, put_row, row_bytes, select_model
 
 pytestmark = pytest.mark.gpu
 
@@ -28,27 +28,6 @@ def speech(built):
 
 
 # ---------------------------------------------------------------- the kernels against host models
-def pack_model(idx, n_slot, prev_in, action, hold, m):
-    """hilc_pack_codes_10bit_fec per slot on host copies: (packets, nbytes, prev_out)"""
-    n_max, B, T = idx.shape
-    W = 1 + m * T
-    packets = torch.zeros(B, wire.fec_packet_bytes(n_max, m, T), dtype=torch.uint8)
-    nbytes = torch.zeros(B, dtype=torch.int32)
-    prev_out = torch.zeros(B, W, dtype=torch.int32)
-    codes = idx.clamp(0, 1023)
-    for b in range(B):
-        row = torch.zeros(W, dtype=torch.int32) if int(action[b]) else prev_in[b].clone()
-        if int(hold[b]):
-            prev_out[b] = row
-            continue
-        nb = min(max(int(n_slot[b]), m), n_max)
-        prev = (row[1:].long() & 1023).view(m, T) if int(row[0]) else None
-        blob = wire.pack_fec_packet(codes[:nb, b], prev)
-        put_row(packets, b, blob)
-        nbytes[b] = len(blob)
-        prev_out[b, 0] = 1
-        prev_out[b, 1:] = codes[:m, b].reshape(-1).to(torch.int32)
-    return packets, nbytes, prev_out
 
 
 @pytest.mark.parametrize("B", [37, 1024])
@@ -83,21 +62,6 @@ def test_pack_fec_kernel(B, T, n_max, m):
     prev_out = torch.zeros(B, W, dtype=torch.int32, device=DEV)
     pk, nb = ops.pack_codes_10bit_fec(idx.to(DEV), prev_in.to(DEV), prev_out, m)
     assert torch.equal(pk.cpu(), exp[0]) and torch.equal(nb.cpu(), exp[1]) and torch.equal(prev_out.cpu(), exp[2])
-
-
-def select_model(wide, fec, n_slot, n_max, m, T):
-    B = wide.shape[0]
-    out = torch.zeros(B, wire.packet_bytes(n_max, T), dtype=torch.uint8)
-    n_out = n_slot.clone()
-    for b in range(B):
-        if int(fec[b]):
-            nb = min(max(int(n_slot[b]), m), n_max)
-            put_row(out, b, wire.fec_redundant(row_bytes(wide, b), nb, m, T))
-            n_out[b] = m
-        else:
-            nb = min(max(int(n_slot[b]), 1), n_max)
-            put_row(out, b, wire.fec_primary(row_bytes(wide, b), nb, T))
-    return out, n_out
 
 
 @pytest.mark.parametrize("B", [37, 1024])

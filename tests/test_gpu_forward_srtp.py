@@ -11,8 +11,8 @@ from hilcodec_amd.forward_srtp import MAX_EPOCH, RT_EPOCH, RT_EXHAUSTED, RT_NOKE
 from tests.alignment import skew
 from tests.forward_loop import Membership
 from tests.forward_srtp_loop import Call, Clients, forge, key
+from tests.hops import SRTP_LENGTHS as LENGTHS
 from tests.hops import arrival_arrays
-from tests.test_gpu_srtp import LENGTHS
 
 pytestmark = pytest.mark.gpu
 

@@ -11,23 +11,13 @@ import pytest
 import torch
 
 from hilcodec_amd import synth
+from tests.models import build, run_bench
 
 pytestmark = pytest.mark.gpu
 
 
 def T(a):
     return torch.from_numpy(np.asarray(a))
-
-
-def build(name):
-    import hilcodec_amd
-    mk = synth.model_kwargs(name)
-    sd = synth.synth_state_dict(name, seed=7)
-    model = hilcodec_amd.HILCodec(24000, 1, **mk).eval()
-    model.load_state_dict(sd, strict=False)
-    for l in model.quantizer.layers:
-        l.initted = True
-    return model, mk
 
 
 def run(model, x):
@@ -43,7 +33,7 @@ def test_full_batch_properties(golden, name):
     from hilcodec_amd import ops
     dev = torch.device("cuda:0")
     g = golden(f"offline_{name}")
-    model, mk = build(name)
+    model, mk, _ = build(name)
     nq = mk["vq_kwargs"]["num_quantizers"]
     B = 256
     x = synth.synth_clips(B, 24000, seed=int(g["clip_seed"])).to(dev)
@@ -87,7 +77,7 @@ def test_full_batch_properties(golden, name):
 def test_streaming_equals_offline_encoder_on_zero_caches():
     """A single full-length streaming call on zero caches is the offline causal encoder."""
     dev = torch.device("cuda:0")
-    model, mk = build("hil_speech")
+    model, mk, _ = build("hil_speech")
     sm = synth.streaming_model()
     x = synth.synth_clips(4, 9600, seed=77).to(dev)
     ce, _ = sm.initialize_cache(x)
@@ -106,7 +96,6 @@ def test_rank7_shard_of_configs4_full_size(golden):
     with: `/root/reference/train.py:51-61` is its only NCCL setup.)"""
     import bench
     from hilcodec_amd import distributed as D
-    from tests.test_gpu_bench import run_bench
     g = golden("shard_rank7_hil_music")
     dev = torch.device("cuda:0")
     lo, hi = D.shard_range(256 * 8, 7, 8)
@@ -144,7 +133,7 @@ def test_batch_beyond_4gib_activations_keeps_the_fast_kernels():
     import time
     from hilcodec_amd import engine
     dev = torch.device("cuda:0")
-    model, mk = build("hil_speech")
+    model, mk, _ = build("hil_speech")
     x = synth.synth_clips(512, 24000, seed=4000).to(dev)
     assert len(engine._clip_chunks(512, 96 * 24000)) == 2 and len(engine._clip_chunks(256, 96 * 24000)) == 1
 

@@ -6,9 +6,9 @@ import numpy as np
 import pytest
 import torch
 
-from hilcodec_amd import dtx, jitter, synth, wire
+from hilcodec_amd import jitter, synth, wire
 from hilcodec_amd.jitter import AdaptConfig, JitterConfig, JitterModel
-from tests.hops import arrival_records
+from tests.hops import Network, arrival_records
 
 pytestmark = pytest.mark.gpu
 
@@ -20,81 +20,6 @@ ADAPT = AdaptConfig(window=8, resync=3, force_windows=2)     # every branch fire
 @pytest.fixture(scope="module")
 def speech():
     return synth.streaming_model()
-
-
-class Network:
-    """seeded traffic of B senders: each hop every slot sends a codes packet, a SID (DTX) or nothing; packets are lost, delayed up
-    to `delay` hops (reordered), duplicated or corrupted; `hold` / `start` rates give the host holds and the restarts of sender and
-    receiver together, `restart` the rate of sender restarts the receiver is not told of.  Slot b drifts by b mod 3: 1 a slow
-    sender (sends nothing on every `every`-th hop), 2 a fast one (two packets on that hop), 0 none; with `mild`, the slots with
-    b // 3 even see a good network (nothing lost, duplicated or corrupted, a delay of at most one hop), so that their clock is
-    moved by the windowed estimate and not by late arrivals."""
-
-    def __init__(self, B, n, m, K, T, seed, loss=0.05, delay=3, dup=0.01, bad=0.0, hold=0.0, start=0.0, sid=0.0, restart=0.0, every=20,
-                 mild=True):
-        self.B, self.n, self.m, self.K, self.T = B, n, m, K, T
-        self.rng = np.random.default_rng(seed)
-        self.tbytes = wire.transport_bytes(n, m, T)
-        self.h = self.rng.integers(0, 65536, B).astype(np.int64)
-        self.dtx = np.zeros(B, dtype=bool)
-        self.rates = dict(loss=loss, delay=delay, dup=dup, bad=bad, hold=hold, start=start, sid=sid, restart=restart)
-        self.every, self.mild = every, mild
-        self.flight = []                                     # (due hop, slot, packet bytes, byte count)
-        self.k = 0
-
-    def _packet(self, b):
-        r, h = self.rng, int(self.h[b])
-        if self.K is not None and (self.dtx[b] or r.random() < self.rates["sid"]):
-            self.dtx[b] = r.random() < 0.8
-            if r.random() < 0.4 or not self.dtx[b]:
-                body = r.integers(0, 256, dtx.sid_bytes(self.K)).astype(np.uint8).tobytes()
-                return wire.pack_transport(h, body, 0, sid=True) if self.dtx[b] else None
-            return None                                      # silent: nothing sent
-        nb = int(r.integers(max(self.m, 1), self.n + 1))
-        fec = self.m >= 1 and r.random() < 0.7
-        codes = torch.from_numpy(r.integers(0, 1024, (nb + (self.m if fec else 0), self.T)))
-        return wire.pack_transport(h, wire.pack_stream_packet(codes), nb, fec=fec)
-
-    def hop(self):
-        """-> (slots, packets uint8 [A, tbytes], nbytes, action [B], hold [B]) of this hop"""
-        r, B, k = self.rng, self.B, self.k
-        action = (r.random(B) < self.rates["start"]).astype(np.int32)
-        hold = (r.random(B) < self.rates["hold"]).astype(np.int32)
-        for b in np.nonzero(action)[0]:
-            self.h[b] = 0
-            self.dtx[b] = False
-        for b in np.nonzero(r.random(B) < self.rates["restart"])[0]:
-            self.h[b] = int(r.integers(0, 65536))
-        for b in range(B):
-            if hold[b]:
-                continue
-            tick = k % self.every == self.every - 1
-            good = self.mild and (b // 3) % 2 == 0
-            for _ in range((0 if b % 3 == 1 else 2 if b % 3 == 2 else 1) if tick else 1):
-                p = self._packet(b)
-                self.h[b] = (self.h[b] + 1) & 0xFFFF
-                if p is None or r.random() < (0.0 if good else self.rates["loss"]):
-                    continue
-                for _ in range(2 if r.random() < (0.0 if good else self.rates["dup"]) else 1):
-                    q = bytearray(p)
-                    nb = len(q)
-                    if r.random() < (0.0 if good else self.rates["bad"]):
-                        how = int(r.integers(0, 3))
-                        if how == 0:
-                            q[2] |= 0x20
-                        elif how == 1:
-                            nb -= 1
-                        else:
-                            nb = 2
-                    self.flight.append((k + int(r.integers(0, (1 if good else self.rates["delay"]) + 1)), b, bytes(q), nb))
-        now = [f for f in self.flight if f[0] <= k]
-        self.flight = [f for f in self.flight if f[0] > k]
-        now = [now[i] for i in r.permutation(len(now))]
-        pk = np.zeros((len(now), self.tbytes), dtype=np.uint8)
-        for a, f in enumerate(now):
-            pk[a, :len(f[2])] = np.frombuffer(f[2], dtype=np.uint8)
-        self.k += 1
-        return [f[1] for f in now], pk, [f[3] for f in now], action, hold
 
 
 # ---------------------------------------------------------------- the kernel against jitter.py

@@ -10,9 +10,7 @@ import pytest
 
 from hilcodec_amd import dtx, synth
 from tests import lifecycle as L
-from tests.hops import DEV, HOP, first_difference, first_non_finite, observe, slot_views
-from tests.test_gpu_vbr import speech as vbr_speech          # noqa: F401  (the fixture: falling per-stage codebooks, so that VBR decides)
-from tests.test_gpu_vbr import target_from_reference
+from tests.hops import DEV, HOP, first_difference, first_non_finite, observe, slot_views, target_from_reference, vbr_speech_model
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +30,13 @@ def plain():
 
 
 @pytest.fixture(scope="module")
-def models(plain, vbr_speech):                               # noqa: F811
+def vbr_speech():
+    """falling per-stage codebooks, so that VBR decides"""
+    return vbr_speech_model()
+
+
+@pytest.fixture(scope="module")
+def models(plain, vbr_speech):
     """{configuration: (model, VBR target or None)}: the sender with every option takes test_gpu_vbr's model and the target of its
     reference at hop 0, every other configuration the plain streaming model"""
     target = target_from_reference(vbr_speech, 8, 1, L.N, synth.synth_clips(8, HOP, seed=1).to(DEV))

@@ -10,6 +10,7 @@ import hilcodec_amd
 from hilcodec_amd import dtx, mixer, synth, wire
 from hilcodec_amd.jitter import JitterConfig
 from hilcodec_amd.mixer import MixConfig, MixModel
+from tests.hops import rooms_case
 
 pytestmark = pytest.mark.gpu
 
@@ -54,20 +55,6 @@ def test_mix_levels_kernel(L):
     model.step(x2, [-1] * B)
     assert torch.equal(score.cpu(), model.score)
     assert score[1].item() == 0.5 * mixer.levels(x)[1]
-
-
-def rooms_case(name):
-    if name == "b6":
-        return np.array([0, 0, 0, 1, -1, 1])
-    if name == "b70":                                       # one room of 67 members: crosses a wave
-        room = np.full(70, 5)
-        room[[3, 40, 69]] = -1
-        return room
-    room = np.full(300, -1)                                 # two rooms of 130, interleaved: cross a 256-thread block; 40 slots in none
-    perm = np.random.default_rng(300).permutation(300)
-    room[perm[:130]] = 7
-    room[perm[130:260]] = 299
-    return room
 
 
 @pytest.mark.parametrize("top_k", [1, 3, 8])

@@ -10,7 +10,7 @@ import torch
 import hilcodec_amd
 from hilcodec_amd import mixer, synth
 from hilcodec_amd.mixer import Dynamics, LevelConfig, LimitConfig, MixConfig, MixModel
-from tests.test_gpu_mix import rooms_case
+from tests.hops import rooms_case
 
 pytestmark = pytest.mark.gpu
 

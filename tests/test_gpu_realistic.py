@@ -24,7 +24,7 @@ def T(a):
 @pytest.fixture(scope="module")
 def real(golden):
     import hilcodec_amd
-    from tests.test_oracle_golden import realistic_state_dict
+    from tests.models import realistic_state_dict
     g = golden("realistic")
     mk = synth.model_kwargs("hil_speech")
     sd = realistic_state_dict(g)
@@ -37,7 +37,7 @@ def real(golden):
 
 def oracle_and_compare(model, mk, sd, x, golden_idx=None):
     from oracle import hilcodec_oracle as O
-    from tests.test_gpu_offline import compare
+    from tests.models import compare
     with torch.no_grad():
         wav_o, _, _, aux = O.codec_forward(sd, x, mk)
     if golden_idx is not None:

@@ -7,322 +7,22 @@ integer ones (two runs).  A call must return what the same call returns on plain
 reaches an output shows as a NaN or as a difference between the two integer runs, even where it is multiplied by zero — and every
 zone must still hold its pattern afterwards.
 
-The C-ABI rows are those of tests/test_gpu_alignment.py (`ROWS`: raw pointers, small ragged shapes, a float64 reference, a checked
-aligned baseline) plus the `EDGE` rows below, which cross the tile edges that table lacks; the per-slot float kernels are its
-`MISC` cases plus the layouts below; the kernels that move variable-length byte rows get one case each against their host models."""
+The C-ABI rows are `ALL_ROWS` of tests/entry_rows.py: the base rows of the alignment sweep (raw pointers, small ragged shapes, a
+float64 reference, a checked aligned baseline) plus its `EDGE` rows, which cross the tile edges the base rows lack; the per-slot
+float kernels are the `MISC` cases of tests/slot_cases.py plus the layouts below; the kernels that move variable-length byte rows
+(`BYTE_ENTRY_POINTS` and `MORE_ENTRY_POINTS` of tests/redzone.py) get one case each against their host models."""
 import numpy as np
 import pytest
 import torch
 
 from tests import alignment as A
-from tests import test_gpu_alignment as TA
+from tests import slot_cases
+from tests.entry_rows import ALL_ROWS, EDGE, EDGE_FLOORS, FLOORS, ROWS, SENT, aligned, built, check_ok, env, rnd, sentinel  # noqa: F401  (env: the fixture)
+from tests.hops import CONCEAL_FADE as F
+from tests.hops import pack_model, prepare_model, select_model
 from tests.redzone import INT_FILLS, check, damage, guarded
-from tests.test_gpu_alignment import ROWS, SENT, Built, aligned, built, check_ok, env, rnd, sentinel  # noqa: F401  (env: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-# ======================================================================================================================
-# rows that cross the tile edges (same builders, same requirements: a float64 reference, tolerance >= 4 x its measured floor)
-# ======================================================================================================================
-# entry point(s): kernel, its tiles -> the rows that cross each tiled dimension and end ragged there ("ROWS": a row of the alignment table)
-#   pw_conv, dws_conv, dws_conv_stream, up_conv, up_conv_stream, up_conv_expanded: the GEMM cores (gemm_core.h, gemm_lin.h), BN = 128 columns
-#     x BM = 32 * MB rows (MB = 1..4 picked per launch), K slices of BK
-#       -> pw_conv-2x17x36x132 (M = 32 + 4, 264 columns = 2 tiles + 8, K = 17), pw_conv-1x16x132x8 (M = 128 + 4: ragged whatever MB is),
-#          dws_conv-k5-1x16x128x260 (ROWS: 2 tiles + 4), up_conv-3x32x36x22-r2 / up_conv_stream-3x32x36x11-r4 (132 columns, M = 32 + 4),
-#          up_conv_expanded-3x48x24x12-r5 (180 columns), dws_conv_stream-k5-9x32x36x24 (216 columns of whole clips, M = 32 + 4),
-#          dws_conv_stream-r5-5x16x32x40 (ROWS: 200 columns), dws_conv_stream-r4-3x16x32x160 (ROWS: per-clip tiles, T = 128 + 32);
-#          pw_conv / dws_conv_stream with T = 1 (frame1.hip): 32 streams per workgroup -> the frame1 rows of ROWS (5 streams: one ragged
-#          workgroup; more than 32 streams only repeats it)
-#   stft_logmag: the same cores; the generic loader walks B * Tf flat columns, the segment form (no hist, Tf >= 512) per-clip tiles of 128
-#       -> stft_logmag-n16-T132-hist (264 columns = 2 tiles + 8), stft_logmag-n16-T516-seg (4 tiles + 4); M = n_fft + 2 = 18 rows: ragged
-#   spec_block, spec_block_conv_pre (spec.hip): TF = 128 frames per tile; flat over B * Tf for 32 <= Tf < 512 (spec_block only), else per clip
-#       -> spec_block-n64-T132 (flat: 264 frames = 2 tiles + 8), spec_block-n64-T516 (per clip: 4 tiles + 4),
-#          spec_block_conv_pre-n64-T132 (per clip: 1 tile + 4)
-#   dw_conv, conv_pre (dwconv.hip): flat, 256 outputs (k = 5, T % 4 == 0: 256 groups of 4) per workgroup
-#       -> every such row of ROWS ends in a ragged workgroup after a full one (432 groups; 320 outputs); dw_conv-16x38-k8s4-hist: T = 38 is
-#          no multiple of the stride 4
-#   dw_convtr: flat, 256 outputs per workgroup -> dw_convtr-16x13-r4 (1664 = 6 x 256 + 128; the row of ROWS is 6 x 256 exactly)
-#   tail, and every hist_out of dw_conv / dw_convtr / conv_post (hist_out_kernel): flat, 256 elements per workgroup -> tail-2x15x7-pad9 (270)
-#   conv_post: 256 samples of one clip per workgroup -> conv_post-8x260-k5-hist (T = 256 + 4)
-#   l2norm: 64 frames per workgroup, 16 channels per round -> l2norm-5x36x13 (65 frames, C = 32 + 4)
-#   rvq_encode, rvq_encode_mixed (rvq.hip): VALU form 16 frames per workgroup -> rvq_encode-valu-2x128x9 (ROWS: 18 frames), rvq_encode_mixed-3x128x9
-#     (27); matrix-pipe form (8192 frames and more) 32 frames per workgroup -> rvq_encode-mfma-8x128x1025 (8200 = 256 x 32 + 8)
-#   rvq_decode, rvq_decode_mixed: flat, 256 elements per workgroup -> rvq_decode-3x128x3 (1152 = 4 x 256 + 128; the row of ROWS is 9 x 256
-#     exactly), rvq_decode_mixed-3x128x9 (3456 = 13 x 256 + 128)
-#   resblock, resblock_balanced, resblock_chain, encoder_stage, encoder_stage0, decoder_stage, decoder_stage_post: the stage kernel
-#     (resblock_cfg.h).  C <= 192: NCOL = 128 columns per tile, a lane owns a 4-column group; offline: carries from tile to tile
-#       -> resblock-64x132x2, resblock_balanced-64x132x2-offline, resblock_chain-64x132x2-offline, encoder_stage-128x132-r4-offline,
-#          encoder_stage0-T132-offline, decoder_stage-96-r2-Tin66-offline, decoder_stage_post-96-r2-Tin66-offline (T = 128 + 4)
-#     streaming, one block: TO = 120 columns of the flat column space (8-column halo)
-#       -> resblock_stream-64x160x5, resblock_balanced-64x160x5-stream (800 columns = 6 tiles + 80)
-#     streaming, chain / stage: runs of whole streams, T = 160: 5 tiles = 4 streams
-#       -> resblock_chain-64x160x5-stream, encoder_stage-128x160-r4-stream, encoder_stage0-T160-stream, decoder_stage-96-r2-Tin80-stream,
-#          decoder_stage_post-96-r2-Tin80-stream (5 streams = one run + 1)
-#     C >= 256: 32- / 64-column tiles of whole streams -> encoder_stage-512x8-r8-*, decoder_stage-384-r5-Tin4-* (ROWS: 2 / 3 streams of 8 /
-#       20 columns, a ragged tile; a second tile only repeats the first, whole streams never straddle one)
-#   the channel dimension of the stage kernel is not tiled (C is a template parameter), nor is K of the RVQ (1024) or n_fft of spec_block
-# resblock_balanced and the two *_mixed RVQ entry points are rows the alignment table does not have (the caller's two scheduler words; an
-# int32 row of per-clip stage counts, unused index rows hold -1)
-# The rows go into the alignment module's `ROWS`, because its helpers (`built`, `reference`, `aligned`) look rows up there, and their floors
-# into its `FLOORS`, because its own `test_every_operand_has_a_class` asserts that the two tables have the same keys.  Without a
-# tests/__init__.py pytest collects that file as module `test_gpu_alignment` while this one imports `tests.test_gpu_alignment`: two copies,
-# the collected one untouched (and each aligned baseline run once per copy).  Under `--import-mode=importlib`, or with a package file, it
-# is one module: its parametrised ids were fixed when it was imported, before anything here ran, so it collects the same tests either
-# way and only its bookkeeping test sees (and checks) the rows below too.  Registering is idempotent: a second copy of this module
-# (the ledger imports `tests.test_gpu_redzone`) writes the same rows again.
-TA._pw("pw_conv-2x17x36x132", 2, 17, 36, 132)
-TA._pw("pw_conv-1x16x132x8", 1, 16, 132, 8)
-TA._dwc("dw_conv-16x38-k8s4-hist", 2, 16, 38, 8, 4, True, False)
-TA._up("up_conv-3x32x36x22-r2", "hilc_up_conv", 3, 32, 36, 22, 2)
-TA._up("up_conv_stream-3x32x36x11-r4", "hilc_up_conv_stream", 3, 32, 36, 11, 4)
-TA._up("up_conv_expanded-3x48x24x12-r5", "hilc_up_conv_expanded", 3, 48, 24, 12, 5)
-TA._dwss("dws_conv_stream-k5-9x32x36x24", 9, 32, 36, 24, 5, 1,
-         {"x": "F", "wt": "R", "dw_w": "S", "dw_b": "S", "hist": "F", "hist_out": "F", "res": "F", "y": "F"})
-TA._resblock("resblock-64x132x2", 2, 64, 132, False)
-TA._resblock("resblock_stream-64x160x5", 5, 64, 160, True)
-TA._chain("resblock_chain-64x132x2-offline", 2, 64, 132, 2, False)
-TA._chain("resblock_chain-64x160x5-stream", 5, 64, 160, 2, True)
-TA._enc("encoder_stage-128x132-r4-offline", 2, 128, 132, 4, 2, False)
-TA._enc("encoder_stage-128x160-r4-stream", 5, 128, 160, 4, 2, True)
-TA._dec("decoder_stage-96-r2-Tin66-offline", 2, 96, 66, 2, 3, False)
-TA._dec("decoder_stage-96-r2-Tin80-stream", 5, 96, 80, 2, 3, True)
-TA._enc("encoder_stage0-T132-offline", 2, 64, 132, 2, 2, False, stage0=True)
-TA._enc("encoder_stage0-T160-stream", 5, 64, 160, 2, 2, True, stage0=True)
-TA._dec("decoder_stage_post-96-r2-Tin66-offline", 2, 96, 66, 2, 3, False, post=True)
-TA._dec("decoder_stage_post-96-r2-Tin80-stream", 5, 96, 80, 2, 3, True, post=True)
-TA._stft("stft_logmag-n16-T132-hist", 2, 132, 16, 1, True)
-TA._stft("stft_logmag-n16-T516-seg", 1, 516, 16, 1, False)
-TA._rvq_enc("rvq_encode-mfma-8x128x1025", 8, 1025)
-
-
-def _spec(name, pre, B, T):
-    """TA._spec at another clip length (the alignment table's two rows are one whole tile)"""
-    cls = {"wav": "S", "hist": "S", "dft_packed": "R", "nyq_sin": "S", "pw_packed": "R", "bias": "S", "y": "R"}
-    cls.update({"pre_w": "S", "pre_b": "S"} if pre else {"x": "R"})
-
-    @TA.row(name, 2e-4, cls)
-    def _():
-        N = 64
-
-        def build(e):
-            bt = e.fold.stft_basis_layout(TA.synth.stft_basis(N))
-            wt = rnd(N + 1, N // 2 + 1, N) / (N // 2 + 1) ** 0.5
-            dft_p, nyq, pw_p = e.ops.spec_block_tables(bt.to(e.dev), wt.to(e.dev), N)          # layout only
-            ins = {"wav": TA.synth.synth_clips(B, T, seed=T + B), "hist": TA.synth.synth_clips(B, N - 1, seed=3), "dft_packed": dft_p, "nyq_sin": nyq,
-                   "pw_packed": pw_p, "bias": rnd(N + 2, N) * 0.1}
-            aux = {"wav": ins["wav"], "hist": ins["hist"], "bias": ins["bias"], "basis_t": bt, "wt": wt}
-            if pre:
-                aux["pre_w"] = ins["pre_w"] = rnd(71, N, 5) * 0.5
-                aux["pre_b"] = ins["pre_b"] = rnd(72, N) * 0.1
-            else:
-                aux["x"] = ins["x"] = rnd(9, B, N, T)
-
-            def call(p):
-                if pre:
-                    return e.lib.hilc_spec_block_conv_pre(p["wav"], p["hist"], N - 1, p["dft_packed"], p["nyq_sin"], p["pw_packed"], p["bias"],
-                                                          p["pre_w"], p["pre_b"], 1 / 0.1122080159, p["y"], B, T, N, 1, 5, -4.0, 2.8, 1, 0.37,
-                                                          e.stream())
-                return e.lib.hilc_spec_block(p["wav"], p["hist"], N - 1, p["dft_packed"], p["nyq_sin"], p["pw_packed"], p["bias"], p["x"], p["y"],
-                                             B, T, N, 1, -4.0, 2.8, 1, 0.37, e.stream())
-            return Built(ins, {"y": (B, N, T)}, aux, call)
-
-        def ref(a):
-            x = A.ref_conv_pre(a["wav"], a["hist"], a["pre_w"], a["pre_b"], 1 / 0.1122080159) if pre else a["x"]
-            return {"y": A.ref_spec_block(a["wav"], a["hist"], a["basis_t"], a["wt"], a["bias"], x, N, 1, -4.0, 2.8, 1, 0.37)}
-        return build, ref
-
-
-_spec("spec_block-n64-T132", False, 2, 132)
-_spec("spec_block-n64-T516", False, 1, 516)
-_spec("spec_block_conv_pre-n64-T132", True, 2, 132)
-
-
-@TA.row("dw_convtr-16x13-r4", 5e-6, {"x": "S", "hist": "S", "w": "S", "y": "S", "hist_out": "S"})
-def _():
-    B, C, T, r = 2, 16, 13, 4
-
-    def build(e):
-        ins = {"x": rnd(31, B, C, T), "hist": rnd(32, B, C, 1) * 0.5, "w": rnd(33, C, 2 * r)}
-
-        def call(p):
-            return e.lib.hilc_dw_convtr(p["x"], p["hist"], p["w"], p["y"], p["hist_out"], B, C, T, r, 0.7, 1, e.stream())
-        return Built(ins, {"y": (B, C, T * r), "hist_out": (B, C, 1)}, dict(ins), call)
-
-    def ref(a):
-        y, h = A.ref_dw_convtr(a["x"], a["hist"], a["w"], r, 0.7, True)
-        return {"y": y, "hist_out": h}
-    return build, ref
-
-
-@TA.row("tail-2x15x7-pad9", 0.0, {"x": "S", "hist": "S", "out": "S"})
-def _():
-    def build(e):
-        ins = {"x": rnd(41, 2, 15, 7), "hist": rnd(42, 2, 15, 10)}
-        return Built(ins, {"out": (2, 15, 9)}, dict(ins), lambda p: e.lib.hilc_tail(p["x"], p["hist"], p["out"], 30, 7, 9, 10, e.stream()))
-    return build, lambda a: {"out": torch.cat([a["hist"], a["x"]], dim=2)[:, :, -9:]}
-
-
-@TA.row("rvq_decode-3x128x3", 1e-6, {"indices": "S", "codebooks": "S", "q": "S"})
-def _():
-    B, T, Nq, K, C, n = 3, 3, 3, 1024, 128, 3
-
-    def build(e):
-        cb = TA._rvq_tables(Nq, K, C)[0]
-        idx = torch.from_numpy(np.random.RandomState(6).randint(0, K, size=(B, n, T))).to(torch.int64)
-        ins = {"indices": idx, "codebooks": cb}
-        return Built(ins, {"q": (B, C, T)}, dict(ins),
-                     lambda p: e.lib.hilc_rvq_decode(p["indices"], p["codebooks"], p["q"], B, C, T, K, Nq, n, 0, 0, e.stream()))
-
-    def ref(a):
-        q = sum(a["codebooks"][s][a["indices"][:, s]] for s in range(n))          # [B, T, C]
-        return {"q": q.transpose(1, 2)}
-    return build, ref
-
-
-@TA.row("conv_post-8x260-k5-hist", 2e-6, {"x": "F", "hist": "F", "w": "S", "bias": "S", "y": "S", "hist_out": "S"}, exact=("hist_out",))
-def _():
-    B, C, T, k = 2, 8, 260, 5
-
-    def build(e):
-        ins = {"x": rnd(19, B, C, T), "hist": rnd(18, B, C, 4) * 0.6, "w": rnd(13, C, k) / 20, "bias": rnd(14, 1) * 0.1}
-
-        def call(p):
-            return e.lib.hilc_conv_post(p["x"], p["hist"], p["w"], p["bias"], p["y"], p["hist_out"], B, C, T, k, 0.707, 1, 0.1122080159, 1,
-                                        e.stream())
-        return Built(ins, {"y": (B, 1, T), "hist_out": (B, C, 4)}, dict(ins), call)
-
-    def ref(a):
-        y, h = A.ref_conv_post(a["x"], a["hist"], a["w"], a["bias"], 0.707, True, 0.1122080159, True)
-        return {"y": y, "hist_out": h}
-    return build, ref
-
-
-@TA.row("l2norm-5x36x13", 1e-6, {"x": "S", "y": "S"})
-def _():
-    B, C, T = 5, 36, 13
-
-    def build(e):
-        ins = {"x": rnd(21, B, C, T)}
-        return Built(ins, {"y": (B, T, C)}, dict(ins), lambda p: e.lib.hilc_l2norm(p["x"], p["y"], B, C, T, 1e-12, 1.0, 1, e.stream()))
-    return build, lambda a: {"y": A.ref_l2norm(a["x"], 1e-12, 1.0, True)}
-
-
-def _rvq_mixed(name, encode):
-    """the mixed-bitrate forms: clip b uses its first n_per_clip[b] stages (int32 [B] on the device)"""
-    B, T, Nq, K, C, n = 3, 9, 3, 1024, 128, 3
-    n_b = [2, 3, 1]
-    cls = {"z": "S", "codebooks": "S", "codebooks_t": "F", "norms": "F", "n_per_clip": "S", "indices": "S", "q": "S", "frame_err": "S"} if encode else \
-        {"indices": "S", "codebooks": "S", "n_per_clip": "S", "q": "S"}
-
-    @TA.row(name, 1e-6, cls)
-    def _():
-        def build(e):
-            cb, cbt, nrm = TA._rvq_tables(Nq, K, C)
-            clip = torch.tensor(n_b, dtype=torch.int32)
-            if encode:
-                ins = {"z": rnd(7, B, C, T) * 0.4, "codebooks": cb, "codebooks_t": cbt, "norms": nrm, "n_per_clip": clip}
-
-                def call(p):
-                    return e.lib.hilc_rvq_encode_mixed(p["z"], p["codebooks"], p["codebooks_t"], p["norms"], p["n_per_clip"], p["indices"], p["q"],
-                                                       p["frame_err"], B, C, T, K, Nq, n, 0, 0, 0, e.stream())
-                return Built(ins, {"indices": ((B, n, T), torch.int64), "q": (B, C, T), "frame_err": (B * T,)}, dict(ins), call)
-            idx = torch.from_numpy(np.random.RandomState(4).randint(0, K, size=(B, n, T))).to(torch.int64)
-            for b, nb in enumerate(n_b):
-                idx[b, nb:] = -1                                  # what hilc_rvq_encode_mixed writes there: ignored
-            ins = {"indices": idx, "codebooks": cb, "n_per_clip": clip}
-            return Built(ins, {"q": (B, C, T)}, dict(ins),
-                         lambda p: e.lib.hilc_rvq_decode_mixed(p["indices"], p["codebooks"], p["n_per_clip"], p["q"], B, C, T, K, Nq, n, 0, 0, e.stream()))
-
-        def ref(a):
-            if encode:
-                return {}                                         # like the RVQ encode rows of the alignment sweep: equality with the aligned call
-            q = torch.stack([sum(a["codebooks"][s][a["indices"][b, s]] for s in range(n_b[b])) for b in range(B)])       # [B, T, C]
-            return {"q": q.transpose(1, 2)}
-        return build, ref
-
-
-def _balanced(name, B, C, T, streaming):
-    """hilc_resblock / hilc_resblock_stream with the caller-owned tile scheduler: `sched`, two ints that are zero at the launch and zero
-    again at its end — an input as far as a row is concerned (the sweep asserts it is unchanged), and one the kernel writes between"""
-    cls = {"x": "R", "y": "R", "sched": "S"}
-    cls.update(TA.block_cls(1, streaming))
-
-    @TA.row(name, 2e-5, cls)
-    def _():
-        raw = TA.raw_blocks(C, 1)
-
-        def build(e):
-            ins, outs, aux = {"x": rnd(C + T, B, C, T), "sched": torch.zeros(2, dtype=torch.int32)}, {"y": (B, C, T)}, {}
-            aux["x"] = ins["x"]
-            TA.block_operands(e, raw, B, C, streaming, e.ops.resblock_pack, ins, outs, aux)
-
-            def call(p):
-                w = [p[f"b0.{nm}"] for nm in TA.BLK]
-                caches = [p.get(f"b0.{nm}") for nm in ("hist1", "hist2", "hist1_out", "hist2_out")]
-                return e.lib.hilc_resblock_balanced(p["x"], *w, *caches, p["y"], p["sched"], int(streaming), B, C, T, float(raw[0][6]),
-                                                    float(raw[0][7]), e.stream())
-            return Built(ins, outs, aux, call)
-
-        def ref(a):
-            out = {}
-            out["y"] = TA.ref_blocks(a, a["x"], streaming, out)
-            return out
-        return build, ref
-
-
-_balanced("resblock_balanced-64x132x2-offline", 2, 64, 132, False)
-_balanced("resblock_balanced-64x160x5-stream", 5, 64, 160, True)
-_rvq_mixed("rvq_encode_mixed-3x128x9", True)
-_rvq_mixed("rvq_decode_mixed-3x128x9", False)
-
-# the floor of each (the largest difference between its reference in float32 and in float64 on the CPU, as measured; asserted again
-# where the tests run, like the alignment rows')
-EDGE_FLOORS = {
-    "pw_conv-2x17x36x132": 2.68e-07,
-    "pw_conv-1x16x132x8": 2.82e-07,
-    "dw_conv-16x38-k8s4-hist": 1.72e-07,
-    "up_conv-3x32x36x22-r2": 1.99e-07,
-    "up_conv_stream-3x32x36x11-r4": 1.92e-07,
-    "up_conv_expanded-3x48x24x12-r5": 3.74e-07,
-    "dws_conv_stream-k5-9x32x36x24": 5.17e-07,
-    "resblock-64x132x2": 4.26e-07,
-    "resblock_stream-64x160x5": 8.46e-07,
-    "resblock_chain-64x132x2-offline": 5.86e-07,
-    "resblock_chain-64x160x5-stream": 8.86e-07,
-    "encoder_stage-128x132-r4-offline": 8.55e-07,
-    "encoder_stage-128x160-r4-stream": 1.10e-06,
-    "decoder_stage-96-r2-Tin66-offline": 7.41e-07,
-    "decoder_stage-96-r2-Tin80-stream": 8.20e-07,
-    "conv_post-8x260-k5-hist": 7.84e-08,
-    "l2norm-5x36x13": 4.45e-08,
-    "resblock_balanced-64x132x2-offline": 4.26e-07,          # the operands and the reference of resblock-64x132x2 / resblock_stream-64x160x5
-    "resblock_balanced-64x160x5-stream": 8.46e-07,
-    "rvq_encode_mixed-3x128x9": 0.0,         # integers and equality, like the RVQ encode rows of the alignment sweep
-    "rvq_decode_mixed-3x128x9": 8.94e-08,
-    "encoder_stage0-T132-offline": 1.07e-06,
-    "encoder_stage0-T160-stream": 1.41e-06,
-    "decoder_stage_post-96-r2-Tin66-offline": 9.97e-08,
-    "decoder_stage_post-96-r2-Tin80-stream": 5.78e-07,
-    "stft_logmag-n16-T132-hist": 1.49e-07,
-    "stft_logmag-n16-T516-seg": 1.31e-07,
-    "rvq_encode-mfma-8x128x1025": 0.0,
-    "spec_block-n64-T132": 2.26e-06,
-    "spec_block-n64-T516": 4.07e-06,
-    "spec_block_conv_pre-n64-T132": 2.28e-06,
-    "dw_convtr-16x13-r4": 2.92e-07,
-    "tail-2x15x7-pad9": 0.0,
-    "rvq_decode-3x128x3": 8.94e-08,
-}
-EDGE = list(EDGE_FLOORS)
-assert set(EDGE) <= set(ROWS)
-TA.FLOORS.update(EDGE_FLOORS)
-ALL_ROWS = list(ROWS)
-
-
-def entry_of(name):
-    """the entry point a row calls: the row's name up to its first `-`"""
-    return name.split("-")[0]
-
 
 # what the fused rows must be: the shapes the library takes in one launch (else the row would test a fall-back)
 FUSED = {"resblock-64x132x2": ("hilc_resblock_supported", (64, 132)), "resblock_stream-64x160x5": ("hilc_resblock_stream_supported", (64, 160)),
@@ -340,7 +40,7 @@ FUSED = {"resblock-64x132x2": ("hilc_resblock_supported", (64, 132)), "resblock_
 
 
 def test_edge_rows(env):
-    assert set(ROWS) == set(TA.FLOORS) and set(EDGE) <= set(ROWS) and set(FUSED) <= set(EDGE)          # every row has its floor
+    assert set(ROWS) == set(FLOORS) and set(EDGE) <= set(ROWS) and set(FUSED) <= set(EDGE)          # every row has its floor
     for name, (query, args) in FUSED.items():
         assert getattr(env.lib, query)(*args) == 1, f"{name}: {query}{args} != 1"
     for name in EDGE:
@@ -534,14 +234,11 @@ def check_case(e, label, case, base=None):
 
 
 # ---- the per-slot float kernels ----------------------------------------------------------------------------------------
-MISC_CASES = tuple(TA.MISC)
-
-
-@pytest.mark.parametrize("name", MISC_CASES)
+@pytest.mark.parametrize("name", tuple(slot_cases.MISC))
 def test_per_slot_float_kernels(env, name):
-    base, _ = TA._misc_run(env, name)                      # the unguarded baseline the alignment sweep pins to the host model
-    case = TA._MISC[name]
-    assert set(case[0]) == set(TA.MISC[name])
+    base, _ = slot_cases.misc_run(env, name)                      # the unguarded baseline the alignment sweep pins to the host model
+    case = slot_cases.CASES[name]
+    assert set(case[0]) == set(slot_cases.MISC[name])
     check_case(env, name, case, base)
 
 
@@ -665,12 +362,9 @@ def test_resample_poly_edges(env, B, T):
 
 # ---- the kernels that move variable-length byte rows: B = 65 (one slot more than a workgroup of 64), the last slot carries the
 # longest row; caller-owned outputs wherever the wrapper takes them (what a wrapper allocates itself cannot be guarded) --------------------
-BYTE_ENTRY_POINTS = ("pack_codes_10bit", "pack_codes_10bit_fec", "rvq_decode_packed", "packet_header", "jitter_step", "srtp_protect",
-                     "srtp_unprotect", "srtp_protect_routes")
-# the same kind of case for entry points that were on the ledger's LATER list
-MORE_ENTRY_POINTS = ("fec_select", "conceal_prepare")
+# (tests/redzone.py names them for the ledger: `BYTE_ENTRY_POINTS`, `MORE_ENTRY_POINTS`)
 NB = 65
-# byte counts of the SRTP rows (tests/test_gpu_srtp.py, `LENGTHS`): nothing, no header, a bare header, one below / at / above the AES
+# byte counts of the SRTP rows (tests/hops.py, `SRTP_LENGTHS`): nothing, no header, a bare header, one below / at / above the AES
 # block edges (payloads of 16, 32, 48 bytes: 19, 35, 51) and the SHA-1 padding edges (51, 52, 59, 60), the whole row
 SRTP_LENGTHS = (0, 2, 3, 13, 18, 19, 20, 34, 35, 36, 50, 51, 52, 53, 58, 59, 60, 61, 80)
 
@@ -718,7 +412,6 @@ def test_pack_codes_10bit(env, n, T):
 
 @pytest.mark.parametrize("n,m,T", [(6, 2, 2), (8, 3, 1)], ids=["20-bytes", "14-bytes"])
 def test_pack_codes_10bit_fec(env, n, m, T):
-    from tests.test_gpu_fec import pack_model
     g = torch.Generator().manual_seed(n + m)
     W = 1 + m * T
     idx = torch.randint(-2, 1100, (n, NB, T), generator=g)
@@ -740,10 +433,9 @@ def test_pack_codes_10bit_fec(env, n, m, T):
 
 @pytest.mark.parametrize("n,m,T", [(6, 2, 2), (8, 3, 1)], ids=["20-to-15-bytes", "14-to-10-bytes"])
 def test_fec_select(env, n, m, T):
-    """the FEC receiver's compaction against tests/test_gpu_fec.py's host model: wide rows with every bit set at random, the redundant
+    """the FEC receiver's compaction against the host model of tests/hops.py: wide rows with every bit set at random, the redundant
     section taken in a third of the slots and in the last one"""
     from hilcodec_amd import wire
-    from tests.test_gpu_fec import select_model
     g = torch.Generator().manual_seed(10 * n + m)
     wide = torch.randint(0, 256, (NB, wire.fec_packet_bytes(n, m, T)), generator=g, dtype=torch.uint8)
     fec = torch.tensor([int(b % 3 == 0) * (1 + b % 2) for b in range(NB - 1)] + [1], dtype=torch.int32)
@@ -756,9 +448,8 @@ def test_fec_select(env, n, m, T):
 
 @pytest.mark.parametrize("n,T", [(8, 2), (7, 3)], ids=["20-bytes", "27-bytes"])
 def test_conceal_prepare(env, n, T):
-    """the receiver's concealment step against tests/test_gpu_conceal.py's host model of its table: received, lost (with and without
+    """the receiver's concealment step against the host model of its table in tests/hops.py: received, lost (with and without
     something to repeat, at every run length) and held slots, starts; the last slot is lost and gets the longest substitute packet"""
-    from tests.test_gpu_conceal import F, prepare_model
     g = torch.Generator().manual_seed(n + T)
     idx, n_list = _ragged_codes(n, T, 21)
     packets, _ = _host_packets(idx, n_list)

@@ -10,9 +10,8 @@ from hilcodec_amd import dtx, jitter, report, synth, wire
 from hilcodec_amd.jitter import AdaptConfig, JitterConfig, JitterModel
 from hilcodec_amd.report import FecAdaptConfig, FecAdaptModel, ReportConfig, ReportModel, report_word
 from hilcodec_amd.vbr import VbrConfig
-from tests.hops import caches_equal
-from tests.test_gpu_jitter_adapt import Network
-from tests.test_report_cpu import LOOP, LOOP_ADAPT, LOOP_REPORT, check_closed_loop, closed_loop
+from tests.hops import Network, caches_equal
+from tests.report_loop import LOOP, LOOP_ADAPT, LOOP_REPORT, check_closed_loop, closed_loop
 
 pytestmark = pytest.mark.gpu
 

@@ -10,9 +10,8 @@ from hilcodec_amd import dtx, jitter, rtx, synth, wire
 from hilcodec_amd.jitter import AdaptConfig, JitterConfig, JitterModel
 from hilcodec_amd.rtx import NackConfig, NackModel, RtxConfig, RtxModel, nack_words
 from hilcodec_amd.vbr import VbrConfig
-from tests.hops import arrival_arrays, arrival_records, caches_equal
+from tests.hops import Network, arrival_arrays, arrival_records, caches_equal
 from tests.rtx_loop import HOPS, LOOP_JITTER, LOOP_NACK, LOOP_RTX, Channel, bursts_of_two, singles_and_pairs
-from tests.test_gpu_jitter_adapt import Network
 
 pytestmark = pytest.mark.gpu
 

@@ -8,15 +8,13 @@ import torch
 
 from hilcodec_amd import forward, srtp, wire
 from tests.alignment import skew
+from tests.hops import SRTP_LENGTHS as LENGTHS
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 B_KERNEL = 67                                                # two workgroups of 64, the second a partial wave
 TB = 80
-# the three AES block edges (payloads of 16, 32 and 48 bytes: 19, 35, 51) and, for an HMAC message of nbytes + 4 bytes behind the pad
-# block, its lengths 55, 56, 63 and 64 mod 64 (51, 52, 59, 60), one either side, nothing, no header, a bare header, the whole row
-LENGTHS = (0, 2, 3, 13, 18, 19, 20, 35, 51, 52, 59, 60, 61, 80)
 UNKEYED = (5, 64)
 
 

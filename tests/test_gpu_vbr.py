@@ -15,9 +15,6 @@ Two notes on the inputs.
     decisions, 0.95^s with four, and a one-frame hop with seven.  rho is the reference's own median of D[:, n / 2] / D[:, 0] at
     hop 0, and every sender test asserts on the reference that n_eff takes at least 3 values among the slots that are neither
     held nor under a lower ceiling."""
-import math
-
-import numpy as np
 import pytest
 import torch
 
@@ -25,6 +22,7 @@ from hilcodec_amd import dtx, synth, vbr, wire
 from hilcodec_amd.jitter import JitterConfig
 from hilcodec_amd.resample import design, hop_samples, reference
 from hilcodec_amd.vbr import VbrConfig, VbrModel
+from tests.hops import target_from_reference, vbr_speech_model
 
 pytestmark = pytest.mark.gpu
 
@@ -165,18 +163,7 @@ def test_vbr_select_many_stages(n):
 @pytest.fixture(scope="module")
 def speech():
     """the streaming model with falling per-stage codebooks, scaled to its latents (module docstring)"""
-    model = synth.streaming_model()
-    x = synth.synth_clips(8, HOP, seed=1).to(DEV)
-    with torch.no_grad():
-        z, _ = model.encoder(x, *[c.to(DEV) for c in model.initialize_cache(x)[0]])
-    g = 0.05 * float(z.float().norm(dim=-1).median())
-    gen = torch.Generator().manual_seed(11)
-    with torch.no_grad():
-        for s, (ql, dl) in enumerate(zip(model.quantizer.layers, model.dequantizer.layers)):
-            e = torch.randn(K, C, generator=gen) * g * 0.95 ** s
-            ql.embed.copy_(e)
-            dl.embed.copy_(e)
-    return model
+    return vbr_speech_model()
 
 
 class Eager:
@@ -272,17 +259,6 @@ def signal(B, S_in, hops, seed, gaps=False):
     for b in range(0, B, 2):                                # every other stream falls silent for a few hops
         gain[b, 2 + b % 3:5 + b % 3] = 3e-5
     return (x.view(B, 1, hops, S_in) * gain.view(B, 1, hops, 1)).view(B, 1, hops * S_in)
-
-
-def target_from_reference(model, B, frames, n, x0):
-    """the median over the slots of D[:, n / 2] / D[:, 0] at hop 0, as target_db"""
-    with torch.no_grad():
-        z, _ = model.encoder(x0, *[c.to(DEV) for c in model.initialize_cache(x0)[0]])
-        idx = model.quantizer(z, n)
-    D = vbr.distortions(z.cpu(), idx.cpu(), model.quantizer._tables(DEV).codebooks.cpu())
-    rho = float(np.median(D[:, n // 2] / D[:, 0]))
-    assert 0.0 < rho < 1.0
-    return -10.0 * math.log10(rho)
 
 
 def run_sender(model, B=8, frames=1, n=8, hops=7, seed=21, sessions=False, plan=False, input_rate=24000, fec=0, header=False,

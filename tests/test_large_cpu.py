@@ -1,4 +1,4 @@
-"""The large-tensor tests' own machinery, on the CPU (tests/large.py; the GPU side is tests/test_gpu_large.py).
+"""The large-tensor tests' own machinery, on the CPU (tests/large.py, tests/large_families.py; the GPU side is tests/test_gpu_large.py).
 
   * every row's builder at a small size with its float32 reference as the "kernel": the whole-tensor compare passes, and fails for
     each of three injected faults — an offset that wraps modulo 2^k elements, a clip base taken from another clip, a row read from
@@ -14,8 +14,8 @@ import torch
 
 from hilcodec_amd import synth
 from tests import large as L
-from tests import test_gpu_large as G
-from tests.test_gpu_alignment import ROWS, cast
+from tests import large_families as G
+from tests.entry_rows import ROWS, cast
 
 
 class _Lib:
@@ -282,7 +282,7 @@ def test_model_receptive_field_on_four_periods():
 
 
 def test_specblock_waveform_stays_clear_of_the_log_clamp():
-    """tests/test_gpu_large.py: SPEC_WAV_SEED.  log(max(|STFT|, 1e-5)) magnifies the rounding of a nearly cancelled bin beyond the rows'
+    """tests/large_families.py: SPEC_WAV_SEED.  log(max(|STFT|, 1e-5)) magnifies the rounding of a nearly cancelled bin beyond the rows'
     tolerance; the seed's three patterns keep every magnitude a decade above the clamp (measured 9.8e-5), whatever `synth` becomes."""
     from hilcodec_amd import fold
     from tests import alignment as A

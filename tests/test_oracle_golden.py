@@ -6,6 +6,7 @@ import torch
 
 from hilcodec_amd import synth
 from oracle import hilcodec_oracle as O
+from tests.models import realistic_state_dict
 
 torch.set_num_threads(max(1, min(8, torch.get_num_threads())))
 
@@ -194,14 +195,6 @@ def test_rvq_train_kat(golden):
         assert torch.equal(st[f"layers.{i}.embed"][::16], T(g["embed_rows"][i]))
         assert torch.equal(st[f"layers.{i}.ema_embed"][::16], T(g["ema_embed_rows"][i]))
         assert abs(float(st[f"layers.{i}.embed"].double().sum()) - float(g["embed_sum"][i])) < 1e-9
-
-
-def realistic_state_dict(g):
-    """seeded synthetic conv weights + the reference's SHIPPED trained codebooks (tests/golden/realistic.npz)"""
-    sd = synth.synth_state_dict("hil_speech", seed=int(g["weight_seed"]))
-    for i in range(8):
-        sd[f"quantizer.layers.{i}.embed"] = T(g["codebooks"][i]).clone()
-    return sd
 
 
 def test_realistic_and_adversarial_inputs(golden):

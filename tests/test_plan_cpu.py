@@ -11,7 +11,6 @@ reaches.
 
   python tests/test_plan_cpu.py --dump DIR      one JSON file of full rows per scenario (diff two trees when a hash differs)
   python tests/test_plan_cpu.py --write         rewrite the fixture from THIS tree (only for a change that is meant to move the plan)"""
-import dataclasses
 import functools
 import hashlib
 import importlib.util
@@ -25,11 +24,9 @@ if __name__ == "__main__":
 
 import pytest
 import torch
-from torch.utils._python_dispatch import TorchDispatchMode
-from torch.utils._pytree import tree_leaves
 
-import hilcodec_amd
-from hilcodec_amd import engine, synth
+from hilcodec_amd import engine
+from tests.plan import Recorder, launches, specs
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "plan_trace.json")
 
@@ -68,64 +65,6 @@ def _key(name, block, off=(), extra={}):
     return name + (" {" + ", ".join(what) + (" off" if off else "") + "}" if what else "") + (" [caches_out]" if block else "")
 
 
-@functools.lru_cache(maxsize=None)
-def _specs(model_name, streaming):
-    mk = dict(synth.model_kwargs(model_name))
-    sd = synth.synth_state_dict(model_name, seed=7)
-    if streaming:
-        m = synth.streaming_model(model_name, state_dict=sd)
-    else:
-        m = hilcodec_amd.HILCodec(24000, 1, **mk).eval()
-        m.load_state_dict(sd, strict=False)
-    return tuple(engine.finalize_spec(engine.spec_to(half.build_spec("cpu"), "meta"), streaming=streaming) for half in (m.encoder, m.decoder))
-
-
-class _Recorder(TorchDispatchMode):
-    """rows = [op name, [arguments], {keyword arguments}] of every op that reaches the dispatcher, ATen ones included; a tensor is
-    written as its name, and the outputs of op k are named `#k.j`"""
-
-    def __init__(self):
-        super().__init__()
-        self.names = {}         # id(tensor) -> name
-        self.keep = []          # ... and the tensors themselves: an id must not be handed out twice
-        self.rows = []
-
-    def name(self, t, name):
-        if id(t) not in self.names:
-            self.names[id(t)] = name
-            self.keep.append(t)
-
-    def name_tree(self, obj, path):
-        if isinstance(obj, torch.Tensor):
-            self.name(obj, path)
-        elif isinstance(obj, (list, tuple)):
-            for i, v in enumerate(obj):
-                self.name_tree(v, f"{path}[{i}]")
-        elif dataclasses.is_dataclass(obj):
-            for f in dataclasses.fields(obj):
-                self.name_tree(getattr(obj, f.name), f"{path}.{f.name}")
-
-    def _enc(self, a, where):
-        if isinstance(a, torch.Tensor):
-            assert id(a) in self.names, f"{where}: a tensor {tuple(a.shape)} that is neither a spec field, an input, a cache nor an op's output"
-            return self.names[id(a)]
-        if isinstance(a, (list, tuple)):
-            return [self._enc(v, where) for v in a]
-        return repr(a)
-
-    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
-        kwargs = kwargs or {}
-        k = len(self.rows)
-        op = func._schema.name.replace("::", ".") + ("." + func._overloadname if func._overloadname else "")
-        where = f"op {k} {op}"
-        self.rows.append([op, [self._enc(a, where) for a in args], {n: self._enc(v, where) for n, v in sorted(kwargs.items())}])
-        out = func(*args, **kwargs)
-        for j, t in enumerate(tree_leaves(out)):
-            if isinstance(t, torch.Tensor):
-                self.name(t, f"#{k}.{j}")
-        return out
-
-
 def trace(name, block, off=(), extra={}):
     """the rows of one scenario: run_encoder, then run_decoder on what it returned; `off` = the module switches that are False meanwhile"""
     saved = {sw: getattr(engine, sw) for sw in off}
@@ -141,9 +80,9 @@ def trace(name, block, off=(), extra={}):
 def _trace(name, block, extra):
     model_name, mode, B, T, opts = SCENARIOS[name]
     streaming = mode == "streaming"
-    es, ds = _specs(model_name, streaming)
+    es, ds = specs(model_name, streaming)
     opts = engine.ExecOptions(**dict(opts, **extra))
-    rec = _Recorder()
+    rec = Recorder()
     rec.name_tree(es, "es")
     rec.name_tree(ds, "ds")
     wav = torch.empty(B, 1, T, device="meta")
@@ -171,16 +110,12 @@ def _trace(name, block, extra):
     return rec.rows
 
 
-def _launches(rows):
-    return [r[0][len("hilcodec."):] for r in rows if r[0].startswith("hilcodec.")]
-
-
 def _digest(rows):
     return hashlib.sha256(json.dumps(rows, sort_keys=True, separators=(",", ":")).encode()).hexdigest()
 
 
 def summary(rows):
-    return {"ops": _launches(rows), "sha256": _digest(rows)}
+    return {"ops": launches(rows), "sha256": _digest(rows)}
 
 
 @functools.lru_cache(maxsize=None)
@@ -197,7 +132,7 @@ def test_fixture_lists_every_case():
 def test_plan_matches_the_recorded_trace(name, block, off, extra):
     rows = trace(name, block, off, extra)
     want = _golden()[_key(name, block, off, extra)]
-    assert _launches(rows) == want["ops"]
+    assert launches(rows) == want["ops"]
     assert _digest(rows) == want["sha256"], "same ops, another argument: `python tests/test_plan_cpu.py --dump DIR` in both trees and diff"
 
 
@@ -206,7 +141,7 @@ def test_plan_matches_the_recorded_trace(name, block, off, extra):
     ("streaming hop 320, 1024 streams", False, 19), ("streaming hop 320, 1024 streams", True, 19)])
 def test_launch_counts_of_the_default_plans(name, block, count):
     """a whole stage per launch: 20 launches for an offline encoder + decoder pass, 19 for a 320-sample hop"""
-    assert len(_launches(trace(name, block))) == count
+    assert len(launches(trace(name, block))) == count
 
 
 if __name__ == "__main__":

@@ -11,7 +11,9 @@ import torch
 
 from tests import redzone as R
 from tests.alignment import skew_bytes
+from tests.entry_rows import ALL_ROWS, entry_of
 from tests.hops import parse_header
+from tests.slot_cases import MISC
 
 DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8)
 SIZES = (1, 17, 1100)                    # one element, a ragged few, more than 4096 bytes in every type but uint8 ...
@@ -194,11 +196,10 @@ def launches_no_kernel(name):
 
 
 def test_ledger():
-    from tests import test_gpu_redzone as G
     protos, _ = parse_header()
     declared = {n[len("hilc_"):] for n in protos}
     assert len(declared) >= 80
-    classes = {"row": {G.entry_of(n) for n in G.ALL_ROWS}, "misc": set(G.MISC_CASES), "bytes": set(G.BYTE_ENTRY_POINTS) | set(G.MORE_ENTRY_POINTS),
+    classes = {"row": {entry_of(n) for n in ALL_ROWS}, "misc": set(MISC), "bytes": set(R.BYTE_ENTRY_POINTS) | set(R.MORE_ENTRY_POINTS),
                "no kernel": {n for n in declared if launches_no_kernel(n)}, "later": set(LATER)}
     for cls, names in classes.items():
         assert names <= declared, f"class `{cls}` names what the header does not declare: {sorted(names - declared)}"
@@ -206,7 +207,7 @@ def test_ledger():
     assert not [n for n, c in where.items() if not c], f"entry points in no class (guard them or say why not): {sorted(n for n, c in where.items() if not c)}"
     assert not [n for n, c in where.items() if len(c) > 1], {n: c for n, c in where.items() if len(c) > 1}
     assert set(LATER) <= LATER_ALLOWED and all(reason and "\n" not in reason for reason in LATER.values())
-    assert set(G.MISC_CASES) == {"resample_poly", "mix_levels", "mix_rooms", "conceal_gain", "cng_synth", "audio_level", "vbr_select",
+    assert set(MISC) == {"resample_poly", "mix_levels", "mix_rooms", "conceal_gain", "cng_synth", "audio_level", "vbr_select",
                                  "state_slots_apply", "state_slots_gather", "state_slots_hold"}
-    assert set(G.BYTE_ENTRY_POINTS) == {"pack_codes_10bit", "pack_codes_10bit_fec", "rvq_decode_packed", "packet_header", "jitter_step",
+    assert set(R.BYTE_ENTRY_POINTS) == {"pack_codes_10bit", "pack_codes_10bit_fec", "rvq_decode_packed", "packet_header", "jitter_step",
                                         "srtp_protect", "srtp_unprotect", "srtp_protect_routes"}

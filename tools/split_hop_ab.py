@@ -81,7 +81,7 @@ if not args.no_sweep:
         del legs
 
 if not args.no_ref:
-    from tests.test_oracle_golden import realistic_state_dict
+    from tests.models import realistic_state_dict
     g = dict(np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "realistic.npz")))
     real = synth.streaming_model(state_dict=realistic_state_dict(g))
     hops = 5 * SR // HOP                                     # 375 hops: the first 5 s
